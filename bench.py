@@ -8,16 +8,20 @@ Update over T=20 frames x S streams (bd-nnet-train-lstm-streams.cc:209-228), on 
   N = 1 : BASELINE.json configs[1] (NumStream = 4 on one GPU).
   N > 1 : BASELINE.json configs[2]'s partitioning: 8 streams per GPU (64 streams on 8 GPUs), independent utterance
           streams sharded over ranks (weak scaling) with ONE all-reduce of the 8.73 MB gradient blob per minibatch (RCCL).
-Timing: after W warm-up steps, exactly K steps are timed between barrier + synchronize fences (`first_k_steps`); because
-K = 20 steps are only ~5 ms of GPU time, the same K-step block is then repeated back to back until at least
---min-seconds (default 1 s) of timed region have accumulated, and `value` / `ms_per_step` are taken over that whole
-region (`timed`).  Max over ranks.  A second run with ragged utterance lengths (900-1100 frames, new utterances enter
-at minibatch boundaries, padded frames masked) exercises the mask / Reset path (`ragged`).
+Timing: after W warm-up steps, exactly K = --steps steps are timed between barrier + synchronize fences, and `value` /
+`ms_per_step` are taken over those K steps (`timed`).  Max over ranks.  A second run with ragged utterance lengths
+(900-1100 frames, new utterances enter at minibatch boundaries, padded frames masked) exercises the mask / Reset path
+(`ragged`).
 
 `--config` selects the BASELINE.json configuration: c2 (default) = configs[1], the headline; c3 = configs[2]'s per-GPU shard
 (the same layer at 8 streams per GPU, = --streams-per-gpu 8); c1 / c4 / c5 = configs[0] / [3] / [4] (bench_configs.py).
 
 Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR: after the timed steps, what the last timed step gave its caller -- `out` [T*S, R] of the Propagate,
+`in_diff` [T*S, I] of the Backpropagate and the parameters after its Update (GetParams order) -- is written as
+DIR/<name>.npy (float32, rank 0).  Inputs and initial parameters are seeded, so the same arguments give the same inputs
+on every run and two builds can be compared output for output.
 """
 import argparse
 import glob
@@ -273,6 +277,24 @@ def kaldi_adapter_leg(S, steps=400, warmup=50):
         return {"error": str(ex)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """arrays: name -> float32 array, written as dirname/<name>.npy.  Above DUMP_LIMIT_BYTES in all, every array is cut to
+    the same fixed, seeded sample fraction of its elements (flattened, in index order)."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)             # (room for the .npy headers)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float32)
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def folded_chain(eng):
     """Did the engine's last minibatch run on a chain that needs the fold product W_rm = W_gifo_r W_r_m?"""
     return eng.profile_query("persist_launches")[1] > 0 or eng.S <= 8
@@ -285,7 +307,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--streams-per-gpu", type=int, default=0,
                     help="default: 4 on one GPU (BASELINE.json configs[1]), 8 per GPU on N > 1 (configs[2]: 64 streams on 8 GPUs)")
-    ap.add_argument("--min-seconds", type=float, default=3.0, help="minimum length of the timed region (whole K-step blocks)")
+    ap.add_argument("--min-seconds", type=float, default=3.0,
+                    help="--config c1 / c4 / c5 and the ragged leg: minimum length of their timed regions (the headline region is "
+                         "exactly --steps steps)")
     ap.add_argument("--config", choices=("c1", "c2", "c3", "c4", "c5"), default="c2",
                     help="BASELINE.json configuration: c2 = configs[1] (headline, default); c3 = configs[2]'s per-GPU shard (8 streams "
                          "per GPU); c1 / c4 / c5 = configs[0] / [3] / [4] on one GPU (bench_configs.py)")
@@ -306,7 +330,13 @@ def main():
     ap.add_argument("--force-collective", action="store_true",
                     help="one rank, but through the N > 1 code path: gradient -> klstm_allreduce_grads on a 1-rank RCCL communicator -> "
                          "momentum -> two-launch Update (what every rank of a multi-GPU run executes, minus the wire)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write out / in_diff / parameters of the last timed step as DIR/<name>.npy (float32), for output-for-output "
+                         "comparison of two builds")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry_launch or args.config in ("c1", "c4", "c5")):
+        sys.exit("bench.py: --dump-outputs covers the headline line (--config c2 / c3), not %s"
+                 % ("--dry-launch" if args.dry_launch else "--config " + args.config))
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` started like the N = 1 line: become the launcher -- one rank per GPU under torch.distributed.run
@@ -523,7 +553,7 @@ def main():
             launch = "graph" if tm[0] <= tm[1] else "eager"
             ab = {"graph_ms_per_step": tm[0] / 16 * 1e3, "eager_ms_per_step": tm[1] / 16 * 1e3}
         eng.set_option("graph", 2 if launch == "graph" else 0)
-        # ---- warm-up, then exactly K steps, then whole K-step blocks until --min-seconds of timed region
+        # ---- warm-up, then exactly K steps
         K = args.steps
 
         region_trouble = []
@@ -541,15 +571,8 @@ def main():
         for i in range(args.warmup):
             run_step(i)
 
-        def timed_region(fn):
-            dt_first = timed_block(fn, args.warmup, K)
-            blocks = max(0, int(np.ceil((args.min_seconds - dt_first) / max(dt_first, 1e-9))))
-            dt_total, nsteps_total = dt_first, K
-            if blocks:
-                dt_total += timed_block(fn, args.warmup + K, blocks * K)
-                nsteps_total += blocks * K
-            return dt_first, dt_total, nsteps_total
-        dt_first, dt_total, nsteps_total = timed_region(run_step)
+        nsteps_total = K
+        dt_total = timed_block(run_step, args.warmup, K)
         if dp.oneshot is not None and dp.use_oneshot:
             # the one-shot exchange must have come through the whole timed region clean on EVERY rank; otherwise the region is void
             # (a rank that timed out reduced nothing) and is measured again on RCCL
@@ -570,7 +593,14 @@ def main():
                 allreduce_ab["chosen"] = "rccl (the one-shot exchange failed inside the timed region)"
                 for i in range(args.warmup):
                     step(i)
-                dt_first, dt_total, nsteps_total = timed_region(step)
+                dt_total = timed_block(step, args.warmup, K)
+
+        # ---- what the last timed step computed, before the legs below reuse out / in_diff and update the parameters
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            torch.cuda.synchronize()
+            outputs = {"out": out.cpu().numpy(), "in_diff": in_diff.cpu().numpy(), "params": eng.get_params()}
+            dumped = {"dir": args.dump_outputs, "files": [n + ".npy" for n in dump_outputs(args.dump_outputs, outputs)]}
 
         # ---- ragged utterance lengths (900..1100): mask / Reset on the timed path
         ragged = None
@@ -584,7 +614,7 @@ def main():
                 dp.train_step(rf[c], out, rod[c], in_diff, MOMENTUM, LR, reset_flags=fl if fl.any() else None)
             for i in range(8):
                 rstep(i)
-            reps = max(1, int(np.ceil(min(args.min_seconds, 0.5) / max(dt_first / K * nrag, 1e-9))))
+            reps = max(1, int(np.ceil(min(args.min_seconds, 0.5) / max(dt_total / K * nrag, 1e-9))))
             dtr = timed_block(rstep, 0, reps * nrag)
             ragged = {"value": reps * sum(rvalid) * world / dtr, "unit": "valid frames/s", "ms_per_step": dtr / (reps * nrag) * 1e3,
                       "minibatches": reps * nrag, "valid_frame_fraction": sum(rvalid) / (nrag * T_BPTT * S),
@@ -756,7 +786,7 @@ def main():
         chain_us = sum(v["us_per_step"] for n, v in kern.items() if n in step_kernels)
         res = {
             "metric": "frames/sec fwd+BPTT, 40in/800cell/512proj LSTM at 1/2/4/8 MI355X",
-            # `steps` = the steps of the timed region (the K asked for, then whole K-blocks until --min-seconds): steps x ms_per_step = timed_region_s
+            # `steps` = the steps of the timed region (= --steps): steps x ms_per_step = timed_region_s
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": nsteps_total, "steps_requested": args.steps, "warmup": args.warmup,
             "timed_region_s": dt_total,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
@@ -780,8 +810,8 @@ def main():
                        "parallelism": "dp%d over streams, 1 all-reduce/minibatch" % world if world > 1 else "single GPU",
                        "collective": dp.collective_in_use(), "ranks_seen": dp.ranks_seen},
             "timed": {"steps": nsteps_total, "seconds": dt_total},
-            "first_k_steps": {"steps": K, "seconds": dt_first, "ms_per_step": dt_first / K * 1e3,
-                              "value": K * frames_per_step / dt_first},
+            "first_k_steps": {"steps": K, "seconds": dt_total, "ms_per_step": dt_total / K * 1e3,      # (= timed: the region is the K steps)
+                              "value": K * frames_per_step / dt_total},
             "roofline": roof,
             "whole_path_tflops": value * FLOPS_PER_FRAME / 1e12 / world,
             "chain_us_per_step": chain_us, "non_chain_us_per_step": sum(v["us_per_step"] for v in kern.values()) - chain_us,
@@ -808,6 +838,8 @@ def main():
         if allreduce_ab:
             res["allreduce_ab"] = allreduce_ab
         res["persist_events"] = persist_events
+        if dumped:
+            res["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(S, args.cpu_seconds)
         line = json.dumps(res)

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -120,3 +122,32 @@ def test_roofline_accounting_is_surveys_8d():
     assert b.ACT_BYTES_PER_FRAME == 79_072
     assert b.WEIGHT_BYTES_PER_MINIBATCH == 5 * bc.n_params(40, 800, 512) * 4 == 43_632_000
     assert b.ACT_BYTES_PER_FRAME * 80 + b.WEIGHT_BYTES_PER_MINIBATCH == 49_957_760                            # the 49.96 MB the traffic ratio divides by
+
+
+def test_dump_outputs_is_refused_where_it_does_not_apply():
+    """--dump-outputs covers the headline line; a configuration it does not cover fails before anything runs (no GPU needed)."""
+    for extra in (["--config", "c4"], ["--dry-launch"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", "unused"] + extra, capture_output=True,
+                           text=True, timeout=120, cwd=ROOT)
+        assert r.returncode != 0 and "--dump-outputs" in r.stderr, r.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_steps_and_dump_outputs(tmp_path):
+    """--steps K times exactly K steps (`ms_per_step` is one of them), and --dump-outputs writes what the last timed step computed
+    (out, in_diff, the updated parameters); the same arguments give the same inputs, so two runs give the same outputs (up to the
+    summation order of the device reductions)."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = _run(["--steps", "7", "--warmup", "3", "--no-extras", "--no-cpu-baseline", "--launch", "eager",
+                  "--dump-outputs", str(tmp_path / str(run))])
+        assert d["steps"] == d["timed"]["steps"] == d["steps_requested"] == 7
+        assert d["ms_per_step"] > 0 and abs(d["ms_per_step"] * 7 - d["timed_region_s"] * 1e3) <= 1e-6 * d["ms_per_step"]
+        assert sorted(d["dump_outputs"]["files"]) == ["in_diff.npy", "out.npy", "params.npy"]
+        dumps.append({n: np.load(tmp_path / str(run) / (n + ".npy")) for n in ("out", "in_diff", "params")})
+    shapes = {"out": (80, 512), "in_diff": (80, 40), "params": (2181600,)}
+    for n, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.shape == shapes[n] and np.isfinite(a).all() and np.abs(a).max() > 0, n
+        b = dumps[1][n]
+        assert np.abs(a - b).max() <= 1e-5 * np.abs(a).max(), n
