@@ -130,6 +130,13 @@ klstm_status klstm_set_state_host(klstm_engine *e, const float *c, const float *
  * (:231, :331). */
 klstm_status klstm_propagate(klstm_engine *e, const float *in, int rows, int in_stride,
                              float *out, int out_stride);
+/* Forward only (scoring, include/klstm_scorer.hpp): the same out rows and the same carried state as klstm_propagate,
+ * bit for bit, but nothing is kept for a backward pass -- klstm_backpropagate answers KLSTM_ERR_STATE until the next
+ * klstm_propagate.  Where the fp32 persistent chain runs one of the measured geometries (40/800/512 from 5 streams,
+ * 512/800/512 up to 8) the launch leaves out every activation-plane store the BPTT would read; every other path (and a persistent
+ * launch that gives up) runs the ordinary forward pass.  klstm_profile_query(e, "fwd_inference_launches") counts the former. */
+klstm_status klstm_propagate_inference(klstm_engine *e, const float *in, int rows, int in_stride,
+                                       float *out, int out_stride);
 
 /* BackpropagateFnc (...streams.h:334-499) for the minibatch of the immediately preceding
  * klstm_propagate (it reuses that call's activation slab, :342-349; rows must match).
@@ -293,6 +300,33 @@ klstm_status klstm_xent_eval_masked_post(const float *net_out, int rows, int col
                                          const int *post_pdf_dev, const float *post_weight_dev, const float *mask_dev, float *diff,
                                          int diff_stride, float *row_xent_dev, float *row_entropy_dev, float *row_correct_dev,
                                          void *hip_stream);
+
+/* Batched scoring (include/klstm_scorer.hpp): many utterances packed into the S streams of one engine, forward only.
+ * klstm_pack_streams  gathers one time-major chunk [T*S x dim] (row = t*S + s) from `feats`, the utterances' rows concatenated
+ *   (row stride feat_stride).  stream_desc_dev: 3 ints per stream on the device, {row offset of the utterance in feats, its length,
+ *   the frame the chunk starts at}; length <= 0 marks an idle stream (rows of zeros).  Row t of stream s is
+ *   feats[off + clamp(start + t + shift, 0, len - 1)]: the TimeShift / targets delay applied to each utterance on its own
+ *   (standard/nnet/nnet-time-shift.h:42-51), rows past the end repeat the last row like the trainer's padding
+ *   (bd-nnet-train-lstm-streams.cc:198-201).  reset_dev (may be NULL): per stream 1 if the chunk starts its utterance (start == 0)
+ *   or the stream is idle, else 0 -- the flags of klstm_reset for this chunk.
+ * klstm_log_softmax_scatter  for each input row i of a chunk's Affine output with dst_row_dev[i] >= 0, writes row dst_row_dev[i] of
+ *   `out` (dst_row_dev[i] < 0: a padding row, nothing is written):
+ *     KLSTM_SCORE_POSTERIOR  softmax(a), the arithmetic of klstm_softmax (bit-identical to it);
+ *     KLSTM_SCORE_LOGPOST    (a - max) - log(sum_j exp(a_j - max)), computed directly: it differs from log(klstm_softmax(a)) by the
+ *                            rounding of the posterior (relative 6e-8 of a value near 1, far more in the tail where the posterior
+ *                            underflows: the log form stays finite there, log of the Softmax output gives -inf);
+ *     KLSTM_SCORE_LOGLIKE    the log-posterior - prior_scale * log_prior_dev[j] (a device vector of cols floats).  Turning Kaldi's
+ *                            class-frame-counts into log priors is the caller's job; this is not claimed to match nnet-forward's
+ *                            PdfPrior bit for bit.
+ *   Rows of 2048..32768 columns (cols % 4 == 0, 16-byte aligned rows) are held in registers, one pass over memory; other shapes
+ *   take three sweeps over the row. */
+#define KLSTM_SCORE_POSTERIOR 0
+#define KLSTM_SCORE_LOGPOST   1
+#define KLSTM_SCORE_LOGLIKE   2
+klstm_status klstm_pack_streams(const float *feats, int dim, int feat_stride, const int *stream_desc_dev, int num_stream, int T,
+                                int shift, float *out, int out_stride, int *reset_dev, void *hip_stream);
+klstm_status klstm_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row_dev, float *out,
+                                       int out_stride, int mode, const float *log_prior_dev, float prior_scale, void *hip_stream);
 
 /* Engine knobs (not part of the reference interface).  Keys:
  *   "graph"   0/1/2  issue plain stream launches (default 0: measured equal or faster at every stream count while the host

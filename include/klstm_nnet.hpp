@@ -103,6 +103,7 @@ class LstmLayer : public Layer {            // LstmProjectedStreams / LstmProjec
   int32 NumParams() const override { return c_->NumParams(); }
   void GetParams(std::vector<BaseFloat> *p) const override { c_->GetParams(p); }
   LstmProjectedStreams *Impl() { return c_.get(); }
+  const LstmProjectedStreams *Impl() const { return c_.get(); }
  private:
   std::unique_ptr<LstmProjectedStreams> c_;
 };
@@ -117,6 +118,7 @@ class TimeShiftLayer : public Layer {
   void WriteData(std::ostream &os, bool b) const override { c_.WriteData(os, b); }
   void PropagateFnc(const MatrixView &in, MatrixView *out) override { c_.PropagateFnc(in, out); }
   void BackpropagateFnc(const MatrixView &a, const MatrixView &b, const MatrixView &c, MatrixView *d) override { c_.BackpropagateFnc(a, b, c, d); }
+  int32 Shift() const { return c_.Shift(); }
  private:
   TimeShift c_;
 };
@@ -251,6 +253,7 @@ class Nnet {                                  // google/nnet/nnet-nnet.h:36-150
   Nnet() {}
   int32 NumComponents() const { return (int32)layers_.size(); }
   Layer &GetComponent(int32 i) { return *layers_[i]; }
+  const Layer &GetComponent(int32 i) const { return *layers_[i]; }
   int32 InputDim() const { KLSTM_ASSERT(!layers_.empty()); return layers_.front()->InputDim(); }
   int32 OutputDim() const { KLSTM_ASSERT(!layers_.empty()); return layers_.back()->OutputDim(); }
   void AppendComponent(Layer *l) {

@@ -67,6 +67,9 @@ def load_library():
     lib.klstm_get_state_host.argtypes = [P, P, P]
     lib.klstm_set_state_host.argtypes = [P, P, P]
     lib.klstm_propagate.argtypes = [P, P, I, I, P, I]
+    lib.klstm_propagate_inference.argtypes = [P, P, I, I, P, I]
+    lib.klstm_pack_streams.argtypes = [P, I, I, P, I, I, I, P, I, P, P]
+    lib.klstm_log_softmax_scatter.argtypes = [P, I, I, I, P, P, I, I, P, F, P]
     lib.klstm_backpropagate.argtypes = [P, P, I, P, I, P, I, I, F, I]
     lib.klstm_propagate_host.argtypes = [P, P, I, I, P, I]
     lib.klstm_backpropagate_host.argtypes = [P, P, I, P, I, P, I, I, F, I]
@@ -238,6 +241,13 @@ class Engine:
         self._keep = [x, out]
         self._chk(self.lib.klstm_propagate(self.h, x.data_ptr(), rows, x.stride(0), out.data_ptr(), out.stride(0)))
         self.T = rows // self.S
+
+    def propagate_inference(self, x, out):
+        """klstm_propagate_inference: the out rows and carried state of propagate(), no activations kept for a backpropagate."""
+        assert x.is_cuda and out.is_cuda and (x.shape[0] == 0 or (x.stride(1) == 1 and out.stride(1) == 1))
+        self._keep = [x, out]
+        self._chk(self.lib.klstm_propagate_inference(self.h, x.data_ptr(), x.shape[0], x.stride(0), out.data_ptr(), out.stride(0)))
+        self.T = x.shape[0] // self.S
 
     def backpropagate(self, x, out_diff, in_diff=None, momentum=0.0, flags=0):
         assert x.is_cuda and out_diff.is_cuda and (x.shape[0] == 0 or (x.stride(1) == 1 and out_diff.stride(1) == 1))
@@ -454,6 +464,32 @@ def sgd_momentum_update(param, corr, grad, momentum, lr, stream=None):
     assert param.is_contiguous() and corr.is_contiguous() and grad.is_contiguous()
     _chk(lib.klstm_sgd_momentum_update(param.data_ptr(), corr.data_ptr(), grad.data_ptr(), param.numel(),
                                        float(momentum), float(lr), _sp(stream)))
+
+
+SCORE_POSTERIOR, SCORE_LOGPOST, SCORE_LOGLIKE = 0, 1, 2
+
+
+def pack_streams(feats, desc, T, shift, out, reset=None, stream=None):
+    """klstm_pack_streams: feats [rows, dim] (the utterances' rows concatenated), desc int32 [S, 3] device tensor of
+    (row offset, length, start frame) per stream (length <= 0: idle), out [T*S, dim]; reset: optional int32 [S] device tensor."""
+    import torch
+    lib = load_library()
+    assert desc.dtype == torch.int32 and desc.is_contiguous() and feats.stride(1) == 1 and out.stride(1) == 1
+    assert reset is None or (reset.dtype == torch.int32 and reset.numel() == desc.shape[0])
+    _chk(lib.klstm_pack_streams(feats.data_ptr(), feats.shape[1], feats.stride(0), desc.data_ptr(), desc.shape[0], int(T), int(shift),
+                                out.data_ptr(), out.stride(0), reset.data_ptr() if reset is not None else None, _sp(stream)))
+
+
+def log_softmax_scatter(a, dst_row, out, mode, log_prior=None, prior_scale=1.0, stream=None):
+    """klstm_log_softmax_scatter: row i of a [rows, cols] goes to row dst_row[i] of out (int32 device tensor; -1: not written) as
+    the posterior (SCORE_POSTERIOR), log-posterior (SCORE_LOGPOST) or log-posterior - prior_scale * log_prior (SCORE_LOGLIKE)."""
+    import torch
+    lib = load_library()
+    assert dst_row.dtype == torch.int32 and dst_row.is_contiguous() and dst_row.numel() == a.shape[0]
+    assert a.stride(1) == 1 and out.stride(1) == 1 and out.shape[1] == a.shape[1]
+    _chk(lib.klstm_log_softmax_scatter(a.data_ptr(), a.shape[0], a.shape[1], a.stride(0), dst_row.data_ptr(), out.data_ptr(),
+                                       out.stride(0), int(mode), log_prior.data_ptr() if log_prior is not None else None,
+                                       float(prior_scale), _sp(stream)))
 
 
 def softmax(x, out, stream=None):

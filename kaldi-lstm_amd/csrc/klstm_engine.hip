@@ -73,6 +73,7 @@ struct MbRec {
   const float *bin = nullptr; int bin_stride = 0; const float *od = nullptr; int od_stride = 0; float *idf = nullptr; int id_stride = 0;
   float mmt = 0.f; int flags = 0;
   float lr = 0.f, clip = 0.f;
+  bool inf = false;                           // the forward pass was klstm_propagate_inference's
 };
 static const klstm_status KLSTM_RECOVERED = (klstm_status)100;   // internal: a give-up was found and answered (never leaves the library)
 
@@ -130,6 +131,8 @@ struct klstm_engine {
   int use_persist = -1;    // weights-resident persistent chain (klstm_persist.hip): -1 auto (both directions, from 8 frames per
                            // stream), 0 off, 1 forward only, 2 forward and backward whenever the shape allows
   bool fwd_persist = false; // the last propagate ran inside one persistent launch
+  bool fwd_inf = false;     // ... and it is klstm_propagate_inference's: that launch leaves the activation planes alone
+  long n_inf = 0;           // forward-only launches that ran an INF instance (klstm_profile_query "fwd_inference_launches")
   bool fwd_ms = false;      // ... the many-stream bf16 one (klstm_persist_ms.hip): batched x term, launch, batched projection
   unsigned short *wrm_l = nullptr;   // W_rm = W_gifo_r W_r_m as bf16, logical rows x C (a bf16 product, refreshed after every Update) for that launch
   uint4 *gran_ms = nullptr; // its granule slots
@@ -506,7 +509,7 @@ static klstm_status ensure_persist(klstm_engine *e) {
 // counted.  The engine stays on the launch-per-step chain for `cooldown_len` minibatches, then tries the persistent one again.
 // Option "persist_verify" = 1 makes every persistent call wait for its launch, so that a give-up is always answered inside the
 // call that caused it, before the caller has seen `out` / `in_diff`.
-static klstm_status do_propagate(klstm_engine *e, const float *in, int rows, int in_stride, float *out, int out_stride);
+static klstm_status do_propagate(klstm_engine *e, const float *in, int rows, int in_stride, float *out, int out_stride, bool inf = false);
 static klstm_status do_backpropagate(klstm_engine *e, const float *in, int in_stride, const float *out_diff, int out_diff_stride,
                                      float *in_diff, int in_diff_stride, int rows, float momentum, int flags);
 static klstm_status do_update(klstm_engine *e, float learn_rate, float clip_grad);
@@ -568,7 +571,7 @@ static klstm_status recover(klstm_engine *e, const unsigned (&w)[16]) {
   if (re_fwd || re_bwd) {
     e->replaying = true;
     klstm_status st = KLSTM_OK;
-    if (re_fwd) st = do_propagate(e, r.in, r.rows, r.in_stride, r.out, r.out_stride);
+    if (re_fwd) st = do_propagate(e, r.in, r.rows, r.in_stride, r.out, r.out_stride, r.inf);
     if (st == KLSTM_OK && re_bwd) st = do_backpropagate(e, r.bin, r.bin_stride, r.od, r.od_stride, r.idf, r.id_stride, r.rows, r.mmt, r.flags);
     if (st == KLSTM_OK && re_upd) st = do_update(e, r.lr, r.clip);
     e->replaying = false;
@@ -999,7 +1002,7 @@ static klstm_status seq_forward(klstm_engine *e, const float *in, int in_stride,
     // step 1 closes over the CARRIED r (set by Reset / the previous minibatch, possibly under older weights): unfolded
     // gates kernel, r(0) mirrored into time block 0; steps 2..T close over m(t-1) through W_rm; r(1..T) in one GEMM
     if (e->fwd_persist) {                         // (all T steps in the one launch, step 1 on the natural matrices)
-      HIPCHK(launch_fwd_persist(d, p, in, in_stride, out, out_stride, e->gran[0], e->pctrl, e->popt, st, probe(e, "k_fwd_persist")));
+      HIPCHK(launch_fwd_persist(d, p, in, in_stride, out, out_stride, e->gran[0], e->pctrl, e->popt, st, probe(e, "k_fwd_persist"), e->fwd_inf));
       e->persist_dirty = true;
       if (persist_r_in_kernel(d, e->popt)) return KLSTM_OK;  // (r(1..T), the output rows and the carried r come out of the same launch)
     } else {
@@ -1161,7 +1164,7 @@ static klstm_status run_graphed(klstm_engine *e, const klstm_engine::Key &key, F
 }
 
 // The body of klstm_propagate (arguments checked by the caller): also what recover() runs a minibatch again with.
-static klstm_status do_propagate(klstm_engine *e, const float *in, int rows, int in_stride, float *out, int out_stride) {
+static klstm_status do_propagate(klstm_engine *e, const float *in, int rows, int in_stride, float *out, int out_stride, bool inf) {
   const int T = rows / e->S;
   const RangeGuardScope rgs(e->rg);                   // (this engine's fp16-plane products look at this engine's range guard)
   { const klstm_status ks = knobs_seen(e); if (ks != KLSTM_OK) return ks; }
@@ -1191,10 +1194,12 @@ static klstm_status do_propagate(klstm_engine *e, const float *in, int rows, int
     HIPCHK(launch_pack(d0, e->params, e->wrT, e->wmT, e->wxT, e->pk, 1, e->use_bf16, e->stream, probe(e, "k_pack")));
     e->pk_stale &= ~1;
   }
-  klstm_engine::Key key(T, in, in_stride, out, out_stride, nullptr, 0, 0.f, (e->fwd_ms ? -4 : e->fwd_persist ? -3 : e->fwd_folded ? -2 : -1) * 2 - e->sp);
+  e->fwd_inf = inf && e->fwd_persist;
+  klstm_engine::Key key(T, in, in_stride, out, out_stride, nullptr, e->fwd_inf ? 1 : 0, 0.f, (e->fwd_ms ? -4 : e->fwd_persist ? -3 : e->fwd_folded ? -2 : -1) * 2 - e->sp);
   st = run_graphed(e, key, [&]() { return seq_forward(e, in, in_stride, out, out_stride, T); },
                    e->fwd_persist && persist_r_in_kernel(Dims{e->I, e->C, e->R, e->S, T}, e->popt));
   if (st != KLSTM_OK) return st;
+  if (e->fwd_inf && persist_fwd_has_inference(Dims{e->I, e->C, e->R, e->S, T}, e->popt)) e->n_inf++;
   if (e->fwd_persist || e->fwd_ms) {                  // (counted here, not inside the launch sequence: a graph replay is a launch too)
     e->pseq++;
     e->persist_dirty = true;
@@ -1202,7 +1207,7 @@ static klstm_status do_propagate(klstm_engine *e, const float *in, int rows, int
   }
   e->sp ^= 1;                                         // c(T), r(T) were written to the other buffer: it is the carried state now
   e->resets.clear();
-  e->T_fwd = T;
+  e->T_fwd = inf ? -1 : T;                            // (forward only: there is nothing for a backpropagate to read)
   e->T_bwd = -1;
   return KLSTM_OK;
 }
@@ -1275,16 +1280,15 @@ static klstm_status verify_deferred(klstm_engine *e) {
   return verify_now(e, e->verify_later_reports);
 }
 
-extern "C" {
-
-klstm_status klstm_propagate(klstm_engine *e, const float *in, int rows, int in_stride, float *out, int out_stride) {
+// klstm_propagate and klstm_propagate_inference: one body, the latter with inf = true
+static klstm_status propagate_entry(klstm_engine *e, const float *in, int rows, int in_stride, float *out, int out_stride, bool inf) {
   if (!e || ((!in || !out) && rows != 0)) return fail(KLSTM_ERR_ARG, "klstm_propagate: null argument");
   if (rows < 0 || rows % e->S != 0)
     return fail(KLSTM_ERR_SHAPE, "klstm_propagate: rows (%d) %% num_stream (%d) != 0", rows, e->S);
   if (rows == 0) {          // T = 0: the reference's loops simply do not run (:261, :328 with zero rows); state is unchanged
     { klstm_status vs = verify_deferred(e); if (vs != KLSTM_OK) return vs; }   // (a pending wait of the previous minibatch needs its record: as for rows > 0)
     e->rec = MbRec();       // (a new minibatch all the same)
-    e->T_fwd = 0;
+    e->T_fwd = inf ? -1 : 0;
     e->T_bwd = -1;
     return KLSTM_OK;
   }
@@ -1301,12 +1305,21 @@ klstm_status klstm_propagate(klstm_engine *e, const float *in, int rows, int in_
   if (e->marks.size() >= klstm_engine::MARKS_MAX) { e->persist_dirty = true; klstm_status ss = settle(e); if (ss != KLSTM_OK) return ss; }
   { klstm_status gs = flush_grads(e); if (gs != KLSTM_OK) return gs; }   // (deferred gradient products read the planes of the last minibatch)
   const int sp0 = e->sp;
-  klstm_status st = do_propagate(e, in, rows, in_stride, out, out_stride);
+  klstm_status st = do_propagate(e, in, rows, in_stride, out, out_stride, inf);
   if (st != KLSTM_OK) return st;
   MbRec &r = e->rec;
   r.have_fwd = true; r.fwd_seq = (e->fwd_persist || e->fwd_ms) ? e->pseq : 0; r.sp_before = sp0;
-  r.in = in; r.rows = rows; r.in_stride = in_stride; r.out = out; r.out_stride = out_stride;
+  r.in = in; r.rows = rows; r.in_stride = in_stride; r.out = out; r.out_stride = out_stride; r.inf = inf;
   return verify_now(e, e->fwd_persist || (e->fwd_ms && !persist_xl_supported(Dims{e->I, e->C, e->R, e->S, rows / e->S}, e->popt)));
+}
+
+extern "C" {
+
+klstm_status klstm_propagate(klstm_engine *e, const float *in, int rows, int in_stride, float *out, int out_stride) {
+  return propagate_entry(e, in, rows, in_stride, out, out_stride, false);
+}
+klstm_status klstm_propagate_inference(klstm_engine *e, const float *in, int rows, int in_stride, float *out, int out_stride) {
+  return propagate_entry(e, in, rows, in_stride, out, out_stride, true);
 }
 
 klstm_status klstm_backpropagate(klstm_engine *e, const float *in, int in_stride, const float *out_diff,
@@ -1759,7 +1772,7 @@ klstm_status klstm_profile_query(klstm_engine *e, const char *kernel, double *to
     const struct { const char *name; long v; } ctr[] = {
         {"persist_giveups", e->n_giveups}, {"persist_replayed", e->n_replayed}, {"persist_dropped", e->n_dropped},
         {"persist_launches", (long)e->pseq}, {"persist_cooldown", (long)e->cooldown}, {"gemm_copies_launches", e->n_copies},
-        {"persist_tail_wgs", e->tail_wgs}, {"tail_merge_launches", (long)e->tr_seq},
+        {"persist_tail_wgs", e->tail_wgs}, {"tail_merge_launches", (long)e->tr_seq}, {"fwd_inference_launches", e->n_inf},
         // range-guard events: this engine's own products + the stateless klstm_affine_* calls made on this device (its default guard)
         {"fp16_redo", ev(REDO_FOLD) + ev(REDO_NT) + ev(REDO_OUTER) + ev(REDO_SKINNY)},
         {"fp16_redo_fold", ev(REDO_FOLD)}, {"fp16_redo_nt", ev(REDO_NT)},
@@ -1997,6 +2010,28 @@ klstm_status klstm_affine_gradient(const float *in, int in_stride, const float *
   else
     HIPCHK(launch_gemm(true, false, out_dim, in_dim, rows, out_diff, od_stride, in, in_stride, 0.f, W_grad, in_dim, nullptr, st));
   HIPCHK(launch_col_sum(out_diff, rows, out_dim, od_stride, 0.f, bias_grad, st));
+  return KLSTM_OK;
+}
+klstm_status klstm_pack_streams(const float *feats, int dim, int feat_stride, const int *stream_desc_dev, int num_stream, int T,
+                                int shift, float *out, int out_stride, int *reset_dev, void *hip_stream) {
+  if ((!feats || !stream_desc_dev || !out) && T > 0) return fail(KLSTM_ERR_ARG, "klstm_pack_streams: null argument");
+  if (dim < 0 || num_stream <= 0 || T < 0 || feat_stride < dim || out_stride < dim)
+    return fail(KLSTM_ERR_ARG, "klstm_pack_streams: bad size (dim %d, streams %d, T %d, strides %d / %d)", dim, num_stream, T, feat_stride, out_stride);
+  if ((long)T * num_stream > 65535) return fail(KLSTM_ERR_SHAPE, "klstm_pack_streams: T * num_stream > 65535");
+  if (T == 0 || dim == 0) return KLSTM_OK;
+  HIPCHK(launch_pack_streams(feats, dim, feat_stride, stream_desc_dev, num_stream, T, shift, out, out_stride, reset_dev, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
+klstm_status klstm_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row_dev, float *out,
+                                       int out_stride, int mode, const float *log_prior_dev, float prior_scale, void *hip_stream) {
+  if ((!in || !dst_row_dev || !out) && rows > 0) return fail(KLSTM_ERR_ARG, "klstm_log_softmax_scatter: null argument");
+  if (rows < 0 || cols <= 0 || in_stride < cols || out_stride < cols) return fail(KLSTM_ERR_ARG, "klstm_log_softmax_scatter: bad size");
+  if (mode != KLSTM_SCORE_POSTERIOR && mode != KLSTM_SCORE_LOGPOST && mode != KLSTM_SCORE_LOGLIKE)
+    return fail(KLSTM_ERR_ARG, "klstm_log_softmax_scatter: unknown mode %d", mode);
+  if (mode == KLSTM_SCORE_LOGLIKE && !log_prior_dev) return fail(KLSTM_ERR_ARG, "klstm_log_softmax_scatter: log-likelihoods need log_prior");
+  if (rows == 0) return KLSTM_OK;
+  HIPCHK(launch_log_softmax_scatter(in, rows, cols, in_stride, dst_row_dev, out, out_stride, mode, log_prior_dev, prior_scale,
+                                    (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
 klstm_status klstm_sgd_momentum_update(float *param, float *corr, const float *grad, long n, float momentum, float lr,

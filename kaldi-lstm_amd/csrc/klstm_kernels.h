@@ -275,6 +275,11 @@ hipError_t launch_time_shift(const float *in, int rows, int cols, int in_stride,
 
 // output tail (Softmax, Xent::EvalMasked) and AffineTransform::Update helpers
 hipError_t launch_softmax(const float *in, int rows, int cols, int in_stride, float *out, int out_stride, hipStream_t st);
+// batched scoring (klstm_score.hip): klstm_pack_streams / klstm_log_softmax_scatter of include/klstm.h
+hipError_t launch_pack_streams(const float *feats, int dim, int feat_stride, const int *desc, int S, int T, int shift, float *out,
+                               int out_stride, int *reset, hipStream_t st);
+hipError_t launch_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row, float *out, int out_stride,
+                                      int mode, const float *log_prior, float prior_scale, hipStream_t st);
 hipError_t launch_xent(const float *y, int rows, int cols, int stride, const int *target, const float *mask, float *diff,
                        int diff_stride, float *row_xent, float *row_correct, hipStream_t st);
 hipError_t launch_softmax_xent(const float *in, int rows, int cols, int in_stride, float *post, int post_stride, const int *target,
@@ -328,7 +333,9 @@ int persist_bwd_grid(const Dims &d);
 size_t persist_gran_bytes(const Dims &d);
 bool persist_r_in_kernel(const Dims &d, const PersistOpts &o);   // r(t) = W_r_m m(t), the output rows and prev_r written by the forward launch (pass out)
 hipError_t launch_fwd_persist(const Dims &d, const FwdPtrs &p, const float *in, int in_stride, float *out, int out_stride,
-                              unsigned long long *gran, unsigned *ctrl, const PersistOpts &o, hipStream_t st, LaunchProbe pr = {});
+                              unsigned long long *gran, unsigned *ctrl, const PersistOpts &o, hipStream_t st, LaunchProbe pr = {},
+                              bool inference = false);   // inference: the INF instance (no activation-plane stores) where persist_fwd_has_inference
+bool persist_fwd_has_inference(const Dims &d, const PersistOpts &o);   // an INF = true instance serves this shape (r inside the launch)
 bool persist_p_in_kernel(const Dims &d, const PersistOpts &o);   // P = out_diff W_r_m computed inside the backward launch (then P may be null)
 bool persist_tail_in_kernel(const Dims &d, bool want_in_diff, const PersistOpts &o);   // d_r / in_diff contracted inside the backward launch
 bool persist_tail_in_chain(const Dims &d, bool want_in_diff, const PersistOpts &o);    // ... on the chain's own workgroups

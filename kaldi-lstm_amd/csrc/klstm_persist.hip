@@ -157,7 +157,10 @@ constexpr int persist_maxu(int maxc) { return maxc == 7 ? 5 : maxc; }
 // fabric the workgroup sweeps, contracts and updates group 1, whose granules were published half a step earlier and are mostly there.
 // Granules lie group-major ([parity][group][C][4 streams]) so that a group's sweep reads whole lines.  Same arithmetic per (cell,
 // stream): bit-identical to the lock-step form (tests/test_persist_robustness_gpu.py).
-template <int TPW, int MAXC, int PNW, int PCELL, int NG, bool XB = false, bool IL = false>
+// INF (klstm_propagate_inference): forward only -- every store of an activation plane the BPTT would read (gifo, c, h, m, r and time
+// block 0 of the c / r planes) is left out; the output rows, the granule exchange and next_c / next_r stay, and so does every READ
+// (XB: the batched x term in the gifo plane).  Same arithmetic in the same order: out and the carried state are bit-identical.
+template <int TPW, int MAXC, int PNW, int PCELL, int NG, bool XB = false, bool IL = false, bool INF = false>
 __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
   static_assert(!IL || (NG >= 2 && NG <= 4), "interleaved chains: two to four stream groups");
   constexpr int PNT = PNW * 64, NCW = 4 * TPW, NSW = (PNW - NCW - 1) * 64, MAXU = persist_maxu(MAXC);   // cell waves, one projection wave, sweepers
@@ -216,7 +219,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
     for (int g = 0; g < NG; g++) {
       e_ong[g] = (lane >> 2) == 3 && 4 * g + es < S && e_cell < C;
       cpg[g] = a.prev_c[(size_t)(e_ong[g] ? 4 * g + es : 0) * C + lc];            // carried c(0) (:231)
-      if (e_ong[g]) a.cc[(size_t)(4 * g + es) * C + e_cell] = cpg[g];              // time block 0 of the c plane: BPTT reads it (:231)
+      if (!INF && e_ong[g]) a.cc[(size_t)(4 * g + es) * C + e_cell] = cpg[g];      // time block 0 of the c plane: BPTT reads it (:231)
     }
     // (the guard word was requested before prev_c and loads return in order: it is here.  Looked at NOW, in front of the weight
     //  requests -- behind them the compiler waits for ALL of them, and the folded rows are meant to arrive under step 1: 1.3 us)
@@ -242,12 +245,14 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
       const float m = h * go;                      // :309
       if ((t < T || a.rin) && !(a.test_stall == t && blockIdx.x == 0))                                           // (m(T): for r(T) only)
         publish(a.gran + (size_t)(t & 1) * C * SS, IL ? (g * C + e_cell) * 4 + es : e_cell * SS + es_g, epoch + (unsigned)t, m);
-      const int vg = (es_g * 4 * C + e_cell) * 4, vc = (es_g * C + e_cell) * 4, sg = t * S * 4 * C * 4, sc = t * S * C * 4;
-      buf_store_f32(rs_g, vg, sg, gg); buf_store_f32(rs_g, vg, sg + C * 4, gi);
-      buf_store_f32(rs_g, vg, sg + 2 * C * 4, gf); buf_store_f32(rs_g, vg, sg + 3 * C * 4, go);
-      buf_store_f32(rs_c, vc, sc, c);
-      buf_store_f32(rs_h, vc, sc, h);
-      buf_store_f32(rs_m, vc, sc, m);
+      if constexpr (!INF) {
+        const int vg = (es_g * 4 * C + e_cell) * 4, vc = (es_g * C + e_cell) * 4, sg = t * S * 4 * C * 4, sc = t * S * C * 4;
+        buf_store_f32(rs_g, vg, sg, gg); buf_store_f32(rs_g, vg, sg + C * 4, gi);
+        buf_store_f32(rs_g, vg, sg + 2 * C * 4, gf); buf_store_f32(rs_g, vg, sg + 3 * C * 4, go);
+        buf_store_f32(rs_c, vc, sc, c);
+        buf_store_f32(rs_h, vc, sc, h);
+        buf_store_f32(rs_m, vc, sc, m);
+      }
       if (t == T) a.next_c[(size_t)es_g * C + e_cell] = c;       // :331 (c columns)
       cp = c;
     };
@@ -398,7 +403,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
           const int ps = 4 * g + bj;
           if (kg == 3 && ps < S) {                   // lanes 12..15: stream ps, components = rows 4*blockIdx .. +3
             const int f = t - 1, g4 = (int)blockIdx.x * 4;
-            *reinterpret_cast<float4 *>(a.rr + ((size_t)f * S + ps) * R + g4) = make_float4(v.x, v.y, v.z, v.w);
+            if (!INF) *reinterpret_cast<float4 *>(a.rr + ((size_t)f * S + ps) * R + g4) = make_float4(v.x, v.y, v.z, v.w);
             float *op = a.out + ((size_t)(f - 1) * S + ps) * a.out_stride + g4;
             op[0] = v.x; op[1] = v.y; op[2] = v.z; op[3] = v.w;
             if (f == T) *reinterpret_cast<float4 *>(a.next_r + (size_t)ps * R + g4) = make_float4(v.x, v.y, v.z, v.w);
@@ -418,7 +423,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
         const int ps = 4 * g + bj;
         if (kg == 3 && ps < S) {                     // lanes 12..15: stream ps, components = rows 4*blockIdx .. +3
           const int f = t - 1, g4 = (int)blockIdx.x * 4;
-          *reinterpret_cast<float4 *>(a.rr + ((size_t)f * S + ps) * R + g4) = make_float4(v.x, v.y, v.z, v.w);
+          if (!INF) *reinterpret_cast<float4 *>(a.rr + ((size_t)f * S + ps) * R + g4) = make_float4(v.x, v.y, v.z, v.w);
           float *op = a.out + ((size_t)(f - 1) * S + ps) * a.out_stride + g4;
           op[0] = v.x; op[1] = v.y; op[2] = v.z; op[3] = v.w;
           if (f == T) *reinterpret_cast<float4 *>(a.next_r + (size_t)ps * R + g4) = make_float4(v.x, v.y, v.z, v.w);
@@ -440,7 +445,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
           const int s_ = i / (R / 4), k = (i % (R / 4)) * 4;
           const float4 rv = *reinterpret_cast<const float4 *>(a.prev_r + (size_t)s_ * R + k);
           *reinterpret_cast<float4 *>(ldsU + s_ * LDU + k) = rv;
-          if (blockIdx.x == 0) *reinterpret_cast<float4 *>(a.rr + (size_t)s_ * R + k) = rv;
+          if (!INF && blockIdx.x == 0) *reinterpret_cast<float4 *>(a.rr + (size_t)s_ * R + k) = rv;
         }
         if (x_on) *reinterpret_cast<float4 *>(ldsU + xs * LDU + RP + xk) = xv;
         lds_barrier();
@@ -501,7 +506,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
           const int s = i / (R / 4), k = (i % (R / 4)) * 4;
           const float4 rv = *reinterpret_cast<const float4 *>(a.prev_r + (size_t)s * R + k);
           *reinterpret_cast<float4 *>(ldsU + s * LDU + k) = rv;
-          if (blockIdx.x == 0) *reinterpret_cast<float4 *>(a.rr + (size_t)s * R + k) = rv;
+          if (!INF && blockIdx.x == 0) *reinterpret_cast<float4 *>(a.rr + (size_t)s * R + k) = rv;
         }
         if (x_on) *reinterpret_cast<float4 *>(ldsU + xs * LDU + RP + xk) = xv;
       } else {
@@ -658,6 +663,22 @@ static hipError_t plaunch(K kern, int grid, int threads, size_t shm, hipStream_t
     return hipErrorInvalidValue;                                                                                \
   } while (0)
 
+// klstm_propagate_inference: the INF = true instances.  Only the geometries of C = 449..896 (two cells per sweeper thread) at <= 7
+// operand chunks -- 40/800/512 and 512/800/512, the configs[3] stack -- whose INF form allocates no worse than its training twin
+// (-Rpass-analysis=kernel-resource-usage: scratch and spills) and measures no slower (tools/score_bench.py).  Left out:
+// the one-group, x-inside-the-step form (40-input layer, <= 4 streams), whose INF form spills 6 VGPRs (28 B scratch) where the training
+// form spills none and measured 59.1 against 53.3 us per chunk; the other PCELL / MAXC forms (not measured).  Everything else runs the
+// ordinary instance: the same out and state, with the planes.
+#define PFINF(XB_, IL_, NG_)                                                                                    \
+  if (xbat == XB_ && il == IL_ && ng == NG_) return plaunch(k_fwd_persist<1, 7, 12, 2, NG_, XB_, IL_, true>, grid, 768, shm, st, pr, a);
+bool persist_fwd_has_inference(const Dims &d, const PersistOpts &o) {
+  const bool xbat = persist_x_batched(d), il = d.S > 4 && o.fwd_interleave != 0;
+  const int ng = (d.S + 3) / 4, Ik = xbat ? 0 : d.I;
+  const PGeo g = pick_geo_fwd(o, d.C, pcdiv(d.C, KCH) + pcdiv(Ik, KCH), pcdiv(d.R, KCH) * KCH + Ik);
+  if (g.waves != 12 || g.tpw != 1 || g.maxc != 7 || g.pcell != 2 || !persist_r_in_kernel(d, o)) return false;
+  return (ng == 1 && xbat) || (il && ng == 2) || (il && !xbat && (ng == 3 || ng == 4));
+}
+
 // r(t) = W_r_m m(t) inside the forward launch: 4 rows of W_r_m per workgroup on its projection wave
 bool persist_r_in_kernel(const Dims &d, const PersistOpts &o) {
   const int Ik = persist_x_batched(d) ? 0 : d.I;
@@ -666,7 +687,8 @@ bool persist_r_in_kernel(const Dims &d, const PersistOpts &o) {
 }
 
 hipError_t launch_fwd_persist(const Dims &d, const FwdPtrs &p, const float *in, int in_stride, float *out, int out_stride,
-                              unsigned long long *gran, unsigned *ctrl, const PersistOpts &o, hipStream_t st, LaunchProbe pr) {
+                              unsigned long long *gran, unsigned *ctrl, const PersistOpts &o, hipStream_t st, LaunchProbe pr,
+                              bool inference) {
   PersistFwdArgs a;
   const bool xbat = persist_x_batched(d);            // (the caller has run the batched x-projection into the gifo plane)
   a.C = d.C; a.I = xbat ? 0 : d.I; a.R = d.R; a.S = d.S; a.T = d.T;
@@ -691,6 +713,9 @@ hipError_t launch_fwd_persist(const Dims &d, const FwdPtrs &p, const float *in, 
   const int ng = (d.S + 3) / 4;
   const size_t shm = (size_t)(4 * ng * (g.maxc * 128 + 16) + 4 * ng * (persist_maxu(g.maxc) * 128 + 16) + 4) * sizeof(float);   // (+ abort flag, projection flag)
   const int grid = d.C / 4 / g.tpw;
+  if (inference && a.rin && persist_fwd_has_inference(d, o)) {   // (without rin the batched projection behind the launch reads the m plane)
+    PFINF(true, false, 1) PFINF(true, true, 2) PFINF(false, true, 2) PFINF(false, true, 3) PFINF(false, true, 4)
+  }
   PDISPATCH_FWD(k_fwd_persist);
 }
 
