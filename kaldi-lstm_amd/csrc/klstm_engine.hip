@@ -152,6 +152,7 @@ struct klstm_engine {
   int tail_merge = 0;
   unsigned *tr_ctr = nullptr;   // device: [0] arrivals of reduce workgroups over the engine's life, [1] expired waits
   unsigned tr_seq = 0;          // merged launches enqueued so far
+  unsigned tr_total = 0;        // their reduce workgroups (tail_reduce_blocks) summed: what ctr[0] reaches once all of them have arrived
   bool tail_pending = false;
   TailReduceJob tr_job;
   bool bwd_persist = false; // ... and its backpropagate runs steps T..1 inside one persistent launch
@@ -364,7 +365,8 @@ static const float *ar_mark_if_reduced(const klstm_engine *e) { return e->ar_mar
 static const TailReduceJob *take_tail_job(klstm_engine *e) {
   if (!e->tail_pending) return nullptr;
   e->tail_pending = false;
-  e->tr_job.ctr = e->tr_ctr; e->tr_job.seq = ++e->tr_seq;
+  ++e->tr_seq; e->tr_total += (unsigned)tail_reduce_blocks(e->tr_job);
+  e->tr_job.ctr = e->tr_ctr; e->tr_job.target = e->tr_total;
   return &e->tr_job;
 }
 // ... or in a launch of its own (somebody wants in_diff / d_r before any gradient launch: klstm_synchronize, a getter, set_corr)
@@ -483,7 +485,7 @@ static klstm_status ensure_persist(klstm_engine *e) {
   HIPCHK(hipMemsetAsync(e->pctrl, 0, 16 * sizeof(unsigned), e->stream));
   HIPCHK(hipMalloc(&e->tr_ctr, 4 * sizeof(unsigned)));   // "tail_merge": arrivals / expired waits (words of their own: recover() rewrites pctrl)
   HIPCHK(hipMemsetAsync(e->tr_ctr, 0, 4 * sizeof(unsigned), e->stream));
-  e->tr_seq = 0;
+  e->tr_seq = 0; e->tr_total = 0;
   if (hipHostMalloc(reinterpret_cast<void **>(&e->pstat_host), 64, hipHostMallocMapped) == hipSuccess) {
     *e->pstat_host = 0u;
     e->pstat_host[1] = 0u;                         // (the done word of finish(): launch count | give-up bit)

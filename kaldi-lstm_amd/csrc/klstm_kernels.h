@@ -231,8 +231,9 @@ struct TailReduceJob {
   const float *tws = nullptr; int nslots = 0, T = 0, S = 0, R = 0, ncols = 0;   // partial rows [nslots][T*S][ncols]; ncols = R (+ I)
   const float *od = nullptr; int od_stride = 0;                                // out_diff: added to the d_r columns (:391), d_r(T) = out_diff(T) (:351)
   float *dr = nullptr; float *in_diff = nullptr; int id_stride = 0;
-  unsigned *ctr = nullptr;        // merged form: [0] arrivals of the reduce workgroups (never reset: launch n waits for n * nred), [1] waits that expired
-  unsigned seq = 0;               // merged form: ordinal of this launch among the engine's merged launches (1, 2, ...)
+  unsigned *ctr = nullptr;        // merged form: [0] arrivals of the reduce workgroups (never reset), [1] waits that expired
+  unsigned target = 0;            // merged form: ctr[0] once this launch's reduce workgroups have arrived = the sum of tail_reduce_blocks
+                                  // over the engine's merged launches so far, this one included (nred changes with T and with in_diff)
 };
 int tail_reduce_blocks(const TailReduceJob &j);   // reduce workgroups of the merged form (a multiple of 8)
 hipError_t launch_tail_reduce(const TailReduceJob &j, const unsigned *guard, hipStream_t st, LaunchProbe pr = {});   // the launch of its own

@@ -2029,7 +2029,8 @@ __device__ __forceinline__ void grads_column_sums(const GradsArgs &a, int vb, fl
 // TM (k_grads_tm, "tail_merge"): the launch also runs the reduction of the tail workgroups' partial rows that used to be k_tail_reduce behind the BPTT
 // launch.  Workgroups [0, nred) (dispatched first) add the partial rows -- d_r as write-through stores --, wait for their stores'
 // acknowledgements and arrive at tr.ctr[0]; the W_r_m tiles (the only readers of d_r) sit at the END of every XCD's range, wait for
-// ctr[0] to reach tr_target (a launch ordinal times nred: nothing to reset, a launch that does nothing still arrives) and read d_r with sc1
+// ctr[0] to reach tr_target (the engine's running total of reduce workgroups over its merged launches, this one included: nothing to
+// reset, a launch that does nothing still arrives, and nred may differ from launch to launch) and read d_r with sc1
 // loads; the W_gifo_x / W_gifo_r tiles and the column sums start at once.  The wait is bounded (200 ms; an expiry is counted in ctr[1] and
 // the tile goes on -- the reduce workgroups have the lowest indices, so they are resident or done before any tile that waits for them).
 template <bool TM>
@@ -3598,7 +3599,7 @@ hipError_t launch_grads(const Dims &d, const float *dgifo, const float *dr, cons
   }
   if (tr) {   // the reduction of the tail workgroups' partial rows on the first workgroups of this launch
     if (!(a.wm.vecA && a.wm.vecB) || !tr->ctr || !tr->tws) return hipErrorInvalidValue;   // (16-byte rows: the engine's own buffers)
-    a.tr = *tr; a.nred = tail_reduce_blocks(*tr); a.tr_target = tr->seq * (unsigned)a.nred;
+    a.tr = *tr; a.nred = tail_reduce_blocks(*tr); a.tr_target = tr->target;
     KLAUNCH(k_grads_tm, dim3(a.nred + 8 * (cdiv(a.nb1, 8) + cdiv(a.nb2 + a.nvec - a.nb1, 8))), dim3(256), st, pr, a);
   }
   KLAUNCH(k_grads, dim3(cdiv(a.nb2 + a.nvec, 8) * 8), dim3(256), st, pr, a);

@@ -322,6 +322,51 @@ def test_tail_merge_bit_identical(I, C, R, S, T, want_in_diff, how):
         e.close()
 
 
+@pytest.mark.parametrize("how", ["plain", "fused"])
+def test_tail_merge_with_varying_reduce_workgroups(how):
+    """"tail_merge" = 1 when the number of reduce workgroups (tail_reduce_blocks: 352 at T = 20 with in_diff, 320 without, 208 at T = 12
+    with it) changes from one minibatch to the next on one engine: first it grows, then it shrinks, then it grows again.  The W_r_m
+    tiles of each merged launch wait until the arrival counter (never reset) has reached the engine's running total of reduce
+    workgroups; a target of (launch ordinal) x (this launch's count) would be too high after growth (the tiles wait out the 200 ms
+    bound: tail_merge_timeouts) and too low after shrinking (they race the reduction for d_r).  Bit-identical to "tail_merge" = 0 at
+    every step."""
+    import kaldi_lstm_amd as k
+    I, C, R, S = 40, 800, 512, 4
+    seq = [(12, True), (20, True), (20, False), (12, False), (20, True), (14, True)]
+    rng = np.random.RandomState(21)
+    p = make_params(I, C, R, scale=0.05, seed=22)
+    flags = {"plain": 0, "fused": 2}[how]
+    eng = []
+    for merge in (1, 0):
+        e = k.Engine(I, C, R, S)
+        e.set_option("persist", 2); e.set_option("tail_merge", merge); e.set_params(p)
+        eng.append(e)
+    for step, (T, want_in_diff) in enumerate(seq):
+        x = rng.randn(T * S, I).astype(np.float32); od = (0.3 * rng.randn(T * S, R)).astype(np.float32)
+        xd, odd = dev(x), dev(od)
+        res = []
+        for e in eng:
+            n0 = e.profile_query("persist_launches")[1]
+            outd = torch.empty(T * S, R, device="cuda"); idd = torch.zeros(T * S, I, device="cuda") if want_in_diff else None
+            e.propagate(xd, outd); e.backpropagate(xd, odd, idd, momentum=0.9, flags=flags)
+            e.update(1e-3); e.synchronize()
+            assert e.profile_query("persist_launches")[1] == n0 + 2, f"step {step} (T = {T}): not both directions persistent"
+            res.append(dict(out=outd.cpu().numpy(), ind=idd.cpu().numpy() if want_in_diff else None, corr=e.get_corr(),
+                            par=e.get_params(), D=e.activations(1)))
+        a, b = res
+        assert eng[0].profile_query("persist_tail_wgs")[1] > 0 and eng[0].profile_query("persist_giveups")[1] == 0
+        assert eng[0].profile_query("tail_merge_launches")[1] == step + 1, f"step {step}: the reduction was not merged"
+        assert eng[0].profile_query("tail_merge_timeouts")[1] == 0, f"step {step} (T = {T}, in_diff {want_in_diff}): a wait expired"
+        assert np.array_equal(a["out"], b["out"]), f"step {step}: out differs"
+        assert np.array_equal(a["D"], b["D"]), f"step {step}: derivative planes / d_r differ"
+        if want_in_diff:
+            assert np.array_equal(a["ind"], b["ind"]), f"step {step}: in_diff differs"
+        assert np.array_equal(a["corr"], b["corr"]) and np.array_equal(a["par"], b["par"]), f"step {step}: gradients / parameters differ"
+    assert eng[1].profile_query("tail_merge_launches")[1] == 0
+    for e in eng:
+        e.close()
+
+
 @pytest.mark.parametrize("fold", [0, 1])
 def test_config_c2_50_chunk_drift(fold):
     """SURVEY 8(d) parity gate "after 1 and after 50 chunks": one whole 1000-frame utterance per stream = 50 chained
