@@ -1875,8 +1875,8 @@ static bool d2h_small(void *dst, const void *src, size_t bytes, hipStream_t st) 
   }
   if (++sg.seq == 0) sg.seq = 1;      // (0 = what the buffer holds before its first use)
   const int nw = (int)(bytes / 4);
-  hipLaunchKernelGGL(k_d2h_small, dim3(1), dim3(64), 0, st, static_cast<const unsigned *>(src), sg.dev, nw, sg.seq);
-  if (hipGetLastError() != hipSuccess) return false;
+  if (launch(k_d2h_small, dim3(1), dim3(64), 0, st, LaunchProbe{}, static_cast<const unsigned *>(src), sg.dev, nw, sg.seq) != hipSuccess)
+    return false;
   const volatile unsigned long long *q = sg.host;
   const auto t0 = std::chrono::steady_clock::now();
   int have = 0;
@@ -2290,9 +2290,7 @@ extern "C" klstm_status klstm_debug_occupy(int device, int workgroups, int micro
     if (!o) HIPCHK(hipStreamCreateWithFlags(&o, hipStreamNonBlocking));
     st = o;
   }
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_occupy), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-  hipLaunchKernelGGL(k_occupy, dim3(workgroups), dim3(1024), 96 * 1024, st, (long long)microseconds * 100, where_dev);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch(k_occupy, dim3(workgroups), dim3(1024), 96 * 1024, st, LaunchProbe{}, (long long)microseconds * 100, where_dev));
   return KLSTM_OK;
 }
 

@@ -30,9 +30,6 @@
 #include "klstm_kernels.h"
 #include "klstm_math.h"
 
-#include <hip/hip_ext.h>
-#include <mutex>
-#include <set>
 #include <type_traits>
 
 namespace klstm {
@@ -306,14 +303,7 @@ hipError_t launch_fold_direct(const Dims &d, const float *wr, const float *wmT, 
   a.nbn = (d.C + 32 * best - 1) / (32 * best);
   a.nwg = nbm * a.nbn;
   const dim3 grid((a.nwg + 7) / 8 * 8), block(256);
-  if (best == 5) {
-    if (pr.start) hipExtLaunchKernelGGL(k_fold_direct<5>, grid, block, 0, st, pr.start, pr.stop, 0, a);
-    else hipLaunchKernelGGL(k_fold_direct<5>, grid, block, 0, st, a);
-  } else {
-    if (pr.start) hipExtLaunchKernelGGL(k_fold_direct<4>, grid, block, 0, st, pr.start, pr.stop, 0, a);
-    else hipLaunchKernelGGL(k_fold_direct<4>, grid, block, 0, st, a);
-  }
-  return hipGetLastError();
+  return launch(best == 5 ? k_fold_direct<5> : k_fold_direct<4>, grid, block, 0, st, pr, a);
 }
 
 // The same product for a NARROW result (the batched x-projection of a wide-input layer at few frames: 80 x 3200 over K = 512): one
@@ -754,21 +744,12 @@ hipError_t launch_skinny_nn(int M, int N, int K, const float *A, int lda, const 
     const int mi = (M + 15) / 16;
     const dim3 grid(((N + 63) / 64) * a.nks), block(256);
     const size_t shm = (size_t)4 * 16 * mi * 64 * sizeof(float);
-#define SK16_GO(MI_) do { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_skinny_nn16<MI_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
-                          hipLaunchKernelGGL((k_skinny_nn16<MI_>), grid, block, shm, st, a, a, (int)grid.x); } while (0)
-    switch (mi) {
-      case 1: SK16_GO(1); break;
-      case 2: SK16_GO(2); break;
-      case 3: SK16_GO(3); break;
-      case 4: SK16_GO(4); break;
-      case 5: SK16_GO(5); break;
-      default: return hipErrorInvalidValue;
-    }
-#undef SK16_GO
-    hipError_t err = hipGetLastError();
+    static void (*const kern[5])(SkinnyNnArgs, SkinnyNnArgs, int) = {k_skinny_nn16<1>, k_skinny_nn16<2>, k_skinny_nn16<3>, k_skinny_nn16<4>,
+                                                                     k_skinny_nn16<5>};
+    if (mi < 1 || mi > 5) return hipErrorInvalidValue;
+    const hipError_t err = launch(kern[mi - 1], grid, block, shm, st, LaunchProbe{}, a, a, (int)grid.x);
     if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_skinny_nn_reduce, dim3((unsigned)(((size_t)M * N / 4 + 31) / 32)), dim3(256), 0, st, a);
-    return hipGetLastError();
+    return launch(k_skinny_nn_reduce, dim3((unsigned)(((size_t)M * N / 4 + 31) / 32)), dim3(256), 0, st, LaunchProbe{}, a);
   }
   if (N % 128 != 0 || N < 128 || !skinny_nn_plan(N, K, &nks, &rem)) return hipErrorInvalidValue;
 #ifdef KLSTM_SKINNY_TIMING
@@ -780,21 +761,11 @@ hipError_t launch_skinny_nn(int M, int N, int K, const float *A, int lda, const 
   const dim3 grid((N / 128) * a.nks), block(256);
   const size_t shm = (size_t)4 * 3 * (mi * 8 / 4) * 64 * sizeof(f32x4) > (size_t)mi * 8 * 64 * sizeof(f32x4)
                          ? (size_t)4 * 3 * (mi * 8 / 4) * 64 * sizeof(f32x4) : (size_t)mi * 8 * 64 * sizeof(f32x4);
-#define SK_GO(MI_) do { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_skinny_nn<MI_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
-                        hipLaunchKernelGGL((k_skinny_nn<MI_>), grid, block, shm, st, a); } while (0)
-  switch (mi) {
-    case 1: SK_GO(1); break;
-    case 2: SK_GO(2); break;
-    case 3: SK_GO(3); break;
-    case 4: SK_GO(4); break;
-    case 5: SK_GO(5); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef SK_GO
-  hipError_t err = hipGetLastError();
+  if (mi < 1 || mi > 5) return hipErrorInvalidValue;
+  static void (*const kern[5])(SkinnyNnArgs) = {k_skinny_nn<1>, k_skinny_nn<2>, k_skinny_nn<3>, k_skinny_nn<4>, k_skinny_nn<5>};
+  const hipError_t err = launch(kern[mi - 1], grid, block, shm, st, LaunchProbe{}, a);
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(k_skinny_nn_reduce, dim3((unsigned)(((size_t)M * N / 4 + 31) / 32)), dim3(256), 0, st, a);
-  return hipGetLastError();
+  return launch(k_skinny_nn_reduce, dim3((unsigned)(((size_t)M * N / 4 + 31) / 32)), dim3(256), 0, st, LaunchProbe{}, a);
 }
 
 // Two products over the same rows of A in one launch (the tail of the folded BPTT: d_r = DGIFO[2..] W_gifo_r and in_diff =
@@ -821,19 +792,10 @@ hipError_t launch_skinny16_pair(int M, int K, const float *A1, const float *A2, 
   const int mi = (M + 15) / 16;
   const dim3 grid(nb1 + nb2), block(256);
   const size_t shm = (size_t)4 * 16 * mi * 64 * sizeof(float);
-#define SK16P_GO(MI_) do { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_skinny_nn16<MI_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
-                           if (pr.start) hipExtLaunchKernelGGL((k_skinny_nn16<MI_>), grid, block, shm, st, pr.start, pr.stop, 0, a, b, nb1); \
-                           else hipLaunchKernelGGL((k_skinny_nn16<MI_>), grid, block, shm, st, a, b, nb1); } while (0)
-  switch (mi) {
-    case 1: SK16P_GO(1); break;
-    case 2: SK16P_GO(2); break;
-    case 3: SK16P_GO(3); break;
-    case 4: SK16P_GO(4); break;
-    case 5: SK16P_GO(5); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef SK16P_GO
-  return hipGetLastError();
+  static void (*const kern[5])(SkinnyNnArgs, SkinnyNnArgs, int) = {k_skinny_nn16<1>, k_skinny_nn16<2>, k_skinny_nn16<3>, k_skinny_nn16<4>,
+                                                                   k_skinny_nn16<5>};
+  if (mi < 1 || mi > 5) return hipErrorInvalidValue;
+  return launch(kern[mi - 1], grid, block, shm, st, pr, a, b, nb1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1285,22 +1247,14 @@ bool direct_nt_supported(int M, int N, int K, const float *A, int lda, const flo
 
 hipError_t launch_direct_nt(int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *Cm, int ldc,
                             const float *bias, hipStream_t st, LaunchProbe pr) {
-#define KS_LAUNCH(MI_) do { if (pr.start) hipExtLaunchKernelGGL((k_direct_nt_ks<MI_>), grid, block, 0, st, pr.start, pr.stop, 0, a); \
-                            else hipLaunchKernelGGL((k_direct_nt_ks<MI_>), grid, block, 0, st, a); } while (0)
+  using NtKern = void (*)(DirectNtArgs);
   DirectNtArgs a{M, N, K, A, lda, B, ldb, Cm, ldc, bias, redo_counters() ? redo_counters() + REDO_NT : nullptr};
   const bool f16_ok = redo_count(REDO_NT) == 0;          // (once the range guard has fired, wide results stay on the fp32 form)
+  const int mi = (M + 15) / 16;
   if (N <= 8192 && K % (4 * 32 * FD) == 0) {                 // narrow result: K split over the four waves of a workgroup
-    const dim3 grid((N + 15) / 16), block(256);
-    switch ((M + 15) / 16) {
-      case 1: KS_LAUNCH(1); break;
-      case 2: KS_LAUNCH(2); break;
-      case 3: KS_LAUNCH(3); break;
-      case 4: KS_LAUNCH(4); break;
-      case 5: KS_LAUNCH(5); break;
-      default: return hipErrorInvalidValue;
-    }
-#undef KS_LAUNCH
-    return hipGetLastError();
+    static const NtKern kern[5] = {k_direct_nt_ks<1>, k_direct_nt_ks<2>, k_direct_nt_ks<3>, k_direct_nt_ks<4>, k_direct_nt_ks<5>};
+    if (mi < 1 || mi > 5) return hipErrorInvalidValue;
+    return launch(kern[mi - 1], dim3((N + 15) / 16), dim3(256), 0, st, pr, a);
   }
   // columns per wave (16*NI) and waves per workgroup: experiment knobs (g_nt_ni, g_nt_waves)
   const int ni = g_nt_ni, nw = g_nt_waves;
@@ -1312,63 +1266,28 @@ hipError_t launch_direct_nt(int M, int N, int K, const float *A, int lda, const 
   if (g_nt_shared == 4 && f16_ok && nt_resident_supported(M, N, K)) {   // round 6, option value 97 (A-B runs): A resident in registers, K in four quarters (one per wave)
     const int nblk = (N + 15) / 16, g4 = (nblk + 3) / 4, g5 = (nblk + 4) / 5;
     const dim3 grid(g4 <= 256 ? g4 : (g5 > 256 ? g5 : 256)), block(256);   // 4 column blocks per workgroup; 5 for some when that keeps the launch in one round
-    const int mi_ = (M + 15) / 16, ks_ = K / 128;
-    const size_t shm = (size_t)4 * 5 * mi_ * 16 * 16 * sizeof(float);
-    // (the dynamic-LDS opt-in is per device and costs the host ~10 us per call: once per (device, instance))
-    static std::mutex ra_mu;
-    static std::set<int> ra_done;
-    int ra_dev = 0;
-    (void)hipGetDevice(&ra_dev);
-#define RA_GO(MI_, KS_) do { if (shm > 64 * 1024) { std::lock_guard<std::mutex> lk(ra_mu); if (ra_done.insert(ra_dev * 64 + MI_ * 8 + KS_).second) \
-                               (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nt_resident_a16<MI_, KS_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } \
-                             if (pr.start) hipExtLaunchKernelGGL((k_nt_resident_a16<MI_, KS_>), grid, block, shm, st, pr.start, pr.stop, 0, a); \
-                             else hipLaunchKernelGGL((k_nt_resident_a16<MI_, KS_>), grid, block, shm, st, a); return hipGetLastError(); } while (0)
-#define RA_MI(MI_) do { switch (ks_) { case 1: RA_GO(MI_, 1); case 2: RA_GO(MI_, 2); case 3: RA_GO(MI_, 3); default: RA_GO(MI_, 4); } } while (0)
-    switch (mi_) {
-      case 1: RA_MI(1);
-      case 2: RA_MI(2);
-      case 3: RA_MI(3);
-      case 4: RA_MI(4);
-      default: RA_MI(5);
-    }
-#undef RA_MI
-#undef RA_GO
+    const size_t shm = (size_t)4 * 5 * mi * 16 * 16 * sizeof(float);
+    static const NtKern kern[5][4] = {{k_nt_resident_a16<1, 1>, k_nt_resident_a16<1, 2>, k_nt_resident_a16<1, 3>, k_nt_resident_a16<1, 4>},
+                                      {k_nt_resident_a16<2, 1>, k_nt_resident_a16<2, 2>, k_nt_resident_a16<2, 3>, k_nt_resident_a16<2, 4>},
+                                      {k_nt_resident_a16<3, 1>, k_nt_resident_a16<3, 2>, k_nt_resident_a16<3, 3>, k_nt_resident_a16<3, 4>},
+                                      {k_nt_resident_a16<4, 1>, k_nt_resident_a16<4, 2>, k_nt_resident_a16<4, 3>, k_nt_resident_a16<4, 4>},
+                                      {k_nt_resident_a16<5, 1>, k_nt_resident_a16<5, 2>, k_nt_resident_a16<5, 3>, k_nt_resident_a16<5, 4>}};
+    return launch(kern[mi - 1][K / 128 - 1], grid, block, shm, st, pr, a);   // (M in 1..80, K in 128..512)
   }
   if (N > 8192 && K % 256 == 0 && g_nt_shared) {
-    const int nbt = (N + 15) / 16, mi_ = (M + 15) / 16;
+    const int nbt = (N + 15) / 16;
     int wgs = (nbt + 3) / 4;
-    if ((g_nt_shared == 2 || !f16_ok) && wgs > 256 && (nbt - 1024) * mi_ <= 1024) wgs = 256;      // the blocks past 1024 go out as extra (block, row block) units
-    const dim3 grid(wgs), block(256);
-#define SA_GO(MI_) do { if (g_nt_shared != 2 && f16_ok) { if (pr.start) hipExtLaunchKernelGGL((k_nt_shared_a16<MI_>), grid, block, 0, st, pr.start, pr.stop, 0, a); \
-                                                else hipLaunchKernelGGL((k_nt_shared_a16<MI_>), grid, block, 0, st, a); } \
-                        else if (pr.start) hipExtLaunchKernelGGL((k_nt_shared_a<MI_>), grid, block, 0, st, pr.start, pr.stop, 0, a); \
-                        else hipLaunchKernelGGL((k_nt_shared_a<MI_>), grid, block, 0, st, a); } while (0)
-    switch ((M + 15) / 16) {
-      case 1: SA_GO(1); break;
-      case 2: SA_GO(2); break;
-      case 3: SA_GO(3); break;
-      case 4: SA_GO(4); break;
-      case 5: SA_GO(5); break;
-      default: return hipErrorInvalidValue;
-    }
-#undef SA_GO
-    return hipGetLastError();
+    if ((g_nt_shared == 2 || !f16_ok) && wgs > 256 && (nbt - 1024) * mi <= 1024) wgs = 256;      // the blocks past 1024 go out as extra (block, row block) units
+    static const NtKern kern[5][2] = {{k_nt_shared_a16<1>, k_nt_shared_a<1>}, {k_nt_shared_a16<2>, k_nt_shared_a<2>}, {k_nt_shared_a16<3>, k_nt_shared_a<3>},
+                                      {k_nt_shared_a16<4>, k_nt_shared_a<4>}, {k_nt_shared_a16<5>, k_nt_shared_a<5>}};
+    if (mi < 1 || mi > 5) return hipErrorInvalidValue;
+    return launch(kern[mi - 1][g_nt_shared != 2 && f16_ok ? 0 : 1], dim3(wgs), dim3(256), 0, st, pr, a);
   }
-#define NT_GO(MI_, NI_) do { if (pr.start) hipExtLaunchKernelGGL((k_direct_nt<MI_, NI_>), grid, block, 0, st, pr.start, pr.stop, 0, a); \
-                             else hipLaunchKernelGGL((k_direct_nt<MI_, NI_>), grid, block, 0, st, a); } while (0)
-#define NT_CASE(MI_)                                                                                   \
-  case MI_:                                                                                            \
-    if (ni == 1) NT_GO(MI_, 1);                                                                        \
-    else if (ni == 2) NT_GO(MI_, 2);                                                                   \
-    else NT_GO(MI_, 4);                                                                                \
-    break;
-  switch ((M + 15) / 16) {
-    NT_CASE(1) NT_CASE(2) NT_CASE(3) NT_CASE(4) NT_CASE(5)
-    default: return hipErrorInvalidValue;
-  }
-#undef NT_CASE
-#undef NT_GO
-  return hipGetLastError();
+  static const NtKern kern[5][3] = {{k_direct_nt<1, 1>, k_direct_nt<1, 2>, k_direct_nt<1, 4>}, {k_direct_nt<2, 1>, k_direct_nt<2, 2>, k_direct_nt<2, 4>},
+                                    {k_direct_nt<3, 1>, k_direct_nt<3, 2>, k_direct_nt<3, 4>}, {k_direct_nt<4, 1>, k_direct_nt<4, 2>, k_direct_nt<4, 4>},
+                                    {k_direct_nt<5, 1>, k_direct_nt<5, 2>, k_direct_nt<5, 4>}};
+  if (mi < 1 || mi > 5) return hipErrorInvalidValue;
+  return launch(kern[mi - 1][ni == 1 ? 0 : ni == 2 ? 1 : 2], grid, block, 0, st, pr, a);
 }
 
 }  // namespace klstm

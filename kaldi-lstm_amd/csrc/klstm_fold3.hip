@@ -37,8 +37,6 @@
 #include "klstm_kernels.h"
 #include "klstm_math.h"
 
-#include <hip/hip_ext.h>
-
 #include <cstring>
 #include <mutex>
 
@@ -473,15 +471,7 @@ static hipError_t launch_fold_planes(const Fold3Args &a, hipStream_t st, LaunchP
   constexpr int MI = 4, NI = 3, NBUF = 3;
   constexpr int shm = NBUF * NPL * (32 * MI + 32 * NI) * 64 > 4 * 16 * NI * (16 * MI + 4) * 4 ? NBUF * NPL * (32 * MI + 32 * NI) * 64
                                                                                               : 4 * 16 * NI * (16 * MI + 4) * 4;
-  {   // (per launch, like every other kernel here: the attribute belongs to the current DEVICE, engines may sit on several)
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fold_bf16x3<MI, NI, NBUF, false, true, NPL>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-    if (err != hipSuccess) return err;
-  }
-  const dim3 grid((a.nwg + 7) / 8 * 8), block(512);
-  if (pr.start) hipExtLaunchKernelGGL((k_fold_bf16x3<MI, NI, NBUF, false, true, NPL>), grid, block, shm, st, pr.start, pr.stop, 0, a);
-  else hipLaunchKernelGGL((k_fold_bf16x3<MI, NI, NBUF, false, true, NPL>), grid, block, shm, st, a);
-  return hipGetLastError();
+  return launch(k_fold_bf16x3<MI, NI, NBUF, false, true, NPL>, dim3((a.nwg + 7) / 8 * 8), dim3(512), shm, st, pr, a);
 }
 
 // The fold product of the bf16 operand mode: W_rm = bf16(W_gifo_r) bf16(W_r_m) with fp32 accumulation, stored as bf16 in logical-row
@@ -499,9 +489,7 @@ hipError_t launch_fold_ms(const Dims &d, const float *wr, const float *wmT, void
     s.n8[0] = apl / 8; s.n8[1] = bpl / 8;
     s.mode = 3;
     const unsigned sgrid = (unsigned)std::min<size_t>((s.n8[0] + s.n8[1] + 255) / 256, 2048);
-    if (pr_split.start) hipExtLaunchKernelGGL(k_split3, dim3(sgrid), dim3(256), 0, st, pr_split.start, pr_split.stop, 0, s);
-    else hipLaunchKernelGGL(k_split3, dim3(sgrid), dim3(256), 0, st, s);
-    hipError_t err = hipGetLastError();
+    const hipError_t err = launch(k_split3, dim3(sgrid), dim3(256), 0, st, pr_split, s);
     if (err != hipSuccess) return err;
   }
   Fold3Args a;
@@ -515,13 +503,7 @@ hipError_t launch_fold_ms(const Dims &d, const float *wr, const float *wmT, void
   a.nwg = ((4 * d.C + 32 * MI - 1) / (32 * MI)) * a.nbn;
   constexpr int stage = NBUF * 1 * (32 * MI + 32 * NI) * 64, transp = 4 * 16 * NI * (16 * MI + 4) * 4;
   constexpr int shm = stage > transp ? stage : transp;
-  auto kern = k_fold_bf16x3<MI, NI, NBUF, false, true, 1>;
-  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-  if (err != hipSuccess) return err;
-  const dim3 grid((a.nwg + 7) / 8 * 8), block(512);
-  if (pr.start) hipExtLaunchKernelGGL(kern, grid, block, shm, st, pr.start, pr.stop, 0, a);
-  else hipLaunchKernelGGL(kern, grid, block, shm, st, a);
-  return hipGetLastError();
+  return launch(k_fold_bf16x3<MI, NI, NBUF, false, true, 1>, dim3((a.nwg + 7) / 8 * 8), dim3(512), shm, st, pr, a);
 }
 
 hipError_t launch_fold_bf16x3(const Dims &d, int mode, const float *wr, const float *wmT, void *scratch, float *pk_fold[2], int nch1,
@@ -536,11 +518,9 @@ hipError_t launch_fold_bf16x3(const Dims &d, int mode, const float *wr, const fl
   s.mode = mode == 2 ? 2 : 1;
   const unsigned sgrid = (unsigned)std::min<size_t>((s.n8[0] + s.n8[1] + 255) / 256, 2048);
   if (!planes_fresh) {
-    if (pr_split.start) hipExtLaunchKernelGGL(k_split3, dim3(sgrid), dim3(256), 0, st, pr_split.start, pr_split.stop, 0, s);
-    else hipLaunchKernelGGL(k_split3, dim3(sgrid), dim3(256), 0, st, s);
+    const hipError_t err = launch(k_split3, dim3(sgrid), dim3(256), 0, st, pr_split, s);
+    if (err != hipSuccess) return err;
   }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return err;
 
   Fold3Args a;
 #ifdef KLSTM_FOLD3_TIMING

@@ -48,7 +48,6 @@
 #include "klstm_kernels.h"
 #include "klstm_persist_dev.h"
 
-#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -501,39 +500,27 @@ hipError_t launch_gemm_bf16_nt2(const Nt2Job *jobs, int njobs, const Nt2Plan &pl
   a.ws_bytes = (unsigned)(need * 4);
   a.dbg = g16_dbg;
   const dim3 grid(8 * a.cpg), block(512);
-  auto go = [&](auto kern, int lds, int hslot = -1) -> hipError_t {
-    // (per launch, like every other kernel here: the attribute belongs to the current DEVICE -- engines may sit on several -- and a
-    //  process-wide "already raised" cache would also be a data race between host threads)
-    (void)hslot;
-    {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return e;
-    }
-    if (pr.start) hipExtLaunchKernelGGL(kern, grid, block, lds, st, pr.start, pr.stop, 0, a);
-    else hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    return hipGetLastError();
-  };
   bool h = true;                                       // every product of the launch has both bf16 copies: the LDS-DMA form
   for (int q = 0; q < njobs; q++) h = h && gemm_bf16_nt2_copies_usable(jobs[q]);
   if (h && g16_dbg) {
-    if (pl.nj == 4) return go(k_gemm_bf16_nt2<4, 4, true, true>, G16Geo<4, 4>::LDSH, 11);
-    if (pl.nj == 2) return go(k_gemm_bf16_nt2<2, 6, true, true>, G16Geo<2, 6>::LDSH, 10);
-    return go(k_gemm_bf16_nt2<1, 6, true, true>, G16Geo<1, 6>::LDSH, 9);
+    if (pl.nj == 4) return launch(k_gemm_bf16_nt2<4, 4, true, true>, grid, block, G16Geo<4, 4>::LDSH, st, pr, a);
+    if (pl.nj == 2) return launch(k_gemm_bf16_nt2<2, 6, true, true>, grid, block, G16Geo<2, 6>::LDSH, st, pr, a);
+    return launch(k_gemm_bf16_nt2<1, 6, true, true>, grid, block, G16Geo<1, 6>::LDSH, st, pr, a);
   }
   if (h) {
     // stage buffers: what fits the LDS -- the DMA's issue-to-landed time (~1 us) is hidden by the stages in flight, nothing else
-    if (pl.nj == 4) return go(k_gemm_bf16_nt2<4, 4, false, true>, G16Geo<4, 4>::LDSH, 8);
-    if (pl.nj == 2) return go(k_gemm_bf16_nt2<2, 6, false, true>, G16Geo<2, 6>::LDSH, 7);
-    return go(k_gemm_bf16_nt2<1, 6, false, true>, G16Geo<1, 6>::LDSH, 6);
+    if (pl.nj == 4) return launch(k_gemm_bf16_nt2<4, 4, false, true>, grid, block, G16Geo<4, 4>::LDSH, st, pr, a);
+    if (pl.nj == 2) return launch(k_gemm_bf16_nt2<2, 6, false, true>, grid, block, G16Geo<2, 6>::LDSH, st, pr, a);
+    return launch(k_gemm_bf16_nt2<1, 6, false, true>, grid, block, G16Geo<1, 6>::LDSH, st, pr, a);
   }
   if (g16_dbg) {
-    if (pl.nj == 4) return go(k_gemm_bf16_nt2<4, 2, true>, G16Geo<4, 2>::LDS);
-    if (pl.nj == 2) return go(k_gemm_bf16_nt2<2, 2, true>, G16Geo<2, 2>::LDS);
-    return go(k_gemm_bf16_nt2<1, 2, true>, G16Geo<1, 2>::LDS);
+    if (pl.nj == 4) return launch(k_gemm_bf16_nt2<4, 2, true>, grid, block, G16Geo<4, 2>::LDS, st, pr, a);
+    if (pl.nj == 2) return launch(k_gemm_bf16_nt2<2, 2, true>, grid, block, G16Geo<2, 2>::LDS, st, pr, a);
+    return launch(k_gemm_bf16_nt2<1, 2, true>, grid, block, G16Geo<1, 2>::LDS, st, pr, a);
   }
-  if (pl.nj == 4) return go(k_gemm_bf16_nt2<4, 2>, G16Geo<4, 2>::LDS);
-  if (pl.nj == 2) return go(k_gemm_bf16_nt2<2, 2>, G16Geo<2, 2>::LDS);
-  return go(k_gemm_bf16_nt2<1, 2>, G16Geo<1, 2>::LDS);
+  if (pl.nj == 4) return launch(k_gemm_bf16_nt2<4, 2>, grid, block, G16Geo<4, 2>::LDS, st, pr, a);
+  if (pl.nj == 2) return launch(k_gemm_bf16_nt2<2, 2>, grid, block, G16Geo<2, 2>::LDS, st, pr, a);
+  return launch(k_gemm_bf16_nt2<1, 2>, grid, block, G16Geo<1, 2>::LDS, st, pr, a);
 }
 
 }  // namespace klstm

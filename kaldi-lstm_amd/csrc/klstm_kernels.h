@@ -2,6 +2,10 @@
 // Every launcher enqueues on `st` and returns the hipError_t of the launch.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+#include <map>
+#include <mutex>
+#include <utility>
 
 namespace klstm {
 
@@ -46,6 +50,34 @@ struct BwdPtrs {
 
 // optional per-launch timing through hipExtLaunchKernelGGL start/stop events
 struct LaunchProbe { hipEvent_t start = nullptr, stop = nullptr; };
+
+// Every kernel launch of the library goes through launch().  A launch that asks for more than the default 64 KiB of dynamic LDS first
+// raises the limit of (current device, kernel) to shm -- only when that pair has not been raised that far yet, under one lock: the
+// attribute call costs the host microseconds -- and returns that call's error without launching if it fails.  A probe with events
+// times the launch.  Returns hipGetLastError() after the launch.
+inline hipError_t raise_lds_limit(const void *kern, size_t shm) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void *>, size_t> raised;
+  int dev = 0;
+  hipError_t err = hipGetDevice(&dev);
+  if (err != hipSuccess) return err;
+  std::lock_guard<std::mutex> lk(mu);
+  size_t &lim = raised[{dev, kern}];
+  if (lim >= shm) return hipSuccess;
+  err = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+  if (err == hipSuccess) lim = shm;
+  return err;
+}
+template <class K, class... A>
+hipError_t launch(K kern, dim3 grid, dim3 block, size_t shm, hipStream_t st, LaunchProbe pr, A... args) {
+  if (shm > 64 * 1024) {
+    const hipError_t err = raise_lds_limit(reinterpret_cast<const void *>(kern), shm);
+    if (err != hipSuccess) return err;
+  }
+  if (pr.start) hipExtLaunchKernelGGL(kern, grid, block, shm, st, pr.start, pr.stop, 0, args...);
+  else hipLaunchKernelGGL(kern, grid, block, shm, st, args...);
+  return hipGetLastError();
+}
 
 // Range guard of the fp16-plane products (klstm_math.h nonfinite_probe): a wave whose accumulators came out non-finite -- an operand
 // beyond the fp16 range -- recomputes its outputs in plain fp32 and counts the event in a host-mapped word (pinned, portable; readable

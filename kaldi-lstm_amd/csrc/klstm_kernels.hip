@@ -30,7 +30,6 @@
 #include "klstm_math.h"
 #include "klstm_persist_dev.h"
 
-#include <hip/hip_ext.h>
 #include <stdint.h>
 
 namespace klstm {
@@ -2985,13 +2984,6 @@ __global__ void k_apply_momentum(float *__restrict__ corr, const float *__restri
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-#define KLAUNCH(kern, grid, block, st, pr, ...)                                               \
-  do {                                                                                        \
-    if ((pr).start) hipExtLaunchKernelGGL(kern, grid, block, 0, st, (pr).start, (pr).stop, 0, __VA_ARGS__); \
-    else hipLaunchKernelGGL(kern, grid, block, 0, st, __VA_ARGS__);                           \
-    return hipGetLastError();                                                                 \
-  } while (0)
-
 // ---- variant selection -------------------------------------------------------------------------
 // generic kernels (any shape): 16 x 16*NT stream tiles, NT in {1,2,4,8}
 static inline int pick_nt(int S) {
@@ -3001,10 +2993,10 @@ static inline int pick_nt(int S) {
 #define GEN_DISPATCH(KERN, nt, grid, st, pr, args, ...)                                           \
   do {                                                                                            \
     const dim3 _blk(NW * 64);                                                                     \
-    if (nt == 1) KLAUNCH((KERN<1 __VA_ARGS__>), grid, _blk, st, pr, args);                        \
-    if (nt == 2) KLAUNCH((KERN<2 __VA_ARGS__>), grid, _blk, st, pr, args);                        \
-    if (nt == 4) KLAUNCH((KERN<4 __VA_ARGS__>), grid, _blk, st, pr, args);                        \
-    KLAUNCH((KERN<8 __VA_ARGS__>), grid, _blk, st, pr, args);                                     \
+    if (nt == 1) return launch((KERN<1 __VA_ARGS__>), grid, _blk, 0, st, pr, args);               \
+    if (nt == 2) return launch((KERN<2 __VA_ARGS__>), grid, _blk, 0, st, pr, args);               \
+    if (nt == 4) return launch((KERN<4 __VA_ARGS__>), grid, _blk, 0, st, pr, args);               \
+    return launch((KERN<8 __VA_ARGS__>), grid, _blk, 0, st, pr, args);                            \
   } while (0)
 // vector kernels: SMALL (4x4x1_16b, S <= 4) with CPW in {1,2,4};  16x16x4 with (NT,CPW) in {(1,1),(1,2),(2,1),(4,1)}
 struct VecCfg { bool small; int nt, cpw; };
@@ -3032,19 +3024,19 @@ static inline VecCfg pick_vec(int S, int nch, bool gates = false) {
   do {                                                                                            \
     const dim3 _blk(NW * 64);                                                                     \
     if (cfg.small && cfg.nt == 2) {                                                               \
-      if (cfg.cpw == 1) KLAUNCH((KERN<2, 1, true __VA_ARGS__>), grid, _blk, st, pr, args);        \
-      if (cfg.cpw == 2) KLAUNCH((KERN<2, 2, true __VA_ARGS__>), grid, _blk, st, pr, args);        \
-      KLAUNCH((KERN<2, 4, true __VA_ARGS__>), grid, _blk, st, pr, args);                          \
+      if (cfg.cpw == 1) return launch((KERN<2, 1, true __VA_ARGS__>), grid, _blk, 0, st, pr, args); \
+      if (cfg.cpw == 2) return launch((KERN<2, 2, true __VA_ARGS__>), grid, _blk, 0, st, pr, args); \
+      return launch((KERN<2, 4, true __VA_ARGS__>), grid, _blk, 0, st, pr, args);                 \
     }                                                                                             \
     if (cfg.small) {                                                                              \
-      if (cfg.cpw == 1) KLAUNCH((KERN<1, 1, true __VA_ARGS__>), grid, _blk, st, pr, args);        \
-      if (cfg.cpw == 2) KLAUNCH((KERN<1, 2, true __VA_ARGS__>), grid, _blk, st, pr, args);        \
-      KLAUNCH((KERN<1, 4, true __VA_ARGS__>), grid, _blk, st, pr, args);                          \
+      if (cfg.cpw == 1) return launch((KERN<1, 1, true __VA_ARGS__>), grid, _blk, 0, st, pr, args); \
+      if (cfg.cpw == 2) return launch((KERN<1, 2, true __VA_ARGS__>), grid, _blk, 0, st, pr, args); \
+      return launch((KERN<1, 4, true __VA_ARGS__>), grid, _blk, 0, st, pr, args);                 \
     }                                                                                             \
-    if (cfg.nt == 1 && cfg.cpw == 1) KLAUNCH((KERN<1, 1, false __VA_ARGS__>), grid, _blk, st, pr, args); \
-    if (cfg.nt == 1) KLAUNCH((KERN<1, 2, false __VA_ARGS__>), grid, _blk, st, pr, args);          \
-    if (cfg.nt == 2) KLAUNCH((KERN<2, 1, false __VA_ARGS__>), grid, _blk, st, pr, args);          \
-    KLAUNCH((KERN<4, 1, false __VA_ARGS__>), grid, _blk, st, pr, args);                           \
+    if (cfg.nt == 1 && cfg.cpw == 1) return launch((KERN<1, 1, false __VA_ARGS__>), grid, _blk, 0, st, pr, args); \
+    if (cfg.nt == 1) return launch((KERN<1, 2, false __VA_ARGS__>), grid, _blk, 0, st, pr, args); \
+    if (cfg.nt == 2) return launch((KERN<2, 1, false __VA_ARGS__>), grid, _blk, 0, st, pr, args); \
+    return launch((KERN<4, 1, false __VA_ARGS__>), grid, _blk, 0, st, pr, args);                  \
   } while (0)
 #define COMMA ,
 static inline dim3 vec_grid(int ntiles, int S, const VecCfg &c, int z = 1) {
@@ -3081,29 +3073,29 @@ hipError_t launch_gates_step(const Dims &d0, const FwdPtrs &p, int t, bool fuse_
         const dim3 fg(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
         const bool bigf = (fuse_x ? cdiv(d.R, KCH) + cdiv(d.I, KCH) : cdiv(d.R, KCH)) > 16;
         if (p.bf16) {
-          if (fuse_x && bigf) KLAUNCH((k_gates_f<2, 4, 32, true, true>), fg, dim3(NW * 64), st, pr, va);
-          if (fuse_x) KLAUNCH((k_gates_f<2, 4, 16, true, true>), fg, dim3(NW * 64), st, pr, va);
-          if (bigf) KLAUNCH((k_gates_f<2, 4, 32, false, true>), fg, dim3(NW * 64), st, pr, va);
-          KLAUNCH((k_gates_f<2, 4, 16, false, true>), fg, dim3(NW * 64), st, pr, va);
+          if (fuse_x && bigf) return launch((k_gates_f<2, 4, 32, true, true>), fg, dim3(NW * 64), 0, st, pr, va);
+          if (fuse_x) return launch((k_gates_f<2, 4, 16, true, true>), fg, dim3(NW * 64), 0, st, pr, va);
+          if (bigf) return launch((k_gates_f<2, 4, 32, false, true>), fg, dim3(NW * 64), 0, st, pr, va);
+          return launch((k_gates_f<2, 4, 16, false, true>), fg, dim3(NW * 64), 0, st, pr, va);
         }
-        if (fuse_x && bigf) KLAUNCH((k_gates_f<2, 4, 32, true, false>), fg, dim3(NW * 64), st, pr, va);
-        if (fuse_x) KLAUNCH((k_gates_f<2, 4, 16, true, false>), fg, dim3(NW * 64), st, pr, va);
-        if (bigf) KLAUNCH((k_gates_f<2, 4, 32, false, false>), fg, dim3(NW * 64), st, pr, va);
-        KLAUNCH((k_gates_f<2, 4, 16, false, false>), fg, dim3(NW * 64), st, pr, va);
+        if (fuse_x && bigf) return launch((k_gates_f<2, 4, 32, true, false>), fg, dim3(NW * 64), 0, st, pr, va);
+        if (fuse_x) return launch((k_gates_f<2, 4, 16, true, false>), fg, dim3(NW * 64), 0, st, pr, va);
+        if (bigf) return launch((k_gates_f<2, 4, 32, false, false>), fg, dim3(NW * 64), 0, st, pr, va);
+        return launch((k_gates_f<2, 4, 16, false, false>), fg, dim3(NW * 64), 0, st, pr, va);
       }
       va.gx = cdiv(d.C, 16);
       const dim3 fgrid(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
       const bool big = (fuse_x ? cdiv(d.R, KCH) + cdiv(d.I, KCH) : cdiv(d.R, KCH)) > 16;
       if (p.bf16) {
-        if (fuse_x && big) KLAUNCH((k_gates_f<4, 2, 32, true, true>), fgrid, dim3(NW * 64), st, pr, va);
-        if (fuse_x) KLAUNCH((k_gates_f<4, 2, 16, true, true>), fgrid, dim3(NW * 64), st, pr, va);
-        if (big) KLAUNCH((k_gates_f<4, 2, 32, false, true>), fgrid, dim3(NW * 64), st, pr, va);
-        KLAUNCH((k_gates_f<4, 2, 16, false, true>), fgrid, dim3(NW * 64), st, pr, va);
+        if (fuse_x && big) return launch((k_gates_f<4, 2, 32, true, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
+        if (fuse_x) return launch((k_gates_f<4, 2, 16, true, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
+        if (big) return launch((k_gates_f<4, 2, 32, false, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
+        return launch((k_gates_f<4, 2, 16, false, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
       }
-      if (fuse_x && big) KLAUNCH((k_gates_f<4, 2, 32, true, false>), fgrid, dim3(NW * 64), st, pr, va);
-      if (fuse_x) KLAUNCH((k_gates_f<4, 2, 16, true, false>), fgrid, dim3(NW * 64), st, pr, va);
-      if (big) KLAUNCH((k_gates_f<4, 2, 32, false, false>), fgrid, dim3(NW * 64), st, pr, va);
-      KLAUNCH((k_gates_f<4, 2, 16, false, false>), fgrid, dim3(NW * 64), st, pr, va);
+      if (fuse_x && big) return launch((k_gates_f<4, 2, 32, true, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
+      if (fuse_x) return launch((k_gates_f<4, 2, 16, true, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
+      if (big) return launch((k_gates_f<4, 2, 32, false, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
+      return launch((k_gates_f<4, 2, 16, false, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
     }
     const VecCfg cfg = pick_vec(d.S, cdiv(d.R, KCH) + (fuse_x ? cdiv(d.I, KCH) : 0), true);
     const dim3 grid = vec_grid(cdiv(d.C, 4), d.S, cfg);
@@ -3135,20 +3127,20 @@ hipError_t launch_proj_step(const Dims &d, const FwdPtrs &p, int t, float *out, 
         va.gx = cdiv(d.R, 16);
         const dim3 fg(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
         if (p.bf16) {
-          if (cdiv(d.C, KCH) > 16) KLAUNCH((k_proj_f<1, 8, 32, true>), fg, dim3(NW * 64), st, pr, va);
-          KLAUNCH((k_proj_f<1, 8, 16, true>), fg, dim3(NW * 64), st, pr, va);
+          if (cdiv(d.C, KCH) > 16) return launch((k_proj_f<1, 8, 32, true>), fg, dim3(NW * 64), 0, st, pr, va);
+          return launch((k_proj_f<1, 8, 16, true>), fg, dim3(NW * 64), 0, st, pr, va);
         }
-        if (cdiv(d.C, KCH) > 16) KLAUNCH((k_proj_f<1, 8, 32, false>), fg, dim3(NW * 64), st, pr, va);
-        KLAUNCH((k_proj_f<1, 8, 16, false>), fg, dim3(NW * 64), st, pr, va);
+        if (cdiv(d.C, KCH) > 16) return launch((k_proj_f<1, 8, 32, false>), fg, dim3(NW * 64), 0, st, pr, va);
+        return launch((k_proj_f<1, 8, 16, false>), fg, dim3(NW * 64), 0, st, pr, va);
       }
       va.gx = cdiv(d.R, 32);
       const dim3 fgrid(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
       if (p.bf16) {
-        if (cdiv(d.C, KCH) > 16) KLAUNCH((k_proj_f<2, 4, 32, true>), fgrid, dim3(NW * 64), st, pr, va);
-        KLAUNCH((k_proj_f<2, 4, 16, true>), fgrid, dim3(NW * 64), st, pr, va);
+        if (cdiv(d.C, KCH) > 16) return launch((k_proj_f<2, 4, 32, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
+        return launch((k_proj_f<2, 4, 16, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
       }
-      if (cdiv(d.C, KCH) > 16) KLAUNCH((k_proj_f<2, 4, 32, false>), fgrid, dim3(NW * 64), st, pr, va);
-      KLAUNCH((k_proj_f<2, 4, 16, false>), fgrid, dim3(NW * 64), st, pr, va);
+      if (cdiv(d.C, KCH) > 16) return launch((k_proj_f<2, 4, 32, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
+      return launch((k_proj_f<2, 4, 16, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
     }
     const VecCfg cfg = pick_vec(d.S, cdiv(d.C, KCH));
     if (p.bf16) VEC_DISPATCH(k_proj_v, cfg, vec_grid(cdiv(d.R, 16), d.S, cfg), st, pr, va, COMMA true);
@@ -3199,11 +3191,11 @@ hipError_t launch_dr_step(const Dims &d, const BwdPtrs &p, int t, float *in_diff
         va.g.ntr = t == 0 ? 0 : cdiv(d.R, 16);
         va.gx = va.g.ntr + (in_diff ? cdiv(d.I, 16) : 0);
         const int gxf = cdiv(va.gx, 8) * 8;
-        if (p.bf16) KLAUNCH((k_dr_f<1, 8, 16, true>), dim3(gxf, cdiv(d.S, FST), ks), dim3(NW * 64), st, pr, va);
-        KLAUNCH((k_dr_f<1, 8, 16, false>), dim3(gxf, cdiv(d.S, FST), ks), dim3(NW * 64), st, pr, va);
+        if (p.bf16) return launch((k_dr_f<1, 8, 16, true>), dim3(gxf, cdiv(d.S, FST), ks), dim3(NW * 64), 0, st, pr, va);
+        return launch((k_dr_f<1, 8, 16, false>), dim3(gxf, cdiv(d.S, FST), ks), dim3(NW * 64), 0, st, pr, va);
       }
-      if (p.bf16) KLAUNCH((k_dr_f<2, 4, 16, true>), dim3(gx, cdiv(d.S, FST), ks), dim3(NW * 64), st, pr, va);
-      KLAUNCH((k_dr_f<2, 4, 16, false>), dim3(gx, cdiv(d.S, FST), ks), dim3(NW * 64), st, pr, va);
+      if (p.bf16) return launch((k_dr_f<2, 4, 16, true>), dim3(gx, cdiv(d.S, FST), ks), dim3(NW * 64), 0, st, pr, va);
+      return launch((k_dr_f<2, 4, 16, false>), dim3(gx, cdiv(d.S, FST), ks), dim3(NW * 64), 0, st, pr, va);
     }
     const VecCfg cfg = pick_vec(d.S, cdiv(a.klen, KCH));
     if (p.bf16) VEC_DISPATCH(k_dr_v, cfg, vec_grid(a.ntr + ntx, d.S, cfg, ks), st, pr, va, COMMA true);
@@ -3237,20 +3229,20 @@ hipError_t launch_dm_step(const Dims &d, const BwdPtrs &p, int t, const float *o
         va.gx = cdiv(d.C, 16);
         const dim3 fg(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
         if (p.bf16) {
-          if (cdiv(d.R, KCH) > 16) KLAUNCH((k_dm_f<1, 8, 32, true>), fg, dim3(NW * 64), st, pr, va);
-          KLAUNCH((k_dm_f<1, 8, 16, true>), fg, dim3(NW * 64), st, pr, va);
+          if (cdiv(d.R, KCH) > 16) return launch((k_dm_f<1, 8, 32, true>), fg, dim3(NW * 64), 0, st, pr, va);
+          return launch((k_dm_f<1, 8, 16, true>), fg, dim3(NW * 64), 0, st, pr, va);
         }
-        if (cdiv(d.R, KCH) > 16) KLAUNCH((k_dm_f<1, 8, 32, false>), fg, dim3(NW * 64), st, pr, va);
-        KLAUNCH((k_dm_f<1, 8, 16, false>), fg, dim3(NW * 64), st, pr, va);
+        if (cdiv(d.R, KCH) > 16) return launch((k_dm_f<1, 8, 32, false>), fg, dim3(NW * 64), 0, st, pr, va);
+        return launch((k_dm_f<1, 8, 16, false>), fg, dim3(NW * 64), 0, st, pr, va);
       }
       va.gx = cdiv(d.C, 32);
       const dim3 fgrid(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
       if (p.bf16) {
-        if (cdiv(d.R, KCH) > 16) KLAUNCH((k_dm_f<2, 4, 32, true>), fgrid, dim3(NW * 64), st, pr, va);
-        KLAUNCH((k_dm_f<2, 4, 16, true>), fgrid, dim3(NW * 64), st, pr, va);
+        if (cdiv(d.R, KCH) > 16) return launch((k_dm_f<2, 4, 32, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
+        return launch((k_dm_f<2, 4, 16, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
       }
-      if (cdiv(d.R, KCH) > 16) KLAUNCH((k_dm_f<2, 4, 32, false>), fgrid, dim3(NW * 64), st, pr, va);
-      KLAUNCH((k_dm_f<2, 4, 16, false>), fgrid, dim3(NW * 64), st, pr, va);
+      if (cdiv(d.R, KCH) > 16) return launch((k_dm_f<2, 4, 32, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
+      return launch((k_dm_f<2, 4, 16, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
     }
     const VecCfg cfg = pick_vec(d.S, cdiv(d.R, KCH));
     if (p.bf16) VEC_DISPATCH(k_dm_v, cfg, vec_grid(cdiv(d.C, 16), d.S, cfg), st, pr, va, COMMA true);
@@ -3275,14 +3267,14 @@ hipError_t launch_dmf_step(const Dims &d, const BwdPtrs &p, int t, const float *
   const int need = cdiv(a.nch_total, NW);
   if (d.S > 4) {                               // two stream groups per workgroup share the weight fetch
     const dim3 grid(cdiv(d.C, 4), cdiv(d.S, 8));
-    if (need <= 1) KLAUNCH((k_dmf_v<1, 2>), grid, blk, st, pr, a);
-    if (need == 2) KLAUNCH((k_dmf_v<2, 2>), grid, blk, st, pr, a);
-    KLAUNCH((k_dmf_v<4, 2>), grid, blk, st, pr, a);
+    if (need <= 1) return launch((k_dmf_v<1, 2>), grid, blk, 0, st, pr, a);
+    if (need == 2) return launch((k_dmf_v<2, 2>), grid, blk, 0, st, pr, a);
+    return launch((k_dmf_v<4, 2>), grid, blk, 0, st, pr, a);
   }
   const dim3 grid(cdiv(d.C, 4), cdiv(d.S, 4));
-  if (need <= 1) KLAUNCH((k_dmf_v<1, 1>), grid, blk, st, pr, a);
-  if (need == 2) KLAUNCH((k_dmf_v<2, 1>), grid, blk, st, pr, a);
-  KLAUNCH((k_dmf_v<4, 1>), grid, blk, st, pr, a);
+  if (need <= 1) return launch((k_dmf_v<1, 1>), grid, blk, 0, st, pr, a);
+  if (need == 2) return launch((k_dmf_v<2, 1>), grid, blk, 0, st, pr, a);
+  return launch((k_dmf_v<4, 1>), grid, blk, 0, st, pr, a);
 }
 
 // x chunks of the folded gates array (the W_rm chunks are written by the fold product itself)
@@ -3316,12 +3308,12 @@ hipError_t launch_fold(const Dims &d, const float *param_blob, const float *wmT,
     if (scratch3 && fold_bf16x3_supported(d, mode3))
       return launch_fold_bf16x3(d, mode3, param_blob + o_wr, wmT, scratch3, pk_fold, g.nch1, g.nch2, st, pr3, pr, planes_fresh);   // klstm_fold3.hip
     if (fold_direct_supported(d)) return launch_fold_direct(d, param_blob + o_wr, wmT, pk_fold, g.nch1, g.nch2, st, pr);   // klstm_fold.hip
-    KLAUNCH((k_gemm<false, true>), grid, block, st, pr, g);
+    return launch((k_gemm<false, true>), grid, block, 0, st, pr, g);
   };
   hipError_t err = first();
   if (err != hipSuccess || !pack_x) return err;
   const long nx = (long)cdiv(d.C, 4) * cdiv(d.I, KCH) * 128;
-  KLAUNCH(k_pack_foldx, dim3((unsigned)cdiv((int)nx, 256)), block, st, pr2, param_blob, g.pk1, d.C, d.I, g.nch1);
+  return launch(k_pack_foldx, dim3((unsigned)cdiv((int)nx, 256)), block, 0, st, pr2, param_blob, g.pk1, d.C, d.I, g.nch1);
 }
 
 // r(1..T) = m(1..T) W_r_m^T (:312) for all frames at once -> rr rows, out rows (:328), last block -> prev_r (:331)
@@ -3339,7 +3331,7 @@ hipError_t launch_rbatch(const Dims &d, const FwdPtrs &p, float *out, int out_st
   g.C3 = p.next_r; g.tail0 = M - d.S;
   g.guard = guard;
   const dim3 grid(cdiv(cdiv(d.R, GT) * cdiv(M, GT), 8) * 8), block(256);
-  KLAUNCH((k_gemm<false, true>), grid, block, st, pr, g);
+  return launch((k_gemm<false, true>), grid, block, 0, st, pr, g);
 }
 
 bool pack_supported(const Dims &d) { return d.R % 8 == 0 && d.I % 8 == 0 && d.C % 8 == 0; }
@@ -3371,7 +3363,7 @@ hipError_t launch_pack(const Dims &d, const float *param_blob, const float *wrT,
   for (int i = 0; i < 4; i++) { a.pk[i] = reinterpret_cast<float4 *>(pk[i]); total += a.n4[i]; }
   if (total == 0) return hipSuccess;
   const long nb = (total + 255) / 256;
-  KLAUNCH(k_pack, dim3((unsigned)(nb > 4096 ? 4096 : nb)), dim3(256), st, pr, a);
+  return launch(k_pack, dim3((unsigned)(nb > 4096 ? 4096 : nb)), dim3(256), 0, st, pr, a);
 }
 
 static GemmJob make_job(bool transA, bool transB, int M, int N, int K, const float *A, int lda, const float *B,
@@ -3393,10 +3385,10 @@ hipError_t launch_gemm(bool transA, bool transB, int M, int N, int K, const floa
                        hipStream_t st, LaunchProbe pr) {
   const GemmJob g = make_job(transA, transB, M, N, K, A, lda, B, ldb, beta, Cm, ldc, bias);
   const dim3 grid(cdiv(cdiv(N, GT) * cdiv(M, GT), 8) * 8), block(256);
-  if (transA && transB) KLAUNCH((k_gemm<true, true>), grid, block, st, pr, g);
-  if (transA && !transB) KLAUNCH((k_gemm<true, false>), grid, block, st, pr, g);
-  if (!transA && transB) KLAUNCH((k_gemm<false, true>), grid, block, st, pr, g);
-  KLAUNCH((k_gemm<false, false>), grid, block, st, pr, g);
+  if (transA && transB) return launch((k_gemm<true, true>), grid, block, 0, st, pr, g);
+  if (transA && !transB) return launch((k_gemm<true, false>), grid, block, 0, st, pr, g);
+  if (!transA && transB) return launch((k_gemm<false, true>), grid, block, 0, st, pr, g);
+  return launch((k_gemm<false, false>), grid, block, 0, st, pr, g);
 }
 
 // C = A B^T + bias with both operands rounded to bf16 (bf16 operand mode; M >= GRADS_BF16_MIN_ROWS rows, K >= 128 -- at K = 40 the
@@ -3410,10 +3402,10 @@ hipError_t launch_gemm_bf16_nt_splitk(int M, int N, int K, const float *A, int l
   auto first = [&]() -> hipError_t {
     if (N % 32 == 0) {                                // (128 x 32 tiles: more workgroups per CU to cover the load latency of a K tile)
       const int nt1 = cdiv(M, BT) * cdiv(N, BT / 4);
-      KLAUNCH(k_gemm_bf16_nt<1>, dim3(cdiv(nt1, 8) * 8, ks), dim3(256), st, pr, g);
+      return launch(k_gemm_bf16_nt<1>, dim3(cdiv(nt1, 8) * 8, ks), dim3(256), 0, st, pr, g);
     }
     const int ntm = cdiv(M, BT), ntn = cdiv(N, BT / 2), nt = ntm * ntn;
-    KLAUNCH(k_gemm_bf16_nt<2>, dim3(cdiv(nt, 8) * 8, ks), dim3(256), st, pr, g);
+    return launch(k_gemm_bf16_nt<2>, dim3(cdiv(nt, 8) * 8, ks), dim3(256), 0, st, pr, g);
   };
   hipError_t err = first();
   if (err != hipSuccess) return err;
@@ -3421,7 +3413,7 @@ hipError_t launch_gemm_bf16_nt_splitk(int M, int N, int K, const float *A, int l
   r.ws = ws; r.ks = ks; r.M = M; r.N = N; r.beta = beta; r.Cm = Cm; r.ldc = ldc; r.bias = nullptr; r.add = add; r.add_ld = add_ld;
   r.C2 = nullptr; r.ldc2 = 0; r.C3 = nullptr; r.tail0 = 0;
   const long nb = ((long)M * N + 255) / 256;
-  KLAUNCH(k_splitk_reduce, dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(256), st, pr2, r);
+  return launch(k_splitk_reduce, dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(256), 0, st, pr2, r);
 }
 bool gemm_bf16_nt_supported(int M, int K, const float *A, int lda, const float *B, int ldb) {
   return M >= GRADS_BF16_MIN_ROWS && K >= 128 && K % 8 == 0 && lda % 4 == 0 && ldb % 4 == 0 && aligned16(A) && aligned16(B);
@@ -3433,14 +3425,14 @@ hipError_t launch_gemm_bf16_nt(int M, int N, int K, const float *A, int lda, con
   const dim3 block(256);
   if (cdiv(N, BT / 2) * cdiv(M, BT) < 512 && N % 32 == 0) {   // few 128 x 64 tiles too: 128 x 32 -- every K tile of 64 exposes a memory latency, more
     const dim3 grid(cdiv(cdiv(N, BT / 4) * cdiv(M, BT), 8) * 8);   // workgroups per CU cover it (640 x 1024 over K = 512: 15.9 -> 11 us; 640 x 4096: no change)
-    KLAUNCH(k_gemm_bf16_nt<1>, grid, block, st, pr, g);
+    return launch(k_gemm_bf16_nt<1>, grid, block, 0, st, pr, g);
   }
   if (cdiv(N, BT) * cdiv(M, BT) < 384) {             // few 128 x 128 tiles (640 x 4096: 160 on 256 CUs): 128 x 64
     const dim3 grid(cdiv(cdiv(N, BT / 2) * cdiv(M, BT), 8) * 8);
-    KLAUNCH(k_gemm_bf16_nt<2>, grid, block, st, pr, g);
+    return launch(k_gemm_bf16_nt<2>, grid, block, 0, st, pr, g);
   }
   const dim3 grid(cdiv(cdiv(N, BT) * cdiv(M, BT), 8) * 8);
-  KLAUNCH(k_gemm_bf16_nt<4>, grid, block, st, pr, g);
+  return launch(k_gemm_bf16_nt<4>, grid, block, 0, st, pr, g);
 }
 
 // Cm = beta*Cm + A^T B (gradient of a weight matrix, K = frames), then P -= lr*Cm in the same pass (GemmJob::P):
@@ -3451,7 +3443,7 @@ hipError_t launch_gemm_tn_update(int M, int N, int K, const float *A, int lda, c
   GemmJob g = make_job(true, false, M, N, K, A, lda, B, ldb, beta, Cm, ldc, nullptr);
   g.P = P; g.lr = lr; g.clip = 0.f;
   const dim3 grid(cdiv(cdiv(N, GT) * cdiv(M, GT), 8) * 8), block(256);
-  KLAUNCH((k_gemm<true, false>), grid, block, st, pr, g);
+  return launch((k_gemm<true, false>), grid, block, 0, st, pr, g);
 }
 
 // Cm = beta*Cm + A^T B through the coalesced epilogue (N, ldc % 4 == 0, 16-byte aligned Cm)
@@ -3460,7 +3452,7 @@ hipError_t launch_gemm_tn_coal(int M, int N, int K, const float *A, int lda, con
   GemmJob g = make_job(true, false, M, N, K, A, lda, B, ldb, beta, Cm, ldc, nullptr);
   g.coal = 1;
   const dim3 grid(cdiv(cdiv(N, GT) * cdiv(M, GT), 8) * 8), block(256);
-  KLAUNCH((k_gemm<true, false>), grid, block, st, pr, g);
+  return launch((k_gemm<true, false>), grid, block, 0, st, pr, g);
 }
 
 // Split-K plan: worth it when the output tiles cover less than half the chip and K is long.
@@ -3479,10 +3471,10 @@ hipError_t launch_gemm_splitk(bool transA, bool transB, int M, int N, int K, con
   const GemmJob g = make_job(transA, transB, M, N, K, A, lda, B, ldb, 0.f, nullptr, N, nullptr);
   const dim3 grid(cdiv(N, GT), cdiv(M, GT), ks), block(256);
   auto first = [&]() -> hipError_t {
-    if (transA && transB) KLAUNCH((k_gemm_splitk<true, true>), grid, block, st, pr, g, klen, ws);
-    if (transA) KLAUNCH((k_gemm_splitk<true, false>), grid, block, st, pr, g, klen, ws);
-    if (transB) KLAUNCH((k_gemm_splitk<false, true>), grid, block, st, pr, g, klen, ws);
-    KLAUNCH((k_gemm_splitk<false, false>), grid, block, st, pr, g, klen, ws);
+    if (transA && transB) return launch((k_gemm_splitk<true, true>), grid, block, 0, st, pr, g, klen, ws);
+    if (transA) return launch((k_gemm_splitk<true, false>), grid, block, 0, st, pr, g, klen, ws);
+    if (transB) return launch((k_gemm_splitk<false, true>), grid, block, 0, st, pr, g, klen, ws);
+    return launch((k_gemm_splitk<false, false>), grid, block, 0, st, pr, g, klen, ws);
   };
   hipError_t err = first();
   if (err != hipSuccess) return err;
@@ -3490,7 +3482,7 @@ hipError_t launch_gemm_splitk(bool transA, bool transB, int M, int N, int K, con
   r.ws = ws; r.ks = ks; r.M = M; r.N = N; r.beta = beta; r.Cm = Cm; r.ldc = ldc; r.bias = bias; r.add = add; r.add_ld = add_ld;
   r.C2 = C2; r.ldc2 = ldc2; r.C3 = C3; r.tail0 = tail0; r.guard = guard;
   const long nb = ((long)M * N + 255) / 256;
-  KLAUNCH(k_splitk_reduce, dim3((unsigned)(nb > 2048 ? 2048 : nb)), block, st, pr2, r);
+  return launch(k_splitk_reduce, dim3((unsigned)(nb > 2048 ? 2048 : nb)), block, 0, st, pr2, r);
 }
 
 // Folded BPTT tail: d_r(1..T) = out_diff + dgifo(2..T+1) W_gifo_r (:391) and, if in_diff != nullptr,
@@ -3519,7 +3511,7 @@ hipError_t launch_bwd_tail(const Dims &d, const float *dgifo, const float *wr, c
       ks = G;                                            // (ws2 above was placed for the larger tiled plan: still in range)
       return launch_skinny16_pair(M, K4, dgifo + (size_t)2 * d.S * K4, dgifo + (size_t)d.S * K4, K4, wr, d.R, wx, in_diff ? d.I : 0, ws, ws2, G, st, pr);
     }
-    KLAUNCH(k_gemm_splitk2, dim3(nb1 + nb2, 1, ks), dim3(256), st, pr, g1, g2, nb1, kl, ws, ws2);
+    return launch(k_gemm_splitk2, dim3(nb1 + nb2, 1, ks), dim3(256), 0, st, pr, g1, g2, nb1, kl, ws, ws2);
   };
   hipError_t err = first();
   if (err != hipSuccess) return err;
@@ -3529,7 +3521,7 @@ hipError_t launch_bwd_tail(const Dims &d, const float *dgifo, const float *wr, c
   r2 = r1;
   r2.ws = ws2; r2.N = d.I; r2.Cm = in_diff; r2.ldc = id_stride; r2.add = nullptr; r2.add_ld = 0;
   const int nbr1 = cdiv(M * d.R, 256), nbr2 = in_diff ? cdiv(M * d.I, 256) : 0;
-  KLAUNCH(k_splitk_reduce2, dim3(nbr1 + nbr2), dim3(256), st, pr2, r1, r2, nbr1);
+  return launch(k_splitk_reduce2, dim3(nbr1 + nbr2), dim3(256), 0, st, pr2, r1, r2, nbr1);
 }
 
 bool grads_bf16_tiles(const Dims &d, bool bf16) { return bf16 && d.T * d.S >= GRADS_BF16_MIN_ROWS; }
@@ -3591,18 +3583,18 @@ hipError_t launch_grads(const Dims &d, const float *dgifo, const float *dr, cons
     a.nb1 = a.nb0 + cdiv(4 * C, BT) * cdiv(R, btn);
     a.nb2 = a.nb1 + cdiv(R, BT) * cdiv(C, btn);
     if (a.bf16_narrow) {
-      if (upd && upd->no_wT32) KLAUNCH((k_grads_bf16<true, true>), dim3(cdiv(a.nb2 + a.nvec, 8) * 8), dim3(256), st, pr, a);
-      KLAUNCH((k_grads_bf16<false, true>), dim3(cdiv(a.nb2 + a.nvec, 8) * 8), dim3(256), st, pr, a);
+      if (upd && upd->no_wT32) return launch((k_grads_bf16<true, true>), dim3(cdiv(a.nb2 + a.nvec, 8) * 8), dim3(256), 0, st, pr, a);
+      return launch((k_grads_bf16<false, true>), dim3(cdiv(a.nb2 + a.nvec, 8) * 8), dim3(256), 0, st, pr, a);
     }
-    if (upd && upd->no_wT32) KLAUNCH(k_grads_bf16<true>, dim3(cdiv(a.nb2 + a.nvec, 8) * 8), dim3(256), st, pr, a);
-    KLAUNCH(k_grads_bf16<false>, dim3(cdiv(a.nb2 + a.nvec, 8) * 8), dim3(256), st, pr, a);
+    if (upd && upd->no_wT32) return launch(k_grads_bf16<true>, dim3(cdiv(a.nb2 + a.nvec, 8) * 8), dim3(256), 0, st, pr, a);
+    return launch(k_grads_bf16<false>, dim3(cdiv(a.nb2 + a.nvec, 8) * 8), dim3(256), 0, st, pr, a);
   }
   if (tr) {   // the reduction of the tail workgroups' partial rows on the first workgroups of this launch
     if (!(a.wm.vecA && a.wm.vecB) || !tr->ctr || !tr->tws) return hipErrorInvalidValue;   // (16-byte rows: the engine's own buffers)
     a.tr = *tr; a.nred = tail_reduce_blocks(*tr); a.tr_target = tr->target;
-    KLAUNCH(k_grads_tm, dim3(a.nred + 8 * (cdiv(a.nb1, 8) + cdiv(a.nb2 + a.nvec - a.nb1, 8))), dim3(256), st, pr, a);
+    return launch(k_grads_tm, dim3(a.nred + 8 * (cdiv(a.nb1, 8) + cdiv(a.nb2 + a.nvec - a.nb1, 8))), dim3(256), 0, st, pr, a);
   }
-  KLAUNCH(k_grads, dim3(cdiv(a.nb2 + a.nvec, 8) * 8), dim3(256), st, pr, a);
+  return launch(k_grads, dim3(cdiv(a.nb2 + a.nvec, 8) * 8), dim3(256), 0, st, pr, a);
 }
 
 bool update_repack_vectorised(const Dims &d, const float *param_blob, const float *corr_blob, const float *grad_blob, const float *wrT,
@@ -3638,32 +3630,31 @@ hipError_t launch_update_repack(const Dims &d, float *param_blob, float *corr_bl
     a.a3 = planes->a3; a.b3 = planes->b3; a.a_plane = planes->a_plane; a.b_plane = planes->b_plane; a.split_mode = planes->split_mode;
     a.dstTh[0] = planes->wxTh; a.dstTh[1] = planes->wrTh;
   }
-  if (vec) KLAUNCH(k_update_repack_v, dim3(nb), dim3(256), st, pr, a);
-  KLAUNCH(k_update_repack, dim3(nb), dim3(256), st, pr, a);
+  if (vec) return launch(k_update_repack_v, dim3(nb), dim3(256), 0, st, pr, a);
+  return launch(k_update_repack, dim3(nb), dim3(256), 0, st, pr, a);
 }
 
 hipError_t launch_time_shift(const float *in, int rows, int cols, int in_stride, float *out, int out_stride, int shift,
                              hipStream_t st, LaunchProbe pr) {
   const int vec = aligned16(in) && aligned16(out) && in_stride % 4 == 0 && out_stride % 4 == 0 && cols % 4 == 0;
   const int per = vec ? 4 : 1;
-  KLAUNCH(k_time_shift, dim3(cdiv(cdiv(cols, per), 256), rows), dim3(256), st, pr, in, rows, cols, in_stride, out, out_stride,
-          shift, vec);
+  return launch(k_time_shift, dim3(cdiv(cdiv(cols, per), 256), rows), dim3(256), 0, st, pr, in, rows, cols, in_stride, out, out_stride, shift, vec);
 }
 
 hipError_t launch_softmax(const float *in, int rows, int cols, int in_stride, float *out, int out_stride, hipStream_t st) {
   LaunchProbe pr;
   const bool wide = cols % 4 == 0 && cols <= 32768 && cols >= 2048 && in_stride % 4 == 0 && out_stride % 4 == 0 &&
                     aligned16(in) && aligned16(out);
-  if (wide) KLAUNCH(k_softmax_rows_v, dim3(rows), dim3(1024), st, pr, in, cols, in_stride, out, out_stride);
-  KLAUNCH(k_softmax_rows, dim3(rows), dim3(256), st, pr, in, cols, in_stride, out, out_stride);
+  if (wide) return launch(k_softmax_rows_v, dim3(rows), dim3(1024), 0, st, pr, in, cols, in_stride, out, out_stride);
+  return launch(k_softmax_rows, dim3(rows), dim3(256), 0, st, pr, in, cols, in_stride, out, out_stride);
 }
 hipError_t launch_xent(const float *y, int rows, int cols, int stride, const int *target, const float *mask, float *diff,
                        int diff_stride, float *row_xent, float *row_correct, hipStream_t st) {
   LaunchProbe pr;
   const bool wide = cols % 4 == 0 && cols <= 32768 && cols >= 2048 && stride % 4 == 0 && diff_stride % 4 == 0 &&
                     aligned16(y) && aligned16(diff);
-  if (wide) KLAUNCH(k_xent_rows_v, dim3(rows), dim3(1024), st, pr, y, cols, stride, target, mask, diff, diff_stride, row_xent, row_correct);
-  KLAUNCH(k_xent_rows, dim3(rows), dim3(256), st, pr, y, cols, stride, target, mask, diff, diff_stride, row_xent, row_correct);
+  if (wide) return launch(k_xent_rows_v, dim3(rows), dim3(1024), 0, st, pr, y, cols, stride, target, mask, diff, diff_stride, row_xent, row_correct);
+  return launch(k_xent_rows, dim3(rows), dim3(256), 0, st, pr, y, cols, stride, target, mask, diff, diff_stride, row_xent, row_correct);
 }
 // one pass when the row fits the registers of 1024 threads (returns hipErrorNotSupported otherwise: the caller runs the pair)
 hipError_t launch_softmax_xent(const float *in, int rows, int cols, int in_stride, float *post, int post_stride, const int *target,
@@ -3673,15 +3664,13 @@ hipError_t launch_softmax_xent(const float *in, int rows, int cols, int in_strid
   const bool wide = cols % 4 == 0 && cols <= 32768 && cols >= 2048 && in_stride % 4 == 0 && diff_stride % 4 == 0 && aligned16(in) &&
                     aligned16(diff) && (!post || (post_stride % 4 == 0 && aligned16(post)));
   if (!wide) return hipErrorNotSupported;
-  KLAUNCH(k_softmax_xent_rows_v, dim3(rows), dim3(1024), st, pr, in, cols, in_stride, post, post_stride, target, mask, diff, diff_stride,
-          row_xent, row_correct, totals, ticket);
+  return launch(k_softmax_xent_rows_v, dim3(rows), dim3(1024), 0, st, pr, in, cols, in_stride, post, post_stride, target, mask, diff, diff_stride, row_xent, row_correct, totals, ticket);
 }
 hipError_t launch_xent_post(const float *y, int rows, int cols, int stride, const int *post_off, const int *post_pdf, const float *post_w,
                             const float *mask, float *diff, int diff_stride, float *row_xent, float *row_ent, float *row_correct,
                             hipStream_t st) {
   LaunchProbe pr;
-  KLAUNCH(k_xent_post_rows, dim3(rows), dim3(256), st, pr, y, cols, stride, post_off, post_pdf, post_w, mask, diff, diff_stride, row_xent,
-          row_ent, row_correct);
+  return launch(k_xent_post_rows, dim3(rows), dim3(256), 0, st, pr, y, cols, stride, post_off, post_pdf, post_w, mask, diff, diff_stride, row_xent, row_ent, row_correct);
 }
 // Loss statistics of a minibatch onto device totals (Xent::EvalMasked adds its three scalars to loss_, correct_, frames_ on the host,
 // nnet-loss.cc:136-141; a trainer that reports every N minibatches reads the totals once): totals[0] += sum row_xent (double),
@@ -3703,27 +3692,27 @@ __global__ __launch_bounds__(256) void k_xent_accumulate(const float *__restrict
 }
 hipError_t launch_xent_accumulate(const float *row_xent, const float *row_correct, const float *mask, int rows, double *totals, hipStream_t st) {
   LaunchProbe pr;
-  KLAUNCH(k_xent_accumulate, dim3(1), dim3(256), st, pr, row_xent, row_correct, mask, rows, totals);
+  return launch(k_xent_accumulate, dim3(1), dim3(256), 0, st, pr, row_xent, row_correct, mask, rows, totals);
 }
 hipError_t launch_col_sum(const float *src, int rows, int cols, int stride, float beta, float *dst, hipStream_t st) {
   LaunchProbe pr;
-  KLAUNCH(k_col_sum, dim3(cdiv(cols, 64)), dim3(256), st, pr, src, rows, cols, stride, beta, dst);
+  return launch(k_col_sum, dim3(cdiv(cols, 64)), dim3(256), 0, st, pr, src, rows, cols, stride, beta, dst);
 }
 static inline int ew_grid(long n);
 hipError_t launch_axpy(float *y, const float *x, float a, long n, hipStream_t st) {
   LaunchProbe pr;
-  KLAUNCH(k_axpy, dim3(ew_grid(n)), dim3(256), st, pr, y, x, a, n);
+  return launch(k_axpy, dim3(ew_grid(n)), dim3(256), 0, st, pr, y, x, a, n);
 }
 
 static inline int ew_grid(long n) { long g = (n + 255) / 256; return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g)); }
 
 hipError_t launch_sgd_momentum(float *param, float *corr, const float *grad, float mmt, float lr, long n, hipStream_t st) {
   LaunchProbe pr;
-  KLAUNCH(k_sgd_momentum, dim3(ew_grid(n)), dim3(256), st, pr, param, corr, grad, mmt, lr, n);
+  return launch(k_sgd_momentum, dim3(ew_grid(n)), dim3(256), 0, st, pr, param, corr, grad, mmt, lr, n);
 }
 hipError_t launch_apply_momentum(float *corr, const float *grad, float mmt, long n, hipStream_t st, LaunchProbe pr, const unsigned *guard,
                                  const float *mark) {
-  KLAUNCH(k_apply_momentum, dim3(ew_grid(n)), dim3(256), st, pr, corr, grad, mmt, n, guard, mark);
+  return launch(k_apply_momentum, dim3(ew_grid(n)), dim3(256), 0, st, pr, corr, grad, mmt, n, guard, mark);
 }
 
 }  // namespace klstm

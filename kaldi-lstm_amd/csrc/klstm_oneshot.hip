@@ -271,8 +271,7 @@ klstm_status klstm_oneshot_allreduce(klstm_oneshot *h, void *hip_stream, int tim
   int grid = (int)((per + 255) / 256);
   grid = grid < 1 ? 1 : grid > 192 ? 192 : grid;        // every workgroup of every rank's kernel must be resident at once (the kernel runs alone on its
                                                         // stream: 256 CUs); 64 workgroups moved 17 MB of local memory in 26 us, too few loads in flight
-  hipLaunchKernelGGL(k_oneshot_allreduce, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
-  OCHK(hipGetLastError());
+  OCHK(launch(k_oneshot_allreduce, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(hip_stream), LaunchProbe{}, a));
   return KLSTM_OK;
 }
 

@@ -30,7 +30,6 @@
 // recomputing its tile in plain fp32 (klstm_math.h "range guard") -- the launcher then keeps this product on the fp32 tile kernel.
 #include "klstm_kernels.h"
 #include "klstm_math.h"
-#include <hip/hip_ext.h>
 #include <type_traits>
 
 namespace klstm {
@@ -338,20 +337,12 @@ hipError_t launch_outer_f16(int M, int N, int K, const float *diff, int ldd, con
   a.m_main = M; a.nextra = 0;
   if (nstrip > ncu && M - 64 * ncu <= ncu) { nstrip = ncu; a.m_main = 64 * ncu; a.nextra = M - a.m_main; }
   const dim3 grid(nstrip), block(256);
-#define OUTER_GO2(NCH_, UPD_) do { const unsigned shm = UPD_ ? 131072u : 0u; \
-                                   if (UPD_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_outer16<NCH_, UPD_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
-                                   if (pr.start) hipExtLaunchKernelGGL((k_outer16<NCH_, UPD_>), grid, block, shm, st, pr.start, pr.stop, 0, a); \
-                                   else hipLaunchKernelGGL((k_outer16<NCH_, UPD_>), grid, block, shm, st, a); } while (0)
-#define OUTER_GO(NCH_) do { if (beta != 0.f || P) OUTER_GO2(NCH_, true); else OUTER_GO2(NCH_, false); } while (0)
-  switch ((K + 31) / 32) {
-    case 1: OUTER_GO(1); break;
-    case 2: OUTER_GO(2); break;
-    case 3: OUTER_GO(3); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef OUTER_GO
-#undef OUTER_GO2
-  return hipGetLastError();
+  static void (*const kern[3][2])(OuterArgs) = {{k_outer16<1, true>, k_outer16<1, false>}, {k_outer16<2, true>, k_outer16<2, false>},
+                                                {k_outer16<3, true>, k_outer16<3, false>}};   // [chunks of K - 1][!UPD]
+  const int nch = (K + 31) / 32;
+  const bool upd = beta != 0.f || P;
+  if (nch < 1 || nch > 3) return hipErrorInvalidValue;
+  return launch(kern[nch - 1][!upd], grid, block, upd ? 131072 : 0, st, pr, a);
 }
 
 }  // namespace klstm

@@ -36,8 +36,6 @@
 #include "klstm_math.h"
 #include "klstm_persist_dev.h"
 
-#include <hip/hip_ext.h>
-
 namespace klstm {
 
 #pragma clang fp contract(off)
@@ -604,49 +602,41 @@ int persist_fwd_grid(const Dims &d, const PersistOpts &o) {
 // forward: [2 parities][C][8 stream slots]; backward: [2 stream groups][BWD_RING = 32 ring slots][C][4 stream slots] (klstm_persist_bwd.hip)
 size_t persist_gran_bytes(const Dims &d) { return (size_t)64 * d.C * 8 * sizeof(unsigned long long); }   // (backward: up to 4 groups x 32 ring slots)
 
-template <class K, class A>
-static hipError_t plaunch(K kern, int grid, int threads, size_t shm, hipStream_t st, LaunchProbe pr, const A &a) {
-  if (shm > 64 * 1024)                               // above the default dynamic-LDS limit
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (pr.start) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(threads), shm, st, pr.start, pr.stop, 0, a);
-  else hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), shm, st, a);
-  return hipGetLastError();
-}
 // geometry x stream-group count; two groups (5..8 streams) only in the 12-wave geometries
 #define PF5(KERN, TP, MC, W, NG_)                                                                               \
   if (g.waves == W && g.tpw == TP && g.maxc == MC && ng == NG_) {                                               \
-    if (g.pcell == 1) return plaunch(KERN<TP, MC, W, 1, NG_>, grid, W * 64, shm, st, pr, a);                    \
-    if (g.pcell == 2) return plaunch(KERN<TP, MC, W, 2, NG_>, grid, W * 64, shm, st, pr, a);                    \
-    if (g.pcell == 3) return plaunch(KERN<TP, MC, W, 3, NG_>, grid, W * 64, shm, st, pr, a);                    \
-    return plaunch(KERN<TP, MC, W, 4, NG_>, grid, W * 64, shm, st, pr, a);                                      \
+    if (g.pcell == 1) return launch(KERN<TP, MC, W, 1, NG_>, grid, W * 64, shm, st, pr, a);                     \
+    if (g.pcell == 2) return launch(KERN<TP, MC, W, 2, NG_>, grid, W * 64, shm, st, pr, a);                     \
+    if (g.pcell == 3) return launch(KERN<TP, MC, W, 3, NG_>, grid, W * 64, shm, st, pr, a);                     \
+    return launch(KERN<TP, MC, W, 4, NG_>, grid, W * 64, shm, st, pr, a);                                       \
   }
 #define PFX(KERN, TP, MC, NG_)                                                                                  \
   if (xbat && g.waves == 12 && g.tpw == TP && g.maxc == MC && ng == NG_) {                                      \
-    if (g.pcell == 1) return plaunch(KERN<TP, MC, 12, 1, NG_, true>, grid, 768, shm, st, pr, a);                \
-    if (g.pcell == 2) return plaunch(KERN<TP, MC, 12, 2, NG_, true>, grid, 768, shm, st, pr, a);                \
-    if (g.pcell == 3) return plaunch(KERN<TP, MC, 12, 3, NG_, true>, grid, 768, shm, st, pr, a);                \
-    return plaunch(KERN<TP, MC, 12, 4, NG_, true>, grid, 768, shm, st, pr, a);                                  \
+    if (g.pcell == 1) return launch(KERN<TP, MC, 12, 1, NG_, true>, grid, 768, shm, st, pr, a);                 \
+    if (g.pcell == 2) return launch(KERN<TP, MC, 12, 2, NG_, true>, grid, 768, shm, st, pr, a);                 \
+    if (g.pcell == 3) return launch(KERN<TP, MC, 12, 3, NG_, true>, grid, 768, shm, st, pr, a);                 \
+    return launch(KERN<TP, MC, 12, 4, NG_, true>, grid, 768, shm, st, pr, a);                                   \
   }
 #define PF5I(KERN, TP, MC)                                                                                      \
   if (il && !xbat && g.waves == 12 && g.tpw == TP && g.maxc == MC && ng == 2) {                                 \
-    if (g.pcell == 1) return plaunch(KERN<TP, MC, 12, 1, 2, false, true>, grid, 768, shm, st, pr, a);           \
-    if (g.pcell == 2) return plaunch(KERN<TP, MC, 12, 2, 2, false, true>, grid, 768, shm, st, pr, a);           \
-    if (g.pcell == 3) return plaunch(KERN<TP, MC, 12, 3, 2, false, true>, grid, 768, shm, st, pr, a);           \
-    return plaunch(KERN<TP, MC, 12, 4, 2, false, true>, grid, 768, shm, st, pr, a);                             \
+    if (g.pcell == 1) return launch(KERN<TP, MC, 12, 1, 2, false, true>, grid, 768, shm, st, pr, a);            \
+    if (g.pcell == 2) return launch(KERN<TP, MC, 12, 2, 2, false, true>, grid, 768, shm, st, pr, a);            \
+    if (g.pcell == 3) return launch(KERN<TP, MC, 12, 3, 2, false, true>, grid, 768, shm, st, pr, a);            \
+    return launch(KERN<TP, MC, 12, 4, 2, false, true>, grid, 768, shm, st, pr, a);                              \
   }
 #define PFXI(KERN, TP, MC)                                                                                      \
   if (il && xbat && g.waves == 12 && g.tpw == TP && g.maxc == MC && ng == 2) {                                  \
-    if (g.pcell == 1) return plaunch(KERN<TP, MC, 12, 1, 2, true, true>, grid, 768, shm, st, pr, a);            \
-    if (g.pcell == 2) return plaunch(KERN<TP, MC, 12, 2, 2, true, true>, grid, 768, shm, st, pr, a);            \
-    if (g.pcell == 3) return plaunch(KERN<TP, MC, 12, 3, 2, true, true>, grid, 768, shm, st, pr, a);            \
-    return plaunch(KERN<TP, MC, 12, 4, 2, true, true>, grid, 768, shm, st, pr, a);                              \
+    if (g.pcell == 1) return launch(KERN<TP, MC, 12, 1, 2, true, true>, grid, 768, shm, st, pr, a);             \
+    if (g.pcell == 2) return launch(KERN<TP, MC, 12, 2, 2, true, true>, grid, 768, shm, st, pr, a);             \
+    if (g.pcell == 3) return launch(KERN<TP, MC, 12, 3, 2, true, true>, grid, 768, shm, st, pr, a);             \
+    return launch(KERN<TP, MC, 12, 4, 2, true, true>, grid, 768, shm, st, pr, a);                               \
   }
 #define PF5IN(KERN, MC, NG_)        /* 9..16 streams: three / four interleaved chains (12 waves, one tile per workgroup) */ \
   if (il && !xbat && g.waves == 12 && g.tpw == 1 && g.maxc == MC && ng == NG_) {                                \
-    if (g.pcell == 1) return plaunch(KERN<1, MC, 12, 1, NG_, false, true>, grid, 768, shm, st, pr, a);          \
-    if (g.pcell == 2) return plaunch(KERN<1, MC, 12, 2, NG_, false, true>, grid, 768, shm, st, pr, a);          \
-    if (g.pcell == 3) return plaunch(KERN<1, MC, 12, 3, NG_, false, true>, grid, 768, shm, st, pr, a);          \
-    return plaunch(KERN<1, MC, 12, 4, NG_, false, true>, grid, 768, shm, st, pr, a);                            \
+    if (g.pcell == 1) return launch(KERN<1, MC, 12, 1, NG_, false, true>, grid, 768, shm, st, pr, a);           \
+    if (g.pcell == 2) return launch(KERN<1, MC, 12, 2, NG_, false, true>, grid, 768, shm, st, pr, a);           \
+    if (g.pcell == 3) return launch(KERN<1, MC, 12, 3, NG_, false, true>, grid, 768, shm, st, pr, a);           \
+    return launch(KERN<1, MC, 12, 4, NG_, false, true>, grid, 768, shm, st, pr, a);                             \
   }
 #define PDISPATCH_FWD(KERN)                                                                                     \
   do {                                                                                                          \
@@ -670,7 +660,7 @@ static hipError_t plaunch(K kern, int grid, int threads, size_t shm, hipStream_t
 // form spills none and measured 59.1 against 53.3 us per chunk; the other PCELL / MAXC forms (not measured).  Everything else runs the
 // ordinary instance: the same out and state, with the planes.
 #define PFINF(XB_, IL_, NG_)                                                                                    \
-  if (xbat == XB_ && il == IL_ && ng == NG_) return plaunch(k_fwd_persist<1, 7, 12, 2, NG_, XB_, IL_, true>, grid, 768, shm, st, pr, a);
+  if (xbat == XB_ && il == IL_ && ng == NG_) return launch(k_fwd_persist<1, 7, 12, 2, NG_, XB_, IL_, true>, grid, 768, shm, st, pr, a);
 bool persist_fwd_has_inference(const Dims &d, const PersistOpts &o) {
   const bool xbat = persist_x_batched(d), il = d.S > 4 && o.fwd_interleave != 0;
   const int ng = (d.S + 3) / 4, Ik = xbat ? 0 : d.I;

@@ -38,8 +38,6 @@
 #include "klstm_math.h"
 #include "klstm_persist_dev.h"
 
-#include <hip/hip_ext.h>
-
 #include <algorithm>
 #include <type_traits>
 
@@ -1204,15 +1202,6 @@ int persist_bwd_tail_wgs(const Dims &d, bool want_in_diff, const PersistOpts &o)
   return ntw;
 }
 
-template <class Kn>
-static hipError_t plaunch2(Kn kern, int grid, int threads, size_t shm, hipStream_t st, LaunchProbe pr, const PersistBwd2Args &a) {
-  if (shm > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (pr.start) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(threads), shm, st, pr.start, pr.stop, 0, a);
-  else hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), shm, st, a);
-  return hipGetLastError();
-}
-
 hipError_t launch_bwd_persist(const Dims &d, const BwdPtrs &p, const float *P, const float *out_diff, int od_stride,
                               float *in_diff, int id_stride, bool tail_inside, unsigned long long *gran, unsigned *ctrl,
                               const PersistOpts &o, hipStream_t st, LaunchProbe pr, float *tws, size_t tws_floats, LaunchProbe pr_reduce,
@@ -1253,17 +1242,17 @@ hipError_t launch_bwd_persist(const Dims &d, const BwdPtrs &p, const float *P, c
   if (bwd_interleaved(d, o)) {
     const int ngi = bwd_groups(d);
     const size_t shmi = bwd2_lds_bytes(g, d.T, a.pin != 0, ngi);
-    if (ngi == 3 && g.nw == 16 && g.nu == 2) err = plaunch2(k_bwd_persist2i<16, 2, 3>, grid, 1024, shmi, st, pr, a);
-    else if (ngi == 4 && g.nw == 16 && g.nu == 2) err = plaunch2(k_bwd_persist2i<16, 2, 4>, grid, 1024, shmi, st, pr, a);
+    if (ngi == 3 && g.nw == 16 && g.nu == 2) err = launch(k_bwd_persist2i<16, 2, 3>, grid, 1024, shmi, st, pr, a);
+    else if (ngi == 4 && g.nw == 16 && g.nu == 2) err = launch(k_bwd_persist2i<16, 2, 4>, grid, 1024, shmi, st, pr, a);
     else if (ngi > 2) err = hipErrorInvalidValue;
-    else if (g.nw == 16 && g.nu == 2) err = plaunch2(k_bwd_persist2i<16, 2>, grid, 1024, shmi, st, pr, a);
-    else if (g.nw == 16 && g.nu == 3) err = plaunch2(k_bwd_persist2i<16, 3>, grid, 1024, shmi, st, pr, a);
-    else if (g.nw == 12 && g.nu == 3) err = plaunch2(k_bwd_persist2i<12, 3>, grid, 768, shmi, st, pr, a);
+    else if (g.nw == 16 && g.nu == 2) err = launch(k_bwd_persist2i<16, 2>, grid, 1024, shmi, st, pr, a);
+    else if (g.nw == 16 && g.nu == 3) err = launch(k_bwd_persist2i<16, 3>, grid, 1024, shmi, st, pr, a);
+    else if (g.nw == 12 && g.nu == 3) err = launch(k_bwd_persist2i<12, 3>, grid, 768, shmi, st, pr, a);
   } else {
     const size_t shm = bwd2_lds_bytes(g, d.T, a.pin != 0);
-    if (g.nw == 16 && g.nu == 2) err = plaunch2(k_bwd_persist2<16, 2>, grid, 1024, shm, st, pr, a);
-    else if (g.nw == 16 && g.nu == 3) err = plaunch2(k_bwd_persist2<16, 3>, grid, 1024, shm, st, pr, a);
-    else if (g.nw == 12 && g.nu == 3) err = plaunch2(k_bwd_persist2<12, 3>, grid, 768, shm, st, pr, a);
+    if (g.nw == 16 && g.nu == 2) err = launch(k_bwd_persist2<16, 2>, grid, 1024, shm, st, pr, a);
+    else if (g.nw == 16 && g.nu == 3) err = launch(k_bwd_persist2<16, 3>, grid, 1024, shm, st, pr, a);
+    else if (g.nw == 12 && g.nu == 3) err = launch(k_bwd_persist2<12, 3>, grid, 768, shm, st, pr, a);
   }
   if (err != hipSuccess || !a.tq) return err;
   // the tail workgroups' partial rows -> d_r, in_diff
@@ -1278,9 +1267,7 @@ hipError_t launch_tail_reduce(const TailReduceJob &j, const unsigned *guard, hip
   TailReduceArgs ra;
   ra.j = j; ra.guard = guard;
   const int nthr = j.T * j.S * (j.ncols / 4) * 8;
-  if (pr.start) hipExtLaunchKernelGGL(k_tail_reduce, dim3(pcdiv2(nthr, 256)), dim3(256), 0, st, pr.start, pr.stop, 0, ra);
-  else hipLaunchKernelGGL(k_tail_reduce, dim3(pcdiv2(nthr, 256)), dim3(256), 0, st, ra);
-  return hipGetLastError();
+  return launch(k_tail_reduce, dim3(pcdiv2(nthr, 256)), dim3(256), 0, st, pr, ra);
 }
 int tail_reduce_blocks(const TailReduceJob &j) { return pcdiv2(pcdiv2(j.T * j.S * (j.ncols / 4) * 8, 256), 8) * 8; }
 

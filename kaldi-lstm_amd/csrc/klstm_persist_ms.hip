@@ -28,8 +28,6 @@
 #include "klstm_math.h"
 #include "klstm_persist_dev.h"
 
-#include <hip/hip_ext.h>
-
 namespace klstm {
 
 #pragma clang fp contract(off)
@@ -315,15 +313,6 @@ size_t persist_ms_gran_bytes(const Dims &d) {      // (the XCD-local kernel of k
   return ms > xl ? ms : xl;
 }
 
-template <int NT, int PG>
-static hipError_t ms_launch(const PersistMsArgs &a, int grid, size_t shm, hipStream_t st, LaunchProbe pr) {
-  auto kern = k_fwd_persist_ms<NT, MS_NSW, PG>;
-  if (shm > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (pr.start) hipExtLaunchKernelGGL(kern, dim3(grid), dim3((4 + MS_NSW) * 64), shm, st, pr.start, pr.stop, 0, a);
-  else hipLaunchKernelGGL(kern, dim3(grid), dim3((4 + MS_NSW) * 64), shm, st, a);
-  return hipGetLastError();
-}
-
 hipError_t launch_fwd_persist_ms(const Dims &d, const FwdPtrs &p, const unsigned short *wrm, float *out, int out_stride, uint4 *gran, unsigned *ctrl,
                                  const PersistOpts &o, hipStream_t st, LaunchProbe pr) {
   if (!persist_ms_supported(d) || !wrm || !gran || !out) return hipErrorInvalidValue;
@@ -341,13 +330,14 @@ hipError_t launch_fwd_persist_ms(const Dims &d, const FwdPtrs &p, const unsigned
   const int nt = d.S > 16 ? 2 : 1, grid = persist_ms_grid(d);
   const int pg = msdiv(grid * nt * MS_NG, MS_NSW * 64);
   const size_t shm = (size_t)16 * nt * a.ldrow + (size_t)2 * 4 * nt * 64 * 16 + (size_t)nt * 72 * 2 + 16;
+  const dim3 block((4 + MS_NSW) * 64);
   if (nt == 2) {
-    if (pg <= 4) return ms_launch<2, 4>(a, grid, shm, st, pr);
-    if (pg <= 8) return ms_launch<2, 8>(a, grid, shm, st, pr);
-    if (pg <= 11) return ms_launch<2, 11>(a, grid, shm, st, pr);
+    if (pg <= 4) return launch(k_fwd_persist_ms<2, MS_NSW, 4>, grid, block, shm, st, pr, a);
+    if (pg <= 8) return launch(k_fwd_persist_ms<2, MS_NSW, 8>, grid, block, shm, st, pr, a);
+    if (pg <= 11) return launch(k_fwd_persist_ms<2, MS_NSW, 11>, grid, block, shm, st, pr, a);
   } else {
-    if (pg <= 3) return ms_launch<1, 3>(a, grid, shm, st, pr);
-    if (pg <= 6) return ms_launch<1, 6>(a, grid, shm, st, pr);
+    if (pg <= 3) return launch(k_fwd_persist_ms<1, MS_NSW, 3>, grid, block, shm, st, pr, a);
+    if (pg <= 6) return launch(k_fwd_persist_ms<1, MS_NSW, 6>, grid, block, shm, st, pr, a);
   }
   return hipErrorInvalidValue;
 }

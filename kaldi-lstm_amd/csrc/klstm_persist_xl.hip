@@ -29,8 +29,6 @@
 #include "klstm_math.h"
 #include "klstm_persist_dev.h"
 
-#include <hip/hip_ext.h>
-
 namespace klstm {
 
 #pragma clang fp contract(off)
@@ -557,10 +555,7 @@ hipError_t launch_fwd_persist_xl(const Dims &d, const FwdPtrs &p, const unsigned
   a.test_stall = o.test_stall_fwd;
   const size_t shm = (size_t)5 * XL_LD + (size_t)2 * 16 * 64 * 16 + 32;
   auto kern = d.C == XL_C ? k_fwd_persist_xl<true> : k_fwd_persist_xl<false>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (pr.start) hipExtLaunchKernelGGL(kern, dim3(256), dim3(1024), shm, st, pr.start, pr.stop, 0, a);
-  else hipLaunchKernelGGL(kern, dim3(256), dim3(1024), shm, st, a);
-  return hipGetLastError();
+  return launch(kern, dim3(256), dim3(1024), shm, st, pr, a);
 }
 
 size_t persist_xl_bwd_gran_bytes() { return (size_t)8 * 2 * 4 * XL_C * 16 + 64; }
@@ -579,10 +574,7 @@ hipError_t launch_bwd_persist_xl(const Dims &d, const BwdPtrs &p, const unsigned
   a.test_stall = o.test_stall_bwd;
   const size_t shm = (size_t)5 * XL_LDB + (size_t)32 * 64 * 16 + 32;
   auto kern = d.C == XL_C ? k_bwd_persist_xl<true> : k_bwd_persist_xl<false>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (pr.start) hipExtLaunchKernelGGL(kern, dim3(256), dim3(1024), shm, st, pr.start, pr.stop, 0, a);
-  else hipLaunchKernelGGL(kern, dim3(256), dim3(1024), shm, st, a);
-  return hipGetLastError();
+  return launch(kern, dim3(256), dim3(1024), shm, st, pr, a);
 }
 
 }  // namespace klstm

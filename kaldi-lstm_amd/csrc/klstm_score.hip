@@ -125,19 +125,14 @@ hipError_t launch_pack_streams(const float *feats, int dim, int feat_stride, con
   const int per = vec ? dim / 4 : dim;
   const int bx = per <= 64 ? 64 : per <= 128 ? 128 : 256;
   const int gx = (per + bx - 1) / bx;
-  hipLaunchKernelGGL(k_pack_streams, dim3(gx, T * S), dim3(bx), 0, st, feats, dim, feat_stride, desc, S, shift, out, out_stride, reset, vec);
-  return hipGetLastError();
+  return launch(k_pack_streams, dim3(gx, T * S), dim3(bx), 0, st, LaunchProbe{}, feats, dim, feat_stride, desc, S, shift, out, out_stride, reset,
+                vec);
 }
 hipError_t launch_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row, float *out, int out_stride,
                                       int mode, const float *log_prior, float prior_scale, hipStream_t st) {
   const bool wide = cols % 4 == 0 && cols <= 32768 && cols >= 2048 && in_stride % 4 == 0 && out_stride % 4 == 0 && al16(in) && al16(out);
-  if (wide)
-    hipLaunchKernelGGL(k_log_softmax_scatter_v, dim3(rows), dim3(1024), 0, st, in, cols, in_stride, dst_row, out, out_stride, mode,
-                       log_prior, prior_scale);
-  else
-    hipLaunchKernelGGL(k_log_softmax_scatter, dim3(rows), dim3(256), 0, st, in, cols, in_stride, dst_row, out, out_stride, mode,
-                       log_prior, prior_scale);
-  return hipGetLastError();
+  return launch(wide ? k_log_softmax_scatter_v : k_log_softmax_scatter, dim3(rows), dim3(wide ? 1024 : 256), 0, st, LaunchProbe{}, in, cols,
+                in_stride, dst_row, out, out_stride, mode, log_prior, prior_scale);
 }
 
 }  // namespace klstm

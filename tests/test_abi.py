@@ -42,3 +42,20 @@ def test_product_package_never_touches_the_oracle():
                 src = open(os.path.join(dp, fn), errors="ignore").read()
                 assert not re.search(r"import\s+oracle|from\s+oracle|#include[^\n]*oracle|liblstmp_oracle|lstmp_oracle_",
                                      src), f"{fn} references the oracle"
+
+
+def test_every_kernel_launch_goes_through_the_one_helper():
+    """launch() in csrc/klstm_kernels.h is the only code that launches a kernel or raises a kernel's dynamic-LDS limit: one probe
+    branch, one error convention, and the limit raised once per (device, kernel) under its lock."""
+    csrc = os.path.join(ROOT, "kaldi-lstm_amd", "csrc")
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith((".hip", ".h")):
+            continue
+        src = open(os.path.join(csrc, fn)).read()
+        src = re.sub(r"//[^\n]*|/\*.*?\*/", "", src, flags=re.S)
+        if fn == "klstm_kernels.h":
+            a, b = src.index("inline hipError_t raise_lds_limit("), src.index("hipError_t launch(K kern")
+            b = src.index("\n}\n", b)
+            src = src[:a] + src[b:]
+        for name in ("hipFuncSetAttribute", "hipLaunchKernelGGL", "hipExtLaunchKernelGGL", "<<<"):
+            assert name not in src, f"{fn} calls {name} outside launch() (klstm_kernels.h)"
