@@ -328,6 +328,23 @@ klstm_status klstm_pack_streams(const float *feats, int dim, int feat_stride, co
 klstm_status klstm_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row_dev, float *out,
                                        int out_stride, int mode, const float *log_prior_dev, float prior_scale, void *hip_stream);
 
+/* The bidirectional layer (include/klstm_blstm.hpp): per-stream, length-aware time reversal of a time-major
+ * block.  in / out [T*S x cols] (row t*S + s), device pointers, strides in elements (column windows such as `ptr + R` with stride 2R
+ * are fine: rows need no alignment); lens_dev: S ints on the device, the length of the utterance in stream s, which starts at t = 0
+ * (0 = idle stream; a value outside [0, T] is clamped to it).  Rows t >= lens[s] are padding.
+ *   KLSTM_REVERSE_SET        t < len: out[t] = in[len-1-t]     padding rows: out = 0
+ *   KLSTM_REVERSE_ADD        t < len: out[t] += in[len-1-t]    padding rows: untouched
+ *   KLSTM_REVERSE_ZERO_PAD   t < len: untouched                padding rows: out = 0      (in is not read, may be NULL)
+ *   KLSTM_REVERSE_MASK_COPY  t < len: out[t] = in[t]           padding rows: out = 0      (no reversal)
+ * in and out must not overlap in the reversing modes (in == out is refused).  T == 0 or cols == 0: nothing to do.  Enqueued on
+ * hip_stream (NULL = the legacy default stream). */
+#define KLSTM_REVERSE_SET        0
+#define KLSTM_REVERSE_ADD        1
+#define KLSTM_REVERSE_ZERO_PAD   2
+#define KLSTM_REVERSE_MASK_COPY  3
+klstm_status klstm_reverse_streams(const float *in, int in_stride, int S, int T, int cols, const int *lens_dev, float *out, int out_stride,
+                                   int mode, void *hip_stream);
+
 /* Engine knobs (not part of the reference interface).  Keys:
  *   "graph"   0/1/2  issue plain stream launches (default 0: measured equal or faster at every stream count while the host
  *                  thread keeps ahead, and indifferent to callers that hand in fresh buffers every minibatch) or replay the

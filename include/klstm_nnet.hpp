@@ -73,6 +73,7 @@ class Layer {
   virtual void SetUpdateFollows(bool) {}                     // Nnet::Backpropagate: Update comes right behind BackpropagateFnc
   virtual void SetTrainOptions(const NnetTrainOptions &) {}
   virtual void Reset(std::vector<int> &) {}                  // the overlay adds Reset to every Component (nnet-nnet.h:133-137)
+  virtual void SetSeqLengths(const std::vector<int32> &) {}   // per-utterance lengths (nnet1's name; the bidirectional layer, klstm_blstm.hpp)
   virtual int32 NumParams() const { return 0; }
   virtual void GetParams(std::vector<BaseFloat> *p) const { p->clear(); }
   void Write(std::ostream &os, bool binary) const {
@@ -306,6 +307,9 @@ class Nnet {                                  // google/nnet/nnet-nnet.h:36-150
   void SetTrainOptions(const NnetTrainOptions &o) { opts_ = o; for (auto &l : layers_) l->SetTrainOptions(o); }
   void Reset(std::vector<int> &stream_reset_flag) {          // nnet-nnet.h:132-138: fan out to EVERY component
     for (auto &l : layers_) l->Reset(stream_reset_flag);
+  }
+  void SetSeqLengths(const std::vector<int32> &lens) {       // fan out to every component (a no-op for all but the bidirectional layer)
+    for (auto &l : layers_) l->SetSeqLengths(lens);
   }
 
   // Nnet::Propagate [UPSTREAM]: each component's output buffer is (re)sized, then PropagateFnc.

@@ -70,6 +70,7 @@ def load_library():
     lib.klstm_propagate_inference.argtypes = [P, P, I, I, P, I]
     lib.klstm_pack_streams.argtypes = [P, I, I, P, I, I, I, P, I, P, P]
     lib.klstm_log_softmax_scatter.argtypes = [P, I, I, I, P, P, I, I, P, F, P]
+    lib.klstm_reverse_streams.argtypes = [P, I, I, I, I, P, P, I, I, P]
     lib.klstm_backpropagate.argtypes = [P, P, I, P, I, P, I, I, F, I]
     lib.klstm_propagate_host.argtypes = [P, P, I, I, P, I]
     lib.klstm_backpropagate_host.argtypes = [P, P, I, P, I, P, I, I, F, I]
@@ -478,6 +479,23 @@ def pack_streams(feats, desc, T, shift, out, reset=None, stream=None):
     assert reset is None or (reset.dtype == torch.int32 and reset.numel() == desc.shape[0])
     _chk(lib.klstm_pack_streams(feats.data_ptr(), feats.shape[1], feats.stride(0), desc.data_ptr(), desc.shape[0], int(T), int(shift),
                                 out.data_ptr(), out.stride(0), reset.data_ptr() if reset is not None else None, _sp(stream)))
+
+
+REVERSE_SET, REVERSE_ADD, REVERSE_ZERO_PAD, REVERSE_MASK_COPY = 0, 1, 2, 3
+
+
+def reverse_streams(x, lens, T, out, mode=REVERSE_SET, stream=None):
+    """klstm_reverse_streams: per-stream, length-aware time reversal of a time-major block.  x, out [T*S, cols] torch CUDA float32
+    (column windows such as out[:, R:] are fine; x may be None with REVERSE_ZERO_PAD), lens an int32 CUDA tensor of S lengths.
+    REVERSE_SET: out[t] = x[len-1-t], padding rows 0; REVERSE_ADD: out[t] += x[len-1-t], padding rows untouched; REVERSE_ZERO_PAD:
+    padding rows of out = 0; REVERSE_MASK_COPY: out[t] = x[t], padding rows 0."""
+    import torch
+    lib = load_library()
+    assert lens.dtype == torch.int32 and lens.is_cuda and lens.is_contiguous()
+    S = lens.numel()
+    assert out.stride(1) == 1 and out.shape[0] == T * S and (x is None or (x.stride(1) == 1 and x.shape == out.shape))
+    _chk(lib.klstm_reverse_streams(x.data_ptr() if x is not None else None, x.stride(0) if x is not None else 0, S, int(T),
+                                   out.shape[1], lens.data_ptr(), out.data_ptr(), out.stride(0), int(mode), _sp(stream)))
 
 
 def log_softmax_scatter(a, dst_row, out, mode, log_prior=None, prior_scale=1.0, stream=None):

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <climits>
 #include <cstddef>
 #include <cstdio>
 #include <atomic>
@@ -2022,6 +2023,21 @@ klstm_status klstm_pack_streams(const float *feats, int dim, int feat_stride, co
   if ((long)T * num_stream > 65535) return fail(KLSTM_ERR_SHAPE, "klstm_pack_streams: T * num_stream > 65535");
   if (T == 0 || dim == 0) return KLSTM_OK;
   HIPCHK(launch_pack_streams(feats, dim, feat_stride, stream_desc_dev, num_stream, T, shift, out, out_stride, reset_dev, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
+klstm_status klstm_reverse_streams(const float *in, int in_stride, int S, int T, int cols, const int *lens_dev, float *out, int out_stride,
+                                   int mode, void *hip_stream) {
+  if (mode < KLSTM_REVERSE_SET || mode > KLSTM_REVERSE_MASK_COPY) return fail(KLSTM_ERR_ARG, "klstm_reverse_streams: unknown mode %d", mode);
+  const bool reads = mode != KLSTM_REVERSE_ZERO_PAD;
+  if (S <= 0 || T < 0 || cols < 0) return fail(KLSTM_ERR_ARG, "klstm_reverse_streams: bad size (streams %d, T %d, cols %d)", S, T, cols);
+  if ((long)T * S > INT_MAX) return fail(KLSTM_ERR_SHAPE, "klstm_reverse_streams: T * num_stream > INT_MAX");
+  if (T == 0 || cols == 0) return KLSTM_OK;
+  if (out_stride < cols || (reads && in_stride < cols))
+    return fail(KLSTM_ERR_ARG, "klstm_reverse_streams: row stride below the column count (%d / %d < %d)", in_stride, out_stride, cols);
+  if (!out || !lens_dev || (reads && !in)) return fail(KLSTM_ERR_ARG, "klstm_reverse_streams: null argument");
+  if ((mode == KLSTM_REVERSE_SET || mode == KLSTM_REVERSE_ADD) && in == out)
+    return fail(KLSTM_ERR_ARG, "klstm_reverse_streams: in == out (the reversal cannot run in place)");
+  HIPCHK(launch_reverse_streams(in, in_stride, S, T, cols, lens_dev, out, out_stride, mode, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
 klstm_status klstm_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row_dev, float *out,

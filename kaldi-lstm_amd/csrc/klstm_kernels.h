@@ -311,6 +311,9 @@ hipError_t launch_softmax(const float *in, int rows, int cols, int in_stride, fl
 // batched scoring (klstm_score.hip): klstm_pack_streams / klstm_log_softmax_scatter of include/klstm.h
 hipError_t launch_pack_streams(const float *feats, int dim, int feat_stride, const int *desc, int S, int T, int shift, float *out,
                                int out_stride, int *reset, hipStream_t st);
+// the bidirectional layer (klstm_score.hip): klstm_reverse_streams of include/klstm.h
+hipError_t launch_reverse_streams(const float *in, int in_stride, int S, int T, int cols, const int *lens, float *out, int out_stride,
+                                  int mode, hipStream_t st);
 hipError_t launch_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row, float *out, int out_stride,
                                       int mode, const float *log_prior, float prior_scale, hipStream_t st);
 hipError_t launch_xent(const float *y, int rows, int cols, int stride, const int *target, const float *mask, float *diff,

@@ -4,6 +4,8 @@
 //                           bd-nnet-train-lstm-streams.cc:198-201), plus the chunk's reset flags
 //   k_log_softmax_scatter   the Affine output rows of a chunk -> posterior / log-posterior / log-likelihood, each row written to
 //                           its row of the per-utterance output (padding rows: dst -1, never written)
+//   k_reverse_streams       per-stream, length-aware time reversal of a time-major block (the bidirectional layer,
+//                           include/klstm_blstm.hpp): the backward direction's input, output, out_diff and in_diff
 #include "../../include/klstm.h"
 #include "klstm_kernels.h"
 
@@ -31,6 +33,45 @@ __global__ void k_pack_streams(const float *__restrict__ feats, int dim, int fea
       *reinterpret_cast<float4 *>(op + c) = *reinterpret_cast<const float4 *>(ip + c);
   } else {
     for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < dim; c += gridDim.x * blockDim.x) op[c] = ip[c];
+  }
+}
+
+// One workgroup per row (blockIdx.x = t*S + s), lane-contiguous columns (blockIdx.y tiles them).  The stream's length is clamped to
+// [0, T] here, so no lens value can make a row read outside the block.  Modes (klstm.h klstm_reverse_streams):
+//   0  t <  len: out[t] = in[len-1-t]   t >= len: out[t] = 0
+//   1  t <  len: out[t] += in[len-1-t]  t >= len: untouched
+//   2  t <  len: untouched              t >= len: out[t] = 0        (in unused)
+//   3  t <  len: out[t] = in[t]         t >= len: out[t] = 0        (masked copy, no reversal)
+__global__ void k_reverse_streams(const float *__restrict__ in, int in_stride, int S, int T, int cols, const int *__restrict__ lens,
+                                  float *__restrict__ out, int out_stride, int mode, int vec) {
+  const int row = blockIdx.x, s = row % S, t = row / S;
+  int len = lens[s];
+  len = len < 0 ? 0 : len > T ? T : len;
+  const bool valid = t < len;
+  if ((mode == 1 && !valid) || (mode == 2 && valid)) return;
+  float *op = out + (size_t)row * out_stride;
+  const int c0 = blockIdx.y * blockDim.x + threadIdx.x, step = gridDim.y * blockDim.x;
+  if (!valid) {
+    if (vec) {
+      for (int c = c0 * 4; c < cols; c += step * 4) *reinterpret_cast<float4 *>(op + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      for (int c = c0; c < cols; c += step) op[c] = 0.f;
+    }
+    return;
+  }
+  const int src = mode == 3 ? row : (len - 1 - t) * S + s;
+  const float *ip = in + (size_t)src * in_stride;
+  if (vec) {
+    for (int c = c0 * 4; c < cols; c += step * 4) {
+      float4 v = *reinterpret_cast<const float4 *>(ip + c);
+      if (mode == 1) {
+        const float4 o = *reinterpret_cast<const float4 *>(op + c);
+        v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
+      }
+      *reinterpret_cast<float4 *>(op + c) = v;
+    }
+  } else {
+    for (int c = c0; c < cols; c += step) op[c] = mode == 1 ? op[c] + ip[c] : ip[c];
   }
 }
 
@@ -127,6 +168,16 @@ hipError_t launch_pack_streams(const float *feats, int dim, int feat_stride, con
   const int gx = (per + bx - 1) / bx;
   return launch(k_pack_streams, dim3(gx, T * S), dim3(bx), 0, st, LaunchProbe{}, feats, dim, feat_stride, desc, S, shift, out, out_stride, reset,
                 vec);
+}
+hipError_t launch_reverse_streams(const float *in, int in_stride, int S, int T, int cols, const int *lens, float *out, int out_stride,
+                                  int mode, hipStream_t st) {
+  const bool in_ok = mode == 2 || (in_stride % 4 == 0 && al16(in));
+  const int vec = cols % 4 == 0 && out_stride % 4 == 0 && al16(out) && in_ok;
+  const int per = vec ? cols / 4 : cols;
+  const int bx = per <= 64 ? 64 : per <= 128 ? 128 : 256;
+  const int gy = (per + bx - 1) / bx;
+  return launch(k_reverse_streams, dim3(T * S, gy), dim3(bx), 0, st, LaunchProbe{}, in, in_stride, S, T, cols, lens, out, out_stride,
+                mode, vec);
 }
 hipError_t launch_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row, float *out, int out_stride,
                                       int mode, const float *log_prior, float prior_scale, hipStream_t st) {
