@@ -345,6 +345,35 @@ klstm_status klstm_log_softmax_scatter(const float *in, int rows, int cols, int 
 klstm_status klstm_reverse_streams(const float *in, int in_stride, int S, int T, int cols, const int *lens_dev, float *out, int out_stride,
                                    int mode, void *hip_stream);
 
+/* Connectionist temporal classification over whole utterances (include/klstm_nnet.hpp class Ctc): the
+ * sequence-level objective of a net that ends in <Softmax>, for label sequences without an alignment.  Stateless, asynchronous on
+ * hip_stream, decided entirely on the device (no host round trip, no error return for a bad utterance).
+ *   net_out [T*S x K]    posteriors as <Softmax> writes them, row t*S + s, row stride `stride` elements; read, never modified.
+ *                        log y is taken as log(max(y, FLT_MIN))
+ *   lens_dev [S]         frames of the utterance in stream s, which starts at t = 0 (the array of SetSeqLengths); 0 = idle stream
+ *   labels_dev, label_offsets_dev [S+1]   CSR: the labels of stream s are labels_dev[off[s] .. off[s+1]), values in [0, K) except `blank`
+ *   blank                the blank's index, any value in [0, K)
+ *   diff [T*S x K]       the gradient with respect to the SOFTMAX INPUT, as Xent produces it (SoftmaxLayer passes it through):
+ *                        diff(t,s,k) = y(t,s,k) - gamma(t,s,k), gamma = the posterior occupation of class k at frame t (sums to 1 over
+ *                        k on a valid frame).  Rows t >= lens[s] are WRITTEN as zero.  Must not overlap net_out
+ *   utt_loss_dev [S]     -log p(labels | x); 0 for an idle stream, +inf for a rejected one
+ *   totals_dev           NULL, or four doubles on the device that this minibatch is ADDED to, streams in order: sum of the losses of
+ *                        the utterances counted, utterances counted, utterances rejected, frames of the utterances counted
+ *   workspace            klstm_ctc_workspace_bytes(T, S, max_label_len) bytes of device memory, 16-byte aligned: both chains' rows are
+ *                        kept, 2 * T*S * (2 max_label_len + 1) floats (1.07 GB at T*S = 65535 with 1023 labels; 39 MB at T = 1000,
+ *                        S = 16, 150 labels).  The label capacity (and with it the launch geometry) follows from workspace_bytes.
+ * REJECTED (infeasible) utterances: lens[s] < L + (number of adjacent equal labels), a label outside [0, K) or equal to blank, lens[s]
+ * outside [0, T], or more labels than the workspace was sized for.  Their diff rows are zero, their loss +inf, they count as rejected
+ * and not in the loss sum.  An empty label sequence is feasible (all blank).
+ * Bit-identical from run to run and independent of which stream an utterance sits in: no floating-point atomics; a class that appears
+ * several times in a label sequence (and the blank) is summed in a fixed order.
+ * Limits: S <= 32, T * S <= 65535, K <= 32768, max_label_len <= 1023; beyond them KLSTM_ERR_SHAPE and nothing is launched
+ * (klstm_ctc_workspace_bytes answers 0 and leaves the message in klstm_last_error()). */
+size_t klstm_ctc_workspace_bytes(int T, int S, int max_label_len);
+klstm_status klstm_ctc_eval(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *labels_dev,
+                            const int *label_offsets_dev, int blank, float *diff, int diff_stride, float *utt_loss_dev,
+                            double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Engine knobs (not part of the reference interface).  Keys:
  *   "graph"   0/1/2  issue plain stream launches (default 0: measured equal or faster at every stream count while the host
  *                  thread keeps ahead, and indifferent to callers that hand in fresh buffers every minibatch) or replay the

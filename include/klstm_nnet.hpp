@@ -5,6 +5,7 @@
 // google/nnetbin/bd-nnet-train-lstm-streams.cc (:143-304) on in-memory utterances.
 // Header-only C++ over the C-ABI (klstm.h); no HIP or Kaldi headers needed.
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <memory>
 
@@ -488,6 +489,138 @@ inline TrainLstmStreamsStats TrainLstmStreams(Nnet *nnet, const std::vector<Utte
   st.frame_accuracy = xent.FrameAccuracy();
   if (report) *report = xent.Report();
   return st;
+}
+
+// Connectionist temporal classification on whole utterances (klstm_ctc_eval, klstm.h; not in the reference, whose only objective is
+// the frame-level Xent above).  diff is the derivative with respect to the Softmax INPUT, like Xent's (SoftmaxLayer passes it on).
+// The statistics stay on the device (four doubles that every Eval adds to) and are read when somebody asks: once per Report().
+class Ctc {
+ public:
+  explicit Ctc(int32 blank = 0) : blank_(blank) {}
+  ~Ctc() { klstm_free(ws_); klstm_free(lens_); klstm_free(lab_); klstm_free(off_); klstm_free(loss_); klstm_free(tot_); }
+  Ctc(const Ctc &) = delete;
+  Ctc &operator=(const Ctc &) = delete;
+
+  // net_out [T*num_stream x K] posteriors (row t*S + s); lens: frames per stream (0 = idle), labels: per stream.  Utterances that
+  // cannot be aligned (klstm.h: too short for their labels, a label outside [0, K) or equal to the blank) get zero diff rows and are
+  // counted as rejected, on the device.  Only the shape is checked here.
+  void Eval(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &labels,
+            DeviceMatrix *diff) {
+    KLSTM_ASSERT((int32)lens.size() == num_stream);
+    Grow(&lens_, &lens_cap_, (size_t)num_stream * sizeof(int32));
+    KCheck(klstm_memcpy_h2d(lens_, lens.data(), (size_t)num_stream * sizeof(int32), nullptr));
+    Eval(net_out, num_stream, (const int32 *)lens_, labels, diff);
+  }
+  // the same with the lengths already on the device (the array SetSeqLengths was given)
+  void Eval(const DeviceMatrix &net_out, int32 num_stream, const int32 *lens_dev, const std::vector<std::vector<int32> > &labels,
+            DeviceMatrix *diff) {
+    const int32 rows = net_out.NumRows(), K = net_out.NumCols();
+    KLSTM_ASSERT(num_stream > 0 && rows > 0 && rows % num_stream == 0 && (int32)labels.size() == num_stream && lens_dev);
+    const int32 T = rows / num_stream;
+    std::vector<int32> off(1, 0), flat;
+    size_t longest = 0;
+    for (const auto &l : labels) { flat.insert(flat.end(), l.begin(), l.end()); off.push_back((int32)flat.size()); longest = std::max(longest, l.size()); }
+    if (flat.empty()) flat.push_back(0);
+    const size_t need = klstm_ctc_workspace_bytes(T, num_stream, (int)longest);
+    if (need == 0) KLSTM_ERR("klstm: " << klstm_last_error());
+    Grow(&ws_, &ws_cap_, need);
+    Grow(&lab_, &lab_cap_, flat.size() * sizeof(int32));
+    Grow(&off_, &off_cap_, off.size() * sizeof(int32));
+    Grow(&loss_, &loss_cap_, (size_t)num_stream * sizeof(BaseFloat));
+    if (!tot_) { void *p; KCheck(klstm_malloc(&p, 4 * sizeof(double))); tot_ = (double *)p; KCheck(klstm_memset_zero(tot_, 4 * sizeof(double), nullptr)); }
+    KCheck(klstm_memcpy_h2d(lab_, flat.data(), flat.size() * sizeof(int32), nullptr));
+    KCheck(klstm_memcpy_h2d(off_, off.data(), off.size() * sizeof(int32), nullptr));
+    diff->Resize(rows, K, false);
+    MatrixView y = net_out.View(), dv = diff->View();
+    KCheck(klstm_ctc_eval(y.Data(), T, num_stream, K, y.Stride(), lens_dev, (const int32 *)lab_, (const int32 *)off_, blank_, dv.Data(),
+                          dv.Stride(), (BaseFloat *)loss_, tot_, ws_, need, nullptr));
+    num_stream_ = num_stream;
+  }
+  // -log p(labels | x) of the streams of the last Eval (+inf: rejected, 0: idle).  Synchronises.
+  void UttLoss(std::vector<BaseFloat> *loss) const {
+    loss->assign(num_stream_, 0.f);
+    if (num_stream_) KCheck(klstm_memcpy_d2h(loss->data(), loss_, (size_t)num_stream_ * sizeof(BaseFloat), nullptr));
+  }
+  double AvgLoss() const { Fetch(); return h_[0] / h_[1]; }                // per utterance counted
+  double AvgLossPerFrame() const { Fetch(); return h_[0] / h_[3]; }
+  double NumUtterances() const { Fetch(); return h_[1]; }
+  double NumRejected() const { Fetch(); return h_[2]; }
+  double Frames() const { Fetch(); return h_[3]; }
+  std::string Report() const {
+    Fetch();
+    std::ostringstream oss;
+    oss << "AvgLoss: " << h_[0] / h_[1] << " (Ctc) per utterance, " << h_[0] / h_[3] << " per frame, [" << h_[1] << " utterances, " << h_[3]
+        << " frames, " << h_[2] << " rejected]" << std::endl;
+    return oss.str();
+  }
+ private:
+  static void Grow(void **p, size_t *cap, size_t need) {
+    if (need <= *cap) return;
+    klstm_free(*p); *p = nullptr; *cap = 0;
+    KCheck(klstm_malloc(p, need));
+    *cap = need;
+  }
+  void Fetch() const {                                                      // one small copy per question, none per minibatch
+    h_[0] = h_[1] = h_[2] = h_[3] = 0;
+    if (tot_) KCheck(klstm_memcpy_d2h(h_, tot_, 4 * sizeof(double), nullptr));
+  }
+  int32 blank_, num_stream_ = 0;
+  void *ws_ = nullptr, *lens_ = nullptr, *lab_ = nullptr, *off_ = nullptr, *loss_ = nullptr;
+  size_t ws_cap_ = 0, lens_cap_ = 0, lab_cap_ = 0, off_cap_ = 0, loss_cap_ = 0;
+  double *tot_ = nullptr;
+  mutable double h_[4] = {0, 0, 0, 0};
+};
+
+struct TrainCtcOptions {
+  NnetTrainOptions trn_opts;
+  int32 num_stream = 4, blank = 0, max_frames = 0;       // max_frames 0: 65535 / num_stream
+  bool sort_by_length = true, crossvalidate = false;
+};
+struct TrainCtcStats {
+  int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
+  double num_rejected = 0, total_frames = 0, seconds = 0, avg_loss = 0, avg_loss_per_frame = 0;
+};
+
+// One pass over the utterances, num_stream whole utterances per minibatch, for unidirectional and bidirectional stacks alike: the
+// lengths go to every component (the bidirectional layer needs them), every stream starts from zero state (a unidirectional
+// <LstmProjectedStreams> stack through Reset; the bidirectional layer resets itself), and a unidirectional layer simply runs on
+// through the padding: padding follows every valid frame and its diff rows are zero.  every_batch (optional) sees each minibatch
+// after Ctc::Eval: (batch, net_out, obj_diff, ctc).
+template <class F>
+inline TrainCtcStats TrainCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const TrainCtcOptions &o, std::string *report,
+                                             F every_batch) {
+  nnet->SetTrainOptions(o.trn_opts);
+  WholeUtteranceBatcher batcher(&utts, o.num_stream, o.sort_by_length, o.max_frames);
+  Ctc ctc(o.blank);
+  UtteranceBatch b;
+  DeviceMatrix feat_dev, nnet_out, obj_diff;
+  TrainCtcStats st;
+  std::vector<int> all(o.num_stream, 1);
+  const auto t0 = std::chrono::steady_clock::now();
+  while (batcher.Next(&b)) {
+    nnet->SetSeqLengths(b.lens);
+    nnet->Reset(all);
+    feat_dev.CopyFromHost(b.feat.data(), b.num_frames * b.num_stream, b.dim);
+    nnet->Propagate(feat_dev.View(), &nnet_out);
+    ctc.Eval(nnet_out, b.num_stream, b.lens, b.labels, &obj_diff);
+    every_batch(b, nnet_out, obj_diff, ctc);
+    if (!o.crossvalidate) nnet->Backpropagate(obj_diff.View(), nullptr);
+    st.num_minibatches++;
+  }
+  KCheck(klstm_stream_synchronize(nullptr));
+  st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  st.num_done = batcher.NumDone();
+  st.num_skipped = batcher.NumSkipped();
+  st.num_rejected = ctc.NumRejected();
+  st.total_frames = ctc.Frames();
+  st.avg_loss = ctc.AvgLoss();
+  st.avg_loss_per_frame = ctc.AvgLossPerFrame();
+  if (report) *report = ctc.Report();
+  return st;
+}
+inline TrainCtcStats TrainCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const TrainCtcOptions &o,
+                                             std::string *report = nullptr) {
+  return TrainCtcWholeUtterances(nnet, utts, o, report, [](const UtteranceBatch &, const DeviceMatrix &, const DeviceMatrix &, const Ctc &) {});
 }
 
 }  // namespace klstm_kaldi

@@ -2,8 +2,12 @@
 // google/nnetbin/bd-nnet-train-lstm-streams.cc (:128-206) that defines exactly which `in` rows, reset
 // flags, padded targets and frame mask the component sees.  Kaldi table I/O is replaced by an in-memory
 // utterance list (file plumbing is out of scope); the stream book-keeping is the reference's.
+// WholeUtteranceBatcher (not in the reference) hands out minibatches of whole utterances for the bidirectional layer and the CTC
+// objective.
 #pragma once
+#include <algorithm>
 #include <cstring>
+#include <numeric>
 #include <vector>
 
 #include "klstm_kaldi_io.hpp"
@@ -14,6 +18,7 @@ struct Utterance {
   int32 num_frames = 0, dim = 0;
   std::vector<BaseFloat> feats;     // [num_frames x dim] row-major
   std::vector<int32> targets;       // one pdf-id per frame (a one-hot Posterior)
+  std::vector<int32> labels;        // the label sequence of the utterance, no blanks (CTC; any length, also empty)
 };
 
 struct StreamBatch {
@@ -80,6 +85,66 @@ class MultiStreamBatcher {
   std::vector<int32> curt_, lent_;
   std::vector<int> flags_;
   int32 num_done_, num_other_error_;
+};
+
+// A minibatch of up to num_stream WHOLE utterances, each starting at t = 0 of its stream.
+struct UtteranceBatch {
+  int32 num_stream = 0, num_frames = 0, dim = 0;   // num_frames = T = the longest utterance of the minibatch
+  std::vector<BaseFloat> feat;                    // [T*num_stream x dim], time-major rows t*S+s, zero rows behind the end of an utterance
+  std::vector<int32> lens;                        // frames per stream, 0 = the stream is idle (the last minibatch)
+  std::vector<std::vector<int32> > labels;        // per stream
+  std::vector<int32> utt_index;                   // per stream: index into the utterance list, -1 = idle
+  int32 NumValidFrames() const { return std::accumulate(lens.begin(), lens.end(), 0); }
+};
+
+// Hands every utterance out exactly once, num_stream at a time.  sort_by_length: longest first (stable: equal lengths keep the
+// order of the list), which keeps the padding of a minibatch small.  Utterances longer than max_frames (default: 65535 / num_stream,
+// the row limit of klstm_ctc_eval and klstm_pack_streams) and empty ones are skipped and counted.  Pure host code.
+class WholeUtteranceBatcher {
+ public:
+  WholeUtteranceBatcher(const std::vector<Utterance> *utts, int32 num_stream, bool sort_by_length = true, int32 max_frames = 0)
+      : utts_(utts), S_(num_stream), pos_(0), num_skipped_(0) {
+    KLSTM_ASSERT(num_stream > 0 && max_frames >= 0);
+    const int32 cap = max_frames > 0 ? max_frames : 65535 / num_stream;
+    for (size_t i = 0; i < utts->size(); i++) {
+      const Utterance &u = (*utts)[i];
+      if (u.num_frames <= 0 || u.num_frames > cap) { num_skipped_++; continue; }
+      KLSTM_ASSERT(u.feats.size() == (size_t)u.num_frames * u.dim);
+      order_.push_back((int32)i);
+    }
+    if (sort_by_length)
+      std::stable_sort(order_.begin(), order_.end(), [utts](int32 a, int32 b) { return (*utts)[a].num_frames > (*utts)[b].num_frames; });
+  }
+  bool Next(UtteranceBatch *b) {
+    if (pos_ >= order_.size()) return false;
+    const size_t n = std::min(order_.size() - pos_, (size_t)S_);
+    int32 T = 0;
+    for (size_t s = 0; s < n; s++) T = std::max(T, (*utts_)[order_[pos_ + s]].num_frames);
+    const int32 dim = (*utts_)[order_[pos_]].dim;
+    b->num_stream = S_; b->num_frames = T; b->dim = dim;
+    b->feat.assign((size_t)T * S_ * dim, 0.f);
+    b->lens.assign(S_, 0);
+    b->labels.assign(S_, std::vector<int32>());
+    b->utt_index.assign(S_, -1);
+    for (size_t s = 0; s < n; s++) {
+      const Utterance &u = (*utts_)[order_[pos_ + s]];
+      if (u.dim != dim) KLSTM_ERR("WholeUtteranceBatcher: feature dimension " << u.dim << " != " << dim);
+      for (int32 t = 0; t < u.num_frames; t++)
+        std::memcpy(&b->feat[((size_t)t * S_ + s) * dim], &u.feats[(size_t)t * dim], (size_t)dim * sizeof(BaseFloat));
+      b->lens[s] = u.num_frames; b->labels[s] = u.labels; b->utt_index[s] = order_[pos_ + s];
+    }
+    pos_ += n;
+    return true;
+  }
+  int32 NumDone() const { return (int32)pos_; }
+  int32 NumSkipped() const { return num_skipped_; }
+
+ private:
+  const std::vector<Utterance> *utts_;
+  int32 S_;
+  size_t pos_;
+  int32 num_skipped_;
+  std::vector<int32> order_;
 };
 
 }  // namespace klstm_kaldi

@@ -13,5 +13,6 @@ from .binding import (Engine, KlstmError, RcclComm, OneshotAllreduce, lib_path, 
                       reverse_streams, REVERSE_SET, REVERSE_ADD, REVERSE_ZERO_PAD, REVERSE_MASK_COPY)
 from .batcher import MultiStreamBatcher  # noqa: F401,E402
 from .blstm import BidirectionalLstm  # noqa: F401,E402
+from .ctc import ctc_eval, ctc_workspace_bytes  # noqa: F401,E402
 from .dp import (DataParallelLstm, DataParallelNnet, LstmDP, AffineDP, SoftmaxXentDP,  # noqa: F401,E402
                  shard_time_major)

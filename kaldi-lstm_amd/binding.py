@@ -112,6 +112,9 @@ def load_library():
     lib.klstm_comm_count.argtypes = [P, ctypes.POINTER(I)]
     lib.klstm_allreduce_grads.argtypes = [P, P]
     lib.klstm_allreduce_buffer.argtypes = [P, ctypes.c_size_t, P, P]
+    lib.klstm_ctc_workspace_bytes.argtypes = [I, I, I]
+    lib.klstm_ctc_workspace_bytes.restype = ctypes.c_size_t
+    lib.klstm_ctc_eval.argtypes = [P, I, I, I, I, P, P, P, I, P, I, P, P, P, ctypes.c_size_t, P]
     _LIB = lib
     return lib
 

@@ -2040,6 +2040,31 @@ klstm_status klstm_reverse_streams(const float *in, int in_stride, int S, int T,
   HIPCHK(launch_reverse_streams(in, in_stride, S, T, cols, lens_dev, out, out_stride, mode, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
+size_t klstm_ctc_workspace_bytes(int T, int S, int max_label_len) {
+  if (T <= 0 || S <= 0 || S > 32 || (long)T * S > 65535 || max_label_len < 0 || max_label_len > 1023) {
+    fail(KLSTM_ERR_SHAPE, "klstm_ctc_workspace_bytes: T %d, streams %d, label length %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, L <= 1023", T, S, max_label_len);
+    return 0;
+  }
+  return ctc_workspace_bytes(T, S, max_label_len);
+}
+klstm_status klstm_ctc_eval(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *labels_dev,
+                            const int *label_offsets_dev, int blank, float *diff, int diff_stride, float *utt_loss_dev,
+                            double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  if (T <= 0 || S <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: bad size (T %d, streams %d, K %d)", T, S, K);
+  if (S > 32 || (long)T * S > 65535 || K > 32768)
+    return fail(KLSTM_ERR_SHAPE, "klstm_ctc_eval: T %d, streams %d, K %d outside S <= 32, T * S <= 65535, K <= 32768", T, S, K);
+  if (!net_out || !lens_dev || !labels_dev || !label_offsets_dev || !diff || !utt_loss_dev || !workspace)
+    return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: null argument");
+  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: blank %d outside [0, %d)", blank, K);
+  if (stride < K || diff_stride < K) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: row stride below K (%d / %d < %d)", stride, diff_stride, K);
+  if (net_out == diff) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: diff == net_out (the posteriors are read while diff is written)");
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: workspace must be 16-byte aligned");
+  const int lcap = ctc_label_capacity(T, S, workspace_bytes);
+  if (lcap < 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: workspace of %zu bytes is below klstm_ctc_workspace_bytes(%d, %d, 0)", workspace_bytes, T, S);
+  HIPCHK(launch_ctc(net_out, T, S, K, stride, lens_dev, labels_dev, label_offsets_dev, blank, diff, diff_stride, utt_loss_dev, totals_dev,
+                    workspace, lcap, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
 klstm_status klstm_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row_dev, float *out,
                                        int out_stride, int mode, const float *log_prior_dev, float prior_scale, void *hip_stream) {
   if ((!in || !dst_row_dev || !out) && rows > 0) return fail(KLSTM_ERR_ARG, "klstm_log_softmax_scatter: null argument");

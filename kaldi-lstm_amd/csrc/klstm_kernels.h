@@ -316,6 +316,14 @@ hipError_t launch_reverse_streams(const float *in, int in_stride, int S, int T, 
                                   int mode, hipStream_t st);
 hipError_t launch_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row, float *out, int out_stride,
                                       int mode, const float *log_prior, float prior_scale, hipStream_t st);
+// CTC on whole utterances (klstm_ctc.hip): klstm_ctc_eval / klstm_ctc_workspace_bytes of include/klstm.h.  The workspace: per stream a
+// feasibility word and two ints per label position (next position of the same class, first-of-its-class flag), then the alpha and the
+// beta rows [S][T][Npad].  Lcap = the label length the workspace was sized for (the chain's geometry follows from it).
+struct CtcWs { int *info, *link; float *A, *B; int Npad, Lcap; };
+size_t ctc_workspace_bytes(int T, int S, int Lcap);
+int ctc_label_capacity(int T, int S, size_t bytes);
+hipError_t launch_ctc(const float *y, int T, int S, int K, int stride, const int *lens, const int *labels, const int *loff, int blank,
+                      float *diff, int dstride, float *utt_loss, double *totals, void *workspace, int Lcap, hipStream_t st);
 hipError_t launch_xent(const float *y, int rows, int cols, int stride, const int *target, const float *mask, float *diff,
                        int diff_stride, float *row_xent, float *row_correct, hipStream_t st);
 hipError_t launch_softmax_xent(const float *in, int rows, int cols, int in_stride, float *post, int post_stride, const int *target,

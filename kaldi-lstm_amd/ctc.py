@@ -1,0 +1,69 @@
+"""ctc_eval: connectionist temporal classification over whole utterances (klstm_ctc_eval of include/klstm.h) on torch
+CUDA tensors.  Plumbing only: the label lists become the CSR arrays of the C-ABI, the workspace is cached per shape."""
+import ctypes
+
+import numpy as np
+
+from .binding import _chk, _sp, load_library
+
+_WS = {}          # (device, T, S, label capacity) -> uint8 workspace tensor
+
+
+def ctc_workspace_bytes(T, S, max_label_len):
+    lib = load_library()
+    n = lib.klstm_ctc_workspace_bytes(int(T), int(S), int(max_label_len))
+    if n == 0:
+        _chk(2)
+    return n
+
+
+def pack_labels(labels, device):
+    """list of S label sequences -> (labels int32 [max(1, total)], offsets int32 [S+1], longest) on `device`"""
+    import torch
+    off = np.zeros(len(labels) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(lab) for lab in labels])
+    flat = np.concatenate([np.asarray(lab, dtype=np.int32).ravel() for lab in labels] + [np.zeros(0, np.int32)])
+    if flat.size == 0:
+        flat = np.zeros(1, np.int32)
+    longest = max([len(lab) for lab in labels] + [0])
+    return torch.from_numpy(flat).to(device), torch.from_numpy(off).to(device), longest
+
+
+def ctc_eval(net_out, lens, labels, blank=0, diff=None, totals=None, stream=None):
+    """net_out [T*S, K] float32 CUDA posteriors (row t*S + s; a column window with a larger row stride is fine); lens: S lengths (a
+    sequence, or an int32 CUDA tensor); labels: a list of S label sequences, or what pack_labels() returned (a caller that keeps
+    the arrays on the device).  Returns (utt_loss [S] float32, diff [T*S, K]): diff = y - gamma, the gradient with respect to the
+    softmax input, zero on padding rows and on every row of an idle or rejected stream; utt_loss = -log p(labels | x), +inf for a
+    rejected stream, 0 for an idle one.  totals: a float64[4] CUDA tensor that loss sum, utterances counted, utterances rejected
+    and frames are added to.  Nothing synchronises."""
+    import torch
+    lib = load_library()
+    dev = net_out.device
+    assert net_out.is_cuda and net_out.dtype == torch.float32 and net_out.dim() == 2 and net_out.stride(1) == 1
+    if isinstance(lens, torch.Tensor) and lens.is_cuda:
+        assert lens.dtype == torch.int32 and lens.is_contiguous()
+        lens_dev = lens
+    else:
+        lens_dev = torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
+    S = lens_dev.numel()
+    assert S > 0 and net_out.shape[0] % S == 0, "rows must be T * len(lens)"
+    T, K = net_out.shape[0] // S, net_out.shape[1]
+    lab_dev, off_dev, longest = labels if isinstance(labels, tuple) else pack_labels(labels, dev)
+    assert off_dev.numel() == S + 1 and lab_dev.dtype == torch.int32 and off_dev.dtype == torch.int32
+    if diff is None:
+        diff = torch.empty(T * S, K, device=dev)
+    assert diff.is_cuda and diff.dtype == torch.float32 and diff.shape == (T * S, K) and diff.stride(1) == 1
+    nbytes = ctc_workspace_bytes(T, S, longest)
+    key = (dev.index, T, S, longest)
+    ws = _WS.get(key)
+    if ws is None:
+        if len(_WS) >= 8:
+            _WS.clear()
+        ws = _WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    utt_loss = torch.empty(S, device=dev)
+    if totals is not None:
+        assert totals.is_cuda and totals.dtype == torch.float64 and totals.numel() == 4 and totals.is_contiguous()
+    _chk(lib.klstm_ctc_eval(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), lab_dev.data_ptr(), off_dev.data_ptr(),
+                            int(blank), diff.data_ptr(), diff.stride(0), utt_loss.data_ptr(),
+                            totals.data_ptr() if totals is not None else None, ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    return utt_loss, diff
