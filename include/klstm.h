@@ -374,6 +374,43 @@ klstm_status klstm_ctc_eval(const float *net_out, int T, int S, int K, int strid
                             const int *label_offsets_dev, int blank, float *diff, int diff_stride, float *utt_loss_dev,
                             double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/* CTC best-path (greedy) decoding of whole utterances and the token error rate against reference label sequences (include/klstm_nnet.hpp
+ * class CtcGreedyDecoder).  Stateless, asynchronous on hip_stream, decided entirely on the device.
+ *   net_out [T*S x K]    posteriors, row t*S + s, row stride `stride` elements (any stride >= K, any 4-byte aligned start: a column window
+ *                        is fine); read, never modified; columns beyond K are never touched
+ *   lens_dev [S]         frames of the utterance in stream s, which starts at t = 0; 0 = idle stream
+ *   blank                the blank's index, any value in [0, K)
+ *   class_weight_dev     NULL, or K floats w: the winner of a frame is argmax_k key(y[k] * w[k]) with ONE fp32 multiply rounded to nearest
+ *                        (label priors enter as w[k] = prior[k]^-alpha, computed by the caller); NULL = no multiply at all.
+ *                        key(v) = v, or -inf where v is NaN (a NaN never wins); ties go to the LOWEST column; a row of all NaN gives 0
+ *   hyp_dev [S*T]        the hypothesis of stream s at hyp_dev[s*T .. s*T + hyp_len_dev[s]): the classes of the frames t with
+ *                        c(t) != blank and (t == 0 or c(t-1) != c(t)), in order.  Entries beyond hyp_len are left alone
+ *   hyp_len_dev [S]      its length
+ *   score_dev            NULL, or [S]: sum over the valid frames of log(max(y[t,s,best], FLT_MIN)) of the UNWEIGHTED posterior of the
+ *                        winner (a NaN there counts as FLT_MIN), accumulated in double in a fixed order, stored as float
+ *   frame_class_dev      NULL, or [T*S]: the winner of row t*S + s (the best-path alignment); -1 on padding rows (t >= lens[s]) and on
+ *                        every row of an idle or rejected stream.  Those rows of net_out are NOT READ and may hold anything
+ *   ref_labels_dev, ref_offsets_dev [S+1]   both NULL (no scoring), or the CSR pair klstm_ctc_eval takes
+ *   errors_dev           NULL, or [S]: the Levenshtein distance (substitution, insertion, deletion cost 1 each) between the hypothesis
+ *                        and the reference of stream s, exact; -1 where the stream is not counted.  Needs the references
+ *   totals_dev           NULL, or five doubles on the device that this minibatch is ADDED to by one thread, streams in order (every term
+ *                        is an integer): edit errors, reference tokens, hypothesis tokens, utterances counted, utterances with at least
+ *                        one error.  Needs the references
+ *   workspace            klstm_ctc_decode_workspace_bytes(T, S, max_ref_len) bytes of device memory, 16-byte aligned (8 bytes per row and
+ *                        a few hundred more; the edit-distance row lives in registers, so max_ref_len is only checked against the limit).
+ *                        One call at a time per workspace
+ * STATUS of a stream: lens[s] == 0 idle, lens[s] outside [0, T] rejected: hyp_len 0, score 0, errors -1, not counted, frame_class -1.
+ * A reference with a label outside [0, K) or equal to blank, or with more than 1023 labels: hypothesis and score as usual, errors -1,
+ * not counted.  An empty reference is legal (errors = hyp_len).
+ * Bit-identical from run to run and independent of which stream an utterance sits in: no floating-point atomics.
+ * Limits: S <= 32, T * S <= 65535, 2 <= K <= 32768, max_ref_len <= 1023; beyond them KLSTM_ERR_SHAPE and nothing is launched
+ * (klstm_ctc_decode_workspace_bytes answers 0 and leaves the message in klstm_last_error()). */
+size_t klstm_ctc_decode_workspace_bytes(int T, int S, int max_ref_len);
+klstm_status klstm_ctc_decode(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
+                              const float *class_weight_dev, int *hyp_dev, int *hyp_len_dev, float *score_dev, int *frame_class_dev,
+                              const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev, double *totals_dev,
+                              void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Engine knobs (not part of the reference interface).  Keys:
  *   "graph"   0/1/2  issue plain stream launches (default 0: measured equal or faster at every stream count while the host
  *                  thread keeps ahead, and indifferent to callers that hand in fresh buffers every minibatch) or replay the

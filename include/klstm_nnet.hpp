@@ -623,4 +623,176 @@ inline TrainCtcStats TrainCtcWholeUtterances(Nnet *nnet, const std::vector<Utter
   return TrainCtcWholeUtterances(nnet, utts, o, report, [](const UtteranceBatch &, const DeviceMatrix &, const DeviceMatrix &, const Ctc &) {});
 }
 
+// CTC best-path decoding of whole utterances and the token error rate against reference label sequences (klstm_ctc_decode, klstm.h;
+// INTEGRATION.md 3e).  The five totals stay on the device and are read when somebody asks, like Ctc's.
+class CtcGreedyDecoder {
+ public:
+  explicit CtcGreedyDecoder(int32 blank = 0) : blank_(blank) {}
+  ~CtcGreedyDecoder() {
+    klstm_free(ws_); klstm_free(lens_); klstm_free(lab_); klstm_free(off_); klstm_free(hyp_); klstm_free(hlen_); klstm_free(score_);
+    klstm_free(fc_); klstm_free(err_); klstm_free(w_); klstm_free(tot_);
+  }
+  CtcGreedyDecoder(const CtcGreedyDecoder &) = delete;
+  CtcGreedyDecoder &operator=(const CtcGreedyDecoder &) = delete;
+
+  // One weight per class: the winner of a frame is argmax_k y[k] * w[k] (label priors: w[k] = prior[k]^-alpha).  Empty: none.
+  void SetClassWeights(const std::vector<BaseFloat> &w) {
+    num_weights_ = (int32)w.size();
+    if (w.empty()) return;
+    Grow(&w_, &w_cap_, w.size() * sizeof(BaseFloat));
+    KCheck(klstm_memcpy_h2d(w_, w.data(), w.size() * sizeof(BaseFloat), nullptr));
+  }
+  // net_out [T*num_stream x K] posteriors (row t*S + s); lens: frames per stream (0 = idle); refs: empty (no scoring) or one reference
+  // per stream; hyps (optional): the hypothesis of every stream.  Asking for hyps synchronises; the rest stays on the device.
+  void Decode(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &refs,
+              std::vector<std::vector<int32> > *hyps) {
+    KLSTM_ASSERT((int32)lens.size() == num_stream);
+    Grow(&lens_, &lens_cap_, (size_t)num_stream * sizeof(int32));
+    KCheck(klstm_memcpy_h2d(lens_, lens.data(), (size_t)num_stream * sizeof(int32), nullptr));
+    Decode(net_out, num_stream, (const int32 *)lens_, refs, hyps);
+  }
+  void Decode(const DeviceMatrix &net_out, int32 num_stream, const int32 *lens_dev, const std::vector<std::vector<int32> > &refs,
+              std::vector<std::vector<int32> > *hyps) {
+    const int32 rows = net_out.NumRows(), K = net_out.NumCols();
+    KLSTM_ASSERT(num_stream > 0 && rows > 0 && rows % num_stream == 0 && lens_dev && (refs.empty() || (int32)refs.size() == num_stream));
+    KLSTM_ASSERT(num_weights_ == 0 || num_weights_ == K);
+    const int32 T = rows / num_stream;
+    const bool scoring = !refs.empty();
+    const size_t need = klstm_ctc_decode_workspace_bytes(T, num_stream, 0);
+    if (need == 0) KLSTM_ERR("klstm: " << klstm_last_error());
+    Grow(&ws_, &ws_cap_, need);
+    Grow(&hyp_, &hyp_cap_, (size_t)rows * sizeof(int32));
+    Grow(&fc_, &fc_cap_, (size_t)rows * sizeof(int32));
+    Grow(&hlen_, &hlen_cap_, (size_t)num_stream * sizeof(int32));
+    Grow(&score_, &score_cap_, (size_t)num_stream * sizeof(BaseFloat));
+    Grow(&err_, &err_cap_, (size_t)num_stream * sizeof(int32));
+    if (scoring) {
+      std::vector<int32> off(1, 0), flat;
+      for (const auto &l : refs) { flat.insert(flat.end(), l.begin(), l.end()); off.push_back((int32)flat.size()); }
+      if (flat.empty()) flat.push_back(0);
+      Grow(&lab_, &lab_cap_, flat.size() * sizeof(int32));
+      Grow(&off_, &off_cap_, off.size() * sizeof(int32));
+      KCheck(klstm_memcpy_h2d(lab_, flat.data(), flat.size() * sizeof(int32), nullptr));
+      KCheck(klstm_memcpy_h2d(off_, off.data(), off.size() * sizeof(int32), nullptr));
+      if (!tot_) { void *p; KCheck(klstm_malloc(&p, 5 * sizeof(double))); tot_ = (double *)p; KCheck(klstm_memset_zero(tot_, 5 * sizeof(double), nullptr)); }
+    }
+    MatrixView y = net_out.View();
+    KCheck(klstm_ctc_decode(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, num_weights_ ? (const BaseFloat *)w_ : nullptr,
+                            (int32 *)hyp_, (int32 *)hlen_, (BaseFloat *)score_, (int32 *)fc_, scoring ? (const int32 *)lab_ : nullptr,
+                            scoring ? (const int32 *)off_ : nullptr, scoring ? (int32 *)err_ : nullptr, scoring ? tot_ : nullptr, ws_, need,
+                            nullptr));
+    num_stream_ = num_stream; rows_ = rows; scored_ = scoring;
+    if (!hyps) return;
+    std::vector<int32> n(num_stream), h((size_t)rows);
+    KCheck(klstm_memcpy_d2h(n.data(), hlen_, n.size() * sizeof(int32), nullptr));
+    KCheck(klstm_memcpy_d2h(h.data(), hyp_, h.size() * sizeof(int32), nullptr));
+    hyps->assign(num_stream, std::vector<int32>());
+    for (int32 s = 0; s < num_stream; s++) (*hyps)[s].assign(h.begin() + (size_t)s * T, h.begin() + (size_t)s * T + n[s]);
+  }
+  // of the last Decode (each synchronises): path scores, edit distances (-1: not counted; all -1 without references), frame classes
+  void UttScores(std::vector<BaseFloat> *v) const { v->assign(num_stream_, 0.f); Get(v->data(), score_, v->size() * sizeof(BaseFloat)); }
+  void UttErrors(std::vector<int32> *v) const { v->assign(num_stream_, -1); if (scored_) Get(v->data(), err_, v->size() * sizeof(int32)); }
+  void FrameClasses(std::vector<int32> *v) const { v->assign(rows_, -1); Get(v->data(), fc_, v->size() * sizeof(int32)); }
+
+  double TokenErrorRate() const { Fetch(); return h_[0] / h_[1]; }          // edit errors / reference tokens
+  double UtteranceErrorRate() const { Fetch(); return h_[4] / h_[3]; }
+  double NumUtterances() const { Fetch(); return h_[3]; }
+  double NumErrors() const { Fetch(); return h_[0]; }
+  double NumRefTokens() const { Fetch(); return h_[1]; }
+  double NumHypTokens() const { Fetch(); return h_[2]; }
+  std::string Report() const {
+    Fetch();
+    std::ostringstream oss;
+    oss << "UTT_ERROR_RATE: " << 100.0 * h_[4] / h_[3] << "% [" << h_[3] << " utterances, " << h_[0] << " errors, " << h_[1]
+        << " reference tokens, " << h_[2] << " hypothesis tokens]" << std::endl;
+    oss << "\nTOKEN_ERROR_RATE >> " << 100.0 * h_[0] / h_[1] << "% <<";
+    return oss.str();
+  }
+ private:
+  static void Grow(void **p, size_t *cap, size_t need) {
+    if (need <= *cap) return;
+    klstm_free(*p); *p = nullptr; *cap = 0;
+    KCheck(klstm_malloc(p, need));
+    *cap = need;
+  }
+  static void Get(void *dst, const void *src, size_t bytes) { if (bytes) KCheck(klstm_memcpy_d2h(dst, src, bytes, nullptr)); }
+  void Fetch() const {
+    for (double &v : h_) v = 0;
+    if (tot_) KCheck(klstm_memcpy_d2h(h_, tot_, 5 * sizeof(double), nullptr));
+  }
+  int32 blank_, num_stream_ = 0, rows_ = 0, num_weights_ = 0;
+  bool scored_ = false;
+  void *ws_ = nullptr, *lens_ = nullptr, *lab_ = nullptr, *off_ = nullptr, *hyp_ = nullptr, *hlen_ = nullptr, *score_ = nullptr, *fc_ = nullptr,
+       *err_ = nullptr, *w_ = nullptr;
+  size_t ws_cap_ = 0, lens_cap_ = 0, lab_cap_ = 0, off_cap_ = 0, hyp_cap_ = 0, hlen_cap_ = 0, score_cap_ = 0, fc_cap_ = 0, err_cap_ = 0, w_cap_ = 0;
+  double *tot_ = nullptr;
+  mutable double h_[5] = {0, 0, 0, 0, 0};
+};
+
+struct DecodeCtcOptions {
+  int32 num_stream = 4, blank = 0, max_frames = 0;       // max_frames 0: 65535 / num_stream
+  bool sort_by_length = true, score = true;              // score: the utterances' labels are references
+  std::vector<BaseFloat> class_weights;                  // empty: none
+};
+struct DecodeCtcStats {
+  int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
+  double token_error_rate = 0, utt_error_rate = 0, num_scored = 0, num_errors = 0, num_ref_tokens = 0, seconds = 0;
+};
+
+// per-stream results of one minibatch -> per-utterance results in the order of the utterance list (idle streams carry nothing)
+template <class V>
+inline void ScatterByUtterance(const UtteranceBatch &b, const std::vector<V> &per_stream, std::vector<V> *per_utt) {
+  KLSTM_ASSERT((int32)per_stream.size() == b.num_stream && (int32)b.utt_index.size() == b.num_stream);
+  for (int32 s = 0; s < b.num_stream; s++) {
+    if (b.utt_index[s] < 0) continue;
+    KLSTM_ASSERT((size_t)b.utt_index[s] < per_utt->size());
+    (*per_utt)[b.utt_index[s]] = per_stream[s];
+  }
+}
+
+// The loop of TrainCtcWholeUtterances without the objective and the backward pass: SetSeqLengths, Reset, Propagate, Decode.
+// (*hypotheses)[i] belongs to utts[i] whatever order the batcher handed them out in; an utterance the batcher skipped (empty, or
+// longer than max_frames) keeps an empty hypothesis and is counted in num_skipped.  every_batch (optional) sees each minibatch after
+// Decode: (batch, net_out, decoder).
+template <class F>
+inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
+                                               std::vector<std::vector<int32> > *hypotheses, std::string *report, F every_batch) {
+  WholeUtteranceBatcher batcher(&utts, o.num_stream, o.sort_by_length, o.max_frames);
+  CtcGreedyDecoder dec(o.blank);
+  dec.SetClassWeights(o.class_weights);
+  UtteranceBatch b;
+  DeviceMatrix feat_dev, nnet_out;
+  DecodeCtcStats st;
+  std::vector<int> all(o.num_stream, 1);
+  std::vector<std::vector<int32> > hyps;
+  const std::vector<std::vector<int32> > none;
+  if (hypotheses) hypotheses->assign(utts.size(), std::vector<int32>());
+  const auto t0 = std::chrono::steady_clock::now();
+  while (batcher.Next(&b)) {
+    nnet->SetSeqLengths(b.lens);
+    nnet->Reset(all);
+    feat_dev.CopyFromHost(b.feat.data(), b.num_frames * b.num_stream, b.dim);
+    nnet->Propagate(feat_dev.View(), &nnet_out);
+    dec.Decode(nnet_out, b.num_stream, b.lens, o.score ? b.labels : none, hypotheses ? &hyps : nullptr);
+    if (hypotheses) ScatterByUtterance(b, hyps, hypotheses);
+    every_batch(b, nnet_out, dec);
+    st.num_minibatches++;
+  }
+  KCheck(klstm_stream_synchronize(nullptr));
+  st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  st.num_done = batcher.NumDone();
+  st.num_skipped = batcher.NumSkipped();
+  st.num_scored = dec.NumUtterances();
+  st.num_errors = dec.NumErrors();
+  st.num_ref_tokens = dec.NumRefTokens();
+  st.token_error_rate = dec.TokenErrorRate();
+  st.utt_error_rate = dec.UtteranceErrorRate();
+  if (report) *report = dec.Report();
+  return st;
+}
+inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
+                                               std::vector<std::vector<int32> > *hypotheses, std::string *report = nullptr) {
+  return DecodeCtcWholeUtterances(nnet, utts, o, hypotheses, report, [](const UtteranceBatch &, const DeviceMatrix &, const CtcGreedyDecoder &) {});
+}
+
 }  // namespace klstm_kaldi

@@ -2065,6 +2065,34 @@ klstm_status klstm_ctc_eval(const float *net_out, int T, int S, int K, int strid
                     workspace, lcap, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
+size_t klstm_ctc_decode_workspace_bytes(int T, int S, int max_ref_len) {
+  if (T <= 0 || S <= 0 || S > 32 || (long)T * S > 65535 || max_ref_len < 0 || max_ref_len > 1023) {
+    fail(KLSTM_ERR_SHAPE, "klstm_ctc_decode_workspace_bytes: T %d, streams %d, reference length %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, L <= 1023", T, S, max_ref_len);
+    return 0;
+  }
+  return ctc_decode_workspace_bytes(T, S);
+}
+klstm_status klstm_ctc_decode(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
+                              const float *class_weight_dev, int *hyp_dev, int *hyp_len_dev, float *score_dev, int *frame_class_dev,
+                              const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev, double *totals_dev,
+                              void *workspace, size_t workspace_bytes, void *hip_stream) {
+  if (T <= 0 || S <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: bad size (T %d, streams %d, K %d)", T, S, K);
+  if (S > 32 || (long)T * S > 65535 || K < 2 || K > 32768)
+    return fail(KLSTM_ERR_SHAPE, "klstm_ctc_decode: T %d, streams %d, K %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768", T, S, K);
+  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !workspace) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: null argument");
+  if ((ref_labels_dev == nullptr) != (ref_offsets_dev == nullptr))
+    return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: reference labels and offsets come together or not at all");
+  if (!ref_labels_dev && (errors_dev || totals_dev)) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: errors / totals need reference labels");
+  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: blank %d outside [0, %d)", blank, K);
+  if (stride < K) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: row stride below K (%d < %d)", stride, K);
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: workspace must be 16-byte aligned");
+  if (workspace_bytes < ctc_decode_workspace_bytes(T, S))
+    return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: workspace of %zu bytes is below klstm_ctc_decode_workspace_bytes(%d, %d, .) = %zu", workspace_bytes,
+                T, S, ctc_decode_workspace_bytes(T, S));
+  HIPCHK(launch_ctc_decode(net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, hyp_dev, hyp_len_dev, score_dev, frame_class_dev,
+                           ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
 klstm_status klstm_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row_dev, float *out,
                                        int out_stride, int mode, const float *log_prior_dev, float prior_scale, void *hip_stream) {
   if ((!in || !dst_row_dev || !out) && rows > 0) return fail(KLSTM_ERR_ARG, "klstm_log_softmax_scatter: null argument");

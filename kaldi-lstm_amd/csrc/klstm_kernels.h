@@ -324,6 +324,13 @@ size_t ctc_workspace_bytes(int T, int S, int Lcap);
 int ctc_label_capacity(int T, int S, size_t bytes);
 hipError_t launch_ctc(const float *y, int T, int S, int K, int stride, const int *lens, const int *labels, const int *loff, int blank,
                       float *diff, int dstride, float *utt_loss, double *totals, void *workspace, int Lcap, hipStream_t st);
+// CTC best-path decoding and token error rate (klstm_ctc_decode.hip): klstm_ctc_decode / klstm_ctc_decode_workspace_bytes of
+// include/klstm.h.  The workspace: frame_class and frame_logp [T*S] each, four ints per stream for the totals, the ticket of the launch
+// that finishes last.
+size_t ctc_decode_workspace_bytes(int T, int S);
+hipError_t launch_ctc_decode(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int *hyp,
+                             int *hyp_len, float *score, int *frame_class, const int *refs, const int *roff, int *errors, double *totals,
+                             void *workspace, hipStream_t st);
 hipError_t launch_xent(const float *y, int rows, int cols, int stride, const int *target, const float *mask, float *diff,
                        int diff_stride, float *row_xent, float *row_correct, hipStream_t st);
 hipError_t launch_softmax_xent(const float *in, int rows, int cols, int in_stride, float *post, int post_stride, const int *target,

@@ -1,5 +1,7 @@
 """ctc_eval: connectionist temporal classification over whole utterances (klstm_ctc_eval of include/klstm.h) on torch
-CUDA tensors.  Plumbing only: the label lists become the CSR arrays of the C-ABI, the workspace is cached per shape."""
+CUDA tensors.  Plumbing only: the label lists become the CSR arrays of the C-ABI, the workspace is cached per shape.
+ctc_greedy_decode: best-path decoding and token error rate of the same posteriors (klstm_ctc_decode)."""
+import collections
 import ctypes
 
 import numpy as np
@@ -67,3 +69,73 @@ def ctc_eval(net_out, lens, labels, blank=0, diff=None, totals=None, stream=None
                             int(blank), diff.data_ptr(), diff.stride(0), utt_loss.data_ptr(),
                             totals.data_ptr() if totals is not None else None, ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
     return utt_loss, diff
+
+
+_DWS = {}         # (device, T, S) -> uint8 workspace tensor of ctc_greedy_decode
+
+CtcDecodeResult = collections.namedtuple("CtcDecodeResult", "hyp hyp_len score frame_class errors")
+
+
+def ctc_decode_workspace_bytes(T, S, max_ref_len=0):
+    lib = load_library()
+    n = lib.klstm_ctc_decode_workspace_bytes(int(T), int(S), int(max_ref_len))
+    if n == 0:
+        _chk(2)
+    return n
+
+
+def ctc_greedy_decode(net_out, lens, blank=0, class_weight=None, refs=None, totals=None, stream=None):
+    """net_out [T*S, K] float32 CUDA posteriors (row t*S + s; a column window with a larger row stride is fine); lens: S lengths (a
+    sequence, or an int32 CUDA tensor); class_weight: None or K float32 on the device (frame winner = argmax_k y[k] * w[k], one fp32
+    product; label priors go in as prior ** -alpha); refs: None, a list of S reference label sequences, or what pack_labels()
+    returned.  Returns CtcDecodeResult(hyp [S, T] int32 (row s valid up to hyp_len[s]), hyp_len [S] int32, score [S] float32,
+    frame_class [T*S] int32 (-1 on padding and idle rows), errors [S] int32 edit distances (-1: not counted) or None without refs).
+    totals: a float64[5] CUDA tensor that edit errors, reference tokens, hypothesis tokens, utterances counted and utterances with an
+    error are added to (needs refs).  Nothing synchronises; hypotheses_to_lists() does."""
+    import torch
+    lib = load_library()
+    dev = net_out.device
+    assert net_out.is_cuda and net_out.dtype == torch.float32 and net_out.dim() == 2 and net_out.stride(1) == 1
+    if isinstance(lens, torch.Tensor) and lens.is_cuda:
+        assert lens.dtype == torch.int32 and lens.is_contiguous()
+        lens_dev = lens
+    else:
+        lens_dev = torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
+    S = lens_dev.numel()
+    assert S > 0 and net_out.shape[0] % S == 0, "rows must be T * len(lens)"
+    T, K = net_out.shape[0] // S, net_out.shape[1]
+    if class_weight is not None:
+        assert class_weight.is_cuda and class_weight.dtype == torch.float32 and class_weight.numel() == K and class_weight.is_contiguous()
+    lab_dev = off_dev = errors = None
+    longest = 0
+    if refs is not None:
+        lab_dev, off_dev, longest = refs if isinstance(refs, tuple) else pack_labels(refs, dev)
+        assert off_dev.numel() == S + 1 and lab_dev.dtype == torch.int32 and off_dev.dtype == torch.int32
+        errors = torch.empty(S, dtype=torch.int32, device=dev)
+    if totals is not None:
+        assert refs is not None, "totals need refs"
+        assert totals.is_cuda and totals.dtype == torch.float64 and totals.numel() == 5 and totals.is_contiguous()
+    nbytes = ctc_decode_workspace_bytes(T, S, min(longest, 1023))       # a longer reference is the device's to refuse (errors -1)
+    key = (dev.index, T, S)
+    ws = _DWS.get(key)
+    if ws is None:
+        if len(_DWS) >= 8:
+            _DWS.clear()
+        ws = _DWS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    hyp = torch.empty(S, T, dtype=torch.int32, device=dev)
+    hyp_len = torch.empty(S, dtype=torch.int32, device=dev)
+    score = torch.empty(S, device=dev)
+    frame_class = torch.empty(T * S, dtype=torch.int32, device=dev)
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+    _chk(lib.klstm_ctc_decode(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), ptr(class_weight),
+                              hyp.data_ptr(), hyp_len.data_ptr(), score.data_ptr(), frame_class.data_ptr(), ptr(lab_dev), ptr(off_dev),
+                              ptr(errors), ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    return CtcDecodeResult(hyp, hyp_len, score, frame_class, errors)
+
+
+def hypotheses_to_lists(hyp, hyp_len):
+    """(hyp [S, T], hyp_len [S]) of ctc_greedy_decode -> S Python lists.  The one place that synchronises."""
+    h, n = hyp.cpu().numpy(), hyp_len.cpu().numpy()
+    return [h[s, :n[s]].tolist() for s in range(len(n))]
