@@ -411,6 +411,42 @@ klstm_status klstm_ctc_decode(const float *net_out, int T, int S, int K, int str
                               const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev, double *totals_dev,
                               void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/* CTC forced alignment (Viterbi) of whole utterances: the single most probable alignment of the label sequence of stream s to its
+ * frames (include/klstm_nnet.hpp class CtcAligner).  Stateless, asynchronous on hip_stream, decided
+ * entirely on the device.  net_out, lens_dev, labels_dev / label_offsets_dev and blank exactly as klstm_ctc_eval takes them (row
+ * t*S + s, any row stride >= K, any 4-byte aligned start: a column window is fine; read, never modified).
+ * THE PATH.  Lattice states 0 .. 2L (even: blank, odd i: label i >> 1); start in state 0 or 1, end in 2L or 2L - 1, per frame stay,
+ * advance by one, or skip a blank onto a label that differs from the label before it.  The emission of a frame is
+ * log(max(y[class], FLT_MIN)), a NaN counts as FLT_MIN.  The path with the largest sum of emissions wins; among equal predecessors
+ * stay is preferred, then advance, then skip; at the end state 2L over 2L - 1.  The sums run in float32.
+ *   class_weight_dev     NULL, or K floats w: the emission becomes log(max(y[k] * w[k], FLT_MIN)) with ONE fp32 multiply (label priors
+ *                        enter as w[k] = prior[k]^-alpha, computed by the caller); the score stays that of the unweighted posterior
+ *   frame_class_dev [T*S]   the class of frame (t, s) on the path (blank or a label); -1 on padding rows (t >= lens[s]) and on every
+ *                        row of an idle or rejected stream: comparable with klstm_ctc_decode's frame_class element by element
+ *   frame_pos_dev        NULL, or [T*S]: the label position j in [0, L) the frame belongs to; -1 on a blank frame and wherever
+ *                        frame_class is -1
+ *   token_begin_dev, token_end_dev   both NULL, or parallel to labels_dev: the first frame of token j and one past its last frame
+ *                        (end > begin for every token of an aligned utterance); -1 for idle and rejected streams
+ *   score_dev            NULL, or [S]: the sum of the UNWEIGHTED emissions along the returned path, accumulated in double in a fixed
+ *                        order, stored as float; 0 for an idle stream, -inf for a rejected one
+ *   totals_dev           NULL, or five doubles on the device that this minibatch is ADDED to by one thread, streams in order: sum of the
+ *                        scores of the utterances aligned, utterances aligned, utterances rejected, frames, blank frames
+ *   workspace            klstm_ctc_align_workspace_bytes(T, S, max_label_len) bytes of device memory, 16-byte aligned: two bits per
+ *                        lattice state and frame (8 bytes per 32 states; 75 KB per stream at T = 1000 with 150 labels, 33 MB at
+ *                        T*S = 65535 with 1023) and 512 bytes.  The label capacity (and with it the launch geometry) follows from
+ *                        workspace_bytes.  One call at a time per workspace
+ * STATUS of a stream, as klstm_ctc_eval decides it: lens[s] == 0 idle; REJECTED when lens[s] is outside [0, T], lens[s] < L + (number
+ * of adjacent equal labels), a label is outside [0, K) or equal to blank, or there are more labels than the workspace was sized
+ * for.  An empty label sequence is feasible (all blank).  Rows t >= lens[s] and all rows of idle / rejected streams are NOT READ.
+ * Bit-identical from run to run and independent of which stream an utterance sits in and of its neighbours: no floating-point atomics.
+ * Limits: S <= 32, T * S <= 65535, 2 <= K <= 32768, max_label_len <= 1023; beyond them KLSTM_ERR_SHAPE and nothing is launched
+ * (klstm_ctc_align_workspace_bytes answers 0 and leaves the message in klstm_last_error()). */
+size_t klstm_ctc_align_workspace_bytes(int T, int S, int max_label_len);
+klstm_status klstm_ctc_align(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *labels_dev,
+                             const int *label_offsets_dev, int blank, const float *class_weight_dev, int *frame_class_dev,
+                             int *frame_pos_dev, int *token_begin_dev, int *token_end_dev, float *score_dev, double *totals_dev,
+                             void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Engine knobs (not part of the reference interface).  Keys:
  *   "graph"   0/1/2  issue plain stream launches (default 0: measured equal or faster at every stream count while the host
  *                  thread keeps ahead, and indifferent to callers that hand in fresh buffers every minibatch) or replay the

@@ -795,4 +795,204 @@ inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utt
   return DecodeCtcWholeUtterances(nnet, utts, o, hypotheses, report, [](const UtteranceBatch &, const DeviceMatrix &, const CtcGreedyDecoder &) {});
 }
 
+// CTC forced alignment of whole utterances: the most probable alignment of each stream's labels to its frames (klstm_ctc_align,
+// klstm.h).  The five totals stay on the device and are read when somebody asks, like Ctc's.
+class CtcAligner {
+ public:
+  explicit CtcAligner(int32 blank = 0) : blank_(blank) {}
+  ~CtcAligner() {
+    klstm_free(ws_); klstm_free(lens_); klstm_free(lab_); klstm_free(off_); klstm_free(fc_); klstm_free(fp_); klstm_free(tb_); klstm_free(te_);
+    klstm_free(score_); klstm_free(w_); klstm_free(tot_);
+  }
+  CtcAligner(const CtcAligner &) = delete;
+  CtcAligner &operator=(const CtcAligner &) = delete;
+
+  // One weight per class: the emission of a frame becomes log(y[k] * w[k]) (label priors: w[k] = prior[k]^-alpha).  Empty: none.
+  void SetClassWeights(const std::vector<BaseFloat> &w) {
+    num_weights_ = (int32)w.size();
+    if (w.empty()) return;
+    Grow(&w_, &w_cap_, w.size() * sizeof(BaseFloat));
+    KCheck(klstm_memcpy_h2d(w_, w.data(), w.size() * sizeof(BaseFloat), nullptr));
+  }
+  // net_out [T*num_stream x K] posteriors (row t*S + s); lens: frames per stream (0 = idle); labels: per stream.  Utterances that
+  // cannot be aligned (klstm.h) are rejected on the device.  Nothing synchronises.
+  void Align(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &labels) {
+    KLSTM_ASSERT((int32)lens.size() == num_stream);
+    Grow(&lens_, &lens_cap_, (size_t)num_stream * sizeof(int32));
+    KCheck(klstm_memcpy_h2d(lens_, lens.data(), (size_t)num_stream * sizeof(int32), nullptr));
+    Align(net_out, num_stream, (const int32 *)lens_, labels);
+  }
+  void Align(const DeviceMatrix &net_out, int32 num_stream, const int32 *lens_dev, const std::vector<std::vector<int32> > &labels) {
+    const int32 rows = net_out.NumRows(), K = net_out.NumCols();
+    KLSTM_ASSERT(num_stream > 0 && rows > 0 && rows % num_stream == 0 && (int32)labels.size() == num_stream && lens_dev);
+    KLSTM_ASSERT(num_weights_ == 0 || num_weights_ == K);
+    const int32 T = rows / num_stream;
+    std::vector<int32> flat;
+    off_h_.assign(1, 0);
+    size_t longest = 0;
+    for (const auto &l : labels) { flat.insert(flat.end(), l.begin(), l.end()); off_h_.push_back((int32)flat.size()); longest = std::max(longest, l.size()); }
+    num_labels_ = flat.size();
+    if (flat.empty()) flat.push_back(0);
+    const size_t need = klstm_ctc_align_workspace_bytes(T, num_stream, (int)std::min(longest, (size_t)1023));   // longer: the device's to reject
+    if (need == 0) KLSTM_ERR("klstm: " << klstm_last_error());
+    Grow(&ws_, &ws_cap_, need);
+    Grow(&lab_, &lab_cap_, flat.size() * sizeof(int32));
+    Grow(&off_, &off_cap_, off_h_.size() * sizeof(int32));
+    Grow(&fc_, &fc_cap_, (size_t)rows * sizeof(int32));
+    Grow(&fp_, &fp_cap_, (size_t)rows * sizeof(int32));
+    Grow(&tb_, &tb_cap_, flat.size() * sizeof(int32));
+    Grow(&te_, &te_cap_, flat.size() * sizeof(int32));
+    Grow(&score_, &score_cap_, (size_t)num_stream * sizeof(BaseFloat));
+    if (!tot_) { void *p; KCheck(klstm_malloc(&p, 5 * sizeof(double))); tot_ = (double *)p; KCheck(klstm_memset_zero(tot_, 5 * sizeof(double), nullptr)); }
+    KCheck(klstm_memcpy_h2d(lab_, flat.data(), flat.size() * sizeof(int32), nullptr));
+    KCheck(klstm_memcpy_h2d(off_, off_h_.data(), off_h_.size() * sizeof(int32), nullptr));
+    MatrixView y = net_out.View();
+    KCheck(klstm_ctc_align(y.Data(), T, num_stream, K, y.Stride(), lens_dev, (const int32 *)lab_, (const int32 *)off_, blank_,
+                           num_weights_ ? (const BaseFloat *)w_ : nullptr, (int32 *)fc_, (int32 *)fp_, (int32 *)tb_, (int32 *)te_,
+                           (BaseFloat *)score_, tot_, ws_, need, nullptr));
+    num_stream_ = num_stream; rows_ = rows;
+  }
+  // of the last Align (each synchronises).  Frame classes and positions [T*num_stream], row t*S + s; -1 where there is no path
+  void FrameClasses(std::vector<int32> *v) const { v->assign(rows_, -1); Get(v->data(), fc_, v->size() * sizeof(int32)); }
+  void FramePositions(std::vector<int32> *v) const { v->assign(rows_, -1); Get(v->data(), fp_, v->size() * sizeof(int32)); }
+  // per stream: first frame of every token and one past its last (empty for a stream without labels; -1 where not aligned)
+  void TokenBounds(std::vector<std::vector<int32> > *begin, std::vector<std::vector<int32> > *end) const {
+    std::vector<int32> b(num_labels_), e(num_labels_);
+    Get(b.data(), tb_, b.size() * sizeof(int32));
+    Get(e.data(), te_, e.size() * sizeof(int32));
+    begin->assign(num_stream_, std::vector<int32>());
+    end->assign(num_stream_, std::vector<int32>());
+    for (int32 s = 0; s < num_stream_; s++) {
+      (*begin)[s].assign(b.begin() + off_h_[s], b.begin() + off_h_[s + 1]);
+      (*end)[s].assign(e.begin() + off_h_[s], e.begin() + off_h_[s + 1]);
+    }
+  }
+  // log probability of the path (0: idle, -inf: rejected)
+  void UttScores(std::vector<BaseFloat> *v) const { v->assign(num_stream_, 0.f); Get(v->data(), score_, v->size() * sizeof(BaseFloat)); }
+
+  double AvgScorePerFrame() const { Fetch(); return h_[0] / h_[3]; }
+  double BlankRatio() const { Fetch(); return h_[4] / h_[3]; }
+  double NumAligned() const { Fetch(); return h_[1]; }
+  double NumRejected() const { Fetch(); return h_[2]; }
+  double Frames() const { Fetch(); return h_[3]; }
+  std::string Report() const {
+    Fetch();
+    std::ostringstream oss;
+    oss << "AvgPathScore: " << h_[0] / h_[3] << " (CtcAligner) per frame, blank ratio " << h_[4] / h_[3] << " [" << h_[1] << " utterances, " << h_[3]
+        << " frames, " << h_[2] << " rejected]" << std::endl;
+    return oss.str();
+  }
+ private:
+  static void Grow(void **p, size_t *cap, size_t need) {
+    if (need <= *cap) return;
+    klstm_free(*p); *p = nullptr; *cap = 0;
+    KCheck(klstm_malloc(p, need));
+    *cap = need;
+  }
+  static void Get(void *dst, const void *src, size_t bytes) { if (bytes) KCheck(klstm_memcpy_d2h(dst, src, bytes, nullptr)); }
+  void Fetch() const {
+    for (double &v : h_) v = 0;
+    if (tot_) KCheck(klstm_memcpy_d2h(h_, tot_, 5 * sizeof(double), nullptr));
+  }
+  int32 blank_, num_stream_ = 0, rows_ = 0, num_weights_ = 0;
+  size_t num_labels_ = 0;
+  std::vector<int32> off_h_;
+  void *ws_ = nullptr, *lens_ = nullptr, *lab_ = nullptr, *off_ = nullptr, *fc_ = nullptr, *fp_ = nullptr, *tb_ = nullptr, *te_ = nullptr,
+       *score_ = nullptr, *w_ = nullptr;
+  size_t ws_cap_ = 0, lens_cap_ = 0, lab_cap_ = 0, off_cap_ = 0, fc_cap_ = 0, fp_cap_ = 0, tb_cap_ = 0, te_cap_ = 0, score_cap_ = 0, w_cap_ = 0;
+  double *tot_ = nullptr;
+  mutable double h_[5] = {0, 0, 0, 0, 0};
+};
+
+struct AlignCtcOptions {
+  int32 num_stream = 4, blank = 0, max_frames = 0;       // max_frames 0: 65535 / num_stream
+  bool sort_by_length = true;
+  std::vector<BaseFloat> class_weights;                  // empty: none
+};
+struct CtcAlignment {                                     // of one utterance; everything empty and aligned = false where there is none
+  bool aligned = false;
+  int32 blank = 0;                                        // the blank's index among frame_class
+  BaseFloat score = 0.f;
+  std::vector<int32> frame_class, token_begin, token_end;
+};
+struct AlignCtcStats {
+  int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
+  double num_aligned = 0, num_rejected = 0, total_frames = 0, avg_score_per_frame = 0, blank_ratio = 0, seconds = 0;
+};
+
+// The loop of DecodeCtcWholeUtterances with the aligner in place of the decoder.  (*alignments)[i] belongs to utts[i] whatever
+// order the batcher handed them out in; an utterance the batcher skipped or the device rejected keeps an empty alignment.
+// every_batch (optional) sees each minibatch after Align: (batch, net_out, aligner).
+template <class F>
+inline AlignCtcStats AlignCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const AlignCtcOptions &o,
+                                             std::vector<CtcAlignment> *alignments, std::string *report, F every_batch) {
+  WholeUtteranceBatcher batcher(&utts, o.num_stream, o.sort_by_length, o.max_frames);
+  CtcAligner al(o.blank);
+  al.SetClassWeights(o.class_weights);
+  UtteranceBatch b;
+  DeviceMatrix feat_dev, nnet_out;
+  AlignCtcStats st;
+  std::vector<int> all(o.num_stream, 1);
+  std::vector<int32> fc;
+  std::vector<BaseFloat> score;
+  std::vector<std::vector<int32> > tb, te;
+  std::vector<CtcAlignment> per_stream;
+  if (alignments) alignments->assign(utts.size(), CtcAlignment());
+  const auto t0 = std::chrono::steady_clock::now();
+  while (batcher.Next(&b)) {
+    nnet->SetSeqLengths(b.lens);
+    nnet->Reset(all);
+    feat_dev.CopyFromHost(b.feat.data(), b.num_frames * b.num_stream, b.dim);
+    nnet->Propagate(feat_dev.View(), &nnet_out);
+    al.Align(nnet_out, b.num_stream, b.lens, b.labels);
+    if (alignments) {
+      al.FrameClasses(&fc); al.UttScores(&score); al.TokenBounds(&tb, &te);
+      per_stream.assign(b.num_stream, CtcAlignment());
+      for (int32 s = 0; s < b.num_stream; s++) {
+        if (b.lens[s] <= 0 || fc[s] < 0) continue;                       // idle, or rejected: frame 0 carries -1
+        CtcAlignment &a = per_stream[s];
+        a.aligned = true; a.blank = o.blank; a.score = score[s]; a.token_begin = tb[s]; a.token_end = te[s];
+        a.frame_class.resize(b.lens[s]);
+        for (int32 t = 0; t < b.lens[s]; t++) a.frame_class[t] = fc[(size_t)t * b.num_stream + s];
+      }
+      ScatterByUtterance(b, per_stream, alignments);
+    }
+    every_batch(b, nnet_out, al);
+    st.num_minibatches++;
+  }
+  KCheck(klstm_stream_synchronize(nullptr));
+  st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  st.num_done = batcher.NumDone();
+  st.num_skipped = batcher.NumSkipped();
+  st.num_aligned = al.NumAligned();
+  st.num_rejected = al.NumRejected();
+  st.total_frames = al.Frames();
+  st.avg_score_per_frame = al.AvgScorePerFrame();
+  st.blank_ratio = al.BlankRatio();
+  if (report) *report = al.Report();
+  return st;
+}
+inline AlignCtcStats AlignCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const AlignCtcOptions &o,
+                                             std::vector<CtcAlignment> *alignments, std::string *report = nullptr) {
+  return AlignCtcWholeUtterances(nnet, utts, o, alignments, report, [](const UtteranceBatch &, const DeviceMatrix &, const CtcAligner &) {});
+}
+
+// The bridge to the frame-level trainer (TrainLstmStreams): targets = the class of every frame on the alignment, the blank's frames
+// as blank_target (negative: the blank's own index).  Utterances without an alignment keep their targets.  Returns how many were
+// filled.
+inline int32 SetTargetsFromAlignment(std::vector<Utterance> *utts, const std::vector<CtcAlignment> &alignments, int32 blank_target = -1) {
+  KLSTM_ASSERT(utts->size() == alignments.size());
+  int32 filled = 0;
+  for (size_t i = 0; i < utts->size(); i++) {
+    const CtcAlignment &a = alignments[i];
+    if (!a.aligned) continue;
+    KLSTM_ASSERT((int32)a.frame_class.size() == (*utts)[i].num_frames);
+    (*utts)[i].targets = a.frame_class;
+    if (blank_target >= 0 && blank_target != a.blank)
+      for (int32 &c : (*utts)[i].targets) if (c == a.blank) c = blank_target;
+    filled++;
+  }
+  return filled;
+}
+
 }  // namespace klstm_kaldi

@@ -2093,6 +2093,35 @@ klstm_status klstm_ctc_decode(const float *net_out, int T, int S, int K, int str
                            ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
+size_t klstm_ctc_align_workspace_bytes(int T, int S, int max_label_len) {
+  if (T <= 0 || S <= 0 || S > 32 || (long)T * S > 65535 || max_label_len < 0 || max_label_len > 1023) {
+    fail(KLSTM_ERR_SHAPE, "klstm_ctc_align_workspace_bytes: T %d, streams %d, label length %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, L <= 1023", T, S, max_label_len);
+    return 0;
+  }
+  return ctc_align_workspace_bytes(T, S, max_label_len);
+}
+klstm_status klstm_ctc_align(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *labels_dev,
+                             const int *label_offsets_dev, int blank, const float *class_weight_dev, int *frame_class_dev,
+                             int *frame_pos_dev, int *token_begin_dev, int *token_end_dev, float *score_dev, double *totals_dev,
+                             void *workspace, size_t workspace_bytes, void *hip_stream) {
+  if (T <= 0 || S <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_align: bad size (T %d, streams %d, K %d)", T, S, K);
+  if (S > 32 || (long)T * S > 65535 || K < 2 || K > 32768)
+    return fail(KLSTM_ERR_SHAPE, "klstm_ctc_align: T %d, streams %d, K %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768", T, S, K);
+  if (!net_out || !lens_dev || !labels_dev || !label_offsets_dev || !frame_class_dev || !workspace)
+    return fail(KLSTM_ERR_ARG, "klstm_ctc_align: null argument");
+  if ((token_begin_dev == nullptr) != (token_end_dev == nullptr))
+    return fail(KLSTM_ERR_ARG, "klstm_ctc_align: token begins and ends come together or not at all");
+  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "klstm_ctc_align: blank %d outside [0, %d)", blank, K);
+  if (stride < K) return fail(KLSTM_ERR_ARG, "klstm_ctc_align: row stride below K (%d < %d)", stride, K);
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_align: workspace must be 16-byte aligned");
+  const int lcap = ctc_align_label_capacity(T, S, workspace_bytes);
+  if (lcap < 0)
+    return fail(KLSTM_ERR_ARG, "klstm_ctc_align: workspace of %zu bytes is below klstm_ctc_align_workspace_bytes(%d, %d, 0) = %zu", workspace_bytes, T, S,
+                ctc_align_workspace_bytes(T, S, 0));
+  HIPCHK(launch_ctc_align(net_out, T, S, K, stride, lens_dev, labels_dev, label_offsets_dev, blank, class_weight_dev, frame_class_dev,
+                          frame_pos_dev, token_begin_dev, token_end_dev, score_dev, totals_dev, workspace, lcap, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
 klstm_status klstm_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row_dev, float *out,
                                        int out_stride, int mode, const float *log_prior_dev, float prior_scale, void *hip_stream) {
   if ((!in || !dst_row_dev || !out) && rows > 0) return fail(KLSTM_ERR_ARG, "klstm_log_softmax_scatter: null argument");

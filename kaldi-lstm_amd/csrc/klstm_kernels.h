@@ -331,6 +331,14 @@ size_t ctc_decode_workspace_bytes(int T, int S);
 hipError_t launch_ctc_decode(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int *hyp,
                              int *hyp_len, float *score, int *frame_class, const int *refs, const int *roff, int *errors, double *totals,
                              void *workspace, hipStream_t st);
+// CTC forced alignment (klstm_ctc_align.hip): klstm_ctc_align / klstm_ctc_align_workspace_bytes of include/klstm.h.  The workspace: four
+// ints per stream for the totals, then per stream, frame and group of 32 lattice states two words of back-pointer bits.  Lcap = the
+// label length the workspace was sized for (the chain's geometry follows from it).
+size_t ctc_align_workspace_bytes(int T, int S, int Lcap);
+int ctc_align_label_capacity(int T, int S, size_t bytes);
+hipError_t launch_ctc_align(const float *y, int T, int S, int K, int stride, const int *lens, const int *labels, const int *loff, int blank,
+                            const float *cw, int *fclass, int *fpos, int *tbeg, int *tend, float *score, double *totals, void *workspace,
+                            int Lcap, hipStream_t st);
 hipError_t launch_xent(const float *y, int rows, int cols, int stride, const int *target, const float *mask, float *diff,
                        int diff_stride, float *row_xent, float *row_correct, hipStream_t st);
 hipError_t launch_softmax_xent(const float *in, int rows, int cols, int in_stride, float *post, int post_stride, const int *target,

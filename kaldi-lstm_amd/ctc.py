@@ -1,6 +1,7 @@
 """ctc_eval: connectionist temporal classification over whole utterances (klstm_ctc_eval of include/klstm.h) on torch
 CUDA tensors.  Plumbing only: the label lists become the CSR arrays of the C-ABI, the workspace is cached per shape.
-ctc_greedy_decode: best-path decoding and token error rate of the same posteriors (klstm_ctc_decode)."""
+ctc_greedy_decode: best-path decoding and token error rate of the same posteriors (klstm_ctc_decode).
+ctc_align: the most probable alignment of given label sequences to the frames (klstm_ctc_align)."""
 import collections
 import ctypes
 
@@ -139,3 +140,79 @@ def hypotheses_to_lists(hyp, hyp_len):
     """(hyp [S, T], hyp_len [S]) of ctc_greedy_decode -> S Python lists.  The one place that synchronises."""
     h, n = hyp.cpu().numpy(), hyp_len.cpu().numpy()
     return [h[s, :n[s]].tolist() for s in range(len(n))]
+
+
+_AWS = {}         # (device, T, S, label capacity) -> uint8 workspace tensor of ctc_align
+
+CtcAlignResult = collections.namedtuple("CtcAlignResult", "frame_class frame_pos token_begin token_end score")
+
+
+def ctc_align_workspace_bytes(T, S, max_label_len):
+    lib = load_library()
+    n = lib.klstm_ctc_align_workspace_bytes(int(T), int(S), int(max_label_len))
+    if n == 0:
+        _chk(2)
+    return n
+
+
+def ctc_align(net_out, lens, labels, blank=0, class_weight=None, totals=None, stream=None):
+    """The most probable alignment of labels[s] to the frames of stream s (Viterbi over the CTC lattice; ties: stay, advance, skip).
+    net_out, lens, labels as ctc_eval takes them; class_weight: None or K float32 on the device (emission log(y[k] * w[k]), one fp32
+    product; the score stays unweighted).  Returns CtcAlignResult(frame_class [T*S] int32 (the class of every frame on the path, -1
+    on padding rows and on idle / rejected streams), frame_pos [T*S] int32 (label position of the frame, -1 on blank frames),
+    token_begin, token_end (parallel to the packed labels: first frame of a token and one past its last; -1 where not aligned),
+    score [S] float32 (0 idle, -inf rejected)).  totals: a float64[5] CUDA tensor that score sum, utterances aligned, utterances
+    rejected, frames and blank frames are added to.  Nothing synchronises; alignments_to_lists() does."""
+    import torch
+    lib = load_library()
+    dev = net_out.device
+    assert net_out.is_cuda and net_out.dtype == torch.float32 and net_out.dim() == 2 and net_out.stride(1) == 1
+    if isinstance(lens, torch.Tensor) and lens.is_cuda:
+        assert lens.dtype == torch.int32 and lens.is_contiguous()
+        lens_dev = lens
+    else:
+        lens_dev = torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
+    S = lens_dev.numel()
+    assert S > 0 and net_out.shape[0] % S == 0, "rows must be T * len(lens)"
+    T, K = net_out.shape[0] // S, net_out.shape[1]
+    lab_dev, off_dev, longest = labels if isinstance(labels, tuple) else pack_labels(labels, dev)
+    assert off_dev.numel() == S + 1 and lab_dev.dtype == torch.int32 and off_dev.dtype == torch.int32
+    if class_weight is not None:
+        assert class_weight.is_cuda and class_weight.dtype == torch.float32 and class_weight.numel() == K and class_weight.is_contiguous()
+    if totals is not None:
+        assert totals.is_cuda and totals.dtype == torch.float64 and totals.numel() == 5 and totals.is_contiguous()
+    cap = min(longest, 1023)                                            # a longer sequence is the device's to reject
+    nbytes = ctc_align_workspace_bytes(T, S, cap)
+    key = (dev.index, T, S, cap)
+    ws = _AWS.get(key)
+    if ws is None:
+        if len(_AWS) >= 8:
+            _AWS.clear()
+        ws = _AWS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    frame_class = torch.empty(T * S, dtype=torch.int32, device=dev)
+    frame_pos = torch.empty(T * S, dtype=torch.int32, device=dev)
+    token_begin = torch.empty(lab_dev.numel(), dtype=torch.int32, device=dev)
+    token_end = torch.empty(lab_dev.numel(), dtype=torch.int32, device=dev)
+    score = torch.empty(S, device=dev)
+    _chk(lib.klstm_ctc_align(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), lab_dev.data_ptr(), off_dev.data_ptr(),
+                             int(blank), class_weight.data_ptr() if class_weight is not None else None, frame_class.data_ptr(),
+                             frame_pos.data_ptr(), token_begin.data_ptr(), token_end.data_ptr(), score.data_ptr(),
+                             totals.data_ptr() if totals is not None else None, ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    return CtcAlignResult(frame_class, frame_pos, token_begin, token_end, score)
+
+
+def alignments_to_lists(result, lens, offsets):
+    """CtcAlignResult -> per stream dict(frame_class, frame_pos (lists over the stream's frames), token_begin, token_end (lists over
+    its labels), score); lens: S lengths, offsets: the S + 1 label offsets (a sequence or a tensor).  An idle or rejected stream
+    (frame_class -1 throughout) gives empty frame lists.  The one place that synchronises."""
+    lens = [int(v) for v in (lens.cpu().tolist() if hasattr(lens, "cpu") else lens)]
+    off = [int(v) for v in (offsets.cpu().tolist() if hasattr(offsets, "cpu") else offsets)]
+    S = len(lens)
+    fc, fp = result.frame_class.cpu().numpy().reshape(-1, S), result.frame_pos.cpu().numpy().reshape(-1, S)
+    tb, te, sc = result.token_begin.cpu().numpy(), result.token_end.cpu().numpy(), result.score.cpu().numpy()
+    out = []
+    for s in range(S):
+        n = lens[s] if 0 < lens[s] <= fc.shape[0] and fc[0, s] >= 0 else 0
+        out.append(dict(frame_class=fc[:n, s].tolist(), frame_pos=fp[:n, s].tolist(), token_begin=tb[off[s]:off[s + 1]].tolist(),
+                        token_end=te[off[s]:off[s + 1]].tolist(), score=float(sc[s])))
+    return out
