@@ -411,6 +411,45 @@ klstm_status klstm_ctc_decode(const float *net_out, int T, int S, int K, int str
                               const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev, double *totals_dev,
                               void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/* CTC prefix beam search of whole utterances: the most probable LABELLINGS (sums over alignments) as an n-best list with scores, and
+ * their edit distances against reference label sequences (include/klstm_nnet.hpp class CtcBeamDecoder; DESIGN.md
+ * 4k).  Stateless, asynchronous on hip_stream, decided entirely on the device.  net_out, stride, lens_dev, blank, class_weight_dev
+ * and the references exactly as klstm_ctc_decode takes them.
+ * THE SEARCH is defined bit for bit by tests/ctc_beam_ref.py.  Probabilities stay in the linear domain; every step is ONE fp32
+ * product or sum rounded to nearest.  The emission e[k] = y[k] * w[k] (y[k] without weights); a NaN or a value below 2^-60 counts as
+ * exactly 0, a value above 2^60 as 2^60.  Per frame: the `cands` non-blank classes with the largest e > 0 (ties: the lower column)
+ * extend each of the at most `beam` prefixes; an extension that equals a prefix of the beam is added to that prefix's entry; the
+ * `beam` largest totals pb + pnb survive (ties: the stay entries in beam order, then the extensions in order of parent and rank); the
+ * beam is rescaled by the power of two that brings its largest total into [0.5, 1), values below 2^-60 become 0.  Two prefixes are
+ * the same iff their lengths and their 64-bit hashes agree (h(empty) = 0x243F6A8885A308D3; H(h, c): x = (h ^ (c + 1)) *
+ * 0x9E3779B97F4A7C15 mod 2^64, x ^ (x >> 29)).
+ *   beam, cands, nbest   1 <= beam <= 64, 1 <= cands <= min(K - 1, 32), 1 <= nbest <= beam
+ *   hyp_dev [S*N*T]      hypothesis q of stream s at hyp_dev[(s*N + q)*T .. + hyp_len_dev[s*N + q]), q < nbest_count_dev[s]: the first
+ *                        N beam entries with a total > 0, best first.  Entries beyond hyp_len and list slots beyond nbest_count are
+ *                        left alone
+ *   hyp_len_dev [S*N], nbest_count_dev [S]
+ *   score_dev            NULL, or [S*N]: log p of the hypothesis as the search summed it (a lower bound of log p(labels | y)):
+ *                        float(log(double(total)) + exponent * ln 2)
+ *   errors_dev           NULL, or [S*N]: the Levenshtein distance of every listed hypothesis to the reference of its stream; -1 in slots
+ *                        beyond nbest_count and where the stream is not counted.  Needs the references
+ *   totals_dev           NULL, or six doubles on the device that this minibatch is ADDED to by one thread, streams in order: 1-best edit
+ *                        errors, reference tokens, 1-best hypothesis tokens, utterances counted, utterances with a 1-best error, oracle
+ *                        errors (the minimum over the list).  Needs the references
+ *   workspace            klstm_ctc_beam_workspace_bytes(T, S, beam, cands) bytes of device memory, 16-byte aligned: 8 bytes per row and
+ *                        candidate, 8 bytes per frame and beam entry (the prefix tree) and about 1 KB.  One call at a time per workspace
+ * STATUS of a stream: lens[s] == 0 idle, lens[s] outside [0, T] rejected: nbest_count 0, errors -1, not counted.  A DEAD utterance (a
+ * frame in which every emission is 0) lists the first entry of its beam alone, with score -inf.  A reference with a label outside
+ * [0, K) or equal to blank, or with more than 1023 labels: the list as usual, errors -1, not counted.  Rows t >= lens[s] and all rows of
+ * idle / rejected streams are NOT READ.
+ * Bit-identical from run to run and independent of which stream an utterance sits in: no floating-point atomics.
+ * Limits: S <= 32, T * S <= 65535, 2 <= K <= 32768, beam <= 64, cands <= min(K - 1, 32), nbest <= beam; beyond them KLSTM_ERR_SHAPE
+ * and nothing is launched (klstm_ctc_beam_workspace_bytes answers 0 and leaves the message in klstm_last_error()). */
+size_t klstm_ctc_beam_workspace_bytes(int T, int S, int beam, int cands);
+klstm_status klstm_ctc_beam_decode(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
+                                   const float *class_weight_dev, int beam, int cands, int nbest, int *hyp_dev, int *hyp_len_dev,
+                                   int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
+                                   int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* CTC forced alignment (Viterbi) of whole utterances: the single most probable alignment of the label sequence of stream s to its
  * frames (include/klstm_nnet.hpp class CtcAligner).  Stateless, asynchronous on hip_stream, decided
  * entirely on the device.  net_out, lens_dev, labels_dev / label_offsets_dev and blank exactly as klstm_ctc_eval takes them (row

@@ -729,14 +729,160 @@ class CtcGreedyDecoder {
   mutable double h_[5] = {0, 0, 0, 0, 0};
 };
 
+// CTC prefix beam search of whole utterances: the most probable labellings as n-best lists with scores, the token error rate of the
+// 1-best and the oracle error rate of the list (klstm_ctc_beam_decode, klstm.h).  The six totals stay on the device
+// and are read when somebody asks, like CtcGreedyDecoder's.
+struct CtcHypothesis {
+  std::vector<int32> tokens;
+  BaseFloat score = 0.f;       // log probability as the search summed it
+  int32 errors = -1;           // edit distance to the reference; -1: not counted
+};
+typedef std::vector<CtcHypothesis> CtcNbestList;     // best first
+
+class CtcBeamDecoder {
+ public:
+  explicit CtcBeamDecoder(int32 blank = 0, int32 beam = 16, int32 cands = 8, int32 nbest = 1) : blank_(blank), beam_(beam), cands_(cands), nbest_(nbest) {}
+  ~CtcBeamDecoder() {
+    klstm_free(ws_); klstm_free(lens_); klstm_free(lab_); klstm_free(off_); klstm_free(hyp_); klstm_free(hlen_); klstm_free(cnt_);
+    klstm_free(score_); klstm_free(err_); klstm_free(w_); klstm_free(tot_);
+  }
+  CtcBeamDecoder(const CtcBeamDecoder &) = delete;
+  CtcBeamDecoder &operator=(const CtcBeamDecoder &) = delete;
+
+  // One weight per class: the emission of a frame is y[k] * w[k] (label priors: w[k] = prior[k]^-alpha).  Empty: none.
+  void SetClassWeights(const std::vector<BaseFloat> &w) {
+    num_weights_ = (int32)w.size();
+    if (w.empty()) return;
+    Grow(&w_, &w_cap_, w.size() * sizeof(BaseFloat));
+    KCheck(klstm_memcpy_h2d(w_, w.data(), w.size() * sizeof(BaseFloat), nullptr));
+  }
+  // net_out, lens, refs as CtcGreedyDecoder::Decode takes them; lists (optional): the n-best list of every stream (empty for an idle
+  // one).  Asking for lists synchronises; the rest stays on the device.
+  void Decode(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &refs,
+              std::vector<CtcNbestList> *lists) {
+    KLSTM_ASSERT((int32)lens.size() == num_stream);
+    Grow(&lens_, &lens_cap_, (size_t)num_stream * sizeof(int32));
+    KCheck(klstm_memcpy_h2d(lens_, lens.data(), (size_t)num_stream * sizeof(int32), nullptr));
+    Decode(net_out, num_stream, (const int32 *)lens_, refs, lists);
+  }
+  void Decode(const DeviceMatrix &net_out, int32 num_stream, const int32 *lens_dev, const std::vector<std::vector<int32> > &refs,
+              std::vector<CtcNbestList> *lists) {
+    const int32 rows = net_out.NumRows(), K = net_out.NumCols();
+    KLSTM_ASSERT(num_stream > 0 && rows > 0 && rows % num_stream == 0 && lens_dev && (refs.empty() || (int32)refs.size() == num_stream));
+    KLSTM_ASSERT(num_weights_ == 0 || num_weights_ == K);
+    KLSTM_ASSERT(nbest_ >= 1);
+    const int32 T = rows / num_stream, N = nbest_;
+    const bool scoring = !refs.empty();
+    const size_t need = klstm_ctc_beam_workspace_bytes(T, num_stream, beam_, cands_);
+    if (need == 0) KLSTM_ERR("klstm: " << klstm_last_error());
+    Grow(&ws_, &ws_cap_, need);
+    Grow(&hyp_, &hyp_cap_, (size_t)rows * N * sizeof(int32));
+    Grow(&hlen_, &hlen_cap_, (size_t)num_stream * N * sizeof(int32));
+    Grow(&cnt_, &cnt_cap_, (size_t)num_stream * sizeof(int32));
+    Grow(&score_, &score_cap_, (size_t)num_stream * N * sizeof(BaseFloat));
+    Grow(&err_, &err_cap_, (size_t)num_stream * N * sizeof(int32));
+    if (scoring) {
+      std::vector<int32> off(1, 0), flat;
+      for (const auto &l : refs) { flat.insert(flat.end(), l.begin(), l.end()); off.push_back((int32)flat.size()); }
+      if (flat.empty()) flat.push_back(0);
+      Grow(&lab_, &lab_cap_, flat.size() * sizeof(int32));
+      Grow(&off_, &off_cap_, off.size() * sizeof(int32));
+      KCheck(klstm_memcpy_h2d(lab_, flat.data(), flat.size() * sizeof(int32), nullptr));
+      KCheck(klstm_memcpy_h2d(off_, off.data(), off.size() * sizeof(int32), nullptr));
+      if (!tot_) { void *p; KCheck(klstm_malloc(&p, 6 * sizeof(double))); tot_ = (double *)p; KCheck(klstm_memset_zero(tot_, 6 * sizeof(double), nullptr)); }
+    }
+    MatrixView y = net_out.View();
+    KCheck(klstm_ctc_beam_decode(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, num_weights_ ? (const BaseFloat *)w_ : nullptr,
+                                 beam_, cands_, N, (int32 *)hyp_, (int32 *)hlen_, (int32 *)cnt_, (BaseFloat *)score_,
+                                 scoring ? (const int32 *)lab_ : nullptr, scoring ? (const int32 *)off_ : nullptr,
+                                 scoring ? (int32 *)err_ : nullptr, scoring ? tot_ : nullptr, ws_, need, nullptr));
+    num_stream_ = num_stream; scored_ = scoring;
+    if (!lists) return;
+    std::vector<int32> c(num_stream), n((size_t)num_stream * N), h((size_t)rows * N), e((size_t)num_stream * N, -1);
+    std::vector<BaseFloat> sc((size_t)num_stream * N);
+    Get(c.data(), cnt_, c.size() * sizeof(int32));
+    Get(n.data(), hlen_, n.size() * sizeof(int32));
+    Get(h.data(), hyp_, h.size() * sizeof(int32));
+    Get(sc.data(), score_, sc.size() * sizeof(BaseFloat));
+    if (scoring) Get(e.data(), err_, e.size() * sizeof(int32));
+    lists->assign(num_stream, CtcNbestList());
+    for (int32 s = 0; s < num_stream; s++)
+      for (int32 q = 0; q < c[s]; q++) {
+        const size_t o = (size_t)s * N + q;
+        CtcHypothesis hy;
+        hy.tokens.assign(h.begin() + o * T, h.begin() + o * T + n[o]);
+        hy.score = sc[o];
+        hy.errors = e[o];
+        (*lists)[s].push_back(hy);
+      }
+  }
+  // of the last Decode (each synchronises), per stream: entries of the list, the 1-best's score (0 for an empty list) and its edit
+  // distance (-1: not counted; all -1 without references)
+  void NbestCounts(std::vector<int32> *v) const { v->assign(num_stream_, 0); Get(v->data(), cnt_, v->size() * sizeof(int32)); }
+  void UttScores(std::vector<BaseFloat> *v) const {
+    std::vector<int32> c;
+    NbestCounts(&c);
+    std::vector<BaseFloat> sc((size_t)num_stream_ * nbest_);
+    Get(sc.data(), score_, sc.size() * sizeof(BaseFloat));
+    v->assign(num_stream_, 0.f);
+    for (int32 s = 0; s < num_stream_; s++) if (c[s] > 0) (*v)[s] = sc[(size_t)s * nbest_];
+  }
+  void UttErrors(std::vector<int32> *v) const {
+    v->assign(num_stream_, -1);
+    if (!scored_) return;
+    std::vector<int32> e((size_t)num_stream_ * nbest_);
+    Get(e.data(), err_, e.size() * sizeof(int32));
+    for (int32 s = 0; s < num_stream_; s++) (*v)[s] = e[(size_t)s * nbest_];
+  }
+
+  double TokenErrorRate() const { Fetch(); return h_[0] / h_[1]; }          // 1-best edit errors / reference tokens
+  double OracleTokenErrorRate() const { Fetch(); return h_[5] / h_[1]; }    // the best of each list
+  double UtteranceErrorRate() const { Fetch(); return h_[4] / h_[3]; }
+  double NumUtterances() const { Fetch(); return h_[3]; }
+  double NumErrors() const { Fetch(); return h_[0]; }
+  double NumOracleErrors() const { Fetch(); return h_[5]; }
+  double NumRefTokens() const { Fetch(); return h_[1]; }
+  double NumHypTokens() const { Fetch(); return h_[2]; }
+  std::string Report() const {
+    Fetch();
+    std::ostringstream oss;
+    oss << "UTT_ERROR_RATE: " << 100.0 * h_[4] / h_[3] << "% [" << h_[3] << " utterances, " << h_[0] << " errors, " << h_[1]
+        << " reference tokens, " << h_[2] << " hypothesis tokens]" << std::endl;
+    oss << "ORACLE_TOKEN_ERROR_RATE: " << 100.0 * h_[5] / h_[1] << "% [" << nbest_ << "-best, beam " << beam_ << ", " << cands_ << " candidates]" << std::endl;
+    oss << "\nTOKEN_ERROR_RATE >> " << 100.0 * h_[0] / h_[1] << "% <<";
+    return oss.str();
+  }
+ private:
+  static void Grow(void **p, size_t *cap, size_t need) {
+    if (need <= *cap) return;
+    klstm_free(*p); *p = nullptr; *cap = 0;
+    KCheck(klstm_malloc(p, need));
+    *cap = need;
+  }
+  static void Get(void *dst, const void *src, size_t bytes) { if (bytes) KCheck(klstm_memcpy_d2h(dst, src, bytes, nullptr)); }
+  void Fetch() const {
+    for (double &v : h_) v = 0;
+    if (tot_) KCheck(klstm_memcpy_d2h(h_, tot_, 6 * sizeof(double), nullptr));
+  }
+  int32 blank_, beam_, cands_, nbest_, num_stream_ = 0, num_weights_ = 0;
+  bool scored_ = false;
+  void *ws_ = nullptr, *lens_ = nullptr, *lab_ = nullptr, *off_ = nullptr, *hyp_ = nullptr, *hlen_ = nullptr, *cnt_ = nullptr, *score_ = nullptr,
+       *err_ = nullptr, *w_ = nullptr;
+  size_t ws_cap_ = 0, lens_cap_ = 0, lab_cap_ = 0, off_cap_ = 0, hyp_cap_ = 0, hlen_cap_ = 0, cnt_cap_ = 0, score_cap_ = 0, err_cap_ = 0, w_cap_ = 0;
+  double *tot_ = nullptr;
+  mutable double h_[6] = {0, 0, 0, 0, 0, 0};
+};
+
 struct DecodeCtcOptions {
   int32 num_stream = 4, blank = 0, max_frames = 0;       // max_frames 0: 65535 / num_stream
   bool sort_by_length = true, score = true;              // score: the utterances' labels are references
   std::vector<BaseFloat> class_weights;                  // empty: none
+  int32 beam = 0, cands = 8, nbest = 1;                  // beam 0: best path (CtcGreedyDecoder); beam > 0: prefix beam search (CtcBeamDecoder)
 };
 struct DecodeCtcStats {
   int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
   double token_error_rate = 0, utt_error_rate = 0, num_scored = 0, num_errors = 0, num_ref_tokens = 0, seconds = 0;
+  double oracle_token_error_rate = 0;                    // beam search only: the best hypothesis of every n-best list
 };
 
 // per-stream results of one minibatch -> per-utterance results in the order of the utterance list (idle streams carry nothing)
@@ -750,13 +896,70 @@ inline void ScatterByUtterance(const UtteranceBatch &b, const std::vector<V> &pe
   }
 }
 
+// The same loop with the prefix beam search (o.beam > 0).  (*hypotheses)[i] is the 1-best of utts[i], (*nbest_lists)[i] its whole list
+// with scores and edit distances (either may be null; both empty for a skipped utterance).  every_batch sees (batch, net_out,
+// CtcBeamDecoder) after Decode.
+template <class F>
+inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
+                                               std::vector<std::vector<int32> > *hypotheses, std::vector<CtcNbestList> *nbest_lists,
+                                               std::string *report, F every_batch) {
+  KLSTM_ASSERT(o.beam > 0);
+  WholeUtteranceBatcher batcher(&utts, o.num_stream, o.sort_by_length, o.max_frames);
+  CtcBeamDecoder dec(o.blank, o.beam, o.cands, o.nbest);
+  dec.SetClassWeights(o.class_weights);
+  UtteranceBatch b;
+  DeviceMatrix feat_dev, nnet_out;
+  DecodeCtcStats st;
+  std::vector<int> all(o.num_stream, 1);
+  std::vector<CtcNbestList> lists;
+  const std::vector<std::vector<int32> > none;
+  const bool want = hypotheses || nbest_lists;
+  if (hypotheses) hypotheses->assign(utts.size(), std::vector<int32>());
+  if (nbest_lists) nbest_lists->assign(utts.size(), CtcNbestList());
+  const auto t0 = std::chrono::steady_clock::now();
+  while (batcher.Next(&b)) {
+    nnet->SetSeqLengths(b.lens);
+    nnet->Reset(all);
+    feat_dev.CopyFromHost(b.feat.data(), b.num_frames * b.num_stream, b.dim);
+    nnet->Propagate(feat_dev.View(), &nnet_out);
+    dec.Decode(nnet_out, b.num_stream, b.lens, o.score ? b.labels : none, want ? &lists : nullptr);
+    if (nbest_lists) ScatterByUtterance(b, lists, nbest_lists);
+    if (hypotheses) {
+      std::vector<std::vector<int32> > best(b.num_stream);
+      for (int32 s = 0; s < b.num_stream; s++) if (!lists[s].empty()) best[s] = lists[s][0].tokens;
+      ScatterByUtterance(b, best, hypotheses);
+    }
+    every_batch(b, nnet_out, dec);
+    st.num_minibatches++;
+  }
+  KCheck(klstm_stream_synchronize(nullptr));
+  st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  st.num_done = batcher.NumDone();
+  st.num_skipped = batcher.NumSkipped();
+  st.num_scored = dec.NumUtterances();
+  st.num_errors = dec.NumErrors();
+  st.num_ref_tokens = dec.NumRefTokens();
+  st.token_error_rate = dec.TokenErrorRate();
+  st.utt_error_rate = dec.UtteranceErrorRate();
+  st.oracle_token_error_rate = dec.OracleTokenErrorRate();
+  if (report) *report = dec.Report();
+  return st;
+}
+inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
+                                               std::vector<std::vector<int32> > *hypotheses, std::vector<CtcNbestList> *nbest_lists,
+                                               std::string *report = nullptr) {
+  return DecodeCtcWholeUtterances(nnet, utts, o, hypotheses, nbest_lists, report, [](const UtteranceBatch &, const DeviceMatrix &, const CtcBeamDecoder &) {});
+}
+
 // The loop of TrainCtcWholeUtterances without the objective and the backward pass: SetSeqLengths, Reset, Propagate, Decode.
 // (*hypotheses)[i] belongs to utts[i] whatever order the batcher handed them out in; an utterance the batcher skipped (empty, or
 // longer than max_frames) keeps an empty hypothesis and is counted in num_skipped.  every_batch (optional) sees each minibatch after
-// Decode: (batch, net_out, decoder).
+// Decode: (batch, net_out, decoder).  With o.beam > 0 the prefix beam search decodes instead (the overload above; hypotheses are its
+// 1-best) and every_batch, which expects the best-path decoder, is not called.
 template <class F>
 inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
                                                std::vector<std::vector<int32> > *hypotheses, std::string *report, F every_batch) {
+  if (o.beam > 0) return DecodeCtcWholeUtterances(nnet, utts, o, hypotheses, (std::vector<CtcNbestList> *)nullptr, report);
   WholeUtteranceBatcher batcher(&utts, o.num_stream, o.sort_by_length, o.max_frames);
   CtcGreedyDecoder dec(o.blank);
   dec.SetClassWeights(o.class_weights);

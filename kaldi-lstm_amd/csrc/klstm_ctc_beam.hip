@@ -1,0 +1,379 @@
+// kaldi-lstm_amd/csrc/klstm_ctc_beam.hip -- CTC prefix beam search over whole utterances with n-best lists, their scores and their edit
+// distances (klstm_ctc_beam_decode of include/klstm.h; the definition is tests/ctc_beam_ref.py).  Three launches:
+//   k_ctc_topc_sub<LPR> / k_ctc_topc_wg   one valid row (t, s) per group of LPR lanes / per workgroup: the C best non-blank
+//                  (emission, column) pairs in descending order (larger value first, then the lower column), found by C rounds of the
+//                  decoder's (value, index) reduction, each over the columns that come AFTER the winner of the round before.  The order
+//                  is total, so the reduction tree does not matter.  Padding rows and idle / rejected streams are not read.
+//   k_ctc_beam     grid (S), 64 to 256 threads: the frame chain of one stream.  Beam entries, the frame's list of up to B (C + 1) entries
+//                  and its keys live in LDS.  A total is a non-negative float, so (float bits, ~list position) is ONE 64-bit integer
+//                  key and selection is an integer rank: a key's place in the new beam is the number of keys above it.  Prefix-tree nodes (parent, token) go to the workspace, B a frame.
+//                  After the last frame the first N live entries are written out: the prefix by walking the parents, the score.
+//   k_ctc_beam_tail grid (S), 256 threads, only with references: wave q % 4 runs the one-wave Levenshtein recurrence of
+//                  klstm_ctc_dev.h for hypothesis q; the workgroup that finishes last adds the statistics onto the totals, streams in order.
+// ARITHMETIC.  Every step on the chain is ONE float32 operation rounded to nearest (bmul / badd below: never contracted into an
+// FMA); the per-frame rescale multiplies by a power of two.  Emissions and rescaled values below 2^-60 are exactly 0, so no product
+// is ever denormal and the denormal mode of the device cannot matter.  The twin reproduces every bit.
+// DETERMINISM.  No floating-point atomics; all state of a stream is its own.
+#include <cfloat>
+#include <climits>
+#include <cmath>
+
+#include "../../include/klstm.h"
+#include "klstm_ctc_dev.h"
+#include "klstm_kernels.h"
+
+// hipcc contracts a * b + c into an FMA by default, and the header's __fmul_rn / __fadd_rn are plain operators that carry that
+// licence with them when they are inlined.  The pragma governs the operators written BELOW it in this file: every product and every
+// sum of the chain goes through bmul / badd, which therefore stay two instructions wherever they end up.
+#pragma clang fp contract(off)
+
+namespace klstm {
+
+typedef unsigned long long u64;
+
+__device__ __forceinline__ float bmul(float a, float b) { return a * b; }
+__device__ __forceinline__ float badd(float a, float b) { return a + b; }
+__device__ __forceinline__ double bmul(double a, double b) { return a * b; }
+__device__ __forceinline__ double badd(double a, double b) { return a + b; }
+
+constexpr float BEAM_TINY = 0x1p-60f, BEAM_HUGE = 0x1p60f;
+constexpr u64 BEAM_H0 = 0x243F6A8885A308D3ull, BEAM_HMUL = 0x9E3779B97F4A7C15ull;
+constexpr int BEAM_KPT = 9;            // keys a thread ranks at the largest list: 2112 entries over 256 threads
+constexpr int BEAM_MAXB = 64, BEAM_MAXC = 32, BEAM_MAXLIST = 2114;      // B (C + 1) <= 2112, one more for the pair reads, even
+
+// NaN or below 2^-60: exactly 0; above 2^60 (+inf too): 2^60
+__device__ __forceinline__ float beam_emit(float v) { return v >= BEAM_TINY ? fminf(v, BEAM_HUGE) : 0.f; }
+__device__ __forceinline__ float beam_emit_at(const float *__restrict__ yp, const float *__restrict__ w, int k) {
+  return beam_emit(w ? bmul(yp[k], w[k]) : yp[k]);
+}
+__device__ __forceinline__ u64 beam_hash(u64 h, int c) {
+  const u64 x = (h ^ (u64)(unsigned)(c + 1)) * BEAM_HMUL;
+  return x ^ (x >> 29);
+}
+__device__ __forceinline__ bool beam_row_valid(int r, int T, int S, const int *__restrict__ lens) {
+  const int s = r % S, t = r / S, len = lens[s];
+  return len > 0 && len <= T && t < len;
+}
+
+// the best pair of the row that comes after `prev` in the order (and is not the blank), over the lanes' shares
+__device__ __forceinline__ Best topc_scan(const float *__restrict__ yp, const float *__restrict__ w, int K, int blank, Best prev, int lane, int nl) {
+  Best b{0.f, INT_MAX};
+  ctc_for_row(yp, w, K, lane, nl, [&](float v, int c) {
+    const float e = beam_emit(v);
+    if (c != blank && (e < prev.v || (e == prev.v && c > prev.i))) best_take(b, e, c);
+  });
+  return b;
+}
+
+// 256 threads, 256 / LPR rows per workgroup, LPR = 16 or 64 lanes per row.  ticket: zeroed here for k_ctc_beam_tail.
+template <int LPR>
+__global__ __launch_bounds__(256) void k_ctc_topc_sub(const float *__restrict__ y, int T, int S, int K, int stride, const int *__restrict__ lens,
+                                                      const float *__restrict__ w, int blank, int C, float *__restrict__ topv,
+                                                      int *__restrict__ topi, unsigned *__restrict__ ticket) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *ticket = 0u;
+  const int r = blockIdx.x * (256 / LPR) + threadIdx.x / LPR, lane = threadIdx.x % LPR;
+  const bool inside = r < T * S;
+  const bool valid = inside && beam_row_valid(r, T, S, lens);
+  const float *yp = y + (size_t)(inside ? r : 0) * stride;
+  Best prev{INFINITY, -1};
+  for (int j = 0; j < C; j++) {                                     // every lane takes part: DPP reads its neighbours' registers
+    Best b{0.f, INT_MAX};
+    if (valid && prev.v > 0.f) b = topc_scan(yp, w, K, blank, prev, lane, LPR);
+    if (LPR == 16) row16_best(b); else wave_best(b);
+    const int src = (threadIdx.x & 63) | (LPR - 1);
+    prev.v = __shfl(b.v, src);
+    prev.i = __shfl(b.i, src);
+    if (!(prev.v > 0.f)) { prev.v = 0.f; prev.i = -1; }
+    if (valid && lane == LPR - 1) { topv[(size_t)r * C + j] = prev.v; topi[(size_t)r * C + j] = prev.i; }
+  }
+}
+
+// one workgroup of four waves per row
+__global__ __launch_bounds__(256) void k_ctc_topc_wg(const float *__restrict__ y, int T, int S, int K, int stride, const int *__restrict__ lens,
+                                                     const float *__restrict__ w, int blank, int C, float *__restrict__ topv,
+                                                     int *__restrict__ topi, unsigned *__restrict__ ticket) {
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  if (r == 0 && tid == 0) *ticket = 0u;
+  if (!beam_row_valid(r, T, S, lens)) return;                      // uniform over the workgroup
+  const float *yp = y + (size_t)r * stride;
+  Best prev{INFINITY, -1};
+  for (int j = 0; j < C; j++) {
+    if (prev.v > 0.f) {                                            // uniform
+      Best b = topc_scan(yp, w, K, blank, prev, tid, 256);
+      wave_best(b);
+      if ((tid & 63) == 63) { sv[tid >> 6] = b.v; si[tid >> 6] = b.i; }
+      __syncthreads();
+      Best a{sv[0], si[0]};
+      best_take(a, sv[1], si[1]); best_take(a, sv[2], si[2]); best_take(a, sv[3], si[3]);
+      __syncthreads();
+      prev = a;
+      if (!(prev.v > 0.f)) { prev.v = 0.f; prev.i = -1; }
+    }
+    if (tid == 0) { topv[(size_t)r * C + j] = prev.v; topi[(size_t)r * C + j] = prev.i; }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The search.  List position of the stay entry of beam entry i: i; of the extension of entry i by the candidate of rank r: Bc + i C + r.
+// ------------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, int T, int S, int K, int stride, const int *__restrict__ lens,
+                                                  const float *__restrict__ w, int blank, int B, int C, int N, const float *__restrict__ topv,
+                                                  const int *__restrict__ topi, int *npar, int *ntok, int *hyp, int *__restrict__ hyp_len,
+                                                  int *__restrict__ count, float *__restrict__ score) {
+  __shared__ __attribute__((aligned(16))) u64 keys[BEAM_MAXLIST];
+  __shared__ u64 sel[BEAM_MAXB];                                   // the new beam's keys, best first
+  __shared__ u64 e_hash[BEAM_MAXB], e_ph[BEAM_MAXB];               // hash of the prefix, hash of the prefix without its last token
+  __shared__ int e_node[BEAM_MAXB], e_tok[BEAM_MAXB], e_len[BEAM_MAXB];
+  __shared__ float e_pb[BEAM_MAXB], e_pnb[BEAM_MAXB], s_pb[BEAM_MAXB], s_pnb[BEAM_MAXB];
+  __shared__ float cv[BEAM_MAXC];
+  __shared__ int ci[BEAM_MAXC];
+  __shared__ unsigned char merged[BEAM_MAXB * BEAM_MAXC];          // extension (i, r) went into the stay entry of its prefix
+
+  const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  int len = lens[s];
+  if (len < 0 || len > T) len = 0;                                 // rejected: the outputs of an idle stream
+  if (len == 0) {
+    if (tid == 0) count[s] = 0;
+    return;
+  }
+  const size_t nbase = (size_t)s * ((size_t)T * B + 1);            // node 0 of the stream: the empty prefix
+  for (int q = tid; q < BEAM_MAXB * BEAM_MAXC; q += nt) merged[q] = 0;
+  if (tid == 0) {
+    e_node[0] = 0; e_tok[0] = -1; e_len[0] = 0; e_hash[0] = BEAM_H0; e_ph[0] = 0; e_pb[0] = 1.f; e_pnb[0] = 0.f;
+    npar[nbase] = -1; ntok[nbase] = -1;
+  }
+  int Bc = 1, E = 0;
+  // the candidates and the blank's emission of a frame are fetched one frame ahead: their latency is off the chain
+  float nv = 0.f, neb = beam_emit_at(y + (size_t)s * stride, w, blank);
+  int ni = -1;
+  if (tid < C) { nv = topv[(size_t)s * C + tid]; ni = topi[(size_t)s * C + tid]; }
+
+  for (int t = 0; t < len; t++) {
+    const size_t r = (size_t)t * S + s;
+    const float *yp = y + r * stride;
+    if (tid < C) { cv[tid] = nv; ci[tid] = ni; }
+    const float eb = neb;
+    if (tid < B) sel[tid] = 0;                                     // slots no key lands in: no entry
+    if (t + 1 < len) {
+      const size_t r1 = r + S;
+      neb = beam_emit_at(y + r1 * stride, w, blank);
+      if (tid < C) { nv = topv[r1 * C + tid]; ni = topi[r1 * C + tid]; }
+    }
+    __syncthreads();                                               // the candidates; the beam the frame before wrote
+    if (tid < Bc) {                                                // stay entries
+      const int j = tid, l = e_tok[j];
+      const float tot = badd(e_pb[j], e_pnb[j]);
+      const float spb = bmul(tot, eb);
+      float spnb = 0.f;
+      if (l >= 0) {
+        spnb = bmul(e_pnb[j], beam_emit_at(yp, w, l));
+        int pi = -1, rr = -1;
+        for (int i = 0; i < Bc; i++)
+          if (e_len[i] + 1 == e_len[j] && e_hash[i] == e_ph[j]) pi = i;
+        for (int q = 0; q < C; q++)
+          if (ci[q] == l && cv[q] > 0.f) rr = q;
+        if (pi >= 0 && rr >= 0) {                                  // the extension of the parent by l IS this prefix
+          const float v = bmul(l == e_tok[pi] ? e_pb[pi] : badd(e_pb[pi], e_pnb[pi]), cv[rr]);
+          spnb = badd(spnb, v);
+          merged[pi * C + rr] = 1;
+        }
+      }
+      s_pb[j] = spb; s_pnb[j] = spnb;
+      keys[j] = ((u64)__float_as_uint(badd(spb, spnb)) << 32) | (u64)(0xFFFFFFFFu - (unsigned)j);
+    }
+    __syncthreads();
+    const int n = Bc * (C + 1);
+    for (int pos = Bc + tid; pos < n; pos += nt) {                 // extensions; key 0: no entry
+      u64 key = 0;
+      const int q = pos - Bc, i = q / C, rr = q - i * C;
+      if (merged[q]) merged[q] = 0;
+      else if (cv[rr] > 0.f) {
+        const float v = bmul(ci[rr] == e_tok[i] ? e_pb[i] : badd(e_pb[i], e_pnb[i]), cv[rr]);
+        if (v > 0.f) key = ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)pos);
+      }
+      keys[pos] = key;
+    }
+    if (tid == 0) keys[n] = 0;                                     // the pair reads below may run one past an odd n
+    __syncthreads();
+    // selection by rank: the keys are distinct, so the number of larger keys IS the place in the new beam.  Every thread walks the
+    // same addresses (LDS broadcasts, two keys a read); no sorting network, no barrier between its stages
+    const ulonglong2 *k2 = reinterpret_cast<const ulonglong2 *>(keys);
+    const int np = (n + 1) / 2;
+    if (n <= nt) {                                                 // one key a thread
+      const u64 key = tid < n ? keys[tid] : 0;
+      int rank = 0;
+#pragma unroll 8
+      for (int j = 0; j < np; j++) {
+        const ulonglong2 o = k2[j];
+        rank += (o.x > key) + (o.y > key);
+      }
+      if (key && rank < B) sel[rank] = key;
+    } else {                                                       // up to BEAM_KPT keys a thread, every read serves all of them
+      u64 my[BEAM_KPT];
+      int rank[BEAM_KPT];
+#pragma unroll
+      for (int e = 0; e < BEAM_KPT; e++) {
+        const int pos = tid + e * nt;
+        my[e] = pos < n ? keys[pos] : ~0ull;                        // nothing is above ~0: rank 0 for free, never stored
+        rank[e] = 0;
+      }
+#pragma unroll 2
+      for (int j = 0; j < np; j++) {
+        const ulonglong2 o = k2[j];
+#pragma unroll
+        for (int e = 0; e < BEAM_KPT; e++) rank[e] += (o.x > my[e]) + (o.y > my[e]);
+      }
+#pragma unroll
+      for (int e = 0; e < BEAM_KPT; e++)
+        if (my[e] != ~0ull && my[e] && rank[e] < B) sel[rank[e]] = my[e];
+    }
+    __syncthreads();
+    // the new beam: the first B keys that are entries
+    const unsigned mbits = (unsigned)(sel[0] >> 32);
+    const u64 key = tid < B ? sel[tid] : 0;
+    int node = 0, tok = 0, ln = 0;
+    u64 hs = 0, ph = 0;
+    float pb = 0.f, pnb = 0.f;
+    if (key) {
+      const int pos = (int)(0xFFFFFFFFu - (unsigned)key);
+      if (pos < Bc) {
+        node = e_node[pos]; tok = e_tok[pos]; ln = e_len[pos]; hs = e_hash[pos]; ph = e_ph[pos]; pb = s_pb[pos]; pnb = s_pnb[pos];
+      } else {
+        const int q = pos - Bc, i = q / C, rr = q - i * C;
+        node = 1 + t * B + tid; tok = ci[rr]; ln = e_len[i] + 1; ph = e_hash[i]; hs = beam_hash(ph, tok);
+        pnb = __uint_as_float((unsigned)(key >> 32));
+        npar[nbase + node] = e_node[i]; ntok[nbase + node] = tok;
+      }
+      if (mbits) {                                                 // M = m 2^k, m in [0.5, 1): times 2^-k, exact
+        const int ex = (int)((mbits >> 23) & 0xffu);
+        const float sc = __uint_as_float((unsigned)(253 - ex) << 23);
+        pb = bmul(pb, sc); pnb = bmul(pnb, sc);
+        pb = pb >= BEAM_TINY ? pb : 0.f; pnb = pnb >= BEAM_TINY ? pnb : 0.f;
+      }
+    }
+    Bc = __syncthreads_count(key != 0);                            // everybody has read the old beam
+    if (mbits) E += (int)((mbits >> 23) & 0xffu) - 126;
+    if (key) { e_node[tid] = node; e_tok[tid] = tok; e_len[tid] = ln; e_hash[tid] = hs; e_ph[tid] = ph; e_pb[tid] = pb; e_pnb[tid] = pnb; }
+  }
+  __syncthreads();
+  __threadfence_block();                                           // the nodes other threads wrote
+  if (tid >= 64) return;
+  // the first N entries with a total > 0, in beam order (B <= 64: one wave sees the whole beam); none: the first entry alone, dead
+  const float tot = tid < Bc ? badd(e_pb[tid], e_pnb[tid]) : 0.f;
+  const u64 live = __ballot(tot > 0.f);
+  int slot = live ? (tot > 0.f ? __popcll(live & ((1ull << tid) - 1ull)) : N) : (tid == 0 ? 0 : N);
+  const int cnt = live ? min(N, (int)__popcll(live)) : 1;
+  if (tid == 0) count[s] = cnt;
+  if (slot >= N) return;
+  const size_t o = (size_t)s * N + slot;
+  const int ln = e_len[tid];
+  hyp_len[o] = ln;
+  if (score) score[o] = tot > 0.f ? (float)badd(log((double)tot), bmul((double)E, 0.6931471805599453)) : -INFINITY;
+  int node = e_node[tid];
+  for (int q = ln - 1; q >= 0; q--) {
+    hyp[o * T + q] = __hip_atomic_load(ntok + nbase + node, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    node = __hip_atomic_load(npar + nbase + node, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// stat [S][8]: 1-best errors, reference tokens, 1-best tokens, counted, oracle errors
+__global__ __launch_bounds__(256) void k_ctc_beam_tail(const int *__restrict__ hyp, const int *__restrict__ hyp_len, const int *__restrict__ count,
+                                                       int T, int S, int K, int N, int blank, const int *__restrict__ refs,
+                                                       const int *__restrict__ roff, int *__restrict__ errors, double *__restrict__ totals,
+                                                       int *__restrict__ stat, unsigned *__restrict__ ticket) {
+  __shared__ int errs[BEAM_MAXB];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int cnt = count[s];
+  int L = 0;
+  bool scored = false;
+  if (cnt > 0) {                                                   // the reference: usable iff every label is a class other than the blank, at most 1023
+    const int o0 = roff[s];
+    L = roff[s + 1] - o0;
+    int bad = L < 0 || L > 1023;
+    if (!bad)
+      for (int j = tid; j < L; j += 256) {
+        const int c = refs[o0 + j];
+        bad |= (c < 0 || c >= K || c == blank);
+      }
+    scored = !__syncthreads_or(bad);
+    if (scored) {
+      const int *ref = refs + o0;
+      for (int q = wv; q < cnt; q += 4) {
+        const int *h = hyp + ((size_t)s * N + q) * T;
+        const int hl = hyp_len[(size_t)s * N + q];
+        const int e = L < 64 ? edit_distance<1, false>(h, 1, 0, hl, -1, ref, L) : L < 256 ? edit_distance<4, false>(h, 1, 0, hl, -1, ref, L)
+                                                                                 : edit_distance<16, false>(h, 1, 0, hl, -1, ref, L);
+        if (lane == 0) errs[q] = e;
+      }
+    }
+  }
+  __syncthreads();
+  if (errors)
+    for (int q = tid; q < N; q += 256) errors[(size_t)s * N + q] = (scored && q < cnt) ? errs[q] : -1;
+  if (tid != 0 || !totals) return;
+  int oracle = 0;
+  if (scored) {
+    oracle = errs[0];
+    for (int q = 1; q < cnt; q++) oracle = min(oracle, errs[q]);
+  }
+  int *st = stat + 8 * s;
+  st[0] = scored ? errs[0] : 0; st[1] = L; st[2] = scored ? hyp_len[(size_t)s * N] : 0; st[3] = scored; st[4] = oracle;
+  __threadfence();                                                 // the stream's statistics before its ticket
+  if (atomicAdd(ticket, 1u) != (unsigned)(S - 1)) return;
+  __threadfence();                                                 // the last workgroup: everybody's statistics are visible
+  double e = 0, n = 0, h = 0, u = 0, wr = 0, orc = 0;
+  for (int q = 0; q < S; q++) {
+    const int *sq = stat + 8 * q;
+    if (!__hip_atomic_load(sq + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;
+    const int eq = __hip_atomic_load(sq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    e += eq; wr += eq > 0; u += 1;
+    n += __hip_atomic_load(sq + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    h += __hip_atomic_load(sq + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    orc += __hip_atomic_load(sq + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  totals[0] += e; totals[1] += n; totals[2] += h; totals[3] += u; totals[4] += wr; totals[5] += orc;
+}
+
+static size_t up256(size_t n) { return (n + 255) / 256 * 256; }
+static size_t beam_top_bytes(int T, int S, int C) { return up256((size_t)T * S * C * sizeof(int)); }
+static size_t beam_node_bytes(int T, int S, int B) { return up256(((size_t)T * B + 1) * S * sizeof(int)); }
+
+// top values, top columns, node parents, node tokens, stat [32][8], ticket
+size_t ctc_beam_workspace_bytes(int T, int S, int B, int C) { return 2 * beam_top_bytes(T, S, C) + 2 * beam_node_bytes(T, S, B) + 1024 + 256; }
+
+hipError_t launch_ctc_beam(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
+                           int *hyp, int *hyp_len, int *count, float *score, const int *refs, const int *roff, int *errors, double *totals,
+                           void *workspace, hipStream_t st) {
+  char *p = reinterpret_cast<char *>(workspace);
+  float *topv = reinterpret_cast<float *>(p);
+  int *topi = reinterpret_cast<int *>(p + beam_top_bytes(T, S, C));
+  int *npar = reinterpret_cast<int *>(p + 2 * beam_top_bytes(T, S, C));
+  int *ntok = reinterpret_cast<int *>(p + 2 * beam_top_bytes(T, S, C) + beam_node_bytes(T, S, B));
+  int *stat = reinterpret_cast<int *>(p + 2 * beam_top_bytes(T, S, C) + 2 * beam_node_bytes(T, S, B));
+  unsigned *ticket = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(stat) + 1024);
+  const int rows = T * S;
+  // measured (T = 1000, S = 32, C = 32): 16 lanes per row up to 256 classes (level with the others), a wave per row up to
+  // 2048 (K = 1024: 11.7 against 11.8 and 12.1 ms a call), a workgroup per row beyond: the C passes over a long row stay in the
+  // caches of ONE compute unit (K = 16624: 22.6 against 25.1 ms; 1200 rows: 3.9 against 4.9 ms; level at K = 4096)
+  const int g = K <= 256 ? 16 : K <= 2048 ? 64 : 256;
+  // measured: a list that fits one or two waves is served fastest by just those (2.2 against 2.4 us a frame at B = 4,
+  // C = 4); beyond 128 entries four waves, and BEAM_KPT keys a thread need all 256 threads at the largest list
+  const int nthreads = B * (C + 1) <= 64 ? 64 : B * (C + 1) <= 128 ? 128 : 256;
+  hipError_t err;
+  if (g == 16)
+    err = launch(k_ctc_topc_sub<16>, dim3((rows + 15) / 16), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
+  else if (g == 64)
+    err = launch(k_ctc_topc_sub<64>, dim3((rows + 3) / 4), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
+  else
+    err = launch(k_ctc_topc_wg, dim3(rows), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
+  if (err != hipSuccess) return err;
+  err = launch(k_ctc_beam, dim3(S), dim3(nthreads), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, B, C, N, (const float *)topv,
+               (const int *)topi, npar, ntok, hyp, hyp_len, count, score);
+  if (err != hipSuccess || !refs) return err;
+  return launch(k_ctc_beam_tail, dim3(S), dim3(256), 0, st, LaunchProbe{}, (const int *)hyp, (const int *)hyp_len, (const int *)count, T, S, K, N,
+                blank, refs, roff, errors, totals, stat, ticket);
+}
+
+}  // namespace klstm

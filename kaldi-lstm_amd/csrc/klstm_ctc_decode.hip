@@ -16,78 +16,17 @@
 #include <cmath>
 
 #include "../../include/klstm.h"
+#include "klstm_ctc_dev.h"
 #include "klstm_kernels.h"
 
 namespace klstm {
 
-// ------------------------------------------------------------------------------------------------------------------------------------
-// (value, index) pairs.  a beats b iff a.v > b.v, or a.v == b.v and a.i < b.i: a total order on (non-NaN value, distinct index), so
-// any reduction tree gives the same winner.  The neutral element is (-inf, INT_MAX): it loses to every real column.
-// ------------------------------------------------------------------------------------------------------------------------------------
-struct Best { float v; int i; };
-__device__ __forceinline__ void best_take(Best &b, float v, int i) {
-  const bool t = v > b.v || (v == b.v && i < b.i);
-  b.v = t ? v : b.v;
-  b.i = t ? i : b.i;
-}
 __device__ __forceinline__ float ctc_key(float v) { return v == v ? v : -INFINITY; }      // a NaN never wins
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ void dpp_best(Best &b) {        // lanes without a source (or outside the row mask) see themselves
-  const int ov = __builtin_amdgcn_update_dpp(__float_as_int(b.v), __float_as_int(b.v), CTRL, ROW_MASK, 0xf, false);
-  const int oi = __builtin_amdgcn_update_dpp(b.i, b.i, CTRL, ROW_MASK, 0xf, false);
-  best_take(b, __int_as_float(ov), oi);
-}
-// after this, lane 15 of every row of 16 lanes holds the best of its row
-__device__ __forceinline__ void row16_best(Best &b) {
-  dpp_best<0x111, 0xf>(b);      // row_shr:1
-  dpp_best<0x112, 0xf>(b);      // row_shr:2
-  dpp_best<0x114, 0xf>(b);      // row_shr:4
-  dpp_best<0x118, 0xf>(b);      // row_shr:8
-}
-// ... and after this, lane 63 holds the best of the wave
-__device__ __forceinline__ void wave_best(Best &b) {
-  row16_best(b);
-  dpp_best<0x142, 0xa>(b);      // row_bcast:15 into rows 1 and 3
-  dpp_best<0x143, 0xc>(b);      // row_bcast:31 into rows 2 and 3
-}
-
-// One row of K columns seen by lane `lane` of `nl` lanes: a scalar head up to the first 16-byte boundary of the row, float4 body,
-// scalar tail.  A lane meets its columns in ascending order.  w (or null): the class weights, indexed by column.
+// One row seen by lane `lane` of `nl` lanes (ctc_for_row of klstm_ctc_dev.h); w (or null): the class weights, indexed by column.
 __device__ __forceinline__ Best scan_row(const float *__restrict__ yp, const float *__restrict__ w, int K, int lane, int nl) {
   Best b{-INFINITY, INT_MAX};
-  int head = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(yp) & 15u)) & 15u) >> 2);
-  head = head < K ? head : K;
-  const int n4 = (K - head) >> 2, tail0 = head + 4 * n4;
-  if (lane < head) best_take(b, ctc_key(w ? yp[lane] * w[lane] : yp[lane]), lane);
-  const float4 *y4 = reinterpret_cast<const float4 *>(yp + head);
-  if (!w) {
-#pragma unroll 4
-    for (int q = lane; q < n4; q += nl) {
-      const float4 a = y4[q];
-      const int c = head + 4 * q;
-      best_take(b, ctc_key(a.x), c); best_take(b, ctc_key(a.y), c + 1); best_take(b, ctc_key(a.z), c + 2); best_take(b, ctc_key(a.w), c + 3);
-    }
-  } else if ((reinterpret_cast<uintptr_t>(w + head) & 15u) == 0) {
-    const float4 *w4 = reinterpret_cast<const float4 *>(w + head);
-#pragma unroll 4
-    for (int q = lane; q < n4; q += nl) {
-      const float4 a = y4[q], m = w4[q];
-      const int c = head + 4 * q;
-      best_take(b, ctc_key(a.x * m.x), c); best_take(b, ctc_key(a.y * m.y), c + 1);
-      best_take(b, ctc_key(a.z * m.z), c + 2); best_take(b, ctc_key(a.w * m.w), c + 3);
-    }
-  } else {
-#pragma unroll 2
-    for (int q = lane; q < n4; q += nl) {
-      const float4 a = y4[q];
-      const int c = head + 4 * q;
-      best_take(b, ctc_key(a.x * w[c]), c); best_take(b, ctc_key(a.y * w[c + 1]), c + 1);
-      best_take(b, ctc_key(a.z * w[c + 2]), c + 2); best_take(b, ctc_key(a.w * w[c + 3]), c + 3);
-    }
-  }
-  const int c = tail0 + lane;
-  if (c < K) best_take(b, ctc_key(w ? yp[c] * w[c] : yp[c]), c);
+  ctc_for_row(yp, w, K, lane, nl, [&](float v, int c) { best_take(b, ctc_key(v), c); });
   return b;
 }
 
@@ -139,72 +78,6 @@ __global__ __launch_bounds__(256) void k_ctc_argmax_wg(const float *__restrict__
     best_take(a, sv[1], si[1]); best_take(a, sv[2], si[2]); best_take(a, sv[3], si[3]);
     put_row(r, true, a.i, yp, fclass, flogp);
   }
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------------
-// Levenshtein distance between the collapsed best path of stream s and ref[0 .. L), by ONE wave.  Column j of the row (0 .. L) sits in
-// lane j / P, slot j % P.  For every hypothesis token:  tmp[j] = min(D'[j] + 1, D'[j-1] + (ref[j-1] != token)),  tmp[0] = row number,
-// D[j] = j + min_{k <= j}(tmp[k] - k): a prefix minimum, in the lane's own slots first, then across the lanes by the DPP scan.
-// The tokens come straight from frame_class (the launch before wrote it), 64 frames at a time, the kept ones picked off a ballot.
-// ------------------------------------------------------------------------------------------------------------------------------------
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_min(int v) {
-  return min(v, __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ int wave_scan_min(int v) {              // inclusive prefix minimum over the lanes (min is idempotent: no bank masks)
-  v = dpp_min<0x111, 0xf>(v);
-  v = dpp_min<0x112, 0xf>(v);
-  v = dpp_min<0x114, 0xf>(v);
-  v = dpp_min<0x118, 0xf>(v);
-  v = dpp_min<0x142, 0xa>(v);
-  v = dpp_min<0x143, 0xc>(v);
-  return v;
-}
-constexpr int ED_BIG = 1 << 29;
-
-template <int P>
-__device__ int edit_distance(const int *__restrict__ fclass, int S, int s, int len, int blank, const int *__restrict__ ref, int L) {
-  const int lane = threadIdx.x & 63;
-  int prev[P], rl[P];
-#pragma unroll
-  for (int e = 0; e < P; e++) {
-    const int j = lane * P + e;
-    prev[e] = j;
-    rl[e] = (j >= 1 && j <= L) ? ref[j - 1] : -2;                  // -2: no class, never equal to a token
-  }
-  int row = 0;
-  for (int t0 = 0; t0 < len; t0 += 64) {
-    const int t = t0 + lane;
-    const int c = t < len ? fclass[(size_t)t * S + s] : blank;
-    const int cb = (t > 0 && t < len) ? fclass[(size_t)(t - 1) * S + s] : -1;
-    unsigned long long mask = __ballot(c != blank && c != cb);
-    while (mask) {
-      const int k = __builtin_ctzll(mask);
-      mask &= mask - 1;
-      const int tok = __shfl(c, k);
-      row++;
-      int up = __shfl_up(prev[P - 1], 1);                          // D'[j - 1] of the lane's first slot
-      int run = ED_BIG;
-      int v[P];
-#pragma unroll
-      for (int e = 0; e < P; e++) {
-        const int j = lane * P + e;
-        const int diag = e ? prev[e - 1] : up;
-        int tmp = min(prev[e] + 1, diag + (rl[e] != tok));
-        if (j == 0) tmp = row;
-        run = min(run, tmp - j);
-        v[e] = run;
-      }
-      int excl = __shfl_up(wave_scan_min(run), 1);
-      if (lane == 0) excl = ED_BIG;
-#pragma unroll
-      for (int e = 0; e < P; e++) prev[e] = lane * P + e + min(v[e], excl);
-    }
-  }
-  int out = 0;
-#pragma unroll
-  for (int e = 0; e < P; e++) if (lane * P + e == L) out = prev[e];
-  return __shfl(out, L / P);
 }
 
 struct CtcDecWs { int *fclass; float *flogp; int *stat; unsigned *ticket; };       // stat [S][4]: errors, ref tokens, hyp tokens, counted

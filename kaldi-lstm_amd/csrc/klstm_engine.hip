@@ -2093,6 +2093,39 @@ klstm_status klstm_ctc_decode(const float *net_out, int T, int S, int K, int str
                            ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
+static bool ctc_beam_shape_ok(int T, int S, int beam, int cands) {
+  return T > 0 && S > 0 && S <= 32 && (long)T * S <= 65535 && beam >= 1 && beam <= 64 && cands >= 1 && cands <= 32;
+}
+size_t klstm_ctc_beam_workspace_bytes(int T, int S, int beam, int cands) {
+  if (!ctc_beam_shape_ok(T, S, beam, cands)) {
+    fail(KLSTM_ERR_SHAPE, "klstm_ctc_beam_workspace_bytes: T %d, streams %d, beam %d, candidates %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, 1 <= beam <= 64, 1 <= candidates <= 32", T, S, beam, cands);
+    return 0;
+  }
+  return ctc_beam_workspace_bytes(T, S, beam, cands);
+}
+klstm_status klstm_ctc_beam_decode(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
+                                   const float *class_weight_dev, int beam, int cands, int nbest, int *hyp_dev, int *hyp_len_dev,
+                                   int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
+                                   int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  if (T <= 0 || S <= 0 || K <= 0 || beam <= 0 || cands <= 0 || nbest <= 0)
+    return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: bad size (T %d, streams %d, K %d, beam %d, candidates %d, n-best %d)", T, S, K, beam, cands, nbest);
+  if (!ctc_beam_shape_ok(T, S, beam, cands) || K < 2 || K > 32768 || cands > K - 1 || nbest > beam)
+    return fail(KLSTM_ERR_SHAPE, "klstm_ctc_beam_decode: T %d, streams %d, K %d, beam %d, candidates %d, n-best %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768, beam <= 64, candidates <= min(K - 1, 32), n-best <= beam",
+                T, S, K, beam, cands, nbest);
+  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !nbest_count_dev || !workspace) return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: null argument");
+  if ((ref_labels_dev == nullptr) != (ref_offsets_dev == nullptr))
+    return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: reference labels and offsets come together or not at all");
+  if (!ref_labels_dev && (errors_dev || totals_dev)) return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: errors / totals need reference labels");
+  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: blank %d outside [0, %d)", blank, K);
+  if (stride < K) return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: row stride below K (%d < %d)", stride, K);
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: workspace must be 16-byte aligned");
+  if (workspace_bytes < ctc_beam_workspace_bytes(T, S, beam, cands))
+    return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: workspace of %zu bytes is below klstm_ctc_beam_workspace_bytes(%d, %d, %d, %d) = %zu", workspace_bytes,
+                T, S, beam, cands, ctc_beam_workspace_bytes(T, S, beam, cands));
+  HIPCHK(launch_ctc_beam(net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest, hyp_dev, hyp_len_dev, nbest_count_dev,
+                         score_dev, ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
 size_t klstm_ctc_align_workspace_bytes(int T, int S, int max_label_len) {
   if (T <= 0 || S <= 0 || S > 32 || (long)T * S > 65535 || max_label_len < 0 || max_label_len > 1023) {
     fail(KLSTM_ERR_SHAPE, "klstm_ctc_align_workspace_bytes: T %d, streams %d, label length %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, L <= 1023", T, S, max_label_len);

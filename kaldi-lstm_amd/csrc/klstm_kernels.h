@@ -331,6 +331,12 @@ size_t ctc_decode_workspace_bytes(int T, int S);
 hipError_t launch_ctc_decode(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int *hyp,
                              int *hyp_len, float *score, int *frame_class, const int *refs, const int *roff, int *errors, double *totals,
                              void *workspace, hipStream_t st);
+// CTC prefix beam search with n-best lists (klstm_ctc_beam.hip): klstm_ctc_beam_decode / klstm_ctc_beam_workspace_bytes of
+// include/klstm.h.  The workspace: C (value, column) pairs per row, B prefix-tree nodes per frame and stream, statistics and a ticket.
+size_t ctc_beam_workspace_bytes(int T, int S, int B, int C);
+hipError_t launch_ctc_beam(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
+                           int *hyp, int *hyp_len, int *count, float *score, const int *refs, const int *roff, int *errors, double *totals,
+                           void *workspace, hipStream_t st);
 // CTC forced alignment (klstm_ctc_align.hip): klstm_ctc_align / klstm_ctc_align_workspace_bytes of include/klstm.h.  The workspace: four
 // ints per stream for the totals, then per stream, frame and group of 32 lattice states two words of back-pointer bits.  Lcap = the
 // label length the workspace was sized for (the chain's geometry follows from it).

@@ -1,7 +1,8 @@
 """ctc_eval: connectionist temporal classification over whole utterances (klstm_ctc_eval of include/klstm.h) on torch
 CUDA tensors.  Plumbing only: the label lists become the CSR arrays of the C-ABI, the workspace is cached per shape.
 ctc_greedy_decode: best-path decoding and token error rate of the same posteriors (klstm_ctc_decode).
-ctc_align: the most probable alignment of given label sequences to the frames (klstm_ctc_align)."""
+ctc_align: the most probable alignment of given label sequences to the frames (klstm_ctc_align).
+ctc_beam_decode: prefix beam search, n-best lists with scores and edit distances (klstm_ctc_beam_decode)."""
 import collections
 import ctypes
 
@@ -216,3 +217,77 @@ def alignments_to_lists(result, lens, offsets):
         out.append(dict(frame_class=fc[:n, s].tolist(), frame_pos=fp[:n, s].tolist(), token_begin=tb[off[s]:off[s + 1]].tolist(),
                         token_end=te[off[s]:off[s + 1]].tolist(), score=float(sc[s])))
     return out
+
+
+_BWS = {}         # (device, T, S, beam, cands) -> uint8 workspace tensor of ctc_beam_decode
+
+CtcBeamResult = collections.namedtuple("CtcBeamResult", "hyp hyp_len nbest_count score errors")
+
+
+def ctc_beam_workspace_bytes(T, S, beam, cands):
+    lib = load_library()
+    n = lib.klstm_ctc_beam_workspace_bytes(int(T), int(S), int(beam), int(cands))
+    if n == 0:
+        _chk(2)
+    return n
+
+
+def ctc_beam_decode(net_out, lens, blank=0, beam=16, cands=8, nbest=1, class_weight=None, refs=None, totals=None, stream=None):
+    """CTC prefix beam search: the most probable LABELLINGS of every stream, best first.  net_out, lens, class_weight and refs as
+    ctc_greedy_decode takes them; beam <= 64 prefixes survive a frame, each extended by the cands <= min(K - 1, 32) best classes of
+    the frame, nbest <= beam of them are returned.  Returns CtcBeamResult(hyp [S, N, T] int32 (row (s, q) valid up to hyp_len[s, q]),
+    hyp_len [S, N] int32, nbest_count [S] int32 (list slots beyond it are not written), score [S, N] float32 (log probability as the
+    search summed it), errors [S, N] int32 edit distances (-1: not counted, or no such slot) or None without refs).  totals: a
+    float64[6] CUDA tensor that 1-best edit errors, reference tokens, 1-best hypothesis tokens, utterances counted, utterances with a
+    1-best error and oracle errors (the minimum over the list) are added to (needs refs).  Nothing synchronises; nbest_to_lists()
+    does."""
+    import torch
+    lib = load_library()
+    dev = net_out.device
+    assert net_out.is_cuda and net_out.dtype == torch.float32 and net_out.dim() == 2 and net_out.stride(1) == 1
+    if isinstance(lens, torch.Tensor) and lens.is_cuda:
+        assert lens.dtype == torch.int32 and lens.is_contiguous()
+        lens_dev = lens
+    else:
+        lens_dev = torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
+    S = lens_dev.numel()
+    assert S > 0 and net_out.shape[0] % S == 0, "rows must be T * len(lens)"
+    T, K = net_out.shape[0] // S, net_out.shape[1]
+    beam, cands, nbest = int(beam), int(cands), int(nbest)
+    if class_weight is not None:
+        assert class_weight.is_cuda and class_weight.dtype == torch.float32 and class_weight.numel() == K and class_weight.is_contiguous()
+    lab_dev = off_dev = errors = None
+    if refs is not None:
+        lab_dev, off_dev, _ = refs if isinstance(refs, tuple) else pack_labels(refs, dev)
+        assert off_dev.numel() == S + 1 and lab_dev.dtype == torch.int32 and off_dev.dtype == torch.int32
+    if totals is not None:
+        assert refs is not None, "totals need refs"
+        assert totals.is_cuda and totals.dtype == torch.float64 and totals.numel() == 6 and totals.is_contiguous()
+    nbytes = ctc_beam_workspace_bytes(T, S, beam, cands)
+    key = (dev.index, T, S, beam, cands)
+    ws = _BWS.get(key)
+    if ws is None:
+        if len(_BWS) >= 8:
+            _BWS.clear()
+        ws = _BWS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    hyp = torch.empty(S, max(nbest, 0), T, dtype=torch.int32, device=dev)
+    hyp_len = torch.empty(S, max(nbest, 0), dtype=torch.int32, device=dev)
+    count = torch.empty(S, dtype=torch.int32, device=dev)
+    score = torch.empty(S, max(nbest, 0), device=dev)
+    if refs is not None:
+        errors = torch.empty(S, max(nbest, 0), dtype=torch.int32, device=dev)
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+    _chk(lib.klstm_ctc_beam_decode(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), ptr(class_weight),
+                                   beam, cands, nbest, hyp.data_ptr(), hyp_len.data_ptr(), count.data_ptr(), score.data_ptr(),
+                                   ptr(lab_dev), ptr(off_dev), ptr(errors), ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    return CtcBeamResult(hyp, hyp_len, count, score, errors)
+
+
+def nbest_to_lists(result):
+    """CtcBeamResult -> per stream a list of (hypothesis list, score, errors or None), best first.  The one place that synchronises."""
+    h, n, c, sc = result.hyp.cpu().numpy(), result.hyp_len.cpu().numpy(), result.nbest_count.cpu().numpy(), result.score.cpu().numpy()
+    er = result.errors.cpu().numpy() if result.errors is not None else None
+    return [[(h[s, q, :n[s, q]].tolist(), float(sc[s, q]), int(er[s, q]) if er is not None else None) for q in range(c[s])]
+            for s in range(len(c))]
