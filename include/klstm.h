@@ -450,6 +450,35 @@ klstm_status klstm_ctc_beam_decode(const float *net_out, int T, int S, int K, in
                                    int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
                                    int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/* The same search with a LABEL LANGUAGE MODEL fused in (include/klstm_nnet.hpp class CtcLabelLm, CtcBeamDecoder::SetLanguageModel;
+ * INTEGRATION.md 3h; the definition is tests/ctc_beam_lm_ref.py).  The LM is a dense deterministic weighted automaton
+ * over the labels: state 0 is the start; from state q, label c leads to state lm_next_dev[q*K + c] and multiplies the probability
+ * of the prefix by lm_weight_dev[q*K + c]; lm_final_dev[q] (may be NULL) multiplies a hypothesis that ends in q.  An n-gram model
+ * (states = histories, weight = P(c | q)^alpha * e^beta folded on the host), a lexicon (a trie whose separator returns to the root,
+ * weight 0 where no word continues, final 0 inside a word) and their composition are all tables of this form.
+ *   the fused emission of extending a prefix in state q by candidate c:  f = flush(float32(e[c] * flush(weight[q][c]))), flush
+ *   being the emission rule (NaN or below 2^-60: exactly 0, above 2^60: 2^60); f = 0 where next[q][c] lies outside [0, lm_states): a
+ *   bad table entry is a forbidden extension, decided on the device, never a fault.  The extension is worth float32(p * f) wherever
+ *   klstm_ctc_beam_decode has p * e[c]: merged into the entry of the same prefix, or as a new entry, whose state is next[q][c].
+ *   Candidates are still chosen by the emission alone.  The blank's column of both tables is never read.
+ *   with lm_final_dev: tf = float32(total * flush(final[state])); the list is the beam entries with tf > 0 by tf descending (ties: the
+ *   earlier beam position), the first nbest.  None (also: every extension forbidden in some frame and the blank's emission 0): the
+ *   utterance is DEAD as above.  Without it the list is klstm_ctc_beam_decode's.
+ *   score_dev            the FUSED score, acoustic times language model as the search summed them: float(log(double(tf)) +
+ *                        exponent * ln 2)
+ * Everything else -- arguments, outputs, statuses, the workspace (klstm_ctc_beam_workspace_bytes, unchanged) -- as
+ * klstm_ctc_beam_decode, which is this call without tables and returns the bits it always did.  Bit-identical from run to run,
+ * independent of the stream an utterance sits in and of where the tables are read from: klstm_ctc_beam_lm_resident answers 1 where a
+ * call of that shape stages the tables into LDS (8 bytes per entry) and 0 where it gathers them from global memory.
+ * Limits: 1 <= lm_states, lm_states * K <= 2^24; beyond them KLSTM_ERR_SHAPE and nothing is launched.  A null lm_next_dev or
+ * lm_weight_dev: KLSTM_ERR_ARG. */
+klstm_status klstm_ctc_beam_decode_lm(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
+                                      const float *class_weight_dev, int beam, int cands, int nbest, int lm_states, const int *lm_next_dev,
+                                      const float *lm_weight_dev, const float *lm_final_dev, int *hyp_dev, int *hyp_len_dev,
+                                      int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
+                                      int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
+int klstm_ctc_beam_lm_resident(int lm_states, int K, int beam, int cands);
+
 /* CTC forced alignment (Viterbi) of whole utterances: the single most probable alignment of the label sequence of stream s to its
  * frames (include/klstm_nnet.hpp class CtcAligner).  Stateless, asynchronous on hip_stream, decided
  * entirely on the device.  net_out, lens_dev, labels_dev / label_offsets_dev and blank exactly as klstm_ctc_eval takes them (row

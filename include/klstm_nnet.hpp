@@ -739,6 +739,45 @@ struct CtcHypothesis {
 };
 typedef std::vector<CtcHypothesis> CtcNbestList;     // best first
 
+// A label language model or a lexicon for the beam search (klstm_ctc_beam_decode_lm, klstm.h): a dense deterministic
+// weighted automaton over the K classes.  State 0 is the start; label c leads from state q to next[q*K + c] and multiplies the prefix
+// probability by weight[q*K + c]; final[q] (empty: none) multiplies a hypothesis that ends in q.  Host tables in, device tables owned.
+class CtcLabelLm {
+ public:
+  CtcLabelLm(int32 num_states, int32 num_classes, const std::vector<int32> &next, const std::vector<BaseFloat> &weight,
+             const std::vector<BaseFloat> &final_weight = std::vector<BaseFloat>())
+      : states_(num_states), classes_(num_classes) {
+    const size_t n = (size_t)num_states * num_classes;
+    KLSTM_ASSERT(num_states >= 1 && num_classes >= 2 && next.size() == n && weight.size() == n);
+    KLSTM_ASSERT(final_weight.empty() || final_weight.size() == (size_t)num_states);
+    try {
+      KCheck(klstm_malloc(&next_, n * sizeof(int32)));
+      KCheck(klstm_malloc(&weight_, n * sizeof(BaseFloat)));
+      KCheck(klstm_memcpy_h2d(next_, next.data(), n * sizeof(int32), nullptr));
+      KCheck(klstm_memcpy_h2d(weight_, weight.data(), n * sizeof(BaseFloat), nullptr));
+      if (!final_weight.empty()) {
+        KCheck(klstm_malloc(&final_, final_weight.size() * sizeof(BaseFloat)));
+        KCheck(klstm_memcpy_h2d(final_, final_weight.data(), final_weight.size() * sizeof(BaseFloat), nullptr));
+      }
+    } catch (...) {                                          // no destructor runs for a half-built object
+      Free();
+      throw;
+    }
+  }
+  ~CtcLabelLm() { Free(); }
+  CtcLabelLm(const CtcLabelLm &) = delete;
+  CtcLabelLm &operator=(const CtcLabelLm &) = delete;
+  int32 NumStates() const { return states_; }
+  int32 NumClasses() const { return classes_; }
+  const int32 *Next() const { return (const int32 *)next_; }
+  const BaseFloat *Weight() const { return (const BaseFloat *)weight_; }
+  const BaseFloat *Final() const { return (const BaseFloat *)final_; }       // null: no final weights
+ private:
+  void Free() { klstm_free(next_); klstm_free(weight_); klstm_free(final_); next_ = weight_ = final_ = nullptr; }
+  int32 states_, classes_;
+  void *next_ = nullptr, *weight_ = nullptr, *final_ = nullptr;
+};
+
 class CtcBeamDecoder {
  public:
   explicit CtcBeamDecoder(int32 blank = 0, int32 beam = 16, int32 cands = 8, int32 nbest = 1) : blank_(blank), beam_(beam), cands_(cands), nbest_(nbest) {}
@@ -756,6 +795,9 @@ class CtcBeamDecoder {
     Grow(&w_, &w_cap_, w.size() * sizeof(BaseFloat));
     KCheck(klstm_memcpy_h2d(w_, w.data(), w.size() * sizeof(BaseFloat), nullptr));
   }
+  // Fuses a language model into the search: every later Decode goes through klstm_ctc_beam_decode_lm and its scores are the fused
+  // ones.  The decoder keeps the pointer, not the tables; null: the search without one, as before.
+  void SetLanguageModel(const CtcLabelLm *lm) { lm_ = lm; }
   // net_out, lens, refs as CtcGreedyDecoder::Decode takes them; lists (optional): the n-best list of every stream (empty for an idle
   // one).  Asking for lists synchronises; the rest stays on the device.
   void Decode(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &refs,
@@ -792,10 +834,19 @@ class CtcBeamDecoder {
       if (!tot_) { void *p; KCheck(klstm_malloc(&p, 6 * sizeof(double))); tot_ = (double *)p; KCheck(klstm_memset_zero(tot_, 6 * sizeof(double), nullptr)); }
     }
     MatrixView y = net_out.View();
-    KCheck(klstm_ctc_beam_decode(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, num_weights_ ? (const BaseFloat *)w_ : nullptr,
-                                 beam_, cands_, N, (int32 *)hyp_, (int32 *)hlen_, (int32 *)cnt_, (BaseFloat *)score_,
-                                 scoring ? (const int32 *)lab_ : nullptr, scoring ? (const int32 *)off_ : nullptr,
-                                 scoring ? (int32 *)err_ : nullptr, scoring ? tot_ : nullptr, ws_, need, nullptr));
+    if (!lm_) {
+      KCheck(klstm_ctc_beam_decode(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, num_weights_ ? (const BaseFloat *)w_ : nullptr,
+                                   beam_, cands_, N, (int32 *)hyp_, (int32 *)hlen_, (int32 *)cnt_, (BaseFloat *)score_,
+                                   scoring ? (const int32 *)lab_ : nullptr, scoring ? (const int32 *)off_ : nullptr,
+                                   scoring ? (int32 *)err_ : nullptr, scoring ? tot_ : nullptr, ws_, need, nullptr));
+    } else {
+      KLSTM_ASSERT(lm_->NumClasses() == K);
+      KCheck(klstm_ctc_beam_decode_lm(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, num_weights_ ? (const BaseFloat *)w_ : nullptr,
+                                      beam_, cands_, N, lm_->NumStates(), lm_->Next(), lm_->Weight(), lm_->Final(), (int32 *)hyp_,
+                                      (int32 *)hlen_, (int32 *)cnt_, (BaseFloat *)score_, scoring ? (const int32 *)lab_ : nullptr,
+                                      scoring ? (const int32 *)off_ : nullptr, scoring ? (int32 *)err_ : nullptr, scoring ? tot_ : nullptr,
+                                      ws_, need, nullptr));
+    }
     num_stream_ = num_stream; scored_ = scoring;
     if (!lists) return;
     std::vector<int32> c(num_stream), n((size_t)num_stream * N), h((size_t)rows * N), e((size_t)num_stream * N, -1);
@@ -866,6 +917,7 @@ class CtcBeamDecoder {
   }
   int32 blank_, beam_, cands_, nbest_, num_stream_ = 0, num_weights_ = 0;
   bool scored_ = false;
+  const CtcLabelLm *lm_ = nullptr;
   void *ws_ = nullptr, *lens_ = nullptr, *lab_ = nullptr, *off_ = nullptr, *hyp_ = nullptr, *hlen_ = nullptr, *cnt_ = nullptr, *score_ = nullptr,
        *err_ = nullptr, *w_ = nullptr;
   size_t ws_cap_ = 0, lens_cap_ = 0, lab_cap_ = 0, off_cap_ = 0, hyp_cap_ = 0, hlen_cap_ = 0, cnt_cap_ = 0, score_cap_ = 0, err_cap_ = 0, w_cap_ = 0;
@@ -878,6 +930,7 @@ struct DecodeCtcOptions {
   bool sort_by_length = true, score = true;              // score: the utterances' labels are references
   std::vector<BaseFloat> class_weights;                  // empty: none
   int32 beam = 0, cands = 8, nbest = 1;                  // beam 0: best path (CtcGreedyDecoder); beam > 0: prefix beam search (CtcBeamDecoder)
+  const CtcLabelLm *lm = nullptr;                        // beam > 0 only: fused into the search (CtcBeamDecoder::SetLanguageModel); not owned
 };
 struct DecodeCtcStats {
   int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
@@ -907,6 +960,7 @@ inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utt
   WholeUtteranceBatcher batcher(&utts, o.num_stream, o.sort_by_length, o.max_frames);
   CtcBeamDecoder dec(o.blank, o.beam, o.cands, o.nbest);
   dec.SetClassWeights(o.class_weights);
+  dec.SetLanguageModel(o.lm);
   UtteranceBatch b;
   DeviceMatrix feat_dev, nnet_out;
   DecodeCtcStats st;

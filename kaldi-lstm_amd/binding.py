@@ -121,6 +121,8 @@ def load_library():
     lib.klstm_ctc_beam_workspace_bytes.argtypes = [I, I, I, I]
     lib.klstm_ctc_beam_workspace_bytes.restype = ctypes.c_size_t
     lib.klstm_ctc_beam_decode.argtypes = [P, I, I, I, I, P, I, P, I, I, I, P, P, P, P, P, P, P, P, P, ctypes.c_size_t, P]
+    lib.klstm_ctc_beam_decode_lm.argtypes = [P, I, I, I, I, P, I, P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, ctypes.c_size_t, P]
+    lib.klstm_ctc_beam_lm_resident.argtypes = [I, I, I, I]
     lib.klstm_ctc_align_workspace_bytes.argtypes = [I, I, I]
     lib.klstm_ctc_align_workspace_bytes.restype = ctypes.c_size_t
     lib.klstm_ctc_align.argtypes = [P, I, I, I, I, P, P, P, I, P, P, P, P, P, P, P, P, ctypes.c_size_t, P]

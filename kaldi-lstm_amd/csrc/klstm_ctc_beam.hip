@@ -14,6 +14,16 @@
 // FMA); the per-frame rescale multiplies by a power of two.  Emissions and rescaled values below 2^-60 are exactly 0, so no product
 // is ever denormal and the denormal mode of the device cannot matter.  The twin reproduces every bit.
 // DETERMINISM.  No floating-point atomics; all state of a stream is its own.
+// LANGUAGE MODEL (klstm_ctc_beam_decode_lm; the definition is tests/ctc_beam_lm_ref.py).  k_ctc_beam<LM>: 0 is the search
+// without one, compiled to the code it was.  With a dense automaton (next, weight, final) a beam entry carries its state e_lm, and
+// the extension of entry i by the candidate c is worth p * f, f = flush(e[c] * flush(weight[state_i][c])), 0 where next[state_i][c]
+// leaves [0, Q).  The lookup depends on the beam just selected, so it is issued the moment the new states are in LDS -- right after the
+// barrier that ends frame t, for the candidates of frame t + 1 that were prefetched a frame earlier -- and lands in REGISTERS of the
+// thread that builds that very extension two barriers later (thread q % nt owns extension q in both places): the stay entries of
+// frame t + 1 are computed under its latency.  The one reader of ANOTHER thread's factor would be the stay entry an extension
+// merges into; there the roles are swapped: the stay entry leaves its slot number in merged[] and the extension's thread adds its
+// value onto it (one extension per stay entry, so no race and the same two roundings).  LM = 1 reads the tables from global memory,
+// LM = 2 from a copy staged into dynamic LDS at the start (ctc_beam_lm_resident decides); the two give the same bits.
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -38,6 +48,7 @@ __device__ __forceinline__ double badd(double a, double b) { return a + b; }
 
 constexpr float BEAM_TINY = 0x1p-60f, BEAM_HUGE = 0x1p60f;
 constexpr u64 BEAM_H0 = 0x243F6A8885A308D3ull, BEAM_HMUL = 0x9E3779B97F4A7C15ull;
+constexpr int BEAM_LMK = 8;            // extensions a thread builds at the largest list: 2048 over 256 threads
 constexpr int BEAM_KPT = 9;            // keys a thread ranks at the largest list: 2112 entries over 256 threads
 constexpr int BEAM_MAXB = 64, BEAM_MAXC = 32, BEAM_MAXLIST = 2114;      // B (C + 1) <= 2112, one more for the pair reads, even
 
@@ -118,18 +129,32 @@ __global__ __launch_bounds__(256) void k_ctc_topc_wg(const float *__restrict__ y
 // ------------------------------------------------------------------------------------------------------------------------------------
 // The search.  List position of the stay entry of beam entry i: i; of the extension of entry i by the candidate of rank r: Bc + i C + r.
 // ------------------------------------------------------------------------------------------------------------------------------------
+struct BeamLm {                         // the label language model: Q states, next / weight [Q][K], fin [Q] or null
+  int Q;
+  const int *next;
+  const float *weight, *fin;
+};
+
+template <int LM>
 __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, int T, int S, int K, int stride, const int *__restrict__ lens,
                                                   const float *__restrict__ w, int blank, int B, int C, int N, const float *__restrict__ topv,
                                                   const int *__restrict__ topi, int *npar, int *ntok, int *hyp, int *__restrict__ hyp_len,
-                                                  int *__restrict__ count, float *__restrict__ score) {
+                                                  int *__restrict__ count, float *__restrict__ score, BeamLm lm) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char beam_dyn[];     // LM = 2: weight [Q K] float, next [Q K] int
   __shared__ __attribute__((aligned(16))) u64 keys[BEAM_MAXLIST];
   __shared__ u64 sel[BEAM_MAXB];                                   // the new beam's keys, best first
   __shared__ u64 e_hash[BEAM_MAXB], e_ph[BEAM_MAXB];               // hash of the prefix, hash of the prefix without its last token
   __shared__ int e_node[BEAM_MAXB], e_tok[BEAM_MAXB], e_len[BEAM_MAXB];
   __shared__ float e_pb[BEAM_MAXB], e_pnb[BEAM_MAXB], s_pb[BEAM_MAXB], s_pnb[BEAM_MAXB];
-  __shared__ float cv[BEAM_MAXC];
-  __shared__ int ci[BEAM_MAXC];
-  __shared__ unsigned char merged[BEAM_MAXB * BEAM_MAXC];          // extension (i, r) went into the stay entry of its prefix
+  __shared__ float cvs[LM ? 2 * BEAM_MAXC : BEAM_MAXC];            // with an LM: the candidates of frame t in half t & 1
+  __shared__ int cis[LM ? 2 * BEAM_MAXC : BEAM_MAXC];
+  __shared__ unsigned char merged[BEAM_MAXB * BEAM_MAXC];          // extension (i, r) went into the stay entry of its prefix (LM: 1 + its slot)
+  __shared__ int e_lm[LM ? 2 * BEAM_MAXB : 1];                     // LM state of the beam entries of frame t in half t & 1
+  __shared__ int nq[LM ? BEAM_MAXB * BEAM_MAXC : 1];               // LM state an extension leads to
+  float gw[BEAM_LMK];                                              // weight and next state of this thread's extensions, fetched a frame ahead
+  int gn[BEAM_LMK];
+  const float *const lw = reinterpret_cast<const float *>(beam_dyn);
+  const int *const lnx = reinterpret_cast<const int *>(beam_dyn) + (LM == 2 ? lm.Q * K : 0);
 
   const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   int len = lens[s];
@@ -149,11 +174,53 @@ __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, i
   float nv = 0.f, neb = beam_emit_at(y + (size_t)s * stride, w, blank);
   int ni = -1;
   if (tid < C) { nv = topv[(size_t)s * C + tid]; ni = topi[(size_t)s * C + tid]; }
+  // the table entries of the extensions q = tid + k nt < nbc of the beam and the candidates in half `half`
+  auto lm_fetch = [&](int half, int nbc) {
+#pragma unroll
+    for (int k = 0; k < BEAM_LMK; k++) {
+      gw[k] = 0.f; gn[k] = -1;
+      const int q = tid + k * nt;
+      if (q < nbc) {
+        const int i = q / C, c = cis[half * BEAM_MAXC + q - i * C];
+        if ((unsigned)c < (unsigned)K) {                            // -1: no candidate of that rank
+          const int idx = e_lm[half * BEAM_MAXB + i] * K + c;      // states in e_lm lie inside [0, Q): only a checked `next` gets there
+          if constexpr (LM == 2) { gw[k] = lw[idx]; gn[k] = lnx[idx]; }
+          else { gw[k] = lm.weight[idx]; gn[k] = lm.next[idx]; }
+        }
+      }
+    }
+  };
+  if constexpr (LM != 0) {
+    if constexpr (LM == 2) {                                       // stage the tables: 16 bytes a load where the pointers allow it
+      float *dw = reinterpret_cast<float *>(beam_dyn);
+      int *dn = reinterpret_cast<int *>(beam_dyn) + lm.Q * K;
+      const int nel = lm.Q * K;
+      if (nel % 4 == 0 && ((reinterpret_cast<uintptr_t>(lm.weight) | reinterpret_cast<uintptr_t>(lm.next)) & 15) == 0) {
+        const float4 *sw = reinterpret_cast<const float4 *>(lm.weight);
+        const int4 *sn = reinterpret_cast<const int4 *>(lm.next);
+#pragma unroll 4
+        for (int q = tid; q < nel / 4; q += nt) {
+          reinterpret_cast<float4 *>(dw)[q] = sw[q];
+          reinterpret_cast<int4 *>(dn)[q] = sn[q];
+        }
+      } else {
+#pragma unroll 4
+        for (int q = tid; q < nel; q += nt) { dw[q] = lm.weight[q]; dn[q] = lm.next[q]; }
+      }
+    }
+    if (tid == 0) e_lm[0] = 0;
+    if (tid < C) { cvs[tid] = nv; cis[tid] = ni; }
+    __syncthreads();
+    lm_fetch(0, C);
+  }
 
   for (int t = 0; t < len; t++) {
     const size_t r = (size_t)t * S + s;
     const float *yp = y + r * stride;
-    if (tid < C) { cv[tid] = nv; ci[tid] = ni; }
+    float *const cv = cvs + (LM ? (t & 1) * BEAM_MAXC : 0);
+    int *const ci = cis + (LM ? (t & 1) * BEAM_MAXC : 0);
+    if constexpr (LM == 0)
+      if (tid < C) { cv[tid] = nv; ci[tid] = ni; }
     const float eb = neb;
     if (tid < B) sel[tid] = 0;                                     // slots no key lands in: no entry
     if (t + 1 < len) {
@@ -167,6 +234,7 @@ __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, i
       const float tot = badd(e_pb[j], e_pnb[j]);
       const float spb = bmul(tot, eb);
       float spnb = 0.f;
+      bool deferred = false;
       if (l >= 0) {
         spnb = bmul(e_pnb[j], beam_emit_at(yp, w, l));
         int pi = -1, rr = -1;
@@ -175,25 +243,54 @@ __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, i
         for (int q = 0; q < C; q++)
           if (ci[q] == l && cv[q] > 0.f) rr = q;
         if (pi >= 0 && rr >= 0) {                                  // the extension of the parent by l IS this prefix
-          const float v = bmul(l == e_tok[pi] ? e_pb[pi] : badd(e_pb[pi], e_pnb[pi]), cv[rr]);
-          spnb = badd(spnb, v);
-          merged[pi * C + rr] = 1;
+          if constexpr (LM == 0) {
+            const float v = bmul(l == e_tok[pi] ? e_pb[pi] : badd(e_pb[pi], e_pnb[pi]), cv[rr]);
+            spnb = badd(spnb, v);
+            merged[pi * C + rr] = 1;
+          } else {                                                 // the thread that holds the extension's factor adds it and writes the key
+            merged[pi * C + rr] = (unsigned char)(j + 1);
+            deferred = true;
+          }
         }
       }
       s_pb[j] = spb; s_pnb[j] = spnb;
-      keys[j] = ((u64)__float_as_uint(badd(spb, spnb)) << 32) | (u64)(0xFFFFFFFFu - (unsigned)j);
+      if (!deferred) keys[j] = ((u64)__float_as_uint(badd(spb, spnb)) << 32) | (u64)(0xFFFFFFFFu - (unsigned)j);
     }
     __syncthreads();
     const int n = Bc * (C + 1);
-    for (int pos = Bc + tid; pos < n; pos += nt) {                 // extensions; key 0: no entry
-      u64 key = 0;
-      const int q = pos - Bc, i = q / C, rr = q - i * C;
-      if (merged[q]) merged[q] = 0;
-      else if (cv[rr] > 0.f) {
-        const float v = bmul(ci[rr] == e_tok[i] ? e_pb[i] : badd(e_pb[i], e_pnb[i]), cv[rr]);
-        if (v > 0.f) key = ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)pos);
+    if constexpr (LM != 0) {                                       // extensions with the fused emission f in place of cv[rr]
+#pragma unroll
+      for (int k = 0; k < BEAM_LMK; k++) {
+        const int q = tid + k * nt;
+        if (q < Bc * C) {
+          const int i = q / C, rr = q - i * C, pos = Bc + q, n1 = gn[k];
+          float f = 0.f;
+          if (cv[rr] > 0.f && (unsigned)n1 < (unsigned)lm.Q) f = beam_emit(bmul(cv[rr], beam_emit(gw[k])));
+          const float v = bmul(ci[rr] == e_tok[i] ? e_pb[i] : badd(e_pb[i], e_pnb[i]), f);
+          const int m = merged[q];
+          u64 key = 0;
+          if (m) {
+            const int j = m - 1;
+            const float spnb = badd(s_pnb[j], v);
+            merged[q] = 0;
+            s_pnb[j] = spnb;
+            keys[j] = ((u64)__float_as_uint(badd(s_pb[j], spnb)) << 32) | (u64)(0xFFFFFFFFu - (unsigned)j);
+          } else if (v > 0.f) key = ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)pos);
+          keys[pos] = key;
+          nq[q] = n1;
+        }
       }
-      keys[pos] = key;
+    } else {
+      for (int pos = Bc + tid; pos < n; pos += nt) {               // extensions; key 0: no entry
+        u64 key = 0;
+        const int q = pos - Bc, i = q / C, rr = q - i * C;
+        if (merged[q]) merged[q] = 0;
+        else if (cv[rr] > 0.f) {
+          const float v = bmul(ci[rr] == e_tok[i] ? e_pb[i] : badd(e_pb[i], e_pnb[i]), cv[rr]);
+          if (v > 0.f) key = ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)pos);
+        }
+        keys[pos] = key;
+      }
     }
     if (tid == 0) keys[n] = 0;                                     // the pair reads below may run one past an odd n
     __syncthreads();
@@ -233,18 +330,20 @@ __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, i
     // the new beam: the first B keys that are entries
     const unsigned mbits = (unsigned)(sel[0] >> 32);
     const u64 key = tid < B ? sel[tid] : 0;
-    int node = 0, tok = 0, ln = 0;
+    int node = 0, tok = 0, ln = 0, lst = 0;
     u64 hs = 0, ph = 0;
     float pb = 0.f, pnb = 0.f;
     if (key) {
       const int pos = (int)(0xFFFFFFFFu - (unsigned)key);
       if (pos < Bc) {
         node = e_node[pos]; tok = e_tok[pos]; ln = e_len[pos]; hs = e_hash[pos]; ph = e_ph[pos]; pb = s_pb[pos]; pnb = s_pnb[pos];
+        if constexpr (LM != 0) lst = e_lm[(t & 1) * BEAM_MAXB + pos];
       } else {
         const int q = pos - Bc, i = q / C, rr = q - i * C;
         node = 1 + t * B + tid; tok = ci[rr]; ln = e_len[i] + 1; ph = e_hash[i]; hs = beam_hash(ph, tok);
         pnb = __uint_as_float((unsigned)(key >> 32));
         npar[nbase + node] = e_node[i]; ntok[nbase + node] = tok;
+        if constexpr (LM != 0) lst = nq[q];
       }
       if (mbits) {                                                 // M = m 2^k, m in [0.5, 1): times 2^-k, exact
         const int ex = (int)((mbits >> 23) & 0xffu);
@@ -253,7 +352,14 @@ __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, i
         pb = pb >= BEAM_TINY ? pb : 0.f; pnb = pnb >= BEAM_TINY ? pnb : 0.f;
       }
     }
+    if constexpr (LM != 0) {                                       // the other halves: nobody reads them in this frame
+      const int h1 = (t + 1) & 1;
+      if (key) e_lm[h1 * BEAM_MAXB + tid] = lst;
+      if (tid < C) { cvs[h1 * BEAM_MAXC + tid] = nv; cis[h1 * BEAM_MAXC + tid] = ni; }
+    }
     Bc = __syncthreads_count(key != 0);                            // everybody has read the old beam
+    if constexpr (LM != 0)
+      if (t + 1 < len) lm_fetch((t + 1) & 1, Bc * C);              // in flight over the barrier and the stay entries of frame t + 1
     if (mbits) E += (int)((mbits >> 23) & 0xffu) - 126;
     if (key) { e_node[tid] = node; e_tok[tid] = tok; e_len[tid] = ln; e_hash[tid] = hs; e_ph[tid] = ph; e_pb[tid] = pb; e_pnb[tid] = pnb; }
   }
@@ -261,9 +367,24 @@ __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, i
   __threadfence_block();                                           // the nodes other threads wrote
   if (tid >= 64) return;
   // the first N entries with a total > 0, in beam order (B <= 64: one wave sees the whole beam); none: the first entry alone, dead
-  const float tot = tid < Bc ? badd(e_pb[tid], e_pnb[tid]) : 0.f;
+  float tot = tid < Bc ? badd(e_pb[tid], e_pnb[tid]) : 0.f;
+  bool ranked = false;
+  if constexpr (LM != 0)
+    if (lm.fin) {                                                  // uniform.  tot becomes tf = total * flush(final[state])
+      if (tid < Bc) tot = bmul(tot, beam_emit(lm.fin[e_lm[(len & 1) * BEAM_MAXB + tid]]));
+      ranked = true;
+    }
   const u64 live = __ballot(tot > 0.f);
   int slot = live ? (tot > 0.f ? __popcll(live & ((1ull << tid) - 1ull)) : N) : (tid == 0 ? 0 : N);
+  if (ranked && live) {                                            // by tf, ties to the earlier beam position: the integer rank of the frame selection, one wave
+    const unsigned mine = __float_as_uint(tot);                    // tf >= 0: the bits order as the values do
+    int rank = 0;
+    for (int j = 0; j < 64; j++) {
+      const unsigned o = __shfl(mine, j);
+      rank += (o > mine) || (o == mine && j < tid);
+    }
+    slot = tot > 0.f ? rank : N;
+  }
   const int cnt = live ? min(N, (int)__popcll(live)) : 1;
   if (tid == 0) count[s] = cnt;
   if (slot >= N) return;
@@ -343,9 +464,28 @@ static size_t beam_node_bytes(int T, int S, int B) { return up256(((size_t)T * B
 // top values, top columns, node parents, node tokens, stat [32][8], ticket
 size_t ctc_beam_workspace_bytes(int T, int S, int B, int C) { return 2 * beam_top_bytes(T, S, C) + 2 * beam_node_bytes(T, S, B) + 1024 + 256; }
 
+// measured (T = 1000, K = 64, tables of 33 to 124 KB): resident tables are level with the gather at beam 4 / 4 and 16 / 8 and
+// 0.3 to 0.7 us a frame ahead at 64 / 32 at EVERY size that fits (122.7 against 123.2 at S = 8, 96 KB), so there is no crossover in table
+// size: resident whenever the tables fit beside the search's own 31 KB of LDS with room to spare
+#ifndef KLSTM_BEAM_LM_RESIDENT_BYTES
+#define KLSTM_BEAM_LM_RESIDENT_BYTES (96 * 1024)
+#endif
+bool ctc_beam_lm_resident(int Q, int K, int B, int C) {
+  (void)B; (void)C;
+  return (size_t)Q * K * 8 <= (size_t)KLSTM_BEAM_LM_RESIDENT_BYTES;
+}
+
 hipError_t launch_ctc_beam(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
                            int *hyp, int *hyp_len, int *count, float *score, const int *refs, const int *roff, int *errors, double *totals,
                            void *workspace, hipStream_t st) {
+  return launch_ctc_beam_lm(y, T, S, K, stride, lens, blank, w, B, C, N, 0, nullptr, nullptr, nullptr, hyp, hyp_len, count, score, refs, roff,
+                            errors, totals, workspace, st);
+}
+
+// Q = 0: no language model
+hipError_t launch_ctc_beam_lm(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
+                              int Q, const int *lm_next, const float *lm_weight, const float *lm_final, int *hyp, int *hyp_len, int *count,
+                              float *score, const int *refs, const int *roff, int *errors, double *totals, void *workspace, hipStream_t st) {
   char *p = reinterpret_cast<char *>(workspace);
   float *topv = reinterpret_cast<float *>(p);
   int *topi = reinterpret_cast<int *>(p + beam_top_bytes(T, S, C));
@@ -369,8 +509,23 @@ hipError_t launch_ctc_beam(const float *y, int T, int S, int K, int stride, cons
   else
     err = launch(k_ctc_topc_wg, dim3(rows), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
   if (err != hipSuccess) return err;
-  err = launch(k_ctc_beam, dim3(S), dim3(nthreads), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, B, C, N, (const float *)topv,
-               (const int *)topi, npar, ntok, hyp, hyp_len, count, score);
+  const BeamLm lm{Q, lm_next, lm_weight, lm_final};
+  if (Q == 0)
+    err = launch(k_ctc_beam<0>, dim3(S), dim3(nthreads), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, B, C, N, (const float *)topv,
+                 (const int *)topi, npar, ntok, hyp, hyp_len, count, score, lm);
+  else if (!ctc_beam_lm_resident(Q, K, B, C))
+    err = launch(k_ctc_beam<1>, dim3(S), dim3(nthreads), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, B, C, N, (const float *)topv,
+                 (const int *)topi, npar, ntok, hyp, hyp_len, count, score, lm);
+  else {
+    // about 32 KB of static LDS come on top: past 64 KB in all the kernel needs the opt-in that launch() applies to the dynamic part alone
+    const size_t dyn = (size_t)Q * K * 8;
+    if (dyn > 32 * 1024 && dyn <= 64 * 1024) {
+      err = raise_lds_limit(reinterpret_cast<const void *>(k_ctc_beam<2>), dyn);
+      if (err != hipSuccess) return err;
+    }
+    err = launch(k_ctc_beam<2>, dim3(S), dim3(nthreads), dyn, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, B, C, N,
+                 (const float *)topv, (const int *)topi, npar, ntok, hyp, hyp_len, count, score, lm);
+  }
   if (err != hipSuccess || !refs) return err;
   return launch(k_ctc_beam_tail, dim3(S), dim3(256), 0, st, LaunchProbe{}, (const int *)hyp, (const int *)hyp_len, (const int *)count, T, S, K, N,
                 blank, refs, roff, errors, totals, stat, ticket);

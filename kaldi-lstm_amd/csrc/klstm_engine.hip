@@ -2103,28 +2103,55 @@ size_t klstm_ctc_beam_workspace_bytes(int T, int S, int beam, int cands) {
   }
   return ctc_beam_workspace_bytes(T, S, beam, cands);
 }
+// the checks and the launch behind klstm_ctc_beam_decode (Q = 0, no tables) and klstm_ctc_beam_decode_lm (with_lm: 1 <= Q)
+static klstm_status ctc_beam_decode_checked(const char *fn, bool with_lm, const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
+                                            const float *class_weight_dev, int beam, int cands, int nbest, int Q, const int *lm_next_dev,
+                                            const float *lm_weight_dev, const float *lm_final_dev, int *hyp_dev, int *hyp_len_dev,
+                                            int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
+                                            int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  if (T <= 0 || S <= 0 || K <= 0 || beam <= 0 || cands <= 0 || nbest <= 0)
+    return fail(KLSTM_ERR_ARG, "%s: bad size (T %d, streams %d, K %d, beam %d, candidates %d, n-best %d)", fn, T, S, K, beam, cands, nbest);
+  if (!ctc_beam_shape_ok(T, S, beam, cands) || K < 2 || K > 32768 || cands > K - 1 || nbest > beam)
+    return fail(KLSTM_ERR_SHAPE, "%s: T %d, streams %d, K %d, beam %d, candidates %d, n-best %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768, beam <= 64, candidates <= min(K - 1, 32), n-best <= beam",
+                fn, T, S, K, beam, cands, nbest);
+  if (Q < (with_lm ? 1 : 0) || (long)Q * K > (1L << 24))
+    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 1 <= states, states * K <= 2^24", fn, Q, K);
+  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !nbest_count_dev || !workspace) return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
+  if (Q > 0 && (!lm_next_dev || !lm_weight_dev)) return fail(KLSTM_ERR_ARG, "%s: the language model's next and weight tables come together", fn);
+  if ((ref_labels_dev == nullptr) != (ref_offsets_dev == nullptr))
+    return fail(KLSTM_ERR_ARG, "%s: reference labels and offsets come together or not at all", fn);
+  if (!ref_labels_dev && (errors_dev || totals_dev)) return fail(KLSTM_ERR_ARG, "%s: errors / totals need reference labels", fn);
+  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "%s: blank %d outside [0, %d)", fn, blank, K);
+  if (stride < K) return fail(KLSTM_ERR_ARG, "%s: row stride below K (%d < %d)", fn, stride, K);
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
+  if (workspace_bytes < ctc_beam_workspace_bytes(T, S, beam, cands))
+    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_beam_workspace_bytes(%d, %d, %d, %d) = %zu", fn, workspace_bytes,
+                T, S, beam, cands, ctc_beam_workspace_bytes(T, S, beam, cands));
+  HIPCHK(launch_ctc_beam_lm(net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest, Q, lm_next_dev, lm_weight_dev,
+                            lm_final_dev, hyp_dev, hyp_len_dev, nbest_count_dev, score_dev, ref_labels_dev, ref_offsets_dev, errors_dev,
+                            totals_dev, workspace, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
 klstm_status klstm_ctc_beam_decode(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
                                    const float *class_weight_dev, int beam, int cands, int nbest, int *hyp_dev, int *hyp_len_dev,
                                    int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
                                    int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  if (T <= 0 || S <= 0 || K <= 0 || beam <= 0 || cands <= 0 || nbest <= 0)
-    return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: bad size (T %d, streams %d, K %d, beam %d, candidates %d, n-best %d)", T, S, K, beam, cands, nbest);
-  if (!ctc_beam_shape_ok(T, S, beam, cands) || K < 2 || K > 32768 || cands > K - 1 || nbest > beam)
-    return fail(KLSTM_ERR_SHAPE, "klstm_ctc_beam_decode: T %d, streams %d, K %d, beam %d, candidates %d, n-best %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768, beam <= 64, candidates <= min(K - 1, 32), n-best <= beam",
-                T, S, K, beam, cands, nbest);
-  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !nbest_count_dev || !workspace) return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: null argument");
-  if ((ref_labels_dev == nullptr) != (ref_offsets_dev == nullptr))
-    return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: reference labels and offsets come together or not at all");
-  if (!ref_labels_dev && (errors_dev || totals_dev)) return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: errors / totals need reference labels");
-  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: blank %d outside [0, %d)", blank, K);
-  if (stride < K) return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: row stride below K (%d < %d)", stride, K);
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: workspace must be 16-byte aligned");
-  if (workspace_bytes < ctc_beam_workspace_bytes(T, S, beam, cands))
-    return fail(KLSTM_ERR_ARG, "klstm_ctc_beam_decode: workspace of %zu bytes is below klstm_ctc_beam_workspace_bytes(%d, %d, %d, %d) = %zu", workspace_bytes,
-                T, S, beam, cands, ctc_beam_workspace_bytes(T, S, beam, cands));
-  HIPCHK(launch_ctc_beam(net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest, hyp_dev, hyp_len_dev, nbest_count_dev,
-                         score_dev, ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, (hipStream_t)hip_stream));
-  return KLSTM_OK;
+  return ctc_beam_decode_checked("klstm_ctc_beam_decode", false, net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest, 0,
+                                 nullptr, nullptr, nullptr, hyp_dev, hyp_len_dev, nbest_count_dev, score_dev, ref_labels_dev, ref_offsets_dev,
+                                 errors_dev, totals_dev, workspace, workspace_bytes, hip_stream);
+}
+klstm_status klstm_ctc_beam_decode_lm(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
+                                      const float *class_weight_dev, int beam, int cands, int nbest, int lm_states, const int *lm_next_dev,
+                                      const float *lm_weight_dev, const float *lm_final_dev, int *hyp_dev, int *hyp_len_dev,
+                                      int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
+                                      int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  return ctc_beam_decode_checked("klstm_ctc_beam_decode_lm", true, net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest,
+                                 lm_states, lm_next_dev, lm_weight_dev, lm_final_dev, hyp_dev, hyp_len_dev, nbest_count_dev, score_dev,
+                                 ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, workspace_bytes, hip_stream);
+}
+int klstm_ctc_beam_lm_resident(int lm_states, int K, int beam, int cands) {
+  if (lm_states < 1 || K < 2 || (long)lm_states * K > (1L << 24)) return 0;
+  return ctc_beam_lm_resident(lm_states, K, beam, cands) ? 1 : 0;
 }
 size_t klstm_ctc_align_workspace_bytes(int T, int S, int max_label_len) {
   if (T <= 0 || S <= 0 || S > 32 || (long)T * S > 65535 || max_label_len < 0 || max_label_len > 1023) {

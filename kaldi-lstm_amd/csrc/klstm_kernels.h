@@ -337,6 +337,12 @@ size_t ctc_beam_workspace_bytes(int T, int S, int B, int C);
 hipError_t launch_ctc_beam(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
                            int *hyp, int *hyp_len, int *count, float *score, const int *refs, const int *roff, int *errors, double *totals,
                            void *workspace, hipStream_t st);
+// the same search with a label language model fused in (klstm_ctc_beam_decode_lm): Q states, next / weight [Q][K], final [Q] or null on
+// the device.  ctc_beam_lm_resident: the tables are staged into LDS (Q K 8 bytes of dynamic LDS) instead of gathered from global memory
+bool ctc_beam_lm_resident(int Q, int K, int B, int C);
+hipError_t launch_ctc_beam_lm(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
+                              int Q, const int *lm_next, const float *lm_weight, const float *lm_final, int *hyp, int *hyp_len, int *count,
+                              float *score, const int *refs, const int *roff, int *errors, double *totals, void *workspace, hipStream_t st);
 // CTC forced alignment (klstm_ctc_align.hip): klstm_ctc_align / klstm_ctc_align_workspace_bytes of include/klstm.h.  The workspace: four
 // ints per stream for the totals, then per stream, frame and group of 32 lattice states two words of back-pointer bits.  Lcap = the
 // label length the workspace was sized for (the chain's geometry follows from it).

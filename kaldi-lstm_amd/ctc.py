@@ -2,7 +2,8 @@
 CUDA tensors.  Plumbing only: the label lists become the CSR arrays of the C-ABI, the workspace is cached per shape.
 ctc_greedy_decode: best-path decoding and token error rate of the same posteriors (klstm_ctc_decode).
 ctc_align: the most probable alignment of given label sequences to the frames (klstm_ctc_align).
-ctc_beam_decode: prefix beam search, n-best lists with scores and edit distances (klstm_ctc_beam_decode)."""
+ctc_beam_decode: prefix beam search, n-best lists with scores and edit distances (klstm_ctc_beam_decode), with
+lm=CtcLabelLm(...) fused with a label language model or a lexicon (klstm_ctc_beam_decode_lm; tables: lm.py)."""
 import collections
 import ctypes
 
@@ -232,14 +233,36 @@ def ctc_beam_workspace_bytes(T, S, beam, cands):
     return n
 
 
-def ctc_beam_decode(net_out, lens, blank=0, beam=16, cands=8, nbest=1, class_weight=None, refs=None, totals=None, stream=None):
+class CtcLabelLm:
+    """The device tables of a label language model for ctc_beam_decode(lm=...): a dense deterministic weighted automaton, next [Q, K]
+    int32, weight [Q, K] float32, final [Q] float32 or None (klstm_ctc_beam_decode_lm of include/klstm.h).  Takes numpy arrays or
+    tensors (ngram_label_lm / lexicon_label_lm of lm.py build them) and keeps contiguous copies on `device`."""
+
+    def __init__(self, next, weight, final=None, device="cuda"):
+        import torch
+
+        def dev(a, dtype):
+            return torch.as_tensor(a).to(device=device, dtype=dtype).contiguous()
+        self.next, self.weight = dev(next, torch.int32), dev(weight, torch.float32)
+        self.final = dev(final, torch.float32) if final is not None else None
+        assert self.next.dim() == 2 and self.next.shape == self.weight.shape and self.next.shape[0] >= 1
+        self.states, self.classes = int(self.next.shape[0]), int(self.next.shape[1])
+        assert self.final is None or self.final.shape == (self.states,)
+
+    def resident(self, beam, cands):
+        """whether a call of this shape looks the tables up in LDS (True) or gathers them from global memory"""
+        return bool(load_library().klstm_ctc_beam_lm_resident(self.states, self.classes, int(beam), int(cands)))
+
+
+def ctc_beam_decode(net_out, lens, blank=0, beam=16, cands=8, nbest=1, class_weight=None, refs=None, totals=None, stream=None, lm=None):
     """CTC prefix beam search: the most probable LABELLINGS of every stream, best first.  net_out, lens, class_weight and refs as
     ctc_greedy_decode takes them; beam <= 64 prefixes survive a frame, each extended by the cands <= min(K - 1, 32) best classes of
     the frame, nbest <= beam of them are returned.  Returns CtcBeamResult(hyp [S, N, T] int32 (row (s, q) valid up to hyp_len[s, q]),
     hyp_len [S, N] int32, nbest_count [S] int32 (list slots beyond it are not written), score [S, N] float32 (log probability as the
     search summed it), errors [S, N] int32 edit distances (-1: not counted, or no such slot) or None without refs).  totals: a
     float64[6] CUDA tensor that 1-best edit errors, reference tokens, 1-best hypothesis tokens, utterances counted, utterances with a
-    1-best error and oracle errors (the minimum over the list) are added to (needs refs).  Nothing synchronises; nbest_to_lists()
+    1-best error and oracle errors (the minimum over the list) are added to (needs refs).  lm: a CtcLabelLm whose factors enter
+    every extension; the scores are then the fused ones, acoustic times language model.  Nothing synchronises; nbest_to_lists()
     does."""
     import torch
     lib = load_library()
@@ -279,9 +302,16 @@ def ctc_beam_decode(net_out, lens, blank=0, beam=16, cands=8, nbest=1, class_wei
 
     def ptr(t):
         return t.data_ptr() if t is not None else None
-    _chk(lib.klstm_ctc_beam_decode(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), ptr(class_weight),
-                                   beam, cands, nbest, hyp.data_ptr(), hyp_len.data_ptr(), count.data_ptr(), score.data_ptr(),
-                                   ptr(lab_dev), ptr(off_dev), ptr(errors), ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    if lm is None:
+        _chk(lib.klstm_ctc_beam_decode(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), ptr(class_weight),
+                                       beam, cands, nbest, hyp.data_ptr(), hyp_len.data_ptr(), count.data_ptr(), score.data_ptr(),
+                                       ptr(lab_dev), ptr(off_dev), ptr(errors), ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    else:
+        assert lm.classes == K and lm.next.device == dev, "the language model's tables have K columns and live on net_out's device"
+        _chk(lib.klstm_ctc_beam_decode_lm(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), ptr(class_weight),
+                                          beam, cands, nbest, lm.states, lm.next.data_ptr(), lm.weight.data_ptr(), ptr(lm.final),
+                                          hyp.data_ptr(), hyp_len.data_ptr(), count.data_ptr(), score.data_ptr(), ptr(lab_dev), ptr(off_dev),
+                                          ptr(errors), ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
     return CtcBeamResult(hyp, hyp_len, count, score, errors)
 
 
