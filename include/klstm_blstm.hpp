@@ -51,7 +51,6 @@ class BLstmProjectedStreams {
     f_->SetPersistVerify(true);
     b_->SetPersistVerify(true);
   }
-  ~BLstmProjectedStreams() { if (lens_own_) klstm_free(lens_own_); }
   BLstmProjectedStreams(const BLstmProjectedStreams &) = delete;
   BLstmProjectedStreams &operator=(const BLstmProjectedStreams &) = delete;
 
@@ -82,14 +81,9 @@ class BLstmProjectedStreams {
   void SetSeqLengths(const std::vector<int32> &lens) {
     if ((int32)lens.size() != NumStream()) KLSTM_ERR("SetSeqLengths: " << lens.size() << " lengths for " << NumStream() << " streams");
     for (int32 v : lens) if (v < 0) KLSTM_ERR("SetSeqLengths: negative length " << v);
-    if (!lens_own_) {
-      void *p = nullptr;
-      KCheck(klstm_malloc(&p, (size_t)NumStream() * sizeof(int32)));
-      lens_own_ = (int32 *)p;
-    }
-    KCheck(klstm_memcpy_h2d(lens_own_, lens.data(), lens.size() * sizeof(int32), stream_));
+    lens_own_.Upload(lens, stream_);
     lens_host_ = lens;
-    lens_dev_ = lens_own_;
+    lens_dev_ = lens_own_.As<int32>();
   }
   // The same from S ints the caller keeps on the device (they must stay there, unchanged, until the Update of the minibatch).  The
   // kernels clamp them to [0, T]; nothing is checked on the host.
@@ -166,7 +160,7 @@ class BLstmProjectedStreams {
   std::unique_ptr<LstmProjectedStreams> f_, b_;
   void *stream_ = nullptr;
   bool update_follows_ = false;
-  int32 *lens_own_ = nullptr;                 // device copy of SetSeqLengths(vector)
+  DeviceBuffer lens_own_;                     // device copy of SetSeqLengths(vector)
   const int32 *lens_dev_ = nullptr;           // the lengths the kernels read
   std::vector<int32> lens_host_;              // (empty with the device-pointer form)
   int32 T_ = 0;

@@ -16,46 +16,92 @@ namespace klstm_kaldi {
 
 inline void KCheck(klstm_status st) { if (st != KLSTM_OK) KLSTM_ERR("klstm: " << klstm_last_error() << " (status " << (int)st << ")"); }
 
+// Owning device memory, move-only and grow-only: the one place in the headers that calls klstm_malloc.  Grow frees before it
+// allocates and forgets the old block first, so a klstm_malloc that fails (KCheck throws) leaves an empty buffer behind.
+class DeviceBuffer {
+ public:
+  DeviceBuffer() {}
+  ~DeviceBuffer() { klstm_free(p_); }
+  DeviceBuffer(DeviceBuffer &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+  DeviceBuffer &operator=(DeviceBuffer &&o) noexcept {
+    if (this != &o) { klstm_free(p_); p_ = o.p_; cap_ = o.cap_; o.p_ = nullptr; o.cap_ = 0; }
+    return *this;
+  }
+  void Grow(size_t bytes) {                                   // contents are not kept
+    if (bytes <= cap_) return;
+    klstm_free(p_); p_ = nullptr; cap_ = 0;
+    KCheck(klstm_malloc(&p_, bytes));
+    cap_ = bytes;
+  }
+  size_t Capacity() const { return cap_; }                    // bytes
+  template <class T> T *As() const { return static_cast<T *>(p_); }       // null while nothing was ever needed
+  template <class T> void Upload(const std::vector<T> &v, void *hip_stream = nullptr) {
+    Grow(v.size() * sizeof(T));
+    if (!v.empty()) KCheck(klstm_memcpy_h2d(p_, v.data(), v.size() * sizeof(T), hip_stream));
+  }
+  template <class T> void Download(T *dst, size_t n) const { if (n) KCheck(klstm_memcpy_d2h(dst, p_, n * sizeof(T), nullptr)); }
+ private:
+  void *p_ = nullptr;
+  size_t cap_ = 0;
+};
+
+// N running sums that kernels add to: allocated and zeroed at the first Dev(), copied back once per Read() (all zeros before that).
+template <int N>
+class DeviceTotals {
+ public:
+  double *Dev() {
+    if (!zeroed_) {
+      buf_.Grow(N * sizeof(double));
+      KCheck(klstm_memset_zero(buf_.As<double>(), N * sizeof(double), nullptr));
+      zeroed_ = true;
+    }
+    return buf_.As<double>();
+  }
+  const double *Read() const {                                // synchronises; valid until the next Read
+    for (double &v : h_) v = 0;
+    buf_.Download(h_, zeroed_ ? N : 0);
+    return h_;
+  }
+ private:
+  DeviceBuffer buf_;
+  bool zeroed_ = false;
+  mutable double h_[N];
+};
+
 // CuMatrix stand-in: owning, pitched device matrix (cu-matrix.cc:51-84: rows are pitched; here the stride is the
 // column count rounded up to 64 floats = 256 B).
 class DeviceMatrix {
  public:
-  DeviceMatrix() : data_(nullptr), rows_(0), cols_(0), stride_(0), cap_(0) {}
-  ~DeviceMatrix() { if (data_) klstm_free(data_); }
+  DeviceMatrix() : rows_(0), cols_(0), stride_(0) {}
   DeviceMatrix(const DeviceMatrix &) = delete;
   DeviceMatrix &operator=(const DeviceMatrix &) = delete;
   void Resize(int32 rows, int32 cols, bool set_zero = true) {     // no realloc when the shape is unchanged (cu-matrix.cc:56-59)
     const int32 stride = (cols + 63) / 64 * 64;
     const size_t need = (size_t)rows * stride;
-    if (need > cap_) {
-      if (data_) KCheck(klstm_free(data_));
-      void *p = nullptr;
-      KCheck(klstm_malloc(&p, need * sizeof(BaseFloat)));
-      data_ = (BaseFloat *)p; cap_ = need;
-    }
+    buf_.Grow(need * sizeof(BaseFloat));
     rows_ = rows; cols_ = cols; stride_ = stride;
-    if (set_zero && need) KCheck(klstm_memset_zero(data_, need * sizeof(BaseFloat), nullptr));
+    if (set_zero && need) KCheck(klstm_memset_zero(Data(), need * sizeof(BaseFloat), nullptr));
   }
   int32 NumRows() const { return rows_; }
   int32 NumCols() const { return cols_; }
   int32 Stride() const { return stride_; }
-  MatrixView View() const { return MatrixView(data_, rows_, cols_, stride_); }
+  MatrixView View() const { return MatrixView(Data(), rows_, cols_, stride_); }
   void CopyFromHost(const BaseFloat *src, int32 rows, int32 cols) {          // CuMatrix(const Matrix&), cu-matrix.cc:287-311
     Resize(rows, cols, false);
     std::vector<BaseFloat> tmp((size_t)rows * stride_, 0.f);
     for (int32 r = 0; r < rows; r++) std::memcpy(&tmp[(size_t)r * stride_], src + (size_t)r * cols, cols * sizeof(BaseFloat));
-    if (!tmp.empty()) KCheck(klstm_memcpy_h2d(data_, tmp.data(), tmp.size() * sizeof(BaseFloat), nullptr));
+    buf_.Upload(tmp);
   }
   void CopyToHost(std::vector<BaseFloat> *dst) const {
     std::vector<BaseFloat> tmp((size_t)rows_ * stride_);
-    if (!tmp.empty()) KCheck(klstm_memcpy_d2h(tmp.data(), data_, tmp.size() * sizeof(BaseFloat), nullptr));
+    buf_.Download(tmp.data(), tmp.size());
     dst->resize((size_t)rows_ * cols_);
     for (int32 r = 0; r < rows_; r++) std::memcpy(&(*dst)[(size_t)r * cols_], &tmp[(size_t)r * stride_], cols_ * sizeof(BaseFloat));
   }
  private:
-  BaseFloat *data_;
+  BaseFloat *Data() const { return buf_.As<BaseFloat>(); }
+  DeviceBuffer buf_;
   int32 rows_, cols_, stride_;
-  size_t cap_;
 };
 
 // Polymorphic view of one nnet1 component (Component / UpdatableComponent, [UPSTREAM-unvendored] nnet-component.h).
@@ -141,9 +187,7 @@ class TransmitLayer : public Layer {
 // "<AffineTransform> 16624 512 <LearnRateCoef> 1 <BiasLearnRateCoef> 1 <MaxNorm> 0  [ ..." (README.md:27).
 class AffineLayer : public Layer {
  public:
-  AffineLayer(int32 in, int32 out) : in_(in), out_(out), lr_coef_(1.f), bias_lr_coef_(1.f), max_norm_(0.f),
-                                     W_(nullptr), b_(nullptr), Wc_(nullptr), bc_(nullptr) {}
-  ~AffineLayer() override { klstm_free(W_); klstm_free(b_); klstm_free(Wc_); klstm_free(bc_); }
+  AffineLayer(int32 in, int32 out) : in_(in), out_(out), lr_coef_(1.f), bias_lr_coef_(1.f), max_norm_(0.f) {}
   const char *Marker() const override { return "<AffineTransform>"; }
   int32 InputDim() const override { return in_; }
   int32 OutputDim() const override { return out_; }
@@ -178,13 +222,13 @@ class AffineLayer : public Layer {
   void SetParams(const std::vector<BaseFloat> &w, const std::vector<BaseFloat> &b) {
     KLSTM_ASSERT((int32)w.size() == out_ * in_ && (int32)b.size() == out_);
     hw_ = w; hb_ = b; host_fresh_ = true;
-    if (W_) Upload();
+    if (on_device_) Upload();
   }
   void HostParams(std::vector<BaseFloat> *w, std::vector<BaseFloat> *b) const {
-    if (W_ && !host_fresh_) {
+    if (on_device_ && !host_fresh_) {
       hw_.resize((size_t)out_ * in_); hb_.resize(out_);
-      KCheck(klstm_memcpy_d2h(hw_.data(), W_, hw_.size() * sizeof(BaseFloat), nullptr));
-      KCheck(klstm_memcpy_d2h(hb_.data(), b_, hb_.size() * sizeof(BaseFloat), nullptr));
+      W_.Download(hw_.data(), hw_.size());
+      b_.Download(hb_.data(), hb_.size());
       host_fresh_ = true;
     }
     *w = hw_; *b = hb_;
@@ -195,39 +239,41 @@ class AffineLayer : public Layer {
   }
   void PropagateFnc(const MatrixView &in, MatrixView *out) override {
     Alloc();
-    KCheck(klstm_affine_propagate(in.Data(), in.NumRows(), in_, in.Stride(), W_, b_, out->Data(), out_, out->Stride(), nullptr));
+    KCheck(klstm_affine_propagate(in.Data(), in.NumRows(), in_, in.Stride(), W(), b(), out->Data(), out_, out->Stride(), nullptr));
   }
   void BackpropagateFnc(const MatrixView &, const MatrixView &, const MatrixView &od, MatrixView *id) override {
-    if (id) KCheck(klstm_affine_backpropagate(od.Data(), od.NumRows(), out_, od.Stride(), W_, in_, id->Data(), id->Stride(), nullptr));
+    if (id) KCheck(klstm_affine_backpropagate(od.Data(), od.NumRows(), out_, od.Stride(), W(), in_, id->Data(), id->Stride(), nullptr));
   }
   void Update(const MatrixView &input, const MatrixView &diff) override {
     if (opts_.l2_penalty != 0.f || opts_.l1_penalty != 0.f) KLSTM_ERR("AffineTransform: l1/l2 penalties are not implemented");
-    KCheck(klstm_affine_update(input.Data(), input.Stride(), diff.Data(), diff.Stride(), input.NumRows(), in_, out_, W_, b_, Wc_, bc_,
-                               opts_.learn_rate * lr_coef_, opts_.learn_rate * bias_lr_coef_, opts_.momentum, nullptr));
+    KCheck(klstm_affine_update(input.Data(), input.Stride(), diff.Data(), diff.Stride(), input.NumRows(), in_, out_, W(), b(),
+                               Wc_.As<BaseFloat>(), bc_.As<BaseFloat>(), opts_.learn_rate * lr_coef_, opts_.learn_rate * bias_lr_coef_,
+                               opts_.momentum, nullptr));
     host_fresh_ = false;
   }
   void SetTrainOptions(const NnetTrainOptions &o) override { opts_ = o; }
  private:
-  void Alloc() {
-    if (W_) return;
-    void *p;
-    KCheck(klstm_malloc(&p, (size_t)out_ * in_ * 4)); W_ = (BaseFloat *)p;
-    KCheck(klstm_malloc(&p, (size_t)out_ * 4)); b_ = (BaseFloat *)p;
-    KCheck(klstm_malloc(&p, (size_t)out_ * in_ * 4)); Wc_ = (BaseFloat *)p;
-    KCheck(klstm_malloc(&p, (size_t)out_ * 4)); bc_ = (BaseFloat *)p;
-    KCheck(klstm_memset_zero(Wc_, (size_t)out_ * in_ * 4, nullptr));
-    KCheck(klstm_memset_zero(bc_, (size_t)out_ * 4, nullptr));
+  void Alloc() {                          // on_device_ only once everything is there: a failure half way is tried again in full
+    if (on_device_) return;
+    Wc_.Grow((size_t)out_ * in_ * 4);
+    bc_.Grow((size_t)out_ * 4);
+    KCheck(klstm_memset_zero(Wc_.As<BaseFloat>(), (size_t)out_ * in_ * 4, nullptr));
+    KCheck(klstm_memset_zero(bc_.As<BaseFloat>(), (size_t)out_ * 4, nullptr));
     Upload();
+    on_device_ = true;
   }
   void Upload() {
     KLSTM_ASSERT((int32)hw_.size() == out_ * in_ && (int32)hb_.size() == out_);
-    KCheck(klstm_memcpy_h2d(W_, hw_.data(), hw_.size() * sizeof(BaseFloat), nullptr));
-    KCheck(klstm_memcpy_h2d(b_, hb_.data(), hb_.size() * sizeof(BaseFloat), nullptr));
+    W_.Upload(hw_);
+    b_.Upload(hb_);
   }
+  BaseFloat *W() const { return W_.As<BaseFloat>(); }
+  BaseFloat *b() const { return b_.As<BaseFloat>(); }
   int32 in_, out_;
   BaseFloat lr_coef_, bias_lr_coef_, max_norm_;
   NnetTrainOptions opts_;
-  BaseFloat *W_, *b_, *Wc_, *bc_;
+  DeviceBuffer W_, b_, Wc_, bc_;
+  bool on_device_ = false;
   mutable std::vector<BaseFloat> hw_, hb_;
   mutable bool host_fresh_ = true;
 };
@@ -360,11 +406,9 @@ class Nnet {                                  // google/nnet/nnet-nnet.h:36-150
 typedef std::vector<std::vector<std::pair<int32, BaseFloat> > > Posterior;
 
 // Xent with the overlay's EvalMasked (google/nnet/nnet-loss.h:33-80, nnet-loss.cc:76-164, Report :293-307).
-class Xent {
+class Xent {                                    // (not copyable: its buffers are not)
  public:
-  Xent() : frames_(0), correct_(0), loss_(0), entropy_(0), tgt_(nullptr), mask_(nullptr), rx_(nullptr), rc_(nullptr), cap_(0),
-           poff_(nullptr), ppdf_(nullptr), pw_(nullptr), re_(nullptr), pcap_(0), ecap_(0) {}
-  ~Xent() { klstm_free(tgt_); klstm_free(mask_); klstm_free(rx_); klstm_free(rc_); klstm_free(poff_); klstm_free(ppdf_); klstm_free(pw_); klstm_free(re_); }
+  Xent() : frames_(0), correct_(0), loss_(0), entropy_(0) {}
   // EvalMasked with the reference's signature (nnet-loss.cc:76-79): general posteriors.  The (pdf, weight) lists go to the
   // device as CSR arrays (a few KB) instead of the reference's dense num_frames x num_pdf host matrix (:85-97).
   void EvalMasked(const std::vector<BaseFloat> &frame_mask, const DeviceMatrix &net_out, const Posterior &post, DeviceMatrix *diff) {
@@ -380,33 +424,20 @@ class Xent {
       }
       off.push_back((int32)pdf.size());
     }
-    void *p;
-    if ((size_t)n > pcap_) {
-      klstm_free(poff_); klstm_free(mask_); klstm_free(rx_); klstm_free(rc_); klstm_free(re_); klstm_free(tgt_);
-      KCheck(klstm_malloc(&p, (size_t)(n + 1) * 4)); poff_ = (int32 *)p;
-      KCheck(klstm_malloc(&p, (size_t)n * 4)); mask_ = (BaseFloat *)p;
-      KCheck(klstm_malloc(&p, (size_t)n * 4)); rx_ = (BaseFloat *)p;
-      KCheck(klstm_malloc(&p, (size_t)n * 4)); rc_ = (BaseFloat *)p;
-      KCheck(klstm_malloc(&p, (size_t)n * 4)); re_ = (BaseFloat *)p;
-      KCheck(klstm_malloc(&p, (size_t)n * 4)); tgt_ = (int32 *)p;
-      pcap_ = n; cap_ = n;
-    }
-    if (pdf.size() + 1 > ecap_) {
-      klstm_free(ppdf_); klstm_free(pw_);
-      ecap_ = pdf.size() + 1;
-      KCheck(klstm_malloc(&p, ecap_ * 4)); ppdf_ = (int32 *)p;
-      KCheck(klstm_malloc(&p, ecap_ * 4)); pw_ = (BaseFloat *)p;
-    }
-    KCheck(klstm_memcpy_h2d(poff_, off.data(), off.size() * 4, nullptr));
-    if (!pdf.empty()) { KCheck(klstm_memcpy_h2d(ppdf_, pdf.data(), pdf.size() * 4, nullptr)); KCheck(klstm_memcpy_h2d(pw_, w.data(), w.size() * 4, nullptr)); }
-    KCheck(klstm_memcpy_h2d(mask_, frame_mask.data(), (size_t)n * 4, nullptr));
+    poff_.Upload(off);
+    ppdf_.Upload(pdf);
+    pw_.Upload(w);
+    mask_.Upload(frame_mask);
+    rx_.Grow((size_t)n * 4); rc_.Grow((size_t)n * 4); re_.Grow((size_t)n * 4);
     diff->Resize(n, d, false);                                                            // :103
     MatrixView y = net_out.View(), dv = diff->View();
-    KCheck(klstm_xent_eval_masked_post(y.Data(), n, d, y.Stride(), poff_, ppdf_, pw_, mask_, dv.Data(), dv.Stride(), rx_, re_, rc_, nullptr));
+    KCheck(klstm_xent_eval_masked_post(y.Data(), n, d, y.Stride(), poff_.As<int32>(), ppdf_.As<int32>(), pw_.As<BaseFloat>(),
+                                       mask_.As<BaseFloat>(), dv.Data(), dv.Stride(), rx_.As<BaseFloat>(), re_.As<BaseFloat>(),
+                                       rc_.As<BaseFloat>(), nullptr));
     std::vector<BaseFloat> rx(n), rc(n), re(n);
-    KCheck(klstm_memcpy_d2h(rx.data(), rx_, (size_t)n * 4, nullptr));
-    KCheck(klstm_memcpy_d2h(rc.data(), rc_, (size_t)n * 4, nullptr));
-    KCheck(klstm_memcpy_d2h(re.data(), re_, (size_t)n * 4, nullptr));
+    rx_.Download(rx.data(), n);
+    rc_.Download(rc.data(), n);
+    re_.Download(re.data(), n);
     double xe = 0, ent = 0; int32 correct = 0, valid = 0;
     for (int32 i = 0; i < n; i++) { xe += rx[i]; ent += re[i]; correct += (rc[i] == 1.f); valid += (frame_mask[i] == 1.f); }
     loss_ += xe; entropy_ += ent; correct_ += correct; frames_ += valid;                  // :138-142
@@ -417,23 +448,16 @@ class Xent {
     const int32 n = net_out.NumRows(), d = net_out.NumCols();
     KLSTM_ASSERT(n == (int32)target.size() && n == (int32)frame_mask.size());          // :82
     for (int32 t : target) if (t >= d || t < 0) KLSTM_ERR("Posterior pdf-id out of NN-output dimension, please check number of pdfs by 'hmm-info'." << " nn-outputs : " << d << ", posterior pdf-id : " << t);   // :89-92
-    if ((size_t)n > cap_) {
-      klstm_free(tgt_); klstm_free(mask_); klstm_free(rx_); klstm_free(rc_);
-      void *p;
-      KCheck(klstm_malloc(&p, (size_t)n * 4)); tgt_ = (int32 *)p;
-      KCheck(klstm_malloc(&p, (size_t)n * 4)); mask_ = (BaseFloat *)p;
-      KCheck(klstm_malloc(&p, (size_t)n * 4)); rx_ = (BaseFloat *)p;
-      KCheck(klstm_malloc(&p, (size_t)n * 4)); rc_ = (BaseFloat *)p;
-      cap_ = n;
-    }
-    KCheck(klstm_memcpy_h2d(tgt_, target.data(), (size_t)n * 4, nullptr));
-    KCheck(klstm_memcpy_h2d(mask_, frame_mask.data(), (size_t)n * 4, nullptr));
+    tgt_.Upload(target);
+    mask_.Upload(frame_mask);
+    rx_.Grow((size_t)n * 4); rc_.Grow((size_t)n * 4);
     diff->Resize(n, d, false);                                                            // :103
     MatrixView y = net_out.View(), dv = diff->View();
-    KCheck(klstm_xent_eval_masked(y.Data(), n, d, y.Stride(), tgt_, mask_, dv.Data(), dv.Stride(), rx_, rc_, nullptr));
+    KCheck(klstm_xent_eval_masked(y.Data(), n, d, y.Stride(), tgt_.As<int32>(), mask_.As<BaseFloat>(), dv.Data(), dv.Stride(),
+                                  rx_.As<BaseFloat>(), rc_.As<BaseFloat>(), nullptr));
     std::vector<BaseFloat> rx(n), rc(n);
-    KCheck(klstm_memcpy_d2h(rx.data(), rx_, (size_t)n * 4, nullptr));
-    KCheck(klstm_memcpy_d2h(rc.data(), rc_, (size_t)n * 4, nullptr));
+    rx_.Download(rx.data(), n);
+    rc_.Download(rc.data(), n);
     double xe = 0; int32 correct = 0, valid = 0;
     for (int32 i = 0; i < n; i++) { xe += rx[i]; correct += (rc[i] == 1.f); valid += (frame_mask[i] == 1.f); }
     loss_ += xe; correct_ += correct; frames_ += valid;                                   // :138-142 (entropy of one-hot targets is 0)
@@ -450,10 +474,8 @@ class Xent {
   double Frames() const { return frames_; }
  private:
   double frames_, correct_, loss_, entropy_;
-  int32 *tgt_; BaseFloat *mask_, *rx_, *rc_;
-  size_t cap_;
-  int32 *poff_, *ppdf_; BaseFloat *pw_, *re_;      // CSR posterior and per-row target entropy of the general EvalMasked
-  size_t pcap_, ecap_;
+  DeviceBuffer tgt_, mask_, rx_, rc_;
+  DeviceBuffer poff_, ppdf_, pw_, re_;             // CSR posterior and per-row target entropy of the general EvalMasked
 };
 
 struct TrainLstmStreamsOptions {              // bd-nnet-train-lstm-streams.cc:27-71 (the options that matter)
@@ -491,84 +513,104 @@ inline TrainLstmStreamsStats TrainLstmStreams(Nnet *nnet, const std::vector<Utte
   return st;
 }
 
+// What Ctc, CtcGreedyDecoder, CtcBeamDecoder and CtcAligner do before their C call: the device copy of the lengths, the shape of the
+// call, the class weights and the workspace.  (A base for its members only: nothing virtual, and nobody holds a pointer to it.)
+class CtcCallBase {
+ protected:
+  explicit CtcCallBase(int32 blank) : blank_(blank) {}
+  void SetClassWeights(const std::vector<BaseFloat> &w) { num_weights_ = (int32)w.size(); w_.Upload(w); }
+  const int32 *UploadLens(int32 num_stream, const std::vector<int32> &lens) {      // for the overload that takes them on the device
+    KLSTM_ASSERT((int32)lens.size() == num_stream);
+    lens_.Upload(lens);
+    return lens_.As<int32>();
+  }
+  // T of net_out [T*num_stream x K].  num_lists: the label or reference lists given, one per stream (or_none: or none at all)
+  int32 NumFrames(const DeviceMatrix &net_out, int32 num_stream, const int32 *lens_dev, size_t num_lists, bool or_none) const {
+    const int32 rows = net_out.NumRows();
+    KLSTM_ASSERT(num_stream > 0 && rows > 0 && rows % num_stream == 0 && lens_dev);
+    KLSTM_ASSERT((or_none && num_lists == 0) || (int32)num_lists == num_stream);
+    KLSTM_ASSERT(num_weights_ == 0 || num_weights_ == net_out.NumCols());
+    return rows / num_stream;
+  }
+  void *Workspace(size_t need) {                     // need: the answer of the call's klstm_ctc_*_workspace_bytes (0: it refused)
+    if (need == 0) KLSTM_ERR("klstm: " << klstm_last_error());
+    ws_.Grow(need);
+    return ws_.As<void>();
+  }
+  const BaseFloat *Weights() const { return num_weights_ ? w_.As<BaseFloat>() : nullptr; }
+  int32 blank_, num_stream_ = 0, rows_ = 0, num_weights_ = 0;      // num_stream_, rows_: of the last call that succeeded
+ private:
+  DeviceBuffer ws_, lens_, w_;
+};
+
+// Label lists as the CSR arrays of the C-ABI on the device: the labels back to back (one 0 where there are none at all, so that the
+// array exists) and one offset per list plus the end.  The host keeps the offsets, the number of labels and the longest list.
+class PackedLabels {
+ public:
+  void Upload(const std::vector<std::vector<int32> > &lists) {
+    std::vector<int32> flat;
+    offsets.assign(1, 0);
+    longest = 0;
+    for (const auto &l : lists) { flat.insert(flat.end(), l.begin(), l.end()); offsets.push_back((int32)flat.size()); longest = std::max(longest, l.size()); }
+    num_labels = flat.size();
+    if (flat.empty()) flat.push_back(0);
+    lab_.Upload(flat);
+    off_.Upload(offsets);
+  }
+  const int32 *Labels() const { return lab_.As<int32>(); }
+  const int32 *Offsets() const { return off_.As<int32>(); }
+  std::vector<int32> offsets;
+  size_t num_labels = 0, longest = 0;
+ private:
+  DeviceBuffer lab_, off_;
+};
+
 // Connectionist temporal classification on whole utterances (klstm_ctc_eval, klstm.h; not in the reference, whose only objective is
 // the frame-level Xent above).  diff is the derivative with respect to the Softmax INPUT, like Xent's (SoftmaxLayer passes it on).
 // The statistics stay on the device (four doubles that every Eval adds to) and are read when somebody asks: once per Report().
-class Ctc {
+class Ctc : private CtcCallBase {
  public:
-  explicit Ctc(int32 blank = 0) : blank_(blank) {}
-  ~Ctc() { klstm_free(ws_); klstm_free(lens_); klstm_free(lab_); klstm_free(off_); klstm_free(loss_); klstm_free(tot_); }
-  Ctc(const Ctc &) = delete;
-  Ctc &operator=(const Ctc &) = delete;
+  explicit Ctc(int32 blank = 0) : CtcCallBase(blank) {}
 
   // net_out [T*num_stream x K] posteriors (row t*S + s); lens: frames per stream (0 = idle), labels: per stream.  Utterances that
   // cannot be aligned (klstm.h: too short for their labels, a label outside [0, K) or equal to the blank) get zero diff rows and are
   // counted as rejected, on the device.  Only the shape is checked here.
   void Eval(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &labels,
             DeviceMatrix *diff) {
-    KLSTM_ASSERT((int32)lens.size() == num_stream);
-    Grow(&lens_, &lens_cap_, (size_t)num_stream * sizeof(int32));
-    KCheck(klstm_memcpy_h2d(lens_, lens.data(), (size_t)num_stream * sizeof(int32), nullptr));
-    Eval(net_out, num_stream, (const int32 *)lens_, labels, diff);
+    Eval(net_out, num_stream, UploadLens(num_stream, lens), labels, diff);
   }
   // the same with the lengths already on the device (the array SetSeqLengths was given)
   void Eval(const DeviceMatrix &net_out, int32 num_stream, const int32 *lens_dev, const std::vector<std::vector<int32> > &labels,
             DeviceMatrix *diff) {
-    const int32 rows = net_out.NumRows(), K = net_out.NumCols();
-    KLSTM_ASSERT(num_stream > 0 && rows > 0 && rows % num_stream == 0 && (int32)labels.size() == num_stream && lens_dev);
-    const int32 T = rows / num_stream;
-    std::vector<int32> off(1, 0), flat;
-    size_t longest = 0;
-    for (const auto &l : labels) { flat.insert(flat.end(), l.begin(), l.end()); off.push_back((int32)flat.size()); longest = std::max(longest, l.size()); }
-    if (flat.empty()) flat.push_back(0);
-    const size_t need = klstm_ctc_workspace_bytes(T, num_stream, (int)longest);
-    if (need == 0) KLSTM_ERR("klstm: " << klstm_last_error());
-    Grow(&ws_, &ws_cap_, need);
-    Grow(&lab_, &lab_cap_, flat.size() * sizeof(int32));
-    Grow(&off_, &off_cap_, off.size() * sizeof(int32));
-    Grow(&loss_, &loss_cap_, (size_t)num_stream * sizeof(BaseFloat));
-    if (!tot_) { void *p; KCheck(klstm_malloc(&p, 4 * sizeof(double))); tot_ = (double *)p; KCheck(klstm_memset_zero(tot_, 4 * sizeof(double), nullptr)); }
-    KCheck(klstm_memcpy_h2d(lab_, flat.data(), flat.size() * sizeof(int32), nullptr));
-    KCheck(klstm_memcpy_h2d(off_, off.data(), off.size() * sizeof(int32), nullptr));
-    diff->Resize(rows, K, false);
+    const int32 T = NumFrames(net_out, num_stream, lens_dev, labels.size(), false), K = net_out.NumCols();
+    lab_.Upload(labels);
+    const size_t need = klstm_ctc_workspace_bytes(T, num_stream, (int)lab_.longest);
+    void *ws = Workspace(need);
+    loss_.Grow((size_t)num_stream * sizeof(BaseFloat));
+    diff->Resize(net_out.NumRows(), K, false);
     MatrixView y = net_out.View(), dv = diff->View();
-    KCheck(klstm_ctc_eval(y.Data(), T, num_stream, K, y.Stride(), lens_dev, (const int32 *)lab_, (const int32 *)off_, blank_, dv.Data(),
-                          dv.Stride(), (BaseFloat *)loss_, tot_, ws_, need, nullptr));
+    KCheck(klstm_ctc_eval(y.Data(), T, num_stream, K, y.Stride(), lens_dev, lab_.Labels(), lab_.Offsets(), blank_, dv.Data(), dv.Stride(),
+                          loss_.As<BaseFloat>(), tot_.Dev(), ws, need, nullptr));
     num_stream_ = num_stream;
   }
   // -log p(labels | x) of the streams of the last Eval (+inf: rejected, 0: idle).  Synchronises.
-  void UttLoss(std::vector<BaseFloat> *loss) const {
-    loss->assign(num_stream_, 0.f);
-    if (num_stream_) KCheck(klstm_memcpy_d2h(loss->data(), loss_, (size_t)num_stream_ * sizeof(BaseFloat), nullptr));
-  }
-  double AvgLoss() const { Fetch(); return h_[0] / h_[1]; }                // per utterance counted
-  double AvgLossPerFrame() const { Fetch(); return h_[0] / h_[3]; }
-  double NumUtterances() const { Fetch(); return h_[1]; }
-  double NumRejected() const { Fetch(); return h_[2]; }
-  double Frames() const { Fetch(); return h_[3]; }
+  void UttLoss(std::vector<BaseFloat> *loss) const { loss->assign(num_stream_, 0.f); loss_.Download(loss->data(), loss->size()); }
+  double AvgLoss() const { const double *h = tot_.Read(); return h[0] / h[1]; }                // per utterance counted
+  double AvgLossPerFrame() const { const double *h = tot_.Read(); return h[0] / h[3]; }
+  double NumUtterances() const { return tot_.Read()[1]; }
+  double NumRejected() const { return tot_.Read()[2]; }
+  double Frames() const { return tot_.Read()[3]; }
   std::string Report() const {
-    Fetch();
+    const double *h = tot_.Read();                                          // one small copy per question, none per minibatch
     std::ostringstream oss;
-    oss << "AvgLoss: " << h_[0] / h_[1] << " (Ctc) per utterance, " << h_[0] / h_[3] << " per frame, [" << h_[1] << " utterances, " << h_[3]
-        << " frames, " << h_[2] << " rejected]" << std::endl;
+    oss << "AvgLoss: " << h[0] / h[1] << " (Ctc) per utterance, " << h[0] / h[3] << " per frame, [" << h[1] << " utterances, " << h[3]
+        << " frames, " << h[2] << " rejected]" << std::endl;
     return oss.str();
   }
  private:
-  static void Grow(void **p, size_t *cap, size_t need) {
-    if (need <= *cap) return;
-    klstm_free(*p); *p = nullptr; *cap = 0;
-    KCheck(klstm_malloc(p, need));
-    *cap = need;
-  }
-  void Fetch() const {                                                      // one small copy per question, none per minibatch
-    h_[0] = h_[1] = h_[2] = h_[3] = 0;
-    if (tot_) KCheck(klstm_memcpy_d2h(h_, tot_, 4 * sizeof(double), nullptr));
-  }
-  int32 blank_, num_stream_ = 0;
-  void *ws_ = nullptr, *lens_ = nullptr, *lab_ = nullptr, *off_ = nullptr, *loss_ = nullptr;
-  size_t ws_cap_ = 0, lens_cap_ = 0, lab_cap_ = 0, off_cap_ = 0, loss_cap_ = 0;
-  double *tot_ = nullptr;
-  mutable double h_[4] = {0, 0, 0, 0};
+  PackedLabels lab_;
+  DeviceBuffer loss_;
+  DeviceTotals<4> tot_;
 };
 
 struct TrainCtcOptions {
@@ -584,33 +626,46 @@ struct TrainCtcStats {
 // One pass over the utterances, num_stream whole utterances per minibatch, for unidirectional and bidirectional stacks alike: the
 // lengths go to every component (the bidirectional layer needs them), every stream starts from zero state (a unidirectional
 // <LstmProjectedStreams> stack through Reset; the bidirectional layer resets itself), and a unidirectional layer simply runs on
-// through the padding: padding follows every valid frame and its diff rows are zero.  every_batch (optional) sees each minibatch
-// after Ctc::Eval: (batch, net_out, obj_diff, ctc).
-template <class F>
-inline TrainCtcStats TrainCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const TrainCtcOptions &o, std::string *report,
-                                             F every_batch) {
-  nnet->SetTrainOptions(o.trn_opts);
-  WholeUtteranceBatcher batcher(&utts, o.num_stream, o.sort_by_length, o.max_frames);
-  Ctc ctc(o.blank);
+// through the padding: padding follows every valid frame.  body sees each minibatch after Propagate: (batch, net_out).  Returns a
+// Stats (one of the four below) with num_minibatches, seconds, num_done and num_skipped filled in.
+template <class Stats, class Body>
+inline Stats ForEachWholeUtteranceBatch(Nnet *nnet, const std::vector<Utterance> &utts, int32 num_stream, bool sort_by_length,
+                                        int32 max_frames, Body body) {
+  WholeUtteranceBatcher batcher(&utts, num_stream, sort_by_length, max_frames);
   UtteranceBatch b;
-  DeviceMatrix feat_dev, nnet_out, obj_diff;
-  TrainCtcStats st;
-  std::vector<int> all(o.num_stream, 1);
+  DeviceMatrix feat_dev, nnet_out;
+  Stats st;
+  std::vector<int> all(num_stream, 1);
   const auto t0 = std::chrono::steady_clock::now();
   while (batcher.Next(&b)) {
     nnet->SetSeqLengths(b.lens);
     nnet->Reset(all);
     feat_dev.CopyFromHost(b.feat.data(), b.num_frames * b.num_stream, b.dim);
     nnet->Propagate(feat_dev.View(), &nnet_out);
-    ctc.Eval(nnet_out, b.num_stream, b.lens, b.labels, &obj_diff);
-    every_batch(b, nnet_out, obj_diff, ctc);
-    if (!o.crossvalidate) nnet->Backpropagate(obj_diff.View(), nullptr);
+    body(b, nnet_out);
     st.num_minibatches++;
   }
   KCheck(klstm_stream_synchronize(nullptr));
   st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   st.num_done = batcher.NumDone();
   st.num_skipped = batcher.NumSkipped();
+  return st;
+}
+
+// CTC training: the diff rows of the padding are zero.  every_batch (optional) sees each minibatch after Ctc::Eval: (batch, net_out,
+// obj_diff, ctc).
+template <class F>
+inline TrainCtcStats TrainCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const TrainCtcOptions &o, std::string *report,
+                                             F every_batch) {
+  nnet->SetTrainOptions(o.trn_opts);
+  Ctc ctc(o.blank);
+  DeviceMatrix obj_diff;
+  TrainCtcStats st = ForEachWholeUtteranceBatch<TrainCtcStats>(nnet, utts, o.num_stream, o.sort_by_length, o.max_frames,
+      [&](const UtteranceBatch &b, const DeviceMatrix &nnet_out) {
+        ctc.Eval(nnet_out, b.num_stream, b.lens, b.labels, &obj_diff);
+        every_batch(b, nnet_out, obj_diff, ctc);
+        if (!o.crossvalidate) nnet->Backpropagate(obj_diff.View(), nullptr);
+      });
   st.num_rejected = ctc.NumRejected();
   st.total_frames = ctc.Frames();
   st.avg_loss = ctc.AvgLoss();
@@ -625,108 +680,66 @@ inline TrainCtcStats TrainCtcWholeUtterances(Nnet *nnet, const std::vector<Utter
 
 // CTC best-path decoding of whole utterances and the token error rate against reference label sequences (klstm_ctc_decode, klstm.h;
 // INTEGRATION.md 3e).  The five totals stay on the device and are read when somebody asks, like Ctc's.
-class CtcGreedyDecoder {
+class CtcGreedyDecoder : private CtcCallBase {
  public:
-  explicit CtcGreedyDecoder(int32 blank = 0) : blank_(blank) {}
-  ~CtcGreedyDecoder() {
-    klstm_free(ws_); klstm_free(lens_); klstm_free(lab_); klstm_free(off_); klstm_free(hyp_); klstm_free(hlen_); klstm_free(score_);
-    klstm_free(fc_); klstm_free(err_); klstm_free(w_); klstm_free(tot_);
-  }
-  CtcGreedyDecoder(const CtcGreedyDecoder &) = delete;
-  CtcGreedyDecoder &operator=(const CtcGreedyDecoder &) = delete;
+  explicit CtcGreedyDecoder(int32 blank = 0) : CtcCallBase(blank) {}
 
   // One weight per class: the winner of a frame is argmax_k y[k] * w[k] (label priors: w[k] = prior[k]^-alpha).  Empty: none.
-  void SetClassWeights(const std::vector<BaseFloat> &w) {
-    num_weights_ = (int32)w.size();
-    if (w.empty()) return;
-    Grow(&w_, &w_cap_, w.size() * sizeof(BaseFloat));
-    KCheck(klstm_memcpy_h2d(w_, w.data(), w.size() * sizeof(BaseFloat), nullptr));
-  }
+  using CtcCallBase::SetClassWeights;
   // net_out [T*num_stream x K] posteriors (row t*S + s); lens: frames per stream (0 = idle); refs: empty (no scoring) or one reference
   // per stream; hyps (optional): the hypothesis of every stream.  Asking for hyps synchronises; the rest stays on the device.
   void Decode(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &refs,
               std::vector<std::vector<int32> > *hyps) {
-    KLSTM_ASSERT((int32)lens.size() == num_stream);
-    Grow(&lens_, &lens_cap_, (size_t)num_stream * sizeof(int32));
-    KCheck(klstm_memcpy_h2d(lens_, lens.data(), (size_t)num_stream * sizeof(int32), nullptr));
-    Decode(net_out, num_stream, (const int32 *)lens_, refs, hyps);
+    Decode(net_out, num_stream, UploadLens(num_stream, lens), refs, hyps);
   }
   void Decode(const DeviceMatrix &net_out, int32 num_stream, const int32 *lens_dev, const std::vector<std::vector<int32> > &refs,
               std::vector<std::vector<int32> > *hyps) {
-    const int32 rows = net_out.NumRows(), K = net_out.NumCols();
-    KLSTM_ASSERT(num_stream > 0 && rows > 0 && rows % num_stream == 0 && lens_dev && (refs.empty() || (int32)refs.size() == num_stream));
-    KLSTM_ASSERT(num_weights_ == 0 || num_weights_ == K);
-    const int32 T = rows / num_stream;
+    const int32 T = NumFrames(net_out, num_stream, lens_dev, refs.size(), true), rows = net_out.NumRows(), K = net_out.NumCols();
     const bool scoring = !refs.empty();
     const size_t need = klstm_ctc_decode_workspace_bytes(T, num_stream, 0);
-    if (need == 0) KLSTM_ERR("klstm: " << klstm_last_error());
-    Grow(&ws_, &ws_cap_, need);
-    Grow(&hyp_, &hyp_cap_, (size_t)rows * sizeof(int32));
-    Grow(&fc_, &fc_cap_, (size_t)rows * sizeof(int32));
-    Grow(&hlen_, &hlen_cap_, (size_t)num_stream * sizeof(int32));
-    Grow(&score_, &score_cap_, (size_t)num_stream * sizeof(BaseFloat));
-    Grow(&err_, &err_cap_, (size_t)num_stream * sizeof(int32));
-    if (scoring) {
-      std::vector<int32> off(1, 0), flat;
-      for (const auto &l : refs) { flat.insert(flat.end(), l.begin(), l.end()); off.push_back((int32)flat.size()); }
-      if (flat.empty()) flat.push_back(0);
-      Grow(&lab_, &lab_cap_, flat.size() * sizeof(int32));
-      Grow(&off_, &off_cap_, off.size() * sizeof(int32));
-      KCheck(klstm_memcpy_h2d(lab_, flat.data(), flat.size() * sizeof(int32), nullptr));
-      KCheck(klstm_memcpy_h2d(off_, off.data(), off.size() * sizeof(int32), nullptr));
-      if (!tot_) { void *p; KCheck(klstm_malloc(&p, 5 * sizeof(double))); tot_ = (double *)p; KCheck(klstm_memset_zero(tot_, 5 * sizeof(double), nullptr)); }
-    }
+    void *ws = Workspace(need);
+    hyp_.Grow((size_t)rows * sizeof(int32));
+    fc_.Grow((size_t)rows * sizeof(int32));
+    hlen_.Grow((size_t)num_stream * sizeof(int32));
+    score_.Grow((size_t)num_stream * sizeof(BaseFloat));
+    err_.Grow((size_t)num_stream * sizeof(int32));
+    if (scoring) refs_.Upload(refs);
     MatrixView y = net_out.View();
-    KCheck(klstm_ctc_decode(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, num_weights_ ? (const BaseFloat *)w_ : nullptr,
-                            (int32 *)hyp_, (int32 *)hlen_, (BaseFloat *)score_, (int32 *)fc_, scoring ? (const int32 *)lab_ : nullptr,
-                            scoring ? (const int32 *)off_ : nullptr, scoring ? (int32 *)err_ : nullptr, scoring ? tot_ : nullptr, ws_, need,
-                            nullptr));
+    KCheck(klstm_ctc_decode(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, Weights(), hyp_.As<int32>(), hlen_.As<int32>(),
+                            score_.As<BaseFloat>(), fc_.As<int32>(), scoring ? refs_.Labels() : nullptr, scoring ? refs_.Offsets() : nullptr,
+                            scoring ? err_.As<int32>() : nullptr, scoring ? tot_.Dev() : nullptr, ws, need, nullptr));
     num_stream_ = num_stream; rows_ = rows; scored_ = scoring;
     if (!hyps) return;
     std::vector<int32> n(num_stream), h((size_t)rows);
-    KCheck(klstm_memcpy_d2h(n.data(), hlen_, n.size() * sizeof(int32), nullptr));
-    KCheck(klstm_memcpy_d2h(h.data(), hyp_, h.size() * sizeof(int32), nullptr));
+    hlen_.Download(n.data(), n.size());
+    hyp_.Download(h.data(), h.size());
     hyps->assign(num_stream, std::vector<int32>());
     for (int32 s = 0; s < num_stream; s++) (*hyps)[s].assign(h.begin() + (size_t)s * T, h.begin() + (size_t)s * T + n[s]);
   }
   // of the last Decode (each synchronises): path scores, edit distances (-1: not counted; all -1 without references), frame classes
-  void UttScores(std::vector<BaseFloat> *v) const { v->assign(num_stream_, 0.f); Get(v->data(), score_, v->size() * sizeof(BaseFloat)); }
-  void UttErrors(std::vector<int32> *v) const { v->assign(num_stream_, -1); if (scored_) Get(v->data(), err_, v->size() * sizeof(int32)); }
-  void FrameClasses(std::vector<int32> *v) const { v->assign(rows_, -1); Get(v->data(), fc_, v->size() * sizeof(int32)); }
+  void UttScores(std::vector<BaseFloat> *v) const { v->assign(num_stream_, 0.f); score_.Download(v->data(), v->size()); }
+  void UttErrors(std::vector<int32> *v) const { v->assign(num_stream_, -1); if (scored_) err_.Download(v->data(), v->size()); }
+  void FrameClasses(std::vector<int32> *v) const { v->assign(rows_, -1); fc_.Download(v->data(), v->size()); }
 
-  double TokenErrorRate() const { Fetch(); return h_[0] / h_[1]; }          // edit errors / reference tokens
-  double UtteranceErrorRate() const { Fetch(); return h_[4] / h_[3]; }
-  double NumUtterances() const { Fetch(); return h_[3]; }
-  double NumErrors() const { Fetch(); return h_[0]; }
-  double NumRefTokens() const { Fetch(); return h_[1]; }
-  double NumHypTokens() const { Fetch(); return h_[2]; }
+  double TokenErrorRate() const { const double *h = tot_.Read(); return h[0] / h[1]; }          // edit errors / reference tokens
+  double UtteranceErrorRate() const { const double *h = tot_.Read(); return h[4] / h[3]; }
+  double NumUtterances() const { return tot_.Read()[3]; }
+  double NumErrors() const { return tot_.Read()[0]; }
+  double NumRefTokens() const { return tot_.Read()[1]; }
+  double NumHypTokens() const { return tot_.Read()[2]; }
   std::string Report() const {
-    Fetch();
+    const double *h = tot_.Read();
     std::ostringstream oss;
-    oss << "UTT_ERROR_RATE: " << 100.0 * h_[4] / h_[3] << "% [" << h_[3] << " utterances, " << h_[0] << " errors, " << h_[1]
-        << " reference tokens, " << h_[2] << " hypothesis tokens]" << std::endl;
-    oss << "\nTOKEN_ERROR_RATE >> " << 100.0 * h_[0] / h_[1] << "% <<";
+    oss << "UTT_ERROR_RATE: " << 100.0 * h[4] / h[3] << "% [" << h[3] << " utterances, " << h[0] << " errors, " << h[1]
+        << " reference tokens, " << h[2] << " hypothesis tokens]" << std::endl;
+    oss << "\nTOKEN_ERROR_RATE >> " << 100.0 * h[0] / h[1] << "% <<";
     return oss.str();
   }
  private:
-  static void Grow(void **p, size_t *cap, size_t need) {
-    if (need <= *cap) return;
-    klstm_free(*p); *p = nullptr; *cap = 0;
-    KCheck(klstm_malloc(p, need));
-    *cap = need;
-  }
-  static void Get(void *dst, const void *src, size_t bytes) { if (bytes) KCheck(klstm_memcpy_d2h(dst, src, bytes, nullptr)); }
-  void Fetch() const {
-    for (double &v : h_) v = 0;
-    if (tot_) KCheck(klstm_memcpy_d2h(h_, tot_, 5 * sizeof(double), nullptr));
-  }
-  int32 blank_, num_stream_ = 0, rows_ = 0, num_weights_ = 0;
   bool scored_ = false;
-  void *ws_ = nullptr, *lens_ = nullptr, *lab_ = nullptr, *off_ = nullptr, *hyp_ = nullptr, *hlen_ = nullptr, *score_ = nullptr, *fc_ = nullptr,
-       *err_ = nullptr, *w_ = nullptr;
-  size_t ws_cap_ = 0, lens_cap_ = 0, lab_cap_ = 0, off_cap_ = 0, hyp_cap_ = 0, hlen_cap_ = 0, score_cap_ = 0, fc_cap_ = 0, err_cap_ = 0, w_cap_ = 0;
-  double *tot_ = nullptr;
-  mutable double h_[5] = {0, 0, 0, 0, 0};
+  PackedLabels refs_;
+  DeviceBuffer hyp_, hlen_, score_, fc_, err_;
+  DeviceTotals<5> tot_;
 };
 
 // CTC prefix beam search of whole utterances: the most probable labellings as n-best lists with scores, the token error rate of the
@@ -750,51 +763,27 @@ class CtcLabelLm {
     const size_t n = (size_t)num_states * num_classes;
     KLSTM_ASSERT(num_states >= 1 && num_classes >= 2 && next.size() == n && weight.size() == n);
     KLSTM_ASSERT(final_weight.empty() || final_weight.size() == (size_t)num_states);
-    try {
-      KCheck(klstm_malloc(&next_, n * sizeof(int32)));
-      KCheck(klstm_malloc(&weight_, n * sizeof(BaseFloat)));
-      KCheck(klstm_memcpy_h2d(next_, next.data(), n * sizeof(int32), nullptr));
-      KCheck(klstm_memcpy_h2d(weight_, weight.data(), n * sizeof(BaseFloat), nullptr));
-      if (!final_weight.empty()) {
-        KCheck(klstm_malloc(&final_, final_weight.size() * sizeof(BaseFloat)));
-        KCheck(klstm_memcpy_h2d(final_, final_weight.data(), final_weight.size() * sizeof(BaseFloat), nullptr));
-      }
-    } catch (...) {                                          // no destructor runs for a half-built object
-      Free();
-      throw;
-    }
+    next_.Upload(next);
+    weight_.Upload(weight);
+    final_.Upload(final_weight);
   }
-  ~CtcLabelLm() { Free(); }
-  CtcLabelLm(const CtcLabelLm &) = delete;
-  CtcLabelLm &operator=(const CtcLabelLm &) = delete;
   int32 NumStates() const { return states_; }
   int32 NumClasses() const { return classes_; }
-  const int32 *Next() const { return (const int32 *)next_; }
-  const BaseFloat *Weight() const { return (const BaseFloat *)weight_; }
-  const BaseFloat *Final() const { return (const BaseFloat *)final_; }       // null: no final weights
+  const int32 *Next() const { return next_.As<int32>(); }
+  const BaseFloat *Weight() const { return weight_.As<BaseFloat>(); }
+  const BaseFloat *Final() const { return final_.As<BaseFloat>(); }          // null: no final weights
  private:
-  void Free() { klstm_free(next_); klstm_free(weight_); klstm_free(final_); next_ = weight_ = final_ = nullptr; }
   int32 states_, classes_;
-  void *next_ = nullptr, *weight_ = nullptr, *final_ = nullptr;
+  DeviceBuffer next_, weight_, final_;
 };
 
-class CtcBeamDecoder {
+class CtcBeamDecoder : private CtcCallBase {
  public:
-  explicit CtcBeamDecoder(int32 blank = 0, int32 beam = 16, int32 cands = 8, int32 nbest = 1) : blank_(blank), beam_(beam), cands_(cands), nbest_(nbest) {}
-  ~CtcBeamDecoder() {
-    klstm_free(ws_); klstm_free(lens_); klstm_free(lab_); klstm_free(off_); klstm_free(hyp_); klstm_free(hlen_); klstm_free(cnt_);
-    klstm_free(score_); klstm_free(err_); klstm_free(w_); klstm_free(tot_);
-  }
-  CtcBeamDecoder(const CtcBeamDecoder &) = delete;
-  CtcBeamDecoder &operator=(const CtcBeamDecoder &) = delete;
+  explicit CtcBeamDecoder(int32 blank = 0, int32 beam = 16, int32 cands = 8, int32 nbest = 1)
+      : CtcCallBase(blank), beam_(beam), cands_(cands), nbest_(nbest) {}
 
   // One weight per class: the emission of a frame is y[k] * w[k] (label priors: w[k] = prior[k]^-alpha).  Empty: none.
-  void SetClassWeights(const std::vector<BaseFloat> &w) {
-    num_weights_ = (int32)w.size();
-    if (w.empty()) return;
-    Grow(&w_, &w_cap_, w.size() * sizeof(BaseFloat));
-    KCheck(klstm_memcpy_h2d(w_, w.data(), w.size() * sizeof(BaseFloat), nullptr));
-  }
+  using CtcCallBase::SetClassWeights;
   // Fuses a language model into the search: every later Decode goes through klstm_ctc_beam_decode_lm and its scores are the fused
   // ones.  The decoder keeps the pointer, not the tables; null: the search without one, as before.
   void SetLanguageModel(const CtcLabelLm *lm) { lm_ = lm; }
@@ -802,60 +791,43 @@ class CtcBeamDecoder {
   // one).  Asking for lists synchronises; the rest stays on the device.
   void Decode(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &refs,
               std::vector<CtcNbestList> *lists) {
-    KLSTM_ASSERT((int32)lens.size() == num_stream);
-    Grow(&lens_, &lens_cap_, (size_t)num_stream * sizeof(int32));
-    KCheck(klstm_memcpy_h2d(lens_, lens.data(), (size_t)num_stream * sizeof(int32), nullptr));
-    Decode(net_out, num_stream, (const int32 *)lens_, refs, lists);
+    Decode(net_out, num_stream, UploadLens(num_stream, lens), refs, lists);
   }
   void Decode(const DeviceMatrix &net_out, int32 num_stream, const int32 *lens_dev, const std::vector<std::vector<int32> > &refs,
               std::vector<CtcNbestList> *lists) {
-    const int32 rows = net_out.NumRows(), K = net_out.NumCols();
-    KLSTM_ASSERT(num_stream > 0 && rows > 0 && rows % num_stream == 0 && lens_dev && (refs.empty() || (int32)refs.size() == num_stream));
-    KLSTM_ASSERT(num_weights_ == 0 || num_weights_ == K);
+    const int32 T = NumFrames(net_out, num_stream, lens_dev, refs.size(), true), rows = net_out.NumRows(), K = net_out.NumCols(), N = nbest_;
     KLSTM_ASSERT(nbest_ >= 1);
-    const int32 T = rows / num_stream, N = nbest_;
     const bool scoring = !refs.empty();
     const size_t need = klstm_ctc_beam_workspace_bytes(T, num_stream, beam_, cands_);
-    if (need == 0) KLSTM_ERR("klstm: " << klstm_last_error());
-    Grow(&ws_, &ws_cap_, need);
-    Grow(&hyp_, &hyp_cap_, (size_t)rows * N * sizeof(int32));
-    Grow(&hlen_, &hlen_cap_, (size_t)num_stream * N * sizeof(int32));
-    Grow(&cnt_, &cnt_cap_, (size_t)num_stream * sizeof(int32));
-    Grow(&score_, &score_cap_, (size_t)num_stream * N * sizeof(BaseFloat));
-    Grow(&err_, &err_cap_, (size_t)num_stream * N * sizeof(int32));
-    if (scoring) {
-      std::vector<int32> off(1, 0), flat;
-      for (const auto &l : refs) { flat.insert(flat.end(), l.begin(), l.end()); off.push_back((int32)flat.size()); }
-      if (flat.empty()) flat.push_back(0);
-      Grow(&lab_, &lab_cap_, flat.size() * sizeof(int32));
-      Grow(&off_, &off_cap_, off.size() * sizeof(int32));
-      KCheck(klstm_memcpy_h2d(lab_, flat.data(), flat.size() * sizeof(int32), nullptr));
-      KCheck(klstm_memcpy_h2d(off_, off.data(), off.size() * sizeof(int32), nullptr));
-      if (!tot_) { void *p; KCheck(klstm_malloc(&p, 6 * sizeof(double))); tot_ = (double *)p; KCheck(klstm_memset_zero(tot_, 6 * sizeof(double), nullptr)); }
-    }
+    void *ws = Workspace(need);
+    hyp_.Grow((size_t)rows * N * sizeof(int32));
+    hlen_.Grow((size_t)num_stream * N * sizeof(int32));
+    cnt_.Grow((size_t)num_stream * sizeof(int32));
+    score_.Grow((size_t)num_stream * N * sizeof(BaseFloat));
+    err_.Grow((size_t)num_stream * N * sizeof(int32));
+    if (scoring) refs_.Upload(refs);
+    const int32 *rl = scoring ? refs_.Labels() : nullptr, *ro = scoring ? refs_.Offsets() : nullptr;
+    int32 *er = scoring ? err_.As<int32>() : nullptr;
+    double *tot = scoring ? tot_.Dev() : nullptr;
     MatrixView y = net_out.View();
     if (!lm_) {
-      KCheck(klstm_ctc_beam_decode(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, num_weights_ ? (const BaseFloat *)w_ : nullptr,
-                                   beam_, cands_, N, (int32 *)hyp_, (int32 *)hlen_, (int32 *)cnt_, (BaseFloat *)score_,
-                                   scoring ? (const int32 *)lab_ : nullptr, scoring ? (const int32 *)off_ : nullptr,
-                                   scoring ? (int32 *)err_ : nullptr, scoring ? tot_ : nullptr, ws_, need, nullptr));
+      KCheck(klstm_ctc_beam_decode(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, Weights(), beam_, cands_, N, hyp_.As<int32>(),
+                                   hlen_.As<int32>(), cnt_.As<int32>(), score_.As<BaseFloat>(), rl, ro, er, tot, ws, need, nullptr));
     } else {
       KLSTM_ASSERT(lm_->NumClasses() == K);
-      KCheck(klstm_ctc_beam_decode_lm(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, num_weights_ ? (const BaseFloat *)w_ : nullptr,
-                                      beam_, cands_, N, lm_->NumStates(), lm_->Next(), lm_->Weight(), lm_->Final(), (int32 *)hyp_,
-                                      (int32 *)hlen_, (int32 *)cnt_, (BaseFloat *)score_, scoring ? (const int32 *)lab_ : nullptr,
-                                      scoring ? (const int32 *)off_ : nullptr, scoring ? (int32 *)err_ : nullptr, scoring ? tot_ : nullptr,
-                                      ws_, need, nullptr));
+      KCheck(klstm_ctc_beam_decode_lm(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, Weights(), beam_, cands_, N, lm_->NumStates(),
+                                      lm_->Next(), lm_->Weight(), lm_->Final(), hyp_.As<int32>(), hlen_.As<int32>(), cnt_.As<int32>(),
+                                      score_.As<BaseFloat>(), rl, ro, er, tot, ws, need, nullptr));
     }
     num_stream_ = num_stream; scored_ = scoring;
     if (!lists) return;
     std::vector<int32> c(num_stream), n((size_t)num_stream * N), h((size_t)rows * N), e((size_t)num_stream * N, -1);
     std::vector<BaseFloat> sc((size_t)num_stream * N);
-    Get(c.data(), cnt_, c.size() * sizeof(int32));
-    Get(n.data(), hlen_, n.size() * sizeof(int32));
-    Get(h.data(), hyp_, h.size() * sizeof(int32));
-    Get(sc.data(), score_, sc.size() * sizeof(BaseFloat));
-    if (scoring) Get(e.data(), err_, e.size() * sizeof(int32));
+    cnt_.Download(c.data(), c.size());
+    hlen_.Download(n.data(), n.size());
+    hyp_.Download(h.data(), h.size());
+    score_.Download(sc.data(), sc.size());
+    if (scoring) err_.Download(e.data(), e.size());
     lists->assign(num_stream, CtcNbestList());
     for (int32 s = 0; s < num_stream; s++)
       for (int32 q = 0; q < c[s]; q++) {
@@ -869,12 +841,12 @@ class CtcBeamDecoder {
   }
   // of the last Decode (each synchronises), per stream: entries of the list, the 1-best's score (0 for an empty list) and its edit
   // distance (-1: not counted; all -1 without references)
-  void NbestCounts(std::vector<int32> *v) const { v->assign(num_stream_, 0); Get(v->data(), cnt_, v->size() * sizeof(int32)); }
+  void NbestCounts(std::vector<int32> *v) const { v->assign(num_stream_, 0); cnt_.Download(v->data(), v->size()); }
   void UttScores(std::vector<BaseFloat> *v) const {
     std::vector<int32> c;
     NbestCounts(&c);
     std::vector<BaseFloat> sc((size_t)num_stream_ * nbest_);
-    Get(sc.data(), score_, sc.size() * sizeof(BaseFloat));
+    score_.Download(sc.data(), sc.size());
     v->assign(num_stream_, 0.f);
     for (int32 s = 0; s < num_stream_; s++) if (c[s] > 0) (*v)[s] = sc[(size_t)s * nbest_];
   }
@@ -882,47 +854,34 @@ class CtcBeamDecoder {
     v->assign(num_stream_, -1);
     if (!scored_) return;
     std::vector<int32> e((size_t)num_stream_ * nbest_);
-    Get(e.data(), err_, e.size() * sizeof(int32));
+    err_.Download(e.data(), e.size());
     for (int32 s = 0; s < num_stream_; s++) (*v)[s] = e[(size_t)s * nbest_];
   }
 
-  double TokenErrorRate() const { Fetch(); return h_[0] / h_[1]; }          // 1-best edit errors / reference tokens
-  double OracleTokenErrorRate() const { Fetch(); return h_[5] / h_[1]; }    // the best of each list
-  double UtteranceErrorRate() const { Fetch(); return h_[4] / h_[3]; }
-  double NumUtterances() const { Fetch(); return h_[3]; }
-  double NumErrors() const { Fetch(); return h_[0]; }
-  double NumOracleErrors() const { Fetch(); return h_[5]; }
-  double NumRefTokens() const { Fetch(); return h_[1]; }
-  double NumHypTokens() const { Fetch(); return h_[2]; }
+  double TokenErrorRate() const { const double *h = tot_.Read(); return h[0] / h[1]; }          // 1-best edit errors / reference tokens
+  double OracleTokenErrorRate() const { const double *h = tot_.Read(); return h[5] / h[1]; }    // the best of each list
+  double UtteranceErrorRate() const { const double *h = tot_.Read(); return h[4] / h[3]; }
+  double NumUtterances() const { return tot_.Read()[3]; }
+  double NumErrors() const { return tot_.Read()[0]; }
+  double NumOracleErrors() const { return tot_.Read()[5]; }
+  double NumRefTokens() const { return tot_.Read()[1]; }
+  double NumHypTokens() const { return tot_.Read()[2]; }
   std::string Report() const {
-    Fetch();
+    const double *h = tot_.Read();
     std::ostringstream oss;
-    oss << "UTT_ERROR_RATE: " << 100.0 * h_[4] / h_[3] << "% [" << h_[3] << " utterances, " << h_[0] << " errors, " << h_[1]
-        << " reference tokens, " << h_[2] << " hypothesis tokens]" << std::endl;
-    oss << "ORACLE_TOKEN_ERROR_RATE: " << 100.0 * h_[5] / h_[1] << "% [" << nbest_ << "-best, beam " << beam_ << ", " << cands_ << " candidates]" << std::endl;
-    oss << "\nTOKEN_ERROR_RATE >> " << 100.0 * h_[0] / h_[1] << "% <<";
+    oss << "UTT_ERROR_RATE: " << 100.0 * h[4] / h[3] << "% [" << h[3] << " utterances, " << h[0] << " errors, " << h[1]
+        << " reference tokens, " << h[2] << " hypothesis tokens]" << std::endl;
+    oss << "ORACLE_TOKEN_ERROR_RATE: " << 100.0 * h[5] / h[1] << "% [" << nbest_ << "-best, beam " << beam_ << ", " << cands_ << " candidates]" << std::endl;
+    oss << "\nTOKEN_ERROR_RATE >> " << 100.0 * h[0] / h[1] << "% <<";
     return oss.str();
   }
  private:
-  static void Grow(void **p, size_t *cap, size_t need) {
-    if (need <= *cap) return;
-    klstm_free(*p); *p = nullptr; *cap = 0;
-    KCheck(klstm_malloc(p, need));
-    *cap = need;
-  }
-  static void Get(void *dst, const void *src, size_t bytes) { if (bytes) KCheck(klstm_memcpy_d2h(dst, src, bytes, nullptr)); }
-  void Fetch() const {
-    for (double &v : h_) v = 0;
-    if (tot_) KCheck(klstm_memcpy_d2h(h_, tot_, 6 * sizeof(double), nullptr));
-  }
-  int32 blank_, beam_, cands_, nbest_, num_stream_ = 0, num_weights_ = 0;
+  int32 beam_, cands_, nbest_;
   bool scored_ = false;
   const CtcLabelLm *lm_ = nullptr;
-  void *ws_ = nullptr, *lens_ = nullptr, *lab_ = nullptr, *off_ = nullptr, *hyp_ = nullptr, *hlen_ = nullptr, *cnt_ = nullptr, *score_ = nullptr,
-       *err_ = nullptr, *w_ = nullptr;
-  size_t ws_cap_ = 0, lens_cap_ = 0, lab_cap_ = 0, off_cap_ = 0, hyp_cap_ = 0, hlen_cap_ = 0, cnt_cap_ = 0, score_cap_ = 0, err_cap_ = 0, w_cap_ = 0;
-  double *tot_ = nullptr;
-  mutable double h_[6] = {0, 0, 0, 0, 0, 0};
+  PackedLabels refs_;
+  DeviceBuffer hyp_, hlen_, cnt_, score_, err_;
+  DeviceTotals<6> tot_;
 };
 
 struct DecodeCtcOptions {
@@ -948,55 +907,46 @@ inline void ScatterByUtterance(const UtteranceBatch &b, const std::vector<V> &pe
     (*per_utt)[b.utt_index[s]] = per_stream[s];
   }
 }
+// what both decoders know at the end of a pass
+template <class Decoder>
+inline void FillDecodeCtcStats(const Decoder &dec, DecodeCtcStats *st, std::string *report) {
+  st->num_scored = dec.NumUtterances();
+  st->num_errors = dec.NumErrors();
+  st->num_ref_tokens = dec.NumRefTokens();
+  st->token_error_rate = dec.TokenErrorRate();
+  st->utt_error_rate = dec.UtteranceErrorRate();
+  if (report) *report = dec.Report();
+}
 
-// The same loop with the prefix beam search (o.beam > 0).  (*hypotheses)[i] is the 1-best of utts[i], (*nbest_lists)[i] its whole list
-// with scores and edit distances (either may be null; both empty for a skipped utterance).  every_batch sees (batch, net_out,
-// CtcBeamDecoder) after Decode.
+// The loop of DecodeCtcWholeUtterances below with the prefix beam search (o.beam > 0).  (*hypotheses)[i] is the 1-best of utts[i],
+// (*nbest_lists)[i] its whole list with scores and edit distances (either may be null; both empty for a skipped utterance).
+// every_batch sees (batch, net_out, CtcBeamDecoder) after Decode.
 template <class F>
 inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
                                                std::vector<std::vector<int32> > *hypotheses, std::vector<CtcNbestList> *nbest_lists,
                                                std::string *report, F every_batch) {
   KLSTM_ASSERT(o.beam > 0);
-  WholeUtteranceBatcher batcher(&utts, o.num_stream, o.sort_by_length, o.max_frames);
   CtcBeamDecoder dec(o.blank, o.beam, o.cands, o.nbest);
   dec.SetClassWeights(o.class_weights);
   dec.SetLanguageModel(o.lm);
-  UtteranceBatch b;
-  DeviceMatrix feat_dev, nnet_out;
-  DecodeCtcStats st;
-  std::vector<int> all(o.num_stream, 1);
   std::vector<CtcNbestList> lists;
   const std::vector<std::vector<int32> > none;
   const bool want = hypotheses || nbest_lists;
   if (hypotheses) hypotheses->assign(utts.size(), std::vector<int32>());
   if (nbest_lists) nbest_lists->assign(utts.size(), CtcNbestList());
-  const auto t0 = std::chrono::steady_clock::now();
-  while (batcher.Next(&b)) {
-    nnet->SetSeqLengths(b.lens);
-    nnet->Reset(all);
-    feat_dev.CopyFromHost(b.feat.data(), b.num_frames * b.num_stream, b.dim);
-    nnet->Propagate(feat_dev.View(), &nnet_out);
-    dec.Decode(nnet_out, b.num_stream, b.lens, o.score ? b.labels : none, want ? &lists : nullptr);
-    if (nbest_lists) ScatterByUtterance(b, lists, nbest_lists);
-    if (hypotheses) {
-      std::vector<std::vector<int32> > best(b.num_stream);
-      for (int32 s = 0; s < b.num_stream; s++) if (!lists[s].empty()) best[s] = lists[s][0].tokens;
-      ScatterByUtterance(b, best, hypotheses);
-    }
-    every_batch(b, nnet_out, dec);
-    st.num_minibatches++;
-  }
-  KCheck(klstm_stream_synchronize(nullptr));
-  st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  st.num_done = batcher.NumDone();
-  st.num_skipped = batcher.NumSkipped();
-  st.num_scored = dec.NumUtterances();
-  st.num_errors = dec.NumErrors();
-  st.num_ref_tokens = dec.NumRefTokens();
-  st.token_error_rate = dec.TokenErrorRate();
-  st.utt_error_rate = dec.UtteranceErrorRate();
+  DecodeCtcStats st = ForEachWholeUtteranceBatch<DecodeCtcStats>(nnet, utts, o.num_stream, o.sort_by_length, o.max_frames,
+      [&](const UtteranceBatch &b, const DeviceMatrix &nnet_out) {
+        dec.Decode(nnet_out, b.num_stream, b.lens, o.score ? b.labels : none, want ? &lists : nullptr);
+        if (nbest_lists) ScatterByUtterance(b, lists, nbest_lists);
+        if (hypotheses) {
+          std::vector<std::vector<int32> > best(b.num_stream);
+          for (int32 s = 0; s < b.num_stream; s++) if (!lists[s].empty()) best[s] = lists[s][0].tokens;
+          ScatterByUtterance(b, best, hypotheses);
+        }
+        every_batch(b, nnet_out, dec);
+      });
   st.oracle_token_error_rate = dec.OracleTokenErrorRate();
-  if (report) *report = dec.Report();
+  FillDecodeCtcStats(dec, &st, report);
   return st;
 }
 inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
@@ -1014,37 +964,18 @@ template <class F>
 inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
                                                std::vector<std::vector<int32> > *hypotheses, std::string *report, F every_batch) {
   if (o.beam > 0) return DecodeCtcWholeUtterances(nnet, utts, o, hypotheses, (std::vector<CtcNbestList> *)nullptr, report);
-  WholeUtteranceBatcher batcher(&utts, o.num_stream, o.sort_by_length, o.max_frames);
   CtcGreedyDecoder dec(o.blank);
   dec.SetClassWeights(o.class_weights);
-  UtteranceBatch b;
-  DeviceMatrix feat_dev, nnet_out;
-  DecodeCtcStats st;
-  std::vector<int> all(o.num_stream, 1);
   std::vector<std::vector<int32> > hyps;
   const std::vector<std::vector<int32> > none;
   if (hypotheses) hypotheses->assign(utts.size(), std::vector<int32>());
-  const auto t0 = std::chrono::steady_clock::now();
-  while (batcher.Next(&b)) {
-    nnet->SetSeqLengths(b.lens);
-    nnet->Reset(all);
-    feat_dev.CopyFromHost(b.feat.data(), b.num_frames * b.num_stream, b.dim);
-    nnet->Propagate(feat_dev.View(), &nnet_out);
-    dec.Decode(nnet_out, b.num_stream, b.lens, o.score ? b.labels : none, hypotheses ? &hyps : nullptr);
-    if (hypotheses) ScatterByUtterance(b, hyps, hypotheses);
-    every_batch(b, nnet_out, dec);
-    st.num_minibatches++;
-  }
-  KCheck(klstm_stream_synchronize(nullptr));
-  st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  st.num_done = batcher.NumDone();
-  st.num_skipped = batcher.NumSkipped();
-  st.num_scored = dec.NumUtterances();
-  st.num_errors = dec.NumErrors();
-  st.num_ref_tokens = dec.NumRefTokens();
-  st.token_error_rate = dec.TokenErrorRate();
-  st.utt_error_rate = dec.UtteranceErrorRate();
-  if (report) *report = dec.Report();
+  DecodeCtcStats st = ForEachWholeUtteranceBatch<DecodeCtcStats>(nnet, utts, o.num_stream, o.sort_by_length, o.max_frames,
+      [&](const UtteranceBatch &b, const DeviceMatrix &nnet_out) {
+        dec.Decode(nnet_out, b.num_stream, b.lens, o.score ? b.labels : none, hypotheses ? &hyps : nullptr);
+        if (hypotheses) ScatterByUtterance(b, hyps, hypotheses);
+        every_batch(b, nnet_out, dec);
+      });
+  FillDecodeCtcStats(dec, &st, report);
   return st;
 }
 inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
@@ -1054,111 +985,69 @@ inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utt
 
 // CTC forced alignment of whole utterances: the most probable alignment of each stream's labels to its frames (klstm_ctc_align,
 // klstm.h).  The five totals stay on the device and are read when somebody asks, like Ctc's.
-class CtcAligner {
+class CtcAligner : private CtcCallBase {
  public:
-  explicit CtcAligner(int32 blank = 0) : blank_(blank) {}
-  ~CtcAligner() {
-    klstm_free(ws_); klstm_free(lens_); klstm_free(lab_); klstm_free(off_); klstm_free(fc_); klstm_free(fp_); klstm_free(tb_); klstm_free(te_);
-    klstm_free(score_); klstm_free(w_); klstm_free(tot_);
-  }
-  CtcAligner(const CtcAligner &) = delete;
-  CtcAligner &operator=(const CtcAligner &) = delete;
+  explicit CtcAligner(int32 blank = 0) : CtcCallBase(blank) {}
 
   // One weight per class: the emission of a frame becomes log(y[k] * w[k]) (label priors: w[k] = prior[k]^-alpha).  Empty: none.
-  void SetClassWeights(const std::vector<BaseFloat> &w) {
-    num_weights_ = (int32)w.size();
-    if (w.empty()) return;
-    Grow(&w_, &w_cap_, w.size() * sizeof(BaseFloat));
-    KCheck(klstm_memcpy_h2d(w_, w.data(), w.size() * sizeof(BaseFloat), nullptr));
-  }
+  using CtcCallBase::SetClassWeights;
   // net_out [T*num_stream x K] posteriors (row t*S + s); lens: frames per stream (0 = idle); labels: per stream.  Utterances that
   // cannot be aligned (klstm.h) are rejected on the device.  Nothing synchronises.
   void Align(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &labels) {
-    KLSTM_ASSERT((int32)lens.size() == num_stream);
-    Grow(&lens_, &lens_cap_, (size_t)num_stream * sizeof(int32));
-    KCheck(klstm_memcpy_h2d(lens_, lens.data(), (size_t)num_stream * sizeof(int32), nullptr));
-    Align(net_out, num_stream, (const int32 *)lens_, labels);
+    Align(net_out, num_stream, UploadLens(num_stream, lens), labels);
   }
   void Align(const DeviceMatrix &net_out, int32 num_stream, const int32 *lens_dev, const std::vector<std::vector<int32> > &labels) {
-    const int32 rows = net_out.NumRows(), K = net_out.NumCols();
-    KLSTM_ASSERT(num_stream > 0 && rows > 0 && rows % num_stream == 0 && (int32)labels.size() == num_stream && lens_dev);
-    KLSTM_ASSERT(num_weights_ == 0 || num_weights_ == K);
-    const int32 T = rows / num_stream;
-    std::vector<int32> flat;
-    off_h_.assign(1, 0);
-    size_t longest = 0;
-    for (const auto &l : labels) { flat.insert(flat.end(), l.begin(), l.end()); off_h_.push_back((int32)flat.size()); longest = std::max(longest, l.size()); }
-    num_labels_ = flat.size();
-    if (flat.empty()) flat.push_back(0);
-    const size_t need = klstm_ctc_align_workspace_bytes(T, num_stream, (int)std::min(longest, (size_t)1023));   // longer: the device's to reject
-    if (need == 0) KLSTM_ERR("klstm: " << klstm_last_error());
-    Grow(&ws_, &ws_cap_, need);
-    Grow(&lab_, &lab_cap_, flat.size() * sizeof(int32));
-    Grow(&off_, &off_cap_, off_h_.size() * sizeof(int32));
-    Grow(&fc_, &fc_cap_, (size_t)rows * sizeof(int32));
-    Grow(&fp_, &fp_cap_, (size_t)rows * sizeof(int32));
-    Grow(&tb_, &tb_cap_, flat.size() * sizeof(int32));
-    Grow(&te_, &te_cap_, flat.size() * sizeof(int32));
-    Grow(&score_, &score_cap_, (size_t)num_stream * sizeof(BaseFloat));
-    if (!tot_) { void *p; KCheck(klstm_malloc(&p, 5 * sizeof(double))); tot_ = (double *)p; KCheck(klstm_memset_zero(tot_, 5 * sizeof(double), nullptr)); }
-    KCheck(klstm_memcpy_h2d(lab_, flat.data(), flat.size() * sizeof(int32), nullptr));
-    KCheck(klstm_memcpy_h2d(off_, off_h_.data(), off_h_.size() * sizeof(int32), nullptr));
+    const int32 T = NumFrames(net_out, num_stream, lens_dev, labels.size(), false), rows = net_out.NumRows(), K = net_out.NumCols();
+    lab_.Upload(labels);
+    const size_t need = klstm_ctc_align_workspace_bytes(T, num_stream, (int)std::min(lab_.longest, (size_t)1023));   // longer: the device's to reject
+    void *ws = Workspace(need);
+    const size_t tokens = std::max(lab_.num_labels, (size_t)1);         // (as many as the label array has)
+    fc_.Grow((size_t)rows * sizeof(int32));
+    fp_.Grow((size_t)rows * sizeof(int32));
+    tb_.Grow(tokens * sizeof(int32));
+    te_.Grow(tokens * sizeof(int32));
+    score_.Grow((size_t)num_stream * sizeof(BaseFloat));
     MatrixView y = net_out.View();
-    KCheck(klstm_ctc_align(y.Data(), T, num_stream, K, y.Stride(), lens_dev, (const int32 *)lab_, (const int32 *)off_, blank_,
-                           num_weights_ ? (const BaseFloat *)w_ : nullptr, (int32 *)fc_, (int32 *)fp_, (int32 *)tb_, (int32 *)te_,
-                           (BaseFloat *)score_, tot_, ws_, need, nullptr));
+    KCheck(klstm_ctc_align(y.Data(), T, num_stream, K, y.Stride(), lens_dev, lab_.Labels(), lab_.Offsets(), blank_, Weights(),
+                           fc_.As<int32>(), fp_.As<int32>(), tb_.As<int32>(), te_.As<int32>(), score_.As<BaseFloat>(), tot_.Dev(), ws, need,
+                           nullptr));
     num_stream_ = num_stream; rows_ = rows;
   }
   // of the last Align (each synchronises).  Frame classes and positions [T*num_stream], row t*S + s; -1 where there is no path
-  void FrameClasses(std::vector<int32> *v) const { v->assign(rows_, -1); Get(v->data(), fc_, v->size() * sizeof(int32)); }
-  void FramePositions(std::vector<int32> *v) const { v->assign(rows_, -1); Get(v->data(), fp_, v->size() * sizeof(int32)); }
+  void FrameClasses(std::vector<int32> *v) const { v->assign(rows_, -1); fc_.Download(v->data(), v->size()); }
+  void FramePositions(std::vector<int32> *v) const { v->assign(rows_, -1); fp_.Download(v->data(), v->size()); }
   // per stream: first frame of every token and one past its last (empty for a stream without labels; -1 where not aligned)
   void TokenBounds(std::vector<std::vector<int32> > *begin, std::vector<std::vector<int32> > *end) const {
-    std::vector<int32> b(num_labels_), e(num_labels_);
-    Get(b.data(), tb_, b.size() * sizeof(int32));
-    Get(e.data(), te_, e.size() * sizeof(int32));
+    const std::vector<int32> &off = lab_.offsets;
+    std::vector<int32> b(lab_.num_labels), e(lab_.num_labels);
+    tb_.Download(b.data(), b.size());
+    te_.Download(e.data(), e.size());
     begin->assign(num_stream_, std::vector<int32>());
     end->assign(num_stream_, std::vector<int32>());
     for (int32 s = 0; s < num_stream_; s++) {
-      (*begin)[s].assign(b.begin() + off_h_[s], b.begin() + off_h_[s + 1]);
-      (*end)[s].assign(e.begin() + off_h_[s], e.begin() + off_h_[s + 1]);
+      (*begin)[s].assign(b.begin() + off[s], b.begin() + off[s + 1]);
+      (*end)[s].assign(e.begin() + off[s], e.begin() + off[s + 1]);
     }
   }
   // log probability of the path (0: idle, -inf: rejected)
-  void UttScores(std::vector<BaseFloat> *v) const { v->assign(num_stream_, 0.f); Get(v->data(), score_, v->size() * sizeof(BaseFloat)); }
+  void UttScores(std::vector<BaseFloat> *v) const { v->assign(num_stream_, 0.f); score_.Download(v->data(), v->size()); }
 
-  double AvgScorePerFrame() const { Fetch(); return h_[0] / h_[3]; }
-  double BlankRatio() const { Fetch(); return h_[4] / h_[3]; }
-  double NumAligned() const { Fetch(); return h_[1]; }
-  double NumRejected() const { Fetch(); return h_[2]; }
-  double Frames() const { Fetch(); return h_[3]; }
+  double AvgScorePerFrame() const { const double *h = tot_.Read(); return h[0] / h[3]; }
+  double BlankRatio() const { const double *h = tot_.Read(); return h[4] / h[3]; }
+  double NumAligned() const { return tot_.Read()[1]; }
+  double NumRejected() const { return tot_.Read()[2]; }
+  double Frames() const { return tot_.Read()[3]; }
   std::string Report() const {
-    Fetch();
+    const double *h = tot_.Read();
     std::ostringstream oss;
-    oss << "AvgPathScore: " << h_[0] / h_[3] << " (CtcAligner) per frame, blank ratio " << h_[4] / h_[3] << " [" << h_[1] << " utterances, " << h_[3]
-        << " frames, " << h_[2] << " rejected]" << std::endl;
+    oss << "AvgPathScore: " << h[0] / h[3] << " (CtcAligner) per frame, blank ratio " << h[4] / h[3] << " [" << h[1] << " utterances, " << h[3]
+        << " frames, " << h[2] << " rejected]" << std::endl;
     return oss.str();
   }
  private:
-  static void Grow(void **p, size_t *cap, size_t need) {
-    if (need <= *cap) return;
-    klstm_free(*p); *p = nullptr; *cap = 0;
-    KCheck(klstm_malloc(p, need));
-    *cap = need;
-  }
-  static void Get(void *dst, const void *src, size_t bytes) { if (bytes) KCheck(klstm_memcpy_d2h(dst, src, bytes, nullptr)); }
-  void Fetch() const {
-    for (double &v : h_) v = 0;
-    if (tot_) KCheck(klstm_memcpy_d2h(h_, tot_, 5 * sizeof(double), nullptr));
-  }
-  int32 blank_, num_stream_ = 0, rows_ = 0, num_weights_ = 0;
-  size_t num_labels_ = 0;
-  std::vector<int32> off_h_;
-  void *ws_ = nullptr, *lens_ = nullptr, *lab_ = nullptr, *off_ = nullptr, *fc_ = nullptr, *fp_ = nullptr, *tb_ = nullptr, *te_ = nullptr,
-       *score_ = nullptr, *w_ = nullptr;
-  size_t ws_cap_ = 0, lens_cap_ = 0, lab_cap_ = 0, off_cap_ = 0, fc_cap_ = 0, fp_cap_ = 0, tb_cap_ = 0, te_cap_ = 0, score_cap_ = 0, w_cap_ = 0;
-  double *tot_ = nullptr;
-  mutable double h_[5] = {0, 0, 0, 0, 0};
+  PackedLabels lab_;
+  DeviceBuffer fc_, fp_, tb_, te_, score_;
+  DeviceTotals<5> tot_;
 };
 
 struct AlignCtcOptions {
@@ -1183,44 +1072,30 @@ struct AlignCtcStats {
 template <class F>
 inline AlignCtcStats AlignCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const AlignCtcOptions &o,
                                              std::vector<CtcAlignment> *alignments, std::string *report, F every_batch) {
-  WholeUtteranceBatcher batcher(&utts, o.num_stream, o.sort_by_length, o.max_frames);
   CtcAligner al(o.blank);
   al.SetClassWeights(o.class_weights);
-  UtteranceBatch b;
-  DeviceMatrix feat_dev, nnet_out;
-  AlignCtcStats st;
-  std::vector<int> all(o.num_stream, 1);
   std::vector<int32> fc;
   std::vector<BaseFloat> score;
   std::vector<std::vector<int32> > tb, te;
   std::vector<CtcAlignment> per_stream;
   if (alignments) alignments->assign(utts.size(), CtcAlignment());
-  const auto t0 = std::chrono::steady_clock::now();
-  while (batcher.Next(&b)) {
-    nnet->SetSeqLengths(b.lens);
-    nnet->Reset(all);
-    feat_dev.CopyFromHost(b.feat.data(), b.num_frames * b.num_stream, b.dim);
-    nnet->Propagate(feat_dev.View(), &nnet_out);
-    al.Align(nnet_out, b.num_stream, b.lens, b.labels);
-    if (alignments) {
-      al.FrameClasses(&fc); al.UttScores(&score); al.TokenBounds(&tb, &te);
-      per_stream.assign(b.num_stream, CtcAlignment());
-      for (int32 s = 0; s < b.num_stream; s++) {
-        if (b.lens[s] <= 0 || fc[s] < 0) continue;                       // idle, or rejected: frame 0 carries -1
-        CtcAlignment &a = per_stream[s];
-        a.aligned = true; a.blank = o.blank; a.score = score[s]; a.token_begin = tb[s]; a.token_end = te[s];
-        a.frame_class.resize(b.lens[s]);
-        for (int32 t = 0; t < b.lens[s]; t++) a.frame_class[t] = fc[(size_t)t * b.num_stream + s];
-      }
-      ScatterByUtterance(b, per_stream, alignments);
-    }
-    every_batch(b, nnet_out, al);
-    st.num_minibatches++;
-  }
-  KCheck(klstm_stream_synchronize(nullptr));
-  st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  st.num_done = batcher.NumDone();
-  st.num_skipped = batcher.NumSkipped();
+  AlignCtcStats st = ForEachWholeUtteranceBatch<AlignCtcStats>(nnet, utts, o.num_stream, o.sort_by_length, o.max_frames,
+      [&](const UtteranceBatch &b, const DeviceMatrix &nnet_out) {
+        al.Align(nnet_out, b.num_stream, b.lens, b.labels);
+        if (alignments) {
+          al.FrameClasses(&fc); al.UttScores(&score); al.TokenBounds(&tb, &te);
+          per_stream.assign(b.num_stream, CtcAlignment());
+          for (int32 s = 0; s < b.num_stream; s++) {
+            if (b.lens[s] <= 0 || fc[s] < 0) continue;                       // idle, or rejected: frame 0 carries -1
+            CtcAlignment &a = per_stream[s];
+            a.aligned = true; a.blank = o.blank; a.score = score[s]; a.token_begin = tb[s]; a.token_end = te[s];
+            a.frame_class.resize(b.lens[s]);
+            for (int32 t = 0; t < b.lens[s]; t++) a.frame_class[t] = fc[(size_t)t * b.num_stream + s];
+          }
+          ScatterByUtterance(b, per_stream, alignments);
+        }
+        every_batch(b, nnet_out, al);
+      });
   st.num_aligned = al.NumAligned();
   st.num_rejected = al.NumRejected();
   st.total_frames = al.Frames();

@@ -148,8 +148,8 @@ class BatchScorer {
     std::vector<BaseFloat> w, b;
     aff.HostParams(&w, &b);
     aff_in_ = aff.InputDim(); out_dim_ = aff.OutputDim();
-    W_ = Upload(w); b_ = Upload(b);
-    if (o.mode == KLSTM_SCORE_LOGLIKE) lp_ = Upload(o.log_prior);
+    W_.Upload(w); b_.Upload(b);
+    if (o.mode == KLSTM_SCORE_LOGLIKE) lp_.Upload(o.log_prior);
     const int32 rows = o.num_stream * o.chunk;
     int32 wmax = in_dim_;
     for (int32 d : dims_) wmax = std::max(wmax, d);
@@ -188,7 +188,6 @@ class BatchScorer {
     if (lstm_end) *lstm_end = e;
     return shift;
   }
-  ~BatchScorer() { klstm_free(W_); klstm_free(b_); klstm_free(lp_); klstm_free(pdesc_); klstm_free(pdst_); }
   BatchScorer(const BatchScorer &) = delete;
   BatchScorer &operator=(const BatchScorer &) = delete;
 
@@ -205,13 +204,11 @@ class BatchScorer {
     if (!p.num_chunks) return;
     if (feat_stride < in_dim_ || out_stride < out_dim_) KLSTM_ERR("BatchScorer: stride smaller than the row");
     KCheck(klstm_stream_synchronize(nullptr));        // (the plan arrays may still be read by an earlier call's kernels)
-    Ensure(&pdesc_, &cap_desc_, p.desc.size());
-    Ensure(&pdst_, &cap_dst_, p.dst.size());
-    KCheck(klstm_memcpy_h2d(pdesc_, p.desc.data(), p.desc.size() * sizeof(int32), nullptr));
-    KCheck(klstm_memcpy_h2d(pdst_, p.dst.data(), p.dst.size() * sizeof(int32), nullptr));
+    pdesc_.Upload(p.desc);
+    pdst_.Upload(p.dst);
     std::vector<int> flags(S);
     for (int32 c = 0; c < p.num_chunks; c++) {
-      KCheck(klstm_pack_streams(feats_dev, in_dim_, feat_stride, pdesc_ + (size_t)c * 3 * S, S, T, shift_, act_[0].View().Data(),
+      KCheck(klstm_pack_streams(feats_dev, in_dim_, feat_stride, pdesc_.As<int32>() + (size_t)c * 3 * S, S, T, shift_, act_[0].View().Data(),
                                 act_[0].Stride(), nullptr, nullptr));
       for (int32 s = 0; s < S; s++) flags[s] = p.reset[(size_t)c * S + s];
       int k = 0;
@@ -221,10 +218,10 @@ class BatchScorer {
         KCheck(klstm_propagate_inference(e, act_[k].View().Data(), rows, act_[k].Stride(), act_[k ^ 1].View().Data(), act_[k ^ 1].Stride()));
         k ^= 1;
       }
-      KCheck(klstm_affine_propagate(act_[k].View().Data(), rows, aff_in_, act_[k].Stride(), W_, b_, aout_.View().Data(), out_dim_,
-                                    aout_.Stride(), nullptr));
-      KCheck(klstm_log_softmax_scatter(aout_.View().Data(), rows, out_dim_, aout_.Stride(), pdst_ + (size_t)c * rows, out_dev, out_stride,
-                                       o_.mode, lp_, o_.prior_scale, nullptr));
+      KCheck(klstm_affine_propagate(act_[k].View().Data(), rows, aff_in_, act_[k].Stride(), W_.As<BaseFloat>(), b_.As<BaseFloat>(),
+                                    aout_.View().Data(), out_dim_, aout_.Stride(), nullptr));
+      KCheck(klstm_log_softmax_scatter(aout_.View().Data(), rows, out_dim_, aout_.Stride(), pdst_.As<int32>() + (size_t)c * rows, out_dev,
+                                       out_stride, o_.mode, lp_.As<BaseFloat>(), o_.prior_scale, nullptr));
     }
   }
   // Host API: one [len x InputDim()] row-major matrix per utterance in, one [len x OutputDim()] matrix per utterance out.
@@ -255,27 +252,13 @@ class BatchScorer {
   }
 
  private:
-  static BaseFloat *Upload(const std::vector<BaseFloat> &v) {
-    void *p = nullptr;
-    KCheck(klstm_malloc(&p, std::max<size_t>(v.size(), 1) * sizeof(BaseFloat)));
-    if (!v.empty()) KCheck(klstm_memcpy_h2d(p, v.data(), v.size() * sizeof(BaseFloat), nullptr));
-    return (BaseFloat *)p;
-  }
-  static void Ensure(int32 **p, size_t *cap, size_t n) {
-    if (n <= *cap) return;
-    klstm_free(*p); *p = nullptr;
-    void *q = nullptr;
-    KCheck(klstm_malloc(&q, n * sizeof(int32)));
-    *p = (int32 *)q; *cap = n;
-  }
   BatchScorerOptions o_;
   int32 shift_ = 0, in_dim_ = 0, aff_in_ = 0, out_dim_ = 0;
   struct EngineDel { void operator()(klstm_engine *e) const { klstm_destroy(e); } };
   std::vector<std::unique_ptr<klstm_engine, EngineDel> > engines_;
   std::vector<int32> dims_;
-  BaseFloat *W_ = nullptr, *b_ = nullptr, *lp_ = nullptr;
-  int32 *pdesc_ = nullptr, *pdst_ = nullptr;
-  size_t cap_desc_ = 0, cap_dst_ = 0;
+  DeviceBuffer W_, b_, lp_;                   // lp_ stays empty (null) unless the mode is KLSTM_SCORE_LOGLIKE
+  DeviceBuffer pdesc_, pdst_;                 // the plan of the ScoreDevice call in flight
   DeviceMatrix act_[2], aout_;
 };
 

@@ -2040,54 +2040,65 @@ klstm_status klstm_reverse_streams(const float *in, int in_stride, int S, int T,
   HIPCHK(launch_reverse_streams(in, in_stride, S, T, cols, lens_dev, out, out_stride, mode, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
+// ---- the checks of the CTC entry points, spelled once; fn is the entry's name, which every message begins with ----
+// the shape rule of the three workspace queries that take a label length (what: the entry's word for that length)
+static bool ctc_query_ok(const char *fn, const char *what, int T, int S, int L) {
+  if (T > 0 && S > 0 && S <= 32 && (long)T * S <= 65535 && L >= 0 && L <= 1023) return true;
+  fail(KLSTM_ERR_SHAPE, "%s: T %d, streams %d, %s length %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, L <= 1023", fn, T, S, what, L);
+  return false;
+}
+// What the calls share, in the order it has always fired: sizes, limits (min_k: the fewest classes the call takes), the call's own
+// finding about its pointers (null: none; where a call has several, the first to apply), blank, row stride (the smallest of the
+// call's), its finding about aliasing, workspace alignment.
+static klstm_status ctc_call_check(const char *fn, int T, int S, int K, int min_k, const char *pointers, int blank, int stride,
+                                   const char *aliasing, const void *workspace) {
+  if (T <= 0 || S <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "%s: bad size (T %d, streams %d, K %d)", fn, T, S, K);
+  if (S > 32 || (long)T * S > 65535 || K < min_k || K > 32768)
+    return fail(KLSTM_ERR_SHAPE, "%s: T %d, streams %d, K %d outside S <= 32, T * S <= 65535, %d <= K <= 32768", fn, T, S, K, min_k);
+  if (pointers) return fail(KLSTM_ERR_ARG, "%s: %s", fn, pointers);
+  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "%s: blank %d outside [0, %d)", fn, blank, K);
+  if (stride < K) return fail(KLSTM_ERR_ARG, "%s: row stride below K (%d < %d)", fn, stride, K);
+  if (aliasing) return fail(KLSTM_ERR_ARG, "%s: %s", fn, aliasing);
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
+  return KLSTM_OK;
+}
+// the decoders' finding about their references: a pair, and what is counted against them needs them
+static const char *ctc_refs_finding(const int *ref_labels_dev, const int *ref_offsets_dev, const int *errors_dev, const double *totals_dev) {
+  if ((ref_labels_dev == nullptr) != (ref_offsets_dev == nullptr)) return "reference labels and offsets come together or not at all";
+  if (!ref_labels_dev && (errors_dev || totals_dev)) return "errors / totals need reference labels";
+  return nullptr;
+}
 size_t klstm_ctc_workspace_bytes(int T, int S, int max_label_len) {
-  if (T <= 0 || S <= 0 || S > 32 || (long)T * S > 65535 || max_label_len < 0 || max_label_len > 1023) {
-    fail(KLSTM_ERR_SHAPE, "klstm_ctc_workspace_bytes: T %d, streams %d, label length %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, L <= 1023", T, S, max_label_len);
-    return 0;
-  }
-  return ctc_workspace_bytes(T, S, max_label_len);
+  return ctc_query_ok("klstm_ctc_workspace_bytes", "label", T, S, max_label_len) ? ctc_workspace_bytes(T, S, max_label_len) : 0;
 }
 klstm_status klstm_ctc_eval(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *labels_dev,
                             const int *label_offsets_dev, int blank, float *diff, int diff_stride, float *utt_loss_dev,
                             double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  if (T <= 0 || S <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: bad size (T %d, streams %d, K %d)", T, S, K);
-  if (S > 32 || (long)T * S > 65535 || K > 32768)
-    return fail(KLSTM_ERR_SHAPE, "klstm_ctc_eval: T %d, streams %d, K %d outside S <= 32, T * S <= 65535, K <= 32768", T, S, K);
-  if (!net_out || !lens_dev || !labels_dev || !label_offsets_dev || !diff || !utt_loss_dev || !workspace)
-    return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: null argument");
-  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: blank %d outside [0, %d)", blank, K);
-  if (stride < K || diff_stride < K) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: row stride below K (%d / %d < %d)", stride, diff_stride, K);
-  if (net_out == diff) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: diff == net_out (the posteriors are read while diff is written)");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: workspace must be 16-byte aligned");
+  const char *fn = "klstm_ctc_eval";
+  const bool null = !net_out || !lens_dev || !labels_dev || !label_offsets_dev || !diff || !utt_loss_dev || !workspace;
+  const klstm_status st = ctc_call_check(fn, T, S, K, 1, null ? "null argument" : nullptr, blank, stride < diff_stride ? stride : diff_stride,
+                                         net_out == diff ? "diff == net_out (the posteriors are read while diff is written)" : nullptr, workspace);
+  if (st != KLSTM_OK) return st;
   const int lcap = ctc_label_capacity(T, S, workspace_bytes);
-  if (lcap < 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_eval: workspace of %zu bytes is below klstm_ctc_workspace_bytes(%d, %d, 0)", workspace_bytes, T, S);
+  if (lcap < 0) return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_workspace_bytes(%d, %d, 0)", fn, workspace_bytes, T, S);
   HIPCHK(launch_ctc(net_out, T, S, K, stride, lens_dev, labels_dev, label_offsets_dev, blank, diff, diff_stride, utt_loss_dev, totals_dev,
                     workspace, lcap, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
 size_t klstm_ctc_decode_workspace_bytes(int T, int S, int max_ref_len) {
-  if (T <= 0 || S <= 0 || S > 32 || (long)T * S > 65535 || max_ref_len < 0 || max_ref_len > 1023) {
-    fail(KLSTM_ERR_SHAPE, "klstm_ctc_decode_workspace_bytes: T %d, streams %d, reference length %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, L <= 1023", T, S, max_ref_len);
-    return 0;
-  }
-  return ctc_decode_workspace_bytes(T, S);
+  return ctc_query_ok("klstm_ctc_decode_workspace_bytes", "reference", T, S, max_ref_len) ? ctc_decode_workspace_bytes(T, S) : 0;
 }
 klstm_status klstm_ctc_decode(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
                               const float *class_weight_dev, int *hyp_dev, int *hyp_len_dev, float *score_dev, int *frame_class_dev,
                               const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev, double *totals_dev,
                               void *workspace, size_t workspace_bytes, void *hip_stream) {
-  if (T <= 0 || S <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: bad size (T %d, streams %d, K %d)", T, S, K);
-  if (S > 32 || (long)T * S > 65535 || K < 2 || K > 32768)
-    return fail(KLSTM_ERR_SHAPE, "klstm_ctc_decode: T %d, streams %d, K %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768", T, S, K);
-  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !workspace) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: null argument");
-  if ((ref_labels_dev == nullptr) != (ref_offsets_dev == nullptr))
-    return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: reference labels and offsets come together or not at all");
-  if (!ref_labels_dev && (errors_dev || totals_dev)) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: errors / totals need reference labels");
-  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: blank %d outside [0, %d)", blank, K);
-  if (stride < K) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: row stride below K (%d < %d)", stride, K);
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: workspace must be 16-byte aligned");
+  const char *fn = "klstm_ctc_decode";
+  const char *pointers = ctc_refs_finding(ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev);
+  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !workspace) pointers = "null argument";
+  const klstm_status st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride, nullptr, workspace);
+  if (st != KLSTM_OK) return st;
   if (workspace_bytes < ctc_decode_workspace_bytes(T, S))
-    return fail(KLSTM_ERR_ARG, "klstm_ctc_decode: workspace of %zu bytes is below klstm_ctc_decode_workspace_bytes(%d, %d, .) = %zu", workspace_bytes,
+    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_decode_workspace_bytes(%d, %d, .) = %zu", fn, workspace_bytes,
                 T, S, ctc_decode_workspace_bytes(T, S));
   HIPCHK(launch_ctc_decode(net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, hyp_dev, hyp_len_dev, score_dev, frame_class_dev,
                            ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, (hipStream_t)hip_stream));
@@ -2116,14 +2127,11 @@ static klstm_status ctc_beam_decode_checked(const char *fn, bool with_lm, const 
                 fn, T, S, K, beam, cands, nbest);
   if (Q < (with_lm ? 1 : 0) || (long)Q * K > (1L << 24))
     return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 1 <= states, states * K <= 2^24", fn, Q, K);
-  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !nbest_count_dev || !workspace) return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
-  if (Q > 0 && (!lm_next_dev || !lm_weight_dev)) return fail(KLSTM_ERR_ARG, "%s: the language model's next and weight tables come together", fn);
-  if ((ref_labels_dev == nullptr) != (ref_offsets_dev == nullptr))
-    return fail(KLSTM_ERR_ARG, "%s: reference labels and offsets come together or not at all", fn);
-  if (!ref_labels_dev && (errors_dev || totals_dev)) return fail(KLSTM_ERR_ARG, "%s: errors / totals need reference labels", fn);
-  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "%s: blank %d outside [0, %d)", fn, blank, K);
-  if (stride < K) return fail(KLSTM_ERR_ARG, "%s: row stride below K (%d < %d)", fn, stride, K);
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
+  const char *pointers = ctc_refs_finding(ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev);      // (the later one here fires first)
+  if (Q > 0 && (!lm_next_dev || !lm_weight_dev)) pointers = "the language model's next and weight tables come together";
+  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !nbest_count_dev || !workspace) pointers = "null argument";
+  const klstm_status st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride, nullptr, workspace);
+  if (st != KLSTM_OK) return st;
   if (workspace_bytes < ctc_beam_workspace_bytes(T, S, beam, cands))
     return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_beam_workspace_bytes(%d, %d, %d, %d) = %zu", fn, workspace_bytes,
                 T, S, beam, cands, ctc_beam_workspace_bytes(T, S, beam, cands));
@@ -2154,29 +2162,20 @@ int klstm_ctc_beam_lm_resident(int lm_states, int K, int beam, int cands) {
   return ctc_beam_lm_resident(lm_states, K, beam, cands) ? 1 : 0;
 }
 size_t klstm_ctc_align_workspace_bytes(int T, int S, int max_label_len) {
-  if (T <= 0 || S <= 0 || S > 32 || (long)T * S > 65535 || max_label_len < 0 || max_label_len > 1023) {
-    fail(KLSTM_ERR_SHAPE, "klstm_ctc_align_workspace_bytes: T %d, streams %d, label length %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, L <= 1023", T, S, max_label_len);
-    return 0;
-  }
-  return ctc_align_workspace_bytes(T, S, max_label_len);
+  return ctc_query_ok("klstm_ctc_align_workspace_bytes", "label", T, S, max_label_len) ? ctc_align_workspace_bytes(T, S, max_label_len) : 0;
 }
 klstm_status klstm_ctc_align(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *labels_dev,
                              const int *label_offsets_dev, int blank, const float *class_weight_dev, int *frame_class_dev,
                              int *frame_pos_dev, int *token_begin_dev, int *token_end_dev, float *score_dev, double *totals_dev,
                              void *workspace, size_t workspace_bytes, void *hip_stream) {
-  if (T <= 0 || S <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_align: bad size (T %d, streams %d, K %d)", T, S, K);
-  if (S > 32 || (long)T * S > 65535 || K < 2 || K > 32768)
-    return fail(KLSTM_ERR_SHAPE, "klstm_ctc_align: T %d, streams %d, K %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768", T, S, K);
-  if (!net_out || !lens_dev || !labels_dev || !label_offsets_dev || !frame_class_dev || !workspace)
-    return fail(KLSTM_ERR_ARG, "klstm_ctc_align: null argument");
-  if ((token_begin_dev == nullptr) != (token_end_dev == nullptr))
-    return fail(KLSTM_ERR_ARG, "klstm_ctc_align: token begins and ends come together or not at all");
-  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "klstm_ctc_align: blank %d outside [0, %d)", blank, K);
-  if (stride < K) return fail(KLSTM_ERR_ARG, "klstm_ctc_align: row stride below K (%d < %d)", stride, K);
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "klstm_ctc_align: workspace must be 16-byte aligned");
+  const char *fn = "klstm_ctc_align";
+  const char *pointers = (token_begin_dev == nullptr) != (token_end_dev == nullptr) ? "token begins and ends come together or not at all" : nullptr;
+  if (!net_out || !lens_dev || !labels_dev || !label_offsets_dev || !frame_class_dev || !workspace) pointers = "null argument";
+  const klstm_status st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride, nullptr, workspace);
+  if (st != KLSTM_OK) return st;
   const int lcap = ctc_align_label_capacity(T, S, workspace_bytes);
   if (lcap < 0)
-    return fail(KLSTM_ERR_ARG, "klstm_ctc_align: workspace of %zu bytes is below klstm_ctc_align_workspace_bytes(%d, %d, 0) = %zu", workspace_bytes, T, S,
+    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_align_workspace_bytes(%d, %d, 0) = %zu", fn, workspace_bytes, T, S,
                 ctc_align_workspace_bytes(T, S, 0));
   HIPCHK(launch_ctc_align(net_out, T, S, K, stride, lens_dev, labels_dev, label_offsets_dev, blank, class_weight_dev, frame_class_dev,
                           frame_pos_dev, token_begin_dev, token_end_dev, score_dev, totals_dev, workspace, lcap, (hipStream_t)hip_stream));

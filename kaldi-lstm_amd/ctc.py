@@ -11,15 +11,69 @@ import numpy as np
 
 from .binding import _chk, _sp, load_library
 
-_WS = {}          # (device, T, S, label capacity) -> uint8 workspace tensor
+_WS = {}          # operation -> {(device, the shape its workspace depends on) -> uint8 workspace tensor}
 
 
-def ctc_workspace_bytes(T, S, max_label_len):
-    lib = load_library()
-    n = lib.klstm_ctc_workspace_bytes(int(T), int(S), int(max_label_len))
+def _workspace_bytes(fn_name, *args):
+    n = getattr(load_library(), fn_name)(*(int(a) for a in args))
     if n == 0:
         _chk(2)
     return n
+
+
+def _workspace(op, key, nbytes, dev):
+    """the cached workspace of operation `op` for the shape `key`; an operation that has seen 8 shapes starts over"""
+    import torch
+    cache = _WS.setdefault(op, {})
+    key = (dev.index,) + tuple(key)
+    ws = cache.get(key)
+    if ws is None:
+        if len(cache) >= 8:
+            cache.clear()
+        ws = cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _shape(net_out, lens):
+    """(net_out [T*S, K], lens) -> (lens as an int32 tensor on net_out's device, S, T, K)"""
+    import torch
+    assert net_out.is_cuda and net_out.dtype == torch.float32 and net_out.dim() == 2 and net_out.stride(1) == 1
+    if isinstance(lens, torch.Tensor) and lens.is_cuda:
+        assert lens.dtype == torch.int32 and lens.is_contiguous()
+        lens_dev = lens
+    else:
+        lens_dev = torch.tensor([int(v) for v in lens], dtype=torch.int32, device=net_out.device)
+    S = lens_dev.numel()
+    assert S > 0 and net_out.shape[0] % S == 0, "rows must be T * len(lens)"
+    return lens_dev, S, net_out.shape[0] // S, net_out.shape[1]
+
+
+def _check_class_weight(class_weight, K):
+    import torch
+    if class_weight is not None:
+        assert class_weight.is_cuda and class_weight.dtype == torch.float32 and class_weight.numel() == K and class_weight.is_contiguous()
+
+
+def _check_totals(totals, n):
+    import torch
+    if totals is not None:
+        assert totals.is_cuda and totals.dtype == torch.float64 and totals.numel() == n and totals.is_contiguous()
+
+
+def _packed(labels, S, dev):
+    """label lists, or what pack_labels() returned -> (labels, offsets, longest) on the device, checked against S streams"""
+    import torch
+    lab_dev, off_dev, longest = labels if isinstance(labels, tuple) else pack_labels(labels, dev)
+    assert off_dev.numel() == S + 1 and lab_dev.dtype == torch.int32 and off_dev.dtype == torch.int32
+    return lab_dev, off_dev, longest
+
+
+def ctc_workspace_bytes(T, S, max_label_len):
+    return _workspace_bytes("klstm_ctc_workspace_bytes", T, S, max_label_len)
 
 
 def pack_labels(labels, device):
@@ -44,47 +98,26 @@ def ctc_eval(net_out, lens, labels, blank=0, diff=None, totals=None, stream=None
     import torch
     lib = load_library()
     dev = net_out.device
-    assert net_out.is_cuda and net_out.dtype == torch.float32 and net_out.dim() == 2 and net_out.stride(1) == 1
-    if isinstance(lens, torch.Tensor) and lens.is_cuda:
-        assert lens.dtype == torch.int32 and lens.is_contiguous()
-        lens_dev = lens
-    else:
-        lens_dev = torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
-    S = lens_dev.numel()
-    assert S > 0 and net_out.shape[0] % S == 0, "rows must be T * len(lens)"
-    T, K = net_out.shape[0] // S, net_out.shape[1]
-    lab_dev, off_dev, longest = labels if isinstance(labels, tuple) else pack_labels(labels, dev)
-    assert off_dev.numel() == S + 1 and lab_dev.dtype == torch.int32 and off_dev.dtype == torch.int32
+    lens_dev, S, T, K = _shape(net_out, lens)
+    lab_dev, off_dev, longest = _packed(labels, S, dev)
     if diff is None:
         diff = torch.empty(T * S, K, device=dev)
     assert diff.is_cuda and diff.dtype == torch.float32 and diff.shape == (T * S, K) and diff.stride(1) == 1
     nbytes = ctc_workspace_bytes(T, S, longest)
-    key = (dev.index, T, S, longest)
-    ws = _WS.get(key)
-    if ws is None:
-        if len(_WS) >= 8:
-            _WS.clear()
-        ws = _WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace("eval", (T, S, longest), nbytes, dev)
     utt_loss = torch.empty(S, device=dev)
-    if totals is not None:
-        assert totals.is_cuda and totals.dtype == torch.float64 and totals.numel() == 4 and totals.is_contiguous()
+    _check_totals(totals, 4)
     _chk(lib.klstm_ctc_eval(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), lab_dev.data_ptr(), off_dev.data_ptr(),
-                            int(blank), diff.data_ptr(), diff.stride(0), utt_loss.data_ptr(),
-                            totals.data_ptr() if totals is not None else None, ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+                            int(blank), diff.data_ptr(), diff.stride(0), utt_loss.data_ptr(), _ptr(totals), ws.data_ptr(),
+                            ctypes.c_size_t(nbytes), _sp(stream)))
     return utt_loss, diff
 
-
-_DWS = {}         # (device, T, S) -> uint8 workspace tensor of ctc_greedy_decode
 
 CtcDecodeResult = collections.namedtuple("CtcDecodeResult", "hyp hyp_len score frame_class errors")
 
 
 def ctc_decode_workspace_bytes(T, S, max_ref_len=0):
-    lib = load_library()
-    n = lib.klstm_ctc_decode_workspace_bytes(int(T), int(S), int(max_ref_len))
-    if n == 0:
-        _chk(2)
-    return n
+    return _workspace_bytes("klstm_ctc_decode_workspace_bytes", T, S, max_ref_len)
 
 
 def ctc_greedy_decode(net_out, lens, blank=0, class_weight=None, refs=None, totals=None, stream=None):
@@ -98,43 +131,24 @@ def ctc_greedy_decode(net_out, lens, blank=0, class_weight=None, refs=None, tota
     import torch
     lib = load_library()
     dev = net_out.device
-    assert net_out.is_cuda and net_out.dtype == torch.float32 and net_out.dim() == 2 and net_out.stride(1) == 1
-    if isinstance(lens, torch.Tensor) and lens.is_cuda:
-        assert lens.dtype == torch.int32 and lens.is_contiguous()
-        lens_dev = lens
-    else:
-        lens_dev = torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
-    S = lens_dev.numel()
-    assert S > 0 and net_out.shape[0] % S == 0, "rows must be T * len(lens)"
-    T, K = net_out.shape[0] // S, net_out.shape[1]
-    if class_weight is not None:
-        assert class_weight.is_cuda and class_weight.dtype == torch.float32 and class_weight.numel() == K and class_weight.is_contiguous()
+    lens_dev, S, T, K = _shape(net_out, lens)
+    _check_class_weight(class_weight, K)
     lab_dev = off_dev = errors = None
     longest = 0
     if refs is not None:
-        lab_dev, off_dev, longest = refs if isinstance(refs, tuple) else pack_labels(refs, dev)
-        assert off_dev.numel() == S + 1 and lab_dev.dtype == torch.int32 and off_dev.dtype == torch.int32
+        lab_dev, off_dev, longest = _packed(refs, S, dev)
         errors = torch.empty(S, dtype=torch.int32, device=dev)
-    if totals is not None:
-        assert refs is not None, "totals need refs"
-        assert totals.is_cuda and totals.dtype == torch.float64 and totals.numel() == 5 and totals.is_contiguous()
+    assert totals is None or refs is not None, "totals need refs"
+    _check_totals(totals, 5)
     nbytes = ctc_decode_workspace_bytes(T, S, min(longest, 1023))       # a longer reference is the device's to refuse (errors -1)
-    key = (dev.index, T, S)
-    ws = _DWS.get(key)
-    if ws is None:
-        if len(_DWS) >= 8:
-            _DWS.clear()
-        ws = _DWS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace("decode", (T, S), nbytes, dev)
     hyp = torch.empty(S, T, dtype=torch.int32, device=dev)
     hyp_len = torch.empty(S, dtype=torch.int32, device=dev)
     score = torch.empty(S, device=dev)
     frame_class = torch.empty(T * S, dtype=torch.int32, device=dev)
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
-    _chk(lib.klstm_ctc_decode(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), ptr(class_weight),
-                              hyp.data_ptr(), hyp_len.data_ptr(), score.data_ptr(), frame_class.data_ptr(), ptr(lab_dev), ptr(off_dev),
-                              ptr(errors), ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    _chk(lib.klstm_ctc_decode(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), _ptr(class_weight),
+                              hyp.data_ptr(), hyp_len.data_ptr(), score.data_ptr(), frame_class.data_ptr(), _ptr(lab_dev), _ptr(off_dev),
+                              _ptr(errors), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
     return CtcDecodeResult(hyp, hyp_len, score, frame_class, errors)
 
 
@@ -144,17 +158,11 @@ def hypotheses_to_lists(hyp, hyp_len):
     return [h[s, :n[s]].tolist() for s in range(len(n))]
 
 
-_AWS = {}         # (device, T, S, label capacity) -> uint8 workspace tensor of ctc_align
-
 CtcAlignResult = collections.namedtuple("CtcAlignResult", "frame_class frame_pos token_begin token_end score")
 
 
 def ctc_align_workspace_bytes(T, S, max_label_len):
-    lib = load_library()
-    n = lib.klstm_ctc_align_workspace_bytes(int(T), int(S), int(max_label_len))
-    if n == 0:
-        _chk(2)
-    return n
+    return _workspace_bytes("klstm_ctc_align_workspace_bytes", T, S, max_label_len)
 
 
 def ctc_align(net_out, lens, labels, blank=0, class_weight=None, totals=None, stream=None):
@@ -168,38 +176,21 @@ def ctc_align(net_out, lens, labels, blank=0, class_weight=None, totals=None, st
     import torch
     lib = load_library()
     dev = net_out.device
-    assert net_out.is_cuda and net_out.dtype == torch.float32 and net_out.dim() == 2 and net_out.stride(1) == 1
-    if isinstance(lens, torch.Tensor) and lens.is_cuda:
-        assert lens.dtype == torch.int32 and lens.is_contiguous()
-        lens_dev = lens
-    else:
-        lens_dev = torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
-    S = lens_dev.numel()
-    assert S > 0 and net_out.shape[0] % S == 0, "rows must be T * len(lens)"
-    T, K = net_out.shape[0] // S, net_out.shape[1]
-    lab_dev, off_dev, longest = labels if isinstance(labels, tuple) else pack_labels(labels, dev)
-    assert off_dev.numel() == S + 1 and lab_dev.dtype == torch.int32 and off_dev.dtype == torch.int32
-    if class_weight is not None:
-        assert class_weight.is_cuda and class_weight.dtype == torch.float32 and class_weight.numel() == K and class_weight.is_contiguous()
-    if totals is not None:
-        assert totals.is_cuda and totals.dtype == torch.float64 and totals.numel() == 5 and totals.is_contiguous()
+    lens_dev, S, T, K = _shape(net_out, lens)
+    lab_dev, off_dev, longest = _packed(labels, S, dev)
+    _check_class_weight(class_weight, K)
+    _check_totals(totals, 5)
     cap = min(longest, 1023)                                            # a longer sequence is the device's to reject
     nbytes = ctc_align_workspace_bytes(T, S, cap)
-    key = (dev.index, T, S, cap)
-    ws = _AWS.get(key)
-    if ws is None:
-        if len(_AWS) >= 8:
-            _AWS.clear()
-        ws = _AWS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace("align", (T, S, cap), nbytes, dev)
     frame_class = torch.empty(T * S, dtype=torch.int32, device=dev)
     frame_pos = torch.empty(T * S, dtype=torch.int32, device=dev)
     token_begin = torch.empty(lab_dev.numel(), dtype=torch.int32, device=dev)
     token_end = torch.empty(lab_dev.numel(), dtype=torch.int32, device=dev)
     score = torch.empty(S, device=dev)
     _chk(lib.klstm_ctc_align(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), lab_dev.data_ptr(), off_dev.data_ptr(),
-                             int(blank), class_weight.data_ptr() if class_weight is not None else None, frame_class.data_ptr(),
-                             frame_pos.data_ptr(), token_begin.data_ptr(), token_end.data_ptr(), score.data_ptr(),
-                             totals.data_ptr() if totals is not None else None, ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+                             int(blank), _ptr(class_weight), frame_class.data_ptr(), frame_pos.data_ptr(), token_begin.data_ptr(),
+                             token_end.data_ptr(), score.data_ptr(), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
     return CtcAlignResult(frame_class, frame_pos, token_begin, token_end, score)
 
 
@@ -220,17 +211,11 @@ def alignments_to_lists(result, lens, offsets):
     return out
 
 
-_BWS = {}         # (device, T, S, beam, cands) -> uint8 workspace tensor of ctc_beam_decode
-
 CtcBeamResult = collections.namedtuple("CtcBeamResult", "hyp hyp_len nbest_count score errors")
 
 
 def ctc_beam_workspace_bytes(T, S, beam, cands):
-    lib = load_library()
-    n = lib.klstm_ctc_beam_workspace_bytes(int(T), int(S), int(beam), int(cands))
-    if n == 0:
-        _chk(2)
-    return n
+    return _workspace_bytes("klstm_ctc_beam_workspace_bytes", T, S, beam, cands)
 
 
 class CtcLabelLm:
@@ -267,51 +252,32 @@ def ctc_beam_decode(net_out, lens, blank=0, beam=16, cands=8, nbest=1, class_wei
     import torch
     lib = load_library()
     dev = net_out.device
-    assert net_out.is_cuda and net_out.dtype == torch.float32 and net_out.dim() == 2 and net_out.stride(1) == 1
-    if isinstance(lens, torch.Tensor) and lens.is_cuda:
-        assert lens.dtype == torch.int32 and lens.is_contiguous()
-        lens_dev = lens
-    else:
-        lens_dev = torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
-    S = lens_dev.numel()
-    assert S > 0 and net_out.shape[0] % S == 0, "rows must be T * len(lens)"
-    T, K = net_out.shape[0] // S, net_out.shape[1]
+    lens_dev, S, T, K = _shape(net_out, lens)
     beam, cands, nbest = int(beam), int(cands), int(nbest)
-    if class_weight is not None:
-        assert class_weight.is_cuda and class_weight.dtype == torch.float32 and class_weight.numel() == K and class_weight.is_contiguous()
+    _check_class_weight(class_weight, K)
     lab_dev = off_dev = errors = None
     if refs is not None:
-        lab_dev, off_dev, _ = refs if isinstance(refs, tuple) else pack_labels(refs, dev)
-        assert off_dev.numel() == S + 1 and lab_dev.dtype == torch.int32 and off_dev.dtype == torch.int32
-    if totals is not None:
-        assert refs is not None, "totals need refs"
-        assert totals.is_cuda and totals.dtype == torch.float64 and totals.numel() == 6 and totals.is_contiguous()
+        lab_dev, off_dev, _ = _packed(refs, S, dev)
+    assert totals is None or refs is not None, "totals need refs"
+    _check_totals(totals, 6)
     nbytes = ctc_beam_workspace_bytes(T, S, beam, cands)
-    key = (dev.index, T, S, beam, cands)
-    ws = _BWS.get(key)
-    if ws is None:
-        if len(_BWS) >= 8:
-            _BWS.clear()
-        ws = _BWS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace("beam", (T, S, beam, cands), nbytes, dev)
     hyp = torch.empty(S, max(nbest, 0), T, dtype=torch.int32, device=dev)
     hyp_len = torch.empty(S, max(nbest, 0), dtype=torch.int32, device=dev)
     count = torch.empty(S, dtype=torch.int32, device=dev)
     score = torch.empty(S, max(nbest, 0), device=dev)
     if refs is not None:
         errors = torch.empty(S, max(nbest, 0), dtype=torch.int32, device=dev)
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
     if lm is None:
-        _chk(lib.klstm_ctc_beam_decode(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), ptr(class_weight),
+        _chk(lib.klstm_ctc_beam_decode(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), _ptr(class_weight),
                                        beam, cands, nbest, hyp.data_ptr(), hyp_len.data_ptr(), count.data_ptr(), score.data_ptr(),
-                                       ptr(lab_dev), ptr(off_dev), ptr(errors), ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+                                       _ptr(lab_dev), _ptr(off_dev), _ptr(errors), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
     else:
         assert lm.classes == K and lm.next.device == dev, "the language model's tables have K columns and live on net_out's device"
-        _chk(lib.klstm_ctc_beam_decode_lm(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), ptr(class_weight),
-                                          beam, cands, nbest, lm.states, lm.next.data_ptr(), lm.weight.data_ptr(), ptr(lm.final),
-                                          hyp.data_ptr(), hyp_len.data_ptr(), count.data_ptr(), score.data_ptr(), ptr(lab_dev), ptr(off_dev),
-                                          ptr(errors), ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+        _chk(lib.klstm_ctc_beam_decode_lm(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), _ptr(class_weight),
+                                          beam, cands, nbest, lm.states, lm.next.data_ptr(), lm.weight.data_ptr(), _ptr(lm.final),
+                                          hyp.data_ptr(), hyp_len.data_ptr(), count.data_ptr(), score.data_ptr(), _ptr(lab_dev), _ptr(off_dev),
+                                          _ptr(errors), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
     return CtcBeamResult(hyp, hyp_len, count, score, errors)
 
 

@@ -1,5 +1,7 @@
 // tests/cpp/ctc_test.cpp -- drives WholeUtteranceBatcher (include/klstm_trainer.hpp; host only) and Ctc / TrainCtcWholeUtterances
-// (include/klstm_nnet.hpp; GPU) for tests/test_ctc.py and tests/test_ctc_gpu.py.
+// (include/klstm_nnet.hpp; GPU) for tests/test_ctc.py and tests/test_ctc_gpu.py; on the GPU also the pieces the CTC classes are built from
+// (DeviceBuffer, DeviceTotals) and one object of each class through calls of changing shape.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -55,6 +57,68 @@ static LstmProjectedStreams *new_lstm(int32 in, int32 cell, int32 out, int32 str
   std::istringstream is(cfg.str());
   c->InitData(is);
   return c.release();
+}
+
+// ---- the reuse check: one call of every CTC class on seeded posteriors, everything a stream gets out of it as raw bytes ----
+struct ReuseCase {
+  int32 T, S;
+  std::vector<int32> lens;
+  std::vector<std::vector<int32> > labels;
+};
+template <class T>
+static void append(std::string *bytes, const std::vector<T> &v) { bytes->append(reinterpret_cast<const char *>(v.data()), v.size() * sizeof(T)); }
+static void append(std::string *bytes, const std::vector<std::vector<int32> > &v) {
+  for (const auto &l : v) { const std::vector<int32> n(1, (int32)l.size()); append(bytes, n); append(bytes, l); }
+}
+// seeded softmax rows [T*S x K]
+static void fill_posteriors(unsigned seed, int32 rows, int32 K, DeviceMatrix *y) {
+  unsigned s = seed * 2654435761u + 99u;
+  std::vector<BaseFloat> h((size_t)rows * K);
+  for (int32 r = 0; r < rows; r++) {
+    double sum = 0;
+    for (int32 k = 0; k < K; k++) sum += h[(size_t)r * K + k] = std::exp(3.f * (float)(lcg(&s) % 1000u) / 1000.f);
+    for (int32 k = 0; k < K; k++) h[(size_t)r * K + k] = (BaseFloat)(h[(size_t)r * K + k] / sum);
+  }
+  y->CopyFromHost(h.data(), rows, K);
+}
+struct ReuseObjects {
+  Ctc ctc;
+  CtcGreedyDecoder greedy;
+  CtcBeamDecoder beam{0, 4, 2, 2};
+  CtcAligner aligner;
+};
+// sums[]: what the totals of the four objects grow by in this call, from the per-stream outputs
+static std::string reuse_call(ReuseObjects *o, const ReuseCase &c, const DeviceMatrix &y, double *sums) {
+  std::string out;
+  DeviceMatrix diff;
+  std::vector<BaseFloat> f, d;
+  std::vector<int32> a, b;
+  std::vector<std::vector<int32> > u, v;
+  o->ctc.Eval(y, c.S, c.lens, c.labels, &diff);
+  o->ctc.UttLoss(&f); diff.CopyToHost(&d);
+  append(&out, f); append(&out, d);
+  for (int32 s = 0; s < c.S; s++) if (c.lens[s] > 0 && std::isfinite(f[s])) sums[0] += (double)f[s];
+  o->greedy.Decode(y, c.S, c.lens, c.labels, &u);
+  o->greedy.UttScores(&f); o->greedy.UttErrors(&a); o->greedy.FrameClasses(&b);
+  append(&out, u); append(&out, f); append(&out, a); append(&out, b);
+  for (int32 s = 0; s < c.S; s++) if (a[s] > 0) sums[1] += 1;
+  std::vector<CtcNbestList> lists;
+  o->beam.Decode(y, c.S, c.lens, c.labels, &lists);
+  for (const auto &l : lists)
+    for (const auto &h : l) { append(&out, h.tokens); append(&out, std::vector<BaseFloat>(1, h.score)); append(&out, std::vector<int32>(1, h.errors)); }
+  o->beam.NbestCounts(&a); append(&out, a);
+  o->beam.UttScores(&f); append(&out, f);
+  o->beam.UttErrors(&a); append(&out, a);
+  for (int32 s = 0; s < c.S; s++) if (a[s] > 0) sums[2] += 1;
+  o->aligner.Align(y, c.S, c.lens, c.labels);
+  o->aligner.FrameClasses(&a); o->aligner.FramePositions(&b); o->aligner.TokenBounds(&u, &v); o->aligner.UttScores(&f);
+  append(&out, a); append(&out, b); append(&out, u); append(&out, v); append(&out, f);
+  for (int32 s = 0; s < c.S; s++) {
+    if (c.lens[s] <= 0 || !std::isfinite(f[s])) continue;
+    sums[3] += (double)f[s];
+    for (int32 t = 0; t < c.lens[s]; t++) sums[4] += a[(size_t)t * c.S + s] == 0;
+  }
+  return out;
 }
 
 int main(int argc, char **argv) {
@@ -141,8 +205,87 @@ int main(int argc, char **argv) {
       }
       std::cout << "OK first_epoch_loss_per_frame=" << first << " last_epoch_loss_per_frame=" << last << " rejected=" << (int)rejected
                 << " planted_rejected=" << planted_rejected << " skipped=" << skipped << " planted_skipped=" << planted_skipped << "\n";
+    } else if (mode == "buffers" && argc == 2) {
+      // buffers      GPU.  The contracts of DeviceBuffer and DeviceTotals (include/klstm_nnet.hpp), one key=0/1 each
+      DeviceBuffer a;
+      a.Grow(100);
+      const void *p = a.As<void>();
+      a.Grow(50);
+      const bool keeps = p && a.As<void>() == p && a.Capacity() >= 100;
+      a.Grow(200);
+      const bool grows = a.As<void>() && a.Capacity() >= 200;
+      const void *q = a.As<void>();
+      DeviceBuffer b(std::move(a));
+      const bool moved = !a.As<void>() && a.Capacity() == 0 && b.As<void>() == q && b.Capacity() >= 200;
+      DeviceBuffer c;
+      c.Grow(16);
+      c = std::move(b);
+      const bool assigned = !b.As<void>() && b.Capacity() == 0 && c.As<void>() == q && c.Capacity() >= 200;
+      DeviceBuffer e;
+      int32 x = 7;
+      e.Upload(std::vector<int32>());
+      e.Download(&x, 0);
+      const bool empty = !e.As<void>() && e.Capacity() == 0 && x == 7;
+      std::vector<int32> five = {1, 2, 3, 4, 5}, back(5, 0);
+      c.Upload(five);                                                       // fits: the block stays
+      c.Download(back.data(), back.size());
+      const bool round_trip = back == five && c.As<void>() == q;
+      DeviceTotals<4> t;
+      const double *h = t.Read();
+      bool untouched = h[0] == 0 && h[1] == 0 && h[2] == 0 && h[3] == 0;
+      KLSTM_ASSERT(t.Dev() != nullptr && t.Dev() == t.Dev());
+      h = t.Read();
+      untouched = untouched && h[0] == 0 && h[1] == 0 && h[2] == 0 && h[3] == 0;
+      DeviceMatrix y, diff;                                                 // one call that adds to a totals block, read twice
+      fill_posteriors(1, 12, 5, &y);
+      Ctc ctc;
+      ctc.Eval(y, 2, std::vector<int32>{6, 5}, std::vector<std::vector<int32> >{{1, 2}, {3}}, &diff);
+      const double r1[4] = {ctc.AvgLoss(), ctc.NumUtterances(), ctc.NumRejected(), ctc.Frames()};
+      const double r2[4] = {ctc.AvgLoss(), ctc.NumUtterances(), ctc.NumRejected(), ctc.Frames()};
+      const bool twice = std::memcmp(r1, r2, sizeof(r1)) == 0 && r1[1] == 2 && r1[2] == 0 && r1[3] == 11 && std::isfinite(r1[0]) && r1[0] > 0;
+      std::cout << "OK grow_smaller_keeps_pointer=" << keeps << " grow_larger_has_capacity=" << grows << " moved_from_is_empty=" << moved
+                << " move_assigned_from_is_empty=" << assigned << " empty_upload_download_do_nothing=" << empty << " round_trip=" << round_trip
+                << " untouched_totals_are_zero=" << untouched << " totals_read_twice_agree=" << twice << "\n";
+    } else if (mode == "reuse" && argc == 2) {
+      // reuse      GPU.  One object each of Ctc, CtcGreedyDecoder, CtcBeamDecoder (beam 4, 2 candidates, 2-best) and CtcAligner through three
+      // calls, K = 5, blank 0: (T 6, S 2), (T 12, S 3) with stream 1 idle, (T 6, S 2) again -- the buffers grow, then are larger than
+      // needed.  same<i>: every per-stream output of call i has the bits a fresh set of objects gives; totals: the reused objects'
+      // totals are the three fresh ones added up.
+      const int32 K = 5;
+      const ReuseCase cases[3] = {{6, 2, {6, 4}, {{1, 2, 3}, {}}},
+                                  {12, 3, {12, 0, 9}, {{4, 4, 1}, {2}, {3, 1}}},
+                                  {6, 2, {5, 6}, {{2}, {1, 1, 3}}}};
+      ReuseObjects reused;
+      double want[5] = {0, 0, 0, 0, 0}, ignore[5];
+      bool same[3], fresh_totals = true;
+      double ctc_n = 0, ctc_rej = 0, ctc_frames = 0, g[5] = {0, 0, 0, 0, 0}, bm[6] = {0, 0, 0, 0, 0, 0}, al[3] = {0, 0, 0};
+      for (int32 i = 0; i < 3; i++) {
+        const ReuseCase &c = cases[i];
+        DeviceMatrix y;
+        fill_posteriors(10 + i, c.T * c.S, K, &y);
+        ReuseObjects fresh;
+        const std::string a = reuse_call(&reused, c, y, ignore), b = reuse_call(&fresh, c, y, want);
+        same[i] = !a.empty() && a == b;
+        ctc_n += fresh.ctc.NumUtterances(); ctc_rej += fresh.ctc.NumRejected(); ctc_frames += fresh.ctc.Frames();
+        g[0] += fresh.greedy.NumErrors(); g[1] += fresh.greedy.NumRefTokens(); g[2] += fresh.greedy.NumHypTokens(); g[3] += fresh.greedy.NumUtterances();
+        bm[0] += fresh.beam.NumErrors(); bm[1] += fresh.beam.NumRefTokens(); bm[2] += fresh.beam.NumHypTokens(); bm[3] += fresh.beam.NumUtterances();
+        bm[5] += fresh.beam.NumOracleErrors();
+        al[0] += fresh.aligner.NumAligned(); al[1] += fresh.aligner.NumRejected(); al[2] += fresh.aligner.Frames();
+        fresh_totals = fresh_totals && fresh.ctc.NumUtterances() > 0 && fresh.greedy.NumRefTokens() > 0 && fresh.aligner.Frames() > 0;
+      }
+      const bool totals =
+          reused.ctc.NumUtterances() == ctc_n && reused.ctc.NumRejected() == ctc_rej && reused.ctc.Frames() == ctc_frames &&
+          reused.ctc.AvgLoss() == want[0] / ctc_n && reused.ctc.AvgLossPerFrame() == want[0] / ctc_frames &&
+          reused.greedy.NumErrors() == g[0] && reused.greedy.NumRefTokens() == g[1] && reused.greedy.NumHypTokens() == g[2] &&
+          reused.greedy.NumUtterances() == g[3] && reused.greedy.UtteranceErrorRate() == want[1] / g[3] &&
+          reused.beam.NumErrors() == bm[0] && reused.beam.NumRefTokens() == bm[1] && reused.beam.NumHypTokens() == bm[2] &&
+          reused.beam.NumUtterances() == bm[3] && reused.beam.NumOracleErrors() == bm[5] && reused.beam.UtteranceErrorRate() == want[2] / bm[3] &&
+          reused.aligner.NumAligned() == al[0] && reused.aligner.NumRejected() == al[1] && reused.aligner.Frames() == al[2] &&
+          reused.aligner.AvgScorePerFrame() == want[3] / al[2] && reused.aligner.BlankRatio() == want[4] / al[2];
+      std::cout << "OK same0=" << same[0] << " same1=" << same[1] << " same2=" << same[2] << " totals=" << totals << " fresh_totals_counted="
+                << fresh_totals << " utterances=" << ctc_n << " frames=" << ctc_frames << " ref_tokens=" << g[1] << " aligned=" << al[0] << "\n";
     } else {
-      std::cerr << "usage: ctc_test batcher <streams> <sort> <max_frames> <lens> <out> | train <blstm|lstm> <dump>\n";
+      std::cerr << "usage: ctc_test batcher <streams> <sort> <max_frames> <lens> <out> | train <blstm|lstm> <dump> | buffers | reuse\n";
       return 2;
     }
   } catch (const std::exception &e) {

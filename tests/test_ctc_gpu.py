@@ -215,3 +215,28 @@ def test_cpp_trainer_unidirectional_counts_rejected(tmp_path):
     assert int(kv["rejected"]) == int(kv["planted_rejected"]) > 0
     assert int(kv["skipped"]) == int(kv["planted_skipped"]) > 0
     assert np.isfinite(float(kv["last_epoch_loss_per_frame"]))
+
+
+def test_cpp_device_buffer_and_totals_semantics():
+    """DeviceBuffer and DeviceTotals, the pieces every owner of device memory in include/ is built from: growing to a smaller size
+    keeps the block, growing reports the capacity, a moved-from buffer is null with capacity 0, an empty Upload and a Download of
+    nothing do nothing, an untouched totals block reads as zeros and two reads after one call agree."""
+    from tests.test_ctc import run_driver
+    r = run_driver("buffers")
+    kv = dict(f.split("=") for f in r.stdout.split() if "=" in f)
+    print("ctc_test buffers:", r.stdout.strip(), flush=True)
+    for key in ("grow_smaller_keeps_pointer", "grow_larger_has_capacity", "moved_from_is_empty", "move_assigned_from_is_empty",
+                "empty_upload_download_do_nothing", "round_trip", "untouched_totals_are_zero", "totals_read_twice_agree"):
+        assert kv[key] == "1", key
+
+
+def test_cpp_objects_reused_across_shapes():
+    """One Ctc, CtcGreedyDecoder, CtcBeamDecoder and CtcAligner through (T 6, S 2), (T 12, S 3, one stream idle), (T 6, S 2): every
+    per-stream output has the bits of a fresh object's, and the totals are the three fresh ones added up."""
+    from tests.test_ctc import run_driver
+    r = run_driver("reuse")
+    kv = dict(f.split("=") for f in r.stdout.split() if "=" in f)
+    print("ctc_test reuse:", r.stdout.strip(), flush=True)
+    assert kv["same0"] == "1" and kv["same1"] == "1" and kv["same2"] == "1"
+    assert kv["fresh_totals_counted"] == "1" and int(kv["utterances"]) == 6 and int(kv["frames"]) == 42
+    assert kv["totals"] == "1"
