@@ -479,6 +479,47 @@ klstm_status klstm_ctc_beam_decode_lm(const float *net_out, int T, int S, int K,
                                       int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
 int klstm_ctc_beam_lm_resident(int lm_states, int K, int beam, int cands);
 
+/* Minimum expected token error over CTC n-best lists (MWER / minimum Bayes risk over n-best; include/klstm_nnet.hpp class CtcMbr;
+ * INTEGRATION.md 3i): the sequence-discriminative objective that follows CTC training, on the lists and edit distances
+ * klstm_ctc_beam_decode wrote.  Stateless, asynchronous on hip_stream, decided entirely on the device.  net_out, stride, lens_dev,
+ * blank, diff and diff_stride exactly as klstm_ctc_eval takes them.  For stream s, over its listed entries q < nbest_count[s]:
+ *   l_q = log p(h_q | y)      what klstm_ctc_eval returns as -utt_loss for the labels h_q (the same chain, the same bits), kept in double
+ *   P_q = softmax_q(risk_scale * l_q)   in double, q ascending, over the entries that are not dropped
+ *   R   = sum_q P_q W_q       the expected errors, W_q = errors_dev[s*N + q]
+ *   diff(t,k) = risk_scale * sum_q P_q (W_q - R) gamma_q(t,k) + ctc_weight * (y(t,k) - gamma_ref(t,k))
+ * the gradient of R + ctc_weight * (-log p(ref | y)) with respect to the SOFTMAX INPUT; gamma_q = the per-frame occupation of h_q.
+ * The coefficient risk_scale * P_q (W_q - R) is rounded to float once; the row is accumulated in fp32, q ascending, the reference last.
+ *   hyp_dev, hyp_stride, hyp_len_dev [S*N], nbest_count_dev [S], errors_dev [S*N], list_n = N
+ *                        the arrays of klstm_ctc_beam_decode, unchanged (hyp_stride = T there): labelling q of stream s at
+ *                        hyp_dev[(s*N + q)*hyp_stride .. + hyp_len].  Slots q >= nbest_count[s] are NOT READ
+ *   ref_labels_dev, ref_offsets_dev [S+1]   the CSR pair klstm_ctc_eval takes; both NULL if and only if ctc_weight == 0
+ *   risk_scale, ctc_weight   finite, risk_scale > 0, ctc_weight >= 0
+ *   risk_dev [S]         R as float; 0 for an idle stream, -1 for a rejected or skipped one
+ *   hyp_logp_dev         NULL, or [S*N]: float(l_q); -inf for a dropped or unlisted entry and on streams that are not counted
+ *   hyp_post_dev         NULL, or [S*N]: float(P_q); 0 there
+ *   ref_loss_dev         NULL, or [S]: -log p(ref | y) with the bits of klstm_ctc_eval's utt_loss on a counted stream when ctc_weight > 0,
+ *                        0 otherwise
+ *   totals_dev           NULL, or six doubles that this minibatch is ADDED to, streams in order: sum of R, sum of the cost of entry 0,
+ *                        utterances counted, utterances rejected or skipped, frames counted, sum of the reference losses
+ *   workspace            klstm_ctc_mbr_workspace_bytes(T, S, list_n, max_len, with_ref) bytes, 16-byte aligned: both chains' rows of
+ *                        EVERY entry, 2 * T*S * (list_n + with_ref) * (2 max_len + 1) floats (350 MB at T = 1000, S = 16, 8 entries and
+ *                        the reference, 150 labels), 128 KB per stream for the class map and the per-entry links.  The label capacity
+ *                        (and with it the launch geometry) follows from workspace_bytes.  One call at a time per workspace
+ * An ENTRY IS DROPPED (no contribution) when its length is outside [0, capacity] or above hyp_stride, a label is outside [0, K) or
+ * equals blank, or lens[s] < length + (adjacent equal labels).  An empty labelling is legal.
+ * STATUS of a stream: lens[s] == 0 idle.  REJECTED: lens[s] outside [0, T], nbest_count[s] outside [0, N], or ctc_weight > 0 and the
+ * reference is one klstm_ctc_eval rejects.  SKIPPED: nbest_count[s] == 0, a listed cost < 0, or every entry dropped.  All of them
+ * get zero diff rows and hyp_post 0; padding rows (t >= lens[s]) are written as zero; those rows of net_out are NOT READ.
+ * Bit-identical from run to run and independent of which stream an utterance sits in: no floating-point atomics.
+ * Limits: S <= 32, T * S <= 65535, 2 <= K <= 32768, 1 <= list_n <= 16, max_len <= 1023, hyp_stride >= 1; beyond them KLSTM_ERR_SHAPE /
+ * KLSTM_ERR_ARG and nothing is launched (klstm_ctc_mbr_workspace_bytes answers 0 and leaves the message in klstm_last_error()). */
+size_t klstm_ctc_mbr_workspace_bytes(int T, int S, int list_n, int max_len, int with_ref);
+klstm_status klstm_ctc_mbr_eval(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank, const int *hyp_dev,
+                                int hyp_stride, const int *hyp_len_dev, const int *nbest_count_dev, const int *errors_dev, int list_n,
+                                const int *ref_labels_dev, const int *ref_offsets_dev, float risk_scale, float ctc_weight, float *diff,
+                                int diff_stride, float *risk_dev, float *hyp_logp_dev, float *hyp_post_dev, float *ref_loss_dev,
+                                double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* CTC forced alignment (Viterbi) of whole utterances: the single most probable alignment of the label sequence of stream s to its
  * frames (include/klstm_nnet.hpp class CtcAligner).  Stateless, asynchronous on hip_stream, decided
  * entirely on the device.  net_out, lens_dev, labels_dev / label_offsets_dev and blank exactly as klstm_ctc_eval takes them (row

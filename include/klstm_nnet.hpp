@@ -777,6 +777,10 @@ class CtcLabelLm {
   DeviceBuffer next_, weight_, final_;
 };
 
+// What a CtcBeamDecoder's last Decode left on the device: hypotheses [num_stream][nbest][stride], their lengths [num_stream][nbest],
+// the entries listed per stream, their edit distances [num_stream][nbest] (null when it had no references)
+struct CtcNbestDevice { const int32 *hyp, *hyp_len, *count, *errors; int32 num_stream, nbest, stride; };
+
 class CtcBeamDecoder : private CtcCallBase {
  public:
   explicit CtcBeamDecoder(int32 blank = 0, int32 beam = 16, int32 cands = 8, int32 nbest = 1)
@@ -819,7 +823,7 @@ class CtcBeamDecoder : private CtcCallBase {
                                       lm_->Next(), lm_->Weight(), lm_->Final(), hyp_.As<int32>(), hlen_.As<int32>(), cnt_.As<int32>(),
                                       score_.As<BaseFloat>(), rl, ro, er, tot, ws, need, nullptr));
     }
-    num_stream_ = num_stream; scored_ = scoring;
+    num_stream_ = num_stream; scored_ = scoring; frames_ = T;
     if (!lists) return;
     std::vector<int32> c(num_stream), n((size_t)num_stream * N), h((size_t)rows * N), e((size_t)num_stream * N, -1);
     std::vector<BaseFloat> sc((size_t)num_stream * N);
@@ -858,6 +862,11 @@ class CtcBeamDecoder : private CtcCallBase {
     for (int32 s = 0; s < num_stream_; s++) (*v)[s] = e[(size_t)s * nbest_];
   }
 
+  // the device arrays of the last Decode as klstm_ctc_mbr_eval takes them (CtcMbr::Eval), with the shape they were written for
+  CtcNbestDevice DeviceLists() const {
+    return CtcNbestDevice{hyp_.As<int32>(), hlen_.As<int32>(), cnt_.As<int32>(), scored_ ? err_.As<int32>() : nullptr, num_stream_, nbest_, frames_};
+  }
+
   double TokenErrorRate() const { const double *h = tot_.Read(); return h[0] / h[1]; }          // 1-best edit errors / reference tokens
   double OracleTokenErrorRate() const { const double *h = tot_.Read(); return h[5] / h[1]; }    // the best of each list
   double UtteranceErrorRate() const { const double *h = tot_.Read(); return h[4] / h[3]; }
@@ -876,13 +885,124 @@ class CtcBeamDecoder : private CtcCallBase {
     return oss.str();
   }
  private:
-  int32 beam_, cands_, nbest_;
+  int32 beam_, cands_, nbest_, frames_ = 0;
   bool scored_ = false;
   const CtcLabelLm *lm_ = nullptr;
   PackedLabels refs_;
   DeviceBuffer hyp_, hlen_, cnt_, score_, err_;
   DeviceTotals<6> tot_;
 };
+
+// Minimum expected token error over the n-best lists of a CtcBeamDecoder (klstm_ctc_mbr_eval, klstm.h): the
+// sequence-discriminative objective that follows CTC training.  With P = softmax over a stream's list of risk_scale * log p(h | y)
+// and R = sum P errors, diff is the derivative of R + ctc_weight * (-log p(ref | y)) with respect to the Softmax INPUT, like Ctc's.
+// The six totals stay on the device and are read when somebody asks.
+class CtcMbr : private CtcCallBase {
+ public:
+  // max_hyp_len: the longest labelling the workspace serves (longer list entries are dropped); 0: min(1023, 2 * longest reference + 8)
+  explicit CtcMbr(int32 blank = 0, BaseFloat risk_scale = 1.f, BaseFloat ctc_weight = 0.f, int32 max_hyp_len = 0)
+      : CtcCallBase(blank), risk_scale_(risk_scale), ctc_weight_(ctc_weight), max_hyp_len_(max_hyp_len) {}
+
+  // net_out, lens as Ctc::Eval takes them, and the SAME as the last lists.Decode(net_out, ..., refs, ...) took, which must have had
+  // the references (its edit distances are the costs); refs: one list per stream.  Everything is decided on the device (klstm.h):
+  // dropped entries, idle / rejected / skipped streams get zero diff rows.
+  void Eval(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const CtcBeamDecoder &lists,
+            const std::vector<std::vector<int32> > &refs, DeviceMatrix *diff) {
+    Eval(net_out, num_stream, UploadLens(num_stream, lens), lists, refs, diff);
+  }
+  void Eval(const DeviceMatrix &net_out, int32 num_stream, const int32 *lens_dev, const CtcBeamDecoder &lists,
+            const std::vector<std::vector<int32> > &refs, DeviceMatrix *diff) {
+    const CtcNbestDevice nb = lists.DeviceLists();
+    const int32 T = NumFrames(net_out, num_stream, lens_dev, refs.size(), false), K = net_out.NumCols(), N = nb.nbest;
+    KLSTM_ASSERT(nb.num_stream == num_stream && nb.stride == T && nb.errors);
+    refs_.Upload(refs);
+    const bool with_ref = ctc_weight_ > 0.f;
+    const int32 max_len = max_hyp_len_ > 0 ? max_hyp_len_ : (int32)std::min<size_t>(1023, 2 * refs_.longest + 8);
+    const size_t need = klstm_ctc_mbr_workspace_bytes(T, num_stream, N, max_len, with_ref);
+    void *ws = Workspace(need);
+    risk_.Grow((size_t)num_stream * sizeof(BaseFloat));
+    logp_.Grow((size_t)num_stream * N * sizeof(BaseFloat));
+    diff->Resize(net_out.NumRows(), K, false);
+    MatrixView y = net_out.View(), dv = diff->View();
+    KCheck(klstm_ctc_mbr_eval(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, nb.hyp, nb.stride, nb.hyp_len, nb.count, nb.errors, N, with_ref ? refs_.Labels() : nullptr,
+                              with_ref ? refs_.Offsets() : nullptr, risk_scale_, ctc_weight_, dv.Data(), dv.Stride(), risk_.As<BaseFloat>(),
+                              logp_.As<BaseFloat>(), nullptr, nullptr, tot_.Dev(), ws, need, nullptr));
+    num_stream_ = num_stream; nbest_ = N;
+  }
+  // of the last Eval (each synchronises): the expected errors per stream (0: idle, -1: rejected or skipped); log p(h_q | y) per
+  // stream and list slot, [S][N] (-inf: dropped or not listed)
+  void UttRisk(std::vector<BaseFloat> *v) const { v->assign(num_stream_, 0.f); risk_.Download(v->data(), v->size()); }
+  void HypLogp(std::vector<BaseFloat> *v) const { v->assign((size_t)num_stream_ * nbest_, 0.f); logp_.Download(v->data(), v->size()); }
+  double AvgRisk() const { const double *h = tot_.Read(); return h[0] / h[2]; }                 // expected errors per utterance counted
+  double AvgFirstBestErrors() const { const double *h = tot_.Read(); return h[1] / h[2]; }
+  double NumUtterances() const { return tot_.Read()[2]; }
+  double NumRejectedOrSkipped() const { return tot_.Read()[3]; }
+  double Frames() const { return tot_.Read()[4]; }
+  double AvgRefLoss() const { const double *h = tot_.Read(); return h[5] / h[2]; }
+  std::string Report() const {
+    const double *h = tot_.Read();
+    std::ostringstream oss;
+    oss << "AvgRisk: " << h[0] / h[2] << " expected errors per utterance (1-best: " << h[1] / h[2] << "), reference loss " << h[5] / h[2]
+        << " per utterance, [" << h[2] << " utterances, " << h[4] << " frames, " << h[3] << " rejected or skipped]" << std::endl;
+    return oss.str();
+  }
+ private:
+  BaseFloat risk_scale_, ctc_weight_;
+  int32 max_hyp_len_, nbest_ = 0;
+  PackedLabels refs_;
+  DeviceBuffer risk_, logp_;
+  DeviceTotals<6> tot_;
+};
+
+struct TrainMbrOptions {
+  NnetTrainOptions trn_opts;
+  int32 num_stream = 4, blank = 0, max_frames = 0;       // max_frames 0: 65535 / num_stream
+  bool sort_by_length = true, crossvalidate = false;
+  int32 beam = 16, cands = 8, nbest = 8;                 // the search that makes the lists (CtcBeamDecoder)
+  BaseFloat risk_scale = 1.f, ctc_weight = 0.f;
+  const CtcLabelLm *lm = nullptr;                        // fused into the search; not owned
+  std::vector<BaseFloat> class_weights;                  // empty: none
+  int32 max_hyp_len = 0;                                 // 0: min(1023, 2 * longest reference + 8)
+};
+struct TrainMbrStats {
+  int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
+  double num_rejected = 0, total_frames = 0, seconds = 0, avg_loss = 0, avg_loss_per_frame = 0;     // the reference's CTC loss (0 without ctc_weight)
+  double avg_risk = 0, token_error_rate = 0;             // expected errors per utterance; 1-best token error rate of the lists
+};
+
+// Minimum expected token error training over the model's own n-best lists: Propagate, beam search against the labels, CtcMbr::Eval,
+// Backpropagate (not under crossvalidate).  every_batch (optional) sees each minibatch after the Eval: (batch, net_out, obj_diff,
+// decoder, mbr).
+template <class F>
+inline TrainMbrStats TrainMbrWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const TrainMbrOptions &o, std::string *report,
+                                             F every_batch) {
+  nnet->SetTrainOptions(o.trn_opts);
+  CtcBeamDecoder dec(o.blank, o.beam, o.cands, o.nbest);
+  if (!o.class_weights.empty()) dec.SetClassWeights(o.class_weights);
+  dec.SetLanguageModel(o.lm);
+  CtcMbr mbr(o.blank, o.risk_scale, o.ctc_weight, o.max_hyp_len);
+  DeviceMatrix obj_diff;
+  TrainMbrStats st = ForEachWholeUtteranceBatch<TrainMbrStats>(nnet, utts, o.num_stream, o.sort_by_length, o.max_frames,
+      [&](const UtteranceBatch &b, const DeviceMatrix &nnet_out) {
+        dec.Decode(nnet_out, b.num_stream, b.lens, b.labels, nullptr);
+        mbr.Eval(nnet_out, b.num_stream, b.lens, dec, b.labels, &obj_diff);
+        every_batch(b, nnet_out, obj_diff, dec, mbr);
+        if (!o.crossvalidate) nnet->Backpropagate(obj_diff.View(), nullptr);
+      });
+  st.num_rejected = mbr.NumRejectedOrSkipped();
+  st.total_frames = mbr.Frames();
+  st.avg_loss = mbr.AvgRefLoss();
+  st.avg_loss_per_frame = mbr.Frames() > 0 ? mbr.AvgRefLoss() * mbr.NumUtterances() / mbr.Frames() : 0;
+  st.avg_risk = mbr.AvgRisk();
+  st.token_error_rate = dec.TokenErrorRate();
+  if (report) *report = mbr.Report() + dec.Report();
+  return st;
+}
+inline TrainMbrStats TrainMbrWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const TrainMbrOptions &o,
+                                             std::string *report = nullptr) {
+  return TrainMbrWholeUtterances(nnet, utts, o, report,
+                                 [](const UtteranceBatch &, const DeviceMatrix &, const DeviceMatrix &, const CtcBeamDecoder &, const CtcMbr &) {});
+}
 
 struct DecodeCtcOptions {
   int32 num_stream = 4, blank = 0, max_frames = 0;       // max_frames 0: 65535 / num_stream

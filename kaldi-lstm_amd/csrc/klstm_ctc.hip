@@ -22,15 +22,11 @@
 
 namespace klstm {
 
-constexpr int CTC_DEPTH = 4;           // steps the emission gather runs ahead of the chain
-
 template <int NW, int P>
 __global__ __launch_bounds__(64 * NW) void k_ctc_chain(const float *__restrict__ y, int T, int S, int K, int stride,
                                                        const int *__restrict__ lens, const int *__restrict__ labels,
                                                        const int *__restrict__ loff, int blank, float *__restrict__ utt_loss, CtcWs ws) {
-  constexpr int NT = 64 * NW, CAP = NT * P;
-  __shared__ float row[2][CAP + 4];           // state i at [i + 2]; two cells of CTC_NEG on either side
-  __shared__ float pmax[2][NW];
+  constexpr int NT = 64 * NW;
   __shared__ int sm[2];
   const int s = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
   const int L = loff[s + 1] - loff[s], len = lens[s];
@@ -57,100 +53,9 @@ __global__ __launch_bounds__(64 * NW) void k_ctc_chain(const float *__restrict__
     return;
   }
 
-  const int N = 2 * L + 1;
-  const int sgn = dir ? 1 : -1;                // neighbours i + sgn, i + 2 sgn
-  const float *yp[P];
-  bool act[P], allow2[P];
-  float w[P], base0[P];
-#pragma unroll
-  for (int k = 0; k < P; k++) {
-    const int i = tid + k * NT;
-    act[k] = i < N;
-    const int cls = (act[k] && (i & 1)) ? lab[i >> 1] : blank;
-    yp[k] = y + (size_t)s * stride + cls;
-    const int j = dir ? i + 2 : i;             // the state a skip would arrive at
-    allow2[k] = act[k] && (j & 1) && j >= 3 && j < N && lab[j >> 1] != lab[(j >> 1) - 1];
-    base0[k] = !act[k] ? CTC_NEG : dir ? (i >= N - 2 ? 0.f : CTC_NEG) : (i <= 1 ? 0.f : CTC_NEG);
-    w[k] = CTC_NEG;
-  }
-  if (tid < 2) {
-    row[0][tid] = CTC_NEG; row[1][tid] = CTC_NEG;
-    row[0][CAP + 2 + tid] = CTC_NEG; row[1][CAP + 2 + tid] = CTC_NEG;
-  }
-  const size_t tstride = (size_t)S * stride;
   float *gout = (dir ? ws.B : ws.A) + (size_t)s * T * ws.Npad;
-
-  float en[CTC_DEPTH][P];
-#pragma unroll
-  for (int d = 0; d < CTC_DEPTH; d++)
-#pragma unroll
-    for (int k = 0; k < P; k++) en[d][k] = d < len ? yp[k][(size_t)(dir ? len - 1 - d : d) * tstride] : 1.f;
-
-  double csum = 0.0;                           // sum of the offsets taken out so far (the loss needs it; alpha only)
-  float M = 0.f;
-  for (int u0 = 0; u0 < len; u0 += CTC_DEPTH) {
-    float ec[CTC_DEPTH][P];
-#pragma unroll
-    for (int d = 0; d < CTC_DEPTH; d++)
-#pragma unroll
-      for (int k = 0; k < P; k++) {
-        ec[d][k] = en[d][k];
-        const int un = u0 + CTC_DEPTH + d;
-        en[d][k] = un < len ? yp[k][(size_t)(dir ? len - 1 - un : un) * tstride] : 1.f;
-      }
-#pragma unroll
-    for (int d = 0; d < CTC_DEPTH; d++) {
-      const int u = u0 + d;
-      if (u >= len) break;
-      const int b = u & 1, tt = dir ? len - 1 - u : u;
-      float lmax = CTC_NEG;
-      if (u > 0) csum += (double)M;
-#pragma unroll
-      for (int k = 0; k < P; k++) {
-        const int i = tid + k * NT;
-        float base = base0[k];
-        if (u > 0) {
-          const float x0 = w[k], x1 = row[b ^ 1][i + 2 + sgn];
-          const float x2 = allow2[k] ? row[b ^ 1][i + 2 + 2 * sgn] : CTC_NEG;
-          const float m = fmaxf(x0, fmaxf(x1, x2));
-          base = m + __logf(__expf(x0 - m) + __expf(x1 - m) + __expf(x2 - m)) - M;
-        }
-        const float em = logf(fmaxf(ec[d][k], FLT_MIN));    // off the chain: the accurate one
-        const float wk = act[k] ? base + em : CTC_NEG;
-        if (act[k]) gout[(size_t)tt * ws.Npad + i] = dir ? base : wk;
-        w[k] = wk;
-        lmax = fmaxf(lmax, wk);
-      }
-#pragma unroll
-      for (int k = 0; k < P; k++) row[b][tid + k * NT + 2] = w[k];
-      lmax = wave_max(lmax);
-      if (NW > 1) {
-        if ((tid & 63) == 0) pmax[b][tid >> 6] = lmax;
-      }
-      __syncthreads();
-      if (NW > 1) {
-        lmax = pmax[b][0];
-#pragma unroll
-        for (int q = 1; q < NW; q++) lmax = fmaxf(lmax, pmax[b][q]);
-      }
-      M = lmax;
-    }
-  }
-  if (dir == 0 && tid == 0) {
-    const int b = (len - 1) & 1;
-    const float a1 = row[b][N - 1 + 2], a2 = N > 1 ? row[b][N - 2 + 2] : CTC_NEG;
-    const float m = fmaxf(a1, a2);
-    const float tail = m + logf(expf(a1 - m) + expf(a2 - m));
-    utt_loss[s] = (float)(-(csum + (double)tail));
-  }
-}
-
-__device__ __forceinline__ float ctc_block_reduce(float v, float *sm, bool is_max) {     // 256 threads, fixed tree
-  for (int o = 32; o > 0; o >>= 1) { const float x = __shfl_xor(v, o); v = is_max ? fmaxf(v, x) : v + x; }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return is_max ? fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])) : (sm[0] + sm[1]) + (sm[2] + sm[3]);
+  const double lp = ctc_chain_run<NW, P>(y + (size_t)s * stride, (size_t)S * stride, len, lab, L, blank, dir, gout, ws.Npad);
+  if (dir == 0 && tid == 0) utt_loss[s] = (float)(-lp);
 }
 
 __global__ __launch_bounds__(256) void k_ctc_combine(const float *__restrict__ y, int T, int S, int K, int stride,

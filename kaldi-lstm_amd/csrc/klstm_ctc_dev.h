@@ -1,9 +1,11 @@
 // kaldi-lstm_amd/csrc/klstm_ctc_dev.h -- device code shared by the CTC kernels (klstm_ctc.hip: the loss; klstm_ctc_align.hip: the forced
-// alignment; klstm_ctc_decode.hip: best path; klstm_ctc_beam.hip: prefix beam search): the status of an utterance, the maximum over a
-// wave, (value, index) reductions, the row reader and the one-wave Levenshtein distance.
+// alignment; klstm_ctc_decode.hip: best path; klstm_ctc_beam.hip: prefix beam search; klstm_ctc_mbr.hip: the n-best risk): the status of
+// an utterance, the maximum over a wave, the fixed-tree reduction over a workgroup, (value, index) reductions, the row reader, the
+// one-wave Levenshtein distance and the alpha / beta chain of the loss (ctc_chain_run).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -48,6 +50,15 @@ __device__ __forceinline__ float wave_max(float v) {
   v = dpp_max<0x142, 0xa>(v);      // row_bcast:15 into rows 1 and 3
   v = dpp_max<0x143, 0xc>(v);      // row_bcast:31 into rows 2 and 3: lane 63 holds the maximum of the wave
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+// Maximum or sum over a workgroup of 256 threads by a fixed tree, the same value in every thread; sm: 4 floats of LDS.
+__device__ __forceinline__ float ctc_block_reduce(float v, float *sm, bool is_max) {
+  for (int o = 32; o > 0; o >>= 1) { const float x = __shfl_xor(v, o); v = is_max ? fmaxf(v, x) : v + x; }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return is_max ? fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])) : (sm[0] + sm[1]) + (sm[2] + sm[3]);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -183,6 +194,111 @@ __device__ int edit_distance(const int *__restrict__ fclass, int S, int s, int l
 #pragma unroll
   for (int e = 0; e < P; e++) if (lane * P + e == L) out = prev[e];
   return __shfl(out, L / P);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// One chain of the CTC lattice of `lab[0 .. L)` over the `len` frames of one stream, by the whole workgroup of 64 NW threads with P
+// states per thread: dir 0 alpha (forwards, the frame's emission included), dir 1 beta (backwards, without it).  ys:
+// the stream's row 0 of the posteriors, tstride: elements between its frames.  The normalised row of frame t goes to gout[t * Npad +
+// state].  Returns log p(lab | y) = the offsets summed in double plus the last row's tail (valid on thread 0 of an alpha chain).  The
+// caller has established that the labelling is feasible (ctc_status 1) and that 2 L + 1 <= 64 NW P.  Shared by klstm_ctc.hip (the loss)
+// and klstm_ctc_mbr.hip (the n-best risk), whose log probabilities therefore carry the same bits.
+// ------------------------------------------------------------------------------------------------------------------------------------
+constexpr int CTC_DEPTH = 4;           // steps the emission gather runs ahead of the chain
+
+template <int NW, int P>
+__device__ __forceinline__ double ctc_chain_run(const float *__restrict__ ys, size_t tstride, int len, const int *__restrict__ lab, int L,
+                                                int blank, int dir, float *__restrict__ gout, int Npad) {
+  constexpr int NT = 64 * NW, CAP = NT * P;
+  __shared__ float row[2][CAP + 4];           // state i at [i + 2]; two cells of CTC_NEG on either side
+  __shared__ float pmax[2][NW];
+  const int tid = threadIdx.x;
+  const int N = 2 * L + 1;
+  const int sgn = dir ? 1 : -1;                // neighbours i + sgn, i + 2 sgn
+  const float *yp[P];
+  bool act[P], allow2[P];
+  float w[P], base0[P];
+#pragma unroll
+  for (int k = 0; k < P; k++) {
+    const int i = tid + k * NT;
+    act[k] = i < N;
+    const int cls = (act[k] && (i & 1)) ? lab[i >> 1] : blank;
+    yp[k] = ys + cls;
+    const int j = dir ? i + 2 : i;             // the state a skip would arrive at
+    allow2[k] = act[k] && (j & 1) && j >= 3 && j < N && lab[j >> 1] != lab[(j >> 1) - 1];
+    base0[k] = !act[k] ? CTC_NEG : dir ? (i >= N - 2 ? 0.f : CTC_NEG) : (i <= 1 ? 0.f : CTC_NEG);
+    w[k] = CTC_NEG;
+  }
+  if (tid < 2) {
+    row[0][tid] = CTC_NEG; row[1][tid] = CTC_NEG;
+    row[0][CAP + 2 + tid] = CTC_NEG; row[1][CAP + 2 + tid] = CTC_NEG;
+  }
+
+  float en[CTC_DEPTH][P];
+#pragma unroll
+  for (int d = 0; d < CTC_DEPTH; d++)
+#pragma unroll
+    for (int k = 0; k < P; k++) en[d][k] = d < len ? yp[k][(size_t)(dir ? len - 1 - d : d) * tstride] : 1.f;
+
+  double csum = 0.0;                           // sum of the offsets taken out so far (the loss needs it; alpha only)
+  float M = 0.f;
+  for (int u0 = 0; u0 < len; u0 += CTC_DEPTH) {
+    float ec[CTC_DEPTH][P];
+#pragma unroll
+    for (int d = 0; d < CTC_DEPTH; d++)
+#pragma unroll
+      for (int k = 0; k < P; k++) {
+        ec[d][k] = en[d][k];
+        const int un = u0 + CTC_DEPTH + d;
+        en[d][k] = un < len ? yp[k][(size_t)(dir ? len - 1 - un : un) * tstride] : 1.f;
+      }
+#pragma unroll
+    for (int d = 0; d < CTC_DEPTH; d++) {
+      const int u = u0 + d;
+      if (u >= len) break;
+      const int b = u & 1, tt = dir ? len - 1 - u : u;
+      float lmax = CTC_NEG;
+      if (u > 0) csum += (double)M;
+#pragma unroll
+      for (int k = 0; k < P; k++) {
+        const int i = tid + k * NT;
+        float base = base0[k];
+        if (u > 0) {
+          const float x0 = w[k], x1 = row[b ^ 1][i + 2 + sgn];
+          const float x2 = allow2[k] ? row[b ^ 1][i + 2 + 2 * sgn] : CTC_NEG;
+          const float m = fmaxf(x0, fmaxf(x1, x2));
+          base = m + __logf(__expf(x0 - m) + __expf(x1 - m) + __expf(x2 - m)) - M;
+        }
+        const float em = logf(fmaxf(ec[d][k], FLT_MIN));    // off the chain: the accurate one
+        const float wk = act[k] ? base + em : CTC_NEG;
+        if (act[k]) gout[(size_t)tt * Npad + i] = dir ? base : wk;
+        w[k] = wk;
+        lmax = fmaxf(lmax, wk);
+      }
+#pragma unroll
+      for (int k = 0; k < P; k++) row[b][tid + k * NT + 2] = w[k];
+      lmax = wave_max(lmax);
+      if (NW > 1) {
+        if ((tid & 63) == 0) pmax[b][tid >> 6] = lmax;
+      }
+      __syncthreads();
+      if (NW > 1) {
+        lmax = pmax[b][0];
+#pragma unroll
+        for (int q = 1; q < NW; q++) lmax = fmaxf(lmax, pmax[b][q]);
+      }
+      M = lmax;
+    }
+  }
+  double lp = 0.0;
+  if (dir == 0 && tid == 0) {
+    const int b = (len - 1) & 1;
+    const float a1 = row[b][N - 1 + 2], a2 = N > 1 ? row[b][N - 2 + 2] : CTC_NEG;
+    const float m = fmaxf(a1, a2);
+    const float tail = m + logf(expf(a1 - m) + expf(a2 - m));
+    lp = csum + (double)tail;
+  }
+  return lp;
 }
 
 }  // namespace klstm

@@ -2161,6 +2161,44 @@ int klstm_ctc_beam_lm_resident(int lm_states, int K, int beam, int cands) {
   if (lm_states < 1 || K < 2 || (long)lm_states * K > (1L << 24)) return 0;
   return ctc_beam_lm_resident(lm_states, K, beam, cands) ? 1 : 0;
 }
+static bool ctc_mbr_shape_ok(int T, int S, int list_n, int max_len) {
+  return T > 0 && S > 0 && S <= 32 && (long)T * S <= 65535 && list_n >= 1 && list_n <= 16 && max_len >= 0 && max_len <= 1023;
+}
+size_t klstm_ctc_mbr_workspace_bytes(int T, int S, int list_n, int max_len, int with_ref) {
+  if (!ctc_mbr_shape_ok(T, S, list_n, max_len)) {
+    fail(KLSTM_ERR_SHAPE, "klstm_ctc_mbr_workspace_bytes: T %d, streams %d, list of %d, labelling length %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, 1 <= list <= 16, L <= 1023", T, S, list_n, max_len);
+    return 0;
+  }
+  return ctc_mbr_workspace_bytes(T, S, list_n, max_len, with_ref != 0);
+}
+klstm_status klstm_ctc_mbr_eval(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank, const int *hyp_dev,
+                                int hyp_stride, const int *hyp_len_dev, const int *nbest_count_dev, const int *errors_dev, int list_n,
+                                const int *ref_labels_dev, const int *ref_offsets_dev, float risk_scale, float ctc_weight, float *diff,
+                                int diff_stride, float *risk_dev, float *hyp_logp_dev, float *hyp_post_dev, float *ref_loss_dev,
+                                double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  const char *fn = "klstm_ctc_mbr_eval";
+  if (T <= 0 || S <= 0 || K <= 0 || list_n <= 0 || hyp_stride <= 0)
+    return fail(KLSTM_ERR_ARG, "%s: bad size (T %d, streams %d, K %d, list of %d, hypothesis stride %d)", fn, T, S, K, list_n, hyp_stride);
+  if (list_n > 16) return fail(KLSTM_ERR_SHAPE, "%s: list of %d outside 1 <= list <= 16", fn, list_n);
+  if (!(risk_scale > 0.f) || !std::isfinite(risk_scale)) return fail(KLSTM_ERR_ARG, "%s: risk scale %g is not a finite number above 0", fn, (double)risk_scale);
+  if (!(ctc_weight >= 0.f) || !std::isfinite(ctc_weight)) return fail(KLSTM_ERR_ARG, "%s: CTC weight %g is not a finite number >= 0", fn, (double)ctc_weight);
+  const bool with_ref = ctc_weight > 0.f;
+  const char *pointers = nullptr;
+  if ((ref_labels_dev == nullptr) != (ref_offsets_dev == nullptr)) pointers = "reference labels and offsets come together or not at all";
+  else if ((ref_labels_dev != nullptr) != with_ref) pointers = "the reference is given exactly when the CTC weight is above 0";
+  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !nbest_count_dev || !errors_dev || !diff || !risk_dev || !workspace) pointers = "null argument";
+  const klstm_status st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride < diff_stride ? stride : diff_stride,
+                                         net_out == diff ? "diff == net_out (the posteriors are read while diff is written)" : nullptr, workspace);
+  if (st != KLSTM_OK) return st;
+  const int lcap = ctc_mbr_label_capacity(T, S, list_n, with_ref, workspace_bytes);
+  if (lcap < 0)
+    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_mbr_workspace_bytes(%d, %d, %d, 0, %d) = %zu", fn, workspace_bytes, T, S,
+                list_n, (int)with_ref, ctc_mbr_workspace_bytes(T, S, list_n, 0, with_ref));
+  HIPCHK(launch_ctc_mbr(net_out, T, S, K, stride, lens_dev, blank, hyp_dev, hyp_stride, hyp_len_dev, nbest_count_dev, errors_dev, list_n,
+                        ref_labels_dev, ref_offsets_dev, risk_scale, ctc_weight, diff, diff_stride, risk_dev, hyp_logp_dev, hyp_post_dev,
+                        ref_loss_dev, totals_dev, workspace, lcap, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
 size_t klstm_ctc_align_workspace_bytes(int T, int S, int max_label_len) {
   return ctc_query_ok("klstm_ctc_align_workspace_bytes", "label", T, S, max_label_len) ? ctc_align_workspace_bytes(T, S, max_label_len) : 0;
 }

@@ -343,6 +343,15 @@ bool ctc_beam_lm_resident(int Q, int K, int B, int C);
 hipError_t launch_ctc_beam_lm(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
                               int Q, const int *lm_next, const float *lm_weight, const float *lm_final, int *hyp, int *hyp_len, int *count,
                               float *score, const int *refs, const int *roff, int *errors, double *totals, void *workspace, hipStream_t st);
+// Minimum expected token error over CTC n-best lists (klstm_ctc_mbr.hip): klstm_ctc_mbr_eval / klstm_ctc_mbr_workspace_bytes of
+// include/klstm.h.  N list slots per stream, with_ref: one more entry for the reference.  The workspace: statuses, weights, links and
+// accumulator slots per entry, a class map per stream, then the alpha and the beta rows of every entry [S][E][T][Npad].
+size_t ctc_mbr_workspace_bytes(int T, int S, int N, int Lcap, int with_ref);
+int ctc_mbr_label_capacity(int T, int S, int N, int with_ref, size_t bytes);
+hipError_t launch_ctc_mbr(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const int *hyp, int hyp_stride,
+                          const int *hyp_len, const int *count, const int *errors, int N, const int *ref, const int *roff, float kappa,
+                          float lam, float *diff, int dstride, float *risk, float *hyp_logp, float *hyp_post, float *ref_loss,
+                          double *totals, void *workspace, int Lcap, hipStream_t st);
 // CTC forced alignment (klstm_ctc_align.hip): klstm_ctc_align / klstm_ctc_align_workspace_bytes of include/klstm.h.  The workspace: four
 // ints per stream for the totals, then per stream, frame and group of 32 lattice states two words of back-pointer bits.  Lcap = the
 // label length the workspace was sized for (the chain's geometry follows from it).

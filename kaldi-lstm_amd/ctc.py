@@ -3,7 +3,8 @@ CUDA tensors.  Plumbing only: the label lists become the CSR arrays of the C-ABI
 ctc_greedy_decode: best-path decoding and token error rate of the same posteriors (klstm_ctc_decode).
 ctc_align: the most probable alignment of given label sequences to the frames (klstm_ctc_align).
 ctc_beam_decode: prefix beam search, n-best lists with scores and edit distances (klstm_ctc_beam_decode), with
-lm=CtcLabelLm(...) fused with a label language model or a lexicon (klstm_ctc_beam_decode_lm; tables: lm.py)."""
+lm=CtcLabelLm(...) fused with a label language model or a lexicon (klstm_ctc_beam_decode_lm; tables: lm.py).
+ctc_mbr_eval: the expected token errors over such n-best lists and their gradient (klstm_ctc_mbr_eval)."""
 import collections
 import ctypes
 
@@ -287,3 +288,58 @@ def nbest_to_lists(result):
     er = result.errors.cpu().numpy() if result.errors is not None else None
     return [[(h[s, q, :n[s, q]].tolist(), float(sc[s, q]), int(er[s, q]) if er is not None else None) for q in range(c[s])]
             for s in range(len(c))]
+
+
+CtcMbrResult = collections.namedtuple("CtcMbrResult", "risk diff hyp_logp hyp_post ref_loss")
+
+
+def ctc_mbr_workspace_bytes(T, S, list_n, max_len, with_ref=False):
+    return _workspace_bytes("klstm_ctc_mbr_workspace_bytes", T, S, list_n, max_len, 1 if with_ref else 0)
+
+
+def ctc_mbr_eval(net_out, lens, nbest, refs=None, blank=0, risk_scale=1.0, ctc_weight=0.0, max_len=None, diff=None, totals=None, stream=None):
+    """Minimum expected token error over n-best lists: net_out, lens as ctc_eval takes them; nbest: the CtcBeamResult of ctc_beam_decode
+    on the same posteriors (decoded with refs, so that it carries the edit distances), or a tuple (hyp [S, N, stride] int32, hyp_len
+    [S, N], nbest_count [S], errors [S, N]) of int32 CUDA tensors; refs: the reference labels (a list, or what pack_labels() returned),
+    needed exactly when ctc_weight > 0.  With P = softmax over the list of risk_scale * log p(h_q | y) and R = sum_q P_q errors_q:
+    diff = the gradient of R + ctc_weight * (-log p(ref | y)) with respect to the softmax input.  max_len: the label capacity the
+    workspace is sized for (an entry longer than the capacity that follows from the workspace's size, max_len or a label or two more, is
+    dropped; the workspace grows with it: pass it.  None: min(1023, 2 * longest reference + 8)
+    with refs, else min(1023, the hypothesis stride), which no entry exceeds).  Returns
+    CtcMbrResult(risk [S] float32 (0 idle, -1 rejected or skipped), diff [T*S, K], hyp_logp [S, N] float32 (-inf: dropped), hyp_post
+    [S, N] float32, ref_loss [S] float32 or None).  totals: a float64[6] CUDA tensor that sum of R, sum of the 1-best's errors,
+    utterances counted, utterances rejected or skipped, frames and sum of the reference losses are added to.  Nothing synchronises."""
+    import torch
+    lib = load_library()
+    dev = net_out.device
+    lens_dev, S, T, K = _shape(net_out, lens)
+    hyp, hyp_len, count, errors = (nbest.hyp, nbest.hyp_len, nbest.nbest_count, nbest.errors) if isinstance(nbest, CtcBeamResult) else nbest
+    assert errors is not None, "the n-best lists carry no edit distances (decode with refs)"
+    for t in (hyp, hyp_len, count, errors):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    assert hyp.dim() == 3 and hyp.shape[0] == S and count.numel() == S
+    N, hyp_stride = int(hyp.shape[1]), int(hyp.shape[2])
+    assert hyp_len.shape == (S, N) and errors.shape == (S, N)
+    with_ref = float(ctc_weight) > 0
+    lab_dev = off_dev = ref_loss = None
+    longest = 0
+    if with_ref:
+        assert refs is not None, "ctc_weight > 0 needs refs"
+        lab_dev, off_dev, longest = _packed(refs, S, dev)
+        ref_loss = torch.empty(S, device=dev)
+    if max_len is None:
+        max_len = min(1023, 2 * longest + 8 if with_ref else hyp_stride)
+    if diff is None:
+        diff = torch.empty(T * S, K, device=dev)
+    assert diff.is_cuda and diff.dtype == torch.float32 and diff.shape == (T * S, K) and diff.stride(1) == 1
+    _check_totals(totals, 6)
+    nbytes = ctc_mbr_workspace_bytes(T, S, N, max_len, with_ref)
+    ws = _workspace("mbr", (T, S, N, max_len, with_ref), nbytes, dev)
+    risk = torch.empty(S, device=dev)
+    hyp_logp = torch.empty(S, N, device=dev)
+    hyp_post = torch.empty(S, N, device=dev)
+    _chk(lib.klstm_ctc_mbr_eval(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), hyp.data_ptr(), hyp_stride,
+                                hyp_len.data_ptr(), count.data_ptr(), errors.data_ptr(), N, _ptr(lab_dev), _ptr(off_dev), float(risk_scale),
+                                float(ctc_weight), diff.data_ptr(), diff.stride(0), risk.data_ptr(), hyp_logp.data_ptr(), hyp_post.data_ptr(),
+                                _ptr(ref_loss), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    return CtcMbrResult(risk, diff, hyp_logp, hyp_post, ref_loss)
