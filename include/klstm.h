@@ -479,6 +479,56 @@ klstm_status klstm_ctc_beam_decode_lm(const float *net_out, int T, int S, int K,
                                       int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
 int klstm_ctc_beam_lm_resident(int lm_states, int K, int beam, int cands);
 
+/* STREAMING CTC prefix beam search: the search of klstm_ctc_beam_decode / _lm fed chunk by chunk, with the beam carried across the
+ * calls in device memory the caller owns (include/klstm_nnet.hpp class CtcStreamDecoder; include/klstm_scorer.hpp DecodeCtcStreaming;
+ * INTEGRATION.md 3j; the definition is tests/ctc_beam_stream_ref.py).  The calls themselves are stateless and
+ * asynchronous on hip_stream; everything is decided on the device.
+ * klstm_ctc_beam_stream_step consumes lens_dev[s] frames of stream s from net_out (rows t * S + s, t < T; stride, blank,
+ * class_weight_dev, beam, cands and the language-model tables as the whole-utterance calls take them; lm_states 0: no LM):
+ *   lens_dev [S]         the frames of THIS chunk: 0 is idle (its state is not read, not written and not reset, even with start set),
+ *                        a value outside [0, T] is rejected and treated as idle.  Rows t >= lens[s] are NOT READ
+ *   start_dev            NULL (no stream starts), or [S]: nonzero begins a new utterance in stream s with this chunk.  State that no
+ *                        step has ever started counts as started at its first non-idle step: zero-filled state is a valid "nothing yet"
+ *   state                klstm_ctc_beam_stream_state_bytes(max_frames, S, beam) bytes, 16-byte aligned, zero-filled before the first
+ *                        step, the SAME max_frames, S and beam in every call on it.  Per stream, 256-byte aligned: a header of 16
+ *                        ints (started, frames consumed, beam entries, exponent, overflow flag), 64 beam entries (hash and parent
+ *                        hash, node, last token, length, LM state, pb, pnb: 2.5 KB), then the prefix tree at 8 bytes per frame and
+ *                        beam entry (parent and token of node 1 + frame * beam + slot; node 0 is the empty prefix)
+ *   OVERFLOW             a stream with frames + lens[s] > max_frames is rejected for this call: its state is unchanged but for a
+ *                        sticky flag in the header, which the next start clears.  Never a fault, never a partial write
+ *   workspace            klstm_ctc_beam_stream_workspace_bytes(T, S, cands, nbest) bytes, 16-byte aligned: 1.5 KB and 8 bytes per row
+ *                        and candidate.  One call at a time per workspace; step and emit may share it
+ * klstm_ctc_beam_stream_emit writes the current n-best lists.  It modifies nothing in the state, so it may be called between any two
+ * steps, any number of times.  hyp_dev / hyp_len_dev / nbest_count_dev / score_dev / the references / errors_dev / totals_dev as
+ * klstm_ctc_beam_decode, with hyp_stride >= max_frames in the place of T:
+ *   mode_dev [S]         0: skip (the list outputs of the stream are left alone, nbest_count 0); 1: the list without the LM's final
+ *                        weights; 2: the list with them (lm_final_dev, may be NULL), ranked as klstm_ctc_beam_decode_lm ranks it.
+ *                        Edit distances and totals cover the streams emitted with mode 2; every other stream has errors -1
+ *   frames_dev           NULL, or [S]: frames consumed so far; -1 - frames once a step was rejected for overflow
+ *   stable_len_dev       NULL, or [S] (modes 1 and 2): the length of the longest common prefix, token by token, of all beam entries
+ *                        with a total > 0 (a DEAD beam: the first entry's length).  Every hypothesis the utterance can list from now
+ *                        on begins with the first stable_len tokens of today's 1-best: they can no longer change
+ *   workspace            at least klstm_ctc_beam_stream_workspace_bytes(1, S, 1, nbest) bytes
+ * THE CONTRACT.  For any split of an utterance into chunks, and whatever the other streams do meanwhile, emit with mode 2 (mode 1:
+ * without final weights) after the last frame writes what klstm_ctc_beam_decode / _lm write for the whole utterance with the same
+ * parameters, and after n frames what that call writes for its first n frames: hypotheses, lengths, counts, the bits of the scores,
+ * edit distances and the six totals.  A resumed search has no rounding of its own.
+ * Limits: S <= 32 and T * S <= 65535 per call; K, beam, cands, nbest and the LM as the whole-utterance calls; 1 <= max_frames,
+ * max_frames * beam + 1 < 2^31, hyp_stride >= max_frames; beyond them KLSTM_ERR_SHAPE and nothing is launched (the size queries
+ * answer 0 and leave the message in klstm_last_error()).  Null required pointers, a state or a workspace that is too small or
+ * misaligned: KLSTM_ERR_ARG. */
+size_t klstm_ctc_beam_stream_state_bytes(int max_frames, int S, int beam);
+size_t klstm_ctc_beam_stream_workspace_bytes(int T, int S, int cands, int nbest);
+klstm_status klstm_ctc_beam_stream_step(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *start_dev,
+                                        int blank, const float *class_weight_dev, int beam, int cands, int lm_states,
+                                        const int *lm_next_dev, const float *lm_weight_dev, void *state, size_t state_bytes, int max_frames,
+                                        void *workspace, size_t workspace_bytes, void *hip_stream);
+klstm_status klstm_ctc_beam_stream_emit(int S, int K, int blank, int beam, int nbest, const int *mode_dev, int lm_states,
+                                        const float *lm_final_dev, const void *state, size_t state_bytes, int max_frames, int *hyp_dev,
+                                        int hyp_stride, int *hyp_len_dev, int *nbest_count_dev, float *score_dev, int *frames_dev,
+                                        int *stable_len_dev, const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev,
+                                        double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Minimum expected token error over CTC n-best lists (MWER / minimum Bayes risk over n-best; include/klstm_nnet.hpp class CtcMbr;
  * INTEGRATION.md 3i): the sequence-discriminative objective that follows CTC training, on the lists and edit distances
  * klstm_ctc_beam_decode wrote.  Stateless, asynchronous on hip_stream, decided entirely on the device.  net_out, stride, lens_dev,

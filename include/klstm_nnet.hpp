@@ -893,6 +893,126 @@ class CtcBeamDecoder : private CtcCallBase {
   DeviceTotals<6> tot_;
 };
 
+// The prefix beam search fed chunk by chunk (klstm_ctc_beam_stream_step / _emit, klstm.h): num_stream searches whose
+// beams live on the device between the calls, for utterances of at most max_frames frames.  Step consumes a chunk of posteriors where
+// the scorer leaves it (include/klstm_scorer.hpp BatchScorer::ForEachChunk); Emit reads the current n-best lists and changes nothing,
+// so partial results cost one small launch.  For any chunking the lists are CtcBeamDecoder's on the frames consumed so far, bit for
+// bit.  The six totals cover the streams emitted with mode 2 and references; they stay on the device and are read when somebody asks.
+class CtcStreamDecoder : private CtcCallBase {
+ public:
+  CtcStreamDecoder(int32 blank, int32 beam, int32 cands, int32 nbest, int32 num_stream, int32 max_frames)
+      : CtcCallBase(blank), beam_(beam), cands_(cands), nbest_(nbest), max_frames_(max_frames) {
+    num_stream_ = num_stream;
+    KLSTM_ASSERT(nbest >= 1);
+    state_bytes_ = klstm_ctc_beam_stream_state_bytes(max_frames, num_stream, beam);      // host only: a refused shape needs no GPU
+    if (state_bytes_ == 0) KLSTM_ERR("klstm: " << klstm_last_error());
+  }
+  using CtcCallBase::SetClassWeights;
+  void SetLanguageModel(const CtcLabelLm *lm) { lm_ = lm; }         // the decoder keeps the pointer, not the tables; null: none
+  int32 NumStream() const { return num_stream_; }
+  int32 MaxFrames() const { return max_frames_; }
+
+  // chunk [T*num_stream x K], rows t * num_stream + s; lens[s]: the frames of THIS chunk for stream s (0: idle, its state is not
+  // touched); start[s] != 0: a new utterance begins in stream s with this chunk (empty: no stream starts).  A stream whose utterance
+  // would pass max_frames is rejected for the call and Emit reports frames = -1 - frames.  Asynchronous.
+  void Step(const DeviceMatrix &chunk, const std::vector<int32> &lens, const std::vector<int32> &start) {
+    const int32 S = num_stream_;
+    KLSTM_ASSERT(start.empty() || (int32)start.size() == S);
+    const int32 *lens_dev = UploadLens(S, lens);
+    const int32 T = NumFrames(chunk, S, lens_dev, 0, true), K = chunk.NumCols();
+    KLSTM_ASSERT(!lm_ || lm_->NumClasses() == K);
+    if (!start.empty()) start_.Upload(start);
+    const size_t need = klstm_ctc_beam_stream_workspace_bytes(T, S, cands_, nbest_);
+    void *ws = Workspace(need);
+    MatrixView y = chunk.View();
+    KCheck(klstm_ctc_beam_stream_step(y.Data(), T, S, K, y.Stride(), lens_dev, start.empty() ? nullptr : start_.As<int32>(), blank_, Weights(),
+                                      beam_, cands_, lm_ ? lm_->NumStates() : 0, lm_ ? lm_->Next() : nullptr, lm_ ? lm_->Weight() : nullptr,
+                                      State(), state_bytes_, max_frames_, ws, need, nullptr));
+    classes_ = K;
+  }
+  // mode[s]: 0 skip stream s, 1 its list without the language model's final weights, 2 with them (the list CtcBeamDecoder makes).
+  // refs: empty, or one reference per stream (those of the streams emitted with mode 2 are counted).  lists / frames / stable_len
+  // (each optional; asking synchronises): per stream the n-best list (empty where skipped), the frames consumed (-1 - frames after
+  // an overflow) and the number of leading tokens of the 1-best that can no longer change.  Changes nothing in the state.
+  void Emit(const std::vector<int32> &mode, const std::vector<std::vector<int32> > &refs, std::vector<CtcNbestList> *lists,
+            std::vector<int32> *frames, std::vector<int32> *stable_len) {
+    const int32 S = num_stream_, N = nbest_;
+    KLSTM_ASSERT((int32)mode.size() == S && (refs.empty() || (int32)refs.size() == S));
+    if (classes_ == 0) KLSTM_ERR("CtcStreamDecoder::Emit before the first Step");
+    const bool scoring = !refs.empty();
+    mode_.Upload(mode);
+    const size_t need = klstm_ctc_beam_stream_workspace_bytes(1, S, 1, N);
+    void *ws = Workspace(need);
+    hyp_.Grow((size_t)S * N * max_frames_ * sizeof(int32));
+    hlen_.Grow((size_t)S * N * sizeof(int32));
+    cnt_.Grow((size_t)S * sizeof(int32));
+    score_.Grow((size_t)S * N * sizeof(BaseFloat));
+    err_.Grow((size_t)S * N * sizeof(int32));
+    fr_.Grow((size_t)S * sizeof(int32));
+    stab_.Grow((size_t)S * sizeof(int32));
+    KCheck(klstm_memset_zero(stab_.As<int32>(), (size_t)S * sizeof(int32), nullptr));     // a skipped stream's is not written
+    if (scoring) refs_.Upload(refs);
+    KCheck(klstm_ctc_beam_stream_emit(S, classes_, blank_, beam_, N, mode_.As<int32>(), lm_ ? lm_->NumStates() : 0, lm_ ? lm_->Final() : nullptr,
+                                      State(), state_bytes_, max_frames_, hyp_.As<int32>(), max_frames_, hlen_.As<int32>(), cnt_.As<int32>(),
+                                      score_.As<BaseFloat>(), fr_.As<int32>(), stab_.As<int32>(), scoring ? refs_.Labels() : nullptr,
+                                      scoring ? refs_.Offsets() : nullptr, scoring ? err_.As<int32>() : nullptr,
+                                      scoring ? tot_.Dev() : nullptr, ws, need, nullptr));
+    if (frames) { frames->assign(S, 0); fr_.Download(frames->data(), frames->size()); }
+    if (stable_len) { stable_len->assign(S, 0); stab_.Download(stable_len->data(), stable_len->size()); }
+    if (!lists) return;
+    std::vector<int32> c(S), n((size_t)S * N), e((size_t)S * N, -1), h((size_t)S * N * max_frames_);
+    std::vector<BaseFloat> sc((size_t)S * N);
+    cnt_.Download(c.data(), c.size());
+    hlen_.Download(n.data(), n.size());
+    hyp_.Download(h.data(), h.size());
+    score_.Download(sc.data(), sc.size());
+    if (scoring) err_.Download(e.data(), e.size());
+    lists->assign(S, CtcNbestList());
+    for (int32 s = 0; s < S; s++)
+      for (int32 q = 0; q < c[s]; q++) {
+        const size_t o = (size_t)s * N + q;
+        CtcHypothesis hy;
+        hy.tokens.assign(h.begin() + o * max_frames_, h.begin() + o * max_frames_ + n[o]);
+        hy.score = sc[o];
+        hy.errors = e[o];
+        (*lists)[s].push_back(hy);
+      }
+  }
+
+  // over the utterances finalised so far: emitted with mode 2 and a reference
+  double TokenErrorRate() const { const double *h = tot_.Read(); return h[0] / h[1]; }
+  double OracleTokenErrorRate() const { const double *h = tot_.Read(); return h[5] / h[1]; }
+  double UtteranceErrorRate() const { const double *h = tot_.Read(); return h[4] / h[3]; }
+  double NumUtterances() const { return tot_.Read()[3]; }
+  double NumErrors() const { return tot_.Read()[0]; }
+  double NumOracleErrors() const { return tot_.Read()[5]; }
+  double NumRefTokens() const { return tot_.Read()[1]; }
+  double NumHypTokens() const { return tot_.Read()[2]; }
+  std::string Report() const {
+    const double *h = tot_.Read();
+    std::ostringstream oss;
+    oss << "UTT_ERROR_RATE: " << 100.0 * h[4] / h[3] << "% [" << h[3] << " utterances, " << h[0] << " errors, " << h[1]
+        << " reference tokens, " << h[2] << " hypothesis tokens]" << std::endl;
+    oss << "ORACLE_TOKEN_ERROR_RATE: " << 100.0 * h[5] / h[1] << "% [" << nbest_ << "-best, beam " << beam_ << ", " << cands_ << " candidates, streaming]" << std::endl;
+    oss << "\nTOKEN_ERROR_RATE >> " << 100.0 * h[0] / h[1] << "% <<";
+    return oss.str();
+  }
+ private:
+  void *State() {                                       // zero-filled: "nothing yet" in every stream
+    if (!state_.As<void>()) {
+      state_.Grow(state_bytes_);
+      KCheck(klstm_memset_zero(state_.As<void>(), state_bytes_, nullptr));
+    }
+    return state_.As<void>();
+  }
+  int32 beam_, cands_, nbest_, max_frames_, classes_ = 0;
+  size_t state_bytes_ = 0;
+  const CtcLabelLm *lm_ = nullptr;
+  PackedLabels refs_;
+  DeviceBuffer state_, start_, mode_, hyp_, hlen_, cnt_, score_, err_, fr_, stab_;
+  DeviceTotals<6> tot_;
+};
+
 // Minimum expected token error over the n-best lists of a CtcBeamDecoder (klstm_ctc_mbr_eval, klstm.h): the
 // sequence-discriminative objective that follows CTC training.  With P = softmax over a stream's list of risk_scale * log p(h | y)
 // and R = sum P errors, diff is the derivative of R + ctc_weight * (-log p(ref | y)) with respect to the Softmax INPUT, like Ctc's.

@@ -224,6 +224,56 @@ class BatchScorer {
                                        out_stride, o_.mode, lp_.As<BaseFloat>(), o_.prior_scale, nullptr));
     }
   }
+  // The loop of ScoreDevice for a consumer that works chunk by chunk (CtcStreamDecoder::Step): every chunk's scores go to fn in CHUNK
+  // layout, a [chunk * num_stream x OutputDim()] matrix with rows t * num_stream + s, instead of the utterances' rows.  fn(scores,
+  // info) also learns per stream how many frames of the chunk are the utterance's (rows behind them are padding), whether its
+  // utterance starts and whether it ends with this chunk, and the utterance's index in lens (-1: idle).  Asynchronous like
+  // ScoreDevice: fn queues its own work on the library's stream.
+  struct ChunkInfo { std::vector<int32> frames, start, end, utt; };
+  template <class F>
+  void ForEachChunk(const BaseFloat *feats_dev, int32 feat_stride, const std::vector<int32> &lens, F fn) {
+    const int32 S = o_.num_stream, T = o_.chunk, rows = S * T;
+    const ScorePlan p = PlanChunks(lens, S, T);
+    if (!p.num_chunks) return;
+    if (feat_stride < in_dim_) KLSTM_ERR("BatchScorer: stride smaller than the row");
+    std::vector<std::pair<int32, int32> > by_off;     // (row offset, index) of the utterances with frames: offsets ascend
+    for (size_t u = 0, off = 0; u < lens.size(); off += lens[u++])
+      if (lens[u] > 0) by_off.emplace_back((int32)off, (int32)u);
+    KCheck(klstm_stream_synchronize(nullptr));
+    pdesc_.Upload(p.desc);
+    std::vector<int32> ident(rows);
+    for (int32 r = 0; r < rows; r++) ident[r] = r;
+    pdst_.Upload(ident);
+    cpost_.Resize(rows, out_dim_, false);
+    std::vector<int> flags(S);
+    ChunkInfo info;
+    for (int32 c = 0; c < p.num_chunks; c++) {
+      KCheck(klstm_pack_streams(feats_dev, in_dim_, feat_stride, pdesc_.As<int32>() + (size_t)c * 3 * S, S, T, shift_, act_[0].View().Data(),
+                                act_[0].Stride(), nullptr, nullptr));
+      for (int32 s = 0; s < S; s++) flags[s] = p.reset[(size_t)c * S + s];
+      int k = 0;
+      for (auto &eng : engines_) {
+        klstm_engine *e = eng.get();
+        KCheck(klstm_reset(e, flags.data(), S));
+        KCheck(klstm_propagate_inference(e, act_[k].View().Data(), rows, act_[k].Stride(), act_[k ^ 1].View().Data(), act_[k ^ 1].Stride()));
+        k ^= 1;
+      }
+      KCheck(klstm_affine_propagate(act_[k].View().Data(), rows, aff_in_, act_[k].Stride(), W_.As<BaseFloat>(), b_.As<BaseFloat>(),
+                                    aout_.View().Data(), out_dim_, aout_.Stride(), nullptr));
+      KCheck(klstm_log_softmax_scatter(aout_.View().Data(), rows, out_dim_, aout_.Stride(), pdst_.As<int32>(), cpost_.View().Data(),
+                                       cpost_.Stride(), o_.mode, lp_.As<BaseFloat>(), o_.prior_scale, nullptr));
+      info.frames.assign(S, 0); info.start.assign(S, 0); info.end.assign(S, 0); info.utt.assign(S, -1);
+      for (int32 s = 0; s < S; s++) {
+        const int32 *d = &p.desc[((size_t)c * S + s) * 3];
+        if (d[1] <= 0) continue;
+        info.frames[s] = std::min(T, d[1] - d[2]);
+        info.start[s] = d[2] == 0;
+        info.end[s] = d[2] + T >= d[1];
+        info.utt[s] = std::lower_bound(by_off.begin(), by_off.end(), std::make_pair(d[0], (int32)-1))->second;
+      }
+      fn(static_cast<const DeviceMatrix &>(cpost_), static_cast<const ChunkInfo &>(info));
+    }
+  }
   // Host API: one [len x InputDim()] row-major matrix per utterance in, one [len x OutputDim()] matrix per utterance out.
   void Score(const std::vector<std::vector<BaseFloat> > &utts, std::vector<std::vector<BaseFloat> > *out) {
     std::vector<int32> lens;
@@ -259,7 +309,80 @@ class BatchScorer {
   std::vector<int32> dims_;
   DeviceBuffer W_, b_, lp_;                   // lp_ stays empty (null) unless the mode is KLSTM_SCORE_LOGLIKE
   DeviceBuffer pdesc_, pdst_;                 // the plan of the ScoreDevice call in flight
-  DeviceMatrix act_[2], aout_;
+  DeviceMatrix act_[2], aout_, cpost_;        // cpost_: the chunk ForEachChunk hands out
 };
+
+// Streaming CTC decoding of a unidirectional model: the scorer's chunk loop with a CtcStreamDecoder behind it.  The forward pass and
+// the search advance together chunk by chunk, nothing of an utterance but its beam is kept, and an utterance may be as long as the
+// state is sized for (max_frames = the longest one): the limit of DecodeCtcWholeUtterances (65535 / num_stream frames) does not
+// apply.  so: num_stream <= 32 and the chunk length; o: blank, beam > 0, cands, nbest, class weights, lm, score as
+// DecodeCtcWholeUtterances takes them; o.max_frames > 0 skips longer utterances as the batcher there does.  (*hypotheses)[i] is the
+// 1-best of utts[i], (*nbest_lists)[i] its list (either may be null; both empty for a skipped utterance).  A bidirectional model
+// needs the whole utterance before its first output row exists and is refused, before any device work.
+inline DecodeCtcStats DecodeCtcStreaming(const Nnet &nnet, const std::vector<Utterance> &utts, const BatchScorerOptions &so,
+                                         const DecodeCtcOptions &o, std::vector<std::vector<int32> > *hypotheses,
+                                         std::vector<CtcNbestList> *nbest_lists, std::string *report = nullptr) {
+  for (int32 i = 0; i < nnet.NumComponents(); i++)
+    if (std::string(nnet.GetComponent(i).Marker()).find("<BLstm") == 0)
+      KLSTM_ERR("DecodeCtcStreaming: " << nnet.GetComponent(i).Marker() << " at component " << i << " is bidirectional: its first output row "
+                "needs the last input row, so there is nothing to stream (use DecodeCtcWholeUtterances)");
+  if (o.beam <= 0) KLSTM_ERR("DecodeCtcStreaming: beam must be positive (the best path needs no carried beam)");
+  if (so.mode != KLSTM_SCORE_POSTERIOR) KLSTM_ERR("DecodeCtcStreaming: the search reads posteriors (BatchScorerOptions::mode KLSTM_SCORE_POSTERIOR)");
+  if (so.num_stream > 32) KLSTM_ERR("DecodeCtcStreaming: num_stream " << so.num_stream << " > 32");
+  BatchScorer::CheckTopology(nnet, so);
+  if (hypotheses) hypotheses->assign(utts.size(), std::vector<int32>());
+  if (nbest_lists) nbest_lists->assign(utts.size(), CtcNbestList());
+  DecodeCtcStats st;
+  const int32 dim = nnet.GetComponent(0).InputDim();
+  std::vector<int32> lens(utts.size(), 0);
+  long total = 0;
+  int32 longest = 0;
+  for (size_t u = 0; u < utts.size(); u++) {
+    const Utterance &ut = utts[u];
+    if (ut.num_frames <= 0 || (o.max_frames > 0 && ut.num_frames > o.max_frames)) { st.num_skipped++; continue; }
+    if (ut.dim != dim || ut.feats.size() != (size_t)ut.num_frames * dim) KLSTM_ERR("DecodeCtcStreaming: utterance " << u << " is not [frames x " << dim << "]");
+    lens[u] = ut.num_frames; total += ut.num_frames; longest = std::max(longest, ut.num_frames); st.num_done++;
+  }
+  if (!total) return st;
+  if (total > INT_MAX) KLSTM_ERR("DecodeCtcStreaming: more than 2^31 rows");
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<BaseFloat> cat((size_t)total * dim);
+  size_t at = 0;
+  for (size_t u = 0; u < utts.size(); u++)
+    if (lens[u]) { std::copy(utts[u].feats.begin(), utts[u].feats.end(), cat.begin() + at); at += utts[u].feats.size(); }
+  DeviceMatrix feats;
+  feats.CopyFromHost(cat.data(), (int32)total, dim);
+  BatchScorer scorer(nnet, so);
+  CtcStreamDecoder dec(o.blank, o.beam, o.cands, o.nbest, so.num_stream, longest);
+  dec.SetClassWeights(o.class_weights);
+  dec.SetLanguageModel(o.lm);
+  const int32 S = so.num_stream;
+  std::vector<CtcNbestList> lists;
+  std::vector<int32> mode(S);
+  std::vector<std::vector<int32> > refs(S);
+  const std::vector<std::vector<int32> > none;
+  scorer.ForEachChunk(feats.View().Data(), feats.Stride(), lens, [&](const DeviceMatrix &post, const BatchScorer::ChunkInfo &info) {
+    dec.Step(post, info.frames, info.start);
+    st.num_minibatches++;
+    bool any = false;
+    for (int32 s = 0; s < S; s++) {
+      mode[s] = info.frames[s] > 0 && info.end[s] ? 2 : 0;
+      refs[s] = mode[s] && o.score ? utts[info.utt[s]].labels : std::vector<int32>();
+      any |= mode[s] != 0;
+    }
+    if (!any) return;
+    dec.Emit(mode, o.score ? refs : none, hypotheses || nbest_lists ? &lists : nullptr, nullptr, nullptr);
+    for (int32 s = 0; s < S && (hypotheses || nbest_lists); s++) {
+      if (!mode[s]) continue;
+      if (hypotheses && !lists[s].empty()) (*hypotheses)[info.utt[s]] = lists[s][0].tokens;
+      if (nbest_lists) (*nbest_lists)[info.utt[s]] = lists[s];
+    }
+  });
+  KCheck(klstm_stream_synchronize(nullptr));
+  st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  st.oracle_token_error_rate = dec.OracleTokenErrorRate();
+  FillDecodeCtcStats(dec, &st, report);
+  return st;
+}
 
 }  // namespace klstm_kaldi

@@ -531,4 +531,438 @@ hipError_t launch_ctc_beam_lm(const float *y, int T, int S, int K, int stride, c
                 blank, refs, roff, errors, totals, stat, ticket);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// STREAMING (klstm_ctc_beam_stream_step / _emit of include/klstm.h; the definition is tests/ctc_beam_stream_ref.py).  The
+// search above is a frame chain whose whole carried state is Bc, E and at most 64 beam entries plus the prefix tree, so it can stop at
+// any frame boundary and go on in another launch with the same bits.  k_ctc_beam_stream<LM> is the frame loop of k_ctc_beam over the
+// frames of one CHUNK, between a load and a store of that state; k_ctc_beam_emit<LM> is its epilogue as a kernel of its own, which
+// only reads the state.  The frame body is a copy of k_ctc_beam's, not shared code: the whole-utterance kernel stays the code it was.
+// State of stream s at state + s * beam_state_stride(max_frames, B):
+//   int hdr[16]          [0] BEAM_STARTED once a step began an utterance here, [1] frames consumed, [2] Bc, [3] E, [4] overflow flag
+//   u64 hash[64], ph[64]; int node[64], tok[64], len[64], lm[64]; float pb[64], pnb[64]          the beam entries, Bc of them valid
+//   int npar[max_frames B + 1], ntok[max_frames B + 1]                                           the prefix tree, node 0 the empty prefix
+// ------------------------------------------------------------------------------------------------------------------------------------
+constexpr int BEAM_STARTED = 0x4B435442;
+constexpr size_t BEAM_STATE_HEAD = 2816;                            // 64 + 2 * 512 + 6 * 256 = 2624, rounded up to 256
+
+struct BeamState {
+  int *hdr;
+  u64 *hash, *ph;
+  int *node, *tok, *len, *lm;
+  float *pb, *pnb;
+  int *npar, *ntok;
+};
+__host__ __device__ inline size_t beam_tree_bytes(int max_frames, int B) { return (((size_t)max_frames * B + 1) * sizeof(int) + 255) / 256 * 256; }
+__host__ __device__ inline size_t beam_state_stride(int max_frames, int B) { return BEAM_STATE_HEAD + 2 * beam_tree_bytes(max_frames, B); }
+__device__ __forceinline__ BeamState beam_state_at(void *state, int s, int max_frames, int B) {
+  char *p = reinterpret_cast<char *>(state) + (size_t)s * beam_state_stride(max_frames, B);
+  BeamState b;
+  b.hdr = reinterpret_cast<int *>(p);
+  b.hash = reinterpret_cast<u64 *>(p + 64);
+  b.ph = b.hash + BEAM_MAXB;
+  b.node = reinterpret_cast<int *>(p + 64 + 1024);
+  b.tok = b.node + BEAM_MAXB; b.len = b.tok + BEAM_MAXB; b.lm = b.len + BEAM_MAXB;
+  b.pb = reinterpret_cast<float *>(b.lm + BEAM_MAXB);
+  b.pnb = b.pb + BEAM_MAXB;
+  b.npar = reinterpret_cast<int *>(p + BEAM_STATE_HEAD);
+  b.ntok = reinterpret_cast<int *>(p + BEAM_STATE_HEAD + beam_tree_bytes(max_frames, B));
+  return b;
+}
+
+// T, lens: the frames of this chunk; topv / topi: the candidates of its rows
+template <int LM>
+__global__ __launch_bounds__(256) void k_ctc_beam_stream(const float *__restrict__ y, int T, int S, int K, int stride, const int *__restrict__ lens,
+                                                         const int *__restrict__ start, const float *__restrict__ w, int blank, int B, int C,
+                                                         const float *__restrict__ topv, const int *__restrict__ topi, void *state,
+                                                         int max_frames, BeamLm lm) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char beam_dyn[];     // LM = 2: weight [Q K] float, next [Q K] int
+  __shared__ __attribute__((aligned(16))) u64 keys[BEAM_MAXLIST];
+  __shared__ u64 sel[BEAM_MAXB];
+  __shared__ u64 e_hash[BEAM_MAXB], e_ph[BEAM_MAXB];
+  __shared__ int e_node[BEAM_MAXB], e_tok[BEAM_MAXB], e_len[BEAM_MAXB];
+  __shared__ float e_pb[BEAM_MAXB], e_pnb[BEAM_MAXB], s_pb[BEAM_MAXB], s_pnb[BEAM_MAXB];
+  __shared__ float cvs[LM ? 2 * BEAM_MAXC : BEAM_MAXC];
+  __shared__ int cis[LM ? 2 * BEAM_MAXC : BEAM_MAXC];
+  __shared__ unsigned char merged[BEAM_MAXB * BEAM_MAXC];
+  __shared__ int e_lm[LM ? 2 * BEAM_MAXB : 1];
+  __shared__ int nq[LM ? BEAM_MAXB * BEAM_MAXC : 1];
+  float gw[BEAM_LMK];
+  int gn[BEAM_LMK];
+  const float *const lw = reinterpret_cast<const float *>(beam_dyn);
+  const int *const lnx = reinterpret_cast<const int *>(beam_dyn) + (LM == 2 ? lm.Q * K : 0);
+
+  const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int len = lens[s];
+  if (len <= 0 || len > T) return;                                 // idle (or rejected) in this call: the state is not touched
+  const BeamState bs = beam_state_at(state, s, max_frames, B);
+  const bool fresh = bs.hdr[0] != BEAM_STARTED || (start && start[s] != 0);
+  const int t0 = fresh ? 0 : bs.hdr[1];
+  if (t0 < 0 || t0 > max_frames || len > max_frames - t0) {        // uniform.  Overflow: the flag alone, which no thread above reads
+    if (tid == 0) bs.hdr[4] = 1;
+    return;
+  }
+  int *const npar = bs.npar, *const ntok = bs.ntok;
+  int Bc = 1, E = 0;
+  for (int q = tid; q < BEAM_MAXB * BEAM_MAXC; q += nt) merged[q] = 0;
+  if (fresh) {
+    if (tid == 0) {
+      e_node[0] = 0; e_tok[0] = -1; e_len[0] = 0; e_hash[0] = BEAM_H0; e_ph[0] = 0; e_pb[0] = 1.f; e_pnb[0] = 0.f;
+      npar[0] = -1; ntok[0] = -1;
+      if constexpr (LM != 0) e_lm[0] = 0;
+    }
+  } else {
+    Bc = min(max(bs.hdr[2], 1), B);
+    E = bs.hdr[3];
+    if (tid < Bc) {
+      e_node[tid] = bs.node[tid]; e_tok[tid] = bs.tok[tid]; e_len[tid] = bs.len[tid]; e_hash[tid] = bs.hash[tid]; e_ph[tid] = bs.ph[tid];
+      e_pb[tid] = bs.pb[tid]; e_pnb[tid] = bs.pnb[tid];
+      if constexpr (LM != 0) e_lm[tid] = min(max(bs.lm[tid], 0), lm.Q - 1);
+    }
+  }
+  // the prefetches restart at the chunk's first frame as k_ctc_beam starts at frame 0: a value fetched a frame later is the same value
+  float nv = 0.f, neb = beam_emit_at(y + (size_t)s * stride, w, blank);
+  int ni = -1;
+  if (tid < C) { nv = topv[(size_t)s * C + tid]; ni = topi[(size_t)s * C + tid]; }
+  auto lm_fetch = [&](int half, int nbc) {
+#pragma unroll
+    for (int k = 0; k < BEAM_LMK; k++) {
+      gw[k] = 0.f; gn[k] = -1;
+      const int q = tid + k * nt;
+      if (q < nbc) {
+        const int i = q / C, c = cis[half * BEAM_MAXC + q - i * C];
+        if ((unsigned)c < (unsigned)K) {
+          const int idx = e_lm[half * BEAM_MAXB + i] * K + c;
+          if constexpr (LM == 2) { gw[k] = lw[idx]; gn[k] = lnx[idx]; }
+          else { gw[k] = lm.weight[idx]; gn[k] = lm.next[idx]; }
+        }
+      }
+    }
+  };
+  if constexpr (LM != 0) {
+    if constexpr (LM == 2) {
+      float *dw = reinterpret_cast<float *>(beam_dyn);
+      int *dn = reinterpret_cast<int *>(beam_dyn) + lm.Q * K;
+      const int nel = lm.Q * K;
+      if (nel % 4 == 0 && ((reinterpret_cast<uintptr_t>(lm.weight) | reinterpret_cast<uintptr_t>(lm.next)) & 15) == 0) {
+        const float4 *sw = reinterpret_cast<const float4 *>(lm.weight);
+        const int4 *sn = reinterpret_cast<const int4 *>(lm.next);
+#pragma unroll 4
+        for (int q = tid; q < nel / 4; q += nt) {
+          reinterpret_cast<float4 *>(dw)[q] = sw[q];
+          reinterpret_cast<int4 *>(dn)[q] = sn[q];
+        }
+      } else {
+#pragma unroll 4
+        for (int q = tid; q < nel; q += nt) { dw[q] = lm.weight[q]; dn[q] = lm.next[q]; }
+      }
+    }
+    if (tid < C) { cvs[tid] = nv; cis[tid] = ni; }
+    __syncthreads();
+    lm_fetch(0, Bc * C);
+  }
+
+  for (int t = 0; t < len; t++) {
+    const size_t r = (size_t)t * S + s;
+    const float *yp = y + r * stride;
+    float *const cv = cvs + (LM ? (t & 1) * BEAM_MAXC : 0);
+    int *const ci = cis + (LM ? (t & 1) * BEAM_MAXC : 0);
+    if constexpr (LM == 0)
+      if (tid < C) { cv[tid] = nv; ci[tid] = ni; }
+    const float eb = neb;
+    if (tid < B) sel[tid] = 0;
+    if (t + 1 < len) {
+      const size_t r1 = r + S;
+      neb = beam_emit_at(y + r1 * stride, w, blank);
+      if (tid < C) { nv = topv[r1 * C + tid]; ni = topi[r1 * C + tid]; }
+    }
+    __syncthreads();
+    if (tid < Bc) {                                                // stay entries
+      const int j = tid, l = e_tok[j];
+      const float tot = badd(e_pb[j], e_pnb[j]);
+      const float spb = bmul(tot, eb);
+      float spnb = 0.f;
+      bool deferred = false;
+      if (l >= 0) {
+        spnb = bmul(e_pnb[j], beam_emit_at(yp, w, l));
+        int pi = -1, rr = -1;
+        for (int i = 0; i < Bc; i++)
+          if (e_len[i] + 1 == e_len[j] && e_hash[i] == e_ph[j]) pi = i;
+        for (int q = 0; q < C; q++)
+          if (ci[q] == l && cv[q] > 0.f) rr = q;
+        if (pi >= 0 && rr >= 0) {
+          if constexpr (LM == 0) {
+            const float v = bmul(l == e_tok[pi] ? e_pb[pi] : badd(e_pb[pi], e_pnb[pi]), cv[rr]);
+            spnb = badd(spnb, v);
+            merged[pi * C + rr] = 1;
+          } else {
+            merged[pi * C + rr] = (unsigned char)(j + 1);
+            deferred = true;
+          }
+        }
+      }
+      s_pb[j] = spb; s_pnb[j] = spnb;
+      if (!deferred) keys[j] = ((u64)__float_as_uint(badd(spb, spnb)) << 32) | (u64)(0xFFFFFFFFu - (unsigned)j);
+    }
+    __syncthreads();
+    const int n = Bc * (C + 1);
+    if constexpr (LM != 0) {
+#pragma unroll
+      for (int k = 0; k < BEAM_LMK; k++) {
+        const int q = tid + k * nt;
+        if (q < Bc * C) {
+          const int i = q / C, rr = q - i * C, pos = Bc + q, n1 = gn[k];
+          float f = 0.f;
+          if (cv[rr] > 0.f && (unsigned)n1 < (unsigned)lm.Q) f = beam_emit(bmul(cv[rr], beam_emit(gw[k])));
+          const float v = bmul(ci[rr] == e_tok[i] ? e_pb[i] : badd(e_pb[i], e_pnb[i]), f);
+          const int m = merged[q];
+          u64 key = 0;
+          if (m) {
+            const int j = m - 1;
+            const float spnb = badd(s_pnb[j], v);
+            merged[q] = 0;
+            s_pnb[j] = spnb;
+            keys[j] = ((u64)__float_as_uint(badd(s_pb[j], spnb)) << 32) | (u64)(0xFFFFFFFFu - (unsigned)j);
+          } else if (v > 0.f) key = ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)pos);
+          keys[pos] = key;
+          nq[q] = n1;
+        }
+      }
+    } else {
+      for (int pos = Bc + tid; pos < n; pos += nt) {
+        u64 key = 0;
+        const int q = pos - Bc, i = q / C, rr = q - i * C;
+        if (merged[q]) merged[q] = 0;
+        else if (cv[rr] > 0.f) {
+          const float v = bmul(ci[rr] == e_tok[i] ? e_pb[i] : badd(e_pb[i], e_pnb[i]), cv[rr]);
+          if (v > 0.f) key = ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)pos);
+        }
+        keys[pos] = key;
+      }
+    }
+    if (tid == 0) keys[n] = 0;
+    __syncthreads();
+    const ulonglong2 *k2 = reinterpret_cast<const ulonglong2 *>(keys);
+    const int np = (n + 1) / 2;
+    if (n <= nt) {
+      const u64 key = tid < n ? keys[tid] : 0;
+      int rank = 0;
+#pragma unroll 8
+      for (int j = 0; j < np; j++) {
+        const ulonglong2 o = k2[j];
+        rank += (o.x > key) + (o.y > key);
+      }
+      if (key && rank < B) sel[rank] = key;
+    } else {
+      u64 my[BEAM_KPT];
+      int rank[BEAM_KPT];
+#pragma unroll
+      for (int e = 0; e < BEAM_KPT; e++) {
+        const int pos = tid + e * nt;
+        my[e] = pos < n ? keys[pos] : ~0ull;
+        rank[e] = 0;
+      }
+#pragma unroll 2
+      for (int j = 0; j < np; j++) {
+        const ulonglong2 o = k2[j];
+#pragma unroll
+        for (int e = 0; e < BEAM_KPT; e++) rank[e] += (o.x > my[e]) + (o.y > my[e]);
+      }
+#pragma unroll
+      for (int e = 0; e < BEAM_KPT; e++)
+        if (my[e] != ~0ull && my[e] && rank[e] < B) sel[rank[e]] = my[e];
+    }
+    __syncthreads();
+    const unsigned mbits = (unsigned)(sel[0] >> 32);
+    const u64 key = tid < B ? sel[tid] : 0;
+    int node = 0, tok = 0, ln = 0, lst = 0;
+    u64 hs = 0, ph = 0;
+    float pb = 0.f, pnb = 0.f;
+    if (key) {
+      const int pos = (int)(0xFFFFFFFFu - (unsigned)key);
+      if (pos < Bc) {
+        node = e_node[pos]; tok = e_tok[pos]; ln = e_len[pos]; hs = e_hash[pos]; ph = e_ph[pos]; pb = s_pb[pos]; pnb = s_pnb[pos];
+        if constexpr (LM != 0) lst = e_lm[(t & 1) * BEAM_MAXB + pos];
+      } else {
+        const int q = pos - Bc, i = q / C, rr = q - i * C;
+        node = 1 + (t0 + t) * B + tid; tok = ci[rr]; ln = e_len[i] + 1; ph = e_hash[i]; hs = beam_hash(ph, tok);   // t0 + t < max_frames
+        pnb = __uint_as_float((unsigned)(key >> 32));
+        npar[node] = e_node[i]; ntok[node] = tok;
+        if constexpr (LM != 0) lst = nq[q];
+      }
+      if (mbits) {
+        const int ex = (int)((mbits >> 23) & 0xffu);
+        const float sc = __uint_as_float((unsigned)(253 - ex) << 23);
+        pb = bmul(pb, sc); pnb = bmul(pnb, sc);
+        pb = pb >= BEAM_TINY ? pb : 0.f; pnb = pnb >= BEAM_TINY ? pnb : 0.f;
+      }
+    }
+    if constexpr (LM != 0) {
+      const int h1 = (t + 1) & 1;
+      if (key) e_lm[h1 * BEAM_MAXB + tid] = lst;
+      if (tid < C) { cvs[h1 * BEAM_MAXC + tid] = nv; cis[h1 * BEAM_MAXC + tid] = ni; }
+    }
+    Bc = __syncthreads_count(key != 0);
+    if constexpr (LM != 0)
+      if (t + 1 < len) lm_fetch((t + 1) & 1, Bc * C);
+    if (mbits) E += (int)((mbits >> 23) & 0xffu) - 126;
+    if (key) { e_node[tid] = node; e_tok[tid] = tok; e_len[tid] = ln; e_hash[tid] = hs; e_ph[tid] = ph; e_pb[tid] = pb; e_pnb[tid] = pnb; }
+  }
+  __syncthreads();
+  if (tid < Bc) {                                                  // the beam goes back where the next step, or an emit, finds it
+    bs.node[tid] = e_node[tid]; bs.tok[tid] = e_tok[tid]; bs.len[tid] = e_len[tid]; bs.hash[tid] = e_hash[tid]; bs.ph[tid] = e_ph[tid];
+    bs.pb[tid] = e_pb[tid]; bs.pnb[tid] = e_pnb[tid];
+    if constexpr (LM != 0) bs.lm[tid] = e_lm[(len & 1) * BEAM_MAXB + tid];
+    else bs.lm[tid] = 0;
+  }
+  if (tid == 0) {
+    bs.hdr[0] = BEAM_STARTED; bs.hdr[1] = t0 + len; bs.hdr[2] = Bc; bs.hdr[3] = E;
+    if (fresh) bs.hdr[4] = 0;
+  }
+}
+
+// One wave per stream: the n-best list of the saved beam as k_ctc_beam's epilogue writes it, the frames consumed and the length of
+// the prefix all live entries share.  Reads the state, writes none of it.  tcount: the counts k_ctc_beam_tail sees (mode 2 alone).
+template <int LM>
+__global__ __launch_bounds__(64) void k_ctc_beam_emit(int S, int B, int N, const int *__restrict__ mode, const float *__restrict__ fin,
+                                                      void *state, int max_frames, int *__restrict__ hyp, int hyp_stride,
+                                                      int *__restrict__ hyp_len, int *__restrict__ count, float *__restrict__ score,
+                                                      int *__restrict__ frames, int *__restrict__ stable, int *__restrict__ tcount,
+                                                      unsigned *__restrict__ ticket) {
+  const int s = blockIdx.x, tid = threadIdx.x;
+  if (s == 0 && tid == 0) *ticket = 0u;                            // for k_ctc_beam_tail
+  const BeamState bs = beam_state_at(state, s, max_frames, B);
+  const bool started = bs.hdr[0] == BEAM_STARTED;
+  const int m = mode[s], nfr = started ? bs.hdr[1] : 0;
+  if (tid == 0 && frames) frames[s] = bs.hdr[4] ? -1 - nfr : nfr;
+  if (m < 1 || m > 2 || !started) {                                // skipped, or nothing yet: no list
+    if (tid == 0) {
+      count[s] = 0; tcount[s] = 0;
+      if (stable && m >= 1 && m <= 2) stable[s] = 0;
+    }
+    return;
+  }
+  const int Bc = min(max(bs.hdr[2], 1), B), E = bs.hdr[3];
+  const float tot0 = tid < Bc ? badd(bs.pb[tid], bs.pnb[tid]) : 0.f;
+  float tot = tot0;
+  bool ranked = false;
+  if constexpr (LM != 0)
+    if (m == 2 && fin) {                                           // uniform.  tot becomes tf = total * flush(final[state])
+      if (tid < Bc) tot = bmul(tot, beam_emit(fin[bs.lm[tid]]));
+      ranked = true;
+    }
+  const u64 live = __ballot(tot > 0.f);
+  int slot = live ? (tot > 0.f ? __popcll(live & ((1ull << tid) - 1ull)) : N) : (tid == 0 ? 0 : N);
+  if (ranked && live) {
+    const unsigned mine = __float_as_uint(tot);
+    int rank = 0;
+    for (int j = 0; j < 64; j++) {
+      const unsigned o = __shfl(mine, j);
+      rank += (o > mine) || (o == mine && j < tid);
+    }
+    slot = tot > 0.f ? rank : N;
+  }
+  const int cnt = live ? min(N, (int)__popcll(live)) : 1;
+  if (tid == 0) { count[s] = cnt; tcount[s] = m == 2 ? cnt : 0; }
+  const int myln = tid < Bc ? bs.len[tid] : 0, mynode = tid < Bc ? bs.node[tid] : 0;
+  if (slot < N) {
+    const size_t o = (size_t)s * N + slot;
+    hyp_len[o] = myln;
+    if (score) score[o] = tot > 0.f ? (float)badd(log((double)tot), bmul((double)E, 0.6931471805599453)) : -INFINITY;
+    int node = mynode;
+    for (int q = myln - 1; q >= 0; q--) {
+      hyp[o * hyp_stride + q] = bs.ntok[node];
+      node = bs.npar[node];
+    }
+  }
+  if (!stable) return;
+  // the longest common prefix of the entries with a total > 0, token by token: the same prefix can own two nodes (it left the beam
+  // and came back), so equal nodes end the walk but unequal ones decide nothing
+  const u64 live0 = __ballot(tot0 > 0.f);
+  if (!live0) {                                                    // DEAD: the first entry
+    if (tid == 0) stable[s] = myln;
+    return;
+  }
+  const bool lv = tot0 > 0.f;
+  int d = lv ? myln : INT_MAX;
+  for (int off = 32; off > 0; off >>= 1) d = min(d, __shfl_xor(d, off));
+  int node = lv ? mynode : 0;
+  for (int q = lv ? myln - d : 0; q > 0; q--) node = bs.npar[node];           // every live lane up to the shortest live length
+  const int first = __ffsll((long long)live0) - 1;
+  int ans = d;
+  while (d > 0) {
+    const int n0 = __shfl(node, first);
+    if (!__ballot(lv && node != n0)) break;                        // one node: one prefix from here up
+    const int tk = lv ? bs.ntok[node] : 0, tk0 = __shfl(tk, first);
+    if (__ballot(lv && tk != tk0)) ans = d - 1;                     // token d disagrees: at most d - 1 are common
+    if (lv) node = bs.npar[node];
+    d--;
+  }
+  if (tid == 0) stable[s] = ans;
+}
+
+size_t ctc_beam_stream_state_bytes(int max_frames, int S, int B) { return (size_t)S * beam_state_stride(max_frames, B); }
+
+// statistics [32][8] (1024), ticket (256), the tail's counts [32] (256), then top values, top columns of the chunk's rows
+constexpr size_t BEAM_STREAM_WS_HEAD = 1536;
+size_t ctc_beam_stream_workspace_bytes(int T, int S, int C, int N) {
+  (void)N;
+  return BEAM_STREAM_WS_HEAD + 2 * beam_top_bytes(T, S, C);
+}
+size_t ctc_beam_stream_emit_workspace_bytes() { return BEAM_STREAM_WS_HEAD; }
+
+hipError_t launch_ctc_beam_stream_step(const float *y, int T, int S, int K, int stride, const int *lens, const int *start, int blank,
+                                       const float *w, int B, int C, int Q, const int *lm_next, const float *lm_weight, void *state,
+                                       int max_frames, void *workspace, hipStream_t st) {
+  char *p = reinterpret_cast<char *>(workspace);
+  unsigned *ticket = reinterpret_cast<unsigned *>(p + 1024);
+  float *topv = reinterpret_cast<float *>(p + BEAM_STREAM_WS_HEAD);
+  int *topi = reinterpret_cast<int *>(p + BEAM_STREAM_WS_HEAD + beam_top_bytes(T, S, C));
+  const int rows = T * S;
+  const int g = K <= 256 ? 16 : K <= 2048 ? 64 : 256;              // the rules of launch_ctc_beam_lm
+  const int nthreads = B * (C + 1) <= 64 ? 64 : B * (C + 1) <= 128 ? 128 : 256;
+  hipError_t err;
+  if (g == 16)
+    err = launch(k_ctc_topc_sub<16>, dim3((rows + 15) / 16), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
+  else if (g == 64)
+    err = launch(k_ctc_topc_sub<64>, dim3((rows + 3) / 4), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
+  else
+    err = launch(k_ctc_topc_wg, dim3(rows), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
+  if (err != hipSuccess) return err;
+  const BeamLm lm{Q, lm_next, lm_weight, nullptr};
+  if (Q == 0)
+    return launch(k_ctc_beam_stream<0>, dim3(S), dim3(nthreads), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, start, w, blank, B, C,
+                  (const float *)topv, (const int *)topi, state, max_frames, lm);
+  if (!ctc_beam_lm_resident(Q, K, B, C))
+    return launch(k_ctc_beam_stream<1>, dim3(S), dim3(nthreads), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, start, w, blank, B, C,
+                  (const float *)topv, (const int *)topi, state, max_frames, lm);
+  const size_t dyn = (size_t)Q * K * 8;
+  if (dyn > 32 * 1024 && dyn <= 64 * 1024) {
+    err = raise_lds_limit(reinterpret_cast<const void *>(k_ctc_beam_stream<2>), dyn);
+    if (err != hipSuccess) return err;
+  }
+  return launch(k_ctc_beam_stream<2>, dim3(S), dim3(nthreads), dyn, st, LaunchProbe{}, y, T, S, K, stride, lens, start, w, blank, B, C,
+                (const float *)topv, (const int *)topi, state, max_frames, lm);
+}
+
+hipError_t launch_ctc_beam_stream_emit(int S, int K, int blank, int B, int N, const int *mode, int Q, const float *lm_final, const void *state,
+                                       int max_frames, int *hyp, int hyp_stride, int *hyp_len, int *count, float *score, int *frames,
+                                       int *stable, const int *refs, const int *roff, int *errors, double *totals, void *workspace,
+                                       hipStream_t st) {
+  char *p = reinterpret_cast<char *>(workspace);
+  int *stat = reinterpret_cast<int *>(p);
+  unsigned *ticket = reinterpret_cast<unsigned *>(p + 1024);
+  int *tcount = reinterpret_cast<int *>(p + 1280);
+  void *sp = const_cast<void *>(state);
+  hipError_t err;
+  if (Q > 0 && lm_final)
+    err = launch(k_ctc_beam_emit<1>, dim3(S), dim3(64), 0, st, LaunchProbe{}, S, B, N, mode, lm_final, sp, max_frames, hyp, hyp_stride, hyp_len,
+                 count, score, frames, stable, tcount, ticket);
+  else
+    err = launch(k_ctc_beam_emit<0>, dim3(S), dim3(64), 0, st, LaunchProbe{}, S, B, N, mode, (const float *)nullptr, sp, max_frames, hyp,
+                 hyp_stride, hyp_len, count, score, frames, stable, tcount, ticket);
+  if (err != hipSuccess || !refs) return err;
+  return launch(k_ctc_beam_tail, dim3(S), dim3(256), 0, st, LaunchProbe{}, (const int *)hyp, (const int *)hyp_len, (const int *)tcount, hyp_stride,
+                S, K, N, blank, refs, roff, errors, totals, stat, ticket);
+}
+
 }  // namespace klstm

@@ -2161,6 +2161,89 @@ int klstm_ctc_beam_lm_resident(int lm_states, int K, int beam, int cands) {
   if (lm_states < 1 || K < 2 || (long)lm_states * K > (1L << 24)) return 0;
   return ctc_beam_lm_resident(lm_states, K, beam, cands) ? 1 : 0;
 }
+static bool ctc_beam_stream_state_ok(int max_frames, int S, int beam) {
+  return max_frames >= 1 && S >= 1 && S <= 32 && beam >= 1 && beam <= 64 && (long)max_frames * beam + 1 < (1L << 31);
+}
+size_t klstm_ctc_beam_stream_state_bytes(int max_frames, int S, int beam) {
+  if (!ctc_beam_stream_state_ok(max_frames, S, beam)) {
+    fail(KLSTM_ERR_SHAPE, "klstm_ctc_beam_stream_state_bytes: %d frames, streams %d, beam %d outside 1 <= frames, 1 <= S <= 32, 1 <= beam <= 64, frames * beam + 1 < 2^31", max_frames, S, beam);
+    return 0;
+  }
+  return ctc_beam_stream_state_bytes(max_frames, S, beam);
+}
+size_t klstm_ctc_beam_stream_workspace_bytes(int T, int S, int cands, int nbest) {
+  if (!ctc_beam_shape_ok(T, S, 1, cands) || nbest < 1 || nbest > 64) {
+    fail(KLSTM_ERR_SHAPE, "klstm_ctc_beam_stream_workspace_bytes: T %d, streams %d, candidates %d, n-best %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, 1 <= candidates <= 32, 1 <= n-best <= 64", T, S, cands, nbest);
+    return 0;
+  }
+  return ctc_beam_stream_workspace_bytes(T, S, cands, nbest);
+}
+// what step and emit check alike about the state
+static klstm_status ctc_beam_stream_state_check(const char *fn, int S, int beam, const void *state, size_t state_bytes, int max_frames) {
+  if (!ctc_beam_stream_state_ok(max_frames, S, beam))
+    return fail(KLSTM_ERR_SHAPE, "%s: %d frames, streams %d, beam %d outside 1 <= frames, S <= 32, beam <= 64, frames * beam + 1 < 2^31", fn, max_frames, S, beam);
+  if (!state) return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
+  if ((reinterpret_cast<uintptr_t>(state) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: state must be 16-byte aligned", fn);
+  if (state_bytes < ctc_beam_stream_state_bytes(max_frames, S, beam))
+    return fail(KLSTM_ERR_ARG, "%s: state of %zu bytes is below klstm_ctc_beam_stream_state_bytes(%d, %d, %d) = %zu", fn, state_bytes, max_frames, S,
+                beam, ctc_beam_stream_state_bytes(max_frames, S, beam));
+  return KLSTM_OK;
+}
+klstm_status klstm_ctc_beam_stream_step(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *start_dev,
+                                        int blank, const float *class_weight_dev, int beam, int cands, int lm_states,
+                                        const int *lm_next_dev, const float *lm_weight_dev, void *state, size_t state_bytes, int max_frames,
+                                        void *workspace, size_t workspace_bytes, void *hip_stream) {
+  const char *fn = "klstm_ctc_beam_stream_step";
+  if (T <= 0 || S <= 0 || K <= 0 || beam <= 0 || cands <= 0)
+    return fail(KLSTM_ERR_ARG, "%s: bad size (T %d, streams %d, K %d, beam %d, candidates %d)", fn, T, S, K, beam, cands);
+  if (!ctc_beam_shape_ok(T, S, beam, cands) || K < 2 || K > 32768 || cands > K - 1)
+    return fail(KLSTM_ERR_SHAPE, "%s: T %d, streams %d, K %d, beam %d, candidates %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768, beam <= 64, candidates <= min(K - 1, 32)",
+                fn, T, S, K, beam, cands);
+  if (lm_states < 0 || (long)lm_states * K > (1L << 24))
+    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 0 <= states, states * K <= 2^24", fn, lm_states, K);
+  klstm_status st = ctc_beam_stream_state_check(fn, S, beam, state, state_bytes, max_frames);
+  if (st != KLSTM_OK) return st;
+  const char *pointers = nullptr;
+  if (lm_states > 0 && (!lm_next_dev || !lm_weight_dev)) pointers = "the language model's next and weight tables come together";
+  if (!net_out || !lens_dev || !workspace) pointers = "null argument";
+  st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride, nullptr, workspace);
+  if (st != KLSTM_OK) return st;
+  if (workspace_bytes < ctc_beam_stream_workspace_bytes(T, S, cands, 1))
+    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_beam_stream_workspace_bytes(%d, %d, %d, .) = %zu", fn, workspace_bytes,
+                T, S, cands, ctc_beam_stream_workspace_bytes(T, S, cands, 1));
+  HIPCHK(launch_ctc_beam_stream_step(net_out, T, S, K, stride, lens_dev, start_dev, blank, class_weight_dev, beam, cands, lm_states, lm_next_dev,
+                                     lm_weight_dev, state, max_frames, workspace, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
+klstm_status klstm_ctc_beam_stream_emit(int S, int K, int blank, int beam, int nbest, const int *mode_dev, int lm_states,
+                                        const float *lm_final_dev, const void *state, size_t state_bytes, int max_frames, int *hyp_dev,
+                                        int hyp_stride, int *hyp_len_dev, int *nbest_count_dev, float *score_dev, int *frames_dev,
+                                        int *stable_len_dev, const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev,
+                                        double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  const char *fn = "klstm_ctc_beam_stream_emit";
+  if (S <= 0 || K <= 0 || beam <= 0 || nbest <= 0)
+    return fail(KLSTM_ERR_ARG, "%s: bad size (streams %d, K %d, beam %d, n-best %d)", fn, S, K, beam, nbest);
+  if (S > 32 || K < 2 || K > 32768 || beam > 64 || nbest > beam)
+    return fail(KLSTM_ERR_SHAPE, "%s: streams %d, K %d, beam %d, n-best %d outside S <= 32, 2 <= K <= 32768, beam <= 64, n-best <= beam", fn, S, K, beam, nbest);
+  if (lm_states < 0 || (long)lm_states * K > (1L << 24))
+    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 0 <= states, states * K <= 2^24", fn, lm_states, K);
+  if (ctc_beam_stream_state_ok(max_frames, S, beam) && hyp_stride < max_frames)      // (every limit before any pointer)
+    return fail(KLSTM_ERR_SHAPE, "%s: hypothesis stride %d below the %d frames of the state", fn, hyp_stride, max_frames);
+  klstm_status st = ctc_beam_stream_state_check(fn, S, beam, state, state_bytes, max_frames);
+  if (st != KLSTM_OK) return st;
+  const char *pointers = ctc_refs_finding(ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev);
+  if (!mode_dev || !hyp_dev || !hyp_len_dev || !nbest_count_dev || !workspace) pointers = "null argument";
+  if (pointers) return fail(KLSTM_ERR_ARG, "%s: %s", fn, pointers);
+  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "%s: blank %d outside [0, %d)", fn, blank, K);
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
+  if (workspace_bytes < ctc_beam_stream_emit_workspace_bytes())
+    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_beam_stream_workspace_bytes(1, %d, 1, .) = %zu", fn, workspace_bytes, S,
+                ctc_beam_stream_workspace_bytes(1, S, 1, 1));
+  HIPCHK(launch_ctc_beam_stream_emit(S, K, blank, beam, nbest, mode_dev, lm_states, lm_final_dev, state, max_frames, hyp_dev, hyp_stride,
+                                     hyp_len_dev, nbest_count_dev, score_dev, frames_dev, stable_len_dev, ref_labels_dev, ref_offsets_dev,
+                                     errors_dev, totals_dev, workspace, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
 static bool ctc_mbr_shape_ok(int T, int S, int list_n, int max_len) {
   return T > 0 && S > 0 && S <= 32 && (long)T * S <= 65535 && list_n >= 1 && list_n <= 16 && max_len >= 0 && max_len <= 1023;
 }

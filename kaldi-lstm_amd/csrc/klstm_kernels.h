@@ -343,6 +343,19 @@ bool ctc_beam_lm_resident(int Q, int K, int B, int C);
 hipError_t launch_ctc_beam_lm(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
                               int Q, const int *lm_next, const float *lm_weight, const float *lm_final, int *hyp, int *hyp_len, int *count,
                               float *score, const int *refs, const int *roff, int *errors, double *totals, void *workspace, hipStream_t st);
+// the search fed chunk by chunk (klstm_ctc_beam_stream_step / _emit of include/klstm.h; klstm_ctc_beam.hip): the beam and the prefix
+// tree of every stream live in `state` between the calls.  The workspace: statistics, ticket and the tail's counts (the part an emit
+// needs, ctc_beam_stream_emit_workspace_bytes), then C (value, column) pairs per row of a chunk.
+size_t ctc_beam_stream_state_bytes(int max_frames, int S, int B);
+size_t ctc_beam_stream_workspace_bytes(int T, int S, int C, int N);
+size_t ctc_beam_stream_emit_workspace_bytes();
+hipError_t launch_ctc_beam_stream_step(const float *y, int T, int S, int K, int stride, const int *lens, const int *start, int blank,
+                                       const float *w, int B, int C, int Q, const int *lm_next, const float *lm_weight, void *state,
+                                       int max_frames, void *workspace, hipStream_t st);
+hipError_t launch_ctc_beam_stream_emit(int S, int K, int blank, int B, int N, const int *mode, int Q, const float *lm_final, const void *state,
+                                       int max_frames, int *hyp, int hyp_stride, int *hyp_len, int *count, float *score, int *frames,
+                                       int *stable, const int *refs, const int *roff, int *errors, double *totals, void *workspace,
+                                       hipStream_t st);
 // Minimum expected token error over CTC n-best lists (klstm_ctc_mbr.hip): klstm_ctc_mbr_eval / klstm_ctc_mbr_workspace_bytes of
 // include/klstm.h.  N list slots per stream, with_ref: one more entry for the reference.  The workspace: statuses, weights, links and
 // accumulator slots per entry, a class map per stream, then the alpha and the beta rows of every entry [S][E][T][Npad].

@@ -4,6 +4,8 @@ ctc_greedy_decode: best-path decoding and token error rate of the same posterior
 ctc_align: the most probable alignment of given label sequences to the frames (klstm_ctc_align).
 ctc_beam_decode: prefix beam search, n-best lists with scores and edit distances (klstm_ctc_beam_decode), with
 lm=CtcLabelLm(...) fused with a label language model or a lexicon (klstm_ctc_beam_decode_lm; tables: lm.py).
+CtcBeamStream: the same search fed chunk by chunk, the beam kept on the device between the calls (klstm_ctc_beam_stream_step / _emit;
+INTEGRATION.md 3j).
 ctc_mbr_eval: the expected token errors over such n-best lists and their gradient (klstm_ctc_mbr_eval)."""
 import collections
 import ctypes
@@ -288,6 +290,113 @@ def nbest_to_lists(result):
     er = result.errors.cpu().numpy() if result.errors is not None else None
     return [[(h[s, q, :n[s, q]].tolist(), float(sc[s, q]), int(er[s, q]) if er is not None else None) for q in range(c[s])]
             for s in range(len(c))]
+
+
+CtcStreamResult = collections.namedtuple("CtcStreamResult", "hyp hyp_len nbest_count score errors frames stable_len")
+
+
+def ctc_beam_stream_state_bytes(max_frames, S, beam):
+    return _workspace_bytes("klstm_ctc_beam_stream_state_bytes", max_frames, S, beam)
+
+
+def ctc_beam_stream_workspace_bytes(T, S, cands, nbest):
+    return _workspace_bytes("klstm_ctc_beam_stream_workspace_bytes", T, S, cands, nbest)
+
+
+class CtcBeamStream:
+    """CTC prefix beam search over S streams that is fed chunk by chunk: the beam and the prefix tree of every stream stay on the
+    device between the calls (klstm_ctc_beam_stream_step / _emit of include/klstm.h).  K classes, utterances of at most max_frames
+    frames; blank, beam, cands, class_weight and lm as ctc_beam_decode takes them.  For any split of an utterance into chunks, emit
+    returns the bits ctc_beam_decode returns for the frames consumed so far."""
+
+    def __init__(self, S, K, max_frames, blank=0, beam=16, cands=8, class_weight=None, lm=None, device="cuda"):
+        import torch
+        self.S, self.K, self.max_frames = int(S), int(K), int(max_frames)
+        self.blank, self.beam, self.cands = int(blank), int(beam), int(cands)
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        _check_class_weight(class_weight, self.K)
+        assert lm is None or (lm.classes == self.K and lm.next.device == self.device), \
+            "the language model's tables have K columns and live on the stream's device"
+        self.class_weight, self.lm = class_weight, lm
+        self.state_bytes = ctc_beam_stream_state_bytes(self.max_frames, self.S, self.beam)
+        self.state = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)          # zero-filled: nothing yet
+        self._ws, self._emit_ws = {}, None
+
+    def _workspace(self, T, nbest):
+        """one workspace per chunk length"""
+        import torch
+        nbytes = ctc_beam_stream_workspace_bytes(T, self.S, self.cands, nbest)
+        ws = self._ws.get(T)
+        if ws is None:
+            if len(self._ws) >= 8:
+                self._ws.clear()
+            ws = self._ws[T] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return ws, nbytes
+
+    def _ints(self, v, what):
+        import torch
+        if isinstance(v, torch.Tensor) and v.is_cuda:
+            assert v.dtype == torch.int32 and v.is_contiguous() and v.numel() == self.S, what
+            return v
+        v = [int(x) for x in v]
+        assert len(v) == self.S, what
+        return torch.tensor(v, dtype=torch.int32, device=self.device)
+
+    def step(self, net_out, lens, start=None, stream=None):
+        """net_out [T*S, K] float32 CUDA posteriors of one chunk (row t*S + s; a column window with a larger row stride is fine);
+        lens: the S frame counts of THIS chunk (0: the stream is idle in this call and its state is not touched); start: None, or S
+        flags, nonzero where a new utterance begins with this chunk.  A stream whose utterance would exceed max_frames is rejected
+        for the call (emit reports frames = -1 - frames).  Nothing synchronises."""
+        import torch
+        assert net_out.is_cuda and net_out.dtype == torch.float32 and net_out.dim() == 2 and net_out.stride(1) == 1
+        assert net_out.device == self.device and net_out.shape[1] == self.K, "net_out has K columns and lives on the stream's device"
+        assert net_out.shape[0] > 0 and net_out.shape[0] % self.S == 0, "rows must be T * S"
+        T = net_out.shape[0] // self.S
+        lens_dev = self._ints(lens, "lens: S chunk lengths")
+        start_dev = self._ints(start, "start: S flags") if start is not None else None
+        ws, nbytes = self._workspace(T, 1)
+        lm = self.lm
+        _chk(load_library().klstm_ctc_beam_stream_step(
+            net_out.data_ptr(), T, self.S, self.K, net_out.stride(0), lens_dev.data_ptr(), _ptr(start_dev), self.blank,
+            _ptr(self.class_weight), self.beam, self.cands, lm.states if lm else 0, _ptr(lm.next) if lm else None,
+            _ptr(lm.weight) if lm else None, self.state.data_ptr(), ctypes.c_size_t(self.state_bytes), self.max_frames, ws.data_ptr(),
+            ctypes.c_size_t(nbytes), _sp(stream)))
+
+    def emit(self, mode, nbest=1, refs=None, totals=None, stream=None):
+        """The current n-best lists.  mode: S values, 0 skip the stream (nbest_count 0), 1 the list without the LM's final weights, 2
+        with them.  refs, totals as ctc_beam_decode takes them; they cover the streams emitted with mode 2.  Returns
+        CtcStreamResult: the fields of CtcBeamResult (hyp [S, N, max_frames]), frames [S] int32 (frames consumed; -1 - frames after an
+        overflow) and stable_len [S] int32 (the leading tokens of the 1-best that can no longer change).  Changes nothing in the
+        state: call it between any two steps.  Nothing synchronises; nbest_to_lists() does."""
+        import torch
+        dev, S, nbest = self.device, self.S, int(nbest)
+        mode_dev = self._ints(mode, "mode: S values")
+        lab_dev = off_dev = errors = None
+        if refs is not None:
+            lab_dev, off_dev, _ = _packed(refs, S, dev)
+        assert totals is None or refs is not None, "totals need refs"
+        _check_totals(totals, 6)
+        nbytes = ctc_beam_stream_workspace_bytes(1, S, 1, nbest)
+        if self._emit_ws is None:
+            self._emit_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)          # its size does not depend on nbest
+        ws = self._emit_ws
+        hyp = torch.empty(S, max(nbest, 0), self.max_frames, dtype=torch.int32, device=dev)
+        hyp_len = torch.empty(S, max(nbest, 0), dtype=torch.int32, device=dev)
+        count = torch.empty(S, dtype=torch.int32, device=dev)
+        score = torch.empty(S, max(nbest, 0), device=dev)
+        frames = torch.empty(S, dtype=torch.int32, device=dev)
+        stable = torch.zeros(S, dtype=torch.int32, device=dev)
+        if refs is not None:
+            errors = torch.empty(S, max(nbest, 0), dtype=torch.int32, device=dev)
+        lm = self.lm
+        _chk(load_library().klstm_ctc_beam_stream_emit(
+            S, self.K, self.blank, self.beam, nbest, mode_dev.data_ptr(), lm.states if lm else 0, _ptr(lm.final) if lm else None,
+            self.state.data_ptr(), ctypes.c_size_t(self.state_bytes), self.max_frames, hyp.data_ptr(), self.max_frames, hyp_len.data_ptr(),
+            count.data_ptr(), score.data_ptr(), frames.data_ptr(), stable.data_ptr(), _ptr(lab_dev), _ptr(off_dev), _ptr(errors),
+            _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+        return CtcStreamResult(hyp, hyp_len, count, score, errors, frames, stable)
 
 
 CtcMbrResult = collections.namedtuple("CtcMbrResult", "risk diff hyp_logp hyp_post ref_loss")
