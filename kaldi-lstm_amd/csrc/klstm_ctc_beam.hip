@@ -135,6 +135,34 @@ struct BeamLm {                         // the label language model: Q states, n
   const float *weight, *fin;
 };
 
+// The n-best list of a beam, one wave (B <= 64: it sees the whole beam), under k_ctc_beam's epilogue and k_ctc_beam_emit.  tot: the
+// lane's total, or tf = total * flush(final[state]).
+// by tf, ties to the earlier beam position: the integer rank of the frame selection (tf >= 0: the bits order as the values do)
+__device__ __forceinline__ int beam_tf_rank(float tot, int tid) {
+  const unsigned mine = __float_as_uint(tot);
+  int rank = 0;
+  for (int j = 0; j < 64; j++) {
+    const unsigned o = __shfl(mine, j);
+    rank += (o > mine) || (o == mine && j < tid);
+  }
+  return rank;
+}
+// the lane's place in the list (N: not in it) and the list's length: the first N entries with a total > 0 in beam order, or by tf
+// when `ranked` (uniform); none: the first entry alone, dead
+__device__ __forceinline__ int beam_list_slot(float tot, bool ranked, int N, int tid, int &cnt) {
+  const u64 live = __ballot(tot > 0.f);
+  int slot = live ? (tot > 0.f ? __popcll(live & ((1ull << tid) - 1ull)) : N) : (tid == 0 ? 0 : N);
+  if (ranked && live) {
+    const int rank = beam_tf_rank(tot, tid);
+    slot = tot > 0.f ? rank : N;
+  }
+  cnt = live ? min(N, (int)__popcll(live)) : 1;
+  return slot;
+}
+__device__ __forceinline__ float beam_score(float tot, int E) {
+  return tot > 0.f ? (float)badd(log((double)tot), bmul((double)E, 0.6931471805599453)) : -INFINITY;
+}
+
 template <int LM>
 __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, int T, int S, int K, int stride, const int *__restrict__ lens,
                                                   const float *__restrict__ w, int blank, int B, int C, int N, const float *__restrict__ topv,
@@ -366,7 +394,6 @@ __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, i
   __syncthreads();
   __threadfence_block();                                           // the nodes other threads wrote
   if (tid >= 64) return;
-  // the first N entries with a total > 0, in beam order (B <= 64: one wave sees the whole beam); none: the first entry alone, dead
   float tot = tid < Bc ? badd(e_pb[tid], e_pnb[tid]) : 0.f;
   bool ranked = false;
   if constexpr (LM != 0)
@@ -374,26 +401,16 @@ __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, i
       if (tid < Bc) tot = bmul(tot, beam_emit(lm.fin[e_lm[(len & 1) * BEAM_MAXB + tid]]));
       ranked = true;
     }
-  const u64 live = __ballot(tot > 0.f);
-  int slot = live ? (tot > 0.f ? __popcll(live & ((1ull << tid) - 1ull)) : N) : (tid == 0 ? 0 : N);
-  if (ranked && live) {                                            // by tf, ties to the earlier beam position: the integer rank of the frame selection, one wave
-    const unsigned mine = __float_as_uint(tot);                    // tf >= 0: the bits order as the values do
-    int rank = 0;
-    for (int j = 0; j < 64; j++) {
-      const unsigned o = __shfl(mine, j);
-      rank += (o > mine) || (o == mine && j < tid);
-    }
-    slot = tot > 0.f ? rank : N;
-  }
-  const int cnt = live ? min(N, (int)__popcll(live)) : 1;
+  int cnt;
+  const int slot = beam_list_slot(tot, ranked, N, tid, cnt);
   if (tid == 0) count[s] = cnt;
   if (slot >= N) return;
   const size_t o = (size_t)s * N + slot;
   const int ln = e_len[tid];
   hyp_len[o] = ln;
-  if (score) score[o] = tot > 0.f ? (float)badd(log((double)tot), bmul((double)E, 0.6931471805599453)) : -INFINITY;
+  if (score) score[o] = beam_score(tot, E);
   int node = e_node[tid];
-  for (int q = ln - 1; q >= 0; q--) {
+  for (int q = ln - 1; q >= 0; q--) {                              // this launch wrote the nodes
     hyp[o * T + q] = __hip_atomic_load(ntok + nbase + node, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     node = __hip_atomic_load(npar + nbase + node, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -475,6 +492,40 @@ bool ctc_beam_lm_resident(int Q, int K, int B, int C) {
   return (size_t)Q * K * 8 <= (size_t)KLSTM_BEAM_LM_RESIDENT_BYTES;
 }
 
+// the row top-C of T * S rows; zeroes the ticket of k_ctc_beam_tail
+static hipError_t launch_ctc_topc(const float *y, int T, int S, int K, int stride, const int *lens, const float *w, int blank, int C, float *topv,
+                                  int *topi, unsigned *ticket, hipStream_t st) {
+  const int rows = T * S;
+  // measured (DESIGN.md 4k; T = 1000, S = 32, C = 32): 16 lanes per row up to 256 classes (level with the others), a wave per row up to
+  // 2048 (K = 1024: 11.7 against 11.8 and 12.1 ms a call), a workgroup per row beyond: the C passes over a long row stay in the
+  // caches of ONE compute unit (K = 16624: 22.6 against 25.1 ms; 1200 rows: 3.9 against 4.9 ms; level at K = 4096)
+  if (K <= 256)
+    return launch(k_ctc_topc_sub<16>, dim3((rows + 15) / 16), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
+  if (K <= 2048)
+    return launch(k_ctc_topc_sub<64>, dim3((rows + 3) / 4), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
+  return launch(k_ctc_topc_wg, dim3(rows), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
+}
+
+// measured: a list that fits one or two waves is served fastest by just those (2.2 against 2.4 us a frame at B = 4,
+// C = 4); beyond 128 entries four waves, and BEAM_KPT keys a thread need all 256 threads at the largest list
+static int beam_threads(int B, int C) { return B * (C + 1) <= 64 ? 64 : B * (C + 1) <= 128 ? 128 : 256; }
+
+// One of the three instances of a search kernel template, grid (S): without an LM (Q = 0), gathering its tables, or with the tables
+// resident in dynamic LDS (ctc_beam_lm_resident decides).  args: the kernel's own.
+template <class Kern, class... A>
+static hipError_t launch_beam_chain(Kern none, Kern gathered, Kern resident, int S, int K, int B, int C, int Q, hipStream_t st, A... args) {
+  const dim3 grid(S), block(beam_threads(B, C));
+  if (Q == 0) return launch(none, grid, block, 0, st, LaunchProbe{}, args...);
+  if (!ctc_beam_lm_resident(Q, K, B, C)) return launch(gathered, grid, block, 0, st, LaunchProbe{}, args...);
+  // about 32 KB of static LDS come on top: past 64 KB in all the kernel needs the opt-in that launch() applies to the dynamic part alone
+  const size_t dyn = (size_t)Q * K * 8;
+  if (dyn > 32 * 1024 && dyn <= 64 * 1024) {
+    const hipError_t err = raise_lds_limit(reinterpret_cast<const void *>(resident), dyn);
+    if (err != hipSuccess) return err;
+  }
+  return launch(resident, grid, block, dyn, st, LaunchProbe{}, args...);
+}
+
 hipError_t launch_ctc_beam(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
                            int *hyp, int *hyp_len, int *count, float *score, const int *refs, const int *roff, int *errors, double *totals,
                            void *workspace, hipStream_t st) {
@@ -493,39 +544,10 @@ hipError_t launch_ctc_beam_lm(const float *y, int T, int S, int K, int stride, c
   int *ntok = reinterpret_cast<int *>(p + 2 * beam_top_bytes(T, S, C) + beam_node_bytes(T, S, B));
   int *stat = reinterpret_cast<int *>(p + 2 * beam_top_bytes(T, S, C) + 2 * beam_node_bytes(T, S, B));
   unsigned *ticket = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(stat) + 1024);
-  const int rows = T * S;
-  // measured (DESIGN.md 4k; T = 1000, S = 32, C = 32): 16 lanes per row up to 256 classes (level with the others), a wave per row up to
-  // 2048 (K = 1024: 11.7 against 11.8 and 12.1 ms a call), a workgroup per row beyond: the C passes over a long row stay in the
-  // caches of ONE compute unit (K = 16624: 22.6 against 25.1 ms; 1200 rows: 3.9 against 4.9 ms; level at K = 4096)
-  const int g = K <= 256 ? 16 : K <= 2048 ? 64 : 256;
-  // measured: a list that fits one or two waves is served fastest by just those (2.2 against 2.4 us a frame at B = 4,
-  // C = 4); beyond 128 entries four waves, and BEAM_KPT keys a thread need all 256 threads at the largest list
-  const int nthreads = B * (C + 1) <= 64 ? 64 : B * (C + 1) <= 128 ? 128 : 256;
-  hipError_t err;
-  if (g == 16)
-    err = launch(k_ctc_topc_sub<16>, dim3((rows + 15) / 16), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
-  else if (g == 64)
-    err = launch(k_ctc_topc_sub<64>, dim3((rows + 3) / 4), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
-  else
-    err = launch(k_ctc_topc_wg, dim3(rows), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
+  hipError_t err = launch_ctc_topc(y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket, st);
   if (err != hipSuccess) return err;
-  const BeamLm lm{Q, lm_next, lm_weight, lm_final};
-  if (Q == 0)
-    err = launch(k_ctc_beam<0>, dim3(S), dim3(nthreads), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, B, C, N, (const float *)topv,
-                 (const int *)topi, npar, ntok, hyp, hyp_len, count, score, lm);
-  else if (!ctc_beam_lm_resident(Q, K, B, C))
-    err = launch(k_ctc_beam<1>, dim3(S), dim3(nthreads), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, B, C, N, (const float *)topv,
-                 (const int *)topi, npar, ntok, hyp, hyp_len, count, score, lm);
-  else {
-    // about 32 KB of static LDS come on top: past 64 KB in all the kernel needs the opt-in that launch() applies to the dynamic part alone
-    const size_t dyn = (size_t)Q * K * 8;
-    if (dyn > 32 * 1024 && dyn <= 64 * 1024) {
-      err = raise_lds_limit(reinterpret_cast<const void *>(k_ctc_beam<2>), dyn);
-      if (err != hipSuccess) return err;
-    }
-    err = launch(k_ctc_beam<2>, dim3(S), dim3(nthreads), dyn, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, B, C, N,
-                 (const float *)topv, (const int *)topi, npar, ntok, hyp, hyp_len, count, score, lm);
-  }
+  err = launch_beam_chain(k_ctc_beam<0>, k_ctc_beam<1>, k_ctc_beam<2>, S, K, B, C, Q, st, y, T, S, K, stride, lens, w, blank, B, C, N, (const float *)topv,
+                          (const int *)topi, npar, ntok, hyp, hyp_len, count, score, BeamLm{Q, lm_next, lm_weight, lm_final});
   if (err != hipSuccess || !refs) return err;
   return launch(k_ctc_beam_tail, dim3(S), dim3(256), 0, st, LaunchProbe{}, (const int *)hyp, (const int *)hyp_len, (const int *)count, T, S, K, N,
                 blank, refs, roff, errors, totals, stat, ticket);
@@ -536,7 +558,9 @@ hipError_t launch_ctc_beam_lm(const float *y, int T, int S, int K, int stride, c
 // search above is a frame chain whose whole carried state is Bc, E and at most 64 beam entries plus the prefix tree, so it can stop at
 // any frame boundary and go on in another launch with the same bits.  k_ctc_beam_stream<LM> is the frame loop of k_ctc_beam over the
 // frames of one CHUNK, between a load and a store of that state; k_ctc_beam_emit<LM> is its epilogue as a kernel of its own, which
-// only reads the state.  The frame body is a copy of k_ctc_beam's, not shared code: the whole-utterance kernel stays the code it was.
+// only reads the state and shares the list rule (beam_list_slot, beam_score) with it.  The frame body is a copy of k_ctc_beam's, not
+// shared code: one __forceinline__ body under both kernels was built and measured, and missed the speed bar in the small-beam LM
+// cells (profiles/ctc_beam_shared_body_ab.json).  A change to one frame body is made to the other, identically.
 // State of stream s at state + s * beam_state_stride(max_frames, B):
 //   int hdr[16]          [0] BEAM_STARTED once a step began an utterance here, [1] frames consumed, [2] Bc, [3] E, [4] overflow flag
 //   u64 hash[64], ph[64]; int node[64], tok[64], len[64], lm[64]; float pb[64], pnb[64]          the beam entries, Bc of them valid
@@ -850,24 +874,14 @@ __global__ __launch_bounds__(64) void k_ctc_beam_emit(int S, int B, int N, const
       if (tid < Bc) tot = bmul(tot, beam_emit(fin[bs.lm[tid]]));
       ranked = true;
     }
-  const u64 live = __ballot(tot > 0.f);
-  int slot = live ? (tot > 0.f ? __popcll(live & ((1ull << tid) - 1ull)) : N) : (tid == 0 ? 0 : N);
-  if (ranked && live) {
-    const unsigned mine = __float_as_uint(tot);
-    int rank = 0;
-    for (int j = 0; j < 64; j++) {
-      const unsigned o = __shfl(mine, j);
-      rank += (o > mine) || (o == mine && j < tid);
-    }
-    slot = tot > 0.f ? rank : N;
-  }
-  const int cnt = live ? min(N, (int)__popcll(live)) : 1;
+  int cnt;
+  const int slot = beam_list_slot(tot, ranked, N, tid, cnt);
   if (tid == 0) { count[s] = cnt; tcount[s] = m == 2 ? cnt : 0; }
   const int myln = tid < Bc ? bs.len[tid] : 0, mynode = tid < Bc ? bs.node[tid] : 0;
   if (slot < N) {
     const size_t o = (size_t)s * N + slot;
     hyp_len[o] = myln;
-    if (score) score[o] = tot > 0.f ? (float)badd(log((double)tot), bmul((double)E, 0.6931471805599453)) : -INFINITY;
+    if (score) score[o] = beam_score(tot, E);
     int node = mynode;
     for (int q = myln - 1; q >= 0; q--) {
       hyp[o * hyp_stride + q] = bs.ntok[node];
@@ -917,31 +931,10 @@ hipError_t launch_ctc_beam_stream_step(const float *y, int T, int S, int K, int 
   unsigned *ticket = reinterpret_cast<unsigned *>(p + 1024);
   float *topv = reinterpret_cast<float *>(p + BEAM_STREAM_WS_HEAD);
   int *topi = reinterpret_cast<int *>(p + BEAM_STREAM_WS_HEAD + beam_top_bytes(T, S, C));
-  const int rows = T * S;
-  const int g = K <= 256 ? 16 : K <= 2048 ? 64 : 256;              // the rules of launch_ctc_beam_lm
-  const int nthreads = B * (C + 1) <= 64 ? 64 : B * (C + 1) <= 128 ? 128 : 256;
-  hipError_t err;
-  if (g == 16)
-    err = launch(k_ctc_topc_sub<16>, dim3((rows + 15) / 16), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
-  else if (g == 64)
-    err = launch(k_ctc_topc_sub<64>, dim3((rows + 3) / 4), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
-  else
-    err = launch(k_ctc_topc_wg, dim3(rows), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket);
+  const hipError_t err = launch_ctc_topc(y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket, st);
   if (err != hipSuccess) return err;
-  const BeamLm lm{Q, lm_next, lm_weight, nullptr};
-  if (Q == 0)
-    return launch(k_ctc_beam_stream<0>, dim3(S), dim3(nthreads), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, start, w, blank, B, C,
-                  (const float *)topv, (const int *)topi, state, max_frames, lm);
-  if (!ctc_beam_lm_resident(Q, K, B, C))
-    return launch(k_ctc_beam_stream<1>, dim3(S), dim3(nthreads), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, start, w, blank, B, C,
-                  (const float *)topv, (const int *)topi, state, max_frames, lm);
-  const size_t dyn = (size_t)Q * K * 8;
-  if (dyn > 32 * 1024 && dyn <= 64 * 1024) {
-    err = raise_lds_limit(reinterpret_cast<const void *>(k_ctc_beam_stream<2>), dyn);
-    if (err != hipSuccess) return err;
-  }
-  return launch(k_ctc_beam_stream<2>, dim3(S), dim3(nthreads), dyn, st, LaunchProbe{}, y, T, S, K, stride, lens, start, w, blank, B, C,
-                (const float *)topv, (const int *)topi, state, max_frames, lm);
+  return launch_beam_chain(k_ctc_beam_stream<0>, k_ctc_beam_stream<1>, k_ctc_beam_stream<2>, S, K, B, C, Q, st, y, T, S, K, stride, lens, start, w, blank,
+                           B, C, (const float *)topv, (const int *)topi, state, max_frames, BeamLm{Q, lm_next, lm_weight, nullptr});
 }
 
 hipError_t launch_ctc_beam_stream_emit(int S, int K, int blank, int B, int N, const int *mode, int Q, const float *lm_final, const void *state,

@@ -89,7 +89,7 @@ def make_refs(rng, S, K, blank, longest):
 # ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["random", "peaked"])
 @pytest.mark.parametrize("S,T,K,B,C,N", [(1, 50, 29, 8, 6, 8), (4, 120, 12, 16, 8, 5), (8, 60, 12, 8, 5, 3), (32, 24, 7, 4, 3, 2),
-                                         (1, 40, 48, 64, 32, 64)])
+                                         (1, 40, 48, 64, 32, 64), (2, 30, 12, 12, 8, 4)])
 def test_ragged_posteriors(kind, S, T, K, B, C, N):
     rng = np.random.RandomState(S * 1000 + T)
     lens = ragged_lens(rng, S, T)

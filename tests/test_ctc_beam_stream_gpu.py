@@ -150,10 +150,12 @@ def test_streams_on_chunkings_of_their_own_idle_calls_and_restarts():
     assert res.frames.cpu().numpy().tolist() == [60, 60, 60, 60]
 
 
-def test_the_largest_list():
-    """B = 64, C = 32, N = 64: 2112 list entries, 256 threads, BEAM_KPT keys a thread; chunks of 3"""
+@pytest.mark.parametrize("B,C,N", [(64, 32, 64), (12, 8, 12)])
+def test_the_largest_list(B, C, N):
+    """B = 64, C = 32, N = 64: 2112 list entries, 256 threads, BEAM_KPT keys a thread; B = 12, C = 8: 108 entries, 128 threads; chunks
+    of 3"""
     rng = np.random.RandomState(4122)
-    S, T, K, B, C, N = 1, 40, 48, 64, 32, 64
+    S, T, K = 1, 40, 48
     y = softmax_rows(rng, T, S, K)
     h = Harness(S, K, T, 0, B, C, N)
     tw = R.BeamStreamTwin(S, K, T, 0, B, C)
@@ -180,11 +182,13 @@ def test_edge_parameters_and_a_boundary_after_the_first_frame(K, B, C, N):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # with a label language model: tables in LDS and gathered from global memory, final weights, mode 1 against mode 2
 # ---------------------------------------------------------------------------------------------------------------------------------
+# lists of 16, 108, 144, 200 and 768 entries: 64, 128 and 256 threads, one key and several keys a thread
+@pytest.mark.parametrize("K,B,C", [(29, 16, 8), (12, 4, 3), (12, 12, 8), (12, 40, 4), (12, 64, 11)])
 @pytest.mark.parametrize("where", ["resident", "gather"])
-def test_language_model_resident_and_gathered(where):
+def test_language_model_resident_and_gathered(where, K, B, C):
     from tests.test_ctc_beam_lm_gpu import pad_states, resident
     rng = np.random.RandomState(4123)
-    S, T, K, B, C, N = 3, 40, 29, 16, 8, 6
+    S, T, N = 3, 40, min(B, 6)
     lens = [40, 23, 1]
     y = softmax_rows(rng, T, S, K)
     lm = random_bigram(rng, K)
@@ -207,11 +211,10 @@ def test_language_model_resident_and_gathered(where):
         h.check([2, 1, 2], refs=refs)
         finals.append(h.bs.emit([2] * S, nbest=N, refs=refs))
     same(finals[0], finals[1])
-    if where == "resident":
-        tw = R.BeamStreamTwin(S, K, T, 0, B, C, lm=lm)
-        tw.step(y, lens)
-        check_twin(finals[0], tw.emit([2] * S, N))
-        check_twin(h.bs.emit([1] * S, nbest=N), tw.emit([1] * S, N))
+    tw = R.BeamStreamTwin(S, K, T, 0, B, C, lm=lm)
+    tw.step(y, lens)
+    check_twin(finals[0], tw.emit([2] * S, N))
+    check_twin(h.bs.emit([1] * S, nbest=N), tw.emit([1] * S, N))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
