@@ -570,6 +570,56 @@ klstm_status klstm_ctc_mbr_eval(const float *net_out, int T, int S, int K, int s
                                 int diff_stride, float *risk_dev, float *hyp_logp_dev, float *hyp_post_dev, float *ref_loss_dev,
                                 double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/* MMI (CTC-CRF) training against a label language model (include/klstm_nnet.hpp class CtcMmi): the
+ * posterior of the reference under the automaton the beam search multiplies in (klstm_ctc_beam_decode_lm's tables), with the normaliser
+ * summed exactly over EVERY labelling the automaton accepts.  Stateless apart from the note below, asynchronous on hip_stream, decided
+ * entirely on the device.  net_out, stride, lens_dev, labels_dev / label_offsets_dev, blank, diff and diff_stride exactly as
+ * klstm_ctc_eval takes them.  With y = max(net_out, FLT_MIN) (a NaN counts as FLT_MIN) and W(l) = the product of the weights of l's arcs
+ * from state 0 times final of the state it ends in (0 if an arc is absent):
+ *   num  = p_ctc(ref | y)      what klstm_ctc_eval returns as -utt_loss (the same chain, the same bits), kept in double
+ *   Z    = sum over all frame paths pi of W(collapse(pi)) * prod_t y(t, pi_t)
+ *   loss = -log num - log W(ref) + log Z                                       >= 0
+ *   diff(t,k) = gamma_den(t,k) - gamma_ref(t,k) + ctc_weight * (y(t,k) - gamma_ref(t,k))
+ * the gradient with respect to the SOFTMAX INPUT; gamma_den(t,k): the posterior under the denominator that frame t emits class k.
+ * An arc (q, k) is ABSENT when k == blank, weight[q*K + k] is not > 0, or next[q*K + k] is outside [0, lm_states).  final NULL: all ones;
+ * a final weight that is not > 0 counts as 0.
+ * THE GRAPH is built once per language model by klstm_ctc_mmi_graph_build into a caller-owned device buffer of
+ * klstm_ctc_mmi_graph_bytes(lm_states, K) bytes (16-byte aligned; about 56 bytes per table cell) and serves every call after it on
+ * the same or a later-ordered stream: the validated arcs, the denominator states they reach ((LM state, class of the last frame)
+ * pairs), every state's incoming arcs in ascending source state.  The tables are not needed after the build.  The library remembers
+ * per ADDRESS what the last build there was for (states, K, blank); klstm_ctc_mmi_eval returns KLSTM_ERR_ARG for an address nothing
+ * was built at and for a graph built for other values.  A graph is not to be copied to another address.
+ *   ctc_weight           finite, >= 0
+ *   loss_dev [S]         the loss as float; 0 for an idle stream, +inf for a rejected one
+ *   num_logp_dev         NULL, or [S]: float(log num), bit for bit -utt_loss of klstm_ctc_eval; 0 on streams that are not counted
+ *   den_logz_dev         NULL, or [S]: float(log Z); 0 there
+ *   lm_logw_dev          NULL, or [S]: float(log W(ref)); 0 there
+ *   totals_dev           NULL, or five doubles that this minibatch is ADDED to, streams in order: sum of loss, utterances counted,
+ *                        utterances rejected, frames counted, sum of -num_logp
+ *   workspace            klstm_ctc_mmi_workspace_bytes(T, S, K, lm_states, max_label_len) bytes, 16-byte aligned: the reference's rows as
+ *                        klstm_ctc_eval keeps them and 2 * T*S * lm_states*K floats for the denominator's (sized for the densest
+ *                        automaton; the rows written are as long as the graph has states: 2 lm_states for an n-gram model).  The
+ *                        label capacity (and with it the reference chain's launch geometry, which changes no bit) follows from
+ *                        workspace_bytes.  One call at a time per workspace
+ * STATUS of a stream: lens[s] == 0 idle.  REJECTED: whatever klstm_ctc_eval rejects, and a reference with W(ref) = 0.  An empty
+ * reference is legal where final[0] > 0.  Idle and rejected streams get zero diff rows; padding rows (t >= lens[s]) are written as
+ * zero; those rows of net_out are NOT READ.
+ * NUMBERS.  The denominator runs in the log domain in float32, every frame's row taken relative to its own maximum; the maxima are
+ * summed in double.  No term of either recursion is formed by a subtraction ("all of a state's mass but one class" is summed without
+ * that class).  gamma_den and gamma_ref are normalised per frame in double.
+ * Bit-identical from run to run and independent of which stream an utterance sits in: no floating-point atomics.
+ * Limits: S <= 32, T * S <= 65535, K >= 2, lm_states >= 1, lm_states * K <= 16384, max_label_len <= 1023; beyond them KLSTM_ERR_SHAPE
+ * and nothing is launched (the size queries answer 0 and leave the message in klstm_last_error()). */
+size_t klstm_ctc_mmi_graph_bytes(int lm_states, int K);
+klstm_status klstm_ctc_mmi_graph_build(int lm_states, int K, int blank, const int *lm_next_dev, const float *lm_weight_dev,
+                                       const float *lm_final_dev, void *graph, size_t graph_bytes, void *hip_stream);
+size_t klstm_ctc_mmi_workspace_bytes(int T, int S, int K, int lm_states, int max_label_len);
+klstm_status klstm_ctc_mmi_eval(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *labels_dev,
+                                const int *label_offsets_dev, int blank, const void *graph, size_t graph_bytes, int lm_states,
+                                float ctc_weight, float *diff, int diff_stride, float *loss_dev, float *num_logp_dev,
+                                float *den_logz_dev, float *lm_logw_dev, double *totals_dev, void *workspace, size_t workspace_bytes,
+                                void *hip_stream);
+
 /* CTC forced alignment (Viterbi) of whole utterances: the single most probable alignment of the label sequence of stream s to its
  * frames (include/klstm_nnet.hpp class CtcAligner).  Stateless, asynchronous on hip_stream, decided
  * entirely on the device.  net_out, lens_dev, labels_dev / label_offsets_dev and blank exactly as klstm_ctc_eval takes them (row

@@ -1124,6 +1124,110 @@ inline TrainMbrStats TrainMbrWholeUtterances(Nnet *nnet, const std::vector<Utter
                                  [](const UtteranceBatch &, const DeviceMatrix &, const DeviceMatrix &, const CtcBeamDecoder &, const CtcMbr &) {});
 }
 
+// MMI (CTC-CRF) against a label language model (klstm_ctc_mmi_eval, klstm.h): loss = -log p(ref | y) - log W(ref) +
+// log Z with Z summed over every labelling the model accepts -- the model CtcBeamDecoder::SetLanguageModel fuses into the search.  diff
+// is the derivative of loss + ctc_weight * (-log p(ref | y)) with respect to the Softmax INPUT, like Ctc's.  The denominator graph is
+// built on the device when the model is set and serves every Eval after it; the five totals stay on the device.
+class CtcMmi : private CtcCallBase {
+ public:
+  explicit CtcMmi(int32 blank = 0, BaseFloat ctc_weight = 0.f) : CtcCallBase(blank), ctc_weight_(ctc_weight) {}
+
+  // the model is read here and not needed afterwards; setting another one rebuilds the graph
+  void SetLanguageModel(const CtcLabelLm *lm) {
+    KLSTM_ASSERT(lm);
+    states_ = lm->NumStates(); classes_ = lm->NumClasses();
+    graph_bytes_ = klstm_ctc_mmi_graph_bytes(states_, classes_);
+    if (graph_bytes_ == 0) KLSTM_ERR("klstm: " << klstm_last_error());
+    graph_.Grow(graph_bytes_);
+    KCheck(klstm_ctc_mmi_graph_build(states_, classes_, blank_, lm->Next(), lm->Weight(), lm->Final(), graph_.As<void>(), graph_bytes_, nullptr));
+  }
+  // net_out, lens, labels as Ctc::Eval takes them.  Everything is decided on the device (klstm.h): idle and rejected streams (what
+  // Ctc rejects, and labels the model does not accept) get zero diff rows.
+  void Eval(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &labels,
+            DeviceMatrix *diff) {
+    Eval(net_out, num_stream, UploadLens(num_stream, lens), labels, diff);
+  }
+  void Eval(const DeviceMatrix &net_out, int32 num_stream, const int32 *lens_dev, const std::vector<std::vector<int32> > &labels,
+            DeviceMatrix *diff) {
+    const int32 T = NumFrames(net_out, num_stream, lens_dev, labels.size(), false), K = net_out.NumCols();
+    KLSTM_ASSERT(graph_bytes_ > 0 && K == classes_);
+    lab_.Upload(labels);
+    const size_t need = klstm_ctc_mmi_workspace_bytes(T, num_stream, K, states_, (int)std::min(lab_.longest, (size_t)1023));   // longer: the device's to reject
+    void *ws = Workspace(need);
+    loss_.Grow((size_t)num_stream * sizeof(BaseFloat));
+    diff->Resize(net_out.NumRows(), K, false);
+    MatrixView y = net_out.View(), dv = diff->View();
+    KCheck(klstm_ctc_mmi_eval(y.Data(), T, num_stream, K, y.Stride(), lens_dev, lab_.Labels(), lab_.Offsets(), blank_, graph_.As<void>(),
+                              graph_bytes_, states_, ctc_weight_, dv.Data(), dv.Stride(), loss_.As<BaseFloat>(), nullptr, nullptr, nullptr,
+                              tot_.Dev(), ws, need, nullptr));
+    num_stream_ = num_stream;
+  }
+  // the loss of the streams of the last Eval (+inf: rejected, 0: idle).  Synchronises.
+  void UttLoss(std::vector<BaseFloat> *loss) const { loss->assign(num_stream_, 0.f); loss_.Download(loss->data(), loss->size()); }
+  double AvgLoss() const { const double *h = tot_.Read(); return h[0] / h[1]; }                // per utterance counted
+  double AvgLossPerFrame() const { const double *h = tot_.Read(); return h[0] / h[3]; }
+  double NumUtterances() const { return tot_.Read()[1]; }
+  double NumRejected() const { return tot_.Read()[2]; }
+  double Frames() const { return tot_.Read()[3]; }
+  double AvgRefLoss() const { const double *h = tot_.Read(); return h[4] / h[1]; }             // the CTC loss of the references
+  std::string Report() const {
+    const double *h = tot_.Read();
+    std::ostringstream oss;
+    oss << "AvgLoss: " << h[0] / h[1] << " (CtcMmi) per utterance, " << h[0] / h[3] << " per frame, reference CTC loss " << h[4] / h[1]
+        << " per utterance, [" << h[1] << " utterances, " << h[3] << " frames, " << h[2] << " rejected]" << std::endl;
+    return oss.str();
+  }
+ private:
+  BaseFloat ctc_weight_;
+  int32 states_ = 0, classes_ = 0;
+  size_t graph_bytes_ = 0;
+  PackedLabels lab_;
+  DeviceBuffer graph_, loss_;
+  DeviceTotals<5> tot_;
+};
+
+struct TrainMmiOptions {
+  NnetTrainOptions trn_opts;                             // learning rate, momentum
+  int32 num_stream = 4, blank = 0, max_frames = 0;       // max_frames 0: 65535 / num_stream
+  bool sort_by_length = true, crossvalidate = false;
+  BaseFloat ctc_weight = 0.f;
+  const CtcLabelLm *lm = nullptr;                        // the denominator's model (required); not owned
+};
+struct TrainMmiStats {
+  int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
+  double num_rejected = 0, total_frames = 0, seconds = 0, avg_loss = 0, avg_loss_per_frame = 0;     // the MMI loss
+  double avg_ref_loss = 0;                               // the CTC loss of the references, per utterance
+};
+
+// MMI training: Propagate, CtcMmi::Eval against the labels, Backpropagate (not under crossvalidate).  every_batch (optional) sees each
+// minibatch after the Eval: (batch, net_out, obj_diff, mmi).
+template <class F>
+inline TrainMmiStats TrainMmiWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const TrainMmiOptions &o, std::string *report,
+                                             F every_batch) {
+  KLSTM_ASSERT(o.lm);
+  nnet->SetTrainOptions(o.trn_opts);
+  CtcMmi mmi(o.blank, o.ctc_weight);
+  mmi.SetLanguageModel(o.lm);
+  DeviceMatrix obj_diff;
+  TrainMmiStats st = ForEachWholeUtteranceBatch<TrainMmiStats>(nnet, utts, o.num_stream, o.sort_by_length, o.max_frames,
+      [&](const UtteranceBatch &b, const DeviceMatrix &nnet_out) {
+        mmi.Eval(nnet_out, b.num_stream, b.lens, b.labels, &obj_diff);
+        every_batch(b, nnet_out, obj_diff, mmi);
+        if (!o.crossvalidate) nnet->Backpropagate(obj_diff.View(), nullptr);
+      });
+  st.num_rejected = mmi.NumRejected();
+  st.total_frames = mmi.Frames();
+  st.avg_loss = mmi.AvgLoss();
+  st.avg_loss_per_frame = mmi.AvgLossPerFrame();
+  st.avg_ref_loss = mmi.AvgRefLoss();
+  if (report) *report = mmi.Report();
+  return st;
+}
+inline TrainMmiStats TrainMmiWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const TrainMmiOptions &o,
+                                             std::string *report = nullptr) {
+  return TrainMmiWholeUtterances(nnet, utts, o, report, [](const UtteranceBatch &, const DeviceMatrix &, const DeviceMatrix &, const CtcMmi &) {});
+}
+
 struct DecodeCtcOptions {
   int32 num_stream = 4, blank = 0, max_frames = 0;       // max_frames 0: 65535 / num_stream
   bool sort_by_length = true, score = true;              // score: the utterances' labels are references

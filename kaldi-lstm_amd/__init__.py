@@ -20,6 +20,7 @@ from .ctc import CtcBeamResult, ctc_beam_decode, ctc_beam_workspace_bytes, nbest
 from .ctc import CtcLabelLm  # noqa: F401,E402
 from .ctc import CtcBeamStream, CtcStreamResult, ctc_beam_stream_state_bytes, ctc_beam_stream_workspace_bytes  # noqa: F401,E402
 from .ctc import CtcMbrResult, ctc_mbr_eval, ctc_mbr_workspace_bytes  # noqa: F401,E402
+from .ctc import CtcMmiDenominator, CtcMmiResult, ctc_mmi_eval, ctc_mmi_workspace_bytes  # noqa: F401,E402
 from .lm import lexicon_label_lm, ngram_label_lm  # noqa: F401,E402
 from .dp import (DataParallelLstm, DataParallelNnet, LstmDP, AffineDP, SoftmaxXentDP,  # noqa: F401,E402
                  shard_time_major)

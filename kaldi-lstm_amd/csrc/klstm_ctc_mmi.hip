@@ -1,0 +1,524 @@
+// kaldi-lstm_amd/csrc/klstm_ctc_mmi.hip -- MMI (CTC-CRF) against a label-LM denominator (klstm_ctc_mmi_graph_build / klstm_ctc_mmi_eval of
+// include/klstm.h).  loss = -log p_ctc(ref | y) - log W(ref) + log Z, Z summed over every labelling the automaton accepts.
+// THE GRAPH (k_mmi_graph_build, one workgroup, once per language model).  A denominator state is (LM state q, class c of the last
+// frame; c = blank: after a blank or at the start).  Only states that an arc reaches exist: per q the blank state, then the label
+// states (q, k) in ascending k -- the states of one q are contiguous (soff), so R(q) and the sums "all of q but one" are serial
+// passes over a short range.  Forward arcs (absent ones removed) are numbered in (q, k) order (aoff); every label state lists its
+// incoming arcs in ascending source q (ioff / in_src / in_lw); every class lists its states in ascending q (coff / cstate).
+// THE CALL, three launches:
+//   k_mmi_ref      grid (S, 3).  The reference: ctc_chain_run of klstm_ctc_dev.h (y = 0 alpha, y = 1 beta; the bits of klstm_ctc_eval),
+//                  y = 2 the status of the stream, log W(ref) by one walk in double, the links of k_ctc_combine.
+//   k_mmi_den      grid (S, 2).  The denominator's alpha (y = 0) and beta (y = 1) chain of one stream by ONE workgroup of 256 threads:
+//                  log domain, the current row and one row of partial sums in LDS, every frame's row taken relative to its own
+//                  maximum and written to the workspace; the maxima are summed in double.  (The linear domain with a scale per ROW
+//                  is not enough: on saturated posteriors two states of one row that both matter lie a clamped zero, 2^-126, apart.)
+//   k_mmi_combine  grid (T S).  gamma_den from exp(alpha + beta) per class (double, normalised by the frame's own total), gamma_ref from
+//                  the rows k_ctc_combine reads (its sums in double), the row of diff written once.  The rows of frame 0 write the
+//                  per-stream results, row 0 the totals.
+// NO CANCELLATION.  "R(q) - alpha(q, k)" and its mirror in beta are taken relative to the largest term that REMAINS (mmi_all_but_one: the
+// largest member's own sum runs without it, every other member is taken out of a sum that keeps the largest), so neither loses digits.
+// DETERMINISM.  No floating-point atomics; every sum runs in a fixed order (sources ascending q, members ascending class, fixed trees
+// over 256 threads); the maximum is exact in any order.  Nothing depends on the reference chain's launch plan.
+#include <cfloat>
+#include <cmath>
+
+#include "../../include/klstm.h"
+#include "klstm_ctc_dev.h"
+#include "klstm_kernels.h"
+
+namespace klstm {
+
+constexpr int MMI_MAGIC = 0x4d4d4943;
+enum { MH_MAGIC = 0, MH_Q, MH_K, MH_BLANK, MH_N, MH_A, MH_NPAD, MH_WORDS = 64 };
+
+// the graph: hdr [MH_WORDS]; fin [Q] (validated: > 0 or 0); soff, aoff [Q + 1]; per cell (q, k): arc_of (forward arc or -1), has (the
+// state (q, k) or -1); per state: st_q, st_k, st_g (where beta finds "every arc of q but its own": the arc's slot, or A + q), ioff;
+// per incoming arc: in_src (whose partial sum it takes), in_lw (log weight); per forward arc: arc_w, arc_lw, arc_k, arc_dst (a state), arc_q; coff [K + 1],
+// ccur [K] (the build's cursor), cstate [N]
+struct MmiGraph {
+  int *hdr; float *fin; int *soff, *aoff, *arc_of, *has, *st_q, *st_k, *st_g, *ioff, *in_src; float *in_lw, *arc_w, *arc_lw;
+  int *arc_k, *arc_dst, *arc_q, *coff, *ccur, *cstate;
+};
+// the workspace.  info [S]: 0 idle, 1 counted, 2 rejected; logw, numlp, logz [S] double; link [S][2 Lcap]; A, B: the reference's rows
+// [S][T][Npad]; Ad, Bd: the denominator's [S][T rows of the graph's Npad, within T * Dpad floats]
+struct MmiWs { int *info, *link; double *logw, *numlp, *logz; float *A, *B, *Ad, *Bd; int Npad, Lcap, Dpad; };
+
+static size_t mmi_up(size_t v) { return (v + 255) / 256 * 256; }
+
+static size_t mmi_graph_layout(int Q, int K, void *base, MmiGraph *g) {
+  const size_t QK = (size_t)Q * K;
+  char *p = reinterpret_cast<char *>(base);
+  size_t off = 0;
+  auto take = [&](size_t n) { const size_t o = off; off += mmi_up(n * 4); return p + o; };
+  char *hdr = take(MH_WORDS), *fin = take(Q), *soff = take(Q + 1), *aoff = take(Q + 1), *arc_of = take(QK), *has = take(QK);
+  char *st_q = take(QK), *st_k = take(QK), *st_g = take(QK), *ioff = take(QK + 1), *in_src = take(QK), *in_lw = take(QK);
+  char *arc_w = take(QK), *arc_lw = take(QK), *arc_k = take(QK), *arc_dst = take(QK), *arc_q = take(QK), *coff = take(K + 1), *ccur = take(K), *cstate = take(QK);
+  if (g) {
+    auto I = [](char *q) { return reinterpret_cast<int *>(q); };
+    auto F = [](char *q) { return reinterpret_cast<float *>(q); };
+    *g = MmiGraph{I(hdr), F(fin), I(soff), I(aoff), I(arc_of), I(has), I(st_q), I(st_k), I(st_g), I(ioff), I(in_src), F(in_lw), F(arc_w), F(arc_lw),
+                  I(arc_k), I(arc_dst), I(arc_q), I(coff), I(ccur), I(cstate)};
+  }
+  return off;
+}
+size_t ctc_mmi_graph_bytes(int Q, int K) { return mmi_graph_layout(Q, K, nullptr, nullptr); }
+
+static size_t mmi_layout(int T, int S, int K, int Q, int Lcap, void *base, MmiWs *ws) {
+  const size_t npad = ((size_t)2 * Lcap + 1 + 3) / 4 * 4, dpad = ((size_t)Q * K + 3) / 4 * 4;
+  char *p = reinterpret_cast<char *>(base);
+  size_t off = 0;
+  const size_t o_info = off;  off += mmi_up((size_t)S * sizeof(int));
+  const size_t o_logw = off;  off += mmi_up((size_t)S * sizeof(double));
+  const size_t o_numlp = off; off += mmi_up((size_t)S * sizeof(double));
+  const size_t o_logz = off;  off += mmi_up((size_t)S * sizeof(double));
+  const size_t o_link = off;  off += mmi_up((size_t)S * 2 * (size_t)Lcap * sizeof(int));
+  const size_t o_ad = off;    off += (size_t)T * S * dpad * sizeof(float);
+  const size_t o_bd = off;    off += (size_t)T * S * dpad * sizeof(float);
+  const size_t o_a = off;     off += (size_t)T * S * npad * sizeof(float);
+  const size_t o_b = off;     off += (size_t)T * S * npad * sizeof(float);
+  if (ws) {
+    ws->info = reinterpret_cast<int *>(p + o_info);
+    ws->logw = reinterpret_cast<double *>(p + o_logw);
+    ws->numlp = reinterpret_cast<double *>(p + o_numlp);
+    ws->logz = reinterpret_cast<double *>(p + o_logz);
+    ws->link = reinterpret_cast<int *>(p + o_link);
+    ws->Ad = reinterpret_cast<float *>(p + o_ad);
+    ws->Bd = reinterpret_cast<float *>(p + o_bd);
+    ws->A = reinterpret_cast<float *>(p + o_a);
+    ws->B = reinterpret_cast<float *>(p + o_b);
+    ws->Npad = (int)npad;
+    ws->Lcap = Lcap;
+    ws->Dpad = (int)dpad;
+  }
+  return off;
+}
+size_t ctc_mmi_workspace_bytes(int T, int S, int K, int Q, int Lcap) { return mmi_layout(T, S, K, Q, Lcap, nullptr, nullptr); }
+
+int ctc_mmi_label_capacity(int T, int S, int K, int Q, size_t bytes) {      // the longest label sequence a workspace of `bytes` serves; -1: none
+  if (bytes < ctc_mmi_workspace_bytes(T, S, K, Q, 0)) return -1;
+  int lo = 0, hi = 1023;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) / 2;
+    if (ctc_mmi_workspace_bytes(T, S, K, Q, mid) <= bytes) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// the graph.  One workgroup; the counting sorts that fix an ORDER (incoming arcs by source, states by class) are one thread's serial
+// passes over at most Q K entries -- once per language model.
+// ------------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_mmi_graph_build(int Q, int K, int blank, const int *__restrict__ next, const float *__restrict__ weight,
+                                                         const float *__restrict__ final_, MmiGraph g) {
+  __shared__ int sN, sA;
+  const int tid = threadIdx.x, QK = Q * K;
+  for (int c = tid; c < QK; c += 256) g.has[c] = -1;
+  for (int q = tid; q < Q; q += 256) {
+    const float f = final_ ? final_[q] : 1.f;
+    g.fin[q] = f > 0.f ? f : 0.f;
+  }
+  __syncthreads();
+  for (int c = tid; c < QK; c += 256) {                        // which arcs are present, which states they reach (marker 0)
+    const int q = c / K, k = c - q * K, nx = next[c];
+    const bool present = k != blank && weight[c] > 0.f && nx >= 0 && nx < Q;
+    g.arc_of[c] = present ? 0 : -1;
+    if (present) g.has[nx * K + k] = 0;                        // several writers, one value
+  }
+  __syncthreads();
+  for (int q = tid; q < Q; q += 256) {
+    int na = 0, ns = 1;
+    for (int k = 0; k < K; k++) { na += g.arc_of[q * K + k] == 0; ns += g.has[q * K + k] == 0; }
+    g.aoff[q + 1] = na;
+    g.soff[q + 1] = ns;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int a = 0, s = 0;
+    g.aoff[0] = 0; g.soff[0] = 0;
+    for (int q = 0; q < Q; q++) { a += g.aoff[q + 1]; g.aoff[q + 1] = a; s += g.soff[q + 1]; g.soff[q + 1] = s; }
+    sA = a; sN = s;
+  }
+  __syncthreads();
+  const int N = sN, A = sA;
+  for (int q = tid; q < Q; q += 256) {                         // the cells of q belong to this thread alone
+    int a = g.aoff[q], s = g.soff[q];
+    g.st_q[s] = q; g.st_k[s] = blank; s++;
+    for (int k = 0; k < K; k++) {
+      const int c = q * K + k;
+      if (g.arc_of[c] == 0) { g.arc_of[c] = a; g.arc_q[a] = q; g.arc_k[a] = k; g.arc_w[a] = weight[c]; g.arc_lw[a] = logf(weight[c]); a++; }
+      if (g.has[c] == 0) { g.has[c] = s; g.st_q[s] = q; g.st_k[s] = k; s++; }
+    }
+  }
+  __syncthreads();
+  for (int a = tid; a < A; a += 256) g.arc_dst[a] = g.has[next[g.arc_q[a] * K + g.arc_k[a]] * K + g.arc_k[a]];
+  for (int i = tid; i < N; i += 256) {
+    const int q = g.st_q[i], k = g.st_k[i];
+    const int own = k == blank ? -1 : g.arc_of[q * K + k];
+    g.st_g[i] = own >= 0 ? own : A + q;
+    g.ioff[i + 1] = 0;
+  }
+  for (int k = tid; k <= K; k += 256) g.coff[k] = 0;
+  __syncthreads();
+  if (tid == 0) {
+    g.ioff[0] = 0;
+    for (int a = 0; a < A; a++) g.ioff[g.arc_dst[a] + 1]++;
+    for (int i = 0; i < N; i++) g.ioff[i + 1] += g.ioff[i];
+    for (int i = 0; i < N; i++) g.cstate[i] = g.ioff[i];       // (cstate: the cursor of this pass, rewritten below)
+    for (int a = 0; a < A; a++) {                              // arcs ascend in q: so does every state's list
+      const int q = g.arc_q[a], k = g.arc_k[a], own = g.has[q * K + k];
+      const int j = g.cstate[g.arc_dst[a]]++;
+      g.in_src[j] = own >= 0 ? own : g.soff[q];               // "q without (q, k)": that state's partial sum, or all of q
+      g.in_lw[j] = g.arc_lw[a];
+    }
+    for (int i = 0; i < N; i++) g.coff[g.st_k[i] + 1]++;
+    for (int k = 0; k < K; k++) { g.coff[k + 1] += g.coff[k]; g.ccur[k] = g.coff[k]; }
+    for (int i = 0; i < N; i++) g.cstate[g.ccur[g.st_k[i]]++] = i;      // states ascend in q: so does every class's list
+    g.hdr[MH_Q] = Q; g.hdr[MH_K] = K; g.hdr[MH_BLANK] = blank; g.hdr[MH_N] = N; g.hdr[MH_A] = A; g.hdr[MH_NPAD] = (N + 3) / 4 * 4;
+    g.hdr[MH_MAGIC] = MMI_MAGIC;
+  }
+}
+
+__device__ __forceinline__ bool mmi_graph_is(const MmiGraph &g, int Q, int K, int blank) {
+  return g.hdr[MH_MAGIC] == MMI_MAGIC && g.hdr[MH_Q] == Q && g.hdr[MH_K] == K && g.hdr[MH_BLANK] == blank && g.hdr[MH_N] >= Q &&
+         g.hdr[MH_N] <= Q * K && g.hdr[MH_A] >= 0 && g.hdr[MH_A] + Q <= Q * K;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// the reference: klstm_ctc.hip's k_ctc_chain, with the language model's verdict on the labels
+// ------------------------------------------------------------------------------------------------------------------------------------
+template <int NW, int P>
+__global__ __launch_bounds__(64 * NW) void k_mmi_ref(const float *__restrict__ y, int T, int S, int K, int stride, const int *__restrict__ lens,
+                                                     const int *__restrict__ labels, const int *__restrict__ loff, int blank, MmiGraph g, int Q,
+                                                     MmiWs ws) {
+  constexpr int NT = 64 * NW;
+  __shared__ int sm[2];
+  __shared__ int sst;
+  const int s = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
+  const int L = loff[s + 1] - loff[s], len = lens[s];
+  const int *lab = labels + loff[s];
+  int st = ctc_status(len, T, L, ws.Lcap, lab, K, blank, sm);
+
+  if (dir == 2) {
+    if (tid == 0) {
+      double lw = 0.0;
+      if (st == 1) {
+        bool ok = mmi_graph_is(g, Q, K, blank);
+        int q = 0;
+        for (int j = 0; j < L && ok; j++) {                    // ctc_status has seen every label inside [0, K) and none the blank
+          const int a = g.arc_of[q * K + lab[j]];
+          ok = a >= 0;
+          if (ok) { lw += log((double)g.arc_w[a]); q = g.st_q[g.arc_dst[a]]; }
+        }
+        ok = ok && g.fin[q] > 0.f;
+        if (ok) lw += log((double)g.fin[q]);
+        if (!ok) { st = 2; lw = 0.0; }
+      }
+      ws.info[s] = st;
+      ws.logw[s] = lw;
+      sst = st;
+    }
+    __syncthreads();
+    if (sst != 1) return;
+    int *next = ws.link + (size_t)s * 2 * ws.Lcap, *first = next + ws.Lcap;
+    for (int j = tid; j < L; j += NT) first[j] = 1;
+    __syncthreads();
+    for (int j = tid; j < L; j += NT) {
+      const int c = lab[j];
+      int q = j + 1;
+      while (q < L && lab[q] != c) q++;
+      next[j] = q < L ? q : -1;
+      if (q < L) first[q] = 0;                 // position q has exactly one predecessor: one writer
+    }
+    return;
+  }
+  if (st != 1) return;
+  float *gout = (dir ? ws.B : ws.A) + (size_t)s * T * ws.Npad;
+  const double lp = ctc_chain_run<NW, P>(y + (size_t)s * stride, (size_t)S * stride, len, lab, L, blank, dir, gout, ws.Npad);
+  if (dir == 0 && tid == 0) ws.numlp[s] = lp;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// the denominator's chains
+// ------------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float mmi_ly(float v) { return logf(fmaxf(v, FLT_MIN)); }      // a NaN counts as FLT_MIN
+__device__ __forceinline__ double mmi_block_sum(double v, double *sm) {              // fixed tree over 256 threads; sm: 4 doubles
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+// n members v[0 .. n) in the log domain and a term `base` that is never left out:  v[c] <- log(e^base + sum of every member but c), returns
+// log(e^base + sum of all).  The sums are linear, relative to the largest term (the largest member's own sum is taken relative to the
+// runner-up and summed WITHOUT it).  For every other member c the sum is S - e_c: what remains holds the largest term (e^0 = 1) and
+// e_c <= 1 is one of S's own addends, so the difference is >= 1 up to a rounding and loses nothing -- the one subtraction that is
+// safe.  The argument of every log is >= 1.  On the chain: the hardware's exp2 / log2 (as ctc_chain_run's step).
+__device__ __forceinline__ float mmi_all_but_one(int n, float base, float *v) {
+  float m1 = CTC_NEG, m2 = CTC_NEG;
+  int i1 = -1;
+  for (int c = 0; c < n; c++) {
+    const float x = v[c];
+    if (i1 < 0 || x > m1) { m2 = i1 < 0 ? CTC_NEG : m1; m1 = x; i1 = c; } else m2 = fmaxf(m2, x);
+  }
+  const float r1 = fmaxf(m1, base), r2 = fmaxf(m2, base);
+  const float b1 = __expf(base - r1), b2 = __expf(base - r2);
+  float s1 = 0.f, s2 = 0.f;
+  for (int c = 0; c < n; c++) {
+    const float x = v[c];
+    s1 += __expf(x - r1);
+    if (c != i1) s2 += __expf(x - r2);
+  }
+  for (int c = 0; c < n; c++) v[c] = c == i1 ? r2 + __logf(b2 + s2) : r1 + __logf(b1 + fmaxf(s1 - __expf(v[c] - r1), 0.f));
+  return r1 + __logf(b1 + s1);
+}
+// the row's maximum, 0 for a row without a live state
+__device__ __forceinline__ float mmi_row_max(float lmax, float *sm) {
+  const float m = ctc_block_reduce(lmax, sm, true);
+  return m > 0.5f * CTC_NEG ? m : 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_mmi_den(const float *__restrict__ y, int T, int S, int stride, const int *__restrict__ lens, int blank,
+                                                 MmiGraph g, int Q, int K, MmiWs ws) {
+  extern __shared__ float lds[];
+  __shared__ float smf[4];
+  __shared__ double smd[4];
+  const int s = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
+  if (ws.info[s] != 1) return;                                 // (a counted stream has seen the graph's header checked)
+  const int N = g.hdr[MH_N], A = g.hdr[MH_A], Npad = g.hdr[MH_NPAD], len = lens[s];
+  float *cur = lds, *X = lds + (size_t)Q * K;
+  const float *ys = y + (size_t)s * stride;
+  const size_t tstride = (size_t)S * stride;
+  float *gout = (dir ? ws.Bd : ws.Ad) + (size_t)s * T * ws.Dpad;
+
+  if (dir == 0) {
+    double csum = 0.0;                                         // the maxima taken out so far
+    for (int i = tid; i < N; i += 256) cur[i] = i == 0 ? 0.f : CTC_NEG;              // state 0 = (LM state 0, blank)
+    __syncthreads();
+    for (int t = 0; t < len; t++) {
+      const float *yrow = ys + (size_t)t * tstride;
+      for (int q = tid; q < Q; q += 256) {                     // X[blank state] = log R(q); X[label state] = log (R(q) without that state)
+        const int s0 = g.soff[q], n = g.soff[q + 1] - s0;
+        for (int c = 0; c < n; c++) X[s0 + c] = cur[s0 + c];
+        const float tot = mmi_all_but_one(n, CTC_NEG, X + s0);
+        X[s0] = tot;
+      }
+      __syncthreads();
+      float lmax = CTC_NEG;
+      for (int i = tid; i < N; i += 256) {
+        const int k = g.st_k[i];
+        float v;
+        if (k == blank) v = X[i];
+        else {
+          const int j0 = g.ioff[i], j1 = g.ioff[i + 1];
+          float m = cur[i];
+          for (int j = j0; j < j1; j++) m = fmaxf(m, g.in_lw[j] + X[g.in_src[j]]);
+          float sum = __expf(cur[i] - m);
+          for (int j = j0; j < j1; j++) sum += __expf(g.in_lw[j] + X[g.in_src[j]] - m);
+          v = m + __logf(sum);
+        }
+        v += mmi_ly(yrow[k]);
+        cur[i] = v;                                            // in place: the step reads no other thread's cell of cur
+        lmax = fmaxf(lmax, v);
+      }
+      const float M = mmi_row_max(lmax, smf);
+      csum += (double)M;
+      for (int i = tid; i < N; i += 256) {
+        const float v = fmaxf(cur[i] - M, CTC_NEG);
+        cur[i] = v;
+        gout[(size_t)t * Npad + i] = v;
+      }
+      __syncthreads();
+    }
+    float lmax = CTC_NEG;
+    for (int i = tid; i < N; i += 256) {
+      const float f = g.fin[g.st_q[i]];
+      const float v = f > 0.f ? cur[i] + logf(f) : CTC_NEG;
+      X[i] = v;                                                // (own cells)
+      lmax = fmaxf(lmax, v);
+    }
+    const float M = mmi_row_max(lmax, smf);
+    double z = 0.0;
+    for (int i = tid; i < N; i += 256) z += (double)expf(X[i] - M);
+    z = mmi_block_sum(z, smd);
+    if (tid == 0) ws.logz[s] = csum + (double)M + log(z);
+    return;
+  }
+
+  {
+    float lmax = CTC_NEG;
+    for (int i = tid; i < N; i += 256) {
+      const float f = g.fin[g.st_q[i]];
+      const float v = f > 0.f ? logf(f) : CTC_NEG;
+      cur[i] = v;
+      lmax = fmaxf(lmax, v);
+    }
+    const float M = mmi_row_max(lmax, smf);
+    for (int i = tid; i < N; i += 256) {
+      const float v = fmaxf(cur[i] - M, CTC_NEG);
+      cur[i] = v;
+      gout[(size_t)(len - 1) * Npad + i] = v;
+    }
+    __syncthreads();
+  }
+  for (int t = len - 2; t >= 0; t--) {
+    const float *yrow = ys + (size_t)(t + 1) * tstride;
+    const float lyb = mmi_ly(yrow[blank]);
+    for (int a = tid; a < A; a += 256) X[a] = (g.arc_lw[a] + mmi_ly(yrow[g.arc_k[a]])) + cur[g.arc_dst[a]];
+    __syncthreads();
+    for (int q = tid; q < Q; q += 256) {                       // X[arc] = log(blank term + every arc of q but this one); X[A + q]: all of them
+      const int a0 = g.aoff[q], n = g.aoff[q + 1] - a0;
+      X[A + q] = mmi_all_but_one(n, lyb + cur[g.soff[q]], X + a0);
+    }
+    __syncthreads();
+    float lmax = CTC_NEG;
+    for (int i = tid; i < N; i += 256) {
+      const int k = g.st_k[i];
+      float v = X[g.st_g[i]];
+      if (k != blank) {
+        const float own = mmi_ly(yrow[k]) + cur[i], m = fmaxf(v, own);
+        v = m + __logf(__expf(v - m) + __expf(own - m));
+      }
+      cur[i] = v;
+      lmax = fmaxf(lmax, v);
+    }
+    const float M = mmi_row_max(lmax, smf);
+    for (int i = tid; i < N; i += 256) {
+      const float v = fmaxf(cur[i] - M, CTC_NEG);
+      cur[i] = v;
+      gout[(size_t)t * Npad + i] = v;
+    }
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// the rows of diff
+// ------------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float mmi_stream_loss(const MmiWs &ws, int q) {
+  const int st = ws.info[q];
+  return st == 1 ? (float)(-ws.numlp[q] - ws.logw[q] + ws.logz[q]) : st == 2 ? INFINITY : 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_mmi_combine(const float *__restrict__ y, int T, int S, int K, int stride, const int *__restrict__ lens,
+                                                     const int *__restrict__ labels, const int *__restrict__ loff, int blank, float lam,
+                                                     float *__restrict__ diff, int dstride, float *__restrict__ loss,
+                                                     float *__restrict__ num_logp, float *__restrict__ den_logz, float *__restrict__ lm_logw,
+                                                     double *__restrict__ totals, MmiGraph g, int Q, MmiWs ws, int vec) {
+  extern __shared__ double pd[];               // the row under construction, one double per class
+  __shared__ float gr[2048];
+  __shared__ float sm[4];
+  __shared__ double smd[4];
+  const int r = blockIdx.x, s = r % S, t = r / S, tid = threadIdx.x;
+  if (r < S && tid == 0) {                     // frame 0 of stream r: its results
+    const bool on = ws.info[r] == 1;
+    loss[r] = mmi_stream_loss(ws, r);
+    if (num_logp) num_logp[r] = on ? (float)ws.numlp[r] : 0.f;
+    if (den_logz) den_logz[r] = on ? (float)ws.logz[r] : 0.f;
+    if (lm_logw) lm_logw[r] = on ? (float)ws.logw[r] : 0.f;
+  }
+  if (r == 0 && totals && tid == 0) {          // the minibatch's statistics, streams in order
+    double ls = 0, cnt = 0, rej = 0, frames = 0, nl = 0;
+    for (int q = 0; q < S; q++) {
+      const int st = ws.info[q];
+      if (st == 1) { ls += (double)mmi_stream_loss(ws, q); cnt += 1; frames += lens[q]; nl += (double)(float)(-ws.numlp[q]); }
+      else if (st == 2) rej += 1;
+    }
+    totals[0] += ls; totals[1] += cnt; totals[2] += rej; totals[3] += frames; totals[4] += nl;
+  }
+  float *dp = diff + (size_t)r * dstride;
+  const float *yp = y + (size_t)r * stride;
+  if (ws.info[s] != 1 || t >= lens[s]) {
+    if (vec) for (int c = tid * 4; c < K; c += 1024) *reinterpret_cast<float4 *>(dp + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+    else for (int c = tid; c < K; c += 256) dp[c] = 0.f;
+    return;
+  }
+  // gamma_den: exp(alpha + beta - the frame's maximum) per class, states in ascending q, normalised by the frame's own total
+  const int Npad = g.hdr[MH_NPAD];
+  const float *ad = ws.Ad + (size_t)s * T * ws.Dpad + (size_t)t * Npad, *bd = ws.Bd + (size_t)s * T * ws.Dpad + (size_t)t * Npad;
+  float dmx = CTC_NEG;
+  for (int i = tid; i < g.hdr[MH_N]; i += 256) dmx = fmaxf(dmx, ad[i] + bd[i]);
+  dmx = ctc_block_reduce(dmx, sm, true);
+  double part = 0.0, pb = 0.0;
+  for (int k = tid; k < K; k += 256) {
+    double sk = 0.0;
+    if (k != blank) {
+      const int j1 = g.coff[k + 1];
+      for (int j = g.coff[k]; j < j1; j++) { const int i = g.cstate[j]; sk += (double)expf(ad[i] + bd[i] - dmx); }
+    }
+    pd[k] = sk;
+    part += sk;
+  }
+  for (int q = tid; q < Q; q += 256) { const int i = g.soff[q]; pb += (double)expf(ad[i] + bd[i] - dmx); }
+  pb = mmi_block_sum(pb, smd);
+  part = mmi_block_sum(part, smd);
+  const double inv_tot = 1.0 / (part + pb);
+  for (int k = tid; k < K; k += 256) pd[k] = (k == blank ? pb : pd[k]) * inv_tot + (lam > 0.f ? (double)lam * (double)yp[k] : 0.0);
+  // gamma_ref as k_ctc_combine takes it
+  const int L = loff[s + 1] - loff[s], N = 2 * L + 1;
+  const int *lab = labels + loff[s];
+  const float *a = ws.A + ((size_t)s * T + t) * ws.Npad, *bt = ws.B + ((size_t)s * T + t) * ws.Npad;
+  float mx = CTC_NEG;
+  for (int i = tid; i < N; i += 256) { const float v = a[i] + bt[i]; gr[i] = v; mx = fmaxf(mx, v); }
+  mx = ctc_block_reduce(mx, sm, true);
+  double sall = 0.0, seven = 0.0;              // (in double: the row of gamma_ref then sums to 1 beyond float32, as gamma_den's does)
+  for (int i = tid; i < N; i += 256) {         // 256 is even: a thread's states are all even or all odd
+    const float e = expf(gr[i] - mx);
+    gr[i] = e;
+    sall += (double)e;
+    seven += (i & 1) ? 0.0 : (double)e;
+  }
+  sall = mmi_block_sum(sall, smd);
+  seven = mmi_block_sum(seven, smd);
+  const double cref = (1.0 + (double)lam) / sall;
+  __syncthreads();                             // gr and pd complete
+  if (tid == 0) pd[blank] -= cref * seven;
+  const int *next = ws.link + (size_t)s * 2 * ws.Lcap, *first = next + ws.Lcap;
+  for (int j = tid; j < L; j += 256) {
+    if (!first[j]) continue;
+    double acc = (double)gr[2 * j + 1];
+    for (int q = next[j]; q >= 0; q = next[q]) acc += (double)gr[2 * q + 1];
+    pd[lab[j]] -= cref * acc;                  // the only thread on that class
+  }
+  __syncthreads();
+  if (vec) for (int c = tid * 4; c < K; c += 1024)
+    *reinterpret_cast<float4 *>(dp + c) = make_float4((float)pd[c], (float)pd[c + 1], (float)pd[c + 2], (float)pd[c + 3]);
+  else for (int c = tid; c < K; c += 256) dp[c] = (float)pd[c];
+}
+
+hipError_t launch_ctc_mmi_graph(int Q, int K, int blank, const int *next, const float *weight, const float *final_, void *graph, hipStream_t st) {
+  MmiGraph g;
+  mmi_graph_layout(Q, K, graph, &g);
+  return launch(k_mmi_graph_build, dim3(1), dim3(256), 0, st, LaunchProbe{}, Q, K, blank, next, weight, final_, g);
+}
+
+static bool mmi_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+hipError_t launch_ctc_mmi(const float *y, int T, int S, int K, int stride, const int *lens, const int *labels, const int *loff, int blank,
+                          const void *graph, int Q, float lam, float *diff, int dstride, float *loss, float *num_logp, float *den_logz,
+                          float *lm_logw, double *totals, void *workspace, int Lcap, hipStream_t st) {
+  MmiGraph g;
+  mmi_graph_layout(Q, K, const_cast<void *>(graph), &g);
+  MmiWs ws;
+  mmi_layout(T, S, K, Q, Lcap, workspace, &ws);
+  const int N = 2 * Lcap + 1;
+  // the geometry of klstm_ctc_eval's chain, 16 * waves + states per thread
+  const int plan = N <= 64 ? 16 * 1 + 1 : N <= 256 ? 16 * 4 + 1 : N <= 512 ? 16 * 4 + 2 : N <= 1024 ? 16 * 16 + 1 : 16 * 16 + 2;
+  hipError_t err;
+#define MMI_CASE(NW, P)                                                                                                                      \
+  case 16 * NW + P:                                                                                                                          \
+    err = launch(k_mmi_ref<NW, P>, dim3(S, 3), dim3(64 * NW), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, labels, loff, blank, g, Q, ws); \
+    break;
+  switch (plan) {
+    MMI_CASE(1, 1) MMI_CASE(4, 1) MMI_CASE(4, 2) MMI_CASE(16, 1) MMI_CASE(16, 2)
+    default: return hipErrorInvalidValue;
+  }
+#undef MMI_CASE
+  if (err != hipSuccess) return err;
+  err = launch(k_mmi_den, dim3(S, 2), dim3(256), (size_t)2 * Q * K * sizeof(float), st, LaunchProbe{}, y, T, S, stride, lens, blank, g, Q, K, ws);
+  if (err != hipSuccess) return err;
+  const int vec = K % 4 == 0 && stride % 4 == 0 && dstride % 4 == 0 && mmi_al16(y) && mmi_al16(diff);
+  return launch(k_mmi_combine, dim3(T * S), dim3(256), (size_t)K * sizeof(double), st, LaunchProbe{}, y, T, S, K, stride, lens, labels, loff,
+                blank, lam, diff, dstride, loss, num_logp, den_logz, lm_logw, totals, g, Q, ws, vec);
+}
+
+}  // namespace klstm

@@ -2282,6 +2282,82 @@ klstm_status klstm_ctc_mbr_eval(const float *net_out, int T, int S, int K, int s
                         ref_loss_dev, totals_dev, workspace, lcap, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
+// ---- MMI against a label-LM denominator.  What a graph was built for is remembered per address: the header lives on the device and
+// the calls do not wait for it, so klstm_ctc_mmi_eval knows a graph by where klstm_ctc_mmi_graph_build put it ----
+struct MmiGraphNote { int Q, K, blank; };
+static std::mutex mmi_graph_mu;
+static std::map<const void *, MmiGraphNote> mmi_graphs;
+static bool ctc_mmi_lm_ok(int lm_states, int K) { return lm_states >= 1 && K >= 2 && (long)lm_states * K <= 16384; }
+size_t klstm_ctc_mmi_graph_bytes(int lm_states, int K) {
+  if (!ctc_mmi_lm_ok(lm_states, K)) {
+    fail(KLSTM_ERR_SHAPE, "klstm_ctc_mmi_graph_bytes: %d language-model states of %d classes outside 1 <= states, 2 <= K, states * K <= 16384", lm_states, K);
+    return 0;
+  }
+  return ctc_mmi_graph_bytes(lm_states, K);
+}
+klstm_status klstm_ctc_mmi_graph_build(int lm_states, int K, int blank, const int *lm_next_dev, const float *lm_weight_dev,
+                                       const float *lm_final_dev, void *graph, size_t graph_bytes, void *hip_stream) {
+  const char *fn = "klstm_ctc_mmi_graph_build";
+  if (lm_states <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "%s: bad size (%d language-model states, K %d)", fn, lm_states, K);
+  if (!ctc_mmi_lm_ok(lm_states, K))
+    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 2 <= K, states * K <= 16384", fn, lm_states, K);
+  if (!lm_next_dev || !lm_weight_dev || !graph) return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
+  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "%s: blank %d outside [0, %d)", fn, blank, K);
+  if ((reinterpret_cast<uintptr_t>(graph) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: graph must be 16-byte aligned", fn);
+  if (graph_bytes < ctc_mmi_graph_bytes(lm_states, K))
+    return fail(KLSTM_ERR_ARG, "%s: graph of %zu bytes is below klstm_ctc_mmi_graph_bytes(%d, %d) = %zu", fn, graph_bytes, lm_states, K,
+                ctc_mmi_graph_bytes(lm_states, K));
+  {
+    std::lock_guard<std::mutex> lk(mmi_graph_mu);
+    mmi_graphs.erase(graph);
+  }
+  HIPCHK(launch_ctc_mmi_graph(lm_states, K, blank, lm_next_dev, lm_weight_dev, lm_final_dev, graph, (hipStream_t)hip_stream));
+  std::lock_guard<std::mutex> lk(mmi_graph_mu);
+  mmi_graphs[graph] = MmiGraphNote{lm_states, K, blank};
+  return KLSTM_OK;
+}
+size_t klstm_ctc_mmi_workspace_bytes(int T, int S, int K, int lm_states, int max_label_len) {
+  const char *fn = "klstm_ctc_mmi_workspace_bytes";
+  if (!ctc_query_ok(fn, "label", T, S, max_label_len)) return 0;
+  if (!ctc_mmi_lm_ok(lm_states, K)) {
+    fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 1 <= states, 2 <= K, states * K <= 16384", fn, lm_states, K);
+    return 0;
+  }
+  return ctc_mmi_workspace_bytes(T, S, K, lm_states, max_label_len);
+}
+klstm_status klstm_ctc_mmi_eval(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *labels_dev,
+                                const int *label_offsets_dev, int blank, const void *graph, size_t graph_bytes, int lm_states,
+                                float ctc_weight, float *diff, int diff_stride, float *loss_dev, float *num_logp_dev, float *den_logz_dev,
+                                float *lm_logw_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  const char *fn = "klstm_ctc_mmi_eval";
+  if (T <= 0 || S <= 0 || K <= 0 || lm_states <= 0) return fail(KLSTM_ERR_ARG, "%s: bad size (T %d, streams %d, K %d, %d language-model states)", fn, T, S, K, lm_states);
+  if (!ctc_mmi_lm_ok(lm_states, K))
+    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 2 <= K, states * K <= 16384", fn, lm_states, K);
+  if (!(ctc_weight >= 0.f) || !std::isfinite(ctc_weight)) return fail(KLSTM_ERR_ARG, "%s: CTC weight %g is not a finite number >= 0", fn, (double)ctc_weight);
+  const bool null = !net_out || !lens_dev || !labels_dev || !label_offsets_dev || !graph || !diff || !loss_dev || !workspace;
+  const klstm_status st = ctc_call_check(fn, T, S, K, 2, null ? "null argument" : nullptr, blank, stride < diff_stride ? stride : diff_stride,
+                                         net_out == diff ? "diff == net_out (the posteriors are read while diff is written)" : nullptr, workspace);
+  if (st != KLSTM_OK) return st;
+  if ((reinterpret_cast<uintptr_t>(graph) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: graph must be 16-byte aligned", fn);
+  if (graph_bytes < ctc_mmi_graph_bytes(lm_states, K))
+    return fail(KLSTM_ERR_ARG, "%s: graph of %zu bytes is below klstm_ctc_mmi_graph_bytes(%d, %d) = %zu", fn, graph_bytes, lm_states, K,
+                ctc_mmi_graph_bytes(lm_states, K));
+  {
+    std::lock_guard<std::mutex> lk(mmi_graph_mu);
+    const auto it = mmi_graphs.find(graph);
+    if (it == mmi_graphs.end()) return fail(KLSTM_ERR_ARG, "%s: no graph was built at this address (klstm_ctc_mmi_graph_build)", fn);
+    if (it->second.Q != lm_states || it->second.K != K || it->second.blank != blank)
+      return fail(KLSTM_ERR_ARG, "%s: the graph was built for %d states, K %d, blank %d, not for %d states, K %d, blank %d", fn, it->second.Q,
+                  it->second.K, it->second.blank, lm_states, K, blank);
+  }
+  const int lcap = ctc_mmi_label_capacity(T, S, K, lm_states, workspace_bytes);
+  if (lcap < 0)
+    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_mmi_workspace_bytes(%d, %d, %d, %d, 0) = %zu", fn, workspace_bytes, T, S,
+                K, lm_states, ctc_mmi_workspace_bytes(T, S, K, lm_states, 0));
+  HIPCHK(launch_ctc_mmi(net_out, T, S, K, stride, lens_dev, labels_dev, label_offsets_dev, blank, graph, lm_states, ctc_weight, diff,
+                        diff_stride, loss_dev, num_logp_dev, den_logz_dev, lm_logw_dev, totals_dev, workspace, lcap, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
 size_t klstm_ctc_align_workspace_bytes(int T, int S, int max_label_len) {
   return ctc_query_ok("klstm_ctc_align_workspace_bytes", "label", T, S, max_label_len) ? ctc_align_workspace_bytes(T, S, max_label_len) : 0;
 }

@@ -365,6 +365,17 @@ hipError_t launch_ctc_mbr(const float *y, int T, int S, int K, int stride, const
                           const int *hyp_len, const int *count, const int *errors, int N, const int *ref, const int *roff, float kappa,
                           float lam, float *diff, int dstride, float *risk, float *hyp_logp, float *hyp_post, float *ref_loss,
                           double *totals, void *workspace, int Lcap, hipStream_t st);
+// MMI (CTC-CRF) against a label-LM denominator (klstm_ctc_mmi.hip): klstm_ctc_mmi_graph_build / klstm_ctc_mmi_eval of include/klstm.h.
+// The graph: the reachable denominator states of Q LM states x K classes with their arcs by source and by destination.  The
+// workspace: statuses and log weights per stream, the reference's links and rows as klstm_ctc_eval keeps them, then the
+// denominator's alpha and beta rows [S][T][Q K].  Lcap = the label length the workspace was sized for.
+size_t ctc_mmi_graph_bytes(int Q, int K);
+hipError_t launch_ctc_mmi_graph(int Q, int K, int blank, const int *next, const float *weight, const float *final_, void *graph, hipStream_t st);
+size_t ctc_mmi_workspace_bytes(int T, int S, int K, int Q, int Lcap);
+int ctc_mmi_label_capacity(int T, int S, int K, int Q, size_t bytes);
+hipError_t launch_ctc_mmi(const float *y, int T, int S, int K, int stride, const int *lens, const int *labels, const int *loff, int blank,
+                          const void *graph, int Q, float lam, float *diff, int dstride, float *loss, float *num_logp, float *den_logz,
+                          float *lm_logw, double *totals, void *workspace, int Lcap, hipStream_t st);
 // CTC forced alignment (klstm_ctc_align.hip): klstm_ctc_align / klstm_ctc_align_workspace_bytes of include/klstm.h.  The workspace: four
 // ints per stream for the totals, then per stream, frame and group of 32 lattice states two words of back-pointer bits.  Lcap = the
 // label length the workspace was sized for (the chain's geometry follows from it).

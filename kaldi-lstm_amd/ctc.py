@@ -6,7 +6,8 @@ ctc_beam_decode: prefix beam search, n-best lists with scores and edit distances
 lm=CtcLabelLm(...) fused with a label language model or a lexicon (klstm_ctc_beam_decode_lm; tables: lm.py).
 CtcBeamStream: the same search fed chunk by chunk, the beam kept on the device between the calls (klstm_ctc_beam_stream_step / _emit;
 INTEGRATION.md 3j).
-ctc_mbr_eval: the expected token errors over such n-best lists and their gradient (klstm_ctc_mbr_eval)."""
+ctc_mbr_eval: the expected token errors over such n-best lists and their gradient (klstm_ctc_mbr_eval).
+CtcMmiDenominator / ctc_mmi_eval: MMI (CTC-CRF) against the language model the beam search uses (klstm_ctc_mmi_eval)."""
 import collections
 import ctypes
 
@@ -452,3 +453,56 @@ def ctc_mbr_eval(net_out, lens, nbest, refs=None, blank=0, risk_scale=1.0, ctc_w
                                 float(ctc_weight), diff.data_ptr(), diff.stride(0), risk.data_ptr(), hyp_logp.data_ptr(), hyp_post.data_ptr(),
                                 _ptr(ref_loss), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
     return CtcMbrResult(risk, diff, hyp_logp, hyp_post, ref_loss)
+
+
+CtcMmiResult = collections.namedtuple("CtcMmiResult", "loss diff num_logp den_logz lm_logw")
+
+
+def ctc_mmi_workspace_bytes(T, S, K, lm_states, max_label_len):
+    return _workspace_bytes("klstm_ctc_mmi_workspace_bytes", T, S, K, lm_states, max_label_len)
+
+
+class CtcMmiDenominator:
+    """The denominator graph of ctc_mmi_eval for one language model: built on the device from the tables of a CtcLabelLm (the object
+    ctc_beam_decode(lm=...) takes) and kept for every minibatch of a training run (klstm_ctc_mmi_graph_build of include/klstm.h).
+    Owns the graph's buffer; the tables are not needed afterwards."""
+
+    def __init__(self, lm, blank=0, stream=None):
+        import torch
+        self.states, self.classes, self.blank = lm.states, lm.classes, int(blank)
+        self.device = lm.next.device
+        n = getattr(load_library(), "klstm_ctc_mmi_graph_bytes")(self.states, self.classes)
+        if n == 0:
+            _chk(2)
+        self.graph_bytes = n
+        self.graph = torch.empty(n, dtype=torch.uint8, device=self.device)
+        _chk(load_library().klstm_ctc_mmi_graph_build(self.states, self.classes, self.blank, lm.next.data_ptr(), lm.weight.data_ptr(),
+                                                     _ptr(lm.final), self.graph.data_ptr(), ctypes.c_size_t(n), _sp(stream)))
+
+
+def ctc_mmi_eval(net_out, lens, labels, den, ctc_weight=0.0, diff=None, totals=None, stream=None):
+    """MMI (CTC-CRF) against the language model of `den` (a CtcMmiDenominator): net_out, lens, labels as ctc_eval takes them.  loss =
+    -log p_ctc(labels | y) - log W(labels) + log Z with Z summed over every labelling the model accepts; diff = gamma_den - gamma_ref +
+    ctc_weight * (y - gamma_ref), the gradient with respect to the softmax input.  Returns CtcMmiResult(loss [S] float32 (0 idle, +inf
+    rejected: what ctc_eval rejects, and labels the model does not accept), diff [T*S, K], num_logp [S] (the bits of -utt_loss of
+    ctc_eval), den_logz [S], lm_logw [S]; the last three 0 on streams that are not counted).  totals: a float64[5] CUDA tensor that sum
+    of loss, utterances counted, utterances rejected, frames and sum of -num_logp are added to.  Nothing synchronises."""
+    import torch
+    lib = load_library()
+    dev = net_out.device
+    lens_dev, S, T, K = _shape(net_out, lens)
+    assert den.classes == K and den.device == dev, "the denominator was built for K classes on net_out's device"
+    lab_dev, off_dev, longest = _packed(labels, S, dev)
+    if diff is None:
+        diff = torch.empty(T * S, K, device=dev)
+    assert diff.is_cuda and diff.dtype == torch.float32 and diff.shape == (T * S, K) and diff.stride(1) == 1
+    _check_totals(totals, 5)
+    cap = min(longest, 1023)                                            # a longer sequence is the device's to reject
+    nbytes = ctc_mmi_workspace_bytes(T, S, K, den.states, cap)
+    ws = _workspace("mmi", (T, S, K, den.states, cap), nbytes, dev)
+    loss, num_logp, den_logz, lm_logw = (torch.empty(S, device=dev) for _ in range(4))
+    _chk(lib.klstm_ctc_mmi_eval(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), lab_dev.data_ptr(), off_dev.data_ptr(),
+                                den.blank, den.graph.data_ptr(), ctypes.c_size_t(den.graph_bytes), den.states, float(ctc_weight),
+                                diff.data_ptr(), diff.stride(0), loss.data_ptr(), num_logp.data_ptr(), den_logz.data_ptr(),
+                                lm_logw.data_ptr(), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    return CtcMmiResult(loss, diff, num_logp, den_logz, lm_logw)
