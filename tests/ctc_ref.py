@@ -6,6 +6,7 @@
                    tests/test_ctc_gpu.py, too much for the bars of the small suite, which uses truth64()
   truth64()        loss and diff of the RAW float32 posteriors as the kernel defines them, float64 throughout: emissions
                    log(max(double(y), FLT_MIN)), no renormalisation, loss = -log sum_paths prod_t y, diff = y - gamma
+  truth_core()     its per-utterance core on float64 posteriors taken as given: (log p, gamma)
   brute_force()    -log of the sum over ALL alignments, float64, for tiny cases: pins oracle() and truth64() independently of torch
   norm_twin()      the kernel's own recursion (normalised log domain, offsets summed in double) in numpy float32
   infeasible()     which streams klstm_ctc_eval must reject, from the lengths and labels alone
@@ -77,9 +78,10 @@ def _lattice(lab, blank):
     return ext, skip
 
 
-def _truth_one(y, lab, blank):
-    """one feasible utterance, y [n, K] float32 (valid frames only) -> (loss, diff [n, K]) in float64, log domain throughout"""
-    yd = np.asarray(y, dtype=np.float32).astype(np.float64)
+def truth_core(yd, lab, blank):
+    """one feasible utterance, yd [n, K] FLOAT64 posteriors taken as given (valid frames only, clamped at FLT_MIN, not renormalised)
+    -> (log p, gamma [n, K]) in float64, log domain throughout.  The core of truth64(), and of tests/ctc_mbr_ref.objective64()"""
+    yd = np.asarray(yd, dtype=np.float64)
     n, K = yd.shape
     ext, skip = _lattice(lab, blank)
     N = ext.size
@@ -103,6 +105,13 @@ def _truth_one(y, lab, blank):
         g = g - (m + np.log(np.exp(g - m).sum(1, keepdims=True)))           # per frame: log sum_i alpha beta = log p on every frame
     gam = np.zeros((n, K))
     np.add.at(gam, (np.arange(n)[:, None], ext[None, :]), np.exp(g))
+    return logp, gam
+
+
+def _truth_one(y, lab, blank):
+    """one feasible utterance, y [n, K] float32 (valid frames only) -> (loss, diff [n, K]) in float64"""
+    yd = np.asarray(y, dtype=np.float32).astype(np.float64)
+    logp, gam = truth_core(yd, lab, blank)
     return float(-logp), yd - gam
 
 
