@@ -698,6 +698,16 @@ klstm_status klstm_ctc_align(const float *net_out, int T, int S, int K, int stri
  *                  enqueued while the BPTT launch runs, `in_diff` is valid when klstm_update has returned -- Kaldi's
  *                  Component::Backpropagate returns only then.  (A promised klstm_update that never comes: the next
  *                  klstm_propagate / synchronising call waits and answers.)
+ *                  "persist_epoch" 1/0: where a persistent launch takes the epoch of its granule tags and its launch ordinal from.
+ *                  Both advance by a fixed amount with every launch the engine enqueues (run, skipped or given up alike), so the
+ *                  engine mirrors the device words on the host.  1 (default): a launch that goes straight to the stream (not into
+ *                  a graph of the "graph" option) gets both as kernel arguments; one lane of workgroup 0 writes the words' next
+ *                  values with fire-and-forget stores, and the workgroups simply exit -- no arrival count, no last-workgroup chain of
+ *                  device-scope round trips, no done word -- unless the host waits on that word ("persist_verify" = 1: count and
+ *                  report stay).  0: every launch reads the device words at its head and its last workgroup moves them on (what
+ *                  captured launches and the bf16 many-stream launches always do).  Bit-identical results; the device words
+ *                  hold the same values either way (klstm_profile_query "persist_word_epoch_fwd" | "persist_word_epoch_bwd" |
+ *                  "persist_word_launches" read them back), so the setting may change at any minibatch boundary.  A-B runs and tests.
  *                  Not supported: a hipGraph captured by the CALLER around engine calls that take the persistent chain (the
  *                  engine cannot count launches inside a foreign graph): use "persist" = 0 there.
  *                  Per-engine knobs (A-B experiments and tests): "persist_waves" (forward and backward geometry: 8, 12, 16),

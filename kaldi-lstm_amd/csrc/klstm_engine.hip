@@ -163,6 +163,14 @@ struct klstm_engine {
   unsigned *pstat_host = nullptr;   // pinned, device-mapped word the persistent kernels set when they give up (polled without a sync)
   // ---- give-up handling of the persistent chain (recover()) ----
   unsigned pseq = 0;            // persistent launches enqueued so far, both directions (the device counts the same in pctrl[8])
+  // Host mirror of the two epoch words, pctrl[0] (forward) and pctrl[4] (backward): every persistent launch moves its direction's word on
+  // by its tag count whether it ran, skipped or gave up, so the host knows the value at enqueue time (pseq mirrors pctrl[8] the same way).
+  // Advanced next to pseq; taken from the device words again in recover().  Option "persist_epoch" (1, default): a launch that is NOT
+  // captured into a hipGraph gets epoch and ordinal as kernel arguments and ends without the arrival count of its workgroups unless the
+  // host waits on the done word ("persist_verify"); 0: every launch reads the device words and its last workgroup moves them on.
+  unsigned ep_fwd = 0, ep_bwd = 0;
+  int persist_epoch = 1;
+  bool eager_now = true;        // the launch sequence being issued goes straight to the stream (run_graphed: false while it is captured)
   int persist_verify = 0;       // option: wait for every persistent launch and answer a give-up before the call returns
   int verify_spin = 1;          // option "persist_verify_spin": that wait spins on the host-mapped done word (0: hipStreamSynchronize)
   bool verify_later = false;    // "persist_verify": the wait for this minibatch's BPTT launch has been moved behind the Update's launches
@@ -484,6 +492,7 @@ static klstm_status ensure_persist(klstm_engine *e) {
   }
   HIPCHK(hipMalloc(&e->pctrl, 16 * sizeof(unsigned)));   // (+ 8 diagnostic words: which cells' granules never arrived)
   HIPCHK(hipMemsetAsync(e->pctrl, 0, 16 * sizeof(unsigned), e->stream));
+  e->ep_fwd = 0; e->ep_bwd = 0;                          // (the mirror of the epoch words; pseq is still 0 here)
   HIPCHK(hipMalloc(&e->tr_ctr, 4 * sizeof(unsigned)));   // "tail_merge": arrivals / expired waits (words of their own: recover() rewrites pctrl)
   HIPCHK(hipMemsetAsync(e->tr_ctr, 0, 4 * sizeof(unsigned), e->stream));
   e->tr_seq = 0; e->tr_total = 0;
@@ -524,6 +533,7 @@ static klstm_status recover(klstm_engine *e, const unsigned (&w)[16]) {
   unsigned z[16] = {0};
   z[0] = w[0]; z[4] = w[4]; z[8] = w[8]; z[10] = w[10];   // epochs, the launch counter and the count of Updates left out for a peer stay
   HIPCHK(hipMemcpy(e->pctrl, z, sizeof(z), hipMemcpyHostToDevice));
+  e->ep_fwd = w[0]; e->ep_bwd = w[4];                     // (the stream is idle: the words are what every enqueued launch left -- the mirror's own values)
   if (e->pstat_host) e->pstat_host[1] &= 0x7fffffffu;     // (the done word's give-up bit: answered here)
   e->n_giveups++;
   if (e->cooldown_cur < e->cooldown_len || e->clean_run >= (long)e->cooldown_cur) e->cooldown_cur = e->cooldown_len;
@@ -974,6 +984,16 @@ static BwdPtrs bwd_ptrs(klstm_engine *e) {
 
 static bool use_fused_x(const klstm_engine *e) { return e->fuse_x < 0 ? e->S <= 16 : e->fuse_x != 0; }
 
+// The epoch protocol of the persistent launch about to be issued (PersistOpts::epoch_mode): from the host mirror unless the launch is being
+// captured or "persist_epoch" is 0; with the workgroups' arrival count and the done word only when the host will wait on that word
+// ("persist_verify": inside the call, or deferred to the end of klstm_update).  `epoch`: the mirror of the launch's direction.
+static void set_epoch_args(klstm_engine *e, unsigned epoch) {
+  const bool host = e->persist_epoch != 0 && e->eager_now;
+  e->popt.epoch_mode = !host ? 0 : e->persist_verify ? 2 : 1;
+  e->popt.epoch = epoch;
+  e->popt.ordinal = e->pseq + 1;                      // (pseq moves on once the call's launches are enqueued)
+}
+
 static klstm_status seq_forward(klstm_engine *e, const float *in, int in_stride, float *out, int out_stride, int T) {
   const Dims d{e->I, e->C, e->R, e->S, T};
   const FwdPtrs p = fwd_ptrs(e);
@@ -1005,6 +1025,7 @@ static klstm_status seq_forward(klstm_engine *e, const float *in, int in_stride,
     // step 1 closes over the CARRIED r (set by Reset / the previous minibatch, possibly under older weights): unfolded
     // gates kernel, r(0) mirrored into time block 0; steps 2..T close over m(t-1) through W_rm; r(1..T) in one GEMM
     if (e->fwd_persist) {                         // (all T steps in the one launch, step 1 on the natural matrices)
+      set_epoch_args(e, e->ep_fwd);
       HIPCHK(launch_fwd_persist(d, p, in, in_stride, out, out_stride, e->gran[0], e->pctrl, e->popt, st, probe(e, "k_fwd_persist"), e->fwd_inf));
       e->persist_dirty = true;
       if (persist_r_in_kernel(d, e->popt)) return KLSTM_OK;  // (r(1..T), the output rows and the carried r come out of the same launch)
@@ -1107,6 +1128,7 @@ static klstm_status seq_backward(klstm_engine *e, const float *in, int in_stride
     TailReduceJob tj;
     const bool merge = e->bwd_persist && e->tail_merge && e->tail_wgs > 0 && e->tr_ctr && !e->use_graph && d.R % 8 == 0 && d.C % 8 == 0;
     if (e->bwd_persist) {
+      set_epoch_args(e, e->ep_bwd);
       HIPCHK(launch_bwd_persist(d, p, e->Pm, out_diff, od_stride, in_diff, id_stride, tail_inside, e->gran[1], e->pctrl + 4, e->popt, st,
                                 probe(e, "k_bwd_persist"), e->ws, e->ws_floats, probe(e, "k_tail_reduce"), merge ? &tj : nullptr));
       e->persist_dirty = true;
@@ -1144,7 +1166,10 @@ template <class F>
 static klstm_status run_graphed(klstm_engine *e, const klstm_engine::Key &key, F &&seq, bool short_seq = false) {
   // short_seq: the call is one or two launches (persistent chain): a graph launch costs more than they do (bench A-B at
   // 40/800/512, 4 streams: 196 us per minibatch with a graph per call, 188 with plain launches); option "graph" = 2 forces it
+  e->eager_now = true;
   if (!e->use_graph || e->profile || (short_seq && e->use_graph != 2)) return seq();
+  e->eager_now = false;                               // (captured launches have frozen arguments: epoch and ordinal from the device words)
+  struct Back { klstm_engine *e; ~Back() { e->eager_now = true; } } back{e};
   auto it = e->graphs.find(key);
   if (it == e->graphs.end()) {
     // graphs bake the caller's pointers; a trainer that cycles through a pool of minibatch buffers needs one
@@ -1205,6 +1230,7 @@ static klstm_status do_propagate(klstm_engine *e, const float *in, int rows, int
   if (e->fwd_inf && persist_fwd_has_inference(Dims{e->I, e->C, e->R, e->S, T}, e->popt)) e->n_inf++;
   if (e->fwd_persist || e->fwd_ms) {                  // (counted here, not inside the launch sequence: a graph replay is a launch too)
     e->pseq++;
+    e->ep_fwd += persist_fwd_ntags(Dims{e->I, e->C, e->R, e->S, T});   // (the many-stream launches consume T + 2 tags too)
     e->persist_dirty = true;
     e->marks.push_back(klstm_engine::FwdMark{e->pseq, e->sp, e->resets});   // (the Resets since the forward pass before this one)
   }
@@ -1237,7 +1263,12 @@ static klstm_status do_backpropagate(klstm_engine *e, const float *in, int in_st
     return seq_backward(e, in, in_stride, out_diff, out_diff_stride, in_diff, in_diff_stride, T, momentum, flags);
   }, bwd_short);
   if (st != KLSTM_OK) return st;
-  if (e->bwd_persist || e->bwd_xl) { e->pseq++; e->persist_dirty = true; }
+  if (e->bwd_persist || e->bwd_xl) {
+    const Dims dT{e->I, e->C, e->R, e->S, T};
+    e->pseq++;
+    e->ep_bwd += e->bwd_persist ? persist_bwd_ntags(dT) : persist_fwd_ntags(dT);   // (klstm_persist_xl.hip: one chain, T + 2 tags)
+    e->persist_dirty = true;
+  }
   e->T_bwd = T;
   if (grads_fusable(e, T, flags, e->fwd_folded ? false : e->use_bf16)) {
     e->grads_pending = true;
@@ -1679,6 +1710,7 @@ klstm_status klstm_set_option(klstm_engine *e, const char *key, int value) {
     else if (!strcmp(key, "persist_ncu")) { e->ncu = value; e->popt.ncu = value; }                                      // test hook: pretend the device has this many CUs
     else if (!strcmp(key, "persist_verify")) e->persist_verify = value != 0;
     else if (!strcmp(key, "persist_verify_spin")) e->verify_spin = value != 0;
+    else if (!strcmp(key, "persist_epoch")) e->persist_epoch = value != 0;
     else if (!strcmp(key, "persist_cooldown")) { e->cooldown_len = value < 0 ? 0 : value; e->cooldown_cur = 0; if (e->cooldown > e->cooldown_len) e->cooldown = e->cooldown_len; }
     else return fail(KLSTM_ERR_ARG, "klstm_set_option: unknown key '%s'", key);
     return KLSTM_OK;
@@ -1790,7 +1822,16 @@ klstm_status klstm_profile_query(klstm_engine *e, const char *kernel, double *to
       *total_us = 0.0; *launches = (long)v;
       return KLSTM_OK;
     }
-    if (!strcmp(kernel, "dp_updates_left_out")) {      // Updates every rank left out because SOME rank's gradient of that minibatch was not real
+    // the DEVICE words the persistent launches keep (the stream is idle here): forward epoch, backward epoch, launch count
+    for (const auto &wd : {std::make_pair("persist_word_epoch_fwd", 0), std::make_pair("persist_word_epoch_bwd", 4),
+                           std::make_pair("persist_word_launches", 8)})
+      if (!strcmp(kernel, wd.first)) {
+        unsigned v = 0;
+        if (e->pctrl) HIPCHK(hipMemcpy(&v, e->pctrl + wd.second, sizeof(v), hipMemcpyDeviceToHost));
+        *total_us = 0.0; *launches = (long)v;
+        return KLSTM_OK;
+      }
+    if (!strcmp(kernel, "dp_updates_left_out")) {    // Updates every rank left out because SOME rank's gradient of that minibatch was not real
       unsigned v = 0;
       if (e->pctrl) HIPCHK(hipMemcpy(&v, e->pctrl + 10, sizeof(v), hipMemcpyDeviceToHost));
       *total_us = 0.0; *launches = (long)v;

@@ -427,8 +427,18 @@ struct PersistOpts {
                                   // nothing (whatever was queued behind a give-up leaves state, planes and parameters alone);
                                   // [8] counts the persistent launches of the engine that have run (both directions, in stream order):
                                   // the first launch that gives up records its ordinal ([8] + 1) in its ctrl[3]
+  // Epoch protocol of the NEXT launch_fwd_persist / launch_bwd_persist (klstm_persist_dev.h EPOCH_*), set by the caller per launch:
+  // 0 = the launch reads epoch and launch count from the device words and its last workgroup moves them on (any launch captured into a
+  // hipGraph, and the default of a caller that keeps no mirror); 1 / 2 = `epoch` (the value ctrl[0] holds) and `ordinal` ([8] + 1) travel as
+  // kernel arguments, workgroup 0 writes the words' next values with fire-and-forget stores, and the launch ends without (1) or with (2: a
+  // host waits on the done word) the arrival count of its workgroups.  The many-stream launchers ignore it (always 0).
+  int epoch_mode = 0;
+  unsigned epoch = 0, ordinal = 0;
   long long *dbg = nullptr;       // tools/persist_anatomy (KLSTM_PERSIST_TIMING builds only)
 };
+// tags a launch consumes: what its direction's epoch moves on by (forward and many-stream launches: T + 2; backward: per group of 4 streams)
+inline unsigned persist_fwd_ntags(const Dims &d) { return (unsigned)(d.T + 2); }
+inline unsigned persist_bwd_ntags(const Dims &d) { return (unsigned)(((d.S + 3) / 4) * (d.T + 2)); }
 bool persist_supported(const Dims &d, const PersistOpts &o);       // forward
 bool persist_x_batched(const Dims &d);   // wide input: the caller runs x W_gifo_x^T + bias as one batched product into the gifo plane first
 bool persist_bwd_supported(const Dims &d, const PersistOpts &o);   // backward

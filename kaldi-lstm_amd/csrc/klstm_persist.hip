@@ -14,8 +14,9 @@
 //   * two granule slots (parity of t): a workgroup can publish step t+1 only after it has seen ALL of step t, and every
 //     workgroup publishes step t only after its sweep of step t-1 has finished, so a slot is never rewritten while
 //     somebody still sweeps it.
-//   * tags = epoch + t with a device-resident epoch that the last workgroup to finish advances by T + 2: no per-call
-//     memset, and a hipGraph replay (frozen kernel arguments) still sees fresh tags.
+//   * tags = epoch + t with an epoch that moves on by T + 2 per launch: no per-call memset.  The engine mirrors it on the host and
+//     passes it as a kernel argument; a hipGraph replay (frozen kernel arguments) reads the device-resident word, which the last
+//     workgroup to finish advances, and still sees fresh tags (klstm_persist_dev.h EPOCH_*).
 //   * every wait is bounded (wall clock, 50 ms PER WAIT by default): on expiry the workgroup records the step in ctrl[2] and
 //     leaves; the Update kernels read that word and leave the parameters alone, the engine reports it at the next
 //     synchronising call and falls back.  All workgroups must be co-resident: grid <= 200 workgroups, one per CU (the engine
@@ -65,6 +66,7 @@ struct PersistFwdArgs {
   long long spin_limit;           // wall-clock ticks (100 MHz) a single wait may take before the workgroup gives up
   int test_stall;                 // test hook: workgroup 0 stops publishing at this step (0: never) -> every sweep of that step times out
   unsigned *hstat;                // host-mapped status word (or null): set when a wait expires, read by the engine without a sync
+  EpochArgs ea;                   // where epoch and launch ordinal come from, how the launch ends (klstm_persist_dev.h)
 #ifdef KLSTM_PERSIST_TIMING
   long long *dbg;                 // per workgroup: shader-clock sums of the phases of a step (tools/persist_anatomy.hip)
 #endif
@@ -177,7 +179,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
   const bool proj_on = a.rin && (int)blockIdx.x * 4 < R;   // this workgroup contracts rows 4*blockIdx .. +3 of W_r_m
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const unsigned epoch = __hip_atomic_load(&a.ctrl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned epoch = launch_epoch(a.ea, a.ctrl);
   // a launch queued behind one that gave up (its status word is still set: the host has not looked yet) must not run: its
   // inputs are that launch's invalid outputs.  Requested here, looked at behind the barrier of step 1 -- behind every role's
   // prologue loads (loads return in order: the look costs nothing; a branch up here cost 1.1 us per launch).  Before that barrier
@@ -470,7 +472,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
                                       a.spin_limit, a.nap0, a.nap)) {
             *abortf = 1u;
             if (lane == 0) {
-              atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.guard));
+              atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.ea, a.guard));
               atomicMax(&a.ctrl[2], 0x80000000u | (unsigned)t);
               if (a.hstat) __hip_atomic_store(a.hstat, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
@@ -524,7 +526,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
                                          a.spin_limit, a.nap0, a.nap)) {
           *abortf = 1u;
           if (lane == 0) {
-            atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.guard));            // (which launch: the first one wins, everything behind it does nothing)
+            atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.ea, a.guard));      // (which launch: the first one wins, everything behind it does nothing)
             atomicMax(&a.ctrl[2], 0x80000000u | (unsigned)t);
             if (a.hstat) __hip_atomic_store(a.hstat, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           }
@@ -550,7 +552,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
     }
   }
   PT_FLUSH(0);
-  finish(a.ctrl, epoch, T + 2, a.guard ? a.guard + 8 : nullptr, a.guard, a.hstat ? a.hstat + 1 : nullptr);
+  finish(a.ctrl, epoch, T + 2, a.guard ? a.guard + 8 : nullptr, a.guard, a.hstat ? a.hstat + 1 : nullptr, a.ea);
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -695,6 +697,7 @@ hipError_t launch_fwd_persist(const Dims &d, const FwdPtrs &p, const float *in, 
   a.spin_limit = o.spin_limit > 0 ? o.spin_limit : SPIN_LIMIT_DEFAULT;
   a.test_stall = o.test_stall_fwd;
   a.hstat = o.hstat;
+  a.ea = EpochArgs{o.epoch_mode, o.epoch, o.ordinal};
 #ifdef KLSTM_PERSIST_TIMING
   a.dbg = o.dbg;
 #endif

@@ -81,6 +81,7 @@ struct PersistBwd2Args {
   unsigned *hstat;                // host-mapped status word (or null): set when a wait expires, read by the engine without a sync
   unsigned *guard;                // the engine's control words (or null): [2] / [6] set by an earlier launch -> do nothing; [8] = persistent
                                   // launches of this engine that have run so far: this launch's ordinal, [8] + 1, goes into ctrl[3] if it gives up
+  EpochArgs ea;                   // where epoch and launch ordinal come from, how the launch ends (klstm_persist_dev.h)
 #ifdef KLSTM_PERSIST_TIMING
   long long *dbg;
 #endif
@@ -245,7 +246,7 @@ __device__ __forceinline__ void bwd_tail_role(const PersistBwd2Args &a, float *l
       if (__all(ok)) break;
       if (__any(lost) || ((spins & 15) == 15 && wall_clock64() - t0 > a.spin_limit)) {
         __hip_atomic_store(abortf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (lane == 0) { atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.guard)); atomicMax(&a.ctrl[2], 0x80000000u | 0x4000u | (unsigned)t); }
+        if (lane == 0) { atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.ea, a.guard)); atomicMax(&a.ctrl[2], 0x80000000u | 0x4000u | (unsigned)t); }
         return false;
       }
       for (int i = 0; i < a.nap; i++) __builtin_amdgcn_s_sleep(1);
@@ -374,7 +375,7 @@ __global__ __launch_bounds__(NW * 64) void k_bwd_persist2(PersistBwd2Args a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ngrp = (S + 3) >> 2;
   const long long limit = a.spin_limit;
-  const unsigned epoch = __hip_atomic_load(&a.ctrl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned epoch = launch_epoch(a.ea, a.ctrl);
   // queued behind a launch that gave up (status word still set: the host has not looked yet): the planes this launch would read
   // are invalid -- do nothing.  Requested here, looked at by every role behind the loads of its own prologue (loads return in
   // order: by then the word is there, the look costs nothing; a branch up here cost 1.2 us per launch).  A role that skips
@@ -650,7 +651,7 @@ __global__ __launch_bounds__(NW * 64) void k_bwd_persist2(PersistBwd2Args a) {
               if (__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) { dead = true; break; }
               if (wall_clock64() - t0 > limit) {
                 __hip_atomic_store(abortf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (lane == 0) { atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.guard)); atomicMax(&a.ctrl[2], 0x80000000u | (unsigned)t); }
+                if (lane == 0) { atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.ea, a.guard)); atomicMax(&a.ctrl[2], 0x80000000u | (unsigned)t); }
                 dead = true;
                 break;
               }
@@ -733,11 +734,11 @@ __global__ __launch_bounds__(NW * 64) void k_bwd_persist2(PersistBwd2Args a) {
   }
   __syncthreads();
   if (tid == 0 && *abortf) {                         // (a bounded LDS wait expired or a sweep timed out)
-    atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.guard));
+    atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.ea, a.guard));
     atomicMax(&a.ctrl[2], 0x80000000u | 0x7fffu);
     if (a.hstat) __hip_atomic_store(a.hstat, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
-  finish(a.ctrl, epoch, ngrp * (T + 2), a.guard ? a.guard + 8 : nullptr, a.guard, a.hstat ? a.hstat + 1 : nullptr);
+  finish(a.ctrl, epoch, ngrp * (T + 2), a.guard ? a.guard + 8 : nullptr, a.guard, a.hstat ? a.hstat + 1 : nullptr, a.ea);
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -775,7 +776,7 @@ __global__ __launch_bounds__(NW * 64) void k_bwd_persist2i(PersistBwd2Args a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long long limit = a.spin_limit;
-  const unsigned epoch = __hip_atomic_load(&a.ctrl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned epoch = launch_epoch(a.ea, a.ctrl);
   unsigned behind_giveup = 0u;                       // (as in k_bwd_persist2: looked at behind each role's prologue loads)
 #ifndef KLSTM_NO_CHAIN_GUARD
   if (a.guard) behind_giveup = __hip_atomic_load(&a.guard[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) |
@@ -1044,7 +1045,7 @@ __global__ __launch_bounds__(NW * 64) void k_bwd_persist2i(PersistBwd2Args a) {
               if (__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) { dead = true; break; }
               if (wall_clock64() - t0 > limit) {
                 __hip_atomic_store(abortf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (lane == 0) { atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.guard)); atomicMax(&a.ctrl[2], 0x80000000u | (unsigned)t); }
+                if (lane == 0) { atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.ea, a.guard)); atomicMax(&a.ctrl[2], 0x80000000u | (unsigned)t); }
                 dead = true;
                 break;
               }
@@ -1118,11 +1119,11 @@ __global__ __launch_bounds__(NW * 64) void k_bwd_persist2i(PersistBwd2Args a) {
   }
   __syncthreads();
   if (tid == 0 && *abortf) {                         // (a bounded LDS wait expired or a sweep timed out)
-    atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.guard));
+    atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.ea, a.guard));
     atomicMax(&a.ctrl[2], 0x80000000u | 0x7fffu);
     if (a.hstat) __hip_atomic_store(a.hstat, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
-  finish(a.ctrl, epoch, NGI * (T + 2), a.guard ? a.guard + 8 : nullptr, a.guard, a.hstat ? a.hstat + 1 : nullptr);
+  finish(a.ctrl, epoch, NGI * (T + 2), a.guard ? a.guard + 8 : nullptr, a.guard, a.hstat ? a.hstat + 1 : nullptr, a.ea);
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -1232,6 +1233,7 @@ hipError_t launch_bwd_persist(const Dims &d, const BwdPtrs &p, const float *P, c
   a.test_stall = o.test_stall_bwd;
   a.hstat = o.hstat;
   a.guard = o.guard;
+  a.ea = EpochArgs{o.epoch_mode, o.epoch, o.ordinal};
 #ifdef KLSTM_PERSIST_TIMING
   a.dbg = o.dbg;
 #endif

@@ -168,11 +168,35 @@ __device__ __forceinline__ bool lds_wait_ge(int *ctr, int target, unsigned *abor
   return true;
 }
 
-// end of launch: the last workgroup to arrive advances the epoch for the next call (a later launch cannot start before
-// every workgroup of this one has exited, so nobody reads ctrl[0] concurrently)
-// count (or null): the engine's launch counter (persistent launches that have run): the LAST workgroup moves it on by one --
-// nobody else writes it during a launch, so launch_ordinal() at a give-up (always in front of that workgroup's own arrival
-// here) and the last workgroup itself both see the value the launch started with.
+// ---- epoch and launch ordinal of a launch, and its exit ----
+// The granule tags of a launch are epoch + step; the epoch of a direction moves on by the launch's tag count with EVERY launch (run, skipped
+// or given up alike), and the launch count by one.  Both are therefore known to the host at enqueue time.  Two protocols (engine option
+// "persist_epoch", klstm.h):
+//   EPOCH_DEVICE : the launch reads ctrl[0] (and, at a give-up, the launch count) from memory at its head; at its end the workgroups
+//                  count themselves in (ctrl[1]) and the LAST one writes the next epoch, moves the launch count on and reports to the
+//                  host-mapped done word.  What a launch captured into a hipGraph needs (frozen kernel arguments), and the many-stream
+//                  kernels (klstm_persist_ms.hip, klstm_persist_xl.hip) always run.
+//   EPOCH_HOST   : epoch and ordinal are kernel arguments (the engine mirrors the device words); one lane of workgroup 0 writes the next
+//                  epoch and the new launch count with fire-and-forget stores (nobody reads them during a launch: whoever reads them
+//                  later -- a graph-mode launch, recover(), profile_query -- finds what EPOCH_DEVICE would have left), and the
+//                  workgroups simply exit: no arrival counter, no serial chain of device-scope round trips in the last workgroup.
+//                  (The stores sit at workgroup 0's EXIT, not at the head of the launch: up there they cost the 8-stream forward
+//                  instance and three backward instances 32-36 bytes of scratch; down here no register is live.)
+//   EPOCH_HOST_REPORT : as EPOCH_HOST, but the host WAITS on the done word ("persist_verify"): the arrival counter and the last workgroup's
+//                  report stay; the count it reports is the ordinal argument.
+enum : int { EPOCH_DEVICE = 0, EPOCH_HOST = 1, EPOCH_HOST_REPORT = 2 };
+struct EpochArgs {
+  int mode;                       // EPOCH_*
+  unsigned epoch;                 // EPOCH_HOST*: this launch's epoch (the value ctrl[0] holds)
+  unsigned ordinal;               // EPOCH_HOST*: this launch's ordinal (the launch count it leaves behind)
+};
+// head of a launch: its epoch
+__device__ __forceinline__ unsigned launch_epoch(const EpochArgs &ea, const unsigned *ctrl) {
+  return ea.mode == EPOCH_DEVICE ? __hip_atomic_load(&ctrl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ea.epoch;
+}
+// the ordinal a launch that gives up records in its ctrl[3].  EPOCH_DEVICE: the engine's launch counter (persistent launches that have
+// run) -- the LAST workgroup moves it on by one, nobody else writes it during a launch, so a give-up (always in front of that workgroup's
+// own arrival in finish()) and the last workgroup itself both see the value the launch started with.
 __device__ __forceinline__ unsigned launch_ordinal(const unsigned *guard) {
 #ifdef KLSTM_NO_LAUNCH_COUNT
   return 0u;
@@ -180,21 +204,39 @@ __device__ __forceinline__ unsigned launch_ordinal(const unsigned *guard) {
   return guard ? __hip_atomic_load(guard + 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u : 0u;
 #endif
 }
+__device__ __forceinline__ unsigned launch_ordinal(const EpochArgs &ea, const unsigned *guard) {
+#ifdef KLSTM_NO_LAUNCH_COUNT
+  return 0u;
+#else
+  return ea.mode == EPOCH_DEVICE ? launch_ordinal(guard) : (guard ? ea.ordinal : 0u);
+#endif
+}
+// end of launch (EPOCH_DEVICE, EPOCH_HOST_REPORT): the last workgroup to arrive advances the epoch for the next call (a later launch
+// cannot start before every workgroup of this one has exited, so nobody reads ctrl[0] concurrently).
 // hdone (or null): a HOST-MAPPED word the last workgroup writes when the launch is over: the new launch count in bits 0..30, bit 31 set when
 // a status word of the chain is up (this launch or one in front of it gave up).  A host that waits for a persistent launch
 // ("persist_verify") spins on this word instead of synchronising the stream: it hears of the end of the launch one PCIe write after
 // the last workgroup left, not one completion-signal round trip later.  One word carries both facts: nothing to order.
 __device__ __forceinline__ void finish(unsigned *ctrl, unsigned epoch, int ntags, unsigned *count = nullptr, const unsigned *guard = nullptr,
-                                       unsigned *hdone = nullptr) {
+                                       unsigned *hdone = nullptr, const EpochArgs ea = EpochArgs{EPOCH_DEVICE, 0u, 0u}) {
+  if (ea.mode != EPOCH_DEVICE && blockIdx.x == 0 && threadIdx.x == 0) {
+    // the device words as EPOCH_DEVICE would leave them, for whoever reads them AFTER the launch (finish() is unconditional: workgroup 0
+    // gets here whether the launch ran, skipped or gave up).  Fire and forget: the same write-through stores, nothing waits for them.
+    __hip_atomic_store(&ctrl[0], ea.epoch + (unsigned)ntags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#ifndef KLSTM_NO_LAUNCH_COUNT
+    if (count) __hip_atomic_store(count, ea.ordinal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+  }
+  if (ea.mode == EPOCH_HOST) return;                 // (nobody waits for a report: the workgroups simply exit)
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned old = atomicAdd(&ctrl[1], 1u);
     if (old == gridDim.x - 1) {
       __hip_atomic_store(&ctrl[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&ctrl[0], epoch + (unsigned)ntags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (ea.mode == EPOCH_DEVICE) __hip_atomic_store(&ctrl[0], epoch + (unsigned)ntags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #ifndef KLSTM_NO_LAUNCH_COUNT
-      unsigned n = 0u;
-      if (count) n = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
+      unsigned n = ea.ordinal;
+      if (ea.mode == EPOCH_DEVICE) n = count ? __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u : 0u;
       if (hdone && guard) {
         const unsigned bad = __hip_atomic_load(guard + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) |
                              __hip_atomic_load(guard + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

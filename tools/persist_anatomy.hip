@@ -23,6 +23,8 @@ int main(int argc, char **argv) {
   float *vecs = dalloc(7 * C), *gifo = dalloc((size_t)(T + 2) * S * 4 * C), *cc = dalloc((size_t)(T + 2) * S * C),
         *hh = dalloc((size_t)(T + 2) * S * C), *mm = dalloc((size_t)(T + 2) * S * C), *x = dalloc((size_t)T * S * I), *cs = dalloc(S * C),
         *wr = dalloc((size_t)4 * C * R), *wx = dalloc((size_t)4 * C * I), *pr0 = dalloc(S * R), *rr = dalloc((size_t)(T + 2) * S * R);
+  // (the projection r = W_r_m m rides in the launch as in the engine: its wave shares a SIMD with cell wave 0)
+  float *wmr = dalloc((size_t)R * C), *outr = dalloc((size_t)T * S * R), *nr = dalloc(S * R);
   unsigned long long *gran; CK(hipMalloc(&gran, 32 * C * 8 * 8)); CK(hipMemset(gran, 0, 32 * C * 8 * 8));
   unsigned *ctrl; CK(hipMalloc(&ctrl, 32)); CK(hipMemset(ctrl, 0, 32));
   long long *dbg; CK(hipMalloc(&dbg, 256 * 16 * 10 * 8)); CK(hipMemset(dbg, 0, 256 * 16 * 10 * 8));
@@ -30,9 +32,9 @@ int main(int argc, char **argv) {
     if (4 * tpw >= waves) continue;
     PersistOpts o; o.waves = waves; o.tpw = tpw;
     PersistFwdArgs a{};
-    a.C = C; a.I = I; a.R = R; a.S = S; a.T = T; a.nchm = nchm; a.nch = nch; a.wpk = wpk; a.wr = wr; a.wx = wx; a.prev_r = pr0; a.rr = rr; a.wm = nullptr; a.rin = 0; a.out = nullptr; a.out_stride = 0;
+    a.C = C; a.I = I; a.R = R; a.S = S; a.T = T; a.nchm = nchm; a.nch = nch; a.wpk = wpk; a.wr = wr; a.wx = wx; a.prev_r = pr0; a.rr = rr; a.wm = wmr; a.rin = 1; a.out = outr; a.out_stride = R;
     a.bias = vecs; a.pi = vecs + 4 * C; a.pf = vecs + 5 * C; a.po = vecs + 6 * C;
-    a.gifo = gifo; a.cc = cc; a.hh = hh; a.mm = mm; a.x = x; a.x_stride = I; a.prev_c = cs; a.next_c = cs; a.next_r = pr0; a.guard = nullptr; a.gran = gran; a.ctrl = ctrl; a.dbg = dbg; a.nap0 = nap0; a.nap = nap; a.spin_limit = SPIN_LIMIT_DEFAULT; a.test_stall = 0;
+    a.gifo = gifo; a.cc = cc; a.hh = hh; a.mm = mm; a.x = x; a.x_stride = I; a.prev_c = cs; a.next_c = cs; a.next_r = nr; a.guard = nullptr; a.gran = gran; a.ctrl = ctrl; a.dbg = dbg; a.nap0 = nap0; a.nap = nap; a.spin_limit = SPIN_LIMIT_DEFAULT; a.test_stall = 0;
     const PGeo g = pick_geo_fwd(o, C, nch, (R + 31) / 32 * 32 + I);
     const size_t shm = (size_t)((S > 4 ? 8 : 4) * (g.maxc * 128 + 16) + (S > 4 ? 8 : 4) * (persist_maxu(g.maxc) * 128 + 16) + 4) * sizeof(float);
     const int grid = C / 4 / g.tpw;
