@@ -529,6 +529,46 @@ klstm_status klstm_ctc_beam_stream_emit(int S, int K, int blank, int beam, int n
                                         int *stable_len_dev, const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev,
                                         double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/* The same searches with a SPARSE BACK-OFF language model: a high-order n-gram over characters or word pieces, which the dense tables
+ * cannot hold (include/klstm_nnet.hpp class CtcSparseLabelLm, ReadArpaLabelLm; the definition of a
+ * lookup is sparse_lm_lookup of kaldi-lstm_amd/lm.py).  The model is a deterministic automaton with back-off (failure) arcs over the K
+ * classes, state 0 the start, its arcs in CSR form, all arrays on the device:
+ *   arc_offsets_dev [states + 1]; arc_labels_dev [arcs], strictly ascending within a state, never the blank; arc_next_dev [arcs];
+ *   arc_weight_dev [arcs]; backoff_dev [states], the state to fall back to or -1; backoff_weight_dev [states].  Every back-off chain
+ *   ends (-1) after at most 8 back-offs: n-grams up to order 9.
+ * THE LOOKUP (q, c) -> (g, n): if state q has an arc for c, n is its next and g its weight -- after a back-off, float32(product *
+ * weight).  Otherwise, with backoff[q] < 0: g = 0, n = -1 (forbidden); else product = flush(float32(product * flush(backoff_weight[q]))),
+ * q = backoff[q], and again; the product starts at 1, flush is the emission rule.  (g, n) then stand where weight[q][c] and next[q][c] of
+ * klstm_ctc_beam_decode_lm stand, and everything after them is that call's: the results are, bit for bit, those of the dense call on
+ * the expansion of the model.  An n outside [0, states) forbids the extension.
+ * klstm_ctc_slm_build turns the arrays into an opaque blob of klstm_ctc_slm_bytes(states, arcs, K) bytes (16-byte aligned, about 16
+ * bytes per state and 44 per arc; the arrays may be freed once the build has run), once per model, asynchronously on hip_stream.  It
+ * VALIDATES on the device, so that no content of the arrays can lead a search out of the blob, and counts into status_dev [8] (may be
+ * NULL): states DROPPED (they lose all arcs and keep their back-off) for [0] labels not strictly ascending, [1] a label outside
+ * [0, K), [2] a blank arc, [3] an arc range outside [0, arcs]; back-offs CUT to -1 for [4] a target outside [-1, states), [5] a chain
+ * of more than 8 back-offs, cycles included (decided for every state on the arrays as given); [6] states stored as a direct row of K
+ * entries (those with at least K / 4 arcs), the others by their sorted labels; [7] 0.  For a state with several faults the first arc
+ * at fault decides, in the order [3], then per arc [1], [2], [0].
+ * klstm_ctc_beam_decode_slm / klstm_ctc_beam_stream_step_slm are klstm_ctc_beam_decode_lm / klstm_ctc_beam_stream_step with (slm,
+ * slm_bytes, lm_states, lm_final_dev [lm_states] or NULL) in the place of the tables: the same arguments, checks, statuses, asynchrony,
+ * workspace and state.  klstm_ctc_beam_stream_emit serves both kinds of model: it reads lm_final_dev alone (with a sparse model pass
+ * lm_states = 1).  The blob is known by its address: one that klstm_ctc_slm_build did not write, or wrote for other states or
+ * classes, or slm_bytes below klstm_ctc_slm_bytes: KLSTM_ERR_ARG, as for a null slm.
+ * Limits: 1 <= states <= 2^24, 1 <= arcs <= 2^26, 2 <= K <= 32768; beyond them KLSTM_ERR_SHAPE (klstm_ctc_slm_bytes answers 0). */
+size_t klstm_ctc_slm_bytes(int states, int arcs, int K);
+klstm_status klstm_ctc_slm_build(int states, int arcs, int K, int blank, const int *arc_offsets_dev, const int *arc_labels_dev,
+                                 const int *arc_next_dev, const float *arc_weight_dev, const int *backoff_dev, const float *backoff_weight_dev,
+                                 void *slm, size_t slm_bytes, int *status_dev, void *hip_stream);
+klstm_status klstm_ctc_beam_decode_slm(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
+                                       const float *class_weight_dev, int beam, int cands, int nbest, const void *slm, size_t slm_bytes,
+                                       int lm_states, const float *lm_final_dev, int *hyp_dev, int *hyp_len_dev, int *nbest_count_dev,
+                                       float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev,
+                                       double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
+klstm_status klstm_ctc_beam_stream_step_slm(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *start_dev,
+                                            int blank, const float *class_weight_dev, int beam, int cands, const void *slm, size_t slm_bytes,
+                                            int lm_states, void *state, size_t state_bytes, int max_frames, void *workspace,
+                                            size_t workspace_bytes, void *hip_stream);
+
 /* Minimum expected token error over CTC n-best lists (MWER / minimum Bayes risk over n-best; include/klstm_nnet.hpp class CtcMbr;
  * INTEGRATION.md 3i): the sequence-discriminative objective that follows CTC training, on the lists and edit distances
  * klstm_ctc_beam_decode wrote.  Stateless, asynchronous on hip_stream, decided entirely on the device.  net_out, stride, lens_dev,

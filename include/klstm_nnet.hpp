@@ -7,7 +7,14 @@
 #pragma once
 #include <algorithm>
 #include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <istream>
+#include <map>
 #include <memory>
+#include <set>
+#include <sstream>
+#include <string>
 
 #include "klstm_component.hpp"
 #include "klstm_trainer.hpp"
@@ -777,6 +784,149 @@ class CtcLabelLm {
   DeviceBuffer next_, weight_, final_;
 };
 
+// The host arrays of a sparse back-off language model (klstm_ctc_slm_build, klstm.h): the arcs of the states in CSR
+// form with strictly ascending labels, per state a back-off state (-1: none) and its weight, final dense (empty: none).  What
+// SparseLm of kaldi-lstm_amd/lm.py holds; ReadArpaLabelLm below fills one from an ARPA file.
+struct SparseLabelLm {
+  int32 num_classes = 0;
+  std::vector<int32> arc_offsets, arc_labels, arc_next, backoff;
+  std::vector<BaseFloat> arc_weight, backoff_weight, final_weight;
+  int32 NumStates() const { return (int32)backoff.size(); }
+};
+
+// A sparse back-off model on the device for CtcBeamDecoder / CtcStreamDecoder::SetLanguageModel: the arrays go up, the build
+// validates them there and writes the blob the search walks; Status() (synchronises) is what it dropped or cut, as klstm.h lists it.
+class CtcSparseLabelLm {
+ public:
+  CtcSparseLabelLm(const SparseLabelLm &m, int32 blank) : states_(m.NumStates()), classes_(m.num_classes) {
+    const int32 arcs = (int32)m.arc_labels.size();
+    KLSTM_ASSERT(states_ >= 1 && arcs >= 1 && m.arc_offsets.size() == (size_t)states_ + 1 && m.arc_next.size() == (size_t)arcs);
+    KLSTM_ASSERT(m.arc_weight.size() == (size_t)arcs && m.backoff_weight.size() == (size_t)states_);
+    KLSTM_ASSERT(m.final_weight.empty() || m.final_weight.size() == (size_t)states_);
+    bytes_ = klstm_ctc_slm_bytes(states_, arcs, classes_);
+    if (bytes_ == 0) KLSTM_ERR("klstm: " << klstm_last_error());
+    DeviceBuffer off, lab, nxt, wt, bo, bow;
+    off.Upload(m.arc_offsets); lab.Upload(m.arc_labels); nxt.Upload(m.arc_next); wt.Upload(m.arc_weight);
+    bo.Upload(m.backoff); bow.Upload(m.backoff_weight);
+    final_.Upload(m.final_weight);
+    blob_.Grow(bytes_);
+    status_.Grow(8 * sizeof(int32));
+    KCheck(klstm_ctc_slm_build(states_, arcs, classes_, blank, off.As<int32>(), lab.As<int32>(), nxt.As<int32>(), wt.As<BaseFloat>(),
+                               bo.As<int32>(), bow.As<BaseFloat>(), blob_.As<void>(), bytes_, status_.As<int32>(), nullptr));
+    status_.Download(host_status_, 8);                              // the build has run: the arrays may go
+  }
+  int32 NumStates() const { return states_; }
+  int32 NumClasses() const { return classes_; }
+  const void *Blob() const { return blob_.As<void>(); }
+  size_t Bytes() const { return bytes_; }
+  const BaseFloat *Final() const { return final_.As<BaseFloat>(); }          // null: no final weights
+  const int32 *Status() const { return host_status_; }
+ private:
+  int32 states_, classes_;
+  size_t bytes_ = 0;
+  DeviceBuffer blob_, final_, status_;
+  int32 host_status_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+// Reads a back-off n-gram in ARPA format into the arrays of a sparse model, as arpa_label_lm of kaldi-lstm_amd/lm.py does from the
+// same file: symbols maps a token to its class; n-grams with a token that maps to no class other than the blank are skipped, as are
+// those with <s> anywhere but first or </s> anywhere but last.  States are the histories -- every listed n-gram below the highest
+// order and every context -- with the <s> history state 0, the empty history state 1 and the others by length, then content; the next
+// state is the longest suffix of history + label that is a state; arc weight 10^(alpha logp) e^beta, back-off weight 10^(alpha
+// logbow), final = P(</s> | history)^alpha with back-off applied, in double.  Orders up to 9.
+inline SparseLabelLm ReadArpaLabelLm(std::istream &is, const std::map<std::string, int32> &symbols, int32 num_classes, int32 blank,
+                                     double alpha = 1.0, double beta = 0.0) {
+  typedef std::vector<int32> Gram;                                  // -1: <s>, -2: </s>
+  std::map<Gram, double> logp, logbow;
+  int32 order = 0, n = 0;
+  std::string line;
+  while (std::getline(is, line)) {
+    std::istringstream ls(line);
+    std::vector<std::string> f;
+    for (std::string tok; ls >> tok;) f.push_back(tok);
+    if (f.empty()) continue;
+    if (f[0][0] == '\\') {
+      const size_t dash = f[0].find('-');
+      n = (f[0].size() > 7 && f[0].compare(f[0].size() - 7, 7, "-grams:") == 0) ? std::atoi(f[0].substr(1, dash - 1).c_str()) : 0;
+      order = std::max(order, n);
+      continue;
+    }
+    if (n == 0 || (int32)f.size() < n + 1) continue;
+    Gram gram;
+    bool ok = true;
+    for (int32 i = 0; i < n; i++) {
+      const std::string &tok = f[1 + i];
+      if (tok == "<s>") { ok = ok && i == 0; gram.push_back(-1); }
+      else if (tok == "</s>") { ok = ok && i == n - 1; gram.push_back(-2); }
+      else {
+        const auto it = symbols.find(tok);
+        ok = ok && it != symbols.end() && it->second >= 0 && it->second < num_classes && it->second != blank;
+        gram.push_back(it != symbols.end() ? it->second : 0);
+      }
+    }
+    if (!ok) continue;
+    logp[gram] = std::strtod(f[0].c_str(), nullptr);
+    if ((int32)f.size() > n + 1) logbow[gram] = std::strtod(f[n + 1].c_str(), nullptr);
+  }
+  if (order < 1 || order > 9) KLSTM_ERR("ReadArpaLabelLm: order " << order << " outside 1 to 9");
+  auto by_len = [](const Gram &a, const Gram &b) { return a.size() != b.size() ? a.size() < b.size() : a < b; };
+  std::set<Gram, decltype(by_len)> hist(by_len);
+  hist.insert(Gram());
+  for (const auto &kv : logp) {
+    const Gram &g = kv.first;
+    hist.insert(Gram(g.begin(), g.end() - 1));
+    if ((int32)g.size() < order && g.back() != -2) hist.insert(g);
+  }
+  const Gram start = order > 1 ? Gram(1, -1) : Gram();
+  std::vector<Gram> states(1, start);
+  if (order > 1) states.push_back(Gram());
+  for (const Gram &h : hist)
+    if (h != start && !h.empty()) states.push_back(h);
+  std::map<Gram, int32> index;
+  for (size_t i = 0; i < states.size(); i++) index[states[i]] = (int32)i;
+  auto longest = [&](Gram h) {
+    while (!index.count(h)) h.erase(h.begin());
+    return index[h];
+  };
+  auto bow_log = [&](const Gram &h) {
+    const auto it = logbow.find(h);
+    return it == logbow.end() ? 0.0 : it->second;
+  };
+  std::map<Gram, std::map<int32, double> > arcs;                    // history -> label -> weight
+  for (const auto &kv : logp)
+    if (kv.first.back() >= 0) arcs[Gram(kv.first.begin(), kv.first.end() - 1)][kv.first.back()] = std::pow(10.0, alpha * kv.second) * std::exp(beta);
+  SparseLabelLm m;
+  m.num_classes = num_classes;
+  m.arc_offsets.push_back(0);
+  for (const Gram &h : states) {
+    const auto it = arcs.find(h);
+    if (it != arcs.end())
+      for (const auto &a : it->second) {
+        Gram to(h);
+        to.push_back(a.first);
+        if ((int32)to.size() > order - 1) to.erase(to.begin(), to.end() - (order - 1));
+        m.arc_labels.push_back(a.first);
+        m.arc_weight.push_back((BaseFloat)a.second);
+        m.arc_next.push_back(longest(to));
+      }
+    m.arc_offsets.push_back((int32)m.arc_labels.size());
+    m.backoff.push_back(h.empty() ? -1 : longest(Gram(h.begin() + 1, h.end())));
+    m.backoff_weight.push_back(h.empty() ? 1.f : (BaseFloat)std::pow(10.0, alpha * bow_log(h)));
+    double acc = 0.0;                                               // log10 P(</s> | h) with back-off applied
+    bool found = false;
+    for (Gram g(h);; g.erase(g.begin())) {
+      Gram e(g);
+      e.push_back(-2);
+      const auto ep = logp.find(e);
+      if (ep != logp.end()) { acc += ep->second; found = true; break; }
+      if (g.empty()) break;
+      acc += bow_log(g);
+    }
+    m.final_weight.push_back(found ? (BaseFloat)std::pow(10.0, alpha * acc) : 0.f);
+  }
+  return m;
+}
+
 // What a CtcBeamDecoder's last Decode left on the device: hypotheses [num_stream][nbest][stride], their lengths [num_stream][nbest],
 // the entries listed per stream, their edit distances [num_stream][nbest] (null when it had no references)
 struct CtcNbestDevice { const int32 *hyp, *hyp_len, *count, *errors; int32 num_stream, nbest, stride; };
@@ -790,7 +940,10 @@ class CtcBeamDecoder : private CtcCallBase {
   using CtcCallBase::SetClassWeights;
   // Fuses a language model into the search: every later Decode goes through klstm_ctc_beam_decode_lm and its scores are the fused
   // ones.  The decoder keeps the pointer, not the tables; null: the search without one, as before.
-  void SetLanguageModel(const CtcLabelLm *lm) { lm_ = lm; }
+  void SetLanguageModel(const CtcLabelLm *lm) { lm_ = lm; slm_ = nullptr; }
+  // The same with a sparse back-off model (klstm_ctc_beam_decode_slm); the later of the two calls decides, null: none
+  void SetLanguageModel(const CtcSparseLabelLm *slm) { slm_ = slm; lm_ = nullptr; }
+  void SetLanguageModel(std::nullptr_t) { lm_ = nullptr; slm_ = nullptr; }
   // net_out, lens, refs as CtcGreedyDecoder::Decode takes them; lists (optional): the n-best list of every stream (empty for an idle
   // one).  Asking for lists synchronises; the rest stays on the device.
   void Decode(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &refs,
@@ -814,7 +967,12 @@ class CtcBeamDecoder : private CtcCallBase {
     int32 *er = scoring ? err_.As<int32>() : nullptr;
     double *tot = scoring ? tot_.Dev() : nullptr;
     MatrixView y = net_out.View();
-    if (!lm_) {
+    if (slm_) {
+      KLSTM_ASSERT(slm_->NumClasses() == K);
+      KCheck(klstm_ctc_beam_decode_slm(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, Weights(), beam_, cands_, N, slm_->Blob(),
+                                       slm_->Bytes(), slm_->NumStates(), slm_->Final(), hyp_.As<int32>(), hlen_.As<int32>(), cnt_.As<int32>(),
+                                       score_.As<BaseFloat>(), rl, ro, er, tot, ws, need, nullptr));
+    } else if (!lm_) {
       KCheck(klstm_ctc_beam_decode(y.Data(), T, num_stream, K, y.Stride(), lens_dev, blank_, Weights(), beam_, cands_, N, hyp_.As<int32>(),
                                    hlen_.As<int32>(), cnt_.As<int32>(), score_.As<BaseFloat>(), rl, ro, er, tot, ws, need, nullptr));
     } else {
@@ -888,6 +1046,7 @@ class CtcBeamDecoder : private CtcCallBase {
   int32 beam_, cands_, nbest_, frames_ = 0;
   bool scored_ = false;
   const CtcLabelLm *lm_ = nullptr;
+  const CtcSparseLabelLm *slm_ = nullptr;
   PackedLabels refs_;
   DeviceBuffer hyp_, hlen_, cnt_, score_, err_;
   DeviceTotals<6> tot_;
@@ -908,7 +1067,9 @@ class CtcStreamDecoder : private CtcCallBase {
     if (state_bytes_ == 0) KLSTM_ERR("klstm: " << klstm_last_error());
   }
   using CtcCallBase::SetClassWeights;
-  void SetLanguageModel(const CtcLabelLm *lm) { lm_ = lm; }         // the decoder keeps the pointer, not the tables; null: none
+  void SetLanguageModel(const CtcLabelLm *lm) { lm_ = lm; slm_ = nullptr; }         // the decoder keeps the pointer, not the tables; null: none
+  void SetLanguageModel(const CtcSparseLabelLm *slm) { slm_ = slm; lm_ = nullptr; }  // a sparse back-off model; the later call decides
+  void SetLanguageModel(std::nullptr_t) { lm_ = nullptr; slm_ = nullptr; }
   int32 NumStream() const { return num_stream_; }
   int32 MaxFrames() const { return max_frames_; }
 
@@ -925,6 +1086,14 @@ class CtcStreamDecoder : private CtcCallBase {
     const size_t need = klstm_ctc_beam_stream_workspace_bytes(T, S, cands_, nbest_);
     void *ws = Workspace(need);
     MatrixView y = chunk.View();
+    if (slm_) {
+      KLSTM_ASSERT(slm_->NumClasses() == K);
+      KCheck(klstm_ctc_beam_stream_step_slm(y.Data(), T, S, K, y.Stride(), lens_dev, start.empty() ? nullptr : start_.As<int32>(), blank_, Weights(),
+                                            beam_, cands_, slm_->Blob(), slm_->Bytes(), slm_->NumStates(), State(), state_bytes_, max_frames_, ws,
+                                            need, nullptr));
+      classes_ = K;
+      return;
+    }
     KCheck(klstm_ctc_beam_stream_step(y.Data(), T, S, K, y.Stride(), lens_dev, start.empty() ? nullptr : start_.As<int32>(), blank_, Weights(),
                                       beam_, cands_, lm_ ? lm_->NumStates() : 0, lm_ ? lm_->Next() : nullptr, lm_ ? lm_->Weight() : nullptr,
                                       State(), state_bytes_, max_frames_, ws, need, nullptr));
@@ -952,7 +1121,8 @@ class CtcStreamDecoder : private CtcCallBase {
     stab_.Grow((size_t)S * sizeof(int32));
     KCheck(klstm_memset_zero(stab_.As<int32>(), (size_t)S * sizeof(int32), nullptr));     // a skipped stream's is not written
     if (scoring) refs_.Upload(refs);
-    KCheck(klstm_ctc_beam_stream_emit(S, classes_, blank_, beam_, N, mode_.As<int32>(), lm_ ? lm_->NumStates() : 0, lm_ ? lm_->Final() : nullptr,
+    KCheck(klstm_ctc_beam_stream_emit(S, classes_, blank_, beam_, N, mode_.As<int32>(), slm_ ? 1 : lm_ ? lm_->NumStates() : 0,
+                                      slm_ ? slm_->Final() : lm_ ? lm_->Final() : nullptr,            // (emit reads the final weights alone)
                                       State(), state_bytes_, max_frames_, hyp_.As<int32>(), max_frames_, hlen_.As<int32>(), cnt_.As<int32>(),
                                       score_.As<BaseFloat>(), fr_.As<int32>(), stab_.As<int32>(), scoring ? refs_.Labels() : nullptr,
                                       scoring ? refs_.Offsets() : nullptr, scoring ? err_.As<int32>() : nullptr,
@@ -1008,6 +1178,7 @@ class CtcStreamDecoder : private CtcCallBase {
   int32 beam_, cands_, nbest_, max_frames_, classes_ = 0;
   size_t state_bytes_ = 0;
   const CtcLabelLm *lm_ = nullptr;
+  const CtcSparseLabelLm *slm_ = nullptr;
   PackedLabels refs_;
   DeviceBuffer state_, start_, mode_, hyp_, hlen_, cnt_, score_, err_, fr_, stab_;
   DeviceTotals<6> tot_;
@@ -1127,7 +1298,8 @@ inline TrainMbrStats TrainMbrWholeUtterances(Nnet *nnet, const std::vector<Utter
 // MMI (CTC-CRF) against a label language model (klstm_ctc_mmi_eval, klstm.h): loss = -log p(ref | y) - log W(ref) +
 // log Z with Z summed over every labelling the model accepts -- the model CtcBeamDecoder::SetLanguageModel fuses into the search.  diff
 // is the derivative of loss + ctc_weight * (-log p(ref | y)) with respect to the Softmax INPUT, like Ctc's.  The denominator graph is
-// built on the device when the model is set and serves every Eval after it; the five totals stay on the device.
+// built on the device when the model is set and serves every Eval after it; the five totals stay on the device.  The model is the
+// DENSE one: a sparse back-off model (CtcSparseLabelLm) serves the search only.
 class CtcMmi : private CtcCallBase {
  public:
   explicit CtcMmi(int32 blank = 0, BaseFloat ctc_weight = 0.f) : CtcCallBase(blank), ctc_weight_(ctc_weight) {}
@@ -1234,6 +1406,7 @@ struct DecodeCtcOptions {
   std::vector<BaseFloat> class_weights;                  // empty: none
   int32 beam = 0, cands = 8, nbest = 1;                  // beam 0: best path (CtcGreedyDecoder); beam > 0: prefix beam search (CtcBeamDecoder)
   const CtcLabelLm *lm = nullptr;                        // beam > 0 only: fused into the search (CtcBeamDecoder::SetLanguageModel); not owned
+  const CtcSparseLabelLm *slm = nullptr;                 // beam > 0 only: a sparse back-off model in its place (at most one of the two); not owned
 };
 struct DecodeCtcStats {
   int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
@@ -1272,7 +1445,8 @@ inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utt
   KLSTM_ASSERT(o.beam > 0);
   CtcBeamDecoder dec(o.blank, o.beam, o.cands, o.nbest);
   dec.SetClassWeights(o.class_weights);
-  dec.SetLanguageModel(o.lm);
+  KLSTM_ASSERT(!o.lm || !o.slm);
+  if (o.slm) dec.SetLanguageModel(o.slm); else dec.SetLanguageModel(o.lm);
   std::vector<CtcNbestList> lists;
   const std::vector<std::vector<int32> > none;
   const bool want = hypotheses || nbest_lists;

@@ -355,7 +355,8 @@ inline DecodeCtcStats DecodeCtcStreaming(const Nnet &nnet, const std::vector<Utt
   BatchScorer scorer(nnet, so);
   CtcStreamDecoder dec(o.blank, o.beam, o.cands, o.nbest, so.num_stream, longest);
   dec.SetClassWeights(o.class_weights);
-  dec.SetLanguageModel(o.lm);
+  KLSTM_ASSERT(!o.lm || !o.slm);
+  if (o.slm) dec.SetLanguageModel(o.slm); else dec.SetLanguageModel(o.lm);
   const int32 S = so.num_stream;
   std::vector<CtcNbestList> lists;
   std::vector<int32> mode(S);

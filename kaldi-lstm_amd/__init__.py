@@ -17,10 +17,11 @@ from .ctc import ctc_eval, ctc_workspace_bytes  # noqa: F401,E402
 from .ctc import CtcDecodeResult, ctc_decode_workspace_bytes, ctc_greedy_decode, hypotheses_to_lists  # noqa: F401,E402
 from .ctc import CtcAlignResult, alignments_to_lists, ctc_align, ctc_align_workspace_bytes  # noqa: F401,E402
 from .ctc import CtcBeamResult, ctc_beam_decode, ctc_beam_workspace_bytes, nbest_to_lists  # noqa: F401,E402
-from .ctc import CtcLabelLm  # noqa: F401,E402
+from .ctc import CtcLabelLm, CtcSparseLabelLm  # noqa: F401,E402
 from .ctc import CtcBeamStream, CtcStreamResult, ctc_beam_stream_state_bytes, ctc_beam_stream_workspace_bytes  # noqa: F401,E402
 from .ctc import CtcMbrResult, ctc_mbr_eval, ctc_mbr_workspace_bytes  # noqa: F401,E402
 from .ctc import CtcMmiDenominator, CtcMmiResult, ctc_mmi_eval, ctc_mmi_workspace_bytes  # noqa: F401,E402
 from .lm import lexicon_label_lm, ngram_label_lm  # noqa: F401,E402
+from .lm import SparseLm, arpa_label_lm, backoff_ngram_label_lm, sparse_lm_lookup, sparse_lm_to_dense, sparse_lm_validate  # noqa: F401,E402
 from .dp import (DataParallelLstm, DataParallelNnet, LstmDP, AffineDP, SoftmaxXentDP,  # noqa: F401,E402
                  shard_time_major)

@@ -123,6 +123,11 @@ def load_library():
     lib.klstm_ctc_beam_decode.argtypes = [P, I, I, I, I, P, I, P, I, I, I, P, P, P, P, P, P, P, P, P, ctypes.c_size_t, P]
     lib.klstm_ctc_beam_decode_lm.argtypes = [P, I, I, I, I, P, I, P, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, ctypes.c_size_t, P]
     lib.klstm_ctc_beam_lm_resident.argtypes = [I, I, I, I]
+    lib.klstm_ctc_slm_bytes.argtypes = [I, I, I]
+    lib.klstm_ctc_slm_bytes.restype = ctypes.c_size_t
+    lib.klstm_ctc_slm_build.argtypes = [I, I, I, I, P, P, P, P, P, P, P, ctypes.c_size_t, P, P]
+    lib.klstm_ctc_beam_decode_slm.argtypes = [P, I, I, I, I, P, I, P, I, I, I, P, ctypes.c_size_t, I, P, P, P, P, P, P, P, P, P, P, ctypes.c_size_t, P]
+    lib.klstm_ctc_beam_stream_step_slm.argtypes = [P, I, I, I, I, P, P, I, P, I, I, P, ctypes.c_size_t, I, P, ctypes.c_size_t, I, P, ctypes.c_size_t, P]
     lib.klstm_ctc_beam_stream_state_bytes.argtypes = [I, I, I]
     lib.klstm_ctc_beam_stream_state_bytes.restype = ctypes.c_size_t
     lib.klstm_ctc_beam_stream_workspace_bytes.argtypes = [I, I, I, I]

@@ -24,6 +24,10 @@
 // merges into; there the roles are swapped: the stay entry leaves its slot number in merged[] and the extension's thread adds its
 // value onto it (one extension per stay entry, so no race and the same two roundings).  LM = 1 reads the tables from global memory,
 // LM = 2 from a copy staged into dynamic LDS at the start (ctc_beam_lm_resident decides); the two give the same bits.
+// SPARSE BACK-OFF MODEL (klstm_ctc_slm_build, klstm_ctc_beam_decode_slm; the definition is sparse_lm_lookup of lm.py).
+// LM = 3: the pair (weight, next) of an extension comes from slm_lookup, a walk over a back-off automaton that k_slm_* below built into
+// one device blob from CSR arrays -- at most 9 states visited, a direct row or a binary search in each.  It is issued where the dense
+// gather is and lands in the same registers; nothing downstream of lm_fetch knows which model it was.
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -130,10 +134,77 @@ __global__ __launch_bounds__(256) void k_ctc_topc_wg(const float *__restrict__ y
 // The search.  List position of the stay entry of beam entry i: i; of the extension of entry i by the candidate of rank r: Bc + i C + r.
 // ------------------------------------------------------------------------------------------------------------------------------------
 struct BeamLm {                         // the label language model: Q states, next / weight [Q][K], fin [Q] or null
-  int Q;
+  int Q;                                // LM = 3: next is the blob of klstm_ctc_slm_build, weight is not read
   const int *next;
   const float *weight, *fin;
 };
+
+// The blob of a sparse back-off model, Q states and A arcs (byte offsets, every section 16-byte aligned):
+//   int hdr[16]      [0] SLM_MAGIC, [1] Q, [2] A, [3] K, [4..5] direct cells handed out (one 64-bit counter), [6] blank, [8..15] status
+//   int4 rec[Q]      x: first cell of the state, y: its arcs (-1: a direct row of K cells), z: back-off state or -1, w: back-off weight bits
+//   int raw[Q]       the back-off before the chain check (range-checked only)
+//   int labels[A]    the labels of the arcs as given
+//   int2 cells[5 A]  x: weight bits, y: next (-1 where it left [0, Q); SLM_MISS in a direct row: no arc).  The first A cells are the
+//                    arcs in CSR order; behind them the direct rows, K cells each, of the states with at least K / 4 arcs: at most
+//                    4 A cells as long as the states' arc ranges do not overlap, and a state that finds no room keeps its sorted arcs
+constexpr int SLM_MAGIC = 0x314D4C53, SLM_MAXBACK = 8, SLM_MISS = -2;
+// measured: a state with at least K / 4 arcs gets a direct row (0: no state does, every lookup is a binary search)
+#ifndef KLSTM_SLM_DIRECT_DIV
+#define KLSTM_SLM_DIRECT_DIV 4
+#endif
+static_assert(KLSTM_SLM_DIRECT_DIV >= 0 && KLSTM_SLM_DIRECT_DIV <= 4, "the blob holds 4 A cells of direct rows");
+struct SlmLayout { size_t rec, raw, labels, cells, bytes; };
+__host__ __device__ inline size_t slm_up16(size_t n) { return (n + 15) / 16 * 16; }
+__host__ __device__ inline SlmLayout slm_layout(int Q, int A) {
+  SlmLayout l;
+  l.rec = 64;
+  l.raw = l.rec + (size_t)Q * 16;
+  l.labels = l.raw + slm_up16((size_t)Q * 4);
+  l.cells = l.labels + slm_up16((size_t)A * 4);
+  l.bytes = (l.cells + (size_t)A * 40 + 255) / 256 * 256;
+  return l;
+}
+struct SlmView {
+  const int4 *rec;
+  const int *labels;
+  const int2 *cells;
+};
+__device__ __forceinline__ SlmView slm_view(const void *blob, int Q) {
+  const char *p = reinterpret_cast<const char *>(blob);
+  const SlmLayout l = slm_layout(Q, reinterpret_cast<const int *>(p)[2]);
+  return SlmView{reinterpret_cast<const int4 *>(p + l.rec), reinterpret_cast<const int *>(p + l.labels), reinterpret_cast<const int2 *>(p + l.cells)};
+}
+// sparse_lm_lookup of lm.py, bit for bit: (q, c) -> (g, n).  q in [0, Q), c in [0, K).  The build checked every index a walk
+// follows; the trip count is bounded here whatever the blob holds.
+__device__ __forceinline__ void slm_lookup(const SlmView &m, int q, int c, float &g, int &n) {
+  float prod = 1.f;
+  g = 0.f; n = -1;
+  for (int it = 0; it <= SLM_MAXBACK; it++) {
+    const int4 r = m.rec[q];
+    int at = -1;                                                   // the cell of the arc, if the state has one for c
+    if (r.y < 0) at = r.x + c;
+    else {
+      int lo = 0, hi = r.y;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (m.labels[r.x + mid] < c) lo = mid + 1; else hi = mid;
+      }
+      if (lo < r.y && m.labels[r.x + lo] == c) at = r.x + lo;
+    }
+    if (at >= 0) {
+      const int2 cell = m.cells[at];
+      if (cell.y != SLM_MISS) {
+        const float wt = __int_as_float(cell.x);
+        g = it ? bmul(prod, wt) : wt;
+        n = cell.y;
+        return;
+      }
+    }
+    if (r.z < 0) return;                                           // a miss without a back-off: forbidden
+    prod = beam_emit(bmul(prod, beam_emit(__int_as_float(r.w))));
+    q = r.z;
+  }
+}
 
 // The n-best list of a beam, one wave (B <= 64: it sees the whole beam), under k_ctc_beam's epilogue and k_ctc_beam_emit.  tot: the
 // lane's total, or tf = total * flush(final[state]).
@@ -183,6 +254,8 @@ __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, i
   int gn[BEAM_LMK];
   const float *const lw = reinterpret_cast<const float *>(beam_dyn);
   const int *const lnx = reinterpret_cast<const int *>(beam_dyn) + (LM == 2 ? lm.Q * K : 0);
+  SlmView slm{};                                                   // LM = 3: the sections of the blob
+  if constexpr (LM == 3) slm = slm_view(lm.next, lm.Q);
 
   const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   int len = lens[s];
@@ -212,7 +285,8 @@ __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, i
         const int i = q / C, c = cis[half * BEAM_MAXC + q - i * C];
         if ((unsigned)c < (unsigned)K) {                            // -1: no candidate of that rank
           const int idx = e_lm[half * BEAM_MAXB + i] * K + c;      // states in e_lm lie inside [0, Q): only a checked `next` gets there
-          if constexpr (LM == 2) { gw[k] = lw[idx]; gn[k] = lnx[idx]; }
+          if constexpr (LM == 3) slm_lookup(slm, e_lm[half * BEAM_MAXB + i], c, gw[k], gn[k]);
+          else if constexpr (LM == 2) { gw[k] = lw[idx]; gn[k] = lnx[idx]; }
           else { gw[k] = lm.weight[idx]; gn[k] = lm.next[idx]; }
         }
       }
@@ -474,6 +548,104 @@ __global__ __launch_bounds__(256) void k_ctc_beam_tail(const int *__restrict__ h
   totals[0] += e; totals[1] += n; totals[2] += h; totals[3] += u; totals[4] += wr; totals[5] += orc;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Building the blob of a sparse back-off model, once per model (klstm_ctc_slm_build): four small launches in stream order.  Every
+// index a walk of slm_lookup will follow is checked HERE, against Q, A and K, so that no content of the caller's arrays can send a
+// search out of the blob.  status [8]: states dropped (they keep their back-off and lose their arcs) for [0] labels not strictly
+// ascending, [1] a label outside [0, K), [2] a blank arc, [3] an arc range outside [0, A]; back-offs cut to -1 for [4] a target
+// outside [-1, Q), [5] a chain of more than 8 back-offs (a cycle is one); [6] states that got a direct row.
+// ------------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_slm_arcs(int Q, int A, int K, int blank, const int *__restrict__ labels, const int *__restrict__ nxt,
+                                                  const float *__restrict__ wt, void *blob) {
+  char *p = reinterpret_cast<char *>(blob);
+  const SlmLayout l = slm_layout(Q, A);
+  int *hdr = reinterpret_cast<int *>(p);
+  if (blockIdx.x == 0 && threadIdx.x < 16) {
+    const int t = threadIdx.x;
+    hdr[t] = t == 0 ? SLM_MAGIC : t == 1 ? Q : t == 2 ? A : t == 3 ? K : t == 6 ? blank : 0;
+  }
+  int *lab = reinterpret_cast<int *>(p + l.labels);
+  int2 *cells = reinterpret_cast<int2 *>(p + l.cells);
+  for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < (size_t)A; j += (size_t)gridDim.x * 256) {
+    const int n = nxt[j];
+    lab[j] = labels[j];
+    cells[j] = make_int2(__float_as_int(wt[j]), (unsigned)n < (unsigned)Q ? n : -1);
+  }
+}
+
+// one thread per state: its arcs checked, its record, its direct row
+__global__ __launch_bounds__(256) void k_slm_states(int Q, int A, int K, int blank, const int *__restrict__ off, const int *__restrict__ labels,
+                                                    const int *__restrict__ backoff, const float *__restrict__ bow, void *blob) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= Q) return;
+  char *p = reinterpret_cast<char *>(blob);
+  const SlmLayout l = slm_layout(Q, A);
+  int *hdr = reinterpret_cast<int *>(p), *status = hdr + 8;
+  int2 *cells = reinterpret_cast<int2 *>(p + l.cells);
+  int b = off[q], e = off[q + 1], why = -1;
+  if (b < 0 || e < b || e > A) why = 3;
+  else
+    for (int j = b, prev = -1; j < e; j++) {                       // ascending inside [0, K): at most K arcs are read
+      const int c = labels[j];
+      if (c < 0 || c >= K) why = 1;
+      else if (c == blank) why = 2;
+      else if (c <= prev) why = 0;
+      if (why >= 0) break;
+      prev = c;
+    }
+  if (why >= 0) { atomicAdd(status + why, 1); b = e = 0; }
+  int deg = e - b, bo = backoff[q];
+  if (bo < -1 || bo >= Q) { atomicAdd(status + 4, 1); bo = -1; }
+  if (KLSTM_SLM_DIRECT_DIV > 0 && deg > 0 && (long)deg * KLSTM_SLM_DIRECT_DIV >= K) {      // a direct row, if there is room: K <= 4 deg cells
+    const u64 at = atomicAdd(reinterpret_cast<u64 *>(hdr + 4), (u64)K);
+    if (at + (u64)K <= (u64)4 * (u64)A) {
+      int2 *row = cells + (size_t)A + (size_t)at;
+      for (int c = 0; c < K; c++) row[c] = make_int2(0, SLM_MISS);
+      for (int j = b; j < e; j++) row[labels[j]] = cells[j];       // k_slm_arcs wrote them: an earlier launch
+      atomicAdd(status + 6, 1);
+      b = A + (int)at; deg = -1;
+    }
+  }
+  reinterpret_cast<int4 *>(p + l.rec)[q] = make_int4(b, deg, bo, __float_as_int(bow[q]));
+  reinterpret_cast<int *>(p + l.raw)[q] = bo;
+}
+
+// one thread per state: a back-off whose chain does not end within SLM_MAXBACK states is cut.  Decided on the range-checked back-offs
+// of k_slm_states alone, so the outcome does not depend on the order the threads run in
+__global__ __launch_bounds__(256) void k_slm_chains(int Q, int A, void *blob) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  char *p = reinterpret_cast<char *>(blob);
+  const SlmLayout l = slm_layout(Q, A);
+  int *status = reinterpret_cast<int *>(p) + 8;
+  if (q < Q) {
+    const int *raw = reinterpret_cast<const int *>(p + l.raw);
+    int d = 0;
+    for (int s = raw[q]; s >= 0 && d <= SLM_MAXBACK; s = raw[s]) d++;
+    if (d > SLM_MAXBACK) {
+      reinterpret_cast<int4 *>(p + l.rec)[q].z = -1;
+      atomicAdd(status + 5, 1);
+    }
+  }
+}
+
+__global__ void k_slm_status(const void *blob, int *__restrict__ status_out) {
+  if (threadIdx.x < 8) status_out[threadIdx.x] = reinterpret_cast<const int *>(blob)[8 + threadIdx.x];
+}
+
+size_t ctc_slm_bytes(int Q, int A) { return slm_layout(Q, A).bytes; }
+
+hipError_t launch_ctc_slm_build(int Q, int A, int K, int blank, const int *off, const int *labels, const int *nxt, const float *wt,
+                                const int *backoff, const float *bow, void *blob, int *status, hipStream_t st) {
+  const int gq = (Q + 255) / 256, ga = min((A + 255) / 256, 4096);
+  hipError_t err = launch(k_slm_arcs, dim3(ga), dim3(256), 0, st, LaunchProbe{}, Q, A, K, blank, labels, nxt, wt, blob);
+  if (err != hipSuccess) return err;
+  err = launch(k_slm_states, dim3(gq), dim3(256), 0, st, LaunchProbe{}, Q, A, K, blank, off, labels, backoff, bow, blob);
+  if (err != hipSuccess) return err;
+  err = launch(k_slm_chains, dim3(gq), dim3(256), 0, st, LaunchProbe{}, Q, A, blob);
+  if (err != hipSuccess || !status) return err;
+  return launch(k_slm_status, dim3(1), dim3(64), 0, st, LaunchProbe{}, (const void *)blob, status);
+}
+
 static size_t up256(size_t n) { return (n + 255) / 256 * 256; }
 static size_t beam_top_bytes(int T, int S, int C) { return up256((size_t)T * S * C * sizeof(int)); }
 static size_t beam_node_bytes(int T, int S, int B) { return up256(((size_t)T * B + 1) * S * sizeof(int)); }
@@ -510,11 +682,13 @@ static hipError_t launch_ctc_topc(const float *y, int T, int S, int K, int strid
 // C = 4); beyond 128 entries four waves, and BEAM_KPT keys a thread need all 256 threads at the largest list
 static int beam_threads(int B, int C) { return B * (C + 1) <= 64 ? 64 : B * (C + 1) <= 128 ? 128 : 256; }
 
-// One of the three instances of a search kernel template, grid (S): without an LM (Q = 0), gathering its tables, or with the tables
-// resident in dynamic LDS (ctc_beam_lm_resident decides).  args: the kernel's own.
+// One of the four instances of a search kernel template, grid (S): without an LM (Q = 0), gathering its tables, with the tables
+// resident in dynamic LDS (ctc_beam_lm_resident decides), or walking a sparse back-off model in global memory.  args: the kernel's own.
 template <class Kern, class... A>
-static hipError_t launch_beam_chain(Kern none, Kern gathered, Kern resident, int S, int K, int B, int C, int Q, hipStream_t st, A... args) {
+static hipError_t launch_beam_chain(Kern none, Kern gathered, Kern resident, Kern sparse, bool is_sparse, int S, int K, int B, int C, int Q,
+                                    hipStream_t st, A... args) {
   const dim3 grid(S), block(beam_threads(B, C));
+  if (is_sparse) return launch(sparse, grid, block, 0, st, LaunchProbe{}, args...);
   if (Q == 0) return launch(none, grid, block, 0, st, LaunchProbe{}, args...);
   if (!ctc_beam_lm_resident(Q, K, B, C)) return launch(gathered, grid, block, 0, st, LaunchProbe{}, args...);
   // about 32 KB of static LDS come on top: past 64 KB in all the kernel needs the opt-in that launch() applies to the dynamic part alone
@@ -525,6 +699,10 @@ static hipError_t launch_beam_chain(Kern none, Kern gathered, Kern resident, int
   }
   return launch(resident, grid, block, dyn, st, LaunchProbe{}, args...);
 }
+
+static hipError_t launch_ctc_beam_any(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C,
+                                      int N, BeamLm lm, bool sparse, int *hyp, int *hyp_len, int *count, float *score, const int *refs,
+                                      const int *roff, int *errors, double *totals, void *workspace, hipStream_t st);
 
 hipError_t launch_ctc_beam(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
                            int *hyp, int *hyp_len, int *count, float *score, const int *refs, const int *roff, int *errors, double *totals,
@@ -537,6 +715,21 @@ hipError_t launch_ctc_beam(const float *y, int T, int S, int K, int stride, cons
 hipError_t launch_ctc_beam_lm(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
                               int Q, const int *lm_next, const float *lm_weight, const float *lm_final, int *hyp, int *hyp_len, int *count,
                               float *score, const int *refs, const int *roff, int *errors, double *totals, void *workspace, hipStream_t st) {
+  return launch_ctc_beam_any(y, T, S, K, stride, lens, blank, w, B, C, N, BeamLm{Q, lm_next, lm_weight, lm_final}, false, hyp, hyp_len, count,
+                             score, refs, roff, errors, totals, workspace, st);
+}
+
+// slm: the blob klstm_ctc_slm_build wrote for Q states
+hipError_t launch_ctc_beam_slm(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
+                               int Q, const void *slm, const float *lm_final, int *hyp, int *hyp_len, int *count, float *score,
+                               const int *refs, const int *roff, int *errors, double *totals, void *workspace, hipStream_t st) {
+  return launch_ctc_beam_any(y, T, S, K, stride, lens, blank, w, B, C, N, BeamLm{Q, reinterpret_cast<const int *>(slm), nullptr, lm_final}, true,
+                             hyp, hyp_len, count, score, refs, roff, errors, totals, workspace, st);
+}
+
+static hipError_t launch_ctc_beam_any(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C,
+                                      int N, BeamLm lm, bool sparse, int *hyp, int *hyp_len, int *count, float *score, const int *refs,
+                                      const int *roff, int *errors, double *totals, void *workspace, hipStream_t st) {
   char *p = reinterpret_cast<char *>(workspace);
   float *topv = reinterpret_cast<float *>(p);
   int *topi = reinterpret_cast<int *>(p + beam_top_bytes(T, S, C));
@@ -546,8 +739,8 @@ hipError_t launch_ctc_beam_lm(const float *y, int T, int S, int K, int stride, c
   unsigned *ticket = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(stat) + 1024);
   hipError_t err = launch_ctc_topc(y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket, st);
   if (err != hipSuccess) return err;
-  err = launch_beam_chain(k_ctc_beam<0>, k_ctc_beam<1>, k_ctc_beam<2>, S, K, B, C, Q, st, y, T, S, K, stride, lens, w, blank, B, C, N, (const float *)topv,
-                          (const int *)topi, npar, ntok, hyp, hyp_len, count, score, BeamLm{Q, lm_next, lm_weight, lm_final});
+  err = launch_beam_chain(k_ctc_beam<0>, k_ctc_beam<1>, k_ctc_beam<2>, k_ctc_beam<3>, sparse, S, K, B, C, lm.Q, st, y, T, S, K, stride, lens, w, blank, B,
+                          C, N, (const float *)topv, (const int *)topi, npar, ntok, hyp, hyp_len, count, score, lm);
   if (err != hipSuccess || !refs) return err;
   return launch(k_ctc_beam_tail, dim3(S), dim3(256), 0, st, LaunchProbe{}, (const int *)hyp, (const int *)hyp_len, (const int *)count, T, S, K, N,
                 blank, refs, roff, errors, totals, stat, ticket);
@@ -614,6 +807,8 @@ __global__ __launch_bounds__(256) void k_ctc_beam_stream(const float *__restrict
   int gn[BEAM_LMK];
   const float *const lw = reinterpret_cast<const float *>(beam_dyn);
   const int *const lnx = reinterpret_cast<const int *>(beam_dyn) + (LM == 2 ? lm.Q * K : 0);
+  SlmView slm{};                                                   // LM = 3: the sections of the blob
+  if constexpr (LM == 3) slm = slm_view(lm.next, lm.Q);
 
   const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const int len = lens[s];
@@ -656,7 +851,8 @@ __global__ __launch_bounds__(256) void k_ctc_beam_stream(const float *__restrict
         const int i = q / C, c = cis[half * BEAM_MAXC + q - i * C];
         if ((unsigned)c < (unsigned)K) {
           const int idx = e_lm[half * BEAM_MAXB + i] * K + c;
-          if constexpr (LM == 2) { gw[k] = lw[idx]; gn[k] = lnx[idx]; }
+          if constexpr (LM == 3) slm_lookup(slm, e_lm[half * BEAM_MAXB + i], c, gw[k], gn[k]);
+          else if constexpr (LM == 2) { gw[k] = lw[idx]; gn[k] = lnx[idx]; }
           else { gw[k] = lm.weight[idx]; gn[k] = lm.next[idx]; }
         }
       }
@@ -924,8 +1120,9 @@ size_t ctc_beam_stream_workspace_bytes(int T, int S, int C, int N) {
 }
 size_t ctc_beam_stream_emit_workspace_bytes() { return BEAM_STREAM_WS_HEAD; }
 
+// sparse: lm_next is the blob klstm_ctc_slm_build wrote for Q states, lm_weight is not read
 hipError_t launch_ctc_beam_stream_step(const float *y, int T, int S, int K, int stride, const int *lens, const int *start, int blank,
-                                       const float *w, int B, int C, int Q, const int *lm_next, const float *lm_weight, void *state,
+                                       const float *w, int B, int C, int Q, const int *lm_next, const float *lm_weight, bool sparse, void *state,
                                        int max_frames, void *workspace, hipStream_t st) {
   char *p = reinterpret_cast<char *>(workspace);
   unsigned *ticket = reinterpret_cast<unsigned *>(p + 1024);
@@ -933,8 +1130,9 @@ hipError_t launch_ctc_beam_stream_step(const float *y, int T, int S, int K, int 
   int *topi = reinterpret_cast<int *>(p + BEAM_STREAM_WS_HEAD + beam_top_bytes(T, S, C));
   const hipError_t err = launch_ctc_topc(y, T, S, K, stride, lens, w, blank, C, topv, topi, ticket, st);
   if (err != hipSuccess) return err;
-  return launch_beam_chain(k_ctc_beam_stream<0>, k_ctc_beam_stream<1>, k_ctc_beam_stream<2>, S, K, B, C, Q, st, y, T, S, K, stride, lens, start, w, blank,
-                           B, C, (const float *)topv, (const int *)topi, state, max_frames, BeamLm{Q, lm_next, lm_weight, nullptr});
+  return launch_beam_chain(k_ctc_beam_stream<0>, k_ctc_beam_stream<1>, k_ctc_beam_stream<2>, k_ctc_beam_stream<3>, sparse, S, K, B, C, Q, st, y, T, S, K,
+                           stride, lens, start, w, blank, B, C, (const float *)topv, (const int *)topi, state, max_frames,
+                           BeamLm{Q, lm_next, lm_weight, nullptr});
 }
 
 hipError_t launch_ctc_beam_stream_emit(int S, int K, int blank, int B, int N, const int *mode, int Q, const float *lm_final, const void *state,

@@ -2155,8 +2155,58 @@ size_t klstm_ctc_beam_workspace_bytes(int T, int S, int beam, int cands) {
   }
   return ctc_beam_workspace_bytes(T, S, beam, cands);
 }
-// the checks and the launch behind klstm_ctc_beam_decode (Q = 0, no tables) and klstm_ctc_beam_decode_lm (with_lm: 1 <= Q)
-static klstm_status ctc_beam_decode_checked(const char *fn, bool with_lm, const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
+// ---- sparse back-off models.  What a blob was built for is remembered per address, as for the MMI graphs below: the header lives
+// on the device and the calls do not wait for it ----
+struct SlmNote { int Q, A, K; size_t bytes; };
+static std::mutex slm_mu;
+static std::map<const void *, SlmNote> slm_blobs;
+static bool ctc_slm_shape_ok(int states, int arcs, int K) {
+  return states >= 1 && states <= (1 << 24) && arcs >= 1 && arcs <= (1 << 26) && K >= 2 && K <= 32768;
+}
+size_t klstm_ctc_slm_bytes(int states, int arcs, int K) {
+  if (!ctc_slm_shape_ok(states, arcs, K)) {
+    fail(KLSTM_ERR_SHAPE, "klstm_ctc_slm_bytes: %d states, %d arcs, %d classes outside 1 <= states <= 2^24, 1 <= arcs <= 2^26, 2 <= K <= 32768", states, arcs, K);
+    return 0;
+  }
+  return ctc_slm_bytes(states, arcs);
+}
+klstm_status klstm_ctc_slm_build(int states, int arcs, int K, int blank, const int *arc_offsets_dev, const int *arc_labels_dev,
+                                 const int *arc_next_dev, const float *arc_weight_dev, const int *backoff_dev, const float *backoff_weight_dev,
+                                 void *slm, size_t slm_bytes, int *status_dev, void *hip_stream) {
+  const char *fn = "klstm_ctc_slm_build";
+  if (states <= 0 || arcs <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "%s: bad size (%d states, %d arcs, K %d)", fn, states, arcs, K);
+  if (!ctc_slm_shape_ok(states, arcs, K))
+    return fail(KLSTM_ERR_SHAPE, "%s: %d states, %d arcs, %d classes outside states <= 2^24, arcs <= 2^26, 2 <= K <= 32768", fn, states, arcs, K);
+  if (!arc_offsets_dev || !arc_labels_dev || !arc_next_dev || !arc_weight_dev || !backoff_dev || !backoff_weight_dev || !slm)
+    return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
+  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "%s: blank %d outside [0, %d)", fn, blank, K);
+  if ((reinterpret_cast<uintptr_t>(slm) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: the model's buffer must be 16-byte aligned", fn);
+  if (slm_bytes < ctc_slm_bytes(states, arcs))
+    return fail(KLSTM_ERR_ARG, "%s: buffer of %zu bytes is below klstm_ctc_slm_bytes(%d, %d, %d) = %zu", fn, slm_bytes, states, arcs, K,
+                ctc_slm_bytes(states, arcs));
+  {
+    std::lock_guard<std::mutex> lk(slm_mu);
+    slm_blobs.erase(slm);
+  }
+  HIPCHK(launch_ctc_slm_build(states, arcs, K, blank, arc_offsets_dev, arc_labels_dev, arc_next_dev, arc_weight_dev, backoff_dev,
+                              backoff_weight_dev, slm, status_dev, (hipStream_t)hip_stream));
+  std::lock_guard<std::mutex> lk(slm_mu);
+  slm_blobs[slm] = SlmNote{states, arcs, K, ctc_slm_bytes(states, arcs)};
+  return KLSTM_OK;
+}
+// null: the blob serves a call with these sizes; else what is wrong with it
+static const char *ctc_slm_finding(const void *slm, size_t slm_bytes, int lm_states, int K) {
+  if (!slm) return "null sparse language model";
+  std::lock_guard<std::mutex> lk(slm_mu);
+  const auto it = slm_blobs.find(slm);
+  if (it == slm_blobs.end()) return "no sparse language model was built at this address (klstm_ctc_slm_build)";
+  if (it->second.Q != lm_states || it->second.K != K) return "the sparse language model was built for other states or classes";
+  if (slm_bytes < it->second.bytes) return "the sparse language model's bytes are below klstm_ctc_slm_bytes";
+  return nullptr;
+}
+// the checks and the launch behind klstm_ctc_beam_decode (Q = 0, no tables), klstm_ctc_beam_decode_lm (with_lm: 1 <= Q) and
+// klstm_ctc_beam_decode_slm (slm_call: lm_next_dev is the blob, slm_bytes its size, 1 <= Q)
+static klstm_status ctc_beam_decode_checked(const char *fn, bool with_lm, bool slm_call, size_t slm_bytes, const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
                                             const float *class_weight_dev, int beam, int cands, int nbest, int Q, const int *lm_next_dev,
                                             const float *lm_weight_dev, const float *lm_final_dev, int *hyp_dev, int *hyp_len_dev,
                                             int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
@@ -2166,16 +2216,27 @@ static klstm_status ctc_beam_decode_checked(const char *fn, bool with_lm, const 
   if (!ctc_beam_shape_ok(T, S, beam, cands) || K < 2 || K > 32768 || cands > K - 1 || nbest > beam)
     return fail(KLSTM_ERR_SHAPE, "%s: T %d, streams %d, K %d, beam %d, candidates %d, n-best %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768, beam <= 64, candidates <= min(K - 1, 32), n-best <= beam",
                 fn, T, S, K, beam, cands, nbest);
-  if (Q < (with_lm ? 1 : 0) || (long)Q * K > (1L << 24))
+  if (slm_call && (Q < 1 || Q > (1 << 24)))
+    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states outside 1 <= states <= 2^24", fn, Q);
+  if (!slm_call && (Q < (with_lm ? 1 : 0) || (long)Q * K > (1L << 24)))
     return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 1 <= states, states * K <= 2^24", fn, Q, K);
   const char *pointers = ctc_refs_finding(ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev);      // (the later one here fires first)
-  if (Q > 0 && (!lm_next_dev || !lm_weight_dev)) pointers = "the language model's next and weight tables come together";
+  if (slm_call) {
+    const char *f = ctc_slm_finding(lm_next_dev, slm_bytes, Q, K);
+    if (f) pointers = f;
+  } else if (Q > 0 && (!lm_next_dev || !lm_weight_dev)) pointers = "the language model's next and weight tables come together";
   if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !nbest_count_dev || !workspace) pointers = "null argument";
   const klstm_status st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride, nullptr, workspace);
   if (st != KLSTM_OK) return st;
   if (workspace_bytes < ctc_beam_workspace_bytes(T, S, beam, cands))
     return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_beam_workspace_bytes(%d, %d, %d, %d) = %zu", fn, workspace_bytes,
                 T, S, beam, cands, ctc_beam_workspace_bytes(T, S, beam, cands));
+  if (slm_call) {
+    HIPCHK(launch_ctc_beam_slm(net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest, Q, lm_next_dev, lm_final_dev,
+                               hyp_dev, hyp_len_dev, nbest_count_dev, score_dev, ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev,
+                               workspace, (hipStream_t)hip_stream));
+    return KLSTM_OK;
+  }
   HIPCHK(launch_ctc_beam_lm(net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest, Q, lm_next_dev, lm_weight_dev,
                             lm_final_dev, hyp_dev, hyp_len_dev, nbest_count_dev, score_dev, ref_labels_dev, ref_offsets_dev, errors_dev,
                             totals_dev, workspace, (hipStream_t)hip_stream));
@@ -2185,7 +2246,7 @@ klstm_status klstm_ctc_beam_decode(const float *net_out, int T, int S, int K, in
                                    const float *class_weight_dev, int beam, int cands, int nbest, int *hyp_dev, int *hyp_len_dev,
                                    int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
                                    int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  return ctc_beam_decode_checked("klstm_ctc_beam_decode", false, net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest, 0,
+  return ctc_beam_decode_checked("klstm_ctc_beam_decode", false, false, 0, net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest, 0,
                                  nullptr, nullptr, nullptr, hyp_dev, hyp_len_dev, nbest_count_dev, score_dev, ref_labels_dev, ref_offsets_dev,
                                  errors_dev, totals_dev, workspace, workspace_bytes, hip_stream);
 }
@@ -2194,9 +2255,19 @@ klstm_status klstm_ctc_beam_decode_lm(const float *net_out, int T, int S, int K,
                                       const float *lm_weight_dev, const float *lm_final_dev, int *hyp_dev, int *hyp_len_dev,
                                       int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
                                       int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  return ctc_beam_decode_checked("klstm_ctc_beam_decode_lm", true, net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest,
+  return ctc_beam_decode_checked("klstm_ctc_beam_decode_lm", true, false, 0, net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest,
                                  lm_states, lm_next_dev, lm_weight_dev, lm_final_dev, hyp_dev, hyp_len_dev, nbest_count_dev, score_dev,
                                  ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, workspace_bytes, hip_stream);
+}
+klstm_status klstm_ctc_beam_decode_slm(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
+                                       const float *class_weight_dev, int beam, int cands, int nbest, const void *slm, size_t slm_bytes,
+                                       int lm_states, const float *lm_final_dev, int *hyp_dev, int *hyp_len_dev, int *nbest_count_dev,
+                                       float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev,
+                                       double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  return ctc_beam_decode_checked("klstm_ctc_beam_decode_slm", true, true, slm_bytes, net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam,
+                                 cands, nbest, lm_states, reinterpret_cast<const int *>(slm), nullptr, lm_final_dev, hyp_dev, hyp_len_dev,
+                                 nbest_count_dev, score_dev, ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, workspace_bytes,
+                                 hip_stream);
 }
 int klstm_ctc_beam_lm_resident(int lm_states, int K, int beam, int cands) {
   if (lm_states < 1 || K < 2 || (long)lm_states * K > (1L << 24)) return 0;
@@ -2230,22 +2301,25 @@ static klstm_status ctc_beam_stream_state_check(const char *fn, int S, int beam,
                 beam, ctc_beam_stream_state_bytes(max_frames, S, beam));
   return KLSTM_OK;
 }
-klstm_status klstm_ctc_beam_stream_step(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *start_dev,
-                                        int blank, const float *class_weight_dev, int beam, int cands, int lm_states,
-                                        const int *lm_next_dev, const float *lm_weight_dev, void *state, size_t state_bytes, int max_frames,
-                                        void *workspace, size_t workspace_bytes, void *hip_stream) {
-  const char *fn = "klstm_ctc_beam_stream_step";
+// the checks and the launch behind klstm_ctc_beam_stream_step and klstm_ctc_beam_stream_step_slm (slm_call: lm_next_dev is the blob,
+// slm_bytes its size, 1 <= lm_states)
+static klstm_status ctc_beam_stream_step_checked(const char *fn, bool slm_call, size_t slm_bytes, const float *net_out, int T, int S, int K, int stride,
+                                                 const int *lens_dev, const int *start_dev, int blank, const float *class_weight_dev, int beam,
+                                                 int cands, int lm_states, const int *lm_next_dev, const float *lm_weight_dev, void *state,
+                                                 size_t state_bytes, int max_frames, void *workspace, size_t workspace_bytes, void *hip_stream) {
   if (T <= 0 || S <= 0 || K <= 0 || beam <= 0 || cands <= 0)
     return fail(KLSTM_ERR_ARG, "%s: bad size (T %d, streams %d, K %d, beam %d, candidates %d)", fn, T, S, K, beam, cands);
   if (!ctc_beam_shape_ok(T, S, beam, cands) || K < 2 || K > 32768 || cands > K - 1)
     return fail(KLSTM_ERR_SHAPE, "%s: T %d, streams %d, K %d, beam %d, candidates %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768, beam <= 64, candidates <= min(K - 1, 32)",
                 fn, T, S, K, beam, cands);
-  if (lm_states < 0 || (long)lm_states * K > (1L << 24))
-    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 0 <= states, states * K <= 2^24", fn, lm_states, K);
+  if (slm_call ? (lm_states < 1 || lm_states > (1 << 24)) : (lm_states < 0 || (long)lm_states * K > (1L << 24)))
+    return fail(KLSTM_ERR_SHAPE, slm_call ? "%s: %d language-model states (%d classes) outside 1 <= states <= 2^24"
+                                          : "%s: %d language-model states of %d classes outside 0 <= states, states * K <= 2^24", fn, lm_states, K);
   klstm_status st = ctc_beam_stream_state_check(fn, S, beam, state, state_bytes, max_frames);
   if (st != KLSTM_OK) return st;
   const char *pointers = nullptr;
-  if (lm_states > 0 && (!lm_next_dev || !lm_weight_dev)) pointers = "the language model's next and weight tables come together";
+  if (slm_call) pointers = ctc_slm_finding(lm_next_dev, slm_bytes, lm_states, K);
+  else if (lm_states > 0 && (!lm_next_dev || !lm_weight_dev)) pointers = "the language model's next and weight tables come together";
   if (!net_out || !lens_dev || !workspace) pointers = "null argument";
   st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride, nullptr, workspace);
   if (st != KLSTM_OK) return st;
@@ -2253,8 +2327,24 @@ klstm_status klstm_ctc_beam_stream_step(const float *net_out, int T, int S, int 
     return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_beam_stream_workspace_bytes(%d, %d, %d, .) = %zu", fn, workspace_bytes,
                 T, S, cands, ctc_beam_stream_workspace_bytes(T, S, cands, 1));
   HIPCHK(launch_ctc_beam_stream_step(net_out, T, S, K, stride, lens_dev, start_dev, blank, class_weight_dev, beam, cands, lm_states, lm_next_dev,
-                                     lm_weight_dev, state, max_frames, workspace, (hipStream_t)hip_stream));
+                                     lm_weight_dev, slm_call, state, max_frames, workspace, (hipStream_t)hip_stream));
   return KLSTM_OK;
+}
+klstm_status klstm_ctc_beam_stream_step(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *start_dev,
+                                        int blank, const float *class_weight_dev, int beam, int cands, int lm_states,
+                                        const int *lm_next_dev, const float *lm_weight_dev, void *state, size_t state_bytes, int max_frames,
+                                        void *workspace, size_t workspace_bytes, void *hip_stream) {
+  return ctc_beam_stream_step_checked("klstm_ctc_beam_stream_step", false, 0, net_out, T, S, K, stride, lens_dev, start_dev, blank, class_weight_dev,
+                                      beam, cands, lm_states, lm_next_dev, lm_weight_dev, state, state_bytes, max_frames, workspace,
+                                      workspace_bytes, hip_stream);
+}
+klstm_status klstm_ctc_beam_stream_step_slm(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *start_dev,
+                                            int blank, const float *class_weight_dev, int beam, int cands, const void *slm, size_t slm_bytes,
+                                            int lm_states, void *state, size_t state_bytes, int max_frames, void *workspace,
+                                            size_t workspace_bytes, void *hip_stream) {
+  return ctc_beam_stream_step_checked("klstm_ctc_beam_stream_step_slm", true, slm_bytes, net_out, T, S, K, stride, lens_dev, start_dev, blank,
+                                      class_weight_dev, beam, cands, lm_states, reinterpret_cast<const int *>(slm), nullptr, state, state_bytes,
+                                      max_frames, workspace, workspace_bytes, hip_stream);
 }
 klstm_status klstm_ctc_beam_stream_emit(int S, int K, int blank, int beam, int nbest, const int *mode_dev, int lm_states,
                                         const float *lm_final_dev, const void *state, size_t state_bytes, int max_frames, int *hyp_dev,

@@ -343,14 +343,24 @@ bool ctc_beam_lm_resident(int Q, int K, int B, int C);
 hipError_t launch_ctc_beam_lm(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
                               int Q, const int *lm_next, const float *lm_weight, const float *lm_final, int *hyp, int *hyp_len, int *count,
                               float *score, const int *refs, const int *roff, int *errors, double *totals, void *workspace, hipStream_t st);
+// the same search with a sparse back-off model (klstm_ctc_slm_build / klstm_ctc_beam_decode_slm): Q states and A arcs in CSR form become
+// one device blob of ctc_slm_bytes(Q, A) bytes, validated on the device (status [8] or null: what was dropped or cut); the search
+// walks the blob in global memory.  final [Q] or null stays a dense array.
+size_t ctc_slm_bytes(int Q, int A);
+hipError_t launch_ctc_slm_build(int Q, int A, int K, int blank, const int *off, const int *labels, const int *nxt, const float *wt,
+                                const int *backoff, const float *bow, void *blob, int *status, hipStream_t st);
+hipError_t launch_ctc_beam_slm(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const float *w, int B, int C, int N,
+                               int Q, const void *slm, const float *lm_final, int *hyp, int *hyp_len, int *count, float *score,
+                               const int *refs, const int *roff, int *errors, double *totals, void *workspace, hipStream_t st);
 // the search fed chunk by chunk (klstm_ctc_beam_stream_step / _emit of include/klstm.h; klstm_ctc_beam.hip): the beam and the prefix
 // tree of every stream live in `state` between the calls.  The workspace: statistics, ticket and the tail's counts (the part an emit
-// needs, ctc_beam_stream_emit_workspace_bytes), then C (value, column) pairs per row of a chunk.
+// needs, ctc_beam_stream_emit_workspace_bytes), then C (value, column) pairs per row of a chunk.  sparse: lm_next is the blob of a
+// sparse back-off model of Q states and lm_weight is not read.
 size_t ctc_beam_stream_state_bytes(int max_frames, int S, int B);
 size_t ctc_beam_stream_workspace_bytes(int T, int S, int C, int N);
 size_t ctc_beam_stream_emit_workspace_bytes();
 hipError_t launch_ctc_beam_stream_step(const float *y, int T, int S, int K, int stride, const int *lens, const int *start, int blank,
-                                       const float *w, int B, int C, int Q, const int *lm_next, const float *lm_weight, void *state,
+                                       const float *w, int B, int C, int Q, const int *lm_next, const float *lm_weight, bool sparse, void *state,
                                        int max_frames, void *workspace, hipStream_t st);
 hipError_t launch_ctc_beam_stream_emit(int S, int K, int blank, int B, int N, const int *mode, int Q, const float *lm_final, const void *state,
                                        int max_frames, int *hyp, int hyp_stride, int *hyp_len, int *count, float *score, int *frames,

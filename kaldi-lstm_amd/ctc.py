@@ -3,7 +3,8 @@ CUDA tensors.  Plumbing only: the label lists become the CSR arrays of the C-ABI
 ctc_greedy_decode: best-path decoding and token error rate of the same posteriors (klstm_ctc_decode).
 ctc_align: the most probable alignment of given label sequences to the frames (klstm_ctc_align).
 ctc_beam_decode: prefix beam search, n-best lists with scores and edit distances (klstm_ctc_beam_decode), with
-lm=CtcLabelLm(...) fused with a label language model or a lexicon (klstm_ctc_beam_decode_lm; tables: lm.py).
+lm=CtcLabelLm(...) fused with a label language model or a lexicon (klstm_ctc_beam_decode_lm; tables: lm.py), or
+lm=CtcSparseLabelLm(...) with a sparse back-off n-gram, read from an ARPA file or counted (klstm_ctc_beam_decode_slm).
 CtcBeamStream: the same search fed chunk by chunk, the beam kept on the device between the calls (klstm_ctc_beam_stream_step / _emit;
 INTEGRATION.md 3j).
 ctc_mbr_eval: the expected token errors over such n-best lists and their gradient (klstm_ctc_mbr_eval).
@@ -243,6 +244,46 @@ class CtcLabelLm:
         return bool(load_library().klstm_ctc_beam_lm_resident(self.states, self.classes, int(beam), int(cands)))
 
 
+class CtcSparseLabelLm:
+    """A sparse back-off language model on the device for ctc_beam_decode(lm=...) and CtcBeamStream(lm=...): the arrays of a
+    lm.SparseLm (arpa_label_lm / backoff_ngram_label_lm build them) turned into the blob the search walks (klstm_ctc_slm_build of
+    include/klstm.h), once.  The build validates on the device: `status` (a CUDA int32[8]; status_list() synchronises) counts the
+    states it dropped and the back-offs it cut.  final: the model's own unless given; None in the model: no final weights."""
+
+    def __init__(self, model, blank, final="model", device="cuda", stream=None):
+        import torch
+
+        def dev(a, dtype):
+            return torch.as_tensor(np.asarray(a)).to(device=device, dtype=dtype).contiguous()
+        lib = load_library()
+        self.classes, self.blank = int(model.classes), int(blank)
+        self.states, self.arcs = len(model.backoff), len(model.arc_labels)
+        off, lab, nxt = dev(model.arc_offsets, torch.int32), dev(model.arc_labels, torch.int32), dev(model.arc_next, torch.int32)
+        wt, bo, bow = dev(model.arc_weight, torch.float32), dev(model.backoff, torch.int32), dev(model.backoff_weight, torch.float32)
+        assert off.numel() == self.states + 1 and nxt.numel() == self.arcs and wt.numel() == self.arcs and bow.numel() == self.states
+        final = model.final if isinstance(final, str) else final
+        self.final = dev(final, torch.float32) if final is not None else None
+        assert self.final is None or self.final.shape == (self.states,)
+        self.nbytes = _workspace_bytes("klstm_ctc_slm_bytes", self.states, self.arcs, self.classes)
+        self.blob = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
+        self.status = torch.zeros(8, dtype=torch.int32, device=device)
+        _chk(lib.klstm_ctc_slm_build(self.states, self.arcs, self.classes, self.blank, off.data_ptr(), lab.data_ptr(), nxt.data_ptr(),
+                                     wt.data_ptr(), bo.data_ptr(), bow.data_ptr(), self.blob.data_ptr(), ctypes.c_size_t(self.nbytes),
+                                     self.status.data_ptr(), _sp(stream)))
+        self._inputs = (off, lab, nxt, wt, bo, bow)                      # alive until the build has run
+
+    @property
+    def device(self):
+        return self.blob.device
+
+    def status_list(self):
+        return self.status.cpu().tolist()
+
+
+def _lm_device(lm):
+    return lm.blob.device if isinstance(lm, CtcSparseLabelLm) else lm.next.device
+
+
 def ctc_beam_decode(net_out, lens, blank=0, beam=16, cands=8, nbest=1, class_weight=None, refs=None, totals=None, stream=None, lm=None):
     """CTC prefix beam search: the most probable LABELLINGS of every stream, best first.  net_out, lens, class_weight and refs as
     ctc_greedy_decode takes them; beam <= 64 prefixes survive a frame, each extended by the cands <= min(K - 1, 32) best classes of
@@ -250,7 +291,7 @@ def ctc_beam_decode(net_out, lens, blank=0, beam=16, cands=8, nbest=1, class_wei
     hyp_len [S, N] int32, nbest_count [S] int32 (list slots beyond it are not written), score [S, N] float32 (log probability as the
     search summed it), errors [S, N] int32 edit distances (-1: not counted, or no such slot) or None without refs).  totals: a
     float64[6] CUDA tensor that 1-best edit errors, reference tokens, 1-best hypothesis tokens, utterances counted, utterances with a
-    1-best error and oracle errors (the minimum over the list) are added to (needs refs).  lm: a CtcLabelLm whose factors enter
+    1-best error and oracle errors (the minimum over the list) are added to (needs refs).  lm: a CtcLabelLm or a CtcSparseLabelLm whose factors enter
     every extension; the scores are then the fused ones, acoustic times language model.  Nothing synchronises; nbest_to_lists()
     does."""
     import torch
@@ -276,6 +317,12 @@ def ctc_beam_decode(net_out, lens, blank=0, beam=16, cands=8, nbest=1, class_wei
         _chk(lib.klstm_ctc_beam_decode(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), _ptr(class_weight),
                                        beam, cands, nbest, hyp.data_ptr(), hyp_len.data_ptr(), count.data_ptr(), score.data_ptr(),
                                        _ptr(lab_dev), _ptr(off_dev), _ptr(errors), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    elif isinstance(lm, CtcSparseLabelLm):
+        assert lm.classes == K and lm.blob.device == dev, "the language model has K classes and lives on net_out's device"
+        _chk(lib.klstm_ctc_beam_decode_slm(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), _ptr(class_weight),
+                                           beam, cands, nbest, lm.blob.data_ptr(), ctypes.c_size_t(lm.nbytes), lm.states, _ptr(lm.final),
+                                           hyp.data_ptr(), hyp_len.data_ptr(), count.data_ptr(), score.data_ptr(), _ptr(lab_dev), _ptr(off_dev),
+                                           _ptr(errors), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
     else:
         assert lm.classes == K and lm.next.device == dev, "the language model's tables have K columns and live on net_out's device"
         _chk(lib.klstm_ctc_beam_decode_lm(net_out.data_ptr(), T, S, K, net_out.stride(0), lens_dev.data_ptr(), int(blank), _ptr(class_weight),
@@ -318,7 +365,7 @@ class CtcBeamStream:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         _check_class_weight(class_weight, self.K)
-        assert lm is None or (lm.classes == self.K and lm.next.device == self.device), \
+        assert lm is None or (lm.classes == self.K and _lm_device(lm) == self.device), \
             "the language model's tables have K columns and live on the stream's device"
         self.class_weight, self.lm = class_weight, lm
         self.state_bytes = ctc_beam_stream_state_bytes(self.max_frames, self.S, self.beam)
@@ -359,11 +406,23 @@ class CtcBeamStream:
         start_dev = self._ints(start, "start: S flags") if start is not None else None
         ws, nbytes = self._workspace(T, 1)
         lm = self.lm
+        if isinstance(lm, CtcSparseLabelLm):
+            _chk(load_library().klstm_ctc_beam_stream_step_slm(
+                net_out.data_ptr(), T, self.S, self.K, net_out.stride(0), lens_dev.data_ptr(), _ptr(start_dev), self.blank,
+                _ptr(self.class_weight), self.beam, self.cands, lm.blob.data_ptr(), ctypes.c_size_t(lm.nbytes), lm.states,
+                self.state.data_ptr(), ctypes.c_size_t(self.state_bytes), self.max_frames, ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+            return
         _chk(load_library().klstm_ctc_beam_stream_step(
             net_out.data_ptr(), T, self.S, self.K, net_out.stride(0), lens_dev.data_ptr(), _ptr(start_dev), self.blank,
             _ptr(self.class_weight), self.beam, self.cands, lm.states if lm else 0, _ptr(lm.next) if lm else None,
             _ptr(lm.weight) if lm else None, self.state.data_ptr(), ctypes.c_size_t(self.state_bytes), self.max_frames, ws.data_ptr(),
             ctypes.c_size_t(nbytes), _sp(stream)))
+
+    def _emit_states(self):
+        """the state count emit is told: it reads the final weights alone, so a sparse model (whose states times K may pass the dense
+        limit) counts as one state"""
+        lm = self.lm
+        return 0 if lm is None else 1 if isinstance(lm, CtcSparseLabelLm) else lm.states
 
     def emit(self, mode, nbest=1, refs=None, totals=None, stream=None):
         """The current n-best lists.  mode: S values, 0 skip the stream (nbest_count 0), 1 the list without the LM's final weights, 2
@@ -393,7 +452,7 @@ class CtcBeamStream:
             errors = torch.empty(S, max(nbest, 0), dtype=torch.int32, device=dev)
         lm = self.lm
         _chk(load_library().klstm_ctc_beam_stream_emit(
-            S, self.K, self.blank, self.beam, nbest, mode_dev.data_ptr(), lm.states if lm else 0, _ptr(lm.final) if lm else None,
+            S, self.K, self.blank, self.beam, nbest, mode_dev.data_ptr(), self._emit_states(), _ptr(lm.final) if lm else None,
             self.state.data_ptr(), ctypes.c_size_t(self.state_bytes), self.max_frames, hyp.data_ptr(), self.max_frames, hyp_len.data_ptr(),
             count.data_ptr(), score.data_ptr(), frames.data_ptr(), stable.data_ptr(), _ptr(lab_dev), _ptr(off_dev), _ptr(errors),
             _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
@@ -465,7 +524,8 @@ def ctc_mmi_workspace_bytes(T, S, K, lm_states, max_label_len):
 class CtcMmiDenominator:
     """The denominator graph of ctc_mmi_eval for one language model: built on the device from the tables of a CtcLabelLm (the object
     ctc_beam_decode(lm=...) takes) and kept for every minibatch of a training run (klstm_ctc_mmi_graph_build of include/klstm.h).
-    Owns the graph's buffer; the tables are not needed afterwards."""
+    Owns the graph's buffer; the tables are not needed afterwards.  The dense model only: a CtcSparseLabelLm is for the search, and a
+    small one reaches MMI through CtcLabelLm(*lm.sparse_lm_to_dense(model))."""
 
     def __init__(self, lm, blank=0, stream=None):
         import torch

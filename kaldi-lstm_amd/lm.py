@@ -2,7 +2,9 @@
 include/klstm.h): a dense deterministic weighted automaton over the K classes.  State 0 is the start; label c leads
 from state q to next[q, c] and multiplies the prefix probability by weight[q, c]; final[q] multiplies a hypothesis that ends in q.
 numpy only.  Both builders return (next int32 [Q, K], weight float32 [Q, K], final float32 [Q]); the blank's column is never read
-(next 0, weight 0).  Composing an n-gram with a lexicon (the product automaton) is the caller's."""
+(next 0, weight 0).  Composing an n-gram with a lexicon (the product automaton) is the caller's.  Below them the SPARSE form
+for back-off n-grams of higher order: its definition (sparse_lm_lookup), an ARPA reader and a count-based builder."""
+import collections
 import math
 
 import numpy as np
@@ -88,3 +90,287 @@ def lexicon_label_lm(words, K, blank, separator):
             weight[q, separator] = 1.0
     nxt[:, blank] = 0
     return nxt, weight, np.asarray(is_end, np.float32)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Sparse back-off models (klstm_ctc_slm_build / klstm_ctc_beam_decode_slm of include/klstm.h; ctc.CtcSparseLabelLm):
+# a deterministic automaton with back-off arcs over the K classes, state 0 the start, the arcs of a state in CSR form with strictly
+# ascending labels (never the blank), per state a back-off state (-1: none) and its weight, `final` dense as above.  Every back-off
+# chain ends after at most SPARSE_MAX_BACKOFFS back-offs.
+# ------------------------------------------------------------------------------------------------------------------------------------
+SparseLm = collections.namedtuple("SparseLm", "classes arc_offsets arc_labels arc_next arc_weight backoff backoff_weight final")
+SPARSE_MAX_BACKOFFS = 8
+
+
+def _flush(v, dtype=np.float32):
+    """the emission rule: NaN or below 2^-60 is exactly 0, above 2^60 is 2^60"""
+    v = dtype(v)
+    return min(v, dtype(2.0 ** 60)) if v >= dtype(2.0 ** -60) else dtype(0)
+
+
+def sparse_lm_lookup(lm, q, c, with_depth=False, dtype=np.float32):
+    """THE DEFINITION of a lookup (q, c) -> (g, n), which the device reproduces bit for bit: the arc of q for c gives its weight and
+    its next; without one, and without a back-off, (0, -1): forbidden; else product = flush(product * flush(backoff_weight[q])), q =
+    backoff[q], and again -- the product starts at 1 and multiplies the weight of the arc that is found after a back-off.  Every step
+    is one multiplication in `dtype`.  with_depth: (g, n, back-offs taken)."""
+    F = dtype
+    prod = F(1)
+    with np.errstate(all="ignore"):
+        for depth in range(SPARSE_MAX_BACKOFFS + 1):
+            b, e = int(lm.arc_offsets[q]), int(lm.arc_offsets[q + 1])
+            j = b + int(np.searchsorted(lm.arc_labels[b:e], c))
+            if j < e and int(lm.arc_labels[j]) == c:
+                w = F(lm.arc_weight[j])
+                g, n = (F(prod * w) if depth else w), int(lm.arc_next[j])
+                return (g, n, depth) if with_depth else (g, n)
+            if int(lm.backoff[q]) < 0:
+                break
+            prod = _flush(F(prod * _flush(lm.backoff_weight[q], F)), F)
+            q = int(lm.backoff[q])
+    return (F(0), -1, depth) if with_depth else (F(0), -1)
+
+
+def sparse_lm_to_dense(lm):
+    """the model expanded through sparse_lm_lookup into the tables of CtcLabelLm: (next int32 [Q, K], weight float32 [Q, K], final);
+    next is -1 where the lookup forbids or leaves [0, Q).  For small models: Q K entries.  A row is filled level by level down the
+    back-off chain of its state, every entry by the multiplications sparse_lm_lookup does for it, in its order (a valid model:
+    sparse_lm_validate)."""
+    F = np.float32
+    Q, K = len(lm.backoff), lm.classes
+    off, lab, arc_next = np.asarray(lm.arc_offsets), np.asarray(lm.arc_labels), np.asarray(lm.arc_next)
+    arc_wt = np.asarray(lm.arc_weight, F)
+    nxt, wt = np.full((Q, K), -1, np.int32), np.zeros((Q, K), F)
+    with np.errstate(all="ignore"):
+        for q in range(Q):
+            filled, prod, s = np.zeros(K, bool), F(1), q
+            for depth in range(SPARSE_MAX_BACKOFFS + 1):
+                b, e = int(off[s]), int(off[s + 1])
+                new = ~filled[lab[b:e]]
+                idx = lab[b:e][new]
+                wt[q, idx] = (prod * arc_wt[b:e][new]).astype(F) if depth else arc_wt[b:e][new]
+                n = arc_next[b:e][new]
+                nxt[q, idx] = np.where((n >= 0) & (n < Q), n, -1)
+                filled[idx] = True
+                if int(lm.backoff[s]) < 0:
+                    break
+                prod = _flush(F(prod * _flush(lm.backoff_weight[s])))
+                s = int(lm.backoff[s])
+    return nxt, wt, (None if lm.final is None else np.asarray(lm.final, F))
+
+
+def sparse_lm_validate(lm, blank):
+    """What klstm_ctc_slm_build makes of the arrays, on the host: (the model as cut, status [8]).  A state is DROPPED -- it loses its
+    arcs and keeps its back-off -- for [3] an arc range outside [0, A], or by its first arc at fault: [1] a label outside [0, K), [2]
+    the blank, [0] a label not above the one before.  A back-off is CUT to -1 for [4] a target outside [-1, Q) and for [5] a chain of
+    more than SPARSE_MAX_BACKOFFS back-offs, cycles included, decided for every state on the range-checked array.  [6] counts the
+    states the device stores as a direct row (at least K / 4 arcs): a matter of layout, not of content."""
+    K, Q, A = lm.classes, len(lm.backoff), len(lm.arc_labels)
+    off, lab = [int(v) for v in lm.arc_offsets], [int(v) for v in lm.arc_labels]
+    status = [0] * 8
+    ranges = []
+    for q in range(Q):
+        b, e, why = off[q], off[q + 1], -1
+        if b < 0 or e < b or e > A:
+            why = 3
+        else:
+            prev = -1
+            for j in range(b, e):
+                c = lab[j]
+                why = 1 if c < 0 or c >= K else 2 if c == blank else 0 if c <= prev else -1
+                if why >= 0:
+                    break
+                prev = c
+        if why >= 0:
+            status[why] += 1
+            b = e = 0
+        ranges.append((b, e))
+        if e - b > 0 and (e - b) * 4 >= K:
+            status[6] += 1
+    raw = []
+    for q in range(Q):
+        bo = int(lm.backoff[q])
+        if bo < -1 or bo >= Q:
+            status[4] += 1
+            bo = -1
+        raw.append(bo)
+    cut = list(raw)
+    for q in range(Q):
+        d, s = 0, raw[q]
+        while s >= 0 and d <= SPARSE_MAX_BACKOFFS:
+            d, s = d + 1, raw[s]
+        if d > SPARSE_MAX_BACKOFFS:
+            cut[q] = -1
+            status[5] += 1
+    offsets, labels, nxt, wt = [0], [], [], []
+    for b, e in ranges:
+        labels += lab[b:e]
+        nxt += [int(v) for v in lm.arc_next[b:e]]
+        wt += [np.float32(v) for v in lm.arc_weight[b:e]]
+        offsets.append(len(labels))
+    out = SparseLm(K, np.asarray(offsets, np.int64), np.asarray(labels, np.int64), np.asarray(nxt, np.int64), np.asarray(wt, np.float32),
+                   np.asarray(cut, np.int64), np.asarray(lm.backoff_weight, np.float32), lm.final)
+    return out, status
+
+
+def _sparse_from_states(K, states, arcs_of, bow_of, final_of, order, dtype):
+    """states: the histories (tuples; -1 stands for the start of the sequence), states[0] the start; arcs_of(h) -> {label: weight};
+    the next state of (h, c) is the longest suffix of h + (c,) that is a state, the back-off of h its longest proper suffix that is"""
+    index = {h: i for i, h in enumerate(states)}
+
+    def longest(h):
+        while h not in index:
+            h = h[1:]
+        return index[h]
+    offsets, labels, nxt, wt, backoff, bow, fin = [0], [], [], [], [], [], []
+    for h in states:
+        for c, g in sorted(arcs_of(h).items()):
+            labels.append(c); wt.append(g)
+            nxt.append(longest((h + (c,))[-(order - 1):] if order > 1 else ()))
+        offsets.append(len(labels))
+        backoff.append(longest(h[1:]) if h else -1)
+        bow.append(bow_of(h) if h else 1.0)
+        fin.append(final_of(h))
+    depth = max(len(h) for h in states)
+    assert depth <= SPARSE_MAX_BACKOFFS, "a back-off chain of %d: orders up to %d" % (depth, SPARSE_MAX_BACKOFFS + 1)
+    return SparseLm(K, np.asarray(offsets, np.int32), np.asarray(labels, np.int32), np.asarray(nxt, np.int32), np.asarray(wt, dtype),
+                    np.asarray(backoff, np.int32), np.asarray(bow, dtype), np.asarray(fin, dtype))
+
+
+def _ordered_states(histories, order):
+    """the start history first ((-1,), or () for a unigram), then the empty history, then the others by length and content"""
+    start = (-1,) if order > 1 else ()
+    rest = sorted(set(histories) - {start, ()}, key=lambda h: (len(h), h))
+    return [start] + ([()] if order > 1 else []) + rest
+
+
+def arpa_label_lm(path_or_text, symbols, K, blank, alpha=1.0, beta=0.0):
+    """Reads a back-off n-gram in ARPA format (a path, or the text itself: it begins with a backslash section or holds a newline)
+    into a SparseLm.  symbols: token -> class (a dict, or a sequence whose index is the class); n-grams with a token that maps to no
+    class are skipped, as are those with <s> anywhere but first or </s> anywhere but last.  States are the histories (every listed
+    n-gram below the highest order, every context), the <s> history is state 0; the next state is the longest suffix of history +
+    label that is a state; arc weight 10^(alpha logp) e^beta, back-off weight 10^(alpha logbow) (0 where none is given), final =
+    P(</s> | history)^alpha with back-off applied, in float64.  Orders up to 9."""
+    text = path_or_text
+    if "\n" not in text and not text.lstrip().startswith("\\"):
+        with open(path_or_text) as fh:
+            text = fh.read()
+    if not isinstance(symbols, dict):
+        symbols = {tok: i for i, tok in enumerate(symbols) if tok is not None}
+    logp, logbow, order, n = {}, {}, 0, 0
+    for line in text.splitlines():
+        f = line.split()
+        if not f:
+            continue
+        if f[0].startswith("\\"):
+            n = int(f[0][1:f[0].index("-")]) if f[0].endswith("-grams:") else 0
+            order = max(order, n)
+            continue
+        if n == 0 or len(f) < n + 1:
+            continue
+        gram, ok = [], True
+        for i, tok in enumerate(f[1:n + 1]):
+            if tok == "<s>":
+                ok &= i == 0
+                gram.append(-1)
+            elif tok == "</s>":
+                ok &= i == n - 1
+                gram.append(-2)
+            else:
+                c = symbols.get(tok)
+                ok &= c is not None and 0 <= c < K and c != blank
+                gram.append(c)
+        if not ok:
+            continue
+        gram = tuple(gram)
+        logp[gram] = float(f[0])
+        if len(f) > n + 1:
+            logbow[gram] = float(f[n + 1])
+    assert 1 <= order <= SPARSE_MAX_BACKOFFS + 1, "orders 1 to %d" % (SPARSE_MAX_BACKOFFS + 1)
+    hist = {()}
+    for gram in logp:
+        hist.add(gram[:-1])
+        if len(gram) < order and gram[-1] != -2:
+            hist.add(gram)
+    states = _ordered_states(hist, order)
+
+    by_hist = {}
+    for gram, lp in logp.items():
+        if gram[-1] >= 0:
+            by_hist.setdefault(gram[:-1], {})[gram[-1]] = 10.0 ** (alpha * lp) * math.exp(beta)
+
+    def end_log(h):
+        acc = 0.0
+        while True:
+            if h + (-2,) in logp:
+                return acc + logp[h + (-2,)]
+            if not h:
+                return -math.inf
+            acc += logbow.get(h, 0.0)
+            h = h[1:]
+
+    def final_of(h):
+        lp = end_log(h)
+        return 10.0 ** (alpha * lp) if lp > -math.inf else 0.0
+    return _sparse_from_states(K, states, lambda h: by_hist.get(h, {}), lambda h: 10.0 ** (alpha * logbow.get(h, 0.0)), final_of, order,
+                               np.float32)
+
+
+def backoff_ngram_label_lm(sequences, K, blank, order=3, discount=0.75, alpha=1.0, beta=0.0, dtype=np.float32):
+    """An absolute-discounting back-off n-gram over label sequences (lists of classes other than the blank), order 1 to 9, as a
+    SparseLm.  Events are the K - 1 labels and the end of the sequence; histories are the last order - 1 tokens, the start of the
+    sequence among them.  For a history h with n(h) events, d(h) of them distinct: P(w | h) = (n(h, w) - discount) / n(h) for a seen
+    event, and bow(h) P(w | h') for an unseen one, h' being h without its oldest token and bow(h) = discount d(h) / n(h) over the mass
+    h' gives to the events unseen in h (a history that has seen all K events is not discounted).  The empty history spreads its left-over mass evenly over all K events, so every label has an
+    arc there and every distribution sums to 1.  Arc weight P^alpha e^beta, back-off weight bow^alpha, final P(end | h)^alpha with
+    back-off applied; everything is computed in float64 and cast to `dtype` at the end."""
+    assert 1 <= order <= SPARSE_MAX_BACKOFFS + 1 and 0.0 < discount < 1.0
+    END = K                                                  # the end of the sequence as one more event
+    counts = {}
+    for seq in sequences:
+        ctx = [-1]
+        for w in [int(c) for c in seq] + [END]:
+            assert w == END or (0 <= w < K and w != blank), "labels are classes other than the blank"
+            for k in range(min(order - 1, len(ctx)) + 1):
+                h = tuple(ctx[len(ctx) - k:])
+                row = counts.setdefault(h, {})
+                row[w] = row.get(w, 0) + 1
+            ctx.append(w)
+    counts.setdefault((), {})
+    if order > 1:
+        counts.setdefault((-1,), {})
+    states = _ordered_states(counts.keys(), order)
+    full, seen_p, bows = {}, {}, {}
+    for h in sorted(states, key=len):                        # a history after the one it backs off to
+        row = counts[h]
+        n = float(sum(row.values()))
+        p = np.zeros(K + 1, np.float64)
+        if not h:
+            if n > 0:
+                for w, cnt in row.items():
+                    p[w] = (cnt - discount) / n
+                left = discount * len(row) / n
+            else:
+                left = 1.0
+            share = np.full(K + 1, left / K)
+            share[blank] = 0.0
+            p = p + share
+            seen_p[h], bows[h] = {w: p[w] for w in range(K + 1) if w != blank}, 1.0
+        else:
+            low = full[h[1:]]
+            if len(row) == K:                                # every event seen: nothing to back off to, so nothing is discounted
+                sp, bow = {w: cnt / n for w, cnt in row.items()}, 0.0
+            elif n > 0:
+                sp = {w: (cnt - discount) / n for w, cnt in row.items()}
+                bow = discount * len(row) / n / (1.0 - sum(low[w] for w in sp))
+            else:
+                sp, bow = {}, 1.0
+            p = bow * low
+            for w, v in sp.items():
+                p[w] = v
+            seen_p[h], bows[h] = sp, bow
+        full[h] = p
+    ebeta = math.exp(beta)
+
+    def arcs_of(h):
+        return {w: v ** alpha * ebeta for w, v in seen_p[h].items() if w != END}
+    return _sparse_from_states(K, states, arcs_of, lambda h: bows[h] ** alpha, lambda h: full[h][END] ** alpha, order, dtype)
