@@ -931,19 +931,57 @@ inline SparseLabelLm ReadArpaLabelLm(std::istream &is, const std::map<std::strin
 // the entries listed per stream, their edit distances [num_stream][nbest] (null when it had no references)
 struct CtcNbestDevice { const int32 *hyp, *hyp_len, *count, *errors; int32 num_stream, nbest, stride; };
 
-class CtcBeamDecoder : private CtcCallBase {
+// What CtcBeamDecoder and CtcStreamDecoder share on top of CtcCallBase: the sizes of the search, the language model in use, and the
+// six totals with their accessors and the report.  (A base for its members only, like CtcCallBase.)
+class CtcBeamBase : protected CtcCallBase {
  public:
-  explicit CtcBeamDecoder(int32 blank = 0, int32 beam = 16, int32 cands = 8, int32 nbest = 1)
-      : CtcCallBase(blank), beam_(beam), cands_(cands), nbest_(nbest) {}
-
   // One weight per class: the emission of a frame is y[k] * w[k] (label priors: w[k] = prior[k]^-alpha).  Empty: none.
   using CtcCallBase::SetClassWeights;
-  // Fuses a language model into the search: every later Decode goes through klstm_ctc_beam_decode_lm and its scores are the fused
-  // ones.  The decoder keeps the pointer, not the tables; null: the search without one, as before.
+  // Fuses a language model into the search: every later call goes through the C call that takes one (klstm_ctc_beam_decode_lm,
+  // klstm_ctc_beam_stream_step with its tables) and its scores are the fused ones.  The decoder keeps the pointer, not the tables;
+  // null: the search without one, as before.
   void SetLanguageModel(const CtcLabelLm *lm) { lm_ = lm; slm_ = nullptr; }
-  // The same with a sparse back-off model (klstm_ctc_beam_decode_slm); the later of the two calls decides, null: none
+  // The same with a sparse back-off model (klstm_ctc_beam_decode_slm, klstm_ctc_beam_stream_step_slm); the later of the two calls
+  // decides, null: none
   void SetLanguageModel(const CtcSparseLabelLm *slm) { slm_ = slm; lm_ = nullptr; }
   void SetLanguageModel(std::nullptr_t) { lm_ = nullptr; slm_ = nullptr; }
+
+  // over the utterances counted so far (CtcStreamDecoder: emitted with mode 2 and a reference)
+  double TokenErrorRate() const { const double *h = tot_.Read(); return h[0] / h[1]; }          // 1-best edit errors / reference tokens
+  double OracleTokenErrorRate() const { const double *h = tot_.Read(); return h[5] / h[1]; }    // the best of each list
+  double UtteranceErrorRate() const { const double *h = tot_.Read(); return h[4] / h[3]; }
+  double NumUtterances() const { return tot_.Read()[3]; }
+  double NumErrors() const { return tot_.Read()[0]; }
+  double NumOracleErrors() const { return tot_.Read()[5]; }
+  double NumRefTokens() const { return tot_.Read()[1]; }
+  double NumHypTokens() const { return tot_.Read()[2]; }
+  std::string Report() const {
+    const double *h = tot_.Read();
+    std::ostringstream oss;
+    oss << "UTT_ERROR_RATE: " << 100.0 * h[4] / h[3] << "% [" << h[3] << " utterances, " << h[0] << " errors, " << h[1]
+        << " reference tokens, " << h[2] << " hypothesis tokens]" << std::endl;
+    oss << "ORACLE_TOKEN_ERROR_RATE: " << 100.0 * h[5] / h[1] << "% [" << nbest_ << "-best, beam " << beam_ << ", " << cands_ << " candidates" << how_
+        << "]" << std::endl;
+    oss << "\nTOKEN_ERROR_RATE >> " << 100.0 * h[0] / h[1] << "% <<";
+    return oss.str();
+  }
+ protected:
+  // how: what the report says behind the sizes ("" or ", streaming")
+  CtcBeamBase(int32 blank, int32 beam, int32 cands, int32 nbest, const char *how)
+      : CtcCallBase(blank), beam_(beam), cands_(cands), nbest_(nbest), how_(how) {}
+  int32 beam_, cands_, nbest_;
+  const CtcLabelLm *lm_ = nullptr;
+  const CtcSparseLabelLm *slm_ = nullptr;
+  DeviceTotals<6> tot_;
+ private:
+  const char *how_;
+};
+
+// SetClassWeights, SetLanguageModel, the error rates and Report(): CtcBeamBase
+class CtcBeamDecoder : public CtcBeamBase {
+ public:
+  explicit CtcBeamDecoder(int32 blank = 0, int32 beam = 16, int32 cands = 8, int32 nbest = 1) : CtcBeamBase(blank, beam, cands, nbest, "") {}
+
   // net_out, lens, refs as CtcGreedyDecoder::Decode takes them; lists (optional): the n-best list of every stream (empty for an idle
   // one).  Asking for lists synchronises; the rest stays on the device.
   void Decode(const DeviceMatrix &net_out, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &refs,
@@ -1024,32 +1062,11 @@ class CtcBeamDecoder : private CtcCallBase {
   CtcNbestDevice DeviceLists() const {
     return CtcNbestDevice{hyp_.As<int32>(), hlen_.As<int32>(), cnt_.As<int32>(), scored_ ? err_.As<int32>() : nullptr, num_stream_, nbest_, frames_};
   }
-
-  double TokenErrorRate() const { const double *h = tot_.Read(); return h[0] / h[1]; }          // 1-best edit errors / reference tokens
-  double OracleTokenErrorRate() const { const double *h = tot_.Read(); return h[5] / h[1]; }    // the best of each list
-  double UtteranceErrorRate() const { const double *h = tot_.Read(); return h[4] / h[3]; }
-  double NumUtterances() const { return tot_.Read()[3]; }
-  double NumErrors() const { return tot_.Read()[0]; }
-  double NumOracleErrors() const { return tot_.Read()[5]; }
-  double NumRefTokens() const { return tot_.Read()[1]; }
-  double NumHypTokens() const { return tot_.Read()[2]; }
-  std::string Report() const {
-    const double *h = tot_.Read();
-    std::ostringstream oss;
-    oss << "UTT_ERROR_RATE: " << 100.0 * h[4] / h[3] << "% [" << h[3] << " utterances, " << h[0] << " errors, " << h[1]
-        << " reference tokens, " << h[2] << " hypothesis tokens]" << std::endl;
-    oss << "ORACLE_TOKEN_ERROR_RATE: " << 100.0 * h[5] / h[1] << "% [" << nbest_ << "-best, beam " << beam_ << ", " << cands_ << " candidates]" << std::endl;
-    oss << "\nTOKEN_ERROR_RATE >> " << 100.0 * h[0] / h[1] << "% <<";
-    return oss.str();
-  }
  private:
-  int32 beam_, cands_, nbest_, frames_ = 0;
+  int32 frames_ = 0;
   bool scored_ = false;
-  const CtcLabelLm *lm_ = nullptr;
-  const CtcSparseLabelLm *slm_ = nullptr;
   PackedLabels refs_;
   DeviceBuffer hyp_, hlen_, cnt_, score_, err_;
-  DeviceTotals<6> tot_;
 };
 
 // The prefix beam search fed chunk by chunk (klstm_ctc_beam_stream_step / _emit, klstm.h): num_stream searches whose
@@ -1057,19 +1074,16 @@ class CtcBeamDecoder : private CtcCallBase {
 // the scorer leaves it (include/klstm_scorer.hpp BatchScorer::ForEachChunk); Emit reads the current n-best lists and changes nothing,
 // so partial results cost one small launch.  For any chunking the lists are CtcBeamDecoder's on the frames consumed so far, bit for
 // bit.  The six totals cover the streams emitted with mode 2 and references; they stay on the device and are read when somebody asks.
-class CtcStreamDecoder : private CtcCallBase {
+// SetClassWeights, SetLanguageModel, the error rates and Report(): CtcBeamBase.
+class CtcStreamDecoder : public CtcBeamBase {
  public:
   CtcStreamDecoder(int32 blank, int32 beam, int32 cands, int32 nbest, int32 num_stream, int32 max_frames)
-      : CtcCallBase(blank), beam_(beam), cands_(cands), nbest_(nbest), max_frames_(max_frames) {
+      : CtcBeamBase(blank, beam, cands, nbest, ", streaming"), max_frames_(max_frames) {
     num_stream_ = num_stream;
     KLSTM_ASSERT(nbest >= 1);
     state_bytes_ = klstm_ctc_beam_stream_state_bytes(max_frames, num_stream, beam);      // host only: a refused shape needs no GPU
     if (state_bytes_ == 0) KLSTM_ERR("klstm: " << klstm_last_error());
   }
-  using CtcCallBase::SetClassWeights;
-  void SetLanguageModel(const CtcLabelLm *lm) { lm_ = lm; slm_ = nullptr; }         // the decoder keeps the pointer, not the tables; null: none
-  void SetLanguageModel(const CtcSparseLabelLm *slm) { slm_ = slm; lm_ = nullptr; }  // a sparse back-off model; the later call decides
-  void SetLanguageModel(std::nullptr_t) { lm_ = nullptr; slm_ = nullptr; }
   int32 NumStream() const { return num_stream_; }
   int32 MaxFrames() const { return max_frames_; }
 
@@ -1148,25 +1162,6 @@ class CtcStreamDecoder : private CtcCallBase {
         (*lists)[s].push_back(hy);
       }
   }
-
-  // over the utterances finalised so far: emitted with mode 2 and a reference
-  double TokenErrorRate() const { const double *h = tot_.Read(); return h[0] / h[1]; }
-  double OracleTokenErrorRate() const { const double *h = tot_.Read(); return h[5] / h[1]; }
-  double UtteranceErrorRate() const { const double *h = tot_.Read(); return h[4] / h[3]; }
-  double NumUtterances() const { return tot_.Read()[3]; }
-  double NumErrors() const { return tot_.Read()[0]; }
-  double NumOracleErrors() const { return tot_.Read()[5]; }
-  double NumRefTokens() const { return tot_.Read()[1]; }
-  double NumHypTokens() const { return tot_.Read()[2]; }
-  std::string Report() const {
-    const double *h = tot_.Read();
-    std::ostringstream oss;
-    oss << "UTT_ERROR_RATE: " << 100.0 * h[4] / h[3] << "% [" << h[3] << " utterances, " << h[0] << " errors, " << h[1]
-        << " reference tokens, " << h[2] << " hypothesis tokens]" << std::endl;
-    oss << "ORACLE_TOKEN_ERROR_RATE: " << 100.0 * h[5] / h[1] << "% [" << nbest_ << "-best, beam " << beam_ << ", " << cands_ << " candidates, streaming]" << std::endl;
-    oss << "\nTOKEN_ERROR_RATE >> " << 100.0 * h[0] / h[1] << "% <<";
-    return oss.str();
-  }
  private:
   void *State() {                                       // zero-filled: "nothing yet" in every stream
     if (!state_.As<void>()) {
@@ -1175,13 +1170,10 @@ class CtcStreamDecoder : private CtcCallBase {
     }
     return state_.As<void>();
   }
-  int32 beam_, cands_, nbest_, max_frames_, classes_ = 0;
+  int32 max_frames_, classes_ = 0;
   size_t state_bytes_ = 0;
-  const CtcLabelLm *lm_ = nullptr;
-  const CtcSparseLabelLm *slm_ = nullptr;
   PackedLabels refs_;
   DeviceBuffer state_, start_, mode_, hyp_, hlen_, cnt_, score_, err_, fr_, stab_;
-  DeviceTotals<6> tot_;
 };
 
 // Minimum expected token error over the n-best lists of a CtcBeamDecoder (klstm_ctc_mbr_eval, klstm.h): the

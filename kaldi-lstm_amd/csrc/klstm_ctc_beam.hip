@@ -8,6 +8,8 @@
 //                  and its keys live in LDS.  A total is a non-negative float, so (float bits, ~list position) is ONE 64-bit integer
 //                  key and selection is an integer rank: a key's place in the new beam is the number of keys above it.  Prefix-tree nodes (parent, token) go to the workspace, B a frame.
 //                  After the last frame the first N live entries are written out: the prefix by walking the parents, the score.
+//                  Its storage, lm_fetch, table staging and frame loop are the text of klstm_ctc_beam_frame.h, which the streaming
+//                  kernel k_ctc_beam_stream below includes too: ONE frame body in source, compiled into both.
 //   k_ctc_beam_tail grid (S), 256 threads, only with references: wave q % 4 runs the one-wave Levenshtein recurrence of
 //                  klstm_ctc_dev.h for hypothesis q; the workgroup that finishes last adds the statistics onto the totals, streams in order.
 // ARITHMETIC.  Every step on the chain is ONE float32 operation rounded to nearest (bmul / badd below: never contracted into an
@@ -234,28 +236,15 @@ __device__ __forceinline__ float beam_score(float tot, int E) {
   return tot > 0.f ? (float)badd(log((double)tot), bmul((double)E, 0.6931471805599453)) : -INFINITY;
 }
 
+// The frame body -- storage, lm_fetch, the staging of resident tables and the frame loop -- is the text of klstm_ctc_beam_frame.h, included here and in
+// k_ctc_beam_stream part by part; KLSTM_BEAM_FRAME and KLSTM_BEAM_NODE are the two places where the kernels differ.
 template <int LM>
 __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, int T, int S, int K, int stride, const int *__restrict__ lens,
                                                   const float *__restrict__ w, int blank, int B, int C, int N, const float *__restrict__ topv,
                                                   const int *__restrict__ topi, int *npar, int *ntok, int *hyp, int *__restrict__ hyp_len,
                                                   int *__restrict__ count, float *__restrict__ score, BeamLm lm) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char beam_dyn[];     // LM = 2: weight [Q K] float, next [Q K] int
-  __shared__ __attribute__((aligned(16))) u64 keys[BEAM_MAXLIST];
-  __shared__ u64 sel[BEAM_MAXB];                                   // the new beam's keys, best first
-  __shared__ u64 e_hash[BEAM_MAXB], e_ph[BEAM_MAXB];               // hash of the prefix, hash of the prefix without its last token
-  __shared__ int e_node[BEAM_MAXB], e_tok[BEAM_MAXB], e_len[BEAM_MAXB];
-  __shared__ float e_pb[BEAM_MAXB], e_pnb[BEAM_MAXB], s_pb[BEAM_MAXB], s_pnb[BEAM_MAXB];
-  __shared__ float cvs[LM ? 2 * BEAM_MAXC : BEAM_MAXC];            // with an LM: the candidates of frame t in half t & 1
-  __shared__ int cis[LM ? 2 * BEAM_MAXC : BEAM_MAXC];
-  __shared__ unsigned char merged[BEAM_MAXB * BEAM_MAXC];          // extension (i, r) went into the stay entry of its prefix (LM: 1 + its slot)
-  __shared__ int e_lm[LM ? 2 * BEAM_MAXB : 1];                     // LM state of the beam entries of frame t in half t & 1
-  __shared__ int nq[LM ? BEAM_MAXB * BEAM_MAXC : 1];               // LM state an extension leads to
-  float gw[BEAM_LMK];                                              // weight and next state of this thread's extensions, fetched a frame ahead
-  int gn[BEAM_LMK];
-  const float *const lw = reinterpret_cast<const float *>(beam_dyn);
-  const int *const lnx = reinterpret_cast<const int *>(beam_dyn) + (LM == 2 ? lm.Q * K : 0);
-  SlmView slm{};                                                   // LM = 3: the sections of the blob
-  if constexpr (LM == 3) slm = slm_view(lm.next, lm.Q);
+#define KLSTM_BEAM_PART 1
+#include "klstm_ctc_beam_frame.h"
 
   const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   int len = lens[s];
@@ -275,196 +264,23 @@ __global__ __launch_bounds__(256) void k_ctc_beam(const float *__restrict__ y, i
   float nv = 0.f, neb = beam_emit_at(y + (size_t)s * stride, w, blank);
   int ni = -1;
   if (tid < C) { nv = topv[(size_t)s * C + tid]; ni = topi[(size_t)s * C + tid]; }
-  // the table entries of the extensions q = tid + k nt < nbc of the beam and the candidates in half `half`
-  auto lm_fetch = [&](int half, int nbc) {
-#pragma unroll
-    for (int k = 0; k < BEAM_LMK; k++) {
-      gw[k] = 0.f; gn[k] = -1;
-      const int q = tid + k * nt;
-      if (q < nbc) {
-        const int i = q / C, c = cis[half * BEAM_MAXC + q - i * C];
-        if ((unsigned)c < (unsigned)K) {                            // -1: no candidate of that rank
-          const int idx = e_lm[half * BEAM_MAXB + i] * K + c;      // states in e_lm lie inside [0, Q): only a checked `next` gets there
-          if constexpr (LM == 3) slm_lookup(slm, e_lm[half * BEAM_MAXB + i], c, gw[k], gn[k]);
-          else if constexpr (LM == 2) { gw[k] = lw[idx]; gn[k] = lnx[idx]; }
-          else { gw[k] = lm.weight[idx]; gn[k] = lm.next[idx]; }
-        }
-      }
-    }
-  };
+#define KLSTM_BEAM_PART 2
+#include "klstm_ctc_beam_frame.h"
   if constexpr (LM != 0) {
-    if constexpr (LM == 2) {                                       // stage the tables: 16 bytes a load where the pointers allow it
-      float *dw = reinterpret_cast<float *>(beam_dyn);
-      int *dn = reinterpret_cast<int *>(beam_dyn) + lm.Q * K;
-      const int nel = lm.Q * K;
-      if (nel % 4 == 0 && ((reinterpret_cast<uintptr_t>(lm.weight) | reinterpret_cast<uintptr_t>(lm.next)) & 15) == 0) {
-        const float4 *sw = reinterpret_cast<const float4 *>(lm.weight);
-        const int4 *sn = reinterpret_cast<const int4 *>(lm.next);
-#pragma unroll 4
-        for (int q = tid; q < nel / 4; q += nt) {
-          reinterpret_cast<float4 *>(dw)[q] = sw[q];
-          reinterpret_cast<int4 *>(dn)[q] = sn[q];
-        }
-      } else {
-#pragma unroll 4
-        for (int q = tid; q < nel; q += nt) { dw[q] = lm.weight[q]; dn[q] = lm.next[q]; }
-      }
-    }
+#define KLSTM_BEAM_PART 3
+#include "klstm_ctc_beam_frame.h"
     if (tid == 0) e_lm[0] = 0;
     if (tid < C) { cvs[tid] = nv; cis[tid] = ni; }
     __syncthreads();
     lm_fetch(0, C);
   }
 
-  for (int t = 0; t < len; t++) {
-    const size_t r = (size_t)t * S + s;
-    const float *yp = y + r * stride;
-    float *const cv = cvs + (LM ? (t & 1) * BEAM_MAXC : 0);
-    int *const ci = cis + (LM ? (t & 1) * BEAM_MAXC : 0);
-    if constexpr (LM == 0)
-      if (tid < C) { cv[tid] = nv; ci[tid] = ni; }
-    const float eb = neb;
-    if (tid < B) sel[tid] = 0;                                     // slots no key lands in: no entry
-    if (t + 1 < len) {
-      const size_t r1 = r + S;
-      neb = beam_emit_at(y + r1 * stride, w, blank);
-      if (tid < C) { nv = topv[r1 * C + tid]; ni = topi[r1 * C + tid]; }
-    }
-    __syncthreads();                                               // the candidates; the beam the frame before wrote
-    if (tid < Bc) {                                                // stay entries
-      const int j = tid, l = e_tok[j];
-      const float tot = badd(e_pb[j], e_pnb[j]);
-      const float spb = bmul(tot, eb);
-      float spnb = 0.f;
-      bool deferred = false;
-      if (l >= 0) {
-        spnb = bmul(e_pnb[j], beam_emit_at(yp, w, l));
-        int pi = -1, rr = -1;
-        for (int i = 0; i < Bc; i++)
-          if (e_len[i] + 1 == e_len[j] && e_hash[i] == e_ph[j]) pi = i;
-        for (int q = 0; q < C; q++)
-          if (ci[q] == l && cv[q] > 0.f) rr = q;
-        if (pi >= 0 && rr >= 0) {                                  // the extension of the parent by l IS this prefix
-          if constexpr (LM == 0) {
-            const float v = bmul(l == e_tok[pi] ? e_pb[pi] : badd(e_pb[pi], e_pnb[pi]), cv[rr]);
-            spnb = badd(spnb, v);
-            merged[pi * C + rr] = 1;
-          } else {                                                 // the thread that holds the extension's factor adds it and writes the key
-            merged[pi * C + rr] = (unsigned char)(j + 1);
-            deferred = true;
-          }
-        }
-      }
-      s_pb[j] = spb; s_pnb[j] = spnb;
-      if (!deferred) keys[j] = ((u64)__float_as_uint(badd(spb, spnb)) << 32) | (u64)(0xFFFFFFFFu - (unsigned)j);
-    }
-    __syncthreads();
-    const int n = Bc * (C + 1);
-    if constexpr (LM != 0) {                                       // extensions with the fused emission f in place of cv[rr]
-#pragma unroll
-      for (int k = 0; k < BEAM_LMK; k++) {
-        const int q = tid + k * nt;
-        if (q < Bc * C) {
-          const int i = q / C, rr = q - i * C, pos = Bc + q, n1 = gn[k];
-          float f = 0.f;
-          if (cv[rr] > 0.f && (unsigned)n1 < (unsigned)lm.Q) f = beam_emit(bmul(cv[rr], beam_emit(gw[k])));
-          const float v = bmul(ci[rr] == e_tok[i] ? e_pb[i] : badd(e_pb[i], e_pnb[i]), f);
-          const int m = merged[q];
-          u64 key = 0;
-          if (m) {
-            const int j = m - 1;
-            const float spnb = badd(s_pnb[j], v);
-            merged[q] = 0;
-            s_pnb[j] = spnb;
-            keys[j] = ((u64)__float_as_uint(badd(s_pb[j], spnb)) << 32) | (u64)(0xFFFFFFFFu - (unsigned)j);
-          } else if (v > 0.f) key = ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)pos);
-          keys[pos] = key;
-          nq[q] = n1;
-        }
-      }
-    } else {
-      for (int pos = Bc + tid; pos < n; pos += nt) {               // extensions; key 0: no entry
-        u64 key = 0;
-        const int q = pos - Bc, i = q / C, rr = q - i * C;
-        if (merged[q]) merged[q] = 0;
-        else if (cv[rr] > 0.f) {
-          const float v = bmul(ci[rr] == e_tok[i] ? e_pb[i] : badd(e_pb[i], e_pnb[i]), cv[rr]);
-          if (v > 0.f) key = ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)pos);
-        }
-        keys[pos] = key;
-      }
-    }
-    if (tid == 0) keys[n] = 0;                                     // the pair reads below may run one past an odd n
-    __syncthreads();
-    // selection by rank: the keys are distinct, so the number of larger keys IS the place in the new beam.  Every thread walks the
-    // same addresses (LDS broadcasts, two keys a read); no sorting network, no barrier between its stages
-    const ulonglong2 *k2 = reinterpret_cast<const ulonglong2 *>(keys);
-    const int np = (n + 1) / 2;
-    if (n <= nt) {                                                 // one key a thread
-      const u64 key = tid < n ? keys[tid] : 0;
-      int rank = 0;
-#pragma unroll 8
-      for (int j = 0; j < np; j++) {
-        const ulonglong2 o = k2[j];
-        rank += (o.x > key) + (o.y > key);
-      }
-      if (key && rank < B) sel[rank] = key;
-    } else {                                                       // up to BEAM_KPT keys a thread, every read serves all of them
-      u64 my[BEAM_KPT];
-      int rank[BEAM_KPT];
-#pragma unroll
-      for (int e = 0; e < BEAM_KPT; e++) {
-        const int pos = tid + e * nt;
-        my[e] = pos < n ? keys[pos] : ~0ull;                        // nothing is above ~0: rank 0 for free, never stored
-        rank[e] = 0;
-      }
-#pragma unroll 2
-      for (int j = 0; j < np; j++) {
-        const ulonglong2 o = k2[j];
-#pragma unroll
-        for (int e = 0; e < BEAM_KPT; e++) rank[e] += (o.x > my[e]) + (o.y > my[e]);
-      }
-#pragma unroll
-      for (int e = 0; e < BEAM_KPT; e++)
-        if (my[e] != ~0ull && my[e] && rank[e] < B) sel[rank[e]] = my[e];
-    }
-    __syncthreads();
-    // the new beam: the first B keys that are entries
-    const unsigned mbits = (unsigned)(sel[0] >> 32);
-    const u64 key = tid < B ? sel[tid] : 0;
-    int node = 0, tok = 0, ln = 0, lst = 0;
-    u64 hs = 0, ph = 0;
-    float pb = 0.f, pnb = 0.f;
-    if (key) {
-      const int pos = (int)(0xFFFFFFFFu - (unsigned)key);
-      if (pos < Bc) {
-        node = e_node[pos]; tok = e_tok[pos]; ln = e_len[pos]; hs = e_hash[pos]; ph = e_ph[pos]; pb = s_pb[pos]; pnb = s_pnb[pos];
-        if constexpr (LM != 0) lst = e_lm[(t & 1) * BEAM_MAXB + pos];
-      } else {
-        const int q = pos - Bc, i = q / C, rr = q - i * C;
-        node = 1 + t * B + tid; tok = ci[rr]; ln = e_len[i] + 1; ph = e_hash[i]; hs = beam_hash(ph, tok);
-        pnb = __uint_as_float((unsigned)(key >> 32));
-        npar[nbase + node] = e_node[i]; ntok[nbase + node] = tok;
-        if constexpr (LM != 0) lst = nq[q];
-      }
-      if (mbits) {                                                 // M = m 2^k, m in [0.5, 1): times 2^-k, exact
-        const int ex = (int)((mbits >> 23) & 0xffu);
-        const float sc = __uint_as_float((unsigned)(253 - ex) << 23);
-        pb = bmul(pb, sc); pnb = bmul(pnb, sc);
-        pb = pb >= BEAM_TINY ? pb : 0.f; pnb = pnb >= BEAM_TINY ? pnb : 0.f;
-      }
-    }
-    if constexpr (LM != 0) {                                       // the other halves: nobody reads them in this frame
-      const int h1 = (t + 1) & 1;
-      if (key) e_lm[h1 * BEAM_MAXB + tid] = lst;
-      if (tid < C) { cvs[h1 * BEAM_MAXC + tid] = nv; cis[h1 * BEAM_MAXC + tid] = ni; }
-    }
-    Bc = __syncthreads_count(key != 0);                            // everybody has read the old beam
-    if constexpr (LM != 0)
-      if (t + 1 < len) lm_fetch((t + 1) & 1, Bc * C);              // in flight over the barrier and the stay entries of frame t + 1
-    if (mbits) E += (int)((mbits >> 23) & 0xffu) - 126;
-    if (key) { e_node[tid] = node; e_tok[tid] = tok; e_len[tid] = ln; e_hash[tid] = hs; e_ph[tid] = ph; e_pb[tid] = pb; e_pnb[tid] = pnb; }
-  }
+#define KLSTM_BEAM_FRAME t
+#define KLSTM_BEAM_NODE(n) nbase + n
+#define KLSTM_BEAM_PART 4
+#include "klstm_ctc_beam_frame.h"
+#undef KLSTM_BEAM_FRAME
+#undef KLSTM_BEAM_NODE
   __syncthreads();
   __threadfence_block();                                           // the nodes other threads wrote
   if (tid >= 64) return;
@@ -751,9 +567,11 @@ static hipError_t launch_ctc_beam_any(const float *y, int T, int S, int K, int s
 // search above is a frame chain whose whole carried state is Bc, E and at most 64 beam entries plus the prefix tree, so it can stop at
 // any frame boundary and go on in another launch with the same bits.  k_ctc_beam_stream<LM> is the frame loop of k_ctc_beam over the
 // frames of one CHUNK, between a load and a store of that state; k_ctc_beam_emit<LM> is its epilogue as a kernel of its own, which
-// only reads the state and shares the list rule (beam_list_slot, beam_score) with it.  The frame body is a copy of k_ctc_beam's, not
-// shared code: one __forceinline__ body under both kernels was built and measured, and missed the speed bar in the small-beam LM
-// cells (profiles/ctc_beam_shared_body_ab.json).  A change to one frame body is made to the other, identically.
+// only reads the state and shares the list rule (beam_list_slot, beam_score) with it.  The frame body is k_ctc_beam's: the same text,
+// klstm_ctc_beam_frame.h, compiled into both kernels, with the frame's index and the place of a node as the two macros each kernel
+// sets.  Shared TEXT, not a shared function: one __forceinline__ body under both kernels was built and measured, and missed the
+// speed bar in the small-beam LM cells (profiles/ctc_beam_shared_body_ab.json); the included text compiles to the
+// instructions the two copies had (profiles/ctc_beam_one_body_isa.txt).  The prologues and epilogues differ and stay here.
 // State of stream s at state + s * beam_state_stride(max_frames, B):
 //   int hdr[16]          [0] BEAM_STARTED once a step began an utterance here, [1] frames consumed, [2] Bc, [3] E, [4] overflow flag
 //   u64 hash[64], ph[64]; int node[64], tok[64], len[64], lm[64]; float pb[64], pnb[64]          the beam entries, Bc of them valid
@@ -792,23 +610,8 @@ __global__ __launch_bounds__(256) void k_ctc_beam_stream(const float *__restrict
                                                          const int *__restrict__ start, const float *__restrict__ w, int blank, int B, int C,
                                                          const float *__restrict__ topv, const int *__restrict__ topi, void *state,
                                                          int max_frames, BeamLm lm) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char beam_dyn[];     // LM = 2: weight [Q K] float, next [Q K] int
-  __shared__ __attribute__((aligned(16))) u64 keys[BEAM_MAXLIST];
-  __shared__ u64 sel[BEAM_MAXB];
-  __shared__ u64 e_hash[BEAM_MAXB], e_ph[BEAM_MAXB];
-  __shared__ int e_node[BEAM_MAXB], e_tok[BEAM_MAXB], e_len[BEAM_MAXB];
-  __shared__ float e_pb[BEAM_MAXB], e_pnb[BEAM_MAXB], s_pb[BEAM_MAXB], s_pnb[BEAM_MAXB];
-  __shared__ float cvs[LM ? 2 * BEAM_MAXC : BEAM_MAXC];
-  __shared__ int cis[LM ? 2 * BEAM_MAXC : BEAM_MAXC];
-  __shared__ unsigned char merged[BEAM_MAXB * BEAM_MAXC];
-  __shared__ int e_lm[LM ? 2 * BEAM_MAXB : 1];
-  __shared__ int nq[LM ? BEAM_MAXB * BEAM_MAXC : 1];
-  float gw[BEAM_LMK];
-  int gn[BEAM_LMK];
-  const float *const lw = reinterpret_cast<const float *>(beam_dyn);
-  const int *const lnx = reinterpret_cast<const int *>(beam_dyn) + (LM == 2 ? lm.Q * K : 0);
-  SlmView slm{};                                                   // LM = 3: the sections of the blob
-  if constexpr (LM == 3) slm = slm_view(lm.next, lm.Q);
+#define KLSTM_BEAM_PART 1
+#include "klstm_ctc_beam_frame.h"
 
   const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const int len = lens[s];
@@ -842,191 +645,22 @@ __global__ __launch_bounds__(256) void k_ctc_beam_stream(const float *__restrict
   float nv = 0.f, neb = beam_emit_at(y + (size_t)s * stride, w, blank);
   int ni = -1;
   if (tid < C) { nv = topv[(size_t)s * C + tid]; ni = topi[(size_t)s * C + tid]; }
-  auto lm_fetch = [&](int half, int nbc) {
-#pragma unroll
-    for (int k = 0; k < BEAM_LMK; k++) {
-      gw[k] = 0.f; gn[k] = -1;
-      const int q = tid + k * nt;
-      if (q < nbc) {
-        const int i = q / C, c = cis[half * BEAM_MAXC + q - i * C];
-        if ((unsigned)c < (unsigned)K) {
-          const int idx = e_lm[half * BEAM_MAXB + i] * K + c;
-          if constexpr (LM == 3) slm_lookup(slm, e_lm[half * BEAM_MAXB + i], c, gw[k], gn[k]);
-          else if constexpr (LM == 2) { gw[k] = lw[idx]; gn[k] = lnx[idx]; }
-          else { gw[k] = lm.weight[idx]; gn[k] = lm.next[idx]; }
-        }
-      }
-    }
-  };
+#define KLSTM_BEAM_PART 2
+#include "klstm_ctc_beam_frame.h"
   if constexpr (LM != 0) {
-    if constexpr (LM == 2) {
-      float *dw = reinterpret_cast<float *>(beam_dyn);
-      int *dn = reinterpret_cast<int *>(beam_dyn) + lm.Q * K;
-      const int nel = lm.Q * K;
-      if (nel % 4 == 0 && ((reinterpret_cast<uintptr_t>(lm.weight) | reinterpret_cast<uintptr_t>(lm.next)) & 15) == 0) {
-        const float4 *sw = reinterpret_cast<const float4 *>(lm.weight);
-        const int4 *sn = reinterpret_cast<const int4 *>(lm.next);
-#pragma unroll 4
-        for (int q = tid; q < nel / 4; q += nt) {
-          reinterpret_cast<float4 *>(dw)[q] = sw[q];
-          reinterpret_cast<int4 *>(dn)[q] = sn[q];
-        }
-      } else {
-#pragma unroll 4
-        for (int q = tid; q < nel; q += nt) { dw[q] = lm.weight[q]; dn[q] = lm.next[q]; }
-      }
-    }
+#define KLSTM_BEAM_PART 3
+#include "klstm_ctc_beam_frame.h"
     if (tid < C) { cvs[tid] = nv; cis[tid] = ni; }
     __syncthreads();
     lm_fetch(0, Bc * C);
   }
 
-  for (int t = 0; t < len; t++) {
-    const size_t r = (size_t)t * S + s;
-    const float *yp = y + r * stride;
-    float *const cv = cvs + (LM ? (t & 1) * BEAM_MAXC : 0);
-    int *const ci = cis + (LM ? (t & 1) * BEAM_MAXC : 0);
-    if constexpr (LM == 0)
-      if (tid < C) { cv[tid] = nv; ci[tid] = ni; }
-    const float eb = neb;
-    if (tid < B) sel[tid] = 0;
-    if (t + 1 < len) {
-      const size_t r1 = r + S;
-      neb = beam_emit_at(y + r1 * stride, w, blank);
-      if (tid < C) { nv = topv[r1 * C + tid]; ni = topi[r1 * C + tid]; }
-    }
-    __syncthreads();
-    if (tid < Bc) {                                                // stay entries
-      const int j = tid, l = e_tok[j];
-      const float tot = badd(e_pb[j], e_pnb[j]);
-      const float spb = bmul(tot, eb);
-      float spnb = 0.f;
-      bool deferred = false;
-      if (l >= 0) {
-        spnb = bmul(e_pnb[j], beam_emit_at(yp, w, l));
-        int pi = -1, rr = -1;
-        for (int i = 0; i < Bc; i++)
-          if (e_len[i] + 1 == e_len[j] && e_hash[i] == e_ph[j]) pi = i;
-        for (int q = 0; q < C; q++)
-          if (ci[q] == l && cv[q] > 0.f) rr = q;
-        if (pi >= 0 && rr >= 0) {
-          if constexpr (LM == 0) {
-            const float v = bmul(l == e_tok[pi] ? e_pb[pi] : badd(e_pb[pi], e_pnb[pi]), cv[rr]);
-            spnb = badd(spnb, v);
-            merged[pi * C + rr] = 1;
-          } else {
-            merged[pi * C + rr] = (unsigned char)(j + 1);
-            deferred = true;
-          }
-        }
-      }
-      s_pb[j] = spb; s_pnb[j] = spnb;
-      if (!deferred) keys[j] = ((u64)__float_as_uint(badd(spb, spnb)) << 32) | (u64)(0xFFFFFFFFu - (unsigned)j);
-    }
-    __syncthreads();
-    const int n = Bc * (C + 1);
-    if constexpr (LM != 0) {
-#pragma unroll
-      for (int k = 0; k < BEAM_LMK; k++) {
-        const int q = tid + k * nt;
-        if (q < Bc * C) {
-          const int i = q / C, rr = q - i * C, pos = Bc + q, n1 = gn[k];
-          float f = 0.f;
-          if (cv[rr] > 0.f && (unsigned)n1 < (unsigned)lm.Q) f = beam_emit(bmul(cv[rr], beam_emit(gw[k])));
-          const float v = bmul(ci[rr] == e_tok[i] ? e_pb[i] : badd(e_pb[i], e_pnb[i]), f);
-          const int m = merged[q];
-          u64 key = 0;
-          if (m) {
-            const int j = m - 1;
-            const float spnb = badd(s_pnb[j], v);
-            merged[q] = 0;
-            s_pnb[j] = spnb;
-            keys[j] = ((u64)__float_as_uint(badd(s_pb[j], spnb)) << 32) | (u64)(0xFFFFFFFFu - (unsigned)j);
-          } else if (v > 0.f) key = ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)pos);
-          keys[pos] = key;
-          nq[q] = n1;
-        }
-      }
-    } else {
-      for (int pos = Bc + tid; pos < n; pos += nt) {
-        u64 key = 0;
-        const int q = pos - Bc, i = q / C, rr = q - i * C;
-        if (merged[q]) merged[q] = 0;
-        else if (cv[rr] > 0.f) {
-          const float v = bmul(ci[rr] == e_tok[i] ? e_pb[i] : badd(e_pb[i], e_pnb[i]), cv[rr]);
-          if (v > 0.f) key = ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)pos);
-        }
-        keys[pos] = key;
-      }
-    }
-    if (tid == 0) keys[n] = 0;
-    __syncthreads();
-    const ulonglong2 *k2 = reinterpret_cast<const ulonglong2 *>(keys);
-    const int np = (n + 1) / 2;
-    if (n <= nt) {
-      const u64 key = tid < n ? keys[tid] : 0;
-      int rank = 0;
-#pragma unroll 8
-      for (int j = 0; j < np; j++) {
-        const ulonglong2 o = k2[j];
-        rank += (o.x > key) + (o.y > key);
-      }
-      if (key && rank < B) sel[rank] = key;
-    } else {
-      u64 my[BEAM_KPT];
-      int rank[BEAM_KPT];
-#pragma unroll
-      for (int e = 0; e < BEAM_KPT; e++) {
-        const int pos = tid + e * nt;
-        my[e] = pos < n ? keys[pos] : ~0ull;
-        rank[e] = 0;
-      }
-#pragma unroll 2
-      for (int j = 0; j < np; j++) {
-        const ulonglong2 o = k2[j];
-#pragma unroll
-        for (int e = 0; e < BEAM_KPT; e++) rank[e] += (o.x > my[e]) + (o.y > my[e]);
-      }
-#pragma unroll
-      for (int e = 0; e < BEAM_KPT; e++)
-        if (my[e] != ~0ull && my[e] && rank[e] < B) sel[rank[e]] = my[e];
-    }
-    __syncthreads();
-    const unsigned mbits = (unsigned)(sel[0] >> 32);
-    const u64 key = tid < B ? sel[tid] : 0;
-    int node = 0, tok = 0, ln = 0, lst = 0;
-    u64 hs = 0, ph = 0;
-    float pb = 0.f, pnb = 0.f;
-    if (key) {
-      const int pos = (int)(0xFFFFFFFFu - (unsigned)key);
-      if (pos < Bc) {
-        node = e_node[pos]; tok = e_tok[pos]; ln = e_len[pos]; hs = e_hash[pos]; ph = e_ph[pos]; pb = s_pb[pos]; pnb = s_pnb[pos];
-        if constexpr (LM != 0) lst = e_lm[(t & 1) * BEAM_MAXB + pos];
-      } else {
-        const int q = pos - Bc, i = q / C, rr = q - i * C;
-        node = 1 + (t0 + t) * B + tid; tok = ci[rr]; ln = e_len[i] + 1; ph = e_hash[i]; hs = beam_hash(ph, tok);   // t0 + t < max_frames
-        pnb = __uint_as_float((unsigned)(key >> 32));
-        npar[node] = e_node[i]; ntok[node] = tok;
-        if constexpr (LM != 0) lst = nq[q];
-      }
-      if (mbits) {
-        const int ex = (int)((mbits >> 23) & 0xffu);
-        const float sc = __uint_as_float((unsigned)(253 - ex) << 23);
-        pb = bmul(pb, sc); pnb = bmul(pnb, sc);
-        pb = pb >= BEAM_TINY ? pb : 0.f; pnb = pnb >= BEAM_TINY ? pnb : 0.f;
-      }
-    }
-    if constexpr (LM != 0) {
-      const int h1 = (t + 1) & 1;
-      if (key) e_lm[h1 * BEAM_MAXB + tid] = lst;
-      if (tid < C) { cvs[h1 * BEAM_MAXC + tid] = nv; cis[h1 * BEAM_MAXC + tid] = ni; }
-    }
-    Bc = __syncthreads_count(key != 0);
-    if constexpr (LM != 0)
-      if (t + 1 < len) lm_fetch((t + 1) & 1, Bc * C);
-    if (mbits) E += (int)((mbits >> 23) & 0xffu) - 126;
-    if (key) { e_node[tid] = node; e_tok[tid] = tok; e_len[tid] = ln; e_hash[tid] = hs; e_ph[tid] = ph; e_pb[tid] = pb; e_pnb[tid] = pnb; }
-  }
+#define KLSTM_BEAM_FRAME (t0 + t)                                   // t0 + t < max_frames
+#define KLSTM_BEAM_NODE(n) n
+#define KLSTM_BEAM_PART 4
+#include "klstm_ctc_beam_frame.h"
+#undef KLSTM_BEAM_FRAME
+#undef KLSTM_BEAM_NODE
   __syncthreads();
   if (tid < Bc) {                                                  // the beam goes back where the next step, or an emit, finds it
     bs.node[tid] = e_node[tid]; bs.tok[tid] = e_tok[tid]; bs.len[tid] = e_len[tid]; bs.hash[tid] = e_hash[tid]; bs.ph[tid] = e_ph[tid];

@@ -1,13 +1,14 @@
 """The numpy twin of klstm_ctc_beam_decode_lm (include/klstm.h; tests/test_ctc_beam_lm.py, tests/test_ctc_beam_lm_gpu.py), host only: the
 search of tests/ctc_beam_ref.py with a label language model fused in.  The LM is a dense deterministic weighted automaton over the
 labels: state 0 is the start, label c leads from state q to next[q][c] and multiplies the prefix probability by weight[q][c];
-final[q] (optional) multiplies a hypothesis that ends in q.  The twin IS the definition; what it adds to beam_stream:
+final[q] (optional) multiplies a hypothesis that ends in q.  The twin IS the definition.  The frame, the list rule and the accounting
+are the ones of tests/ctc_beam_ref.py (frame, nbest_list, errors_and_totals), given the tables; what they do with them:
   state            every prefix-tree node carries an LM state: 0 for the empty prefix, next[state_i][c] for entry i extended by c
   fused emission   f = flush(float32(e[c] * flush(weight[state_i][c]))), flush being the emission rule (NaN or below 2^-60: exactly 0,
                    above 2^60: 2^60); f = 0 where next[state_i][c] lies outside [0, Q).  The extension's value is float32(p * f), p
                    being pb or pb + pnb as without an LM, both where it is merged into the stay entry of the same prefix and where
                    it becomes a list entry.  e * g first, then the product with p: every product stays inside [2^-120, 2^121].
-                   Candidates are chosen by the emission alone; stay entries, selection, ties and rescale are beam_stream's
+                   Candidates are chosen by the emission alone; stay entries, selection, ties and rescale do not know of the LM
   final weights    tf = float32(total * flush(final[state])); the list is the entries with tf > 0 by tf descending (ties: the earlier
                    beam position), the first N; none: the first beam entry alone with score -inf.  Without `final` the list is
                    beam_twin's.  The blank column of both tables is never read.
@@ -18,10 +19,7 @@ import math
 
 import numpy as np
 
-from tests.ctc_beam_ref import F, H_EMPTY, LN2, candidates_all, emissions, emissions64, hash_step
-from tests.ctc_decode_ref import levenshtein
-
-TINY = F(2.0 ** -60)
+from tests.ctc_beam_ref import Stream, beam_totals, emissions, emissions64, errors_and_totals, frame, nbest_list
 
 
 def lm_tables(lm):
@@ -37,71 +35,10 @@ def beam_stream_lm(e, blank, B, C, nxt_tab, wt_tab, stats=None):
     """e [n, K] emissions of the valid frames; nxt_tab, wt_tab of lm_tables().  -> (entries, E): entries in beam order, each (prefix
     list, pb, pnb, LM state) after the last rescale.  stats: a dict whose "merges" counts the extensions with f > 0 that went into a
     stay entry."""
-    Q = nxt_tab.shape[0]
-    par, tok, ln, hs, st = [-1], [-1], [0], [H_EMPTY], [0]   # the prefix tree; node 0 is the empty prefix, in LM state 0
-    beam = [(0, F(1), F(0))]                                 # (node, pb, pnb)
-    E = 0
-    cands = candidates_all(e, blank, C)
-    with np.errstate(all="ignore"):
-        for t in range(e.shape[0]):
-            row = e[t]
-            eb = row[blank]
-            cand = cands[t]
-            tot = [F(pb + pnb) for _, pb, pnb in beam]
-            spb = [F(tot[i] * eb) for i in range(len(beam))]
-            spnb = [F(beam[i][2] * row[tok[beam[i][0]]]) if tok[beam[i][0]] >= 0 else F(0) for i in range(len(beam))]
-            index = {(ln[nd], hs[nd]): j for j, (nd, _, _) in enumerate(beam)}
-            new = []
-            for i, (nd, pb, pnb) in enumerate(beam):
-                q = st[nd]
-                for c in cand:
-                    q1 = int(nxt_tab[q, c])
-                    f = F(row[c] * wt_tab[q, c])
-                    f = (min(f, F(2.0 ** 60)) if f >= TINY else F(0)) if 0 <= q1 < Q else F(0)
-                    v = F((pb if c == tok[nd] else tot[i]) * f)
-                    key = (ln[nd] + 1, hash_step(hs[nd], c))
-                    j = index.get(key)
-                    if j is not None:
-                        spnb[j] = F(spnb[j] + v)
-                        if stats is not None and f > 0:
-                            stats["merges"] = stats.get("merges", 0) + 1
-                    elif v > 0:
-                        new.append((nd, c, key, v, q1))
-            items = [(F(spb[i] + spnb[i]), i) for i in range(len(beam))] + [(F(F(0) + it[3]), len(beam) + q) for q, it in enumerate(new)]
-            items.sort(key=lambda it: -float(it[0]))         # stable: ties keep the list order
-            items = items[:B]
-            nb = []
-            for _, pos in items:
-                if pos < len(beam):
-                    nb.append((beam[pos][0], spb[pos], spnb[pos]))
-                else:
-                    nd, c, key, v, q1 = new[pos - len(beam)]
-                    par.append(nd); tok.append(c); ln.append(key[0]); hs.append(key[1]); st.append(q1)
-                    nb.append((len(par) - 1, F(0), v))
-            M = items[0][0]
-            if M > 0:
-                _, k = math.frexp(float(M))
-                sc = F(2.0 ** -k)
-                E += k
-
-                def resc(p):
-                    p = F(p * sc)
-                    return p if p >= TINY else F(0)
-                nb = [(nd, resc(pb), resc(pnb)) for nd, pb, pnb in nb]
-            beam = nb
-    out = []
-    for nd, pb, pnb in beam:
-        pre, q = [], st[nd]
-        while nd > 0:
-            pre.append(tok[nd])
-            nd = par[nd]
-        out.append((pre[::-1], pb, pnb, q))
-    return out, E
-
-
-def total_score(tf, E):
-    with np.errstate(all="ignore"):
-        return F(np.log(np.float64(tf)) + E * LN2) if tf > 0 else F(-np.inf)
+    z = Stream()
+    for row in e:
+        frame(z, row, blank, B, C, nxt_tab, wt_tab, stats)
+    return [(z.prefix(nd), pb, pnb, z.st[nd]) for nd, pb, pnb in z.beam], z.E
 
 
 def beam_twin_lm(y, lens, blank, beam, cands, nbest, lm, w=None, refs=None, stats=None):
@@ -118,32 +55,10 @@ def beam_twin_lm(y, lens, blank, beam, cands, nbest, lm, w=None, refs=None, stat
             hyp.append([]); score.append([]); count.append(0); state.append([])
             continue
         ent, E = beam_stream_lm(emissions(y[:n, s], w), blank, beam, cands, nxt_tab, wt_tab, stats)
-        with np.errstate(all="ignore"):
-            tf = [F(pb + pnb) if fin is None else F(F(pb + pnb) * fin[q]) for _, pb, pnb, q in ent]
-        order = list(range(len(ent)))
-        if fin is not None:
-            order.sort(key=lambda i: -float(tf[i]))          # stable: ties keep the beam order
-        live = [i for i in order if tf[i] > 0][:nbest]
-        if live:
-            score.append([total_score(tf[i], E) for i in live])
-        else:
-            live = [0]
-            score.append([F(-np.inf)])
-        hyp.append([ent[i][0] for i in live])
+        live, sc = nbest_list(beam_totals(ent), E, nbest, None if fin is None else [fin[q] for _, _, _, q in ent])
+        hyp.append([ent[i][0] for i in live]); score.append(sc); count.append(len(live))
         state.append([ent[i][3] for i in live])
-        count.append(len(live))
-    errors = totals = None
-    if refs is not None:
-        errors, totals = [[-1] * nbest for _ in range(S)], [0.0] * 6
-        for s in range(S):
-            r = list(refs[s])
-            if not 0 < lens[s] <= T or len(r) > 1023 or any(c < 0 or c >= K or c == blank for c in r):
-                continue
-            for q, h in enumerate(hyp[s]):
-                errors[s][q] = levenshtein(h, r)
-            e1 = errors[s][0]
-            totals = [totals[0] + e1, totals[1] + len(r), totals[2] + len(hyp[s][0]), totals[3] + 1, totals[4] + (e1 > 0),
-                      totals[5] + min(errors[s][:count[s]])]
+    errors, totals = errors_and_totals(hyp, count, lens, T, K, blank, nbest, refs)
     return dict(hyp=hyp, score=score, nbest_count=count, errors=errors, totals=totals, state=state)
 
 
