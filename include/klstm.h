@@ -70,6 +70,12 @@ typedef enum {
 const char *klstm_last_error(void);
 /* Library / kernel-arch identification string, e.g. "klstm 0.4 gfx950 (...)". */
 const char *klstm_version(void);
+/* The host's bookkeeping of the value-only granule rings ("persist_gran", below), exported so that it can be checked without a device:
+ * what value-only launch number `ordinal` (counting from 0) does at T frames, when the last user of the OTHER
+ * ring wrote `last_other` slots and a ring has `slots` slots; cap = 0: the engine's cap.  out[0] = 1 value-only / 0 tagged (T + 2 above
+ * the cap), out[1] = the ring it uses, out[2] = slots 1 .. out[2] of the other ring it writes the poison pattern into again, out[3] = the
+ * slot count the rings must be re-allocated (and poisoned) at first, 0: none. */
+void klstm_gran_plan(unsigned ordinal, int T, int last_other, int slots, int cap, int out[4]);
 
 /* Replaces: LstmProjectedStreams(input_dim, output_dim) + <CellDim>/<NumStream> of
  * InitData/ReadData (...streams.h:27-33, :55-99, :101-131).  recur_dim == output_dim.
@@ -748,6 +754,15 @@ klstm_status klstm_ctc_align(const float *net_out, int T, int S, int K, int stri
  *                  captured launches and the bf16 many-stream launches always do).  Bit-identical results; the device words
  *                  hold the same values either way (klstm_profile_query "persist_word_epoch_fwd" | "persist_word_epoch_bwd" |
  *                  "persist_word_launches" read them back), so the setting may change at any minibatch boundary.  A-B runs and tests.
+ *                  "persist_gran" 1/0: what the in-launch exchange of the fp32 forward chain carries at 1..4 streams.  0: {tag, value}
+ *                  granules of 8 bytes.  1 (default): VALUE-ONLY granules -- the 16 bytes of a cell's four stream values; a dword is
+ *                  fresh when it differs from a signalling-NaN pattern the slot held before (no multiply or add returns one, and a
+ *                  value with exactly those bits would leave as the canonical quiet NaN).  One slot per step in one of two rings;
+ *                  every launch hands the other ring's used slots back as that pattern; the rings grow with the frames per
+ *                  minibatch (up to 254: longer minibatches keep the tags).  Launches captured into a graph of the "graph"
+ *                  option, "persist_verify" = 1, 5..16 streams and the backward chain keep the tags; the two transports own
+ *                  separate buffers, so the setting may change at any minibatch boundary.  Bit-identical results.
+ *                  klstm_profile_query(e, "gran_value_launches", ..) counts the launches that exchanged value-only granules.
  *                  Not supported: a hipGraph captured by the CALLER around engine calls that take the persistent chain (the
  *                  engine cannot count launches inside a foreign graph): use "persist" = 0 there.
  *                  Per-engine knobs (A-B experiments and tests): "persist_waves" (forward and backward geometry: 8, 12, 16),

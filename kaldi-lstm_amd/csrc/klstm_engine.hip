@@ -170,6 +170,15 @@ struct klstm_engine {
   // host waits on the done word ("persist_verify"); 0: every launch reads the device words and its last workgroup moves them on.
   unsigned ep_fwd = 0, ep_bwd = 0;
   int persist_epoch = 1;
+  // Option "persist_gran" (1, default): the fp32 FORWARD chain at 1..4 streams exchanges VALUE-ONLY granules (klstm_persist_dev.h) where the
+  // launch goes straight to the stream and nobody waits on its done word; 0, captured launches, "persist_verify", more streams, T + 2 >
+  // GRAN_CAP_SLOTS: the tagged granules in their own buffer (gran[0]), so the two never hand anything over.  Both rings in one allocation
+  // (grown with T, filled with POISON in stream order whenever allocated and in recover()), and the host's record of who wrote what (gran_plan).
+  // (The backward chain keeps the tags: its value-only form measured 1 us per launch slower)
+  int persist_gran = 1;
+  unsigned *granv = nullptr;
+  GranState gvs;
+  long n_gran_value = 0;        // launches that used the value-only transport (klstm_profile_query "gran_value_launches")
   bool eager_now = true;        // the launch sequence being issued goes straight to the stream (run_graphed: false while it is captured)
   int persist_verify = 0;       // option: wait for every persistent launch and answer a give-up before the call returns
   int verify_spin = 1;          // option "persist_verify_spin": that wait spins on the host-mapped done word (0: hipStreamSynchronize)
@@ -526,6 +535,7 @@ static klstm_status do_backpropagate(klstm_engine *e, const float *in, int in_st
                                      float *in_diff, int in_diff_stride, int rows, float momentum, int flags);
 static klstm_status do_update(klstm_engine *e, float learn_rate, float clip_grad);
 static klstm_status apply_reset(klstm_engine *e, const std::vector<int> &flags);
+static klstm_status poison_rings(klstm_engine *e);
 
 static klstm_status recover(klstm_engine *e, const unsigned (&w)[16]) {
   unsigned fseq = 0;                                  // ordinal of the first launch that gave up
@@ -535,6 +545,8 @@ static klstm_status recover(klstm_engine *e, const unsigned (&w)[16]) {
   HIPCHK(hipMemcpy(e->pctrl, z, sizeof(z), hipMemcpyHostToDevice));
   e->ep_fwd = w[0]; e->ep_bwd = w[4];                     // (the stream is idle: the words are what every enqueued launch left -- the mirror's own values)
   if (e->pstat_host) e->pstat_host[1] &= 0x7fffffffu;     // (the done word's give-up bit: answered here)
+  // value-only granules: launches behind the give-up neither published nor poisoned -- both rings start over
+  { const klstm_status ps = poison_rings(e); if (ps != KLSTM_OK) return ps; }
   e->n_giveups++;
   if (e->cooldown_cur < e->cooldown_len || e->clean_run >= (long)e->cooldown_cur) e->cooldown_cur = e->cooldown_len;
   else e->cooldown_cur = e->cooldown_cur >= (1 << 15) ? (1 << 16) : 2 * e->cooldown_cur;
@@ -722,6 +734,11 @@ extern "C" {
 const char *klstm_last_error(void) { return g_err.c_str(); }
 const char *klstm_version(void) { return "klstm 0.4 gfx950 (f32 MFMA, weights-resident chains for 1..8 streams and per-XCD for 9..32 in bf16, 16-bit split-operand products with range guard)"; }
 
+void klstm_gran_plan(unsigned ordinal, int T, int last_other, int slots, int cap, int out[4]) {
+  const GranPlan p = gran_plan(ordinal, T, last_other, slots, cap > 0 ? cap : GRAN_CAP_SLOTS);
+  out[0] = p.use; out[1] = p.ring; out[2] = p.npoison; out[3] = p.grow_to;
+}
+
 klstm_status klstm_create(int input_dim, int cell_dim, int recur_dim, int num_stream, int device,
                           void *hip_stream, klstm_engine **out) {
   if (!out) return fail(KLSTM_ERR_ARG, "klstm_create: out is null");
@@ -815,6 +832,7 @@ void klstm_destroy(klstm_engine *e) {
   for (float *p : ps) if (p) (void)hipFree(p);
   if (e->flags_dev) (void)hipFree(e->flags_dev);
   for (auto *g : e->gran) if (g) (void)hipFree(g);
+  if (e->granv) (void)hipFree(e->granv);
   if (e->pctrl) (void)hipFree(e->pctrl);
   if (e->tr_ctr) (void)hipFree(e->tr_ctr);
   if (e->fold_scratch) (void)hipFree(e->fold_scratch);
@@ -993,6 +1011,40 @@ static void set_epoch_args(klstm_engine *e, unsigned epoch) {
   e->popt.epoch = epoch;
   e->popt.ordinal = e->pseq + 1;                      // (pseq moves on once the call's launches are enqueued)
 }
+// Both rings back to POISON, in stream order (allocation, growth, recover()).
+static klstm_status poison_rings(klstm_engine *e) {
+  if (!e->granv) return KLSTM_OK;
+  const size_t bytes = persist_granv_bytes(Dims{e->I, e->C, e->R, e->S, 0}, e->gvs.slots);
+  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->granv), (int)GRAN_POISON, bytes / 4, e->stream));
+  gran_reset(e->gvs);
+  return KLSTM_OK;
+}
+// The granule transport of the persistent FORWARD launch about to be issued: value-only rings from gran_plan() where they apply
+// (PersistOpts::gv_*), else the tagged buffer.  Called once per launch that goes straight to the stream.
+static klstm_status set_gran_args(klstm_engine *e, int T) {
+  e->popt.gv_rings = nullptr; e->popt.gv_ring = 0; e->popt.gv_npoison = 0; e->popt.gv_slots = 0;
+  if (!e->persist_gran || !e->eager_now || e->persist_verify) return KLSTM_OK;
+  if (!persist_gran_fwd(Dims{e->I, e->C, e->R, e->S, T}, e->popt)) return KLSTM_OK;   // (5..16 streams, or a geometry without a value-only instance)
+  GranState &gs = e->gvs;
+  const GranPlan pl = gran_plan(gs.n, T, gs.last[1 - (int)(gs.n & 1u)], gs.slots);
+  if (!pl.use) return KLSTM_OK;                       // (above the cap: tags)
+  if (pl.grow_to) {
+    if (e->granv) {                                   // (launches in flight still poll the old rings)
+      HIPCHK(hipStreamSynchronize(e->stream));
+      HIPCHK(hipFree(e->granv));
+      e->granv = nullptr;
+    }
+    gs.slots = pl.grow_to;
+    HIPCHK(hipMalloc(&e->granv, persist_granv_bytes(Dims{e->I, e->C, e->R, e->S, 0}, gs.slots)));
+    const klstm_status ps = poison_rings(e);
+    if (ps != KLSTM_OK) return ps;
+  }
+  e->popt.gv_rings = e->granv; e->popt.gv_ring = pl.ring;
+  e->popt.gv_npoison = pl.npoison; e->popt.gv_slots = gs.slots;
+  gran_advance(gs, pl, T);
+  e->n_gran_value++;
+  return KLSTM_OK;
+}
 
 static klstm_status seq_forward(klstm_engine *e, const float *in, int in_stride, float *out, int out_stride, int T) {
   const Dims d{e->I, e->C, e->R, e->S, T};
@@ -1026,6 +1078,7 @@ static klstm_status seq_forward(klstm_engine *e, const float *in, int in_stride,
     // gates kernel, r(0) mirrored into time block 0; steps 2..T close over m(t-1) through W_rm; r(1..T) in one GEMM
     if (e->fwd_persist) {                         // (all T steps in the one launch, step 1 on the natural matrices)
       set_epoch_args(e, e->ep_fwd);
+      { const klstm_status gs = set_gran_args(e, T); if (gs != KLSTM_OK) return gs; }
       HIPCHK(launch_fwd_persist(d, p, in, in_stride, out, out_stride, e->gran[0], e->pctrl, e->popt, st, probe(e, "k_fwd_persist"), e->fwd_inf));
       e->persist_dirty = true;
       if (persist_r_in_kernel(d, e->popt)) return KLSTM_OK;  // (r(1..T), the output rows and the carried r come out of the same launch)
@@ -1711,6 +1764,7 @@ klstm_status klstm_set_option(klstm_engine *e, const char *key, int value) {
     else if (!strcmp(key, "persist_verify")) e->persist_verify = value != 0;
     else if (!strcmp(key, "persist_verify_spin")) e->verify_spin = value != 0;
     else if (!strcmp(key, "persist_epoch")) e->persist_epoch = value != 0;
+    else if (!strcmp(key, "persist_gran")) e->persist_gran = value != 0;
     else if (!strcmp(key, "persist_cooldown")) { e->cooldown_len = value < 0 ? 0 : value; e->cooldown_cur = 0; if (e->cooldown > e->cooldown_len) e->cooldown = e->cooldown_len; }
     else return fail(KLSTM_ERR_ARG, "klstm_set_option: unknown key '%s'", key);
     return KLSTM_OK;
@@ -1807,7 +1861,7 @@ klstm_status klstm_profile_query(klstm_engine *e, const char *kernel, double *to
     const struct { const char *name; long v; } ctr[] = {
         {"persist_giveups", e->n_giveups}, {"persist_replayed", e->n_replayed}, {"persist_dropped", e->n_dropped},
         {"persist_launches", (long)e->pseq}, {"persist_cooldown", (long)e->cooldown}, {"gemm_copies_launches", e->n_copies},
-        {"persist_tail_wgs", e->tail_wgs}, {"tail_merge_launches", (long)e->tr_seq}, {"fwd_inference_launches", e->n_inf},
+        {"persist_tail_wgs", e->tail_wgs}, {"tail_merge_launches", (long)e->tr_seq}, {"fwd_inference_launches", e->n_inf}, {"gran_value_launches", e->n_gran_value},
         // range-guard events: this engine's own products + the stateless klstm_affine_* calls made on this device (its default guard)
         {"fp16_redo", ev(REDO_FOLD) + ev(REDO_NT) + ev(REDO_OUTER) + ev(REDO_SKINNY)},
         {"fp16_redo_fold", ev(REDO_FOLD)}, {"fp16_redo_nt", ev(REDO_NT)},

@@ -444,8 +444,61 @@ struct PersistOpts {
   // host waits on the done word) the arrival count of its workgroups.  The many-stream launchers ignore it (always 0).
   int epoch_mode = 0;
   unsigned epoch = 0, ordinal = 0;
+  // Value-only granules of the NEXT launch_fwd_persist (klstm_persist_dev.h "value-only transport"), set by the caller per launch from
+  // gran_plan(): the two rings (null: the tagged transport), which of them this launch publishes into and sweeps, how many slots of the
+  // OTHER one (1 .. gv_npoison) it writes POISON into again, and the slots a ring has.  (launch_bwd_persist keeps the tags.)
+  void *gv_rings = nullptr;       // both rings, [2][gv_slots][C][4 streams] dwords
+  int gv_ring = 0, gv_npoison = 0, gv_slots = 0;
   long long *dbg = nullptr;       // tools/persist_anatomy (KLSTM_PERSIST_TIMING builds only)
 };
+
+// ---- value-only granules: the host's bookkeeping of the forward chain's rings (pure: tests/test_gran_plan.py, tests/cpp/gran_plan_test.cpp) ----
+// The chain owns two rings of `slots` slots (one slot = the C 16-byte units of one step).  Value-only launch number n
+// (n counts from 0 and only launches that use this transport) publishes step t into slot t of ring n & 1 -- no slot is written twice inside
+// a launch -- and writes POISON back into slots 1 .. last[1 - (n & 1)] of the OTHER ring, the slots that ring's last user wrote: when launch
+// n + 1 polls that ring every slot it may look at holds POISON again (the kernel boundary makes the stores visible).  A launch of T steps
+// touches slots 1 .. T and needs T + 2 <= slots (one spare slot at either end, as the tagged rings count them).
+//   T + 2 > GRAN_CAP_SLOTS : the launch keeps the tagged transport (use = 0); nothing of this state moves.
+//   T + 2 > slots          : the rings are re-allocated at gran_grow_slots(T) and BOTH are filled with POISON in stream order
+//                            (grow_to > 0): nothing is left to poison, the count starts over.
+// GRAN_CAP_SLOTS = 256: T <= 254 frames per minibatch (truncated BPTT runs at 20); two rings of 256 slots are 6.5 MB per direction at
+// C = 800.  Beyond it a launch is hundreds of microseconds long and the tag dwords are not what it waits for.
+constexpr unsigned GRAN_POISON = 0x7FA5A5A5u;        // a signalling NaN: no IEEE multiply or add returns one
+constexpr int GRAN_CAP_SLOTS = 256;
+struct GranState { unsigned n = 0; int last[2] = {0, 0}; int slots = 0; };    // launches so far, slots each ring's last user wrote, slots per ring
+struct GranPlan { int use, ring, npoison, grow_to; };
+inline int gran_grow_slots(int T, int cap = GRAN_CAP_SLOTS) {
+  int s = 32;
+  while (s < T + 2) s *= 2;
+  return s < cap ? s : cap;
+}
+// What launch `ordinal` of T steps does, given what the other ring's last user wrote (`last_other`), the slots a ring has and the cap.
+inline GranPlan gran_plan(unsigned ordinal, int T, int last_other, int slots, int cap = GRAN_CAP_SLOTS) {
+  GranPlan p{0, 0, 0, 0};
+  if (T < 1 || T + 2 > cap) return p;
+  p.use = 1;
+  if (T + 2 > slots) { p.grow_to = gran_grow_slots(T, cap); return p; }   // (fresh rings: ring 0, nothing to poison)
+  p.ring = (int)(ordinal & 1u);
+  p.npoison = last_other < 0 ? 0 : last_other > slots - 1 ? slots - 1 : last_other;
+  return p;
+}
+// ... and the state behind it: call once per value-only launch that is enqueued (after the rings were regrown where p.grow_to says so).
+inline void gran_advance(GranState &s, const GranPlan &p, int T) {
+  if (!p.use) return;
+  if (p.grow_to) { s.n = 0; s.last[0] = s.last[1] = 0; s.slots = p.grow_to; }
+  const int ring = (int)(s.n & 1u);
+  s.last[ring] = T;                                  // (the other ring is clean once this launch has run)
+  s.last[1 - ring] = 0;
+  s.n++;
+}
+inline void gran_reset(GranState &s) { s.n = 0; s.last[0] = s.last[1] = 0; }   // both rings were just filled with POISON (recover())
+size_t persist_granv_bytes(const Dims &d, int slots);    // both rings
+bool persist_gran_fwd(const Dims &d, const PersistOpts &o);   // the forward launch of this shape has a value-only instance
+// ... as ONE kernel argument word: ring in bit 0, npoison in bits 1..11, slots from bit 12 (slots <= GRAN_CAP_SLOTS)
+constexpr int gran_pack(int ring, int npoison, int slots) { return (ring & 1) | (npoison << 1) | (slots << 12); }
+constexpr int gran_ring(int w) { return w & 1; }
+constexpr int gran_npoison(int w) { return (w >> 1) & 0x7ff; }
+constexpr int gran_slots(int w) { return w >> 12; }
 // tags a launch consumes: what its direction's epoch moves on by (forward and many-stream launches: T + 2; backward: per group of 4 streams)
 inline unsigned persist_fwd_ntags(const Dims &d) { return (unsigned)(d.T + 2); }
 inline unsigned persist_bwd_ntags(const Dims &d) { return (unsigned)(((d.S + 3) / 4) * (d.T + 2)); }

@@ -37,6 +37,8 @@
 #include "klstm_math.h"
 #include "klstm_persist_dev.h"
 
+#include <algorithm>
+
 namespace klstm {
 
 #pragma clang fp contract(off)
@@ -60,11 +62,14 @@ struct PersistFwdArgs {
                                   // that a launch that gives up leaves the state it started from untouched
   unsigned *guard;                // the engine's control words (or null): [2] / [6] set by an earlier launch -> do nothing; [8] = persistent
                                   // launches of this engine that have run so far: this launch's ordinal, [8] + 1, goes into ctrl[3] if it gives up
-  unsigned long long *gran;       // [2][C*4] granules, cell-major (4 stream slots per cell)
+  unsigned long long *gran;       // [2][C*4] granules, cell-major (4 stream slots per cell); the GV instances: the direction's two value-only
+                                  // rings, [2][slots][C][4 streams] dwords (klstm_persist_dev.h)
   unsigned *ctrl;                 // [0] epoch, [1] finished workgroups, [2] status (0 = ok)
   int nap0, nap;                  // sweepers sleep nap0 x 256 clocks before the first pass of a step, nap x 64 between passes
   long long spin_limit;           // wall-clock ticks (100 MHz) a single wait may take before the workgroup gives up
   int test_stall;                 // test hook: workgroup 0 stops publishing at this step (0: never) -> every sweep of that step times out
+  int gvi;                        // GV instances (gran_pack): the ring this launch uses, the slots 1 .. np of the OTHER ring it writes POISON
+                                  // into again, the slots of a ring (in the padding in front of hstat: the other instances' arguments are unchanged)
   unsigned *hstat;                // host-mapped status word (or null): set when a wait expires, read by the engine without a sync
   EpochArgs ea;                   // where epoch and launch ordinal come from, how the launch ends (klstm_persist_dev.h)
 #ifdef KLSTM_PERSIST_TIMING
@@ -100,6 +105,35 @@ __device__ __forceinline__ bool sweep_units(const unsigned long long *slot, int 
       const unsigned u0 = q[k].x, t0_ = q[k].y, u1 = q[k].z, t1 = q[k].w;
       ok &= (((S < 2 * h + 1) | (t0_ == tag)) & ((S < 2 * h + 2) | (t1 == tag))) | (u >= nunits);
       v[k][0] = __uint_as_float(u0); v[k][1] = __uint_as_float(u1);
+    }
+    if (ok) return true;
+    if ((spins & 31) == 31 && wall_clock64() - t0 > limit) return false;
+    for (int i = 0; i < nap; i++) __builtin_amdgcn_s_sleep(1);
+  }
+}
+
+// The same sweep over VALUE-ONLY units (klstm_persist_dev.h): unit u = cell u, the 16 bytes of its streams 0..3; a dword of a live stream is
+// there once it differs from GRAN_POISON.  Half the units and half the bytes of sweep_units; the same contiguous KB per load instruction.
+template <int NUQ>
+__device__ __forceinline__ bool sweep_values(const unsigned *slot, int nunits, int S, int first, int stride, float (&v)[NUQ][4], long long limit,
+                                             int nap0, int nap) {
+  const __amdgpu_buffer_rsrc_t rs = buf_rsrc(slot, nunits * 16);
+  for (int i = 0; i < nap0; i++) __builtin_amdgcn_s_sleep(4);
+  const long long t0 = wall_clock64();
+  for (unsigned spins = 0;; spins++) {
+    u32x4 q[NUQ];
+#pragma unroll
+    for (int k = 0; k < NUQ; k++) {
+      const int u = first + k * stride;
+      q[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, (u < nunits ? u : 0) * 16, 0, 16);   // aux 16 = sc1
+    }
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < NUQ; k++) {
+      const int u = first + k * stride;
+      ok &= (((S < 1) | (q[k].x != GRAN_POISON)) & ((S < 2) | (q[k].y != GRAN_POISON)) & ((S < 3) | (q[k].z != GRAN_POISON)) &
+             ((S < 4) | (q[k].w != GRAN_POISON))) | (u >= nunits);
+      v[k][0] = __uint_as_float(q[k].x); v[k][1] = __uint_as_float(q[k].y); v[k][2] = __uint_as_float(q[k].z); v[k][3] = __uint_as_float(q[k].w);
     }
     if (ok) return true;
     if ((spins & 31) == 31 && wall_clock64() - t0 > limit) return false;
@@ -160,9 +194,12 @@ constexpr int persist_maxu(int maxc) { return maxc == 7 ? 5 : maxc; }
 // INF (klstm_propagate_inference): forward only -- every store of an activation plane the BPTT would read (gifo, c, h, m, r and time
 // block 0 of the c / r planes) is left out; the output rows, the granule exchange and next_c / next_r stay, and so does every READ
 // (XB: the batched x term in the gifo plane).  Same arithmetic in the same order: out and the carried state are bit-identical.
-template <int TPW, int MAXC, int PNW, int PCELL, int NG, bool XB = false, bool IL = false, bool INF = false>
+// GV (one group, lock-step): value-only granules (klstm_persist_dev.h) -- m(t) goes to slot t of this launch's ring, the sweep of step t reads
+// slot t - 1, and the projection wave -- it publishes nothing -- hands the OTHER ring's used slots back as POISON, a few per step.
+template <int TPW, int MAXC, int PNW, int PCELL, int NG, bool XB = false, bool IL = false, bool INF = false, bool GV = false>
 __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
   static_assert(!IL || (NG >= 2 && NG <= 4), "interleaved chains: two to four stream groups");
+  static_assert(!GV || (NG == 1 && !IL), "value-only granules: one group of streams");
   constexpr int PNT = PNW * 64, NCW = 4 * TPW, NSW = (PNW - NCW - 1) * 64, MAXU = persist_maxu(MAXC);   // cell waves, one projection wave, sweepers
   constexpr int SS = 4 * NG;                         // stream slots per cell (slab rows, granules)
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -177,6 +214,10 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
   int *projf = reinterpret_cast<int *>(abortf + 1);  // last step whose slab the projection wave has read
   int *pubcnt = reinterpret_cast<int *>(abortf + 2); // publishes issued by this workgroup's cell waves so far (one count per wave and step)
   const bool proj_on = a.rin && (int)blockIdx.x * 4 < R;   // this workgroup contracts rows 4*blockIdx .. +3 of W_r_m
+  constexpr bool gv = GV;
+  const int gv_slots = gv ? gran_slots(a.gvi) : 0, gv_np = gv ? gran_npoison(a.gvi) : 0;
+  unsigned *gv_ring = reinterpret_cast<unsigned *>(a.gran) + (size_t)(gv ? gran_ring(a.gvi) : 0) * gv_slots * a.C * 4;
+  unsigned *gv_other = reinterpret_cast<unsigned *>(a.gran) + (size_t)(gv ? 1 - gran_ring(a.gvi) : 0) * gv_slots * a.C * 4;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned epoch = launch_epoch(a.ea, a.ctrl);
@@ -243,7 +284,9 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
       ao += wpo * c;                               // :303
       const float go = k_sigmoid(ao);              // :306
       const float m = h * go;                      // :309
-      if ((t < T || a.rin) && !(a.test_stall == t && blockIdx.x == 0))                                           // (m(T): for r(T) only)
+      if (gv) {
+        if ((t < T || a.rin) && !(a.test_stall == t && blockIdx.x == 0)) publish_value(gv_ring + (size_t)t * C * 4, e_cell * 4 + es_g, m);
+      } else if ((t < T || a.rin) && !(a.test_stall == t && blockIdx.x == 0))                                    // (m(T): for r(T) only)
         publish(a.gran + (size_t)(t & 1) * C * SS, IL ? (g * C + e_cell) * 4 + es : e_cell * SS + es_g, epoch + (unsigned)t, m);
       if constexpr (!INF) {
         const int vg = (es_g * 4 * C + e_cell) * 4, vc = (es_g * C + e_cell) * 4, sg = t * S * 4 * C * 4, sc = t * S * C * 4;
@@ -410,10 +453,17 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
           }
         }
       }
-    } else
+    } else {
+    const __amdgpu_buffer_rsrc_t rs_p = buf_rsrc(gv_other, gv_slots * C * 16);
+    const int p_per = gv ? (gv_np + T - 2 + (a.rin ? 1 : 0)) / (T - 1 + (a.rin ? 1 : 0)) : 0;   // slots of the other ring to poison per step
     for (int t = 2; !skip && t <= T + (a.rin ? 1 : 0); t++) {
       lds_barrier();
       if (*abortf) break;
+      if constexpr (gv)
+      for (int i = 0; i < p_per; i++) {              // (this workgroup's own cells; a slot past gv_np was never written)
+        const int ps = 1 + (t - 2) * p_per + i;
+        if (ps <= gv_np) poison_units(rs_p, C, ps, (int)blockIdx.x * 4 * TPW, 4 * TPW, lane);
+      }
       if (!proj_on) continue;
       // (columns >= C of the slab row hold x(t) and pad: their weights are zero)
 #pragma unroll
@@ -429,6 +479,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
           if (f == T) *reinterpret_cast<float4 *>(a.next_r + (size_t)ps * R + g4) = make_float4(v.x, v.y, v.z, v.w);
         }
       }
+    }
     }
   } else {
     // =========================== sweeper: the B operand of every step into the slab ===========================
@@ -522,8 +573,12 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
             if ((spins & 1023) == 1023 && wall_clock64() - w0 > a.spin_limit) break;   // (bounded like every other spin: the sweep below then times out and reports)
           }
         }
-        if (!sweep_units<2 * NG * PCELL>(a.gran + (size_t)((t - 1) & 1) * C * SS, 2 * NG * C, S, 2 * NG, epoch + (unsigned)(t - 1), sidx, NSW, mv,
-                                         a.spin_limit, a.nap0, a.nap)) {
+        float mq[NG == 1 ? PCELL : 1][4];             // ... or value-only units (cell) first + k NSW
+        bool swept;
+        if (NG == 1 && gv) swept = sweep_values<(NG == 1 ? PCELL : 1)>(gv_ring + (size_t)(t - 1) * C * 4, C, S, sidx, NSW, mq, a.spin_limit, a.nap0, a.nap);
+        else swept = sweep_units<2 * NG * PCELL>(a.gran + (size_t)((t - 1) & 1) * C * SS, 2 * NG * C, S, 2 * NG, epoch + (unsigned)(t - 1), sidx, NSW, mv,
+                                                 a.spin_limit, a.nap0, a.nap);
+        if (!swept) {
           *abortf = 1u;
           if (lane == 0) {
             atomicCAS(&a.ctrl[3], 0u, launch_ordinal(a.ea, a.guard));      // (which launch: the first one wins, everything behind it does nothing)
@@ -535,6 +590,17 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
         //  i.e. has finished reading the previous slab; the projection wave says so itself)
         if (proj_on && t > 2)
           while (__hip_atomic_load(projf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < t - 1) __builtin_amdgcn_s_sleep(1);
+        if (NG == 1 && gv) {
+#pragma unroll
+          for (int k = 0; k < (NG == 1 ? PCELL : 1); k++) {
+            const int cl = sidx + k * NSW;
+            if (cl < C) {
+#pragma unroll
+              for (int s_ = 0; s_ < 4; s_++)
+                if (s_ < S) ldsB[s_ * LDB + cl] = mq[k][s_];
+            }
+          }
+        } else {
 #pragma unroll
         for (int k = 0; k < 2 * NG * PCELL; k++) {
           const int u = sidx + k * NSW, cl = u / (2 * NG), s2 = 2 * (u % (2 * NG));
@@ -542,6 +608,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
             if (s2 < S) ldsB[s2 * LDB + cl] = mv[k][0];
             if (s2 + 1 < S) ldsB[(s2 + 1) * LDB + cl] = mv[k][1];
           }
+        }
         }
         if (x_on) *reinterpret_cast<float4 *>(ldsB + xs * LDB + XP + xk) = xv;
       }
@@ -603,10 +670,29 @@ int persist_fwd_grid(const Dims &d, const PersistOpts &o) {
 }
 // forward: [2 parities][C][8 stream slots]; backward: [2 stream groups][BWD_RING = 32 ring slots][C][4 stream slots] (klstm_persist_bwd.hip)
 size_t persist_gran_bytes(const Dims &d) { return (size_t)64 * d.C * 8 * sizeof(unsigned long long); }   // (backward: up to 4 groups x 32 ring slots)
+// value-only granules: [2 rings][slots][C][4 streams] dwords per direction
+size_t persist_granv_bytes(const Dims &d, int slots) { return (size_t)2 * slots * d.C * 16; }
 
 // geometry x stream-group count; two groups (5..8 streams) only in the 12-wave geometries
+// PGV: the geometries with a value-only (GV) instance -- one group of streams at 12 waves, one tile per workgroup and <= 7 operand chunks, the
+// default geometry up to C + I <= 896.  There the GV form allocates no worse than its tagged twin (-Rpass-analysis=kernel-resource-usage:
+// no scratch in either but for the batched-x form, 20 -> 0..8 bytes; profiles/persist_gran_ab.txt); the 8- / 16-wave, two-tile and 9- / 12-chunk
+// geometries spill 250-1000 bytes per lane already and most of their GV forms spill a few bytes more: they keep the tags.
+#define PGV(TP, MC, W, NG_) ((TP) == 1 && (MC) == 7 && (W) == 12 && (NG_) == 1)
+bool persist_gran_fwd(const Dims &d, const PersistOpts &o) {
+  if (d.S > 4) return false;
+  const int Ik = persist_x_batched(d) ? 0 : d.I;
+  const PGeo g = pick_geo_fwd(o, d.C, pcdiv(d.C, KCH) + pcdiv(Ik, KCH), pcdiv(d.R, KCH) * KCH + Ik);
+  return PGV(g.tpw, g.maxc, g.waves, 1);
+}
 #define PF5(KERN, TP, MC, W, NG_)                                                                               \
   if (g.waves == W && g.tpw == TP && g.maxc == MC && ng == NG_) {                                               \
+    if (gvl && PGV(TP, MC, W, NG_)) {                                                                           \
+      if (g.pcell == 1) return launch(KERN<TP, MC, W, 1, NG_, false, false, false, PGV(TP, MC, W, NG_)>, grid, W * 64, shm, st, pr, a); \
+      if (g.pcell == 2) return launch(KERN<TP, MC, W, 2, NG_, false, false, false, PGV(TP, MC, W, NG_)>, grid, W * 64, shm, st, pr, a); \
+      if (g.pcell == 3) return launch(KERN<TP, MC, W, 3, NG_, false, false, false, PGV(TP, MC, W, NG_)>, grid, W * 64, shm, st, pr, a); \
+      return launch(KERN<TP, MC, W, 4, NG_, false, false, false, PGV(TP, MC, W, NG_)>, grid, W * 64, shm, st, pr, a); \
+    }                                                                                                           \
     if (g.pcell == 1) return launch(KERN<TP, MC, W, 1, NG_>, grid, W * 64, shm, st, pr, a);                     \
     if (g.pcell == 2) return launch(KERN<TP, MC, W, 2, NG_>, grid, W * 64, shm, st, pr, a);                     \
     if (g.pcell == 3) return launch(KERN<TP, MC, W, 3, NG_>, grid, W * 64, shm, st, pr, a);                     \
@@ -614,6 +700,12 @@ size_t persist_gran_bytes(const Dims &d) { return (size_t)64 * d.C * 8 * sizeof(
   }
 #define PFX(KERN, TP, MC, NG_)                                                                                  \
   if (xbat && g.waves == 12 && g.tpw == TP && g.maxc == MC && ng == NG_) {                                      \
+    if (gvl && PGV(TP, MC, 12, NG_)) {                                                                          \
+      if (g.pcell == 1) return launch(KERN<TP, MC, 12, 1, NG_, true, false, false, PGV(TP, MC, 12, NG_)>, grid, 768, shm, st, pr, a); \
+      if (g.pcell == 2) return launch(KERN<TP, MC, 12, 2, NG_, true, false, false, PGV(TP, MC, 12, NG_)>, grid, 768, shm, st, pr, a); \
+      if (g.pcell == 3) return launch(KERN<TP, MC, 12, 3, NG_, true, false, false, PGV(TP, MC, 12, NG_)>, grid, 768, shm, st, pr, a); \
+      return launch(KERN<TP, MC, 12, 4, NG_, true, false, false, PGV(TP, MC, 12, NG_)>, grid, 768, shm, st, pr, a); \
+    }                                                                                                           \
     if (g.pcell == 1) return launch(KERN<TP, MC, 12, 1, NG_, true>, grid, 768, shm, st, pr, a);                 \
     if (g.pcell == 2) return launch(KERN<TP, MC, 12, 2, NG_, true>, grid, 768, shm, st, pr, a);                 \
     if (g.pcell == 3) return launch(KERN<TP, MC, 12, 3, NG_, true>, grid, 768, shm, st, pr, a);                 \
@@ -662,7 +754,10 @@ size_t persist_gran_bytes(const Dims &d) { return (size_t)64 * d.C * 8 * sizeof(
 // form spills none and measured 59.1 against 53.3 us per chunk; the other PCELL / MAXC forms (not measured).  Everything else runs the
 // ordinary instance: the same out and state, with the planes.
 #define PFINF(XB_, IL_, NG_)                                                                                    \
-  if (xbat == XB_ && il == IL_ && ng == NG_) return launch(k_fwd_persist<1, 7, 12, 2, NG_, XB_, IL_, true>, grid, 768, shm, st, pr, a);
+  if (xbat == XB_ && il == IL_ && ng == NG_) {                                                                  \
+    if (gvl && NG_ == 1 && !IL_) return launch(k_fwd_persist<1, 7, 12, 2, NG_, XB_, IL_, true, (NG_ == 1 && !IL_)>, grid, 768, shm, st, pr, a); \
+    return launch(k_fwd_persist<1, 7, 12, 2, NG_, XB_, IL_, true>, grid, 768, shm, st, pr, a);                  \
+  }
 bool persist_fwd_has_inference(const Dims &d, const PersistOpts &o) {
   const bool xbat = persist_x_batched(d), il = d.S > 4 && o.fwd_interleave != 0;
   const int ng = (d.S + 3) / 4, Ik = xbat ? 0 : d.I;
@@ -698,6 +793,10 @@ hipError_t launch_fwd_persist(const Dims &d, const FwdPtrs &p, const float *in, 
   a.test_stall = o.test_stall_fwd;
   a.hstat = o.hstat;
   a.ea = EpochArgs{o.epoch_mode, o.epoch, o.ordinal};
+  // value-only granules: the one-group, lock-step instances (the caller asks persist_gran_supported first)
+  const bool gvl = o.gv_rings && persist_gran_fwd(d, o) && d.T + 2 <= o.gv_slots && o.gv_slots <= GRAN_CAP_SLOTS;
+  a.gvi = gvl ? gran_pack(o.gv_ring, std::min(o.gv_npoison, o.gv_slots - 1), o.gv_slots) : 0;
+  if (gvl) a.gran = static_cast<unsigned long long *>(o.gv_rings);
 #ifdef KLSTM_PERSIST_TIMING
   a.dbg = o.dbg;
 #endif

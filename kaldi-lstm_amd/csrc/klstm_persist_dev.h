@@ -4,6 +4,7 @@
 // workgroups' partial rows (k_tail_reduce, and the first workgroups of k_grads).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "klstm_kernels.h"
 #include "klstm_math.h"
 
 namespace klstm {
@@ -35,6 +36,25 @@ __device__ __forceinline__ void buf_store_f32(__amdgpu_buffer_rsrc_t rs, int vof
 __device__ __forceinline__ void publish(unsigned long long *slot, int idx, unsigned tag, float v) {
   __hip_atomic_store(slot + idx, ((unsigned long long)tag << 32) | __float_as_uint(v), __ATOMIC_RELAXED,
                      __HIP_MEMORY_SCOPE_AGENT);                     // one 8-byte sc1 store: tag and value cannot tear
+}
+
+// ---- value-only transport (engine option "persist_gran", the fp32 forward chain at 1..4 streams) ----
+// A unit is the 16 bytes of one cell: the values of streams 0..3, no tag.  A dword is FRESH when it differs from GRAN_POISON, the signalling
+// NaN every slot holds before its step is published: a launch publishes step t into slot t of its ring and nowhere else (no slot is written
+// twice inside a launch), and the ring was filled with POISON before the launch began (by the launch in front of it, or by a stream-ordered
+// fill: klstm_kernels.h gran_plan).  Every dword is checked on its own: nothing is assumed about 16-byte stores arriving whole.  Half the
+// bytes and half the units per sweep of the tagged form; no parity slots, no ring reuse, no "newer frame" case.
+//   publish_value : one 4-byte sc1 store by the lane that owns (cell, stream).  A value whose bits EQUAL the poison pattern (no multiply or
+//                   add returns a signalling NaN; the check assumes nothing) leaves as the canonical quiet NaN.
+//   poison_units  : `nunits` consecutive units of slot `slot` back to POISON, 16 bytes per lane, sc1; issued by a wave that does not publish.
+__device__ __forceinline__ void publish_value(unsigned *slot, int idx, float v) {
+  unsigned u = __float_as_uint(v);
+  u = u == GRAN_POISON ? 0x7FC00000u : u;
+  __hip_atomic_store(slot + idx, u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void poison_units(__amdgpu_buffer_rsrc_t rs, int C, int slot, int unit0, int nunits, int lane) {
+  if (lane < nunits && unit0 + lane < C)
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{GRAN_POISON, GRAN_POISON, GRAN_POISON, GRAN_POISON}, rs, (slot * C + unit0 + lane) * 16, 0, 16);   // aux 16 = sc1
 }
 
 // Sum over the 16 k-groups of the 4-row geometry (lanes with equal lane & 3): two DPP row shifts inside each row of 16 lanes

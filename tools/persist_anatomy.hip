@@ -1,6 +1,7 @@
 // tools/persist_anatomy.hip -- where does a step of the persistent chains (forward, backward) spend its time?  Builds the product
 // kernel (klstm_persist.hip) with KLSTM_PERSIST_TIMING: every wave sums shader-clock intervals per phase
 // (sweep, barrier 1, contraction, barrier 2, owner epilogue, loop head) over the T-1 steps.  Random weights (timing only).
+// persist_anatomy [streams] [gran]: gran = 1 runs the forward launch on value-only granules (engine option "persist_gran").
 #define KLSTM_PERSIST_TIMING
 #include "../kaldi-lstm_amd/csrc/klstm_persist.hip"
 #include "../kaldi-lstm_amd/csrc/klstm_persist_bwd.hip"
@@ -27,6 +28,13 @@ int main(int argc, char **argv) {
   float *wmr = dalloc((size_t)R * C), *outr = dalloc((size_t)T * S * R), *nr = dalloc(S * R);
   unsigned long long *gran; CK(hipMalloc(&gran, 32 * C * 8 * 8)); CK(hipMemset(gran, 0, 32 * C * 8 * 8));
   unsigned *ctrl; CK(hipMalloc(&ctrl, 32)); CK(hipMemset(ctrl, 0, 32));
+  // value-only granules: two rings, launch number n uses ring n & 1 and hands the other one back poisoned (as the engine does)
+  const bool gran_on = argc > 2 && atoi(argv[2]) != 0 && S <= 4;
+  const int gv_slots = gran_grow_slots(T);
+  unsigned *granv; CK(hipMalloc(&granv, persist_granv_bytes(Dims{I, C, R, S, T}, gv_slots)));
+  auto gv_fill = [&]() { CK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(granv), (int)GRAN_POISON, persist_granv_bytes(Dims{I, C, R, S, T}, gv_slots) / 4)); };
+  gv_fill();
+  unsigned gv_n = 0;
   long long *dbg; CK(hipMalloc(&dbg, 256 * 16 * 10 * 8)); CK(hipMemset(dbg, 0, 256 * 16 * 10 * 8));
   for (int waves : {12}) for (int tpw : {1}) for (int nap0 : {0, 1, 2, 3, 4, 5, 6, 8}) for (int nap : {0}) {
     if (4 * tpw >= waves) continue;
@@ -43,7 +51,11 @@ int main(int argc, char **argv) {
     const bool xbat = false;
     const bool il = S > 4;                           // (5..8 streams: the two groups as interleaved chains, like the engine)
     a.xg = nullptr; a.hstat = nullptr;
-    auto go = [&]() -> hipError_t { PDISPATCH_FWD(k_fwd_persist); };
+    const bool gvl = gran_on && persist_gran_fwd(Dims{I, C, R, S, T}, o);
+    auto go = [&]() -> hipError_t {
+      if (gvl) { a.gran = reinterpret_cast<unsigned long long *>(granv); a.gvi = gran_pack((int)(gv_n & 1u), gv_n ? T : 0, gv_slots); gv_n++; }
+      PDISPATCH_FWD(k_fwd_persist);
+    };
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     float best = 1e9;
     for (int rep = 0; rep < 4; rep++) {
@@ -57,7 +69,7 @@ int main(int argc, char **argv) {
     auto row = [&](int wg, int w) { return &d[((size_t)wg * 16 + w) * 10]; };
     long long tot = 0; for (int i = 0; i < 6; i++) tot += row(0, 0)[i];
     const double cyc_per_us = tot / (best * 1e3);
-    printf("S=%d waves=%d tpw=%d grid=%d maxc=%d pcell=%d nap0=%d nap=%d: %.3f us/step (status %x), ~%.0f MHz shader clock\n", S, g.waves, g.tpw, grid, g.maxc, g.pcell, nap0, nap, us_step, stw[2], cyc_per_us);
+    printf("%sS=%d waves=%d tpw=%d grid=%d maxc=%d pcell=%d nap0=%d nap=%d: %.3f us/step (status %x), ~%.0f MHz shader clock\n", gvl ? "VALUE-ONLY " : "", S, g.waves, g.tpw, grid, g.maxc, g.pcell, nap0, nap, us_step, stw[2], cyc_per_us);
     const char *nm[6] = {"sweep+slab", "barrier1", "contract", "barrier2", "epilogue", "loophead"};
     for (int w : {0}) {
       printf("   wg0 wave %2d (%s):", w, w < 4 * g.tpw ? "cell   " : "sweeper");
