@@ -18,6 +18,7 @@
 
 #include "../../include/klstm.h"
 #include "klstm_ctc_dev.h"
+#include "klstm_ctc_host.h"
 #include "klstm_kernels.h"
 
 namespace klstm {
@@ -37,15 +38,7 @@ __global__ __launch_bounds__(64 * NW) void k_ctc_chain(const float *__restrict__
     if (tid == 0) ws.info[s] = st;
     if (st != 1) return;
     int *next = ws.link + (size_t)s * 2 * ws.Lcap, *first = next + ws.Lcap;
-    for (int j = tid; j < L; j += NT) first[j] = 1;
-    __syncthreads();
-    for (int j = tid; j < L; j += NT) {
-      const int c = lab[j];
-      int q = j + 1;
-      while (q < L && lab[q] != c) q++;
-      next[j] = q < L ? q : -1;
-      if (q < L) first[q] = 0;                 // position q has exactly one predecessor: one writer
-    }
+    ctc_links(lab, L, next, first, NT);
     return;
   }
   if (st != 1) {
@@ -77,25 +70,13 @@ __global__ __launch_bounds__(256) void k_ctc_combine(const float *__restrict__ y
   float *dp = diff + (size_t)r * dstride;
   const float *yp = y + (size_t)r * stride;
   if (ws.info[s] != 1 || t >= lens[s]) {
-    if (vec) for (int c = tid * 4; c < K; c += 1024) *reinterpret_cast<float4 *>(dp + c) = make_float4(0.f, 0.f, 0.f, 0.f);
-    else for (int c = tid; c < K; c += 256) dp[c] = 0.f;
+    ctc_zero_row(dp, K, vec);
     return;
   }
   const int L = loff[s + 1] - loff[s], N = 2 * L + 1;
   const int *lab = labels + loff[s];
   const float *a = ws.A + ((size_t)s * T + t) * ws.Npad, *bt = ws.B + ((size_t)s * T + t) * ws.Npad;
-  float mx = CTC_NEG;
-  for (int i = tid; i < N; i += 256) { const float v = a[i] + bt[i]; g[i] = v; mx = fmaxf(mx, v); }
-  mx = ctc_block_reduce(mx, sm, true);
-  float sall = 0.f, seven = 0.f;
-  for (int i = tid; i < N; i += 256) {         // 256 is even: a thread's states are all even or all odd
-    const float e = expf(g[i] - mx);
-    g[i] = e;
-    sall += e;
-    seven += (i & 1) ? 0.f : e;
-  }
-  sall = ctc_block_reduce(sall, sm, false);
-  seven = ctc_block_reduce(seven, sm, false);
+  KLSTM_CTC_GAMMA_ROW(float, ctc_block_sum, sm, a, bt, N, g, sall, seven)
   const float inv = 1.f / sall;
   if (vec) for (int c = tid * 4; c < K; c += 1024) *reinterpret_cast<float4 *>(dp + c) = *reinterpret_cast<const float4 *>(yp + c);
   else for (int c = tid; c < K; c += 256) dp[c] = yp[c];
@@ -111,55 +92,36 @@ __global__ __launch_bounds__(256) void k_ctc_combine(const float *__restrict__ y
   }
 }
 
-size_t ctc_workspace_bytes(int T, int S, int Lcap) {
-  const size_t npad = ((size_t)2 * Lcap + 1 + 3) / 4 * 4;
-  const size_t head = ((size_t)S * (1 + 2 * (size_t)Lcap) * sizeof(int) + 255) / 256 * 256;
+static size_t ctc_layout(int T, int S, int Lcap, void *base, CtcWs *ws) {
+  const size_t npad = ctc_npad(Lcap), head = ctc_up256((size_t)S * (1 + 2 * (size_t)Lcap) * sizeof(int));
+  if (ws) {
+    ws->info = reinterpret_cast<int *>(base);
+    ws->link = ws->info + S;
+    ws->A = reinterpret_cast<float *>(reinterpret_cast<char *>(base) + head);
+    ws->B = ws->A + (size_t)T * S * npad;
+    ws->Npad = (int)npad;
+    ws->Lcap = Lcap;
+  }
   return head + 2 * (size_t)T * S * npad * sizeof(float);
 }
 
-int ctc_label_capacity(int T, int S, size_t bytes) {        // the longest label sequence a workspace of `bytes` serves; -1: none
-  if (bytes < ctc_workspace_bytes(T, S, 0)) return -1;
-  int lo = 0, hi = 1023;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (ctc_workspace_bytes(T, S, mid) <= bytes) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
+size_t ctc_workspace_bytes(int T, int S, int Lcap) { return ctc_layout(T, S, Lcap, nullptr, nullptr); }
 
-static bool ctc_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int ctc_label_capacity(int T, int S, size_t bytes) {
+  return ctc_label_capacity_of(bytes, [&](int Lcap) { return ctc_workspace_bytes(T, S, Lcap); });
+}
 
 hipError_t launch_ctc(const float *y, int T, int S, int K, int stride, const int *lens, const int *labels, const int *loff, int blank,
                       float *diff, int dstride, float *utt_loss, double *totals, void *workspace, int Lcap, hipStream_t st) {
   CtcWs ws;
-  ws.Lcap = Lcap;
-  ws.Npad = (2 * Lcap + 1 + 3) / 4 * 4;
-  const size_t head = ((size_t)S * (1 + 2 * (size_t)Lcap) * sizeof(int) + 255) / 256 * 256;
-  ws.info = reinterpret_cast<int *>(workspace);
-  ws.link = ws.info + S;
-  ws.A = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + head);
-  ws.B = ws.A + (size_t)T * S * ws.Npad;
-  const int N = 2 * Lcap + 1;
-  // measured: four waves with one state per thread beat one wave with two (391 against 487 us at T = 1000, 101 states)
-  // -- the step is bound by its exp / log issue slots, which more waves on more SIMDs share, and the workgroup barrier costs less than
-  // a second state per lane; sixteen waves lose to four with two states each (670 against 633 us at 301 states), so they serve only
-  // what four cannot hold.  16 * waves + states per thread:
-  const int plan = N <= 64 ? 16 * 1 + 1 : N <= 256 ? 16 * 4 + 1 : N <= 512 ? 16 * 4 + 2 : N <= 1024 ? 16 * 16 + 1 : 16 * 16 + 2;
-  const dim3 grid(S, 3);
-  hipError_t err;
-#define CTC_CASE(NW, P)                                                                                                              \
-  case 16 * NW + P:                                                                                                                  \
-    err = launch(k_ctc_chain<NW, P>, grid, dim3(64 * NW), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, labels, loff, blank, utt_loss, ws); \
-    break;
-  switch (plan) {
-    CTC_CASE(1, 1) CTC_CASE(4, 1) CTC_CASE(4, 2) CTC_CASE(16, 1) CTC_CASE(16, 2)
-    default: return hipErrorInvalidValue;
-  }
-#undef CTC_CASE
+  ctc_layout(T, S, Lcap, workspace, &ws);
+  const hipError_t err = ctc_chain_dispatch(ctc_chain_plan(2 * Lcap + 1), hipErrorInvalidValue, [&](auto nw, auto p) {
+    return launch(k_ctc_chain<nw(), p()>, dim3(S, 3), dim3(64 * nw()), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, labels, loff, blank,
+                  utt_loss, ws);
+  });
   if (err != hipSuccess) return err;
-  const int vec = K % 4 == 0 && stride % 4 == 0 && dstride % 4 == 0 && ctc_al16(y) && ctc_al16(diff);
   return launch(k_ctc_combine, dim3(T * S), dim3(256), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, labels, loff, blank, diff, dstride,
-                (const float *)utt_loss, totals, ws, vec);
+                (const float *)utt_loss, totals, ws, ctc_rows_vec(K, stride, dstride, y, diff));
 }
 
 }  // namespace klstm

@@ -21,6 +21,7 @@
 
 #include "../../include/klstm.h"
 #include "klstm_ctc_dev.h"
+#include "klstm_ctc_host.h"
 #include "klstm_kernels.h"
 
 namespace klstm {
@@ -274,17 +275,11 @@ constexpr size_t AL_HEAD = 512;                // stat [32][4]
 static int align_words(int Lcap) { return 2 * ((2 * Lcap + 1 + 31) / 32); }
 
 size_t ctc_align_workspace_bytes(int T, int S, int Lcap) {
-  return AL_HEAD + ((size_t)T * S * align_words(Lcap) * sizeof(unsigned) + 255) / 256 * 256;
+  return AL_HEAD + ctc_up256((size_t)T * S * align_words(Lcap) * sizeof(unsigned));
 }
 
-int ctc_align_label_capacity(int T, int S, size_t bytes) {      // the longest label sequence a workspace of `bytes` serves; -1: none
-  if (bytes < ctc_align_workspace_bytes(T, S, 0)) return -1;
-  int lo = 0, hi = 1023;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (ctc_align_workspace_bytes(T, S, mid) <= bytes) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+int ctc_align_label_capacity(int T, int S, size_t bytes) {
+  return ctc_label_capacity_of(bytes, [&](int Lcap) { return ctc_align_workspace_bytes(T, S, Lcap); });
 }
 
 hipError_t launch_ctc_align(const float *y, int T, int S, int K, int stride, const int *lens, const int *labels, const int *loff, int blank,

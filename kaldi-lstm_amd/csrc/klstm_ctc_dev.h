@@ -1,7 +1,8 @@
 // kaldi-lstm_amd/csrc/klstm_ctc_dev.h -- device code shared by the CTC kernels (klstm_ctc.hip: the loss; klstm_ctc_align.hip: the forced
-// alignment; klstm_ctc_decode.hip: best path; klstm_ctc_beam.hip: prefix beam search; klstm_ctc_mbr.hip: the n-best risk): the status of
-// an utterance, the maximum over a wave, the fixed-tree reduction over a workgroup, (value, index) reductions, the row reader, the
-// one-wave Levenshtein distance and the alpha / beta chain of the loss (ctc_chain_run).
+// alignment; klstm_ctc_decode.hip: best path; klstm_ctc_beam.hip: prefix beam search; klstm_ctc_mbr.hip: the n-best risk;
+// klstm_ctc_mmi.hip: MMI): the status of an utterance, the maximum over a wave, the fixed-tree reduction over a workgroup, the links,
+// the zero row and the gamma row of the three lattice losses, (value, index) reductions, the row reader, the one-wave Levenshtein
+// distance and the alpha / beta chain of the loss (ctc_chain_run).  The host's side of the lattice losses: klstm_ctc_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,6 +61,53 @@ __device__ __forceinline__ float ctc_block_reduce(float v, float *sm, bool is_ma
   __syncthreads();
   return is_max ? fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])) : (sm[0] + sm[1]) + (sm[2] + sm[3]);
 }
+__device__ __forceinline__ float ctc_block_sum(float v, float *sm) { return ctc_block_reduce(v, sm, false); }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The pieces around ctc_chain_run that the loss (klstm_ctc.hip), the n-best risk (klstm_ctc_mbr.hip) and MMI (klstm_ctc_mmi.hip) share
+// ("One copy"): the links of a labelling, the zero row of diff and the gamma row of a frame.
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The links of lab[0 .. L) by a workgroup of nt threads: next[j] = the next position that carries the class of position j (-1: none),
+// first[j] = 1 where no earlier position carries it.  The thread of a first position then sums its class along next, in order.
+__device__ __forceinline__ void ctc_links(const int *__restrict__ lab, int L, int *next, int *first, int nt) {
+  const int tid = threadIdx.x;
+  for (int j = tid; j < L; j += nt) first[j] = 1;
+  __syncthreads();
+  for (int j = tid; j < L; j += nt) {
+    const int c = lab[j];
+    int q = j + 1;
+    while (q < L && lab[q] != c) q++;
+    next[j] = q < L ? q : -1;
+    if (q < L) first[q] = 0;                   // position q has exactly one predecessor: one writer
+  }
+}
+
+// A row of K zeros by a workgroup of 256 threads; vec: 16 bytes at a time (ctc_rows_vec of klstm_ctc_host.h)
+__device__ __forceinline__ void ctc_zero_row(float *dp, int K, int vec) {
+  const int tid = threadIdx.x;
+  if (vec) for (int c = tid * 4; c < K; c += 1024) *reinterpret_cast<float4 *>(dp + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+  else for (int c = tid; c < K; c += 256) dp[c] = 0.f;
+}
+
+// The gamma row of one frame by a workgroup of 256 threads: g[i] = exp(a[i] + bt[i] - their maximum) for the N states, `sall` their
+// sum and `seven` the sum over the even (blank) states, both declared here as ACC and summed by SUM(value, SMS) (float:
+// ctc_block_sum and the 4 floats of LDS; MMI: double).  Expects `tid` and `float sm[4]` (LDS) in scope.  TEXT, not a function: as a
+// function the same instructions come out in another order (profiles/ctc_shared_pieces_isa.txt).
+#define KLSTM_CTC_GAMMA_ROW(ACC, SUM, SMS, a, bt, N, g, sall, seven)                                                                 \
+  ACC sall = 0, seven = 0;                                                                                                           \
+  {                                                                                                                                  \
+    float mx_ = CTC_NEG;                                                                                                             \
+    for (int i = tid; i < (N); i += 256) { const float v = (a)[i] + (bt)[i]; (g)[i] = v; mx_ = fmaxf(mx_, v); }                      \
+    mx_ = ctc_block_reduce(mx_, sm, true);                                                                                           \
+    for (int i = tid; i < (N); i += 256) {     /* 256 is even: a thread's states are all even or all odd */                          \
+      const float ex_ = expf((g)[i] - mx_);                                                                                          \
+      (g)[i] = ex_;                                                                                                                  \
+      sall += (ACC)ex_;                                                                                                              \
+      seven += (i & 1) ? (ACC)0 : (ACC)ex_;                                                                                          \
+    }                                                                                                                                \
+    sall = SUM(sall, SMS);                                                                                                           \
+    seven = SUM(seven, SMS);                                                                                                         \
+  }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // (value, index) pairs.  a beats b iff a.v > b.v, or a.v == b.v and a.i < b.i: a total order on (non-NaN value, distinct index), so

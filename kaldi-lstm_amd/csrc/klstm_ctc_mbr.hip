@@ -4,11 +4,12 @@
 //   diff = kappa sum_q c_q gamma_q + lambda (y - gamma_ref)          (with respect to the softmax input, as klstm_ctc_eval)
 // Three launches, E = list slots (+ 1 for the reference when lambda > 0) entries per stream:
 //   k_mbr_chain    grid (S E, 3).  y = 0 / 1: the alpha / beta chain of ONE entry (ctc_chain_run of klstm_ctc_dev.h, the step of
-//                  klstm_ctc_eval: the log probabilities carry its bits), y = 2: the entry's status and its next / first links.  All
+//                  klstm_ctc_eval: the log probabilities carry its bits), y = 2: the entry's status and its next / first links
+//                  (ctc_links).  The plan is the loss's (ctc_chain_plan of klstm_ctc_host.h, from the same capacity).  All
 //                  S E chains run side by side.
 //   k_mbr_weights  grid (S).  The stream's status; P, R, c in double by one thread, q ascending; the slot of every class that occurs
 //                  in the stream's list (an accumulator index for the third launch).
-//   k_mbr_combine  grid (T S).  One row each: per entry in order gamma from alpha + beta as k_ctc_combine takes it, c_q gamma_q added
+//   k_mbr_combine  grid (T S).  One row each: per entry in order gamma from alpha + beta by the text k_ctc_combine expands, c_q gamma_q added
 //                  into an LDS accumulator (one slot per class of the list, the blank's in a register), then the row written ONCE:
 //                  lambda y (or zero) coalesced, the slots scattered on top.  Row 0 adds the statistics onto the totals.
 // DETERMINISM.  No floating-point atomics.  Within a labelling a class is summed by the thread of its first position, so no two threads
@@ -19,6 +20,7 @@
 
 #include "../../include/klstm.h"
 #include "klstm_ctc_dev.h"
+#include "klstm_ctc_host.h"
 #include "klstm_kernels.h"
 
 namespace klstm {
@@ -31,20 +33,18 @@ struct MbrIn { const int *lens, *hyp, *hyp_len, *count, *errors, *ref, *roff; in
 // position of the same class, first-of-its-class flag, accumulator slot; cmap [S][K]: class -> slot; sclass [S][E Lcap]: slot -> class
 struct MbrWs { int *info, *einfo, *nslot, *link, *cmap, *sclass; double *logp; float *coef, *A, *B; int Npad, Lcap, E, slotcap; };
 
-static size_t mbr_up(size_t v) { return (v + 255) / 256 * 256; }
-
 static size_t mbr_layout(int T, int S, int N, int Lcap, int with_ref, void *base, MbrWs *ws) {
-  const size_t E = (size_t)N + (with_ref ? 1 : 0), npad = ((size_t)2 * Lcap + 1 + 3) / 4 * 4, SE = (size_t)S * E;
+  const size_t E = (size_t)N + (with_ref ? 1 : 0), npad = ctc_npad(Lcap), SE = (size_t)S * E;
   char *p = reinterpret_cast<char *>(base);
   size_t off = 0;
-  const size_t o_logp = off;   off += mbr_up(SE * sizeof(double));
-  const size_t o_coef = off;   off += mbr_up(SE * sizeof(float));
-  const size_t o_info = off;   off += mbr_up((size_t)S * sizeof(int));
-  const size_t o_nslot = off;  off += mbr_up((size_t)S * sizeof(int));
-  const size_t o_einfo = off;  off += mbr_up(SE * sizeof(int));
-  const size_t o_cmap = off;   off += mbr_up((size_t)S * MBR_KMAX * sizeof(int));
-  const size_t o_sclass = off; off += mbr_up(SE * (size_t)Lcap * sizeof(int));
-  const size_t o_link = off;   off += mbr_up(SE * 3 * (size_t)Lcap * sizeof(int));
+  const size_t o_logp = off;   off += ctc_up256(SE * sizeof(double));
+  const size_t o_coef = off;   off += ctc_up256(SE * sizeof(float));
+  const size_t o_info = off;   off += ctc_up256((size_t)S * sizeof(int));
+  const size_t o_nslot = off;  off += ctc_up256((size_t)S * sizeof(int));
+  const size_t o_einfo = off;  off += ctc_up256(SE * sizeof(int));
+  const size_t o_cmap = off;   off += ctc_up256((size_t)S * MBR_KMAX * sizeof(int));
+  const size_t o_sclass = off; off += ctc_up256(SE * (size_t)Lcap * sizeof(int));
+  const size_t o_link = off;   off += ctc_up256(SE * 3 * (size_t)Lcap * sizeof(int));
   const size_t o_a = off;      off += (size_t)T * SE * npad * sizeof(float);
   const size_t o_b = off;      off += (size_t)T * SE * npad * sizeof(float);
   if (ws) {
@@ -68,14 +68,8 @@ static size_t mbr_layout(int T, int S, int N, int Lcap, int with_ref, void *base
 
 size_t ctc_mbr_workspace_bytes(int T, int S, int N, int Lcap, int with_ref) { return mbr_layout(T, S, N, Lcap, with_ref, nullptr, nullptr); }
 
-int ctc_mbr_label_capacity(int T, int S, int N, int with_ref, size_t bytes) {      // the longest labelling a workspace of `bytes` serves; -1: none
-  if (bytes < ctc_mbr_workspace_bytes(T, S, N, 0, with_ref)) return -1;
-  int lo = 0, hi = 1023;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (ctc_mbr_workspace_bytes(T, S, N, mid, with_ref) <= bytes) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+int ctc_mbr_label_capacity(int T, int S, int N, int with_ref, size_t bytes) {
+  return ctc_label_capacity_of(bytes, [&](int Lcap) { return ctc_mbr_workspace_bytes(T, S, N, Lcap, with_ref); });
 }
 
 // the labels of entry e of stream s and their number
@@ -121,15 +115,7 @@ __global__ __launch_bounds__(64 * NW) void k_mbr_chain(const float *__restrict__
     if (tid == 0) ws.einfo[se] = e == a.N ? ref_ok : ok;       // the reference: its own status, whatever the list's
     if (!ok) return;
     int *next = ws.link + (size_t)se * 3 * ws.Lcap, *first = next + ws.Lcap;
-    for (int j = tid; j < L; j += NT) first[j] = 1;
-    __syncthreads();
-    for (int j = tid; j < L; j += NT) {
-      const int c = lab[j];
-      int q = j + 1;
-      while (q < L && lab[q] != c) q++;
-      next[j] = q < L ? q : -1;
-      if (q < L) first[q] = 0;                 // position q has exactly one predecessor: one writer
-    }
+    ctc_links(lab, L, next, first, NT);
     return;
   }
   if (!ok) return;
@@ -232,8 +218,7 @@ __global__ __launch_bounds__(256) void k_mbr_combine(const float *__restrict__ y
   float *dp = diff + (size_t)r * dstride;
   const float *yp = y + (size_t)r * stride;
   if (ws.info[s] != 1 || t >= a.lens[s]) {
-    if (vec) for (int c = tid * 4; c < K; c += 1024) *reinterpret_cast<float4 *>(dp + c) = make_float4(0.f, 0.f, 0.f, 0.f);
-    else for (int c = tid; c < K; c += 256) dp[c] = 0.f;
+    ctc_zero_row(dp, K, vec);
     return;
   }
   const int nsl = ws.nslot[s], cnt = a.count[s];
@@ -248,18 +233,7 @@ __global__ __launch_bounds__(256) void k_mbr_combine(const float *__restrict__ y
     const size_t rowoff = ((size_t)(s * E + e) * a.T + t) * ws.Npad;
     const float *al = ws.A + rowoff, *bt = ws.B + rowoff;
     __syncthreads();                           // the pass before is done with g; its slots are final
-    float mx = CTC_NEG;
-    for (int i = tid; i < NS; i += 256) { const float v = al[i] + bt[i]; g[i] = v; mx = fmaxf(mx, v); }
-    mx = ctc_block_reduce(mx, sm, true);
-    float sall = 0.f, seven = 0.f;
-    for (int i = tid; i < NS; i += 256) {      // 256 is even: a thread's states are all even or all odd
-      const float ex = expf(g[i] - mx);
-      g[i] = ex;
-      sall += ex;
-      seven += (i & 1) ? 0.f : ex;
-    }
-    sall = ctc_block_reduce(sall, sm, false);
-    seven = ctc_block_reduce(seven, sm, false);
+    KLSTM_CTC_GAMMA_ROW(float, ctc_block_sum, sm, al, bt, NS, g, sall, seven)
     const float inv = 1.f / sall;
     bacc += cf * (seven * inv);
     __syncthreads();                           // g complete
@@ -276,10 +250,7 @@ __global__ __launch_bounds__(256) void k_mbr_combine(const float *__restrict__ y
       const float4 v = *reinterpret_cast<const float4 *>(yp + c);
       *reinterpret_cast<float4 *>(dp + c) = make_float4(lam * v.x, lam * v.y, lam * v.z, lam * v.w);
     } else for (int c = tid; c < K; c += 256) dp[c] = lam * yp[c];
-  } else {
-    if (vec) for (int c = tid * 4; c < K; c += 1024) *reinterpret_cast<float4 *>(dp + c) = make_float4(0.f, 0.f, 0.f, 0.f);
-    else for (int c = tid; c < K; c += 256) dp[c] = 0.f;
-  }
+  } else ctc_zero_row(dp, K, vec);
   __syncthreads();                             // the slots are final, the row is visible to the threads that correct it
   if (tid == 0) dp[a.blank] = (lam > 0.f ? lam * yp[a.blank] : 0.f) + bacc;
   const int *sclass = ws.sclass + (size_t)s * ws.slotcap;
@@ -289,8 +260,6 @@ __global__ __launch_bounds__(256) void k_mbr_combine(const float *__restrict__ y
   }
 }
 
-static bool mbr_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 hipError_t launch_ctc_mbr(const float *y, int T, int S, int K, int stride, const int *lens, int blank, const int *hyp, int hyp_stride,
                           const int *hyp_len, const int *count, const int *errors, int N, const int *ref, const int *roff, float kappa,
                           float lam, float *diff, int dstride, float *risk, float *hyp_logp, float *hyp_post, float *ref_loss,
@@ -298,24 +267,13 @@ hipError_t launch_ctc_mbr(const float *y, int T, int S, int K, int stride, const
   MbrWs ws;
   mbr_layout(T, S, N, Lcap, ref != nullptr, workspace, &ws);
   const MbrIn in{lens, hyp, hyp_len, count, errors, ref, roff, hyp_stride, N, T, K, blank};
-  const int NS = 2 * Lcap + 1;
-  // the geometry of klstm_ctc_eval's chain, 16 * waves + states per thread
-  const int plan = NS <= 64 ? 16 * 1 + 1 : NS <= 256 ? 16 * 4 + 1 : NS <= 512 ? 16 * 4 + 2 : NS <= 1024 ? 16 * 16 + 1 : 16 * 16 + 2;
-  const dim3 grid(S * ws.E, 3);
-  hipError_t err;
-#define MBR_CASE(NW, P)                                                                                    \
-  case 16 * NW + P:                                                                                        \
-    err = launch(k_mbr_chain<NW, P>, grid, dim3(64 * NW), 0, st, LaunchProbe{}, y, S, stride, in, ws);     \
-    break;
-  switch (plan) {
-    MBR_CASE(1, 1) MBR_CASE(4, 1) MBR_CASE(4, 2) MBR_CASE(16, 1) MBR_CASE(16, 2)
-    default: return hipErrorInvalidValue;
-  }
-#undef MBR_CASE
+  hipError_t err = ctc_chain_dispatch(ctc_chain_plan(2 * Lcap + 1), hipErrorInvalidValue, [&](auto nw, auto p) {
+    return launch(k_mbr_chain<nw(), p()>, dim3(S * ws.E, 3), dim3(64 * nw()), 0, st, LaunchProbe{}, y, S, stride, in, ws);
+  });
   if (err != hipSuccess) return err;
   err = launch(k_mbr_weights, dim3(S), dim3(256), 0, st, LaunchProbe{}, S, in, kappa, lam, risk, hyp_logp, hyp_post, ref_loss, ws);
   if (err != hipSuccess) return err;
-  const int vec = K % 4 == 0 && stride % 4 == 0 && dstride % 4 == 0 && mbr_al16(y) && mbr_al16(diff);
+  const int vec = ctc_rows_vec(K, stride, dstride, y, diff);
   const int slots = ws.slotcap < K ? ws.slotcap : K;
   const size_t shm = (size_t)(slots > 0 ? slots : 1) * sizeof(float);
   return launch(k_mbr_combine, dim3(T * S), dim3(256), shm, st, LaunchProbe{}, y, S, stride, in, lam, diff, dstride, (const float *)risk,

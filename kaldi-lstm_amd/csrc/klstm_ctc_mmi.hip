@@ -7,7 +7,7 @@
 // incoming arcs in ascending source q (ioff / in_src / in_lw); every class lists its states in ascending q (coff / cstate).
 // THE CALL, three launches:
 //   k_mmi_ref      grid (S, 3).  The reference: ctc_chain_run of klstm_ctc_dev.h (y = 0 alpha, y = 1 beta; the bits of klstm_ctc_eval),
-//                  y = 2 the status of the stream, log W(ref) by one walk in double, the links of k_ctc_combine.
+//                  y = 2 the status of the stream, log W(ref) by one walk in double, the links (ctc_links).
 //   k_mmi_den      grid (S, 2).  The denominator's alpha (y = 0) and beta (y = 1) chain of one stream by ONE workgroup of 256 threads:
 //                  log domain, the current row and one row of partial sums in LDS, every frame's row taken relative to its own
 //                  maximum and written to the workspace; the maxima are summed in double.  (The linear domain with a scale per ROW
@@ -24,6 +24,7 @@
 
 #include "../../include/klstm.h"
 #include "klstm_ctc_dev.h"
+#include "klstm_ctc_host.h"
 #include "klstm_kernels.h"
 
 namespace klstm {
@@ -43,13 +44,11 @@ struct MmiGraph {
 // [S][T][Npad]; Ad, Bd: the denominator's [S][T rows of the graph's Npad, within T * Dpad floats]
 struct MmiWs { int *info, *link; double *logw, *numlp, *logz; float *A, *B, *Ad, *Bd; int Npad, Lcap, Dpad; };
 
-static size_t mmi_up(size_t v) { return (v + 255) / 256 * 256; }
-
 static size_t mmi_graph_layout(int Q, int K, void *base, MmiGraph *g) {
   const size_t QK = (size_t)Q * K;
   char *p = reinterpret_cast<char *>(base);
   size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off += mmi_up(n * 4); return p + o; };
+  auto take = [&](size_t n) { const size_t o = off; off += ctc_up256(n * 4); return p + o; };
   char *hdr = take(MH_WORDS), *fin = take(Q), *soff = take(Q + 1), *aoff = take(Q + 1), *arc_of = take(QK), *has = take(QK);
   char *st_q = take(QK), *st_k = take(QK), *st_g = take(QK), *ioff = take(QK + 1), *in_src = take(QK), *in_lw = take(QK);
   char *arc_w = take(QK), *arc_lw = take(QK), *arc_k = take(QK), *arc_dst = take(QK), *arc_q = take(QK), *coff = take(K + 1), *ccur = take(K), *cstate = take(QK);
@@ -64,14 +63,14 @@ static size_t mmi_graph_layout(int Q, int K, void *base, MmiGraph *g) {
 size_t ctc_mmi_graph_bytes(int Q, int K) { return mmi_graph_layout(Q, K, nullptr, nullptr); }
 
 static size_t mmi_layout(int T, int S, int K, int Q, int Lcap, void *base, MmiWs *ws) {
-  const size_t npad = ((size_t)2 * Lcap + 1 + 3) / 4 * 4, dpad = ((size_t)Q * K + 3) / 4 * 4;
+  const size_t npad = ctc_npad(Lcap), dpad = ((size_t)Q * K + 3) / 4 * 4;
   char *p = reinterpret_cast<char *>(base);
   size_t off = 0;
-  const size_t o_info = off;  off += mmi_up((size_t)S * sizeof(int));
-  const size_t o_logw = off;  off += mmi_up((size_t)S * sizeof(double));
-  const size_t o_numlp = off; off += mmi_up((size_t)S * sizeof(double));
-  const size_t o_logz = off;  off += mmi_up((size_t)S * sizeof(double));
-  const size_t o_link = off;  off += mmi_up((size_t)S * 2 * (size_t)Lcap * sizeof(int));
+  const size_t o_info = off;  off += ctc_up256((size_t)S * sizeof(int));
+  const size_t o_logw = off;  off += ctc_up256((size_t)S * sizeof(double));
+  const size_t o_numlp = off; off += ctc_up256((size_t)S * sizeof(double));
+  const size_t o_logz = off;  off += ctc_up256((size_t)S * sizeof(double));
+  const size_t o_link = off;  off += ctc_up256((size_t)S * 2 * (size_t)Lcap * sizeof(int));
   const size_t o_ad = off;    off += (size_t)T * S * dpad * sizeof(float);
   const size_t o_bd = off;    off += (size_t)T * S * dpad * sizeof(float);
   const size_t o_a = off;     off += (size_t)T * S * npad * sizeof(float);
@@ -94,14 +93,8 @@ static size_t mmi_layout(int T, int S, int K, int Q, int Lcap, void *base, MmiWs
 }
 size_t ctc_mmi_workspace_bytes(int T, int S, int K, int Q, int Lcap) { return mmi_layout(T, S, K, Q, Lcap, nullptr, nullptr); }
 
-int ctc_mmi_label_capacity(int T, int S, int K, int Q, size_t bytes) {      // the longest label sequence a workspace of `bytes` serves; -1: none
-  if (bytes < ctc_mmi_workspace_bytes(T, S, K, Q, 0)) return -1;
-  int lo = 0, hi = 1023;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (ctc_mmi_workspace_bytes(T, S, K, Q, mid) <= bytes) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+int ctc_mmi_label_capacity(int T, int S, int K, int Q, size_t bytes) {
+  return ctc_label_capacity_of(bytes, [&](int Lcap) { return ctc_mmi_workspace_bytes(T, S, K, Q, Lcap); });
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -220,15 +213,7 @@ __global__ __launch_bounds__(64 * NW) void k_mmi_ref(const float *__restrict__ y
     __syncthreads();
     if (sst != 1) return;
     int *next = ws.link + (size_t)s * 2 * ws.Lcap, *first = next + ws.Lcap;
-    for (int j = tid; j < L; j += NT) first[j] = 1;
-    __syncthreads();
-    for (int j = tid; j < L; j += NT) {
-      const int c = lab[j];
-      int q = j + 1;
-      while (q < L && lab[q] != c) q++;
-      next[j] = q < L ? q : -1;
-      if (q < L) first[q] = 0;                 // position q has exactly one predecessor: one writer
-    }
+    ctc_links(lab, L, next, first, NT);
     return;
   }
   if (st != 1) return;
@@ -428,8 +413,7 @@ __global__ __launch_bounds__(256) void k_mmi_combine(const float *__restrict__ y
   float *dp = diff + (size_t)r * dstride;
   const float *yp = y + (size_t)r * stride;
   if (ws.info[s] != 1 || t >= lens[s]) {
-    if (vec) for (int c = tid * 4; c < K; c += 1024) *reinterpret_cast<float4 *>(dp + c) = make_float4(0.f, 0.f, 0.f, 0.f);
-    else for (int c = tid; c < K; c += 256) dp[c] = 0.f;
+    ctc_zero_row(dp, K, vec);
     return;
   }
   // gamma_den: exp(alpha + beta - the frame's maximum) per class, states in ascending q, normalised by the frame's own total
@@ -453,22 +437,11 @@ __global__ __launch_bounds__(256) void k_mmi_combine(const float *__restrict__ y
   part = mmi_block_sum(part, smd);
   const double inv_tot = 1.0 / (part + pb);
   for (int k = tid; k < K; k += 256) pd[k] = (k == blank ? pb : pd[k]) * inv_tot + (lam > 0.f ? (double)lam * (double)yp[k] : 0.0);
-  // gamma_ref as k_ctc_combine takes it
+  // gamma_ref by the text k_ctc_combine expands, its sums in double: the row then sums to 1 beyond float32, as gamma_den's does
   const int L = loff[s + 1] - loff[s], N = 2 * L + 1;
   const int *lab = labels + loff[s];
   const float *a = ws.A + ((size_t)s * T + t) * ws.Npad, *bt = ws.B + ((size_t)s * T + t) * ws.Npad;
-  float mx = CTC_NEG;
-  for (int i = tid; i < N; i += 256) { const float v = a[i] + bt[i]; gr[i] = v; mx = fmaxf(mx, v); }
-  mx = ctc_block_reduce(mx, sm, true);
-  double sall = 0.0, seven = 0.0;              // (in double: the row of gamma_ref then sums to 1 beyond float32, as gamma_den's does)
-  for (int i = tid; i < N; i += 256) {         // 256 is even: a thread's states are all even or all odd
-    const float e = expf(gr[i] - mx);
-    gr[i] = e;
-    sall += (double)e;
-    seven += (i & 1) ? 0.0 : (double)e;
-  }
-  sall = mmi_block_sum(sall, smd);
-  seven = mmi_block_sum(seven, smd);
+  KLSTM_CTC_GAMMA_ROW(double, mmi_block_sum, smd, a, bt, N, gr, sall, seven)
   const double cref = (1.0 + (double)lam) / sall;
   __syncthreads();                             // gr and pd complete
   if (tid == 0) pd[blank] -= cref * seven;
@@ -491,8 +464,6 @@ hipError_t launch_ctc_mmi_graph(int Q, int K, int blank, const int *next, const 
   return launch(k_mmi_graph_build, dim3(1), dim3(256), 0, st, LaunchProbe{}, Q, K, blank, next, weight, final_, g);
 }
 
-static bool mmi_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 hipError_t launch_ctc_mmi(const float *y, int T, int S, int K, int stride, const int *lens, const int *labels, const int *loff, int blank,
                           const void *graph, int Q, float lam, float *diff, int dstride, float *loss, float *num_logp, float *den_logz,
                           float *lm_logw, double *totals, void *workspace, int Lcap, hipStream_t st) {
@@ -500,23 +471,14 @@ hipError_t launch_ctc_mmi(const float *y, int T, int S, int K, int stride, const
   mmi_graph_layout(Q, K, const_cast<void *>(graph), &g);
   MmiWs ws;
   mmi_layout(T, S, K, Q, Lcap, workspace, &ws);
-  const int N = 2 * Lcap + 1;
-  // the geometry of klstm_ctc_eval's chain, 16 * waves + states per thread
-  const int plan = N <= 64 ? 16 * 1 + 1 : N <= 256 ? 16 * 4 + 1 : N <= 512 ? 16 * 4 + 2 : N <= 1024 ? 16 * 16 + 1 : 16 * 16 + 2;
-  hipError_t err;
-#define MMI_CASE(NW, P)                                                                                                                      \
-  case 16 * NW + P:                                                                                                                          \
-    err = launch(k_mmi_ref<NW, P>, dim3(S, 3), dim3(64 * NW), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, labels, loff, blank, g, Q, ws); \
-    break;
-  switch (plan) {
-    MMI_CASE(1, 1) MMI_CASE(4, 1) MMI_CASE(4, 2) MMI_CASE(16, 1) MMI_CASE(16, 2)
-    default: return hipErrorInvalidValue;
-  }
-#undef MMI_CASE
+  hipError_t err = ctc_chain_dispatch(ctc_chain_plan(2 * Lcap + 1), hipErrorInvalidValue, [&](auto nw, auto p) {
+    return launch(k_mmi_ref<nw(), p()>, dim3(S, 3), dim3(64 * nw()), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, labels, loff, blank, g, Q,
+                  ws);
+  });
   if (err != hipSuccess) return err;
   err = launch(k_mmi_den, dim3(S, 2), dim3(256), (size_t)2 * Q * K * sizeof(float), st, LaunchProbe{}, y, T, S, stride, lens, blank, g, Q, K, ws);
   if (err != hipSuccess) return err;
-  const int vec = K % 4 == 0 && stride % 4 == 0 && dstride % 4 == 0 && mmi_al16(y) && mmi_al16(diff);
+  const int vec = ctc_rows_vec(K, stride, dstride, y, diff);
   return launch(k_mmi_combine, dim3(T * S), dim3(256), (size_t)K * sizeof(double), st, LaunchProbe{}, y, T, S, K, stride, lens, labels, loff,
                 blank, lam, diff, dstride, loss, num_logp, den_logz, lm_logw, totals, g, Q, ws, vec);
 }
