@@ -616,6 +616,55 @@ klstm_status klstm_ctc_mbr_eval(const float *net_out, int T, int S, int K, int s
                                 int diff_stride, float *risk_dev, float *hyp_logp_dev, float *hyp_post_dev, float *ref_loss_dev,
                                 double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/* Minimum Bayes risk decoding and token / word confidences over CTC n-best lists (include/klstm_nnet.hpp class CtcConsensus;
+ * INTEGRATION.md 3m): the decode-time counterpart of klstm_ctc_mbr_eval, Kaldi's lattice-mbr-decode in n-best form.
+ * Stateless, asynchronous on hip_stream, decided entirely on the device; nothing is read back.  For stream s, over its LIVE entries:
+ *   units        separator < 0: the tokens of an entry.  separator >= 0: its words, the maximal runs of tokens other than the separator
+ *                (leading, trailing and repeated separators make no empty words).  Two words are equal iff their 64-bit keys are: the
+ *                hash the beam search knows its prefixes by, h <- x ^ (x >> 29) with x = (h ^ (token + 1)) * 0x9E3779B97F4A7C15,
+ *                folded over the word's tokens from h = 0x243F6A8885A308D3
+ *   P_q          exp(z_q - max z) / Z with z_q = (double)scale * (double)logp_q and Z summed q ascending, in double
+ *   D[q][r]      the Levenshtein distance between the unit sequences of entries q and r
+ *   R_q          sum_r P_r D[q][r], r ascending, in double: the expected unit errors of answering with entry q
+ *   map, mbr     argmax z and argmin R, ties to the lowest q; pick = pivot_mode ? mbr : map
+ *   conf_u       sum_r P_r [unit u of the pick is matched against entry r], r ascending, in double.  Matched: in the full table over
+ *                the pick's units (i) and entry r's (j), walk from the far corner -- the diagonal if D[i][j] = D[i-1][j-1] + (a_i != b_j),
+ *                else up (i - 1) if D[i][j] = D[i-1][j] + 1, else left -- and unit i is matched iff it is left by a diagonal step with
+ *                a_i = b_j.  The pick is matched against itself throughout, so conf_u >= P_pick
+ *   hyp_dev, hyp_stride, hyp_len_dev [S*N], nbest_count_dev [S], list_n = N    the arrays of klstm_ctc_beam_decode, unchanged.  Slots
+ *                        q >= nbest_count[s] are NOT READ
+ *   logp_dev [S*N]       natural logarithms: the search's score_dev, or hyp_logp_dev of klstm_ctc_mbr_eval
+ *   errors_dev           NULL, or [S*N] as the search wrote them with references (totals 8 and 9 only)
+ *   max_len              the unit and token capacity, <= 1023
+ *   scale                finite, > 0
+ *   pick_dev, map_dev, mbr_dev [S]   -1 on a stream that is idle or rejected
+ *   post_dev [S*N]       float(P_q); 0 for a dropped or unlisted entry
+ *   risk_dev [S*N]       float(R_q); -1 there
+ *   unit_len_dev [S*N]   the number of units; 0 there
+ *   conf_dev, conf_stride    float(conf_u) at conf_dev[s*conf_stride + u] for the units of the pick; nothing else is written.
+ *                        conf_stride >= min(hyp_stride, max_len)
+ *   dist_dev             NULL, or [S*N*N]: D, exact and symmetric; -1 where either entry is dropped or unlisted
+ *   totals_dev           NULL, or ten doubles that this minibatch is ADDED to, streams in order: streams done, streams idle or rejected,
+ *                        sum of R[pick], sum of R[map], streams with mbr != map, sum of the picks' units, sum of conf over them, entries
+ *                        dropped, sum of errors[pick], sum of errors[map] (the last two 0 without errors_dev)
+ *   workspace            klstm_ctc_consensus_workspace_bytes(S, list_n, max_len, separator >= 0) bytes, 16-byte aligned: per entry 24
+ *                        bytes, 4 N bytes of distances, max_len bytes of matches, in word mode 8 max_len bytes of keys, and for
+ *                        max_len > 255 (where a table of back-pointers no longer fits LDS) 256 max_len bytes of table.  One call at a
+ *                        time per workspace
+ * AN ENTRY q < nbest_count[s] IS LIVE iff logp is finite, 0 <= hyp_len <= min(hyp_stride, max_len) and no token is negative; every
+ * other one is dropped and counted.  STATUS of a stream: REJECTED with nbest_count[s] outside [0, N]; IDLE with a count of 0 or no
+ * live entry; done otherwise.
+ * Bit-identical from run to run: no floating-point atomics, every sum in index order.
+ * Limits: 1 <= S <= 32, 1 <= list_n <= 64, 0 <= max_len <= 1023; beyond them KLSTM_ERR_SHAPE and nothing is launched
+ * (klstm_ctc_consensus_workspace_bytes answers 0 and leaves the message in klstm_last_error(); neither touches a device then).  A
+ * workspace below the size query, a null or misaligned pointer, a bad scale, pivot_mode or stride: KLSTM_ERR_ARG. */
+size_t klstm_ctc_consensus_workspace_bytes(int S, int list_n, int max_len, int word_mode);
+klstm_status klstm_ctc_consensus(const int *hyp_dev, int hyp_stride, const int *hyp_len_dev, const int *nbest_count_dev, const float *logp_dev,
+                                 const int *errors_dev, int S, int list_n, int max_len, float scale, int separator, int pivot_mode,
+                                 int *pick_dev, int *map_dev, int *mbr_dev, float *post_dev, float *risk_dev, int *unit_len_dev,
+                                 float *conf_dev, int conf_stride, int *dist_dev, double *totals_dev, void *workspace, size_t workspace_bytes,
+                                 void *hip_stream);
+
 /* MMI (CTC-CRF) training against a label language model (include/klstm_nnet.hpp class CtcMmi): the
  * posterior of the reference under the automaton the beam search multiplies in (klstm_ctc_beam_decode_lm's tables), with the normaliser
  * summed exactly over EVERY labelling the automaton accepts.  Stateless apart from the note below, asynchronous on hip_stream, decided

@@ -928,8 +928,9 @@ inline SparseLabelLm ReadArpaLabelLm(std::istream &is, const std::map<std::strin
 }
 
 // What a CtcBeamDecoder's last Decode left on the device: hypotheses [num_stream][nbest][stride], their lengths [num_stream][nbest],
-// the entries listed per stream, their edit distances [num_stream][nbest] (null when it had no references)
-struct CtcNbestDevice { const int32 *hyp, *hyp_len, *count, *errors; int32 num_stream, nbest, stride; };
+// the entries listed per stream, their edit distances [num_stream][nbest] (null when it had no references), the search's scores
+// [num_stream][nbest]
+struct CtcNbestDevice { const int32 *hyp, *hyp_len, *count, *errors; int32 num_stream, nbest, stride; const BaseFloat *score; };
 
 // What CtcBeamDecoder and CtcStreamDecoder share on top of CtcCallBase: the sizes of the search, the language model in use, and the
 // six totals with their accessors and the report.  (A base for its members only, like CtcCallBase.)
@@ -1058,9 +1059,11 @@ class CtcBeamDecoder : public CtcBeamBase {
     for (int32 s = 0; s < num_stream_; s++) (*v)[s] = e[(size_t)s * nbest_];
   }
 
-  // the device arrays of the last Decode as klstm_ctc_mbr_eval takes them (CtcMbr::Eval), with the shape they were written for
+  // the device arrays of the last Decode as klstm_ctc_mbr_eval and klstm_ctc_consensus take them (CtcMbr::Eval, CtcConsensus::Eval), with
+  // the shape they were written for
   CtcNbestDevice DeviceLists() const {
-    return CtcNbestDevice{hyp_.As<int32>(), hlen_.As<int32>(), cnt_.As<int32>(), scored_ ? err_.As<int32>() : nullptr, num_stream_, nbest_, frames_};
+    return CtcNbestDevice{hyp_.As<int32>(), hlen_.As<int32>(), cnt_.As<int32>(), scored_ ? err_.As<int32>() : nullptr, num_stream_, nbest_, frames_,
+                          score_.As<BaseFloat>()};
   }
  private:
   int32 frames_ = 0;
@@ -1237,6 +1240,85 @@ class CtcMbr : private CtcCallBase {
   DeviceTotals<6> tot_;
 };
 
+// Minimum Bayes risk decoding and unit confidences over the n-best lists of a CtcBeamDecoder (klstm_ctc_consensus, klstm.h, which
+// defines every quantity): per stream the entry of the list with the smallest expected unit errors under the
+// list's own posterior (or the most probable one), and for each of its tokens or words the posterior mass of the entries that agree
+// with it.  Reads the lists where Decode left them; the ten totals stay on the device and are read when somebody asks.
+class CtcConsensus : private CtcCallBase {
+ public:
+  // mbr_pivot: answer with the MBR entry (false: the MAP entry, with confidences); scale multiplies the log weights; separator: -1
+  // for token units, otherwise the class that separates words; max_len: the token capacity, 0: min(1023, the lists' stride)
+  explicit CtcConsensus(bool mbr_pivot = true, BaseFloat scale = 1.f, int32 separator = -1, int32 max_len = 0)
+      : CtcCallBase(0), mbr_pivot_(mbr_pivot), scale_(scale), separator_(separator), max_len_(max_len) {}
+
+  // over the lists of the last lists.Decode; logp_dev: [num_stream][nbest] natural-log weights on the device (CtcMbr's log p(h | y),
+  // say), null: the search's scores.  Nothing synchronises.
+  void Eval(const CtcBeamDecoder &lists, const BaseFloat *logp_dev = nullptr) {
+    const CtcNbestDevice nb = lists.DeviceLists();
+    const int32 S = nb.num_stream, N = nb.nbest;
+    KLSTM_ASSERT(S > 0 && N > 0 && nb.stride > 0);
+    const int32 max_len = max_len_ > 0 ? max_len_ : std::min<int32>(1023, nb.stride);
+    const size_t need = klstm_ctc_consensus_workspace_bytes(S, N, max_len, separator_ >= 0);
+    void *ws = Workspace(need);
+    idx_.Grow((size_t)S * 3 * sizeof(int32));
+    post_.Grow((size_t)S * N * sizeof(BaseFloat));
+    risk_.Grow((size_t)S * N * sizeof(BaseFloat));
+    ulen_.Grow((size_t)S * N * sizeof(int32));
+    conf_.Grow((size_t)S * nb.stride * sizeof(BaseFloat));
+    int32 *idx = idx_.As<int32>();
+    KCheck(klstm_ctc_consensus(nb.hyp, nb.stride, nb.hyp_len, nb.count, logp_dev ? logp_dev : nb.score, nb.errors, S, N, max_len, scale_,
+                               separator_, mbr_pivot_ ? 1 : 0, idx, idx + S, idx + 2 * S, post_.As<BaseFloat>(), risk_.As<BaseFloat>(),
+                               ulen_.As<int32>(), conf_.As<BaseFloat>(), nb.stride, nullptr, tot_.Dev(), ws, need, nullptr));
+    num_stream_ = S; nbest_ = N; stride_ = nb.stride;
+  }
+  // of the last Eval (each synchronises), per stream: the entry answered with, the MAP and the MBR entry (-1: idle or rejected)
+  void Picks(std::vector<int32> *pick, std::vector<int32> *map = nullptr, std::vector<int32> *mbr = nullptr) const {
+    std::vector<int32> v((size_t)3 * num_stream_);
+    idx_.Download(v.data(), v.size());
+    pick->assign(v.begin(), v.begin() + num_stream_);
+    if (map) map->assign(v.begin() + num_stream_, v.begin() + 2 * num_stream_);
+    if (mbr) mbr->assign(v.begin() + 2 * num_stream_, v.end());
+  }
+  // ... the confidence of every unit of the entry answered with (empty: none), and its expected unit errors (-1: none)
+  void Confidences(std::vector<std::vector<BaseFloat> > *conf, std::vector<BaseFloat> *pick_risk = nullptr) const {
+    std::vector<int32> pick, ulen((size_t)num_stream_ * nbest_);
+    Picks(&pick);
+    ulen_.Download(ulen.data(), ulen.size());
+    std::vector<BaseFloat> c((size_t)num_stream_ * stride_), r((size_t)num_stream_ * nbest_);
+    conf_.Download(c.data(), c.size());
+    risk_.Download(r.data(), r.size());
+    conf->assign(num_stream_, std::vector<BaseFloat>());
+    if (pick_risk) pick_risk->assign(num_stream_, -1.f);
+    for (int32 s = 0; s < num_stream_; s++) {
+      if (pick[s] < 0) continue;
+      const size_t o = (size_t)s * nbest_ + pick[s];
+      (*conf)[s].assign(c.begin() + (size_t)s * stride_, c.begin() + (size_t)s * stride_ + ulen[o]);
+      if (pick_risk) (*pick_risk)[s] = r[o];
+    }
+  }
+  // over the streams done so far
+  double ExpectedErrors() const { const double *h = tot_.Read(); return h[2] / h[0]; }          // of the entry answered with, per utterance
+  double MapExpectedErrors() const { const double *h = tot_.Read(); return h[3] / h[0]; }       // of the most probable entry
+  double MeanConfidence() const { const double *h = tot_.Read(); return h[6] / h[5]; }          // over the units answered with
+  double NumUtterances() const { return tot_.Read()[0]; }
+  double NumPickErrors() const { return tot_.Read()[8]; }                                       // edit errors of the entries answered with (lists decoded with references)
+  std::string Report() const {
+    const double *h = tot_.Read();
+    std::ostringstream oss;
+    oss << "EXPECTED_ERRORS: " << h[2] / h[0] << " per utterance (" << (mbr_pivot_ ? "MBR" : "MAP") << " entry; MAP entry: " << h[3] / h[0] << "), "
+        << (separator_ >= 0 ? "words" : "tokens") << ", mean confidence " << h[6] / h[5] << " [" << h[0] << " utterances, " << h[1]
+        << " idle or rejected, " << h[4] << " where the MBR entry is not the MAP entry, " << h[5] << " units, " << h[7] << " entries dropped, "
+        << h[8] << " errors (MAP entry: " << h[9] << ")]" << std::endl;
+    return oss.str();
+  }
+ private:
+  bool mbr_pivot_;
+  BaseFloat scale_;
+  int32 separator_, max_len_, nbest_ = 0, stride_ = 0;
+  DeviceBuffer idx_, post_, risk_, ulen_, conf_;
+  DeviceTotals<10> tot_;
+};
+
 struct TrainMbrOptions {
   NnetTrainOptions trn_opts;
   int32 num_stream = 4, blank = 0, max_frames = 0;       // max_frames 0: 65535 / num_stream
@@ -1399,11 +1481,18 @@ struct DecodeCtcOptions {
   int32 beam = 0, cands = 8, nbest = 1;                  // beam 0: best path (CtcGreedyDecoder); beam > 0: prefix beam search (CtcBeamDecoder)
   const CtcLabelLm *lm = nullptr;                        // beam > 0 only: fused into the search (CtcBeamDecoder::SetLanguageModel); not owned
   const CtcSparseLabelLm *slm = nullptr;                 // beam > 0 only: a sparse back-off model in its place (at most one of the two); not owned
+  int32 consensus = 0;                                   // beam > 0 only (CtcConsensus over each minibatch's lists): 0 off, 1 the MAP entry with
+                                                         // confidences, 2 the MBR entry is the hypothesis
+  BaseFloat consensus_scale = 1.f;                       // multiplies the search's scores under the lists' posterior
+  int32 separator = -1;                                  // -1: errors and confidences per token; otherwise the class that separates words
 };
 struct DecodeCtcStats {
   int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
   double token_error_rate = 0, utt_error_rate = 0, num_scored = 0, num_errors = 0, num_ref_tokens = 0, seconds = 0;
   double oracle_token_error_rate = 0;                    // beam search only: the best hypothesis of every n-best list
+  // with o.consensus only: expected unit errors per utterance of the hypotheses returned and of the MAP entries under the lists'
+  // posteriors, the mean confidence of the units returned, the edit errors of the hypotheses returned (scored passes)
+  double expected_errors = 0, map_expected_errors = 0, mean_confidence = 0, num_pick_errors = 0;
 };
 
 // per-stream results of one minibatch -> per-utterance results in the order of the utterance list (idle streams carry nothing)
@@ -1429,13 +1518,16 @@ inline void FillDecodeCtcStats(const Decoder &dec, DecodeCtcStats *st, std::stri
 
 // The loop of DecodeCtcWholeUtterances below with the prefix beam search (o.beam > 0).  (*hypotheses)[i] is the 1-best of utts[i],
 // (*nbest_lists)[i] its whole list with scores and edit distances (either may be null; both empty for a skipped utterance).
-// every_batch sees (batch, net_out, CtcBeamDecoder) after Decode.
+// every_batch sees (batch, net_out, CtcBeamDecoder) after Decode.  With o.consensus (1 or 2) a CtcConsensus runs over the lists of
+// every minibatch: (*hypotheses)[i] is then the entry it answers with (the MAP or the MBR one), (*confidences)[i] (may be null) holds
+// one confidence per token or word of it, and the statistics and the report carry the expected errors.
 template <class F>
 inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
                                                std::vector<std::vector<int32> > *hypotheses, std::vector<CtcNbestList> *nbest_lists,
-                                               std::string *report, F every_batch) {
-  KLSTM_ASSERT(o.beam > 0);
+                                               std::vector<std::vector<BaseFloat> > *confidences, std::string *report, F every_batch) {
+  KLSTM_ASSERT(o.beam > 0 && o.consensus >= 0 && o.consensus <= 2);
   CtcBeamDecoder dec(o.blank, o.beam, o.cands, o.nbest);
+  CtcConsensus cons(o.consensus == 2, o.consensus_scale, o.separator);
   dec.SetClassWeights(o.class_weights);
   KLSTM_ASSERT(!o.lm || !o.slm);
   if (o.slm) dec.SetLanguageModel(o.slm); else dec.SetLanguageModel(o.lm);
@@ -1444,25 +1536,57 @@ inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utt
   const bool want = hypotheses || nbest_lists;
   if (hypotheses) hypotheses->assign(utts.size(), std::vector<int32>());
   if (nbest_lists) nbest_lists->assign(utts.size(), CtcNbestList());
+  if (confidences) confidences->assign(utts.size(), std::vector<BaseFloat>());
   DecodeCtcStats st = ForEachWholeUtteranceBatch<DecodeCtcStats>(nnet, utts, o.num_stream, o.sort_by_length, o.max_frames,
       [&](const UtteranceBatch &b, const DeviceMatrix &nnet_out) {
         dec.Decode(nnet_out, b.num_stream, b.lens, o.score ? b.labels : none, want ? &lists : nullptr);
+        std::vector<int32> pick(b.num_stream, 0);          // without a consensus: the head of the list
+        if (o.consensus) {
+          cons.Eval(dec);
+          if (hypotheses) cons.Picks(&pick);
+          if (confidences) {
+            std::vector<std::vector<BaseFloat> > conf;
+            cons.Confidences(&conf);
+            ScatterByUtterance(b, conf, confidences);
+          }
+        }
         if (nbest_lists) ScatterByUtterance(b, lists, nbest_lists);
         if (hypotheses) {
           std::vector<std::vector<int32> > best(b.num_stream);
-          for (int32 s = 0; s < b.num_stream; s++) if (!lists[s].empty()) best[s] = lists[s][0].tokens;
+          for (int32 s = 0; s < b.num_stream; s++)
+            if (pick[s] >= 0 && (size_t)pick[s] < lists[s].size()) best[s] = lists[s][pick[s]].tokens;
           ScatterByUtterance(b, best, hypotheses);
         }
         every_batch(b, nnet_out, dec);
       });
   st.oracle_token_error_rate = dec.OracleTokenErrorRate();
   FillDecodeCtcStats(dec, &st, report);
+  if (o.consensus) {
+    st.expected_errors = cons.ExpectedErrors();
+    st.map_expected_errors = cons.MapExpectedErrors();
+    st.mean_confidence = cons.MeanConfidence();
+    st.num_pick_errors = cons.NumPickErrors();
+    if (report) *report += "\n" + cons.Report();
+  }
   return st;
+}
+template <class F>
+inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
+                                               std::vector<std::vector<int32> > *hypotheses, std::vector<CtcNbestList> *nbest_lists,
+                                               std::string *report, F every_batch) {
+  return DecodeCtcWholeUtterances(nnet, utts, o, hypotheses, nbest_lists, (std::vector<std::vector<BaseFloat> > *)nullptr, report, every_batch);
 }
 inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
                                                std::vector<std::vector<int32> > *hypotheses, std::vector<CtcNbestList> *nbest_lists,
                                                std::string *report = nullptr) {
   return DecodeCtcWholeUtterances(nnet, utts, o, hypotheses, nbest_lists, report, [](const UtteranceBatch &, const DeviceMatrix &, const CtcBeamDecoder &) {});
+}
+// ... with the confidences of the hypotheses (o.consensus 1 or 2; empty vectors without)
+inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
+                                               std::vector<std::vector<int32> > *hypotheses, std::vector<CtcNbestList> *nbest_lists,
+                                               std::vector<std::vector<BaseFloat> > *confidences, std::string *report) {
+  return DecodeCtcWholeUtterances(nnet, utts, o, hypotheses, nbest_lists, confidences, report,
+                                  [](const UtteranceBatch &, const DeviceMatrix &, const CtcBeamDecoder &) {});
 }
 
 // The loop of TrainCtcWholeUtterances without the objective and the backward pass: SetSeqLengths, Reset, Propagate, Decode.

@@ -20,6 +20,7 @@ from .ctc import CtcBeamResult, ctc_beam_decode, ctc_beam_workspace_bytes, nbest
 from .ctc import CtcLabelLm, CtcSparseLabelLm  # noqa: F401,E402
 from .ctc import CtcBeamStream, CtcStreamResult, ctc_beam_stream_state_bytes, ctc_beam_stream_workspace_bytes  # noqa: F401,E402
 from .ctc import CtcMbrResult, ctc_mbr_eval, ctc_mbr_workspace_bytes  # noqa: F401,E402
+from .ctc import CtcConsensusResult, consensus_to_lists, ctc_consensus_workspace_bytes, ctc_nbest_consensus  # noqa: F401,E402
 from .ctc import CtcMmiDenominator, CtcMmiResult, ctc_mmi_eval, ctc_mmi_workspace_bytes  # noqa: F401,E402
 from .lm import lexicon_label_lm, ngram_label_lm  # noqa: F401,E402
 from .lm import SparseLm, arpa_label_lm, backoff_ngram_label_lm, sparse_lm_lookup, sparse_lm_to_dense, sparse_lm_validate  # noqa: F401,E402

@@ -141,6 +141,9 @@ def load_library():
     lib.klstm_ctc_mbr_workspace_bytes.restype = ctypes.c_size_t
     lib.klstm_ctc_mbr_eval.argtypes = [P, I, I, I, I, P, I, P, I, P, P, P, I, P, P, ctypes.c_float, ctypes.c_float, P, I, P, P, P, P, P, P,
                                        ctypes.c_size_t, P]
+    lib.klstm_ctc_consensus_workspace_bytes.argtypes = [I, I, I, I]
+    lib.klstm_ctc_consensus_workspace_bytes.restype = ctypes.c_size_t
+    lib.klstm_ctc_consensus.argtypes = [P, I, P, P, P, P, I, I, I, ctypes.c_float, I, I, P, P, P, P, P, P, P, I, P, P, P, ctypes.c_size_t, P]
     lib.klstm_ctc_mmi_graph_bytes.argtypes = [I, I]
     lib.klstm_ctc_mmi_graph_bytes.restype = ctypes.c_size_t
     lib.klstm_ctc_mmi_graph_build.argtypes = [I, I, I, P, P, P, P, ctypes.c_size_t, P]

@@ -45,15 +45,12 @@
 
 namespace klstm {
 
-typedef unsigned long long u64;
-
 __device__ __forceinline__ float bmul(float a, float b) { return a * b; }
 __device__ __forceinline__ float badd(float a, float b) { return a + b; }
 __device__ __forceinline__ double bmul(double a, double b) { return a * b; }
 __device__ __forceinline__ double badd(double a, double b) { return a + b; }
 
 constexpr float BEAM_TINY = 0x1p-60f, BEAM_HUGE = 0x1p60f;
-constexpr u64 BEAM_H0 = 0x243F6A8885A308D3ull, BEAM_HMUL = 0x9E3779B97F4A7C15ull;
 constexpr int BEAM_LMK = 8;            // extensions a thread builds at the largest list: 2048 over 256 threads
 constexpr int BEAM_KPT = 9;            // keys a thread ranks at the largest list: 2112 entries over 256 threads
 constexpr int BEAM_MAXB = 64, BEAM_MAXC = 32, BEAM_MAXLIST = 2114;      // B (C + 1) <= 2112, one more for the pair reads, even
@@ -62,10 +59,6 @@ constexpr int BEAM_MAXB = 64, BEAM_MAXC = 32, BEAM_MAXLIST = 2114;      // B (C 
 __device__ __forceinline__ float beam_emit(float v) { return v >= BEAM_TINY ? fminf(v, BEAM_HUGE) : 0.f; }
 __device__ __forceinline__ float beam_emit_at(const float *__restrict__ yp, const float *__restrict__ w, int k) {
   return beam_emit(w ? bmul(yp[k], w[k]) : yp[k]);
-}
-__device__ __forceinline__ u64 beam_hash(u64 h, int c) {
-  const u64 x = (h ^ (u64)(unsigned)(c + 1)) * BEAM_HMUL;
-  return x ^ (x >> 29);
 }
 __device__ __forceinline__ bool beam_row_valid(int r, int T, int S, const int *__restrict__ lens) {
   const int s = r % S, t = r / S, len = lens[s];

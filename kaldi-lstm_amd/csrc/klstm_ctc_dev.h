@@ -1,6 +1,6 @@
 // kaldi-lstm_amd/csrc/klstm_ctc_dev.h -- device code shared by the CTC kernels (klstm_ctc.hip: the loss; klstm_ctc_align.hip: the forced
 // alignment; klstm_ctc_decode.hip: best path; klstm_ctc_beam.hip: prefix beam search; klstm_ctc_mbr.hip: the n-best risk;
-// klstm_ctc_mmi.hip: MMI): the status of an utterance, the maximum over a wave, the fixed-tree reduction over a workgroup, the links,
+// klstm_ctc_mmi.hip: MMI; klstm_ctc_consensus.hip: MBR decoding over n-best lists): the prefix hash, the status of an utterance, the maximum over a wave, the fixed-tree reduction over a workgroup, the links,
 // the zero row and the gamma row of the three lattice losses, (value, index) reductions, the row reader, the one-wave Levenshtein
 // distance and the alpha / beta chain of the loss (ctc_chain_run).  The host's side of the lattice losses: klstm_ctc_host.h.
 #pragma once
@@ -14,6 +14,15 @@
 namespace klstm {
 
 constexpr float CTC_NEG = -1e30f;      // "log 0": absorbs every offset (ulp 7e22), exp(CTC_NEG - m) = 0
+
+// The 64-bit hash of a label sequence: beam_hash folded over its labels from BEAM_H0, the hash of the empty prefix.  The prefix beam
+// search (klstm_ctc_beam.hip) knows its prefixes by it; the n-best consensus (klstm_ctc_consensus.hip) knows its words by it.
+typedef unsigned long long u64;
+constexpr u64 BEAM_H0 = 0x243F6A8885A308D3ull, BEAM_HMUL = 0x9E3779B97F4A7C15ull;
+__device__ __forceinline__ u64 beam_hash(u64 h, int c) {
+  const u64 x = (h ^ (u64)(unsigned)(c + 1)) * BEAM_HMUL;
+  return x ^ (x >> 29);
+}
 
 // 0 idle (len 0), 1 feasible, 2 rejected.  Uniform over the workgroup; sm: 2 ints of LDS.
 __device__ __forceinline__ int ctc_status(int len, int T, int L, int Lcap, const int *__restrict__ lab, int K, int blank, int *sm) {

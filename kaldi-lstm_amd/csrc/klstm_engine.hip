@@ -2467,6 +2467,41 @@ klstm_status klstm_ctc_mbr_eval(const float *net_out, int T, int S, int K, int s
                         ref_loss_dev, totals_dev, workspace, lcap, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
+static bool ctc_consensus_shape_ok(int S, int list_n, int max_len) {
+  return S >= 1 && S <= 32 && list_n >= 1 && list_n <= 64 && max_len >= 0 && max_len <= 1023;
+}
+size_t klstm_ctc_consensus_workspace_bytes(int S, int list_n, int max_len, int word_mode) {
+  if (!ctc_consensus_shape_ok(S, list_n, max_len)) {
+    fail(KLSTM_ERR_SHAPE, "klstm_ctc_consensus_workspace_bytes: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", S, list_n, max_len);
+    return 0;
+  }
+  return ctc_consensus_workspace_bytes(S, list_n, max_len, word_mode != 0);
+}
+klstm_status klstm_ctc_consensus(const int *hyp_dev, int hyp_stride, const int *hyp_len_dev, const int *nbest_count_dev, const float *logp_dev,
+                                 const int *errors_dev, int S, int list_n, int max_len, float scale, int separator, int pivot_mode,
+                                 int *pick_dev, int *map_dev, int *mbr_dev, float *post_dev, float *risk_dev, int *unit_len_dev,
+                                 float *conf_dev, int conf_stride, int *dist_dev, double *totals_dev, void *workspace, size_t workspace_bytes,
+                                 void *hip_stream) {
+  const char *fn = "klstm_ctc_consensus";
+  if (!ctc_consensus_shape_ok(S, list_n, max_len))                 // (every limit before any pointer)
+    return fail(KLSTM_ERR_SHAPE, "%s: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", fn, S, list_n, max_len);
+  if (hyp_stride <= 0 || conf_stride < (hyp_stride < max_len ? hyp_stride : max_len))
+    return fail(KLSTM_ERR_ARG, "%s: hypothesis stride %d, confidence stride %d (at least min(hypothesis stride, length %d))", fn, hyp_stride, conf_stride, max_len);
+  if (!(scale > 0.f) || !std::isfinite(scale)) return fail(KLSTM_ERR_ARG, "%s: scale %g is not a finite number above 0", fn, (double)scale);
+  if (pivot_mode != 0 && pivot_mode != 1) return fail(KLSTM_ERR_ARG, "%s: pivot mode %d is neither 0 (MAP) nor 1 (MBR)", fn, pivot_mode);
+  if (!hyp_dev || !hyp_len_dev || !nbest_count_dev || !logp_dev || !pick_dev || !map_dev || !mbr_dev || !post_dev || !risk_dev || !unit_len_dev ||
+      !conf_dev || !workspace)
+    return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
+  const size_t need = ctc_consensus_workspace_bytes(S, list_n, max_len, separator >= 0);
+  if (workspace_bytes < need)
+    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_consensus_workspace_bytes(%d, %d, %d, %d) = %zu", fn, workspace_bytes,
+                S, list_n, max_len, (int)(separator >= 0), need);
+  HIPCHK(launch_ctc_consensus(hyp_dev, hyp_stride, hyp_len_dev, nbest_count_dev, logp_dev, errors_dev, S, list_n, max_len, scale, separator,
+                              pivot_mode, pick_dev, map_dev, mbr_dev, post_dev, risk_dev, unit_len_dev, conf_dev, conf_stride, dist_dev,
+                              totals_dev, workspace, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
 // ---- MMI against a label-LM denominator.  What a graph was built for is remembered per address: the header lives on the device and
 // the calls do not wait for it, so klstm_ctc_mmi_eval knows a graph by where klstm_ctc_mmi_graph_build put it ----
 struct MmiGraphNote { int Q, K, blank; };

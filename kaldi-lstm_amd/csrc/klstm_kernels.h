@@ -375,6 +375,14 @@ hipError_t launch_ctc_mbr(const float *y, int T, int S, int K, int stride, const
                           const int *hyp_len, const int *count, const int *errors, int N, const int *ref, const int *roff, float kappa,
                           float lam, float *diff, int dstride, float *risk, float *hyp_logp, float *hyp_post, float *ref_loss,
                           double *totals, void *workspace, int Lcap, hipStream_t st);
+// MBR decoding and unit confidences over CTC n-best lists (klstm_ctc_consensus.hip): klstm_ctc_consensus /
+// klstm_ctc_consensus_workspace_bytes of include/klstm.h.  The workspace: statuses, posteriors and risks per entry, the distances,
+// a byte per (entry, pivot slot), the words' keys (word mode) and the back-pointer tables that do not fit LDS (max_len > 255).
+size_t ctc_consensus_workspace_bytes(int S, int N, int max_len, int words);
+hipError_t launch_ctc_consensus(const int *hyp, int hyp_stride, const int *hyp_len, const int *count, const float *logp, const int *errors,
+                                int S, int N, int max_len, float scale, int separator, int pivot_mode, int *pick, int *map, int *mbr,
+                                float *post, float *risk, int *unit_len, float *conf, int conf_stride, int *dist, double *totals,
+                                void *workspace, hipStream_t st);
 // MMI (CTC-CRF) against a label-LM denominator (klstm_ctc_mmi.hip): klstm_ctc_mmi_graph_build / klstm_ctc_mmi_eval of include/klstm.h.
 // The graph: the reachable denominator states of Q LM states x K classes with their arcs by source and by destination.  The
 // workspace: statuses and log weights per stream, the reference's links and rows as klstm_ctc_eval keeps them, then the

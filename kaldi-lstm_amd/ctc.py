@@ -8,6 +8,7 @@ lm=CtcSparseLabelLm(...) with a sparse back-off n-gram, read from an ARPA file o
 CtcBeamStream: the same search fed chunk by chunk, the beam kept on the device between the calls (klstm_ctc_beam_stream_step / _emit;
 INTEGRATION.md 3j).
 ctc_mbr_eval: the expected token errors over such n-best lists and their gradient (klstm_ctc_mbr_eval).
+ctc_nbest_consensus: MBR decoding and token / word confidences over such n-best lists (klstm_ctc_consensus).
 CtcMmiDenominator / ctc_mmi_eval: MMI (CTC-CRF) against the language model the beam search uses (klstm_ctc_mmi_eval)."""
 import collections
 import ctypes
@@ -512,6 +513,91 @@ def ctc_mbr_eval(net_out, lens, nbest, refs=None, blank=0, risk_scale=1.0, ctc_w
                                 float(ctc_weight), diff.data_ptr(), diff.stride(0), risk.data_ptr(), hyp_logp.data_ptr(), hyp_post.data_ptr(),
                                 _ptr(ref_loss), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
     return CtcMbrResult(risk, diff, hyp_logp, hyp_post, ref_loss)
+
+
+CtcConsensusResult = collections.namedtuple("CtcConsensusResult", "pick map mbr post risk unit_len conf dist")
+
+
+def ctc_consensus_workspace_bytes(S, list_n, max_len, word_mode=False):
+    return _workspace_bytes("klstm_ctc_consensus_workspace_bytes", S, list_n, max_len, 1 if word_mode else 0)
+
+
+def ctc_nbest_consensus(nbest, logp=None, scale=1.0, separator=None, pivot="mbr", errors=None, max_len=None, want_dist=False, totals=None,
+                        stream=None):
+    """Minimum Bayes risk decoding and unit confidences over n-best lists (klstm_ctc_consensus of include/klstm.h, which defines every
+    quantity).  nbest: the CtcBeamResult of ctc_beam_decode, or a tuple (hyp [S, N, stride] int32, hyp_len [S, N], nbest_count [S],
+    errors [S, N] or None) of CUDA tensors as ctc_mbr_eval takes it; logp [S, N] float32: the natural-log weights of the entries (None:
+    the result's score; ctc_mbr_eval(...).hyp_logp are the exact ones); scale multiplies them; separator: None for token units, or
+    the class that separates words (the lists of a lexicon_label_lm search); pivot: "map" or "mbr"; errors: None (the result's, if it
+    has them) or [S, N] int32; max_len: the token capacity (None: min(1023, stride)).  Returns CtcConsensusResult(pick, map, mbr [S]
+    int32 (-1: idle or rejected), post [S, N] float32, risk [S, N] float32 (-1: dropped), unit_len [S, N] int32, conf [S, stride]
+    float32 (valid up to unit_len[s, pick[s]]), dist [S, N, N] int32 or None without want_dist).  totals: a float64[10] CUDA tensor that
+    streams done, streams idle or rejected, sum of R[pick], sum of R[map], streams with mbr != map, the picks' units, sum of conf over
+    them, entries dropped, sum of errors[pick] and sum of errors[map] are added to.  Nothing synchronises; consensus_to_lists() does."""
+    import torch
+    lib = load_library()
+    if isinstance(nbest, CtcBeamResult):
+        hyp, hyp_len, count, own_errors, score = nbest.hyp, nbest.hyp_len, nbest.nbest_count, nbest.errors, nbest.score
+    else:
+        (hyp, hyp_len, count, own_errors), score = nbest, None
+    if logp is None:
+        logp = score
+    assert logp is not None, "a tuple of lists carries no scores: pass logp"
+    if errors is None:
+        errors = own_errors
+    dev = hyp.device
+    for t in (hyp, hyp_len, count) + ((errors,) if errors is not None else ()):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    assert hyp.dim() == 3 and count.numel() == hyp.shape[0]
+    S, N, stride = (int(v) for v in hyp.shape)
+    assert hyp_len.shape == (S, N) and (errors is None or errors.shape == (S, N))
+    assert logp.is_cuda and logp.dtype == torch.float32 and logp.shape == (S, N) and logp.is_contiguous()
+    assert pivot in ("map", "mbr")
+    sep = -1 if separator is None else int(separator)
+    assert separator is None or sep >= 0, "the separator is a class"
+    if max_len is None:
+        max_len = min(1023, stride)
+    max_len = int(max_len)
+    _check_totals(totals, 10)
+    nbytes = ctc_consensus_workspace_bytes(S, N, max_len, sep >= 0)
+    ws = _workspace("consensus", (S, N, max_len, sep >= 0), nbytes, dev)
+    pick, imap, imbr = (torch.empty(S, dtype=torch.int32, device=dev) for _ in range(3))
+    post, risk = torch.empty(S, N, device=dev), torch.empty(S, N, device=dev)
+    unit_len = torch.empty(S, N, dtype=torch.int32, device=dev)
+    conf = torch.zeros(S, max(stride, 1), device=dev)
+    dist = torch.empty(S, N, N, dtype=torch.int32, device=dev) if want_dist else None
+    _chk(lib.klstm_ctc_consensus(hyp.data_ptr(), max(stride, 1), hyp_len.data_ptr(), count.data_ptr(), logp.data_ptr(), _ptr(errors), S, N, max_len,
+                                 float(scale), sep, 1 if pivot == "mbr" else 0, pick.data_ptr(), imap.data_ptr(), imbr.data_ptr(),
+                                 post.data_ptr(), risk.data_ptr(), unit_len.data_ptr(), conf.data_ptr(), conf.stride(0), _ptr(dist),
+                                 _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    return CtcConsensusResult(pick, imap, imbr, post, risk, unit_len, conf, dist)
+
+
+def consensus_to_lists(result, nbest, separator=None):
+    """CtcConsensusResult and the lists it was computed from -> per stream None (idle or rejected), or a dict(pick, units: a list of
+    (unit, confidence) with unit a token (separator None) or the list of a word's tokens, risk: the pick's expected unit errors).  The
+    one place that synchronises."""
+    hyp, hyp_len = (nbest.hyp, nbest.hyp_len) if isinstance(nbest, CtcBeamResult) else nbest[:2]
+    h, n = hyp.cpu().numpy(), hyp_len.cpu().numpy()
+    pick, risk, conf = result.pick.cpu().numpy(), result.risk.cpu().numpy(), result.conf.cpu().numpy()
+    out = []
+    for s, p in enumerate(pick):
+        if p < 0:
+            out.append(None)
+            continue
+        toks = h[s, p, :n[s, p]].tolist()
+        if separator is None:
+            units = toks
+        else:
+            units, word = [], []
+            for t in toks + [int(separator)]:
+                if t != int(separator):
+                    word.append(t)
+                elif word:
+                    units.append(word)
+                    word = []
+        out.append(dict(pick=int(p), units=[(u, float(conf[s, i])) for i, u in enumerate(units)], risk=float(risk[s, p])))
+    return out
 
 
 CtcMmiResult = collections.namedtuple("CtcMmiResult", "loss diff num_logp den_logz lm_logw")
