@@ -665,6 +665,68 @@ klstm_status klstm_ctc_consensus(const int *hyp_dev, int hyp_stride, const int *
                                  float *conf_dev, int conf_stride, int *dist_dev, double *totals_dev, void *workspace, size_t workspace_bytes,
                                  void *hip_stream);
 
+/* Second-pass rescoring of CTC n-best lists with token and word back-off language models (include/klstm_nnet.hpp class CtcRescorer;
+ * Python ctc_nbest_rescore; the definition is tests/ctc_rescore_ref.py): the stage between
+ * klstm_ctc_beam_decode* and klstm_ctc_consensus -- re-rank the list with a model too large, or of the wrong kind, to fuse into the
+ * search.  Stateless, asynchronous on hip_stream, decided entirely on the device; nothing is read back.  Both models are blobs of
+ * klstm_ctc_slm_build, known by their addresses.  For stream s, over its entries q < nbest_count[s]:
+ *   WELL FORMED      logp finite, 0 <= hyp_len <= min(hyp_stride, max_len), every token in [0, K).  Every other listed entry is
+ *                    DROPPED and counted; tokens are range-checked before any lookup
+ *   units            num_words = 0: the tokens.  num_words > 0: the words, the maximal runs of tokens other than `separator` (leading,
+ *                    trailing and repeated separators make no empty word), known by the 64-bit key klstm_ctc_consensus knows them by
+ *   word table       word_keys_dev [num_words] ascending, word_ids_dev [num_words]: the class of a word in the word model.  The key k is
+ *                    looked up by lo = 0, hi = W; while lo < hi: mid = (lo + hi) >> 1, key[mid] < k ? lo = mid + 1 : hi = mid; a hit
+ *                    iff lo < W and key[lo] = k.  A word is OUT OF VOCABULARY on a miss, on a class outside [0, add_classes) and on
+ *                    the class add_reserved (the `blank` the word model was built with); it takes unk_id, and with unk_id < 0 it
+ *                    FORBIDS the entry.  An unsorted table can only produce misses
+ *   logw(model)      from state 0 and (m, e) = (1.0, 0), per unit u: (g, next) = the model's lookup (sparse_lm_lookup of lm.py, bit for
+ *                    bit), gf = flush(g) (NaN or below 2^-60: 0, above 2^60: 2^60); gf = 0 or next outside [0, states) FORBIDS the
+ *                    entry; else (m, de) = frexp(m * (double)gf), e += de, state = next.  With final weights flush(final[state])
+ *                    enters the same way after the last unit.  logw = log(m) + (double)e * 0.6931471805599453
+ *   sub              NULL, or a model over the K tokens: the one the first pass fused; its logw is taken OUT of logp
+ *   add              NULL, or a model over the K tokens (num_words = 0, add_classes = K) or over the words (add_classes = V <= 32768
+ *                    classes, one of them reserved: a word vocabulary holds at most 32767 words)
+ *   z_q              (double)am_scale * (double)logp_q - logw_sub + (double)add_scale * logw_add + (double)unit_bonus * units_q,
+ *                    left to right, one IEEE double operation each; an absent model contributes nothing
+ *   ranking          the entries neither dropped nor forbidden, by z descending, ties to the lower q
+ *   hyp_dev, hyp_stride, hyp_len_dev [S*N], nbest_count_dev [S], logp_dev [S*N], errors_dev (NULL ok), list_n = N
+ *                        the arrays of klstm_ctc_beam_decode as klstm_ctc_consensus takes them.  Slots q >= nbest_count[s] are NOT READ
+ *   order_dev [S*N]      the entry of rank r; -1 from live_count[s] on, and everywhere on an idle or rejected stream
+ *   live_count_dev [S]   the entries ranked
+ *   score_dev [S*N]      float(z_q); -inf for a dropped, forbidden or unlisted entry
+ *   add_logp_dev, sub_logp_dev   NULL, or [S*N]: float(logw), 0 for an absent model, -inf where the model forbids and for a dropped or
+ *                        unlisted entry
+ *   units_dev, oov_dev   NULL, or [S*N] ints: the units of the entry and how many of its words are out of vocabulary (0 for a dropped
+ *                        or unlisted entry)
+ *   out_n                0, or 1 <= out_n <= N: the first min(live, out_n) entries of the ranking are written in the layout
+ *                        klstm_ctc_consensus and klstm_ctc_mbr_eval read -- out_hyp_dev [S*out_n*out_stride] (the tokens, copied),
+ *                        out_len_dev, out_score_dev = float(z), out_errors_dev (NULL ok; -1 without errors_dev) [S*out_n], out_count_dev
+ *                        [S]; slots beyond the count are left alone.  out_stride >= min(hyp_stride, max_len)
+ *   totals_dev           NULL, or eight doubles that this minibatch is ADDED to, streams in order: streams done, streams idle or
+ *                        rejected, entries dropped, entries forbidden, streams whose 1-best changed, sum of errors of the first pass's
+ *                        entry 0, sum of errors of the new 1-best (both over the done streams, 0 without errors_dev; the first is
+ *                        errors[s*N] whatever became of entry 0: it is read even where that entry was dropped or forbidden), words
+ *                        out of vocabulary
+ *   workspace            klstm_ctc_rescore_workspace_bytes(S, list_n, max_len, num_words > 0) bytes, 16-byte aligned.  One call at a
+ *                        time per workspace
+ * STATUS of a stream: REJECTED with nbest_count[s] outside [0, N]; IDLE with a count of 0 or no rankable entry; done otherwise.
+ * Bit-identical from run to run: no floating-point atomics.
+ * Limits: 1 <= S <= 32, 1 <= list_n <= 64, 0 <= max_len <= 1023, 2 <= K <= 32768, 0 <= num_words <= 2^24, 0 <= out_n <= list_n; beyond
+ * them KLSTM_ERR_SHAPE and nothing is launched (klstm_ctc_rescore_workspace_bytes answers 0 and leaves the message in
+ * klstm_last_error(); neither touches a device then).  A null required pointer, a small or misaligned workspace, a non-finite scale,
+ * neither model given, word arguments without `add`, a separator outside [0, K), an unk_id or add_reserved that is no class of the word
+ * model, a model that was not built at its address or for other sizes: KLSTM_ERR_ARG with the outputs untouched. */
+size_t klstm_ctc_rescore_workspace_bytes(int S, int list_n, int max_len, int word_mode);
+klstm_status klstm_ctc_nbest_rescore(const int *hyp_dev, int hyp_stride, const int *hyp_len_dev, const int *nbest_count_dev, const float *logp_dev,
+                                     const int *errors_dev, int S, int list_n, int max_len, int K, const void *sub_slm, size_t sub_bytes,
+                                     int sub_states, const float *sub_final_dev, const void *add_slm, size_t add_bytes, int add_states,
+                                     int add_classes, const float *add_final_dev, const unsigned long long *word_keys_dev,
+                                     const int *word_ids_dev, int num_words, int unk_id, int separator, int add_reserved, float am_scale,
+                                     float add_scale, float unit_bonus, int *order_dev, int *live_count_dev, float *score_dev,
+                                     float *add_logp_dev, float *sub_logp_dev, int *units_dev, int *oov_dev, int out_n, int *out_hyp_dev,
+                                     int out_stride, int *out_len_dev, int *out_count_dev, float *out_score_dev, int *out_errors_dev,
+                                     double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* MMI (CTC-CRF) training against a label language model (include/klstm_nnet.hpp class CtcMmi): the
  * posterior of the reference under the automaton the beam search multiplies in (klstm_ctc_beam_decode_lm's tables), with the normaliser
  * summed exactly over EVERY labelling the automaton accepts.  Stateless apart from the note below, asynchronous on hip_stream, decided

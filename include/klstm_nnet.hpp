@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <istream>
 #include <map>
@@ -1253,8 +1254,9 @@ class CtcConsensus : private CtcCallBase {
 
   // over the lists of the last lists.Decode; logp_dev: [num_stream][nbest] natural-log weights on the device (CtcMbr's log p(h | y),
   // say), null: the search's scores.  Nothing synchronises.
-  void Eval(const CtcBeamDecoder &lists, const BaseFloat *logp_dev = nullptr) {
-    const CtcNbestDevice nb = lists.DeviceLists();
+  void Eval(const CtcBeamDecoder &lists, const BaseFloat *logp_dev = nullptr) { Eval(lists.DeviceLists(), logp_dev); }
+  // ... over any lists in that layout: CtcRescorer::DeviceLists(), the re-ranked ones
+  void Eval(const CtcNbestDevice &nb, const BaseFloat *logp_dev = nullptr) {
     const int32 S = nb.num_stream, N = nb.nbest;
     KLSTM_ASSERT(S > 0 && N > 0 && nb.stride > 0);
     const int32 max_len = max_len_ > 0 ? max_len_ : std::min<int32>(1023, nb.stride);
@@ -1317,6 +1319,158 @@ class CtcConsensus : private CtcCallBase {
   int32 separator_, max_len_, nbest_ = 0, stride_ = 0;
   DeviceBuffer idx_, post_, risk_, ulen_, conf_;
   DeviceTotals<10> tot_;
+};
+
+// The key a word is known by on the device (klstm_ctc_consensus, klstm_ctc_nbest_rescore; word_key of kaldi-lstm_amd/lm.py): the hash the
+// beam search knows its prefixes by, folded over the word's tokens.
+inline uint64_t CtcWordKey(const std::vector<int32> &tokens) {
+  uint64_t h = 0x243F6A8885A308D3ull;
+  for (int32 c : tokens) {
+    const uint64_t x = (h ^ (uint64_t)(uint32_t)(c + 1)) * 0x9E3779B97F4A7C15ull;
+    h = x ^ (x >> 29);
+  }
+  return h;
+}
+
+// The word table of a CtcRescorer on the device (klstm_ctc_nbest_rescore, klstm.h): the words of a vocabulary, each a
+// non-empty run of token classes other than the separator, with the class of each in the word model (empty ids: its position), sorted
+// by key.  unk_id: the class an unknown word takes (negative: it forbids the entry).  Two words that share a key are an error.
+class CtcWordTable {
+ public:
+  CtcWordTable(const std::vector<std::vector<int32> > &words, int32 separator, int32 unk_id, const std::vector<int32> &ids = std::vector<int32>())
+      : unk_id_(unk_id), separator_(separator) {
+    KLSTM_ASSERT(!words.empty() && separator >= 0 && (ids.empty() || ids.size() == words.size()));
+    std::map<uint64_t, int32> by_key;
+    for (size_t i = 0; i < words.size(); i++) {
+      KLSTM_ASSERT(!words[i].empty());
+      for (int32 c : words[i]) KLSTM_ASSERT(c >= 0 && c != separator);
+      if (!by_key.insert(std::make_pair(CtcWordKey(words[i]), ids.empty() ? (int32)i : ids[i])).second)
+        KLSTM_ERR("CtcWordTable: word " << i << " shares its key with an earlier word");
+    }
+    for (const auto &kv : by_key) { keys_.push_back(kv.first); ids_.push_back(kv.second); }
+    dkeys_.Upload(keys_);
+    dids_.Upload(ids_);
+  }
+  int32 NumWords() const { return (int32)keys_.size(); }
+  int32 UnkId() const { return unk_id_; }
+  int32 Separator() const { return separator_; }
+  const std::vector<uint64_t> &Keys() const { return keys_; }        // ascending
+  const std::vector<int32> &Ids() const { return ids_; }
+  const unsigned long long *KeysDev() const { return dkeys_.As<unsigned long long>(); }
+  const int32 *IdsDev() const { return dids_.As<int32>(); }
+ private:
+  int32 unk_id_, separator_;
+  std::vector<uint64_t> keys_;
+  std::vector<int32> ids_;
+  DeviceBuffer dkeys_, dids_;
+};
+
+// Second-pass rescoring of the n-best lists of a CtcBeamDecoder (klstm_ctc_nbest_rescore, klstm.h, which defines every quantity;
+// INTEGRATION.md 3n): the score of `sub`, the token model the first pass fused, is taken out and the score of `add` is put in -- a
+// token model, or with a word table a model over word classes whose reserved class is add_reserved, the blank it was built with.  The
+// re-ranked lists stay on the device in the layout of the search's (DeviceLists(): CtcConsensus::Eval and CtcMbr take them); the eight
+// totals stay there too and are read when somebody asks.  The models and the table are not owned.
+class CtcRescorer : private CtcCallBase {
+ public:
+  // num_classes: the token classes K; either model may be null, not both; max_len: the token capacity, 0: min(1023, the lists' stride)
+  CtcRescorer(int32 num_classes, const CtcSparseLabelLm *add, const CtcSparseLabelLm *sub, const CtcWordTable *words = nullptr,
+              int32 add_reserved = -1, BaseFloat am_scale = 1.f, BaseFloat add_scale = 1.f, BaseFloat unit_bonus = 0.f, int32 max_len = 0)
+      : CtcCallBase(0), classes_(num_classes), add_(add), sub_(sub), words_(words), add_reserved_(add_reserved), am_scale_(am_scale),
+        add_scale_(add_scale), unit_bonus_(unit_bonus), max_len_(max_len) {
+    KLSTM_ASSERT((add || sub) && (!words || add));
+  }
+  // over the lists of the last lists.Decode.  Nothing synchronises.
+  void Eval(const CtcBeamDecoder &lists) { Eval(lists.DeviceLists()); }
+  void Eval(const CtcNbestDevice &nb) {
+    const int32 S = nb.num_stream, N = nb.nbest;
+    KLSTM_ASSERT(S > 0 && N > 0 && nb.stride > 0 && nb.score);
+    const int32 max_len = max_len_ > 0 ? max_len_ : std::min<int32>(1023, nb.stride);
+    const size_t need = klstm_ctc_rescore_workspace_bytes(S, N, max_len, words_ ? 1 : 0);
+    void *ws = Workspace(need);
+    const size_t SN = (size_t)S * N;
+    order_.Grow(SN * sizeof(int32)); live_.Grow((size_t)S * sizeof(int32)); score_.Grow(SN * sizeof(BaseFloat));
+    addlp_.Grow(SN * sizeof(BaseFloat)); sublp_.Grow(SN * sizeof(BaseFloat)); units_.Grow(SN * sizeof(int32)); oov_.Grow(SN * sizeof(int32));
+    ohyp_.Grow(SN * nb.stride * sizeof(int32)); olen_.Grow(SN * sizeof(int32)); ocnt_.Grow((size_t)S * sizeof(int32));
+    oscore_.Grow(SN * sizeof(BaseFloat)); oerr_.Grow(SN * sizeof(int32));
+    KCheck(klstm_ctc_nbest_rescore(nb.hyp, nb.stride, nb.hyp_len, nb.count, nb.score, nb.errors, S, N, max_len, classes_,
+                                   sub_ ? sub_->Blob() : nullptr, sub_ ? sub_->Bytes() : 0, sub_ ? sub_->NumStates() : 0, sub_ ? sub_->Final() : nullptr,
+                                   add_ ? add_->Blob() : nullptr, add_ ? add_->Bytes() : 0, add_ ? add_->NumStates() : 0,
+                                   add_ ? add_->NumClasses() : 0, add_ ? add_->Final() : nullptr, words_ ? words_->KeysDev() : nullptr,
+                                   words_ ? words_->IdsDev() : nullptr, words_ ? words_->NumWords() : 0, words_ ? words_->UnkId() : -1,
+                                   words_ ? words_->Separator() : -1, words_ ? add_reserved_ : -1, am_scale_, add_scale_, unit_bonus_,
+                                   order_.As<int32>(), live_.As<int32>(), score_.As<BaseFloat>(), addlp_.As<BaseFloat>(), sublp_.As<BaseFloat>(),
+                                   units_.As<int32>(), oov_.As<int32>(), N, ohyp_.As<int32>(), nb.stride, olen_.As<int32>(), ocnt_.As<int32>(),
+                                   oscore_.As<BaseFloat>(), nb.errors ? oerr_.As<int32>() : nullptr, tot_.Dev(), ws, need, nullptr));
+    num_stream_ = S; nbest_ = N; stride_ = nb.stride; scored_ = nb.errors != nullptr;
+  }
+  // the re-ranked lists of the last Eval on the device, in the layout of CtcBeamDecoder::DeviceLists(); slots beyond a stream's count
+  // hold nothing
+  CtcNbestDevice DeviceLists() const {
+    return CtcNbestDevice{ohyp_.As<int32>(), olen_.As<int32>(), ocnt_.As<int32>(), scored_ ? oerr_.As<int32>() : nullptr, num_stream_, nbest_, stride_,
+                          oscore_.As<BaseFloat>()};
+  }
+  // of the last Eval (each synchronises): the re-ranked list of every stream, best first, with the new scores
+  void Lists(std::vector<CtcNbestList> *lists) const {
+    const size_t SN = (size_t)num_stream_ * nbest_;
+    std::vector<int32> c(num_stream_), n(SN), h(SN * stride_), e(SN, -1);
+    std::vector<BaseFloat> sc(SN);
+    ocnt_.Download(c.data(), c.size()); olen_.Download(n.data(), n.size()); ohyp_.Download(h.data(), h.size());
+    oscore_.Download(sc.data(), sc.size());
+    if (scored_) oerr_.Download(e.data(), e.size());
+    lists->assign(num_stream_, CtcNbestList());
+    for (int32 s = 0; s < num_stream_; s++)
+      for (int32 q = 0; q < c[s]; q++) {
+        const size_t o = (size_t)s * nbest_ + q;
+        CtcHypothesis hy;
+        hy.tokens.assign(h.begin() + o * stride_, h.begin() + o * stride_ + n[o]);
+        hy.score = sc[o];
+        hy.errors = e[o];
+        (*lists)[s].push_back(hy);
+      }
+  }
+  // ... the entry of the search's list at every rank [num_stream][nbest] (-1 beyond the entries ranked) and how many were ranked
+  void Order(std::vector<int32> *order, std::vector<int32> *live = nullptr) const {
+    order->assign((size_t)num_stream_ * nbest_, -1);
+    order_.Download(order->data(), order->size());
+    if (live) { live->assign(num_stream_, 0); live_.Download(live->data(), live->size()); }
+  }
+  // ... per entry of the search's list [num_stream][nbest]: the new score (-inf: dropped, forbidden or unlisted), the log weights of
+  // `add` and `sub`, the units and the words out of vocabulary (any may be null)
+  void Entries(std::vector<BaseFloat> *score, std::vector<BaseFloat> *add_logp = nullptr, std::vector<BaseFloat> *sub_logp = nullptr,
+               std::vector<int32> *units = nullptr, std::vector<int32> *oov = nullptr) const {
+    const size_t SN = (size_t)num_stream_ * nbest_;
+    if (score) { score->assign(SN, 0.f); score_.Download(score->data(), SN); }
+    if (add_logp) { add_logp->assign(SN, 0.f); addlp_.Download(add_logp->data(), SN); }
+    if (sub_logp) { sub_logp->assign(SN, 0.f); sublp_.Download(sub_logp->data(), SN); }
+    if (units) { units->assign(SN, 0); units_.Download(units->data(), SN); }
+    if (oov) { oov->assign(SN, 0); oov_.Download(oov->data(), SN); }
+  }
+  // over the streams rescored so far
+  double NumUtterances() const { return tot_.Read()[0]; }
+  double NumChanged() const { return tot_.Read()[4]; }                 // streams whose 1-best is no longer the search's
+  double NumFirstPassErrors() const { return tot_.Read()[5]; }         // edit errors of the search's 1-best (lists decoded with references)
+  double NumRescoredErrors() const { return tot_.Read()[6]; }          // ... of the new 1-best
+  double NumDropped() const { return tot_.Read()[2]; }
+  double NumForbidden() const { return tot_.Read()[3]; }
+  double NumOovWords() const { return tot_.Read()[7]; }
+  std::string Report() const {
+    const double *h = tot_.Read();
+    std::ostringstream oss;
+    oss << "RESCORED: " << h[4] << " of " << h[0] << " 1-bests changed, errors " << h[5] << " -> " << h[6] << " [" << (words_ ? "words" : "tokens")
+        << ", " << h[1] << " idle or rejected, " << h[2] << " entries dropped, " << h[3] << " forbidden, " << h[7] << " words out of vocabulary]"
+        << std::endl;
+    return oss.str();
+  }
+ private:
+  int32 classes_;
+  const CtcSparseLabelLm *add_, *sub_;
+  const CtcWordTable *words_;
+  int32 add_reserved_;
+  BaseFloat am_scale_, add_scale_, unit_bonus_;
+  int32 max_len_, nbest_ = 0, stride_ = 0;
+  bool scored_ = false;
+  DeviceBuffer order_, live_, score_, addlp_, sublp_, units_, oov_, ohyp_, olen_, ocnt_, oscore_, oerr_;
+  DeviceTotals<8> tot_;
 };
 
 struct TrainMbrOptions {
@@ -1485,6 +1639,8 @@ struct DecodeCtcOptions {
                                                          // confidences, 2 the MBR entry is the hypothesis
   BaseFloat consensus_scale = 1.f;                       // multiplies the search's scores under the lists' posterior
   int32 separator = -1;                                  // -1: errors and confidences per token; otherwise the class that separates words
+  CtcRescorer *rescorer = nullptr;                       // beam > 0 only: runs on each minibatch's lists before the consensus step, which then
+                                                         // sees the re-ranked lists, as do hypotheses and nbest_lists; not owned; null: none
 };
 struct DecodeCtcStats {
   int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
@@ -1493,6 +1649,9 @@ struct DecodeCtcStats {
   // with o.consensus only: expected unit errors per utterance of the hypotheses returned and of the MAP entries under the lists'
   // posteriors, the mean confidence of the units returned, the edit errors of the hypotheses returned (scored passes)
   double expected_errors = 0, map_expected_errors = 0, mean_confidence = 0, num_pick_errors = 0;
+  // with o.rescorer only, over this pass: the token error rates of the search's 1-bests and of the rescored ones (scored passes) and
+  // the utterances whose 1-best changed
+  double first_pass_token_error_rate = 0, rescored_token_error_rate = 0, num_changed_1best = 0;
 };
 
 // per-stream results of one minibatch -> per-utterance results in the order of the utterance list (idle streams carry nothing)
@@ -1520,7 +1679,9 @@ inline void FillDecodeCtcStats(const Decoder &dec, DecodeCtcStats *st, std::stri
 // (*nbest_lists)[i] its whole list with scores and edit distances (either may be null; both empty for a skipped utterance).
 // every_batch sees (batch, net_out, CtcBeamDecoder) after Decode.  With o.consensus (1 or 2) a CtcConsensus runs over the lists of
 // every minibatch: (*hypotheses)[i] is then the entry it answers with (the MAP or the MBR one), (*confidences)[i] (may be null) holds
-// one confidence per token or word of it, and the statistics and the report carry the expected errors.
+// one confidence per token or word of it, and the statistics and the report carry the expected errors.  With o.rescorer the lists of
+// every minibatch are re-ranked first (CtcRescorer::Eval): hypotheses, nbest_lists and the consensus then see the re-ranked lists, and
+// the statistics carry the error rates before and after; null leaves the loop as it was.
 template <class F>
 inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
                                                std::vector<std::vector<int32> > *hypotheses, std::vector<CtcNbestList> *nbest_lists,
@@ -1537,12 +1698,18 @@ inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utt
   if (hypotheses) hypotheses->assign(utts.size(), std::vector<int32>());
   if (nbest_lists) nbest_lists->assign(utts.size(), CtcNbestList());
   if (confidences) confidences->assign(utts.size(), std::vector<BaseFloat>());
+  const double resc0[3] = {o.rescorer ? o.rescorer->NumChanged() : 0, o.rescorer ? o.rescorer->NumFirstPassErrors() : 0,
+                           o.rescorer ? o.rescorer->NumRescoredErrors() : 0};          // the rescorer may have seen other passes
   DecodeCtcStats st = ForEachWholeUtteranceBatch<DecodeCtcStats>(nnet, utts, o.num_stream, o.sort_by_length, o.max_frames,
       [&](const UtteranceBatch &b, const DeviceMatrix &nnet_out) {
-        dec.Decode(nnet_out, b.num_stream, b.lens, o.score ? b.labels : none, want ? &lists : nullptr);
+        dec.Decode(nnet_out, b.num_stream, b.lens, o.score ? b.labels : none, want && !o.rescorer ? &lists : nullptr);
+        if (o.rescorer) {
+          o.rescorer->Eval(dec);
+          if (want) o.rescorer->Lists(&lists);
+        }
         std::vector<int32> pick(b.num_stream, 0);          // without a consensus: the head of the list
         if (o.consensus) {
-          cons.Eval(dec);
+          if (o.rescorer) cons.Eval(o.rescorer->DeviceLists()); else cons.Eval(dec);
           if (hypotheses) cons.Picks(&pick);
           if (confidences) {
             std::vector<std::vector<BaseFloat> > conf;
@@ -1567,6 +1734,14 @@ inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utt
     st.mean_confidence = cons.MeanConfidence();
     st.num_pick_errors = cons.NumPickErrors();
     if (report) *report += "\n" + cons.Report();
+  }
+  if (o.rescorer) {
+    st.num_changed_1best = o.rescorer->NumChanged() - resc0[0];
+    if (st.num_ref_tokens > 0) {
+      st.first_pass_token_error_rate = (o.rescorer->NumFirstPassErrors() - resc0[1]) / st.num_ref_tokens;
+      st.rescored_token_error_rate = (o.rescorer->NumRescoredErrors() - resc0[2]) / st.num_ref_tokens;
+    }
+    if (report) *report += "\n" + o.rescorer->Report();
   }
   return st;
 }

@@ -144,6 +144,11 @@ def load_library():
     lib.klstm_ctc_consensus_workspace_bytes.argtypes = [I, I, I, I]
     lib.klstm_ctc_consensus_workspace_bytes.restype = ctypes.c_size_t
     lib.klstm_ctc_consensus.argtypes = [P, I, P, P, P, P, I, I, I, ctypes.c_float, I, I, P, P, P, P, P, P, P, I, P, P, P, ctypes.c_size_t, P]
+    lib.klstm_ctc_rescore_workspace_bytes.argtypes = [I, I, I, I]
+    lib.klstm_ctc_rescore_workspace_bytes.restype = ctypes.c_size_t
+    lib.klstm_ctc_nbest_rescore.argtypes = [P, I, P, P, P, P, I, I, I, I, P, ctypes.c_size_t, I, P, P, ctypes.c_size_t, I, I, P, P, P, I, I, I, I,
+                                            ctypes.c_float, ctypes.c_float, ctypes.c_float, P, P, P, P, P, P, P, I, P, I, P, P, P, P, P, P,
+                                            ctypes.c_size_t, P]
     lib.klstm_ctc_mmi_graph_bytes.argtypes = [I, I]
     lib.klstm_ctc_mmi_graph_bytes.restype = ctypes.c_size_t
     lib.klstm_ctc_mmi_graph_build.argtypes = [I, I, I, P, P, P, P, ctypes.c_size_t, P]

@@ -2502,6 +2502,70 @@ klstm_status klstm_ctc_consensus(const int *hyp_dev, int hyp_stride, const int *
                               totals_dev, workspace, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
+// ---- second-pass rescoring of n-best lists.  The models are blobs of klstm_ctc_slm_build, known by their addresses ----
+static bool ctc_rescore_shape_ok(int S, int list_n, int max_len) {
+  return S >= 1 && S <= 32 && list_n >= 1 && list_n <= 64 && max_len >= 0 && max_len <= 1023;
+}
+size_t klstm_ctc_rescore_workspace_bytes(int S, int list_n, int max_len, int word_mode) {
+  if (!ctc_rescore_shape_ok(S, list_n, max_len)) {
+    fail(KLSTM_ERR_SHAPE, "klstm_ctc_rescore_workspace_bytes: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", S, list_n, max_len);
+    return 0;
+  }
+  return ctc_rescore_workspace_bytes(S, list_n, max_len, word_mode != 0);
+}
+klstm_status klstm_ctc_nbest_rescore(const int *hyp_dev, int hyp_stride, const int *hyp_len_dev, const int *nbest_count_dev, const float *logp_dev,
+                                     const int *errors_dev, int S, int list_n, int max_len, int K, const void *sub_slm, size_t sub_bytes,
+                                     int sub_states, const float *sub_final_dev, const void *add_slm, size_t add_bytes, int add_states,
+                                     int add_classes, const float *add_final_dev, const unsigned long long *word_keys_dev,
+                                     const int *word_ids_dev, int num_words, int unk_id, int separator, int add_reserved, float am_scale,
+                                     float add_scale, float unit_bonus, int *order_dev, int *live_count_dev, float *score_dev,
+                                     float *add_logp_dev, float *sub_logp_dev, int *units_dev, int *oov_dev, int out_n, int *out_hyp_dev,
+                                     int out_stride, int *out_len_dev, int *out_count_dev, float *out_score_dev, int *out_errors_dev,
+                                     double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  const char *fn = "klstm_ctc_nbest_rescore";
+  if (!ctc_rescore_shape_ok(S, list_n, max_len))                   // (every limit before any pointer)
+    return fail(KLSTM_ERR_SHAPE, "%s: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", fn, S, list_n, max_len);
+  if (K < 2 || K > 32768) return fail(KLSTM_ERR_SHAPE, "%s: %d classes outside 2 <= K <= 32768", fn, K);
+  if (num_words < 0 || num_words > (1 << 24)) return fail(KLSTM_ERR_SHAPE, "%s: %d words outside 0 <= words <= 2^24", fn, num_words);
+  if (out_n < 0 || out_n > list_n) return fail(KLSTM_ERR_SHAPE, "%s: a list of %d out of a list of %d", fn, out_n, list_n);
+  if (!hyp_dev || !hyp_len_dev || !nbest_count_dev || !logp_dev || !order_dev || !live_count_dev || !score_dev || !workspace)
+    return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
+  if (out_n >= 1 && (!out_hyp_dev || !out_len_dev || !out_count_dev || !out_score_dev))
+    return fail(KLSTM_ERR_ARG, "%s: null list output with out_n %d", fn, out_n);
+  if (hyp_stride <= 0 || (out_n >= 1 && out_stride < (hyp_stride < max_len ? hyp_stride : max_len)))
+    return fail(KLSTM_ERR_ARG, "%s: hypothesis stride %d, output stride %d (at least min(hypothesis stride, length %d))", fn, hyp_stride, out_stride, max_len);
+  if (!std::isfinite(am_scale) || !std::isfinite(add_scale) || !std::isfinite(unit_bonus))
+    return fail(KLSTM_ERR_ARG, "%s: scales %g, %g and bonus %g must be finite", fn, (double)am_scale, (double)add_scale, (double)unit_bonus);
+  if (!sub_slm && !add_slm) return fail(KLSTM_ERR_ARG, "%s: neither a model to subtract nor one to add", fn);
+  if (num_words > 0 && !add_slm) return fail(KLSTM_ERR_ARG, "%s: a word table without a model to add", fn);
+  if (num_words > 0) {
+    if (!word_keys_dev || !word_ids_dev) return fail(KLSTM_ERR_ARG, "%s: null word table", fn);
+    if (separator < 0 || separator >= K) return fail(KLSTM_ERR_ARG, "%s: separator %d outside [0, %d)", fn, separator, K);
+    if (add_reserved < 0 || add_reserved >= add_classes || unk_id >= add_classes || unk_id == add_reserved)
+      return fail(KLSTM_ERR_ARG, "%s: reserved class %d, unknown-word class %d with %d word classes", fn, add_reserved, unk_id, add_classes);
+  } else if (add_slm && add_classes != K) {
+    return fail(KLSTM_ERR_ARG, "%s: a token-level model of %d classes over %d classes", fn, add_classes, K);
+  }
+  if (sub_slm) {
+    const char *f = ctc_slm_finding(sub_slm, sub_bytes, sub_states, K);
+    if (f) return fail(KLSTM_ERR_ARG, "%s: sub: %s", fn, f);
+  }
+  if (add_slm) {
+    const char *f = ctc_slm_finding(add_slm, add_bytes, add_states, add_classes);
+    if (f) return fail(KLSTM_ERR_ARG, "%s: add: %s", fn, f);
+  }
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
+  const size_t need = ctc_rescore_workspace_bytes(S, list_n, max_len, num_words > 0);
+  if (workspace_bytes < need)
+    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_rescore_workspace_bytes(%d, %d, %d, %d) = %zu", fn, workspace_bytes,
+                S, list_n, max_len, (int)(num_words > 0), need);
+  HIPCHK(launch_ctc_rescore(hyp_dev, hyp_stride, hyp_len_dev, nbest_count_dev, logp_dev, errors_dev, S, list_n, max_len, K, sub_slm, sub_states,
+                            sub_final_dev, add_slm, add_states, add_classes, add_final_dev, word_keys_dev, word_ids_dev, num_words, unk_id,
+                            separator, add_reserved, am_scale, add_scale, unit_bonus, order_dev, live_count_dev, score_dev, add_logp_dev,
+                            sub_logp_dev, units_dev, oov_dev, out_n, out_hyp_dev, out_stride, out_len_dev, out_count_dev, out_score_dev,
+                            out_errors_dev, totals_dev, workspace, (hipStream_t)hip_stream));
+  return KLSTM_OK;
+}
 // ---- MMI against a label-LM denominator.  What a graph was built for is remembered per address: the header lives on the device and
 // the calls do not wait for it, so klstm_ctc_mmi_eval knows a graph by where klstm_ctc_mmi_graph_build put it ----
 struct MmiGraphNote { int Q, K, blank; };

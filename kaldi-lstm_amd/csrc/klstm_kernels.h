@@ -383,6 +383,18 @@ hipError_t launch_ctc_consensus(const int *hyp, int hyp_stride, const int *hyp_l
                                 int S, int N, int max_len, float scale, int separator, int pivot_mode, int *pick, int *map, int *mbr,
                                 float *post, float *risk, int *unit_len, float *conf, int conf_stride, int *dist, double *totals,
                                 void *workspace, hipStream_t st);
+// Second-pass rescoring of CTC n-best lists with sparse back-off models over tokens and words (klstm_ctc_rescore.hip):
+// klstm_ctc_nbest_rescore / klstm_ctc_rescore_workspace_bytes of include/klstm.h.  sub, add: blobs of launch_ctc_slm_build or null;
+// num_words 0: `add` is over the tokens.  The workspace: per entry its state, its unknown words and its score in double, per stream
+// its status and statistics.
+size_t ctc_rescore_workspace_bytes(int S, int N, int max_len, int words);
+hipError_t launch_ctc_rescore(const int *hyp, int hyp_stride, const int *hyp_len, const int *count, const float *logp, const int *errors,
+                              int S, int N, int max_len, int K, const void *sub, int sub_states, const float *sub_final, const void *add,
+                              int add_states, int add_classes, const float *add_final, const unsigned long long *word_keys,
+                              const int *word_ids, int num_words, int unk_id, int separator, int add_reserved, float am_scale,
+                              float add_scale, float unit_bonus, int *order, int *live_count, float *score, float *add_logp,
+                              float *sub_logp, int *units, int *oov, int out_n, int *out_hyp, int out_stride, int *out_len,
+                              int *out_count, float *out_score, int *out_errors, double *totals, void *workspace, hipStream_t st);
 // MMI (CTC-CRF) against a label-LM denominator (klstm_ctc_mmi.hip): klstm_ctc_mmi_graph_build / klstm_ctc_mmi_eval of include/klstm.h.
 // The graph: the reachable denominator states of Q LM states x K classes with their arcs by source and by destination.  The
 // workspace: statuses and log weights per stream, the reference's links and rows as klstm_ctc_eval keeps them, then the

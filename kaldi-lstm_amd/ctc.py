@@ -9,6 +9,7 @@ CtcBeamStream: the same search fed chunk by chunk, the beam kept on the device b
 INTEGRATION.md 3j).
 ctc_mbr_eval: the expected token errors over such n-best lists and their gradient (klstm_ctc_mbr_eval).
 ctc_nbest_consensus: MBR decoding and token / word confidences over such n-best lists (klstm_ctc_consensus).
+ctc_nbest_rescore: such lists re-ranked with token and word back-off models, between the two (klstm_ctc_nbest_rescore).
 CtcMmiDenominator / ctc_mmi_eval: MMI (CTC-CRF) against the language model the beam search uses (klstm_ctc_mmi_eval)."""
 import collections
 import ctypes
@@ -333,8 +334,18 @@ def ctc_beam_decode(net_out, lens, blank=0, beam=16, cands=8, nbest=1, class_wei
     return CtcBeamResult(hyp, hyp_len, count, score, errors)
 
 
+def _as_nbest(nbest):
+    """what ctc_nbest_rescore returned stands for its re-ranked list"""
+    if isinstance(nbest, dict):
+        assert nbest.get("nbest") is not None, "the rescoring was asked for no list (out_n = 0)"
+        return nbest["nbest"]
+    return nbest
+
+
 def nbest_to_lists(result):
-    """CtcBeamResult -> per stream a list of (hypothesis list, score, errors or None), best first.  The one place that synchronises."""
+    """CtcBeamResult (or the dict of ctc_nbest_rescore) -> per stream a list of (hypothesis list, score, errors or None), best first.
+    The one place that synchronises."""
+    result = _as_nbest(result)
     h, n, c, sc = result.hyp.cpu().numpy(), result.hyp_len.cpu().numpy(), result.nbest_count.cpu().numpy(), result.score.cpu().numpy()
     er = result.errors.cpu().numpy() if result.errors is not None else None
     return [[(h[s, q, :n[s, q]].tolist(), float(sc[s, q]), int(er[s, q]) if er is not None else None) for q in range(c[s])]
@@ -483,6 +494,7 @@ def ctc_mbr_eval(net_out, lens, nbest, refs=None, blank=0, risk_scale=1.0, ctc_w
     lib = load_library()
     dev = net_out.device
     lens_dev, S, T, K = _shape(net_out, lens)
+    nbest = _as_nbest(nbest)
     hyp, hyp_len, count, errors = (nbest.hyp, nbest.hyp_len, nbest.nbest_count, nbest.errors) if isinstance(nbest, CtcBeamResult) else nbest
     assert errors is not None, "the n-best lists carry no edit distances (decode with refs)"
     for t in (hyp, hyp_len, count, errors):
@@ -536,6 +548,7 @@ def ctc_nbest_consensus(nbest, logp=None, scale=1.0, separator=None, pivot="mbr"
     them, entries dropped, sum of errors[pick] and sum of errors[map] are added to.  Nothing synchronises; consensus_to_lists() does."""
     import torch
     lib = load_library()
+    nbest = _as_nbest(nbest)
     if isinstance(nbest, CtcBeamResult):
         hyp, hyp_len, count, own_errors, score = nbest.hyp, nbest.hyp_len, nbest.nbest_count, nbest.errors, nbest.score
     else:
@@ -598,6 +611,91 @@ def consensus_to_lists(result, nbest, separator=None):
                     word = []
         out.append(dict(pick=int(p), units=[(u, float(conf[s, i])) for i, u in enumerate(units)], risk=float(risk[s, p])))
     return out
+
+
+class CtcWordTable:
+    """The device arrays of a word table for ctc_nbest_rescore(words=...): keys uint64 [W] ascending and ids int32 [W] as
+    lm.word_table() returns them, the class unk_id an unknown word takes (negative: it forbids the entry) and the separator class."""
+
+    def __init__(self, keys, ids, unk_id, separator, device="cuda"):
+        import torch
+        keys, ids = np.ascontiguousarray(keys, np.uint64), np.ascontiguousarray(ids, np.int32)
+        assert keys.ndim == 1 and keys.shape == ids.shape and keys.size >= 1
+        self.keys = torch.from_numpy(keys.view(np.int64)).to(device)               # the bits; the device reads them unsigned
+        self.ids = torch.from_numpy(ids).to(device)
+        self.words, self.unk_id, self.separator = int(keys.size), int(unk_id), int(separator)
+        assert self.separator >= 0, "the separator is a class"
+
+
+def ctc_rescore_workspace_bytes(S, list_n, max_len, word_mode=False):
+    return _workspace_bytes("klstm_ctc_rescore_workspace_bytes", S, list_n, max_len, 1 if word_mode else 0)
+
+
+def ctc_nbest_rescore(nbest, add=None, sub=None, words=None, am_scale=1.0, add_scale=1.0, unit_bonus=0.0, out_n=None, max_len=None,
+                      totals=None, stream=None, logp=None, out_stride=None, classes=None):
+    """Second-pass rescoring of n-best lists (klstm_ctc_nbest_rescore of include/klstm.h, which defines every quantity).  nbest: the
+    CtcBeamResult of ctc_beam_decode, or a tuple (hyp [S, N, stride] int32, hyp_len [S, N], nbest_count [S], errors [S, N] or None) of
+    CUDA tensors with logp [S, N] float32 given.  sub: None, or the CtcSparseLabelLm the first pass fused, whose score is taken out;
+    add: None, or the CtcSparseLabelLm whose score is put in -- over the tokens, or with words (a CtcWordTable) over the words, its
+    reserved class being the blank it was built with.  z = am_scale * logp - logw(sub) + add_scale * logw(add) + unit_bonus * units.
+    out_n: how many entries of the ranking the re-ranked list keeps (None: N; 0: none); classes: the token classes K (None: sub's, or
+    a token-level add's).  Returns a dict: order [S, N] int32 (the entry of rank r, -1 beyond live_count), live_count [S], score [S, N]
+    float32 (-inf: dropped, forbidden or unlisted), add_logp, sub_logp [S, N] float32, units, oov [S, N] int32, and nbest: the
+    re-ranked list as a CtcBeamResult (None with out_n = 0); ctc_nbest_consensus, ctc_mbr_eval and nbest_to_lists take the dict in
+    place of the search's result.  totals: a float64[8] CUDA tensor that streams done, streams idle or rejected, entries dropped,
+    entries forbidden, streams whose 1-best changed, the errors of the first pass's 1-best, the errors of the new 1-best and words out
+    of vocabulary are added to.  Nothing synchronises."""
+    import torch
+    lib = load_library()
+    if isinstance(nbest, CtcBeamResult):
+        hyp, hyp_len, count, errors, score = nbest.hyp, nbest.hyp_len, nbest.nbest_count, nbest.errors, nbest.score
+    else:
+        (hyp, hyp_len, count, errors), score = nbest, None
+    if logp is None:
+        logp = score
+    assert logp is not None, "a tuple of lists carries no scores: pass logp"
+    dev = hyp.device
+    for t in (hyp, hyp_len, count) + ((errors,) if errors is not None else ()):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    assert hyp.dim() == 3 and count.numel() == hyp.shape[0]
+    S, N, stride = (int(v) for v in hyp.shape)
+    assert hyp_len.shape == (S, N) and (errors is None or errors.shape == (S, N))
+    assert logp.is_cuda and logp.dtype == torch.float32 and logp.shape == (S, N) and logp.is_contiguous()
+    for m in (add, sub):
+        assert m is None or (isinstance(m, CtcSparseLabelLm) and m.blob.device == dev), "the models are CtcSparseLabelLm on the lists' device"
+    assert words is None or isinstance(words, CtcWordTable)
+    if classes is None:
+        classes = sub.classes if sub is not None else add.classes if (add is not None and words is None) else None
+    assert classes is not None, "word-level rescoring without sub: pass classes, the number of token classes"
+    if max_len is None:
+        max_len = min(1023, stride)
+    max_len = int(max_len)
+    out_n = N if out_n is None else int(out_n)
+    _check_totals(totals, 8)
+    nbytes = ctc_rescore_workspace_bytes(S, N, max_len, words is not None)
+    ws = _workspace("rescore", (S, N, max_len), nbytes, dev)
+    order = torch.empty(S, N, dtype=torch.int32, device=dev)
+    live = torch.empty(S, dtype=torch.int32, device=dev)
+    z, add_logp, sub_logp = (torch.empty(S, N, device=dev) for _ in range(3))
+    units, oov = (torch.empty(S, N, dtype=torch.int32, device=dev) for _ in range(2))
+    out = None
+    if out_n >= 1:
+        out_stride = max(min(stride, max_len), 1) if out_stride is None else int(out_stride)
+        n1 = max(out_n, 1)
+        out = CtcBeamResult(torch.zeros(S, n1, out_stride, dtype=torch.int32, device=dev), torch.zeros(S, n1, dtype=torch.int32, device=dev),
+                            torch.zeros(S, dtype=torch.int32, device=dev), torch.full((S, n1), -np.inf, device=dev),
+                            torch.full((S, n1), -1, dtype=torch.int32, device=dev) if errors is not None else None)
+    _chk(lib.klstm_ctc_nbest_rescore(
+        hyp.data_ptr(), max(stride, 1), hyp_len.data_ptr(), count.data_ptr(), logp.data_ptr(), _ptr(errors), S, N, max_len, int(classes),
+        sub.blob.data_ptr() if sub else None, ctypes.c_size_t(sub.nbytes if sub else 0), sub.states if sub else 0, _ptr(sub.final) if sub else None,
+        add.blob.data_ptr() if add else None, ctypes.c_size_t(add.nbytes if add else 0), add.states if add else 0, add.classes if add else 0,
+        _ptr(add.final) if add else None, words.keys.data_ptr() if words else None, words.ids.data_ptr() if words else None,
+        words.words if words else 0, words.unk_id if words else -1, words.separator if words else -1, add.blank if (add and words) else -1,
+        float(am_scale), float(add_scale), float(unit_bonus), order.data_ptr(), live.data_ptr(), z.data_ptr(), add_logp.data_ptr(),
+        sub_logp.data_ptr(), units.data_ptr(), oov.data_ptr(), out_n, _ptr(out.hyp) if out else None, out_stride if out else 0,
+        _ptr(out.hyp_len) if out else None, _ptr(out.nbest_count) if out else None, _ptr(out.score) if out else None,
+        _ptr(out.errors) if out else None, _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    return dict(order=order, live_count=live, score=z, add_logp=add_logp, sub_logp=sub_logp, units=units, oov=oov, nbest=out)
 
 
 CtcMmiResult = collections.namedtuple("CtcMmiResult", "loss diff num_logp den_logz lm_logw")

@@ -3,7 +3,8 @@ include/klstm.h): a dense deterministic weighted automaton ov
 from state q to next[q, c] and multiplies the prefix probability by weight[q, c]; final[q] multiplies a hypothesis that ends in q.
 numpy only.  Both builders return (next int32 [Q, K], weight float32 [Q, K], final float32 [Q]); the blank's column is never read
 (next 0, weight 0).  Composing an n-gram with a lexicon (the product automaton) is the caller's.  Below them the SPARSE form
-for back-off n-grams of higher order: its definition (sparse_lm_lookup), an ARPA reader and a count-based builder."""
+for back-off n-grams of higher order: its definition (sparse_lm_lookup), an ARPA reader and a count-based builder; and at the
+end the words of the second pass (ctc_nbest_rescore): word_key, word_table, word_sequences, dense_lm_to_sparse."""
 import collections
 import math
 
@@ -374,3 +375,79 @@ def backoff_ngram_label_lm(sequences, K, blank, order=3, discount=0.75, alpha=1.
     def arcs_of(h):
         return {w: v ** alpha * ebeta for w, v in seen_p[h].items() if w != END}
     return _sparse_from_states(K, states, arcs_of, lambda h: bows[h] ** alpha, lambda h: full[h][END] ** alpha, order, dtype)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Words for the second pass (klstm_ctc_nbest_rescore of include/klstm.h; ctc.ctc_nbest_rescore, ctc.CtcWordTable):
+# a word is a run of tokens between separators, known on the device by the 64-bit hash the beam search knows its prefixes by.  A word
+# model is a SparseLm over V classes, one per word of the vocabulary, one for unknown words if wanted, and one reserved: the `blank`
+# it is built with, which no word ever maps to.
+# ------------------------------------------------------------------------------------------------------------------------------------
+_WORD_H0, _WORD_HMUL, _M64 = 0x243F6A8885A308D3, 0x9E3779B97F4A7C15, (1 << 64) - 1      # BEAM_H0, BEAM_HMUL of csrc/klstm_ctc_dev.h
+
+
+def word_key(tokens):
+    """the key of a word: h <- x ^ (x >> 29) with x = (h ^ (token + 1)) * 0x9E3779B97F4A7C15 mod 2^64, folded over its tokens"""
+    h = _WORD_H0
+    for c in tokens:
+        x = ((h ^ ((int(c) + 1) & 0xFFFFFFFF)) * _WORD_HMUL) & _M64
+        h = x ^ (x >> 29)
+    return h
+
+
+def word_table(words, separator, ids=None):
+    """words: the vocabulary, each word a non-empty list of token classes other than the separator; ids: the class of each in the word
+    model (None: its position).  -> (keys uint64 [W] ascending, ids int32 [W] in that order), the arrays of CtcWordTable.  Raises
+    ValueError where two different words share a key, or one word is listed twice."""
+    ids = list(range(len(words))) if ids is None else [int(i) for i in ids]
+    assert len(ids) == len(words)
+    seen = {}
+    for w, i in zip(words, ids):
+        w = tuple(int(c) for c in w)
+        assert len(w) > 0 and separator not in w and min(w) >= 0, "a word is a non-empty run of classes other than the separator"
+        k = word_key(w)
+        if k in seen:
+            raise ValueError("the words %r and %r share the key %#x" % (list(seen[k][0]), list(w), k) if seen[k][0] != w
+                             else "the word %r is listed twice" % (list(w),))
+        seen[k] = (w, i)
+    keys = sorted(seen)
+    return np.asarray(keys, np.uint64), np.asarray([seen[k][1] for k in keys], np.int32)
+
+
+def word_sequences(label_seqs, table, separator, unk_id):
+    """label sequences (tokens with separators) -> the sequences of word classes a word model is trained on
+    (backoff_ngram_label_lm(..., K=V, blank=reserved)).  table: what word_table() returned.  A word that is not in the table takes
+    unk_id; with unk_id < 0 the sequence is left out, as the rescoring forbids such an entry."""
+    keys, ids = table
+    index = {int(k): int(i) for k, i in zip(keys, ids)}
+    out = []
+    for seq in label_seqs:
+        row, word, ok = [], [], True
+        for t in [int(c) for c in seq] + [separator]:
+            if t != separator:
+                word.append(t)
+            elif word:
+                i = index.get(word_key(word), unk_id)
+                ok &= i >= 0
+                row.append(i)
+                word = []
+        if ok:
+            out.append(row)
+    return out
+
+
+def dense_lm_to_sparse(next, weight, final=None, blank=None):
+    """the dense tables of CtcLabelLm (ngram_label_lm / lexicon_label_lm) as a SparseLm without back-offs, so that a first pass run with
+    them can be taken out by ctc_nbest_rescore(sub=...): state q keeps an arc for every class c with next[q, c] in [0, Q) and
+    weight[q, c] > 0 -- what the dense search does not forbid -- and a class without an arc is forbidden.  blank: its column is left
+    out whatever it holds."""
+    nxt, wt = np.asarray(next), np.asarray(weight, np.float32)
+    Q, K = nxt.shape
+    keep = (nxt >= 0) & (nxt < Q) & (wt > 0)
+    if blank is not None:
+        keep[:, blank] = False
+    q_idx, c_idx = np.nonzero(keep)                          # row by row, classes ascending
+    offsets = np.zeros(Q + 1, np.int32)
+    offsets[1:] = np.cumsum(keep.sum(1))
+    return SparseLm(K, offsets, c_idx.astype(np.int32), nxt[q_idx, c_idx].astype(np.int32), wt[q_idx, c_idx], np.full(Q, -1, np.int32),
+                    np.ones(Q, np.float32), None if final is None else np.asarray(final, np.float32))
