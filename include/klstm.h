@@ -427,8 +427,8 @@ klstm_status klstm_ctc_decode(const float *net_out, int T, int S, int K, int str
  * extend each of the at most `beam` prefixes; an extension that equals a prefix of the beam is added to that prefix's entry; the
  * `beam` largest totals pb + pnb survive (ties: the stay entries in beam order, then the extensions in order of parent and rank); the
  * beam is rescaled by the power of two that brings its largest total into [0.5, 1), values below 2^-60 become 0.  Two prefixes are
- * the same iff their lengths and their 64-bit hashes agree (h(empty) = 0x243F6A8885A308D3; H(h, c): x = (h ^ (c + 1)) *
- * 0x9E3779B97F4A7C15 mod 2^64, x ^ (x >> 29)).
+ * the same iff their lengths and their 64-bit hashes agree (h(empty) = KLSTM_CTC_HASH_START; H(h, c): x = (h ^ (c + 1)) *
+ * KLSTM_CTC_HASH_MUL mod 2^64, x ^ (x >> 29); the two constants are defined below this comment).
  *   beam, cands, nbest   1 <= beam <= 64, 1 <= cands <= min(K - 1, 32), 1 <= nbest <= beam
  *   hyp_dev [S*N*T]      hypothesis q of stream s at hyp_dev[(s*N + q)*T .. + hyp_len_dev[s*N + q]), q < nbest_count_dev[s]: the first
  *                        N beam entries with a total > 0, best first.  Entries beyond hyp_len and list slots beyond nbest_count are
@@ -450,6 +450,8 @@ klstm_status klstm_ctc_decode(const float *net_out, int T, int S, int K, int str
  * Bit-identical from run to run and independent of which stream an utterance sits in: no floating-point atomics.
  * Limits: S <= 32, T * S <= 65535, 2 <= K <= 32768, beam <= 64, cands <= min(K - 1, 32), nbest <= beam; beyond them KLSTM_ERR_SHAPE
  * and nothing is launched (klstm_ctc_beam_workspace_bytes answers 0 and leaves the message in klstm_last_error()). */
+#define KLSTM_CTC_HASH_START 0x243F6A8885A308D3ull      /* the hash of the empty sequence */
+#define KLSTM_CTC_HASH_MUL   0x9E3779B97F4A7C15ull      /* the multiplier of one step */
 size_t klstm_ctc_beam_workspace_bytes(int T, int S, int beam, int cands);
 klstm_status klstm_ctc_beam_decode(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
                                    const float *class_weight_dev, int beam, int cands, int nbest, int *hyp_dev, int *hyp_len_dev,
@@ -621,8 +623,8 @@ klstm_status klstm_ctc_mbr_eval(const float *net_out, int T, int S, int K, int s
  * Stateless, asynchronous on hip_stream, decided entirely on the device; nothing is read back.  For stream s, over its LIVE entries:
  *   units        separator < 0: the tokens of an entry.  separator >= 0: its words, the maximal runs of tokens other than the separator
  *                (leading, trailing and repeated separators make no empty words).  Two words are equal iff their 64-bit keys are: the
- *                hash the beam search knows its prefixes by, h <- x ^ (x >> 29) with x = (h ^ (token + 1)) * 0x9E3779B97F4A7C15,
- *                folded over the word's tokens from h = 0x243F6A8885A308D3
+ *                hash the beam search knows its prefixes by, h <- x ^ (x >> 29) with x = (h ^ (token + 1)) * KLSTM_CTC_HASH_MUL,
+ *                folded over the word's tokens from h = KLSTM_CTC_HASH_START
  *   P_q          exp(z_q - max z) / Z with z_q = (double)scale * (double)logp_q and Z summed q ascending, in double
  *   D[q][r]      the Levenshtein distance between the unit sequences of entries q and r
  *   R_q          sum_r P_r D[q][r], r ascending, in double: the expected unit errors of answering with entry q

@@ -1241,6 +1241,7 @@ class CtcMbr : private CtcCallBase {
   DeviceTotals<6> tot_;
 };
 
+inline int32 CtcNbestMaxLen(int32 max_len, int32 stride) { return max_len > 0 ? max_len : std::min<int32>(1023, stride); }      // the token capacity of CtcConsensus, CtcRescorer
 // Minimum Bayes risk decoding and unit confidences over the n-best lists of a CtcBeamDecoder (klstm_ctc_consensus, klstm.h, which
 // defines every quantity): per stream the entry of the list with the smallest expected unit errors under the
 // list's own posterior (or the most probable one), and for each of its tokens or words the posterior mass of the entries that agree
@@ -1259,7 +1260,7 @@ class CtcConsensus : private CtcCallBase {
   void Eval(const CtcNbestDevice &nb, const BaseFloat *logp_dev = nullptr) {
     const int32 S = nb.num_stream, N = nb.nbest;
     KLSTM_ASSERT(S > 0 && N > 0 && nb.stride > 0);
-    const int32 max_len = max_len_ > 0 ? max_len_ : std::min<int32>(1023, nb.stride);
+    const int32 max_len = CtcNbestMaxLen(max_len_, nb.stride);
     const size_t need = klstm_ctc_consensus_workspace_bytes(S, N, max_len, separator_ >= 0);
     void *ws = Workspace(need);
     idx_.Grow((size_t)S * 3 * sizeof(int32));
@@ -1324,9 +1325,9 @@ class CtcConsensus : private CtcCallBase {
 // The key a word is known by on the device (klstm_ctc_consensus, klstm_ctc_nbest_rescore; word_key of kaldi-lstm_amd/lm.py): the hash the
 // beam search knows its prefixes by, folded over the word's tokens.
 inline uint64_t CtcWordKey(const std::vector<int32> &tokens) {
-  uint64_t h = 0x243F6A8885A308D3ull;
+  uint64_t h = KLSTM_CTC_HASH_START;
   for (int32 c : tokens) {
-    const uint64_t x = (h ^ (uint64_t)(uint32_t)(c + 1)) * 0x9E3779B97F4A7C15ull;
+    const uint64_t x = (h ^ (uint64_t)(uint32_t)(c + 1)) * KLSTM_CTC_HASH_MUL;
     h = x ^ (x >> 29);
   }
   return h;
@@ -1384,7 +1385,7 @@ class CtcRescorer : private CtcCallBase {
   void Eval(const CtcNbestDevice &nb) {
     const int32 S = nb.num_stream, N = nb.nbest;
     KLSTM_ASSERT(S > 0 && N > 0 && nb.stride > 0 && nb.score);
-    const int32 max_len = max_len_ > 0 ? max_len_ : std::min<int32>(1023, nb.stride);
+    const int32 max_len = CtcNbestMaxLen(max_len_, nb.stride);
     const size_t need = klstm_ctc_rescore_workspace_bytes(S, N, max_len, words_ ? 1 : 0);
     void *ws = Workspace(need);
     const size_t SN = (size_t)S * N;

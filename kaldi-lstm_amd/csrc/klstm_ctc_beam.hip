@@ -269,9 +269,7 @@ __global__ __launch_bounds__(256) void k_ctc_beam_tail(const int *__restrict__ h
   }
   int *st = stat + 8 * s;
   st[0] = scored ? errs[0] : 0; st[1] = L; st[2] = scored ? hyp_len[(size_t)s * N] : 0; st[3] = scored; st[4] = oracle;
-  __threadfence();                                                 // the stream's statistics before its ticket
-  if (atomicAdd(ticket, 1u) != (unsigned)(S - 1)) return;
-  __threadfence();                                                 // the last workgroup: everybody's statistics are visible
+  if (!ctc_last_arrival(ticket, S)) return;
   double e = 0, n = 0, h = 0, u = 0, wr = 0, orc = 0;
   for (int q = 0; q < S; q++) {
     const int *sq = stat + 8 * q;

@@ -6,9 +6,9 @@
 //   map = argmax_q scale l_q,  mbr = argmin_q R_q,  pick = the one the caller asked for
 //   conf_u = sum_r P_r [unit u of h_pick is matched in THE alignment of h_pick against h_r]
 // Five launches:
-//   k_cons_keys   grid (N, S), one wave.  Is the entry live; its unit count; in word mode its keys into the workspace.
-//   k_cons_dist   grid (pair blocks, S), four waves, one unordered pair (q <= r) each: the row formulation of edit_distance of
-//                 klstm_ctc_dev.h (columns across the lanes, P per lane, prefix minimum by wave_scan_min), the longer sequence across
+//   k_cons_keys   grid (N, S), one wave.  Is the entry live (klstm_ctc_nbest.h: the contract of a list); its unit count; word keys.
+//   k_cons_dist   grid (pair blocks, S), four waves, one unordered pair (q <= r) each: the rows of edit_distance of klstm_ctc_dev.h
+//                 (KLSTM_ED_ROW_STEP: columns across the lanes, P per lane, prefix minimum by wave_scan_min), the longer sequence across
 //                 the lanes, P = 1 / 4 / 16 by its length.  Writes D[q][r] and D[r][q].
 //   k_cons_pick   grid (S), one wave.  P, R, map, mbr, pick in double; every sum in index order.
 //   k_cons_align  grid (N, S), one wave: the same rows with the pivot's units as rows and the entry's across the lanes, two bits of
@@ -16,7 +16,7 @@
 //                 that only this lane reads again: in LDS where the table fits CONS_LDS bytes, in the workspace otherwise.  The walk
 //                 back fetches CONS_BR rows of words into registers at a time and steps by __shfl.
 //   k_cons_conf   grid (S).  conf_u summed over r ascending by the thread of slot u; the stream's statistics; the last workgroup to
-//                 arrive (an integer ticket) adds the minibatch onto the totals, streams in order.
+//                 arrive (ctc_last_arrival) adds the minibatch onto the totals, streams in order (KLSTM_NBEST_ADD_TOTALS).
 // DETERMINISM.  No floating-point atomics, no reduction tree over floating-point values: bit-identical from run to run.
 // The products and sums below are the twin's, one rounding each: no contraction into FMAs.
 #pragma clang fp contract(off)
@@ -25,7 +25,8 @@
 #include <type_traits>
 
 #include "../../include/klstm.h"
-#include "klstm_ctc_dev.h"
+#include "klstm_ctc_host.h"
+#include "klstm_ctc_nbest.h"
 #include "klstm_kernels.h"
 
 namespace klstm {
@@ -33,50 +34,33 @@ namespace klstm {
 constexpr int CONS_LDS = 16384;        // bytes of back-pointers a wave keeps in LDS (256 rows of 64 bytes; 10 workgroups per CU)
 constexpr int CONS_BR = 8;             // rows of back-pointer words the walk back holds in registers
 
-// the caller's arrays
-struct ConsIn { const int *hyp, *hyp_len, *count; const float *logp; const int *errors; int stride, N, max_len, sep; };
+struct ConsIn : NbestIn {};             // the caller's arrays; the ninth member is sep (its own type: the kernels keep their names)
 // the workspace.  live [S N]; ulen [S N]; info [S]: 0 idle, 1 done, 2 rejected; pivot [S][4]: pick, map, mbr, entries dropped;
 // P, R [S N] double; stat [S][8] double; match [S N][max_len] bytes; keys [S N][max_len] u64 (word mode); table [S N][max_len][64]
 // words of 4 bytes (max_len > 255 only: below, every table fits LDS)
 struct ConsWs { int *live, *ulen, *info, *pivot, *dist; unsigned *ticket; double *P, *R, *stat; unsigned char *match; u64 *keys; unsigned *table; };
 
-static size_t cons_up256(size_t n) { return (n + 255) / 256 * 256; }
 static bool cons_table_in_lds(int max_len) { return max_len <= 255; }
 
-static size_t cons_layout(int S, int N, int max_len, bool words, void *base, ConsWs *ws) {
+static size_t cons_layout(int S, int N, int max_len, bool words, void *base, ConsWs &ws) {
   const size_t SN = (size_t)S * N, L = (size_t)(max_len > 0 ? max_len : 1);
-  char *p = reinterpret_cast<char *>(base);
-  size_t off = 0;
-  const size_t o_ticket = off; off += 256;
-  const size_t o_info = off;   off += cons_up256((size_t)S * sizeof(int));
-  const size_t o_pivot = off;  off += cons_up256((size_t)S * 4 * sizeof(int));
-  const size_t o_live = off;   off += cons_up256(SN * sizeof(int));
-  const size_t o_ulen = off;   off += cons_up256(SN * sizeof(int));
-  const size_t o_p = off;      off += cons_up256(SN * sizeof(double));
-  const size_t o_r = off;      off += cons_up256(SN * sizeof(double));
-  const size_t o_stat = off;   off += cons_up256((size_t)S * 8 * sizeof(double));
-  const size_t o_dist = off;   off += cons_up256(SN * N * sizeof(int));
-  const size_t o_match = off;  off += cons_up256(SN * L);
-  const size_t o_keys = off;   off += words ? cons_up256(SN * L * sizeof(u64)) : 0;
-  const size_t o_table = off;  off += cons_table_in_lds(max_len) ? 0 : SN * L * 64 * sizeof(unsigned);
-  if (ws) {
-    ws->ticket = reinterpret_cast<unsigned *>(p + o_ticket);
-    ws->info = reinterpret_cast<int *>(p + o_info);
-    ws->pivot = reinterpret_cast<int *>(p + o_pivot);
-    ws->live = reinterpret_cast<int *>(p + o_live);
-    ws->ulen = reinterpret_cast<int *>(p + o_ulen);
-    ws->P = reinterpret_cast<double *>(p + o_p);
-    ws->R = reinterpret_cast<double *>(p + o_r);
-    ws->stat = reinterpret_cast<double *>(p + o_stat);
-    ws->dist = reinterpret_cast<int *>(p + o_dist);
-    ws->match = reinterpret_cast<unsigned char *>(p + o_match);
-    ws->keys = words ? reinterpret_cast<u64 *>(p + o_keys) : nullptr;
-    ws->table = cons_table_in_lds(max_len) ? nullptr : reinterpret_cast<unsigned *>(p + o_table);
-  }
-  return off;
+  CtcCarver c(base);
+  ws.ticket = c.take<unsigned>(64);
+  ws.info = c.take<int>(S);
+  ws.pivot = c.take<int>((size_t)S * 4);
+  ws.live = c.take<int>(SN);
+  ws.ulen = c.take<int>(SN);
+  ws.P = c.take<double>(SN);
+  ws.R = c.take<double>(SN);
+  ws.stat = c.take<double>((size_t)S * 8);
+  ws.dist = c.take<int>(SN * N);
+  ws.match = c.take<unsigned char>(SN * L);
+  ws.keys = words ? c.take<u64>(SN * L) : nullptr;
+  ws.table = cons_table_in_lds(max_len) ? nullptr : c.take<unsigned>(SN * L * 64);
+  return c.bytes();
 }
 
-size_t ctc_consensus_workspace_bytes(int S, int N, int max_len, int words) { return cons_layout(S, N, max_len, words != 0, nullptr, nullptr); }
+size_t ctc_consensus_workspace_bytes(int S, int N, int max_len, int words) { ConsWs ws; return cons_layout(S, N, max_len, words != 0, nullptr, ws); }
 
 // the unit keys of entry (s, q): its tokens, or its words' hashes in the workspace
 template <class KT> struct ConsKeys;
@@ -93,32 +77,18 @@ template <> struct ConsKeys<u64> {
 __global__ __launch_bounds__(64) void k_cons_keys(ConsIn a, ConsWs ws, int *__restrict__ unit_len) {
   const int q = blockIdx.x, s = blockIdx.y, lane = threadIdx.x, se = s * a.N + q;
   if (se == 0 && lane == 0) *ws.ticket = 0u;                       // for k_cons_conf, three launches later
-  const int cnt = a.count[s];
-  bool live = cnt >= 0 && cnt <= a.N && q < cnt;
-  int len = 0;
-  if (live) {                                                      // slots q >= count are not read
-    len = a.hyp_len[se];
-    live = isfinite(a.logp[se]) && len >= 0 && len <= a.stride && len <= a.max_len;
-  }
+  KLSTM_NBEST_SHAPE(a, s, q, se, listed, live, len, lp)
   const int *h = a.hyp + (size_t)se * a.stride;
-  if (live) {
-    bool neg = false;
-    for (int t = lane; t < len; t += 64) neg |= h[t] < 0;
-    live = !__any(neg);
-  }
+  if (live) KLSTM_NBEST_TOKENS(h, len, lane, v_ < 0, live)         // no K here: a token is a class if it is >= 0
   int units = 0;
   if (live && a.sep < 0) units = len;
   if (live && a.sep >= 0) {
     u64 *keys = ws.keys + (size_t)se * a.max_len;
     for (int t0 = 0; t0 < len; t0 += 64) {
       const int t = t0 + lane;
-      const bool start = t < len && h[t] != a.sep && (t == 0 || h[t - 1] == a.sep);
+      const bool start = nbest_word_start(h, len, a.sep, t);
       const unsigned long long mask = __ballot(start);
-      if (start) {                                                 // the thread of a word's first token folds the word
-        u64 hs = BEAM_H0;
-        for (int i = t; i < len && h[i] != a.sep; i++) hs = beam_hash(hs, h[i]);
-        keys[units + __popcll(mask & ((1ull << lane) - 1ull))] = hs;
-      }
+      if (start) keys[units + nbest_word_slot(mask, lane)] = nbest_word_key(h, len, a.sep, t);     // the lane of a word's first token
       units += __popcll(mask);
     }
   }
@@ -126,10 +96,10 @@ __global__ __launch_bounds__(64) void k_cons_keys(ConsIn a, ConsWs ws, int *__re
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
-// The Levenshtein rows of one wave: edit_distance<P, false> of klstm_ctc_dev.h over unit keys.  Column j (0 .. Lc) of the row sits in
+// The Levenshtein rows of one wave: those of edit_distance<P, false> of klstm_ctc_dev.h (KLSTM_ED_ROW_STEP) over unit keys.  Column j (0 .. Lc) of the row sits in
 // lane j / P, slot j % P and carries cols[j - 1]; one row per unit of rows[0 .. Lr).  Returns D[Lr][Lc] in every lane.
-// TRACE: row i (1 .. Lr) leaves a word of two bits per slot in tab[(i - 1) * 64 + lane], the step the fixed walk takes out of cell
-// (i, j): 0 diagonal with equal units, 1 diagonal with a substitution, 2 up, 3 left.  Columns beyond Lc hold values nobody reads.
+// TRACE: row i (1 .. Lr) leaves its word of two bits per slot (KLSTM_ED_ROW_STEP) in tab[(i - 1) * 64 + lane].  Columns beyond Lc hold
+// values nobody reads.
 // ------------------------------------------------------------------------------------------------------------------------------------
 template <int P, class KT, bool TRACE, class W>
 __device__ __forceinline__ int cons_rows(const KT *__restrict__ cols, int Lc, const KT *__restrict__ rows, int Lr, W *tab) {
@@ -149,34 +119,7 @@ __device__ __forceinline__ int cons_rows(const KT *__restrict__ cols, int Lc, co
     for (int k = 0; k < n; k++) {
       const KT tok = __shfl(c, k);
       row++;
-      const int up = __shfl_up(prev[P - 1], 1);                    // D'[j - 1] of the lane's first slot
-      int run = ED_BIG;
-      int v[P];
-#pragma unroll
-      for (int e = 0; e < P; e++) {
-        const int j = lane * P + e;
-        const int diag = e ? prev[e - 1] : up;
-        int tmp = min(prev[e] + 1, diag + (rl[e] != tok));
-        if (j == 0) tmp = row;
-        run = min(run, tmp - j);
-        v[e] = run;
-      }
-      int excl = __shfl_up(wave_scan_min(run), 1);
-      if (lane == 0) excl = ED_BIG;
-      unsigned code = 0;
-      int diag = up;
-#pragma unroll
-      for (int e = 0; e < P; e++) {
-        const int j = lane * P + e;
-        const int nw = j + min(v[e], excl);
-        if (TRACE) {                                               // the old row is still in prev
-          const int ne = rl[e] != tok;
-          const unsigned c2 = j == 0 ? 2u : nw == diag + ne ? (unsigned)ne : nw == prev[e] + 1 ? 2u : 3u;
-          code |= c2 << (2 * e);
-          diag = prev[e];
-        }
-        prev[e] = nw;
-      }
+      KLSTM_ED_ROW_STEP(P, TRACE, prev, rl, tok, row, code)
       if (TRACE) tab[(size_t)(row - 1) * 64 + lane] = (W)code;
     }
   }
@@ -373,16 +316,8 @@ __global__ __launch_bounds__(256) void k_cons_conf(ConsIn a, ConsWs ws, int S, f
   stat[5] = (double)ws.pivot[4 * s + 3];
   stat[6] = (st == 1 && a.errors) ? (double)a.errors[s * N + ipick] : 0.0;
   stat[7] = (st == 1 && a.errors) ? (double)a.errors[s * N + imap] : 0.0;
-  __threadfence();                                                 // the stream's statistics before its ticket
-  if (atomicAdd(ws.ticket, 1u) != (unsigned)(S - 1)) return;
-  __threadfence();                                                 // the last workgroup: everybody's statistics are visible
-  double t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int q = 0; q < S; q++) {
-    const int sq = __hip_atomic_load(ws.info + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    t[sq == 1 ? 0 : 1] += 1.0;
-    for (int i = 0; i < 8; i++) t[2 + i] += __hip_atomic_load(ws.stat + 8 * q + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  for (int i = 0; i < 10; i++) totals[i] += t[i];
+  if (!ctc_last_arrival(ws.ticket, S)) return;
+  KLSTM_NBEST_ADD_TOTALS(ws.info, ws.stat, S, 0, totals)
 }
 
 template <class KT>
@@ -407,8 +342,8 @@ hipError_t launch_ctc_consensus(const int *hyp, int hyp_stride, const int *hyp_l
                                 void *workspace, hipStream_t st) {
   const bool words = separator >= 0;
   ConsWs ws;
-  cons_layout(S, N, max_len, words, workspace, &ws);
-  const ConsIn in{hyp, hyp_len, count, logp, errors, hyp_stride, N, max_len, words ? separator : -1};
+  cons_layout(S, N, max_len, words, workspace, ws);
+  const ConsIn in{{hyp, hyp_len, count, logp, errors, hyp_stride, N, max_len, {words ? separator : -1}}};
   if (!dist) dist = ws.dist;
   if (words) return cons_launch<u64>(in, ws, S, scale, pivot_mode, pick, map, mbr, post, risk, unit_len, conf, conf_stride, dist, totals, st);
   return cons_launch<int>(in, ws, S, scale, pivot_mode, pick, map, mbr, post, risk, unit_len, conf, conf_stride, dist, totals, st);

@@ -142,9 +142,7 @@ __global__ __launch_bounds__(256) void k_ctc_collapse(const int *__restrict__ fc
   if (errors) errors[s] = err;
   if (!totals) return;
   stat[4 * s] = err; stat[4 * s + 1] = L; stat[4 * s + 2] = H; stat[4 * s + 3] = scored;
-  __threadfence();                                                 // the stream's statistics before its ticket
-  if (atomicAdd(ticket, 1u) != (unsigned)(S - 1)) return;
-  __threadfence();                                                 // the last workgroup: everybody's statistics are visible
+  if (!ctc_last_arrival(ticket, S)) return;
   double e = 0, n = 0, h = 0, u = 0, w = 0;
   for (int q = 0; q < S; q++) {
     const int *st = stat + 4 * q;

@@ -1,8 +1,9 @@
 // kaldi-lstm_amd/csrc/klstm_ctc_dev.h -- device code shared by the CTC kernels (klstm_ctc.hip: the loss; klstm_ctc_align.hip: the forced
 // alignment; klstm_ctc_decode.hip: best path; klstm_ctc_beam.hip: prefix beam search; klstm_ctc_mbr.hip: the n-best risk;
-// klstm_ctc_mmi.hip: MMI; klstm_ctc_consensus.hip: MBR decoding over n-best lists): the prefix hash, the status of an utterance, the maximum over a wave, the fixed-tree reduction over a workgroup, the links,
-// the zero row and the gamma row of the three lattice losses, (value, index) reductions, the row reader, the one-wave Levenshtein
-// distance and the alpha / beta chain of the loss (ctc_chain_run).  The host's side of the lattice losses: klstm_ctc_host.h.
+// klstm_ctc_mmi.hip: MMI; through klstm_ctc_nbest.h, the contract of an n-best list, klstm_ctc_consensus.hip and klstm_ctc_rescore.hip):
+// the prefix hash, the status of an utterance, the maximum over a wave, the fixed-tree reduction over a workgroup, the links, the zero
+// row and the gamma row of the three lattice losses, (value, index) reductions, the row reader, the ticket of the last workgroup, the
+// Levenshtein row step with the one-wave distance on it, the alpha / beta chain of the loss (ctc_chain_run).  Host side: klstm_ctc_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,14 +12,16 @@
 #include <cmath>
 #include <cstdint>
 
+#include "../../include/klstm.h"
+
 namespace klstm {
 
 constexpr float CTC_NEG = -1e30f;      // "log 0": absorbs every offset (ulp 7e22), exp(CTC_NEG - m) = 0
 
 // The 64-bit hash of a label sequence: beam_hash folded over its labels from BEAM_H0, the hash of the empty prefix.  The prefix beam
-// search (klstm_ctc_beam.hip) knows its prefixes by it; the n-best consensus (klstm_ctc_consensus.hip) knows its words by it.
+// search (klstm_ctc_beam.hip) knows its prefixes by it; the second pass (klstm_ctc_nbest.h) and CtcWordKey of klstm_nnet.hpp know words by it.
 typedef unsigned long long u64;
-constexpr u64 BEAM_H0 = 0x243F6A8885A308D3ull, BEAM_HMUL = 0x9E3779B97F4A7C15ull;
+constexpr u64 BEAM_H0 = KLSTM_CTC_HASH_START, BEAM_HMUL = KLSTM_CTC_HASH_MUL;
 __device__ __forceinline__ u64 beam_hash(u64 h, int c) {
   const u64 x = (h ^ (u64)(unsigned)(c + 1)) * BEAM_HMUL;
   return x ^ (x >> 29);
@@ -186,6 +189,15 @@ __device__ __forceinline__ void ctc_for_row(const float *__restrict__ yp, const 
   if (c < K) f(w ? yp[c] * w[c] : yp[c], c);
 }
 
+// The ticket of the kernels that add their minibatch onto the caller's totals (k_ctc_collapse, k_ctc_beam_tail, k_cons_conf, k_resc_rank):
+// thread 0 of a stream's workgroup, its statistics written; true for the last of S to arrive, who reads everybody's (agent scope).
+__device__ __forceinline__ bool ctc_last_arrival(unsigned *ticket, int S) {
+  __threadfence();                                                 // the stream's statistics before its ticket
+  if (atomicAdd(ticket, 1u) != (unsigned)(S - 1)) return false;
+  __threadfence();                                                 // the last workgroup: everybody's statistics are visible
+  return true;
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------
 // Levenshtein distance between the collapsed best path of stream s and ref[0 .. L), by ONE wave.  Column j of the row (0 .. L) sits in
 // lane j / P, slot j % P.  For every hypothesis token:  tmp[j] = min(D'[j] + 1, D'[j-1] + (ref[j-1] != token)),  tmp[0] = row number,
@@ -208,6 +220,36 @@ __device__ __forceinline__ int wave_scan_min(int v) {              // inclusive 
 }
 constexpr int ED_BIG = 1 << 29;
 
+// One row of the table, for the hypothesis token `tok` of row number `row` (1 ..): prev[P] holds D' on entry and D on return, rl[P] the
+// keys of the lane's columns (int classes, or u64 word keys: klstm_ctc_consensus.hip).  TRACE (a constant): `code`, declared here, gets
+// two bits per slot, the step the fixed walk back takes out of cell (row, j): 0 diagonal with equal keys, 1 diagonal with a substitution,
+// 2 up, 3 left.  Expects `lane`.  TEXT: as a function edit_distance<16> comes out with other registers (ctc_nbest_shared_isa.txt).
+#define KLSTM_ED_ROW_STEP(P, TRACE, prev, rl, tok, row, code)                                                                        \
+  unsigned code = 0;                                                                                                                 \
+  {                                                                                                                                  \
+    const int up_ = __shfl_up((prev)[(P) - 1], 1);                 /* D'[j - 1] of the lane's first slot */                          \
+    int run_ = ED_BIG, v_[P];                                                                                                        \
+    _Pragma("unroll") for (int e = 0; e < (P); e++) {                                                                                \
+      const int j = lane * (P) + e, diag = e ? (prev)[e - 1] : up_;                                                                  \
+      int tmp = min((prev)[e] + 1, diag + ((rl)[e] != (tok)));                                                                       \
+      if (j == 0) tmp = (row);                                                                                                       \
+      run_ = min(run_, tmp - j);                                                                                                     \
+      v_[e] = run_;                                                                                                                  \
+    }                                                                                                                                \
+    int excl_ = __shfl_up(wave_scan_min(run_), 1), diag_ = up_;                                                                      \
+    if (lane == 0) excl_ = ED_BIG;                                                                                                   \
+    _Pragma("unroll") for (int e = 0; e < (P); e++) {                                                                                \
+      const int j = lane * (P) + e, nw = j + min(v_[e], excl_);                                                                      \
+      if (TRACE) {                                                 /* the old row is still in prev */                                \
+        const int ne = (rl)[e] != (tok);                                                                                             \
+        const unsigned c2 = j == 0 ? 2u : nw == diag_ + ne ? (unsigned)ne : nw == (prev)[e] + 1 ? 2u : 3u;                           \
+        code |= c2 << (2 * e);                                                                                                       \
+        diag_ = (prev)[e];                                                                                                           \
+      }                                                                                                                              \
+      (prev)[e] = nw;                                                                                                                \
+    }                                                                                                                                \
+  }
+
 template <int P, bool COLLAPSE = true>
 __device__ int edit_distance(const int *__restrict__ fclass, int S, int s, int len, int blank, const int *__restrict__ ref, int L) {
   const int lane = threadIdx.x & 63;
@@ -229,22 +271,7 @@ __device__ int edit_distance(const int *__restrict__ fclass, int S, int s, int l
       mask &= mask - 1;
       const int tok = __shfl(c, k);
       row++;
-      int up = __shfl_up(prev[P - 1], 1);                          // D'[j - 1] of the lane's first slot
-      int run = ED_BIG;
-      int v[P];
-#pragma unroll
-      for (int e = 0; e < P; e++) {
-        const int j = lane * P + e;
-        const int diag = e ? prev[e - 1] : up;
-        int tmp = min(prev[e] + 1, diag + (rl[e] != tok));
-        if (j == 0) tmp = row;
-        run = min(run, tmp - j);
-        v[e] = run;
-      }
-      int excl = __shfl_up(wave_scan_min(run), 1);
-      if (lane == 0) excl = ED_BIG;
-#pragma unroll
-      for (int e = 0; e < P; e++) prev[e] = lane * P + e + min(v[e], excl);
+      KLSTM_ED_ROW_STEP(P, false, prev, rl, tok, row, code) (void)code;
     }
   }
   int out = 0;

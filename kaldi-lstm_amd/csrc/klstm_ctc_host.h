@@ -1,7 +1,7 @@
-// kaldi-lstm_amd/csrc/klstm_ctc_host.h -- host code shared by the launchers on the CTC lattice (klstm_ctc.hip: the loss; klstm_ctc_mbr.hip:
-// the n-best risk; klstm_ctc_mmi.hip: MMI; klstm_ctc_align.hip: the forced alignment): the plan of the alpha / beta chain and its
-// dispatch, the label capacity of a workspace, the padding and alignment rules.  Plain C++17, no HIP: a host program compiles it
-// (tests/cpp/ctc_plan_test.cpp).
+// kaldi-lstm_amd/csrc/klstm_ctc_host.h -- host code shared by the CTC launchers (klstm_ctc.hip: the loss; klstm_ctc_mbr.hip: the n-best
+// risk; klstm_ctc_mmi.hip: MMI; klstm_ctc_align.hip: the forced alignment; klstm_ctc_consensus.hip, klstm_ctc_rescore.hip: the second
+// pass): the plan of the alpha / beta chain and its dispatch, the label capacity of a workspace, the padding and alignment rules, the
+// carver of a workspace.  Plain C++17, no HIP: a host program compiles it (tests/cpp/ctc_plan_test.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -16,6 +16,18 @@ inline bool ctc_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 1
 inline int ctc_rows_vec(int K, int stride, int dstride, const void *y, const void *diff) {
   return K % 4 == 0 && stride % 4 == 0 && dstride % 4 == 0 && ctc_al16(y) && ctc_al16(diff);
 }
+
+// A workspace handed out region by region, each named once: packed<T>(n) is n elements at the current offset, take<T>(n) the same
+// with the offset then rounded up to 256 bytes (the regions that need no rounding, the bulk rows, close a layout).  Over a null base
+// every pointer is null and bytes() counts what a real base would have consumed: a layout is one function for both questions.
+struct CtcCarver {
+  char *base;
+  size_t off = 0;
+  explicit CtcCarver(void *b) : base(static_cast<char *>(b)) {}
+  template <class T> T *packed(size_t n) { const size_t o = off; off += n * sizeof(T); return base ? reinterpret_cast<T *>(base + o) : nullptr; }
+  template <class T> T *take(size_t n) { T *p = packed<T>(n); off = ctc_up256(off); return p; }
+  size_t bytes() const { return off; }
+};
 
 // The geometry of ctc_chain_run for N = 2 Lcap + 1 states, as 16 * waves + states per thread.
 // measured: four waves with one state per thread beat one wave with two (391 against 487 us at T = 1000, 101 states)

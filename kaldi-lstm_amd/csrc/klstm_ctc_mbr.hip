@@ -33,40 +33,30 @@ struct MbrIn { const int *lens, *hyp, *hyp_len, *count, *errors, *ref, *roff; in
 // position of the same class, first-of-its-class flag, accumulator slot; cmap [S][K]: class -> slot; sclass [S][E Lcap]: slot -> class
 struct MbrWs { int *info, *einfo, *nslot, *link, *cmap, *sclass; double *logp; float *coef, *A, *B; int Npad, Lcap, E, slotcap; };
 
-static size_t mbr_layout(int T, int S, int N, int Lcap, int with_ref, void *base, MbrWs *ws) {
+static size_t mbr_layout(int T, int S, int N, int Lcap, int with_ref, void *base, MbrWs &ws) {
   const size_t E = (size_t)N + (with_ref ? 1 : 0), npad = ctc_npad(Lcap), SE = (size_t)S * E;
-  char *p = reinterpret_cast<char *>(base);
-  size_t off = 0;
-  const size_t o_logp = off;   off += ctc_up256(SE * sizeof(double));
-  const size_t o_coef = off;   off += ctc_up256(SE * sizeof(float));
-  const size_t o_info = off;   off += ctc_up256((size_t)S * sizeof(int));
-  const size_t o_nslot = off;  off += ctc_up256((size_t)S * sizeof(int));
-  const size_t o_einfo = off;  off += ctc_up256(SE * sizeof(int));
-  const size_t o_cmap = off;   off += ctc_up256((size_t)S * MBR_KMAX * sizeof(int));
-  const size_t o_sclass = off; off += ctc_up256(SE * (size_t)Lcap * sizeof(int));
-  const size_t o_link = off;   off += ctc_up256(SE * 3 * (size_t)Lcap * sizeof(int));
-  const size_t o_a = off;      off += (size_t)T * SE * npad * sizeof(float);
-  const size_t o_b = off;      off += (size_t)T * SE * npad * sizeof(float);
-  if (ws) {
-    ws->logp = reinterpret_cast<double *>(p + o_logp);
-    ws->coef = reinterpret_cast<float *>(p + o_coef);
-    ws->info = reinterpret_cast<int *>(p + o_info);
-    ws->nslot = reinterpret_cast<int *>(p + o_nslot);
-    ws->einfo = reinterpret_cast<int *>(p + o_einfo);
-    ws->cmap = reinterpret_cast<int *>(p + o_cmap);
-    ws->sclass = reinterpret_cast<int *>(p + o_sclass);
-    ws->link = reinterpret_cast<int *>(p + o_link);
-    ws->A = reinterpret_cast<float *>(p + o_a);
-    ws->B = reinterpret_cast<float *>(p + o_b);
-    ws->Npad = (int)npad;
-    ws->Lcap = Lcap;
-    ws->E = (int)E;
-    ws->slotcap = (int)E * Lcap;
-  }
-  return off;
+  CtcCarver c(base);
+  ws.logp = c.take<double>(SE);
+  ws.coef = c.take<float>(SE);
+  ws.info = c.take<int>(S);
+  ws.nslot = c.take<int>(S);
+  ws.einfo = c.take<int>(SE);
+  ws.cmap = c.take<int>((size_t)S * MBR_KMAX);
+  ws.sclass = c.take<int>(SE * (size_t)Lcap);
+  ws.link = c.take<int>(SE * 3 * (size_t)Lcap);
+  ws.A = c.packed<float>((size_t)T * SE * npad);
+  ws.B = c.packed<float>((size_t)T * SE * npad);
+  ws.Npad = (int)npad;
+  ws.Lcap = Lcap;
+  ws.E = (int)E;
+  ws.slotcap = (int)E * Lcap;
+  return c.bytes();
 }
 
-size_t ctc_mbr_workspace_bytes(int T, int S, int N, int Lcap, int with_ref) { return mbr_layout(T, S, N, Lcap, with_ref, nullptr, nullptr); }
+size_t ctc_mbr_workspace_bytes(int T, int S, int N, int Lcap, int with_ref) {
+  MbrWs ws;
+  return mbr_layout(T, S, N, Lcap, with_ref, nullptr, ws);
+}
 
 int ctc_mbr_label_capacity(int T, int S, int N, int with_ref, size_t bytes) {
   return ctc_label_capacity_of(bytes, [&](int Lcap) { return ctc_mbr_workspace_bytes(T, S, N, Lcap, with_ref); });
@@ -265,7 +255,7 @@ hipError_t launch_ctc_mbr(const float *y, int T, int S, int K, int stride, const
                           float lam, float *diff, int dstride, float *risk, float *hyp_logp, float *hyp_post, float *ref_loss,
                           double *totals, void *workspace, int Lcap, hipStream_t st) {
   MbrWs ws;
-  mbr_layout(T, S, N, Lcap, ref != nullptr, workspace, &ws);
+  mbr_layout(T, S, N, Lcap, ref != nullptr, workspace, ws);
   const MbrIn in{lens, hyp, hyp_len, count, errors, ref, roff, hyp_stride, N, T, K, blank};
   hipError_t err = ctc_chain_dispatch(ctc_chain_plan(2 * Lcap + 1), hipErrorInvalidValue, [&](auto nw, auto p) {
     return launch(k_mbr_chain<nw(), p()>, dim3(S * ws.E, 3), dim3(64 * nw()), 0, st, LaunchProbe{}, y, S, stride, in, ws);

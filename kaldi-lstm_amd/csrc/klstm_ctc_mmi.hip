@@ -44,54 +44,42 @@ struct MmiGraph {
 // [S][T][Npad]; Ad, Bd: the denominator's [S][T rows of the graph's Npad, within T * Dpad floats]
 struct MmiWs { int *info, *link; double *logw, *numlp, *logz; float *A, *B, *Ad, *Bd; int Npad, Lcap, Dpad; };
 
-static size_t mmi_graph_layout(int Q, int K, void *base, MmiGraph *g) {
+static size_t mmi_graph_layout(int Q, int K, void *base, MmiGraph &g) {
   const size_t QK = (size_t)Q * K;
-  char *p = reinterpret_cast<char *>(base);
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off += ctc_up256(n * 4); return p + o; };
-  char *hdr = take(MH_WORDS), *fin = take(Q), *soff = take(Q + 1), *aoff = take(Q + 1), *arc_of = take(QK), *has = take(QK);
-  char *st_q = take(QK), *st_k = take(QK), *st_g = take(QK), *ioff = take(QK + 1), *in_src = take(QK), *in_lw = take(QK);
-  char *arc_w = take(QK), *arc_lw = take(QK), *arc_k = take(QK), *arc_dst = take(QK), *arc_q = take(QK), *coff = take(K + 1), *ccur = take(K), *cstate = take(QK);
-  if (g) {
-    auto I = [](char *q) { return reinterpret_cast<int *>(q); };
-    auto F = [](char *q) { return reinterpret_cast<float *>(q); };
-    *g = MmiGraph{I(hdr), F(fin), I(soff), I(aoff), I(arc_of), I(has), I(st_q), I(st_k), I(st_g), I(ioff), I(in_src), F(in_lw), F(arc_w), F(arc_lw),
-                  I(arc_k), I(arc_dst), I(arc_q), I(coff), I(ccur), I(cstate)};
-  }
-  return off;
+  CtcCarver c(base);
+  g.hdr = c.take<int>(MH_WORDS); g.fin = c.take<float>(Q); g.soff = c.take<int>(Q + 1); g.aoff = c.take<int>(Q + 1);
+  g.arc_of = c.take<int>(QK); g.has = c.take<int>(QK); g.st_q = c.take<int>(QK); g.st_k = c.take<int>(QK); g.st_g = c.take<int>(QK);
+  g.ioff = c.take<int>(QK + 1); g.in_src = c.take<int>(QK); g.in_lw = c.take<float>(QK); g.arc_w = c.take<float>(QK);
+  g.arc_lw = c.take<float>(QK); g.arc_k = c.take<int>(QK); g.arc_dst = c.take<int>(QK); g.arc_q = c.take<int>(QK);
+  g.coff = c.take<int>(K + 1); g.ccur = c.take<int>(K); g.cstate = c.take<int>(QK);
+  return c.bytes();
 }
-size_t ctc_mmi_graph_bytes(int Q, int K) { return mmi_graph_layout(Q, K, nullptr, nullptr); }
+size_t ctc_mmi_graph_bytes(int Q, int K) {
+  MmiGraph g;
+  return mmi_graph_layout(Q, K, nullptr, g);
+}
 
-static size_t mmi_layout(int T, int S, int K, int Q, int Lcap, void *base, MmiWs *ws) {
+static size_t mmi_layout(int T, int S, int K, int Q, int Lcap, void *base, MmiWs &ws) {
   const size_t npad = ctc_npad(Lcap), dpad = ((size_t)Q * K + 3) / 4 * 4;
-  char *p = reinterpret_cast<char *>(base);
-  size_t off = 0;
-  const size_t o_info = off;  off += ctc_up256((size_t)S * sizeof(int));
-  const size_t o_logw = off;  off += ctc_up256((size_t)S * sizeof(double));
-  const size_t o_numlp = off; off += ctc_up256((size_t)S * sizeof(double));
-  const size_t o_logz = off;  off += ctc_up256((size_t)S * sizeof(double));
-  const size_t o_link = off;  off += ctc_up256((size_t)S * 2 * (size_t)Lcap * sizeof(int));
-  const size_t o_ad = off;    off += (size_t)T * S * dpad * sizeof(float);
-  const size_t o_bd = off;    off += (size_t)T * S * dpad * sizeof(float);
-  const size_t o_a = off;     off += (size_t)T * S * npad * sizeof(float);
-  const size_t o_b = off;     off += (size_t)T * S * npad * sizeof(float);
-  if (ws) {
-    ws->info = reinterpret_cast<int *>(p + o_info);
-    ws->logw = reinterpret_cast<double *>(p + o_logw);
-    ws->numlp = reinterpret_cast<double *>(p + o_numlp);
-    ws->logz = reinterpret_cast<double *>(p + o_logz);
-    ws->link = reinterpret_cast<int *>(p + o_link);
-    ws->Ad = reinterpret_cast<float *>(p + o_ad);
-    ws->Bd = reinterpret_cast<float *>(p + o_bd);
-    ws->A = reinterpret_cast<float *>(p + o_a);
-    ws->B = reinterpret_cast<float *>(p + o_b);
-    ws->Npad = (int)npad;
-    ws->Lcap = Lcap;
-    ws->Dpad = (int)dpad;
-  }
-  return off;
+  CtcCarver c(base);
+  ws.info = c.take<int>(S);
+  ws.logw = c.take<double>(S);
+  ws.numlp = c.take<double>(S);
+  ws.logz = c.take<double>(S);
+  ws.link = c.take<int>((size_t)S * 2 * (size_t)Lcap);
+  ws.Ad = c.packed<float>((size_t)T * S * dpad);
+  ws.Bd = c.packed<float>((size_t)T * S * dpad);
+  ws.A = c.packed<float>((size_t)T * S * npad);
+  ws.B = c.packed<float>((size_t)T * S * npad);
+  ws.Npad = (int)npad;
+  ws.Lcap = Lcap;
+  ws.Dpad = (int)dpad;
+  return c.bytes();
 }
-size_t ctc_mmi_workspace_bytes(int T, int S, int K, int Q, int Lcap) { return mmi_layout(T, S, K, Q, Lcap, nullptr, nullptr); }
+size_t ctc_mmi_workspace_bytes(int T, int S, int K, int Q, int Lcap) {
+  MmiWs ws;
+  return mmi_layout(T, S, K, Q, Lcap, nullptr, ws);
+}
 
 int ctc_mmi_label_capacity(int T, int S, int K, int Q, size_t bytes) {
   return ctc_label_capacity_of(bytes, [&](int Lcap) { return ctc_mmi_workspace_bytes(T, S, K, Q, Lcap); });
@@ -460,7 +448,7 @@ __global__ __launch_bounds__(256) void k_mmi_combine(const float *__restrict__ y
 
 hipError_t launch_ctc_mmi_graph(int Q, int K, int blank, const int *next, const float *weight, const float *final_, void *graph, hipStream_t st) {
   MmiGraph g;
-  mmi_graph_layout(Q, K, graph, &g);
+  mmi_graph_layout(Q, K, graph, g);
   return launch(k_mmi_graph_build, dim3(1), dim3(256), 0, st, LaunchProbe{}, Q, K, blank, next, weight, final_, g);
 }
 
@@ -468,9 +456,9 @@ hipError_t launch_ctc_mmi(const float *y, int T, int S, int K, int stride, const
                           const void *graph, int Q, float lam, float *diff, int dstride, float *loss, float *num_logp, float *den_logz,
                           float *lm_logw, double *totals, void *workspace, int Lcap, hipStream_t st) {
   MmiGraph g;
-  mmi_graph_layout(Q, K, const_cast<void *>(graph), &g);
+  mmi_graph_layout(Q, K, const_cast<void *>(graph), g);
   MmiWs ws;
-  mmi_layout(T, S, K, Q, Lcap, workspace, &ws);
+  mmi_layout(T, S, K, Q, Lcap, workspace, ws);
   hipError_t err = ctc_chain_dispatch(ctc_chain_plan(2 * Lcap + 1), hipErrorInvalidValue, [&](auto nw, auto p) {
     return launch(k_mmi_ref<nw(), p()>, dim3(S, 3), dim3(64 * nw()), 0, st, LaunchProbe{}, y, T, S, K, stride, lens, labels, loff, blank, g, Q,
                   ws);

@@ -10,13 +10,13 @@
 //   z_q = am_scale l_q - logw(sub) + add_scale logw(add) + unit_bonus units_q, in double, left to right
 //   the entries that are well formed and that no model forbids, ranked by z descending, ties to the lower q
 // Two launches:
-//   k_resc_walk   grid (N, S), one wave per entry.  Stages the entry's tokens in LDS with coalesced loads and range-checks them; in
-//                 word mode the lane of a word's first token folds its key, bisects the table and leaves the word's class in LDS;
+//   k_resc_walk   grid (N, S), one wave per entry.  The entry check of klstm_ctc_nbest.h (the contract of a list) stages the tokens in
+//                 LDS; in word mode the lane of a word's first token folds its key, bisects the table and leaves the class in LDS;
 //                 then lane 0 walks `sub` and lane 1 walks `add`, in lockstep: each walk is one chain of dependent loads to which the
 //                 other lanes have nothing to add.  Lane 0 writes the entry's score.
 //   k_resc_rank   grid (S), one wave per stream (N <= 64: it sees the whole list).  Ranks by integer comparison on an order-preserving
 //                 map of the double's bits, writes the order, gathers the re-ranked list (tokens copied by all lanes) and the stream's
-//                 statistics; the last workgroup to arrive (an integer ticket) adds the minibatch onto the totals, streams in order.
+//                 statistics; the last workgroup to arrive (ctc_last_arrival) adds the minibatch onto the totals, streams in order.
 // DETERMINISM.  No floating-point atomics, no reduction over floating-point values: bit-identical from run to run.
 // BOUNDS.  Every loop is bounded by max_len, the table's size, N or SLM_MAXBACK; a token is checked against [0, K) before it is looked
 // up, a word's class against [0, V), a next state against [0, Q), and the bisection of the table stays inside [0, W) whatever it holds.
@@ -25,7 +25,8 @@
 #include <cstdint>
 
 #include "../../include/klstm.h"
-#include "klstm_ctc_dev.h"
+#include "klstm_ctc_host.h"
+#include "klstm_ctc_nbest.h"
 #include "klstm_ctc_slm.h"
 #include "klstm_kernels.h"
 
@@ -34,8 +35,7 @@ namespace klstm {
 constexpr int RESC_TOK = 1024, RESC_WORDS = 512;      // max_len <= 1023 tokens make at most 512 words
 enum { RESC_UNLISTED = 0, RESC_DROPPED = 1, RESC_FORBIDDEN = 2, RESC_LIVE = 3 };
 
-// the caller's arrays
-struct RescIn { const int *hyp, *hyp_len, *count; const float *logp; const int *errors; int stride, N, max_len, K; };
+struct RescIn : NbestIn {};             // the caller's arrays; the ninth member is K (its own type: the kernels keep their names)
 // a model: the blob (null: none), its final weights (or null), its states
 struct RescLm { const void *blob; const float *fin; int Q; };
 // the word table: W sorted keys with their classes (W = 0: token level), the word model's V classes, its reserved class, the class of
@@ -52,31 +52,20 @@ struct RescOut {
   double *totals;
 };
 
-static size_t resc_up256(size_t n) { return (n + 255) / 256 * 256; }
-
-static size_t resc_layout(int S, int N, void *base, RescWs *ws) {
+static size_t resc_layout(int S, int N, void *base, RescWs &ws) {
   const size_t SN = (size_t)S * N;
-  char *p = reinterpret_cast<char *>(base);
-  size_t off = 0;
-  const size_t o_ticket = off; off += 256;
-  const size_t o_info = off;   off += resc_up256((size_t)S * sizeof(int));
-  const size_t o_state = off;  off += resc_up256(SN * sizeof(int));
-  const size_t o_oov = off;    off += resc_up256(SN * sizeof(int));
-  const size_t o_z = off;      off += resc_up256(SN * sizeof(double));
-  const size_t o_stat = off;   off += resc_up256((size_t)S * 8 * sizeof(double));
-  if (ws) {
-    ws->ticket = reinterpret_cast<unsigned *>(p + o_ticket);
-    ws->info = reinterpret_cast<int *>(p + o_info);
-    ws->state = reinterpret_cast<int *>(p + o_state);
-    ws->oov = reinterpret_cast<int *>(p + o_oov);
-    ws->z = reinterpret_cast<double *>(p + o_z);
-    ws->stat = reinterpret_cast<double *>(p + o_stat);
-  }
-  return off;
+  CtcCarver c(base);
+  ws.ticket = c.take<unsigned>(64);
+  ws.info = c.take<int>(S);
+  ws.state = c.take<int>(SN);
+  ws.oov = c.take<int>(SN);
+  ws.z = c.take<double>(SN);
+  ws.stat = c.take<double>((size_t)S * 8);
+  return c.bytes();
 }
 
 // the same bytes with and without a word table: the words' classes live in LDS
-size_t ctc_rescore_workspace_bytes(int S, int N, int /*max_len*/, int /*words*/) { return resc_layout(S, N, nullptr, nullptr); }
+size_t ctc_rescore_workspace_bytes(int S, int N, int /*max_len*/, int /*words*/) { RescWs ws; return resc_layout(S, N, nullptr, ws); }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // One entry: is it well formed, its units, the two walks, its score.  One wave.
@@ -88,25 +77,10 @@ __global__ __launch_bounds__(64) void k_resc_walk(RescIn a, RescLm sub, RescLm a
   int *tok = lds, *wid = lds + RESC_TOK;
   const int q = blockIdx.x, s = blockIdx.y, lane = threadIdx.x, se = s * a.N + q;
   if (se == 0 && lane == 0) *ws.ticket = 0u;                       // for k_resc_rank, the next launch
-  const int cnt = a.count[s];
-  const bool listed = cnt >= 0 && cnt <= a.N && q < cnt;           // slots q >= count are not read
-  bool ok = listed;
-  int len = 0;
-  float lp = 0.f;
-  if (ok) {
-    len = a.hyp_len[se];
-    lp = a.logp[se];
-    ok = isfinite(lp) && len >= 0 && len <= a.stride && len <= a.max_len;      // max_len <= 1023: the tokens fit
-  }
+  KLSTM_NBEST_SHAPE(a, s, q, se, listed, ok, len, lp)              // max_len <= 1023: the tokens fit
   if (ok) {                                                        // uniform over the wave
     const int *h = a.hyp + (size_t)se * a.stride;
-    bool bad = false;
-    for (int t = lane; t < len; t += 64) {
-      const int v = h[t];
-      tok[t] = v;
-      bad |= v < 0 || v >= a.K;
-    }
-    ok = !__any(bad);
+    KLSTM_NBEST_TOKENS(h, len, lane, (tok[t_] = v_, v_ < 0 || v_ >= a.K), ok)
   }
   __syncthreads();
   int nunits = 0, noov = 0;
@@ -114,12 +88,11 @@ __global__ __launch_bounds__(64) void k_resc_walk(RescIn a, RescLm sub, RescLm a
   if (ok && w.W > 0) {
     for (int t0 = 0; t0 < len; t0 += 64) {
       const int t = t0 + lane;
-      const bool start = t < len && tok[t] != w.sep && (t == 0 || tok[t - 1] == w.sep);
+      const bool start = nbest_word_start(tok, len, w.sep, t);
       const unsigned long long mask = __ballot(start);
       bool isoov = false;
       if (start) {                                                 // the lane of a word's first token folds the word and looks it up
-        u64 hs = BEAM_H0;
-        for (int i = t; i < len && tok[i] != w.sep; i++) hs = beam_hash(hs, tok[i]);
+        const u64 hs = nbest_word_key(tok, len, w.sep, t);
         int lo = 0, hi = w.W;
         for (int it = 0; it < 32 && lo < hi; it++) {               // W <= 2^24: 25 halvings at most; lo, hi, mid stay in [0, W]
           const int mid = (lo + hi) >> 1;
@@ -129,7 +102,7 @@ __global__ __launch_bounds__(64) void k_resc_walk(RescIn a, RescLm sub, RescLm a
         if (lo < w.W && w.keys[lo] == hs) id = w.ids[lo];
         isoov = id < 0 || id >= w.V || id == w.reserved;
         if (isoov) id = w.unk >= 0 ? w.unk : -1;                   // -1: the walk stops here
-        wid[nunits + __popcll(mask & ((1ull << lane) - 1ull))] = id;
+        wid[nunits + nbest_word_slot(mask, lane)] = id;
       }
       noov += __popcll(__ballot(isoov));
       nunits += __popcll(mask);
@@ -253,16 +226,8 @@ __global__ __launch_bounds__(64) void k_resc_rank(RescIn a, RescWs ws, int S, Re
   stat[5] = (st == 1 && a.errors) ? (double)a.errors[s * N] : 0.0;
   stat[6] = (st == 1 && a.errors) ? (double)a.errors[s * N + best] : 0.0;
   stat[7] = (double)oov;
-  __threadfence();                                                 // the stream's statistics before its ticket
-  if (atomicAdd(ws.ticket, 1u) != (unsigned)(S - 1)) return;
-  __threadfence();                                                 // the last workgroup: everybody's statistics are visible
-  double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int q = 0; q < S; q++) {
-    const int sq = __hip_atomic_load(ws.info + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    t[sq == 1 ? 0 : 1] += 1.0;
-    for (int i = 2; i < 8; i++) t[i] += __hip_atomic_load(ws.stat + 8 * q + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  for (int i = 0; i < 8; i++) o.totals[i] += t[i];
+  if (!ctc_last_arrival(ws.ticket, S)) return;
+  KLSTM_NBEST_ADD_TOTALS(ws.info, ws.stat, S, 2, o.totals)
 }
 
 hipError_t launch_ctc_rescore(const int *hyp, int hyp_stride, const int *hyp_len, const int *count, const float *logp, const int *errors,
@@ -273,8 +238,8 @@ hipError_t launch_ctc_rescore(const int *hyp, int hyp_stride, const int *hyp_len
                               float *sub_logp, int *units, int *oov, int out_n, int *out_hyp, int out_stride, int *out_len,
                               int *out_count, float *out_score, int *out_errors, double *totals, void *workspace, hipStream_t st) {
   RescWs ws;
-  resc_layout(S, N, workspace, &ws);
-  const RescIn in{hyp, hyp_len, count, logp, errors, hyp_stride, N, max_len, K};
+  resc_layout(S, N, workspace, ws);
+  const RescIn in{{hyp, hyp_len, count, logp, errors, hyp_stride, N, max_len, {K}}};
   const RescLm lsub{sub, sub ? sub_final : nullptr, sub_states}, ladd{add, add ? add_final : nullptr, add_states};
   const RescWords w{word_keys, word_ids, num_words, add_classes, add_reserved, unk_id, separator};
   const RescOut o{order, live_count, out_n, out_stride, out_hyp, out_len, out_count, out_score, out_errors, totals};

@@ -2467,11 +2467,28 @@ klstm_status klstm_ctc_mbr_eval(const float *net_out, int T, int S, int K, int s
                         ref_loss_dev, totals_dev, workspace, lcap, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
-static bool ctc_consensus_shape_ok(int S, int list_n, int max_len) {
+// ---- calls over n-best lists (the consensus, the rescoring): the checks they share, each fired from the place it always had ----
+static bool ctc_nbest_shape_ok(int S, int list_n, int max_len) {
   return S >= 1 && S <= 32 && list_n >= 1 && list_n <= 64 && max_len >= 0 && max_len <= 1023;
 }
+struct CtcNbestCall {
+  const char *fn; int S, list_n, max_len, hyp_stride;
+  klstm_status shape() const {                                     // every limit before any pointer
+    if (ctc_nbest_shape_ok(S, list_n, max_len)) return KLSTM_OK;
+    return fail(KLSTM_ERR_SHAPE, "%s: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", fn, S, list_n, max_len);
+  }
+  klstm_status strides(const char *what, int out_stride, bool written = true) const {      // of hyp, and of the output of whole entries
+    if (hyp_stride > 0 && !(written && out_stride < (hyp_stride < max_len ? hyp_stride : max_len))) return KLSTM_OK;
+    return fail(KLSTM_ERR_ARG, "%s: hypothesis stride %d, %s stride %d (at least min(hypothesis stride, length %d))", fn, hyp_stride, what, out_stride, max_len);
+  }
+  klstm_status workspace(const void *ws, size_t bytes, const char *size_fn, int word_mode, size_t need) const {      // alignment, then size
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
+    if (bytes >= need) return KLSTM_OK;
+    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below %s(%d, %d, %d, %d) = %zu", fn, bytes, size_fn, S, list_n, max_len, word_mode, need);
+  }
+};
 size_t klstm_ctc_consensus_workspace_bytes(int S, int list_n, int max_len, int word_mode) {
-  if (!ctc_consensus_shape_ok(S, list_n, max_len)) {
+  if (!ctc_nbest_shape_ok(S, list_n, max_len)) {
     fail(KLSTM_ERR_SHAPE, "klstm_ctc_consensus_workspace_bytes: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", S, list_n, max_len);
     return 0;
   }
@@ -2483,31 +2500,24 @@ klstm_status klstm_ctc_consensus(const int *hyp_dev, int hyp_stride, const int *
                                  float *conf_dev, int conf_stride, int *dist_dev, double *totals_dev, void *workspace, size_t workspace_bytes,
                                  void *hip_stream) {
   const char *fn = "klstm_ctc_consensus";
-  if (!ctc_consensus_shape_ok(S, list_n, max_len))                 // (every limit before any pointer)
-    return fail(KLSTM_ERR_SHAPE, "%s: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", fn, S, list_n, max_len);
-  if (hyp_stride <= 0 || conf_stride < (hyp_stride < max_len ? hyp_stride : max_len))
-    return fail(KLSTM_ERR_ARG, "%s: hypothesis stride %d, confidence stride %d (at least min(hypothesis stride, length %d))", fn, hyp_stride, conf_stride, max_len);
+  const CtcNbestCall call{fn, S, list_n, max_len, hyp_stride};
+  if (klstm_status st = call.shape(); st != KLSTM_OK) return st;
+  if (klstm_status st = call.strides("confidence", conf_stride); st != KLSTM_OK) return st;
   if (!(scale > 0.f) || !std::isfinite(scale)) return fail(KLSTM_ERR_ARG, "%s: scale %g is not a finite number above 0", fn, (double)scale);
   if (pivot_mode != 0 && pivot_mode != 1) return fail(KLSTM_ERR_ARG, "%s: pivot mode %d is neither 0 (MAP) nor 1 (MBR)", fn, pivot_mode);
   if (!hyp_dev || !hyp_len_dev || !nbest_count_dev || !logp_dev || !pick_dev || !map_dev || !mbr_dev || !post_dev || !risk_dev || !unit_len_dev ||
       !conf_dev || !workspace)
     return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
-  const size_t need = ctc_consensus_workspace_bytes(S, list_n, max_len, separator >= 0);
-  if (workspace_bytes < need)
-    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_consensus_workspace_bytes(%d, %d, %d, %d) = %zu", fn, workspace_bytes,
-                S, list_n, max_len, (int)(separator >= 0), need);
+  if (klstm_status st = call.workspace(workspace, workspace_bytes, "klstm_ctc_consensus_workspace_bytes", separator >= 0,
+                                       ctc_consensus_workspace_bytes(S, list_n, max_len, separator >= 0)); st != KLSTM_OK) return st;
   HIPCHK(launch_ctc_consensus(hyp_dev, hyp_stride, hyp_len_dev, nbest_count_dev, logp_dev, errors_dev, S, list_n, max_len, scale, separator,
                               pivot_mode, pick_dev, map_dev, mbr_dev, post_dev, risk_dev, unit_len_dev, conf_dev, conf_stride, dist_dev,
                               totals_dev, workspace, (hipStream_t)hip_stream));
   return KLSTM_OK;
 }
 // ---- second-pass rescoring of n-best lists.  The models are blobs of klstm_ctc_slm_build, known by their addresses ----
-static bool ctc_rescore_shape_ok(int S, int list_n, int max_len) {
-  return S >= 1 && S <= 32 && list_n >= 1 && list_n <= 64 && max_len >= 0 && max_len <= 1023;
-}
 size_t klstm_ctc_rescore_workspace_bytes(int S, int list_n, int max_len, int word_mode) {
-  if (!ctc_rescore_shape_ok(S, list_n, max_len)) {
+  if (!ctc_nbest_shape_ok(S, list_n, max_len)) {
     fail(KLSTM_ERR_SHAPE, "klstm_ctc_rescore_workspace_bytes: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", S, list_n, max_len);
     return 0;
   }
@@ -2523,8 +2533,8 @@ klstm_status klstm_ctc_nbest_rescore(const int *hyp_dev, int hyp_stride, const i
                                      int out_stride, int *out_len_dev, int *out_count_dev, float *out_score_dev, int *out_errors_dev,
                                      double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
   const char *fn = "klstm_ctc_nbest_rescore";
-  if (!ctc_rescore_shape_ok(S, list_n, max_len))                   // (every limit before any pointer)
-    return fail(KLSTM_ERR_SHAPE, "%s: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", fn, S, list_n, max_len);
+  const CtcNbestCall call{fn, S, list_n, max_len, hyp_stride};
+  if (klstm_status st = call.shape(); st != KLSTM_OK) return st;
   if (K < 2 || K > 32768) return fail(KLSTM_ERR_SHAPE, "%s: %d classes outside 2 <= K <= 32768", fn, K);
   if (num_words < 0 || num_words > (1 << 24)) return fail(KLSTM_ERR_SHAPE, "%s: %d words outside 0 <= words <= 2^24", fn, num_words);
   if (out_n < 0 || out_n > list_n) return fail(KLSTM_ERR_SHAPE, "%s: a list of %d out of a list of %d", fn, out_n, list_n);
@@ -2532,8 +2542,7 @@ klstm_status klstm_ctc_nbest_rescore(const int *hyp_dev, int hyp_stride, const i
     return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
   if (out_n >= 1 && (!out_hyp_dev || !out_len_dev || !out_count_dev || !out_score_dev))
     return fail(KLSTM_ERR_ARG, "%s: null list output with out_n %d", fn, out_n);
-  if (hyp_stride <= 0 || (out_n >= 1 && out_stride < (hyp_stride < max_len ? hyp_stride : max_len)))
-    return fail(KLSTM_ERR_ARG, "%s: hypothesis stride %d, output stride %d (at least min(hypothesis stride, length %d))", fn, hyp_stride, out_stride, max_len);
+  if (klstm_status st = call.strides("output", out_stride, out_n >= 1); st != KLSTM_OK) return st;
   if (!std::isfinite(am_scale) || !std::isfinite(add_scale) || !std::isfinite(unit_bonus))
     return fail(KLSTM_ERR_ARG, "%s: scales %g, %g and bonus %g must be finite", fn, (double)am_scale, (double)add_scale, (double)unit_bonus);
   if (!sub_slm && !add_slm) return fail(KLSTM_ERR_ARG, "%s: neither a model to subtract nor one to add", fn);
@@ -2554,11 +2563,8 @@ klstm_status klstm_ctc_nbest_rescore(const int *hyp_dev, int hyp_stride, const i
     const char *f = ctc_slm_finding(add_slm, add_bytes, add_states, add_classes);
     if (f) return fail(KLSTM_ERR_ARG, "%s: add: %s", fn, f);
   }
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
-  const size_t need = ctc_rescore_workspace_bytes(S, list_n, max_len, num_words > 0);
-  if (workspace_bytes < need)
-    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_rescore_workspace_bytes(%d, %d, %d, %d) = %zu", fn, workspace_bytes,
-                S, list_n, max_len, (int)(num_words > 0), need);
+  if (klstm_status st = call.workspace(workspace, workspace_bytes, "klstm_ctc_rescore_workspace_bytes", num_words > 0,
+                                       ctc_rescore_workspace_bytes(S, list_n, max_len, num_words > 0)); st != KLSTM_OK) return st;
   HIPCHK(launch_ctc_rescore(hyp_dev, hyp_stride, hyp_len_dev, nbest_count_dev, logp_dev, errors_dev, S, list_n, max_len, K, sub_slm, sub_states,
                             sub_final_dev, add_slm, add_states, add_classes, add_final_dev, word_keys_dev, word_ids_dev, num_words, unk_id,
                             separator, add_reserved, am_scale, add_scale, unit_bonus, order_dev, live_count_dev, score_dev, add_logp_dev,

@@ -17,6 +17,7 @@ import ctypes
 import numpy as np
 
 from .binding import _chk, _sp, load_library
+from .lm import split_words
 
 _WS = {}          # operation -> {(device, the shape its workspace depends on) -> uint8 workspace tensor}
 
@@ -342,6 +343,30 @@ def _as_nbest(nbest):
     return nbest
 
 
+def _nbest_arrays(nbest, logp=None, errors=None, need_logp=True):
+    """The n-best argument of ctc_mbr_eval, ctc_nbest_consensus and ctc_nbest_rescore: a CtcBeamResult, the dict of ctc_nbest_rescore,
+    or a tuple (hyp [S, N, stride], hyp_len [S, N], nbest_count [S], errors [S, N] or None) of int32 CUDA tensors.  logp, errors: the
+    caller's own, which go before the result's score and errors (need_logp False: no scores are looked at).  -> hyp, hyp_len, count, errors, logp, S, N, stride, checked."""
+    import torch
+    nbest = _as_nbest(nbest)
+    if isinstance(nbest, CtcBeamResult):
+        hyp, hyp_len, count, own_errors, score = nbest.hyp, nbest.hyp_len, nbest.nbest_count, nbest.errors, nbest.score
+    else:
+        (hyp, hyp_len, count, own_errors), score = nbest, None
+    if logp is None:
+        logp = score if need_logp else None
+    assert logp is not None or not need_logp, "a tuple of lists carries no scores: pass logp"
+    if errors is None:
+        errors = own_errors
+    for t in (hyp, hyp_len, count) + ((errors,) if errors is not None else ()):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    assert hyp.dim() == 3 and count.numel() == hyp.shape[0]
+    S, N, stride = (int(v) for v in hyp.shape)
+    assert hyp_len.shape == (S, N) and (errors is None or errors.shape == (S, N))
+    assert logp is None or (logp.is_cuda and logp.dtype == torch.float32 and logp.shape == (S, N) and logp.is_contiguous())
+    return hyp, hyp_len, count, errors, logp, S, N, stride
+
+
 def nbest_to_lists(result):
     """CtcBeamResult (or the dict of ctc_nbest_rescore) -> per stream a list of (hypothesis list, score, errors or None), best first.
     The one place that synchronises."""
@@ -494,14 +519,9 @@ def ctc_mbr_eval(net_out, lens, nbest, refs=None, blank=0, risk_scale=1.0, ctc_w
     lib = load_library()
     dev = net_out.device
     lens_dev, S, T, K = _shape(net_out, lens)
-    nbest = _as_nbest(nbest)
-    hyp, hyp_len, count, errors = (nbest.hyp, nbest.hyp_len, nbest.nbest_count, nbest.errors) if isinstance(nbest, CtcBeamResult) else nbest
+    hyp, hyp_len, count, errors, _, Sn, N, hyp_stride = _nbest_arrays(nbest, need_logp=False)
     assert errors is not None, "the n-best lists carry no edit distances (decode with refs)"
-    for t in (hyp, hyp_len, count, errors):
-        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
-    assert hyp.dim() == 3 and hyp.shape[0] == S and count.numel() == S
-    N, hyp_stride = int(hyp.shape[1]), int(hyp.shape[2])
-    assert hyp_len.shape == (S, N) and errors.shape == (S, N)
+    assert Sn == S
     with_ref = float(ctc_weight) > 0
     lab_dev = off_dev = ref_loss = None
     longest = 0
@@ -548,23 +568,8 @@ def ctc_nbest_consensus(nbest, logp=None, scale=1.0, separator=None, pivot="mbr"
     them, entries dropped, sum of errors[pick] and sum of errors[map] are added to.  Nothing synchronises; consensus_to_lists() does."""
     import torch
     lib = load_library()
-    nbest = _as_nbest(nbest)
-    if isinstance(nbest, CtcBeamResult):
-        hyp, hyp_len, count, own_errors, score = nbest.hyp, nbest.hyp_len, nbest.nbest_count, nbest.errors, nbest.score
-    else:
-        (hyp, hyp_len, count, own_errors), score = nbest, None
-    if logp is None:
-        logp = score
-    assert logp is not None, "a tuple of lists carries no scores: pass logp"
-    if errors is None:
-        errors = own_errors
+    hyp, hyp_len, count, errors, logp, S, N, stride = _nbest_arrays(nbest, logp, errors)
     dev = hyp.device
-    for t in (hyp, hyp_len, count) + ((errors,) if errors is not None else ()):
-        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
-    assert hyp.dim() == 3 and count.numel() == hyp.shape[0]
-    S, N, stride = (int(v) for v in hyp.shape)
-    assert hyp_len.shape == (S, N) and (errors is None or errors.shape == (S, N))
-    assert logp.is_cuda and logp.dtype == torch.float32 and logp.shape == (S, N) and logp.is_contiguous()
     assert pivot in ("map", "mbr")
     sep = -1 if separator is None else int(separator)
     assert separator is None or sep >= 0, "the separator is a class"
@@ -599,16 +604,7 @@ def consensus_to_lists(result, nbest, separator=None):
             out.append(None)
             continue
         toks = h[s, p, :n[s, p]].tolist()
-        if separator is None:
-            units = toks
-        else:
-            units, word = [], []
-            for t in toks + [int(separator)]:
-                if t != int(separator):
-                    word.append(t)
-                elif word:
-                    units.append(word)
-                    word = []
+        units = toks if separator is None else split_words(toks, int(separator))
         out.append(dict(pick=int(p), units=[(u, float(conf[s, i])) for i, u in enumerate(units)], risk=float(risk[s, p])))
     return out
 
@@ -635,7 +631,7 @@ def ctc_nbest_rescore(nbest, add=None, sub=None, words=None, am_scale=1.0, add_s
                       totals=None, stream=None, logp=None, out_stride=None, classes=None):
     """Second-pass rescoring of n-best lists (klstm_ctc_nbest_rescore of include/klstm.h, which defines every quantity).  nbest: the
     CtcBeamResult of ctc_beam_decode, or a tuple (hyp [S, N, stride] int32, hyp_len [S, N], nbest_count [S], errors [S, N] or None) of
-    CUDA tensors with logp [S, N] float32 given.  sub: None, or the CtcSparseLabelLm the first pass fused, whose score is taken out;
+    CUDA tensors with logp [S, N] float32 given, or the dict of an earlier rescoring (its re-ranked list).  sub: None, or the CtcSparseLabelLm the first pass fused, whose score is taken out;
     add: None, or the CtcSparseLabelLm whose score is put in -- over the tokens, or with words (a CtcWordTable) over the words, its
     reserved class being the blank it was built with.  z = am_scale * logp - logw(sub) + add_scale * logw(add) + unit_bonus * units.
     out_n: how many entries of the ranking the re-ranked list keeps (None: N; 0: none); classes: the token classes K (None: sub's, or
@@ -647,20 +643,8 @@ def ctc_nbest_rescore(nbest, add=None, sub=None, words=None, am_scale=1.0, add_s
     of vocabulary are added to.  Nothing synchronises."""
     import torch
     lib = load_library()
-    if isinstance(nbest, CtcBeamResult):
-        hyp, hyp_len, count, errors, score = nbest.hyp, nbest.hyp_len, nbest.nbest_count, nbest.errors, nbest.score
-    else:
-        (hyp, hyp_len, count, errors), score = nbest, None
-    if logp is None:
-        logp = score
-    assert logp is not None, "a tuple of lists carries no scores: pass logp"
+    hyp, hyp_len, count, errors, logp, S, N, stride = _nbest_arrays(nbest, logp)
     dev = hyp.device
-    for t in (hyp, hyp_len, count) + ((errors,) if errors is not None else ()):
-        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
-    assert hyp.dim() == 3 and count.numel() == hyp.shape[0]
-    S, N, stride = (int(v) for v in hyp.shape)
-    assert hyp_len.shape == (S, N) and (errors is None or errors.shape == (S, N))
-    assert logp.is_cuda and logp.dtype == torch.float32 and logp.shape == (S, N) and logp.is_contiguous()
     for m in (add, sub):
         assert m is None or (isinstance(m, CtcSparseLabelLm) and m.blob.device == dev), "the models are CtcSparseLabelLm on the lists' device"
     assert words is None or isinstance(words, CtcWordTable)

@@ -383,7 +383,7 @@ def backoff_ngram_label_lm(sequences, K, blank, order=3, discount=0.75, alpha=1.
 # model is a SparseLm over V classes, one per word of the vocabulary, one for unknown words if wanted, and one reserved: the `blank`
 # it is built with, which no word ever maps to.
 # ------------------------------------------------------------------------------------------------------------------------------------
-_WORD_H0, _WORD_HMUL, _M64 = 0x243F6A8885A308D3, 0x9E3779B97F4A7C15, (1 << 64) - 1      # BEAM_H0, BEAM_HMUL of csrc/klstm_ctc_dev.h
+_WORD_H0, _WORD_HMUL, _M64 = 0x243F6A8885A308D3, 0x9E3779B97F4A7C15, (1 << 64) - 1      # KLSTM_CTC_HASH_START, KLSTM_CTC_HASH_MUL of include/klstm.h
 
 
 def word_key(tokens):
@@ -393,6 +393,18 @@ def word_key(tokens):
         x = ((h ^ ((int(c) + 1) & 0xFFFFFFFF)) * _WORD_HMUL) & _M64
         h = x ^ (x >> 29)
     return h
+
+
+def split_words(tokens, separator):
+    """-> the words: the maximal runs of tokens other than the separator, none empty (the device's rule: csrc/klstm_ctc_nbest.h)"""
+    words, word = [], []
+    for t in [int(c) for c in tokens] + [separator]:
+        if t != separator:
+            word.append(t)
+        elif word:
+            words.append(word)
+            word = []
+    return words
 
 
 def word_table(words, separator, ids=None):
@@ -422,16 +434,8 @@ def word_sequences(label_seqs, table, separator, unk_id):
     index = {int(k): int(i) for k, i in zip(keys, ids)}
     out = []
     for seq in label_seqs:
-        row, word, ok = [], [], True
-        for t in [int(c) for c in seq] + [separator]:
-            if t != separator:
-                word.append(t)
-            elif word:
-                i = index.get(word_key(word), unk_id)
-                ok &= i >= 0
-                row.append(i)
-                word = []
-        if ok:
+        row = [index.get(word_key(word), unk_id) for word in split_words(seq, separator)]
+        if all(i >= 0 for i in row):
             out.append(row)
     return out
 

@@ -1,9 +1,12 @@
 // tests/cpp/ctc_plan_test.cpp -- the host helpers of the CTC lattice losses (csrc/klstm_ctc_host.h: ctc_chain_plan, ctc_chain_dispatch,
-// ctc_label_capacity_of, ctc_npad, ctc_up256) without a device: the plan table at both edges of every plan, the dispatcher's pair for
-// every plan and its error for any other, the bisection over a toy byte count and over the loss's formula, which this file computes
-// for itself.  Built with -fsanitize=address,undefined and run on the host (tests/test_ctc_plan.py).
+// ctc_label_capacity_of, ctc_npad, ctc_up256, CtcCarver) without a device: the plan table at both edges of every plan, the dispatcher's
+// pair for every plan and its error for any other, the bisection over a toy byte count and over the loss's formula, which this file
+// computes for itself, and the carver of a workspace over a null and over a real base.  Built with -fsanitize=address,undefined and run on the host (tests/test_ctc_plan.py).
+#include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <initializer_list>
+#include <vector>
 
 #include "../../kaldi-lstm_amd/csrc/klstm_ctc_host.h"
 
@@ -49,7 +52,55 @@ static int check_capacity(F bytes_at) {
   return steps;
 }
 
+// A layout of every kind of region (the shape of cons_layout and mbr_layout: rounded regions of several types, one left out on a flag,
+// packed bulk rows at the end), written through so that the sanitizer sees every byte a region owns.
+struct Carved { std::vector<std::pair<char *, size_t> > regions; size_t bytes; };
+static Carved carve(void *base, size_t n, bool with_keys) {
+  CtcCarver c(base);
+  Carved out;
+  auto note = [&](void *p, size_t bytes) { out.regions.push_back({static_cast<char *>(p), bytes}); };
+  note(c.take<unsigned>(64), 64 * sizeof(unsigned));
+  note(c.take<int>(n), n * sizeof(int));
+  note(c.take<double>(3 * n), 3 * n * sizeof(double));
+  note(c.take<unsigned char>(n + 1), n + 1);
+  if (with_keys) note(c.take<unsigned long long>(n), n * sizeof(unsigned long long));
+  const size_t rounded = out.regions.size();
+  note(c.packed<float>(4 * n + 4), (4 * n + 4) * sizeof(float));
+  note(c.packed<float>(4 * n + 4), (4 * n + 4) * sizeof(float));
+  out.bytes = c.bytes();
+  CHECK(rounded == (with_keys ? 5u : 4u));
+  return out;
+}
+
+static void check_carver() {
+  for (size_t n : {(size_t)1, (size_t)63, (size_t)64, (size_t)65, (size_t)1000})
+    for (bool with_keys : {false, true}) {
+      const Carved count = carve(nullptr, n, with_keys);           // a null base only counts
+      for (const auto &r : count.regions) CHECK(r.first == nullptr);
+      std::vector<char> raw(count.bytes + 256);
+      char *base = raw.data() + (256 - reinterpret_cast<uintptr_t>(raw.data()) % 256) % 256;
+      const Carved real = carve(base, n, with_keys);
+      CHECK(real.bytes == count.bytes && real.regions.size() == count.regions.size());      // ... what a real base consumes
+      const size_t rounded = with_keys ? 5 : 4;
+      char *end = base;
+      for (size_t i = 0; i < real.regions.size(); i++) {
+        const auto &r = real.regions[i];
+        CHECK(r.first == end);                                     // in order, disjoint, nothing between them but the rounding
+        if (i <= rounded) CHECK(reinterpret_cast<uintptr_t>(r.first) % 256 == 0);           // every take, and the first packed one
+        std::memset(r.first, (int)i + 1, r.second);                // inside raw, or the sanitizer says so
+        end = r.first + (i < rounded ? ctc_up256(r.second) : r.second);
+      }
+      CHECK(end == base + real.bytes);
+      for (size_t i = 0; i < real.regions.size(); i++)             // nobody wrote into a neighbour
+        CHECK(real.regions[i].first[0] == (char)(i + 1) && real.regions[i].first[real.regions[i].second - 1] == (char)(i + 1));
+      CHECK(count.bytes == 256 + ctc_up256(4 * n) + ctc_up256(24 * n) + ctc_up256(n + 1) + (with_keys ? ctc_up256(8 * n) : 0) + 2 * (16 * n + 16));
+    }
+  CtcCarver empty(nullptr);
+  CHECK(empty.bytes() == 0 && empty.take<int>(0) == nullptr && empty.bytes() == 0);
+}
+
 int main() {
+  check_carver();
   // the plan table: 16 * waves + states per thread
   const struct { int N, nw, p; } table[] = {{1, 1, 1},    {63, 1, 1},   {64, 1, 1},    {65, 4, 1},    {255, 4, 1},   {256, 4, 1},  {257, 4, 2},
                                            {511, 4, 2},  {512, 4, 2},  {513, 16, 1},  {1023, 16, 1}, {1024, 16, 1}, {1025, 16, 2}, {2047, 16, 2}};

@@ -21,20 +21,12 @@ import math
 
 import numpy as np
 
-from tests.ctc_decode_ref import levenshtein
+from tests.nbest_ref import H0 as H_EMPTY, beam_hash as hash_step, levenshtein  # noqa: F401  (levenshtein: for the tests)
 
 F = np.float32
 TINY = F(2.0 ** -60)
 HUGE = F(2.0 ** 60)
-H_EMPTY = 0x243F6A8885A308D3
-H_MUL = 0x9E3779B97F4A7C15
-M64 = (1 << 64) - 1
 LN2 = math.log(2.0)
-
-
-def hash_step(h, c):
-    x = ((h ^ (c + 1)) * H_MUL) & M64
-    return x ^ (x >> 29)
 
 
 def prefix_hash(prefix):

@@ -6,35 +6,16 @@ import math
 
 import numpy as np
 
-H0, HMUL = 0x243F6A8885A308D3, 0x9E3779B97F4A7C15      # BEAM_H0, BEAM_HMUL of klstm_ctc_dev.h: the search's initial prefix hash, its multiplier
-M64 = (1 << 64) - 1
+from tests.nbest_ref import H0, HMUL, M64, beam_hash, levenshtein, split_words, word_key  # noqa: F401  (for the tests)
+
 TOTALS = 10
-
-
-def beam_hash(h, c):
-    x = ((h ^ ((c + 1) & 0xFFFFFFFF)) * HMUL) & M64
-    return x ^ (x >> 29)
-
-
-def word_key(tokens):
-    h = H0
-    for c in tokens:
-        h = beam_hash(h, int(c))
-    return h
 
 
 def units_of(tokens, separator):
     """the unit keys of a token list: the tokens, or the keys of its words (maximal runs of tokens other than the separator)"""
     if separator < 0:
         return [int(t) for t in tokens]
-    out, word = [], []
-    for t in list(tokens) + [separator]:
-        if t != separator:
-            word.append(int(t))
-        elif word:
-            out.append(word_key(word))
-            word = []
-    return out
+    return [word_key(w) for w in split_words(tokens, separator)]
 
 
 def table(a, b):
@@ -47,20 +28,6 @@ def table(a, b):
         for j in range(1, len(b) + 1):
             D[i][j] = min(D[i - 1][j] + 1, D[i][j - 1] + 1, D[i - 1][j - 1] + (a[i - 1] != b[j - 1]))
     return D
-
-
-def levenshtein(a, b):
-    """two rows in numpy: D[j] = j + the running minimum of (tmp[j] - j), the device's row formulation"""
-    a, b = (a, b) if len(a) >= len(b) else (b, a)
-    cols = np.asarray(a, dtype=np.uint64)
-    j = np.arange(len(a) + 1)
-    prev = j.copy()
-    for i, tok in enumerate(b, 1):
-        tmp = np.empty_like(prev)
-        tmp[0] = i
-        tmp[1:] = np.minimum(prev[1:] + 1, prev[:-1] + (cols != np.uint64(tok)))
-        prev = j + np.minimum.accumulate(tmp - j)
-    return int(prev[-1])
 
 
 def table_rows(a, b):

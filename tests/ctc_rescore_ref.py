@@ -10,6 +10,7 @@ import numpy as np
 import kaldi_lstm_amd.lm as LM
 from kaldi_lstm_amd.lm import word_sequences, word_table
 from tests.ctc_consensus_ref import units_of, word_key  # noqa: F401  (word_key: for the tests)
+from tests.nbest_ref import pack
 
 TOTALS = 8
 LN2 = 0.6931471805599453
@@ -261,17 +262,6 @@ def lists_from_corpus(seed, corpus, S, N, K, blank=0, stride=None, spread=6.0):
         rng.shuffle(ent)
         rows.append(ent)
     return pack(rows, stride) + (-np.sort(spread * rng.random((S, N)), axis=1).astype(F32),)
-
-
-def pack(rows, stride=None, fill=0):
-    """[stream][entry] token lists -> hyp [S, N, stride], hyp_len [S, N], count [S]"""
-    S, N = len(rows), max(len(e) for e in rows)
-    stride = stride or max([len(h) for e in rows for h in e] + [1])
-    hyp, hyp_len = np.full((S, N, stride), fill, np.int32), np.zeros((S, N), np.int32)
-    for s, ent in enumerate(rows):
-        for q, h in enumerate(ent):
-            hyp[s, q, :len(h)], hyp_len[s, q] = h, len(h)
-    return hyp, hyp_len, np.array([len(e) for e in rows], np.int32)
 
 
 def word_setup(seed=3, K=8, nwords=30, sep=0):

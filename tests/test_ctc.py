@@ -3,38 +3,22 @@ tests/cpp/ctc_test (whose build also shows that Ctc / TrainCtcWholeUtterances of
 yardstick of tests/test_ctc_gpu.py pinned without torch (all alignments of a tiny case enumerated in float64), the kernel's recipe --
 normalised log-domain recursions in float32, tests/ctc_ref.norm_twin -- against that yardstick under the GPU tests' bars, and the
 host-side limits of the C-ABI."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from tests import cpp_driver
 from tests import ctc_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "ctc_test")
-SRC = EXE + ".cpp"
-HDRS = [os.path.join(ROOT, "include", h) for h in ("klstm.h", "klstm_component.hpp", "klstm_kaldi_io.hpp", "klstm_trainer.hpp",
-                                                   "klstm_nnet.hpp", "klstm_blstm.hpp")]
 
 
 def build_ctc_driver():
-    import kaldi_lstm_amd as k
-    lib = k.lib_path()
-    assert os.path.exists(lib), "libklstm.so missing: run __graft_entry__.build()"
-    stale = (not os.path.exists(EXE)) or any(os.path.getmtime(f) > os.path.getmtime(EXE) for f in [SRC] + HDRS)
-    if stale:
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-I" + os.path.join(ROOT, "include"), SRC,
-                               "-L" + os.path.dirname(lib), "-lklstm", "-Wl,-rpath,$ORIGIN/../../kaldi-lstm_amd", "-o", EXE])
-    return EXE
+    return cpp_driver.build("ctc_test")
 
 
 def run_driver(*args, ok=True):
-    r = subprocess.run([build_ctc_driver()] + [str(a) for a in args], capture_output=True, text=True, timeout=900)
-    if ok:
-        assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
-    return r
+    return cpp_driver.run("ctc_test", *args, ok=ok)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

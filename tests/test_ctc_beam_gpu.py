@@ -7,6 +7,7 @@ import pytest
 
 from tests import ctc_beam_ref as Bm
 from tests import ctc_decode_ref as D
+from tests.nbest_ref import ulps
 from tests.test_ctc_beam import (GRID_SEEDS, all_prefixes, exhaustive_case, grid_case, margin, score_excess, softmax_rows)
 
 pytestmark = pytest.mark.gpu
@@ -33,15 +34,6 @@ def run(y, lens, blank, B, C, N, w=None, refs=None, window=None):
     res = k.ctc_beam_decode(to_dev(y, window), lens, blank=blank, beam=B, cands=C, nbest=N, class_weight=wd, refs=refs, totals=tot)
     torch.cuda.synchronize()
     return res, (tot.cpu().numpy().tolist() if tot is not None else None)
-
-
-def ulps(a, b):
-    a, b = np.float32(a), np.float32(b)
-    if a == b:
-        return 0
-    if not (np.isfinite(a) and np.isfinite(b)) or (a < 0) != (b < 0):
-        return 1 << 30
-    return abs(int(a.view(np.int32)) - int(b.view(np.int32)))
 
 
 def check(res, totals, tw, N):

@@ -4,37 +4,24 @@ reader against a dense table computed independently from the file's probabilitie
 meet its condition; the host mirror of the device's validation; the C++ reader writes the arrays of the Python reader."""
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cpp_driver
 from tests import ctc_beam_ref as Bm
 from tests import ctc_beam_slm_ref as R
 from tests.test_ctc_beam import softmax_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "ctc_beam_slm_test")
-SRC = EXE + ".cpp"
-HDRS = [os.path.join(ROOT, "include", h) for h in ("klstm.h", "klstm_component.hpp", "klstm_kaldi_io.hpp", "klstm_trainer.hpp",
-                                                   "klstm_nnet.hpp", "klstm_blstm.hpp")]
 
 
 def build_ctc_beam_slm_driver():
-    import kaldi_lstm_amd as k
-    lib = k.lib_path()
-    assert os.path.exists(lib), "libklstm.so missing: run __graft_entry__.build()"
-    stale = (not os.path.exists(EXE)) or any(os.path.getmtime(f) > os.path.getmtime(EXE) for f in [SRC] + HDRS)
-    if stale:
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-I" + os.path.join(ROOT, "include"), SRC,
-                               "-L" + os.path.dirname(lib), "-lklstm", "-Wl,-rpath,$ORIGIN/../../kaldi-lstm_amd", "-o", EXE])
-    return EXE
+    return cpp_driver.build("ctc_beam_slm_test")
 
 
 def run_driver(*args):
-    r = subprocess.run([build_ctc_beam_slm_driver()] + [str(a) for a in args], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
-    return r
+    return cpp_driver.run("ctc_beam_slm_test", *args)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import cpp_driver
 from tests import ctc_beam_lm_ref as L
 from tests import ctc_beam_ref as Bm
 from tests import ctc_beam_stream_ref as R
@@ -14,27 +15,14 @@ from tests.test_ctc_beam import softmax_rows
 from tests.test_ctc_beam_lm import bigram_next
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "ctc_beam_stream_test")
-SRC = EXE + ".cpp"
-HDRS = [os.path.join(ROOT, "include", h) for h in ("klstm.h", "klstm_component.hpp", "klstm_kaldi_io.hpp", "klstm_trainer.hpp",
-                                                   "klstm_nnet.hpp", "klstm_blstm.hpp", "klstm_scorer.hpp")]
 
 
 def build_ctc_beam_stream_driver():
-    import kaldi_lstm_amd as k
-    lib = k.lib_path()
-    assert os.path.exists(lib), "libklstm.so missing: run __graft_entry__.build()"
-    stale = (not os.path.exists(EXE)) or any(os.path.getmtime(f) > os.path.getmtime(EXE) for f in [SRC] + HDRS)
-    if stale:
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-I" + os.path.join(ROOT, "include"), SRC,
-                               "-L" + os.path.dirname(lib), "-lklstm", "-Wl,-rpath,$ORIGIN/../../kaldi-lstm_amd", "-o", EXE])
-    return EXE
+    return cpp_driver.build("ctc_beam_stream_test", headers=cpp_driver.HEADERS + ("klstm_scorer.hpp",))
 
 
 def run_driver(*args):
-    r = subprocess.run([build_ctc_beam_stream_driver()] + [str(a) for a in args], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
-    return r
+    return cpp_driver.run("ctc_beam_stream_test", *args, headers=cpp_driver.HEADERS + ("klstm_scorer.hpp",))
 
 
 def bits(v):

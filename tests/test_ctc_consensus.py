@@ -3,49 +3,27 @@
 and the word tokenisation on hand-written cases, and the limits of the library's entry."""
 import ctypes
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cpp_driver
 from tests import ctc_consensus_ref as C
+from tests import nbest_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "ctc_consensus_test")
-SRC = EXE + ".cpp"
-HDRS = [os.path.join(ROOT, "include", h) for h in ("klstm.h", "klstm_component.hpp", "klstm_kaldi_io.hpp", "klstm_trainer.hpp",
-                                                   "klstm_nnet.hpp", "klstm_blstm.hpp")]
 
 
 def build_ctc_consensus_driver():
-    import kaldi_lstm_amd as k
-    lib = k.lib_path()
-    assert os.path.exists(lib), "libklstm.so missing: run __graft_entry__.build()"
-    stale = (not os.path.exists(EXE)) or any(os.path.getmtime(f) > os.path.getmtime(EXE) for f in [SRC] + HDRS)
-    if stale:
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-I" + os.path.join(ROOT, "include"), SRC,
-                               "-L" + os.path.dirname(lib), "-lklstm", "-Wl,-rpath,$ORIGIN/../../kaldi-lstm_amd", "-o", EXE])
-    return EXE
+    return cpp_driver.build("ctc_consensus_test")
 
 
 def run_driver(*args, ok=True):
-    r = subprocess.run([build_ctc_consensus_driver()] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
-    if ok:
-        assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
-    return r
+    return cpp_driver.run("ctc_consensus_test", *args, ok=ok, timeout=300)
 
 
 def pack(lists, stride=None):
-    """[stream][entry] token lists -> hyp [S, N, stride], hyp_len, count"""
-    S, N = len(lists), max(len(e) for e in lists)
-    stride = stride or max([len(h) for e in lists for h in e] + [1])
-    hyp, hyp_len = np.full((S, N, stride), 10 ** 6, np.int32), np.full((S, N), -7, np.int32)
-    for s, ent in enumerate(lists):
-        for q, h in enumerate(ent):
-            hyp[s, q, :len(h)] = h
-            hyp_len[s, q] = len(h)
-    return hyp, hyp_len, np.array([len(e) for e in lists], np.int32)
+    """nbest_ref.pack with garbage in what the device may not read"""
+    return nbest_ref.pack(lists, stride, fill=10 ** 6, len_fill=-7)
 
 
 @pytest.mark.parametrize("seed,N,L,sep", [(0, 2, 1, -1), (1, 8, 12, -1), (2, 16, 30, -1), (3, 8, 40, 3), (4, 5, 0, -1)])

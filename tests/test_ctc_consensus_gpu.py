@@ -17,22 +17,10 @@ import torch
 
 from tests import ctc_consensus_ref as C
 from tests.margins import bound
+from tests.nbest_ref import garbage, ulps
 
 pytestmark = pytest.mark.gpu
 GAP = 1e-9
-
-
-def garbage(case):
-    """10^6 in every token that may not be read, -7 / NaN in every list slot beyond the count"""
-    hyp, hyp_len, count, logp = (np.array(case[k]) for k in ("hyp", "hyp_len", "count", "logp"))
-    S, N, stride = hyp.shape
-    for s in range(S):
-        for q in range(N):
-            if 0 <= count[s] <= N and q >= count[s]:
-                hyp[s, q], hyp_len[s, q], logp[s, q] = 10 ** 6, -7, np.nan
-            elif 0 <= hyp_len[s, q] <= stride:
-                hyp[s, q, hyp_len[s, q]:] = 10 ** 6
-    return dict(case, hyp=hyp, hyp_len=hyp_len, count=count, logp=logp)
 
 
 def generated(seed, S, N, L=None, lens=None, stride=None, **kw):
@@ -123,13 +111,6 @@ def device(case, pivot="mbr", want_totals=True, stream=None):
     out = {n: getattr(r, n).cpu().numpy() for n in r._fields}
     out["totals"] = totals.cpu().numpy() if want_totals else None
     return out
-
-
-def ulps(a, b):
-    """the largest distance in float32 ulps (the values are >= 0, or exactly -1 on both sides)"""
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    assert np.array_equal(a < 0, b < 0)
-    return int(np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64)).max()) if a.size else 0
 
 
 def twin_of(case, pivot="mbr"):

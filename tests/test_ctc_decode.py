@@ -2,39 +2,23 @@
 klstm_ctc_decode computes (tests/ctc_decode_ref.py) is checked against independent statements, the host-side answers of the C-ABI, and
 the reordering of DecodeCtcWholeUtterances (include/klstm_nnet.hpp) into utterance order through tests/cpp/ctc_decode_test."""
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cpp_driver
 from tests import ctc_decode_ref as D
 from tests import ctc_ref as R
 from tests.test_ctc import plain_utts
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "ctc_decode_test")
-SRC = EXE + ".cpp"
-HDRS = [os.path.join(ROOT, "include", h) for h in ("klstm.h", "klstm_component.hpp", "klstm_kaldi_io.hpp", "klstm_trainer.hpp",
-                                                   "klstm_nnet.hpp", "klstm_blstm.hpp")]
 
 
 def build_ctc_decode_driver():
-    import kaldi_lstm_amd as k
-    lib = k.lib_path()
-    assert os.path.exists(lib), "libklstm.so missing: run __graft_entry__.build()"
-    stale = (not os.path.exists(EXE)) or any(os.path.getmtime(f) > os.path.getmtime(EXE) for f in [SRC] + HDRS)
-    if stale:
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-I" + os.path.join(ROOT, "include"), SRC,
-                               "-L" + os.path.dirname(lib), "-lklstm", "-Wl,-rpath,$ORIGIN/../../kaldi-lstm_amd", "-o", EXE])
-    return EXE
+    return cpp_driver.build("ctc_decode_test")
 
 
 def run_driver(*args, ok=True):
-    r = subprocess.run([build_ctc_decode_driver()] + [str(a) for a in args], capture_output=True, text=True, timeout=900)
-    if ok:
-        assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
-    return r
+    return cpp_driver.run("ctc_decode_test", *args, ok=ok)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

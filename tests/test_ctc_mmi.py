@@ -2,41 +2,25 @@
 by enumeration of every frame path and by central differences of the loss, the float32 twin is held against it, the status rules are
 spelled out, and the library carries the entries with their limits."""
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from tests import cpp_driver
 from tests import ctc_mmi_ref as M
 from tests import ctc_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "ctc_mmi_test")
-SRC = EXE + ".cpp"
-HDRS = [os.path.join(ROOT, "include", h) for h in ("klstm.h", "klstm_component.hpp", "klstm_kaldi_io.hpp", "klstm_trainer.hpp",
-                                                   "klstm_nnet.hpp", "klstm_blstm.hpp")]
 # (K, blank, kind) of the grid that can be enumerated: K <= 4
 SMALL_LMS = [(3, 0, "unigram"), (3, 1, "bigram"), (3, 2, "bigram"), (4, 0, "trigram"), (4, 0, "lexicon"), (4, 3, "bigram")]
 
 
 def build_ctc_mmi_driver():
-    import kaldi_lstm_amd as k
-    lib = k.lib_path()
-    assert os.path.exists(lib), "libklstm.so missing: run __graft_entry__.build()"
-    stale = (not os.path.exists(EXE)) or any(os.path.getmtime(f) > os.path.getmtime(EXE) for f in [SRC] + HDRS)
-    if stale:
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-I" + os.path.join(ROOT, "include"), SRC,
-                               "-L" + os.path.dirname(lib), "-lklstm", "-Wl,-rpath,$ORIGIN/../../kaldi-lstm_amd", "-o", EXE])
-    return EXE
+    return cpp_driver.build("ctc_mmi_test")
 
 
 def run_driver(*args, ok=True):
-    r = subprocess.run([build_ctc_mmi_driver()] + [str(a) for a in args], capture_output=True, text=True, timeout=900)
-    if ok:
-        assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
-    return r
+    return cpp_driver.run("ctc_mmi_test", *args, ok=ok)
 
 
 def _posteriors(kind, T, K, seed):

@@ -3,37 +3,23 @@ rescore) against an independent brute force (dense expansion of the model, math.
 host helpers of lm.py, the limits and argument errors of the library's entry, and the conditions of the GPU cases."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cpp_driver
 from tests import ctc_consensus_ref as C
 from tests import ctc_rescore_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "ctc_rescore_test")
-SRC = EXE + ".cpp"
-HDRS = [os.path.join(ROOT, "include", h) for h in ("klstm.h", "klstm_component.hpp", "klstm_kaldi_io.hpp", "klstm_trainer.hpp",
-                                                   "klstm_nnet.hpp", "klstm_blstm.hpp")]
 
 
 def build_ctc_rescore_driver():
-    import kaldi_lstm_amd as k
-    lib = k.lib_path()
-    assert os.path.exists(lib), "libklstm.so missing: run __graft_entry__.build()"
-    stale = (not os.path.exists(EXE)) or any(os.path.getmtime(f) > os.path.getmtime(EXE) for f in [SRC] + HDRS)
-    if stale:
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-I" + os.path.join(ROOT, "include"), SRC,
-                               "-L" + os.path.dirname(lib), "-lklstm", "-Wl,-rpath,$ORIGIN/../../kaldi-lstm_amd", "-o", EXE])
-    return EXE
+    return cpp_driver.build("ctc_rescore_test")
 
 
 def run_driver(*args, ok=True):
-    r = subprocess.run([build_ctc_rescore_driver()] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
-    if ok:
-        assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
-    return r
+    return cpp_driver.run("ctc_rescore_test", *args, ok=ok, timeout=300)
 
 
 @pytest.fixture(scope="module")
@@ -116,6 +102,20 @@ def test_word_table_and_sequences():
     t = R.Words(keys, ids, 9, 0)
     assert t.lookup(k.word_key([2]), 4, 3) == (1, False) and t.lookup(k.word_key([4]), 4, 3) == (9, True)
     assert t.lookup(k.word_key([5, 5, 5]), 4, 3) == (9, True) and t.lookup(k.word_key([5, 5, 5]), 3, 2) == (9, True)
+
+
+def test_hash_constants_of_python_and_twins_are_the_macros_of_klstm_h():
+    """lm.py and tests/nbest_ref.py cannot see include/klstm.h: their literals are held against its two macros, read as text"""
+    import re
+
+    import kaldi_lstm_amd.lm as LM
+    from tests import nbest_ref
+    text = open(os.path.join(ROOT, "include", "klstm.h")).read()
+    macro = {n: int(v, 16) for n, v in re.findall(r"^#define (KLSTM_CTC_HASH_\w+)\s+(0x[0-9A-Fa-f]+)ull\b", text, re.M)}
+    assert sorted(macro) == ["KLSTM_CTC_HASH_MUL", "KLSTM_CTC_HASH_START"]
+    assert (LM._WORD_H0, LM._WORD_HMUL) == (macro["KLSTM_CTC_HASH_START"], macro["KLSTM_CTC_HASH_MUL"]) == (nbest_ref.H0, nbest_ref.HMUL)
+    assert LM.split_words([0, 3, 1, 0, 0, 2, 0], 0) == nbest_ref.split_words([0, 3, 1, 0, 0, 2, 0], 0) == [[3, 1], [2]]
+    assert LM.split_words([0, 0], 0) == LM.split_words([], 0) == []
 
 
 def test_dense_lm_to_sparse():

@@ -19,6 +19,7 @@ import torch
 from tests import ctc_consensus_ref as C
 from tests import ctc_rescore_ref as R
 from tests.margins import bound
+from tests.nbest_ref import garbage, ulps
 
 pytestmark = pytest.mark.gpu
 GAP = 1e-9
@@ -32,19 +33,6 @@ def dev_model(model, blank):
     if key not in _DEV:
         _DEV[key] = (model, k.CtcSparseLabelLm(model, blank))
     return _DEV[key][1]
-
-
-def garbage(case):
-    """10^6 in every token that may not be read, -7 / NaN in every list slot beyond the count"""
-    hyp, hyp_len, count, logp = (np.array(case[k]) for k in ("hyp", "hyp_len", "count", "logp"))
-    S, N, stride = hyp.shape
-    for s in range(S):
-        for q in range(N):
-            if 0 <= count[s] <= N and q >= count[s]:
-                hyp[s, q], hyp_len[s, q], logp[s, q] = 10 ** 6, -7, np.nan
-            elif 0 <= hyp_len[s, q] <= stride:
-                hyp[s, q, hyp_len[s, q]:] = 10 ** 6
-    return dict(case, hyp=hyp, hyp_len=hyp_len, count=count, logp=logp)
 
 
 def twin_of(case):
@@ -77,18 +65,6 @@ def device(case, want_totals=True, stream=None):
     out["totals"] = totals.cpu().numpy() if want_totals else None
     out["result"] = r
     return out
-
-
-def ulps(a, b):
-    """the largest distance in float32 ulps; infinities sit in the same places on both sides"""
-    a, b = np.ascontiguousarray(a, np.float32).ravel(), np.ascontiguousarray(b, np.float32).ravel()
-    assert np.array_equal(np.isinf(a), np.isinf(b)) and not np.isnan(a).any() and not np.isnan(b).any(), (a, b)
-    fin = np.isfinite(a)
-
-    def ordered(v):
-        i = v[fin].view(np.int32).astype(np.int64)
-        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
-    return int(np.abs(ordered(a) - ordered(b)).max()) if fin.any() else 0
 
 
 def check(case):
