@@ -6,10 +6,11 @@
 //
 // There is deliberately NO CPU fallback: without a usable gfx950 device klstm_create fails with
 // KLSTM_ERR_NOGPU.
-#include <hip/hip_runtime.h>
-
+//
+// This file holds the engine only: struct klstm_engine, the entries that take one, klstm_gran_plan, and the one definition of the error
+// string behind klstm_last_error() (klstm_host.h).  The entries without an engine are in klstm_api_ops.hip (stateless operations,
+// klstm_debug_*), klstm_api_ctc.hip (klstm_ctc_*) and klstm_comm.hip (RCCL).
 #include <cstdarg>
-#include <climits>
 #include <cstddef>
 #include <cstdio>
 #include <atomic>
@@ -24,18 +25,15 @@
 #include <tuple>
 #include <vector>
 
-#include <dlfcn.h>
-#include <rccl/rccl.h>          // types only: the library is resolved at run time (see the RCCL section below)
-
-#include "../../include/klstm.h"
+#include "klstm_host.h"
 #include "klstm_kernels.h"
 
 using namespace klstm;
 void klstm_oneshot_set_abort_words(klstm_oneshot *h, unsigned *guard_word_dev, unsigned *host_mapped_word);   // klstm_oneshot.hip
 long klstm_oneshot_floats(klstm_oneshot *h);                                                                   // klstm_oneshot.hip
 
-static thread_local std::string g_err;
-static klstm_status fail(klstm_status st, const char *fmt, ...) {
+static thread_local std::string g_err;      // what klstm_last_error() reads: the one copy, written through klstm::fail / klstm::note
+klstm_status klstm::fail(klstm_status st, const char *fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -44,8 +42,7 @@ static klstm_status fail(klstm_status st, const char *fmt, ...) {
   g_err = buf;
   return st;
 }
-// a remark for klstm_last_error() that is not a failure (why a faster path was not taken)
-static void note(const char *fmt, ...) {
+void klstm::note(const char *fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -53,12 +50,6 @@ static void note(const char *fmt, ...) {
   va_end(ap);
   g_err = buf;
 }
-#define HIPCHK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess)                                                                     \
-      return fail(KLSTM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
 
 struct ProbeRec { std::string name; hipEvent_t start, stop; };
 
@@ -336,7 +327,6 @@ static size_t ws_need(const klstm_engine *e, int T) {
   }
   return need;
 }
-constexpr int NT2_TICKETS = 8192;
 static klstm_status ensure_tickets(klstm_engine *e) {
   if (e->tickets) return KLSTM_OK;
   HIPCHK(hipMalloc(&e->tickets, NT2_TICKETS * sizeof(unsigned)));
@@ -456,8 +446,6 @@ static klstm_status repack(klstm_engine *e) {
   e->pk_stale = 0;
   return KLSTM_OK;
 }
-
-static int g_d2h_small = 1;           // process-wide A-B knob ("d2h_small"): klstm_memcpy_d2h's small-copy kernel (below)
 
 // ---- folded recurrence: policy, buffers, refresh of W_rm and its packed copies ----
 static bool fold_wanted(const klstm_engine *e, int T) {
@@ -1652,203 +1640,124 @@ klstm_status klstm_get_activations_host(klstm_engine *e, int which, float *dst) 
   return KLSTM_OK;
 }
 
+}  // extern "C"
+
+// ---- klstm_set_option: one row per key (what the keys mean: the comment above the declaration in include/klstm.h).  What must happen
+// before a key's field may change is a mask of steps, run in the order of the enum whatever the key; then the row's setter, which also
+// holds what a key validates or does beyond an assignment.  O_ALL is the one step BEHIND the setter: the process-wide kernel-selection
+// knobs tell every live engine once the knob has its value, so that a graph another thread captures after it has seen the new generation
+// holds the new kernels.
+enum : unsigned {
+  O_DEV = 1,        // hipSetDevice(e->device)
+  O_GRADS = 2,      // flush_grads(e): gradient products that wait for klstm_update run under the old setting
+  O_TAIL = 4,       // flush_tail(e): so does a tail reduction that waits for its gradient launch
+  O_STREAM = 8,     // hipStreamSynchronize(e->stream)
+  O_SYNC = 16,      // klstm_synchronize(e): the stream idle and a give-up of the persistent chain answered
+  O_GRAPHS = 32,    // drop_graphs(e): captured launches bake kernels, geometry and kernel arguments
+  O_ALL = 64,       // behind the setter: knob_changed_everywhere(), hipSetDevice(e->device)
+  O_KERNELS = O_STREAM | O_GRAPHS, O_PERSIST = O_DEV | O_SYNC | O_GRAPHS
+};
+struct OptRow { const char *key; unsigned steps; klstm_status (*set)(klstm_engine *e, int v); };
+#define OPT(...) [](klstm_engine *e, int v) -> klstm_status { __VA_ARGS__; return KLSTM_OK; }
+
+static klstm_status opt_bf16(klstm_engine *e, int value) {
+  if (value != 0 && !e->pk[0]) return fail(KLSTM_ERR_SHAPE, "bf16 mode needs I, C, R multiples of 8");
+  // 1 = where it pays: from 9 streams on.  Up to 8 streams the fp32 engine runs the weights-resident chain (one launch per direction);
+  // bf16 operand mode has no such chain below 9 streams and would step one launch per frame (measured at 40/800/512, T = 20: 4 streams
+  // 291 us per minibatch against 147 in fp32, 8 streams 313 against 191; profiles/r06_scale_probe.txt) -- so a request for bf16 at
+  // <= 8 streams is served by the fp32 chain: faster AND at fp32 accuracy (the option allows bf16 rounding, it does not demand it).
+  // 2 = bf16 operands at any stream count (tests of the launch-per-step bf16 kernels, A-B runs).
+  e->use_bf16 = value == 2 || (value != 0 && e->S > 8);
+  { klstm_status ws = ensure_wT32(e); if (ws != KLSTM_OK) return ws; }
+  if (e->pk[0])       // ("bf16" = 0 on a shape that has no packed operands: nothing to write, and no buffers to write it to)
+    HIPCHK(launch_pack(Dims{e->I, e->C, e->R, e->S, 0}, e->params, e->wrT, e->wmT, e->wxT, e->pk, 15, e->use_bf16, e->stream));
+  if (value == 1 && !e->use_bf16)
+    note("bf16 operand mode at %d streams: served by the fp32 weights-resident chain (one launch per direction up to 8 streams; the bf16 "
+         "step kernels take about 1.9x the time per minibatch at 4 streams, 1.6x at 8); \"bf16\" = 2 forces bf16 operands", e->S);
+  return KLSTM_OK;
+}
+
+static const OptRow g_options[] = {
+    {"graph", 0, OPT(e->use_graph = v < 0 ? 0 : v > 2 ? 2 : v)},
+    {"vector", O_KERNELS, OPT(e->use_vector = v != 0)},
+    {"small_max", O_KERNELS, OPT(set_small_max(v))},
+    {"fat", O_KERNELS, OPT(e->use_fat = v != 0)},
+    {"bf16", O_DEV | O_KERNELS, opt_bf16},
+    {"d2h_small", 0, OPT(set_d2h_small(v))},
+    {"fat_fine", O_KERNELS, OPT(set_fat_fine(v))},
+    {"small_nt2", O_KERNELS, OPT(set_small_nt2(v))},
+    {"fuse_update", O_GRADS, OPT(e->fuse_update_ok = v != 0)},
+    {"gemm_copies_plan", 0, OPT(
+         const int nj = v >> 4, ks = v & 15;               // 16 nj + ks; 0 = the planner
+         if (v != 0 && (v < 0 || (nj != 1 && nj != 2 && nj != 4) || (ks != 1 && ks != 2 && ks != 4 && ks != 8)))
+           return fail(KLSTM_ERR_ARG, "gemm_copies_plan: 16 nj + ks with nj in {1, 2, 4} and ks in {1, 2, 4, 8} (or 0)");
+         e->copies_plan = v)},
+    {"gemm_copies", O_KERNELS, OPT(e->use_copies = v != 0; e->skip_wT32 = v == 1; if (!e->use_copies) e->wth_fresh = false; return ensure_wT32(e))},
+    {"gemm_nt2", O_KERNELS, OPT(e->use_nt2 = v != 0)},
+    {"fold", O_KERNELS, OPT(e->use_fold = v)},
+    // "persist" and the knobs of THIS engine's persistent launches (kernel arguments and geometry)
+    {"persist", O_PERSIST, OPT(e->use_persist = v)},
+    {"persist_tpw", O_PERSIST, OPT(e->popt.tpw = v)},
+    {"persist_waves", O_PERSIST, OPT(e->popt.waves = v; e->popt.bwd_waves = v)},
+    {"persist_bwd_waves", O_PERSIST, OPT(e->popt.bwd_waves = v)},
+    {"persist_bwd_interleave", O_PERSIST, OPT(e->popt.bwd_interleave = v)},
+    {"persist_fwd_interleave", O_PERSIST, OPT(e->popt.fwd_interleave = v)},
+    {"persist_xl", O_PERSIST, OPT(e->popt.xl = v)},
+    {"persist_xl_bwd", O_PERSIST, OPT(e->popt.xl_bwd = v)},
+    {"persist_nap0", O_PERSIST, OPT(e->popt.nap0 = v)},
+    {"persist_nap", O_PERSIST, OPT(e->popt.nap = v)},
+    {"persist_nap0_bwd", O_PERSIST, OPT(e->popt.nap0_bwd = v)},
+    {"persist_spin_us", O_PERSIST, OPT(e->popt.spin_limit = (long long)v * 100)},      // wall clock: 100 MHz
+    {"persist_test_stall_fwd", O_PERSIST, OPT(e->popt.test_stall_fwd = v)},
+    {"persist_test_stall_bwd", O_PERSIST, OPT(e->popt.test_stall_bwd = v)},
+    {"persist_ncu", O_PERSIST, OPT(e->ncu = v; e->popt.ncu = v)},
+    {"persist_verify", O_PERSIST, OPT(e->persist_verify = v != 0)},
+    {"persist_verify_spin", O_PERSIST, OPT(e->verify_spin = v != 0)},
+    {"persist_epoch", O_PERSIST, OPT(e->persist_epoch = v != 0)},
+    {"persist_gran", O_PERSIST, OPT(e->persist_gran = v != 0)},
+    {"persist_cooldown", O_PERSIST, OPT(e->cooldown_len = v < 0 ? 0 : v; e->cooldown_cur = 0; if (e->cooldown > e->cooldown_len) e->cooldown = e->cooldown_len)},
+    {"tail_merge", O_TAIL, OPT(e->tail_merge = v != 0)},
+    {"persist_tail", O_KERNELS, OPT(e->persist_tail = v; e->popt.tail_mode = v)},
+    // process-wide: which kernel a product runs on.  The cached graphs of EVERY live engine hold the old kernels (O_ALL)
+    {"direct_nt_shape", O_ALL, OPT(set_direct_nt_shape(v / 10, v % 10))},               // 10*NI + waves
+    {"skinny_f16_pair", O_ALL, OPT(set_skinny_f16_pair(v))},
+    {"skinny_f16", O_ALL, OPT(set_skinny_f16(v))},
+    {"outer_f16", O_ALL, OPT(set_outer_f16(v))},
+    {"fold_direct", O_ALL, OPT(set_fold_direct(v))},
+    // the fold product of THIS engine (the planes at hand are in another format)
+    {"fold_bf16x3", O_DEV | O_KERNELS, OPT(e->fold_mode = e->fold_eff = v < 0 ? 0 : v > 2 ? 2 : v; e->planes_fresh = false; e->fold_dirty = true)},
+    {"fp16_products", O_DEV | O_KERNELS, OPT(
+         range_guard_reset(e->rg, v != 0);
+         range_guard_reset(nullptr, v != 0);
+         e->fold_mode = e->fold_eff = v ? 2 : 1;           // (the fold product keeps the matrix cores: three bf16 planes have the fp32 range)
+         e->planes_fresh = false; e->fold_dirty = true)},
+    {"fuse_x", O_KERNELS, OPT(e->fuse_x = v)},
+    {"profile", O_DEV | O_STREAM, OPT(
+         for (auto &r : e->probes) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
+         e->probes.clear(); e->prof.clear();
+         e->profile = v != 0)},
+};
+#undef OPT
+
+extern "C" {
+
 klstm_status klstm_set_option(klstm_engine *e, const char *key, int value) {
   if (!e || !key) return fail(KLSTM_ERR_ARG, "null argument");
-  if (!strcmp(key, "graph")) { e->use_graph = value < 0 ? 0 : value > 2 ? 2 : value; return KLSTM_OK; }
-  if (!strcmp(key, "vector")) {          // 0: force the generic kernels (testing)
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    e->use_vector = value != 0;
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "small_max")) {       // process-wide tuning knob (A-B experiments)
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    set_small_max(value);
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "fat")) {             // 0: keep the 16-row tile kernels also for NumStream > 16 (testing / A-B)
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    e->use_fat = value != 0;
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "bf16")) {            // 1: bf16 weight/activation operands with fp32 accumulate in the step kernels
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    if (value != 0 && !e->pk[0]) return fail(KLSTM_ERR_SHAPE, "bf16 mode needs I, C, R multiples of 8");
-    // 1 = where it pays: from 9 streams on.  Up to 8 streams the fp32 engine runs the weights-resident chain (one launch per direction);
-    // bf16 operand mode has no such chain below 9 streams and would step one launch per frame (measured at 40/800/512, T = 20: 4 streams
-    // 291 us per minibatch against 147 in fp32, 8 streams 313 against 191; profiles/r06_scale_probe.txt) -- so a request for bf16 at
-    // <= 8 streams is served by the fp32 chain: faster AND at fp32 accuracy (the option allows bf16 rounding, it does not demand it).
-    // 2 = bf16 operands at any stream count (tests of the launch-per-step bf16 kernels, A-B runs).
-    e->use_bf16 = value == 2 || (value != 0 && e->S > 8);
-    { klstm_status ws = ensure_wT32(e); if (ws != KLSTM_OK) return ws; }
-    HIPCHK(launch_pack(Dims{e->I, e->C, e->R, e->S, 0}, e->params, e->wrT, e->wmT, e->wxT, e->pk, 15, e->use_bf16, e->stream));
-    if (value == 1 && !e->use_bf16)
-      note("bf16 operand mode at %d streams: served by the fp32 weights-resident chain (one launch per direction up to 8 streams; the bf16 "
-           "step kernels take about 1.9x the time per minibatch at 4 streams, 1.6x at 8); \"bf16\" = 2 forces bf16 operands", e->S);
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "d2h_small")) {       // process-wide: 0 = klstm_memcpy_d2h always through hipMemcpyAsync (A-B runs)
-    g_d2h_small = value != 0;
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "fat_fine")) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    set_fat_fine(value);
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "small_nt2")) {       // process-wide tuning knob (A-B experiments)
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    set_small_nt2(value);
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "fuse_update")) {     // 0: KLSTM_BPTT_FUSE_UPDATE is ignored (A-B runs)
-    { klstm_status gs = flush_grads(e); if (gs != KLSTM_OK) return gs; }
-    e->fuse_update_ok = value != 0;
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "gemm_copies_plan")) {
-    const int nj = value >> 4, ks = value & 15;       // 16 nj + ks; 0 = the planner
-    if (value != 0 && (value < 0 || (nj != 1 && nj != 2 && nj != 4) || (ks != 1 && ks != 2 && ks != 4 && ks != 8)))
-      return fail(KLSTM_ERR_ARG, "gemm_copies_plan: 16 nj + ks with nj in {1, 2, 4} and ks in {1, 2, 4, 8} (or 0)");
-    e->copies_plan = value;
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "gemm_copies")) {     // 0: d_r + in_diff of the many-stream bf16 mode round their fp32 operands while staging them (no bf16 copies are written or read)
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    e->use_copies = value != 0;
-    e->skip_wT32 = value == 1;
-    if (!e->use_copies) e->wth_fresh = false;
-    { klstm_status ws = ensure_wT32(e); if (ws != KLSTM_OK) return ws; }
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "gemm_nt2")) {        // 0: the batched bf16 products around the many-stream chains on round 4's kernel + reduction launches
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    e->use_nt2 = value != 0;
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "fold")) {            // -1 auto, 0 never, 1 whenever NumStream <= small_max
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    e->use_fold = value;
-    return KLSTM_OK;
-  }
-  if (!strncmp(key, "persist", 7) && strcmp(key, "persist_tail")) {
-    // "persist": -1 auto, 0 off, 1 forward launch only, 2 both directions whenever the shape allows.  The rest are knobs of
-    // THIS engine's persistent launches (kernel arguments and geometry): A-B experiments and tests.
-    HIPCHK(hipSetDevice(e->device));
-    { klstm_status ss = klstm_synchronize(e); if (ss != KLSTM_OK) return ss; }
-    drop_graphs(e);                                 // captured launches bake geometry and kernel arguments
-    if (!strcmp(key, "persist")) e->use_persist = value;
-    else if (!strcmp(key, "persist_tpw")) e->popt.tpw = value;
-    else if (!strcmp(key, "persist_waves")) { e->popt.waves = value; e->popt.bwd_waves = value; }
-    else if (!strcmp(key, "persist_bwd_waves")) e->popt.bwd_waves = value;
-    else if (!strcmp(key, "persist_bwd_interleave")) e->popt.bwd_interleave = value;
-    else if (!strcmp(key, "persist_fwd_interleave")) e->popt.fwd_interleave = value;
-    else if (!strcmp(key, "persist_xl")) e->popt.xl = value;
-    else if (!strcmp(key, "persist_xl_bwd")) e->popt.xl_bwd = value;
-    else if (!strcmp(key, "persist_nap0")) e->popt.nap0 = value;
-    else if (!strcmp(key, "persist_nap")) e->popt.nap = value;
-    else if (!strcmp(key, "persist_nap0_bwd")) e->popt.nap0_bwd = value;
-    else if (!strcmp(key, "persist_spin_us")) e->popt.spin_limit = (long long)value * 100;      // wall clock: 100 MHz
-    else if (!strcmp(key, "persist_test_stall_fwd")) e->popt.test_stall_fwd = value;            // test hooks: force the timeout path
-    else if (!strcmp(key, "persist_test_stall_bwd")) e->popt.test_stall_bwd = value;
-    else if (!strcmp(key, "persist_ncu")) { e->ncu = value; e->popt.ncu = value; }                                      // test hook: pretend the device has this many CUs
-    else if (!strcmp(key, "persist_verify")) e->persist_verify = value != 0;
-    else if (!strcmp(key, "persist_verify_spin")) e->verify_spin = value != 0;
-    else if (!strcmp(key, "persist_epoch")) e->persist_epoch = value != 0;
-    else if (!strcmp(key, "persist_gran")) e->persist_gran = value != 0;
-    else if (!strcmp(key, "persist_cooldown")) { e->cooldown_len = value < 0 ? 0 : value; e->cooldown_cur = 0; if (e->cooldown > e->cooldown_len) e->cooldown = e->cooldown_len; }
-    else return fail(KLSTM_ERR_ARG, "klstm_set_option: unknown key '%s'", key);
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "tail_merge")) {
-    { klstm_status ts = flush_tail(e); if (ts != KLSTM_OK) return ts; }
-    e->tail_merge = value != 0;
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "persist_tail")) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    e->persist_tail = value;
-    e->popt.tail_mode = value;                       // (1: inside, on tail workgroups where they fit; 2: inside, on the chain's workgroups; 0: after the launch)
-    return KLSTM_OK;
-  }
-  // Process-wide knobs (which kernel a product runs on; A-B experiments and tests): the cached graphs of EVERY live engine hold
-  // the old kernels, so all of them are dropped (knob_changed_everywhere), not only this engine's.
-  if (!strcmp(key, "direct_nt_shape")) {         // value = 10*NI + waves
-    set_direct_nt_shape(value / 10, value % 10);
-    knob_changed_everywhere();
-    HIPCHK(hipSetDevice(e->device));
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "skinny_f16_pair")) {         // 0: d_r / in_diff of the folded BPTT tail on the tiled split-K kernel
-    set_skinny_f16_pair(value);
-    knob_changed_everywhere();
-    HIPCHK(hipSetDevice(e->device));
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "skinny_f16")) {              // 0: in_diff of a wide layer on the fp32 MFMA kernel (the two-job launch of the BPTT tail looks at it too)
-    set_skinny_f16(value);
-    knob_changed_everywhere();
-    HIPCHK(hipSetDevice(e->device));
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "outer_f16")) {               // 0: the wide gradient product on the fp32 tile kernel
-    set_outer_f16(value);
-    knob_changed_everywhere();
-    HIPCHK(hipSetDevice(e->device));
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "fold_direct")) {             // 0: the fold product on the generic 64x64-tile kernel
-    set_fold_direct(value);
-    knob_changed_everywhere();
-    HIPCHK(hipSetDevice(e->device));
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "fold_bf16x3")) {             // the fold product of THIS engine: 0 fp32 MFMA (klstm_fold.hip), 1 three bf16 planes, 2 two fp16 planes
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    e->fold_mode = e->fold_eff = value < 0 ? 0 : value > 2 ? 2 : value;   // (the planes at hand are in another format)
-    e->planes_fresh = false;
-    e->fold_dirty = true;
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "fp16_products")) {           // 0: nothing of THIS engine -- and no stateless klstm_affine_* call on this device -- runs on fp16 planes;
-    HIPCHK(hipSetDevice(e->device));             // 1: the defaults again, the guards' counters and cool-downs cleared.  Other engines keep their own state.
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    range_guard_reset(e->rg, value != 0);
-    range_guard_reset(nullptr, value != 0);
-    e->fold_mode = e->fold_eff = value ? 2 : 1;  // (the fold product keeps the matrix cores: three bf16 planes have the fp32 range)
-    e->planes_fresh = false;
-    e->fold_dirty = true;
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "fuse_x")) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    drop_graphs(e);
-    e->fuse_x = value;
-    return KLSTM_OK;
-  }
-  if (!strcmp(key, "profile")) {
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (auto &r : e->probes) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
-    e->probes.clear();
-    e->prof.clear();
-    e->profile = value != 0;
-    return KLSTM_OK;
-  }
-  return fail(KLSTM_ERR_ARG, "klstm_set_option: unknown key '%s'", key);
+  const OptRow *row = nullptr;
+  for (const OptRow &r : g_options)
+    if (!strcmp(key, r.key)) { row = &r; break; }
+  if (!row) return fail(KLSTM_ERR_ARG, "klstm_set_option: unknown key '%s'", key);
+  if (row->steps & O_DEV) HIPCHK(hipSetDevice(e->device));
+  if (row->steps & O_GRADS) { klstm_status gs = flush_grads(e); if (gs != KLSTM_OK) return gs; }
+  if (row->steps & O_TAIL) { klstm_status ts = flush_tail(e); if (ts != KLSTM_OK) return ts; }
+  if (row->steps & O_STREAM) HIPCHK(hipStreamSynchronize(e->stream));
+  if (row->steps & O_SYNC) { klstm_status ss = klstm_synchronize(e); if (ss != KLSTM_OK) return ss; }
+  if (row->steps & O_GRAPHS) drop_graphs(e);
+  const klstm_status st = row->set(e, value);
+  if (st != KLSTM_OK || !(row->steps & O_ALL)) return st;
+  knob_changed_everywhere();
+  HIPCHK(hipSetDevice(e->device));
+  return KLSTM_OK;
 }
 
 klstm_status klstm_profile_query(klstm_engine *e, const char *kernel, double *total_us, long *launches) {
@@ -1909,952 +1818,6 @@ klstm_status klstm_profile_query(klstm_engine *e, const char *kernel, double *to
   return KLSTM_OK;
 }
 
-klstm_status klstm_time_shift(const float *in, int rows, int cols, int in_stride, float *out, int out_stride, int shift,
-                              void *hip_stream) {
-  if (!in || !out) return fail(KLSTM_ERR_ARG, "klstm_time_shift: null argument");
-  if (rows < 0 || cols < 0 || in_stride < cols || out_stride < cols) return fail(KLSTM_ERR_ARG, "klstm_time_shift: bad shape");
-  if (rows == 0 || cols == 0) return KLSTM_OK;
-  HIPCHK(launch_time_shift(in, rows, cols, in_stride, out, out_stride, shift, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-
-// ---- device memory helpers (keep the C++ mirror and other FFI users free of HIP headers) ----
-klstm_status klstm_malloc(void **p, size_t bytes) {
-  if (!p) return fail(KLSTM_ERR_ARG, "klstm_malloc: null argument");
-  HIPCHK(hipMalloc(p, bytes ? bytes : 4));
-  return KLSTM_OK;
-}
-klstm_status klstm_free(void *p) { if (p) HIPCHK(hipFree(p)); return KLSTM_OK; }
-klstm_status klstm_memcpy_h2d(void *dst, const void *src, size_t bytes, void *hip_stream) {
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
-  HIPCHK(hipStreamSynchronize((hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-// Small device-to-host copies -- the three scalars Xent::EvalMasked reads back EVERY minibatch (google/nnet/nnet-loss.cc:110-141: what an
-// unmodified bd-nnet-train-lstm-streams does), a CuVector::CopyToVec of a few numbers.  hipMemcpy of pageable memory costs ~45 us of idle
-// GPU per call on this stack (staging + completion signal + wake-up: profiles/r05 kaldi_adapter with_d2h_per_minibatch), a third of a
-// 150 us minibatch.  Up to D2H_SMALL_BYTES the copy is a ONE-WAVE KERNEL on the caller's stream that writes {sequence tag, word} granules
-// into a host-mapped staging buffer (8-byte system-scope stores: tag and word cannot tear, the data is the flag -- no fence, no completion
-// signal; the idiom of the persistent chains' granules and of "persist_verify"'s done word), and the host spins on the tags: it has the
-// numbers one PCIe write after the kernel ran.  Same semantics as before: stream-ordered behind everything queued on hip_stream, returns
-// when dst is filled.  Anything else (larger, unaligned, no mapped memory) takes hipMemcpyAsync + hipStreamSynchronize.
-constexpr size_t D2H_SMALL_BYTES = 256;
-__global__ __launch_bounds__(64) void k_d2h_small(const unsigned *__restrict__ src, unsigned long long *dst, int nwords, unsigned seq) {
-  const int i = threadIdx.x;
-  if (i < nwords)
-    __hip_atomic_store(dst + i, ((unsigned long long)seq << 32) | src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-struct D2hStage {
-  unsigned long long *host = nullptr, *dev = nullptr;
-  int device = -1;
-  unsigned seq = 0;
-  bool broken = false;
-  ~D2hStage() { if (host) (void)hipHostFree(host); }
-};
-static bool d2h_small(void *dst, const void *src, size_t bytes, hipStream_t st) {
-  static thread_local D2hStage sg;    // (the call is synchronous: one staging buffer per calling thread)
-  if (!g_d2h_small || sg.broken || bytes == 0 || bytes > D2H_SMALL_BYTES || (bytes & 3) || (reinterpret_cast<uintptr_t>(src) & 3)) return false;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
-  if (!sg.host) {
-    void *hp = nullptr;
-    if (hipHostMalloc(&hp, (D2H_SMALL_BYTES / 4) * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) {
-      (void)hipGetLastError(); sg.broken = true; return false;
-    }
-    memset(hp, 0, (D2H_SMALL_BYTES / 4) * sizeof(unsigned long long));
-    sg.host = static_cast<unsigned long long *>(hp);
-  }
-  if (sg.device != dev) {
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, sg.host, 0) != hipSuccess) { (void)hipGetLastError(); sg.broken = true; return false; }
-    sg.dev = static_cast<unsigned long long *>(dp); sg.device = dev;
-  }
-  if (++sg.seq == 0) sg.seq = 1;      // (0 = what the buffer holds before its first use)
-  const int nw = (int)(bytes / 4);
-  if (launch(k_d2h_small, dim3(1), dim3(64), 0, st, LaunchProbe{}, static_cast<const unsigned *>(src), sg.dev, nw, sg.seq) != hipSuccess)
-    return false;
-  const volatile unsigned long long *q = sg.host;
-  const auto t0 = std::chrono::steady_clock::now();
-  int have = 0;
-  bool synced = false;
-  for (unsigned spins = 1; have < nw; spins++) {
-    while (have < nw && (unsigned)(q[have] >> 32) == sg.seq) have++;
-    if (have == nw) break;
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#else
-    std::this_thread::yield();
-#endif
-    if ((spins & 1023) == 0 && !synced && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-      // a long queue in front of the copy: sleep in the runtime instead of burning a core; the granules are there when it returns
-      if (hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); return false; }
-      synced = true;
-    } else if (synced && (spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-      return false;                   // (never seen: the ordinary copy answers)
-    }
-  }
-  unsigned *out = static_cast<unsigned *>(dst);
-  if ((reinterpret_cast<uintptr_t>(dst) & 3) == 0) for (int i = 0; i < nw; i++) out[i] = (unsigned)q[i];
-  else for (int i = 0; i < nw; i++) { const unsigned w = (unsigned)q[i]; memcpy(static_cast<char *>(dst) + 4 * i, &w, 4); }
-  return true;
-}
-klstm_status klstm_memcpy_d2h(void *dst, const void *src, size_t bytes, void *hip_stream) {
-  if (d2h_small(dst, src, bytes, (hipStream_t)hip_stream)) return KLSTM_OK;
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-  HIPCHK(hipStreamSynchronize((hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-klstm_status klstm_memset_zero(void *dst, size_t bytes, void *hip_stream) {
-  HIPCHK(hipMemsetAsync(dst, 0, bytes, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-klstm_status klstm_stream_synchronize(void *hip_stream) {
-  HIPCHK(hipStreamSynchronize((hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-
-// ---- AffineTransform / Softmax / Xent::EvalMasked (stateless) ----
-klstm_status klstm_affine_propagate(const float *in, int rows, int in_dim, int in_stride, const float *W,
-                                    const float *bias, float *out, int out_dim, int out_stride, void *hip_stream) {
-  if (!in || !W || !out) return fail(KLSTM_ERR_ARG, "klstm_affine_propagate: null argument");
-  if (direct_nt_supported(rows, out_dim, in_dim, in, in_stride, W, in_dim)) {     // few frames, wide layer: the output tail
-    HIPCHK(launch_direct_nt(rows, out_dim, in_dim, in, in_stride, W, in_dim, out, out_stride, bias, (hipStream_t)hip_stream));
-    return KLSTM_OK;
-  }
-  HIPCHK(launch_gemm(false, true, rows, out_dim, in_dim, in, in_stride, W, in_dim, 0.f, out, out_stride, bias,
-                     (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-// split-K workspace of the stateless ops: one growing buffer per (device, stream), owned by the library
-static klstm_status splitk_workspace(hipStream_t st, size_t floats, float **ws) {
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, std::pair<float *, size_t>> pool;
-  int devid = 0;
-  HIPCHK(hipGetDevice(&devid));
-  std::lock_guard<std::mutex> lk(mu);
-  auto &slot = pool[std::make_pair(devid, st)];
-  if (slot.second < floats) {
-    HIPCHK(hipStreamSynchronize(st));                // earlier launches may still read the old buffer
-    if (slot.first) (void)hipFree(slot.first);
-    slot.first = nullptr; slot.second = 0;
-    HIPCHK(hipMalloc(&slot.first, floats * sizeof(float)));
-    slot.second = floats;
-  }
-  *ws = slot.first;
-  return KLSTM_OK;
-}
-klstm_status klstm_affine_backpropagate(const float *out_diff, int rows, int out_dim, int od_stride, const float *W,
-                                        int in_dim, float *in_diff, int id_stride, void *hip_stream) {
-  if (!out_diff || !W || !in_diff) return fail(KLSTM_ERR_ARG, "klstm_affine_backpropagate: null argument");
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (skinny_nn_supported(rows, in_dim, out_dim, out_diff, od_stride, W, in_dim, in_diff, id_stride)) {   // few frames, wide layer (klstm_fold.hip)
-    float *ws = nullptr;
-    klstm_status s = splitk_workspace(st, skinny_nn_workspace_floats(rows, in_dim, out_dim), &ws);
-    if (s != KLSTM_OK) return s;
-    HIPCHK(launch_skinny_nn(rows, in_dim, out_dim, out_diff, od_stride, W, in_dim, in_diff, id_stride, ws, st));
-    return KLSTM_OK;
-  }
-  int klen = 0;
-  const int ks = gemm_splitk_plan(rows, in_dim, out_dim, &klen);       // contraction over the (long) output axis
-  if (ks > 1) {
-    float *ws = nullptr;
-    klstm_status s = splitk_workspace(st, (size_t)ks * rows * in_dim, &ws);
-    if (s != KLSTM_OK) return s;
-    HIPCHK(launch_gemm_splitk(false, false, rows, in_dim, out_dim, out_diff, od_stride, W, in_dim, 0.f, in_diff, id_stride,
-                              nullptr, ws, ks, klen, st));
-    return KLSTM_OK;
-  }
-  HIPCHK(launch_gemm(false, false, rows, in_dim, out_dim, out_diff, od_stride, W, in_dim, 0.f, in_diff, id_stride, nullptr, st));
-  return KLSTM_OK;
-}
-klstm_status klstm_affine_update(const float *in, int in_stride, const float *out_diff, int od_stride, int rows, int in_dim,
-                                 int out_dim, float *W, float *bias, float *W_corr, float *bias_corr, float lr,
-                                 float lr_bias, float momentum, void *hip_stream) {
-  if (!in || !out_diff || !W || !bias || !W_corr || !bias_corr) return fail(KLSTM_ERR_ARG, "klstm_affine_update: null argument");
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (outer_f16_supported(out_dim, in_dim, rows, out_diff, od_stride, in, in_stride, W_corr, in_dim, W, bias_corr)) {   // few frames, wide layer (klstm_outer.hip)
-    if (reinterpret_cast<uintptr_t>(bias) & 15) {        // (the bias step rides along in 16-byte pieces)
-      HIPCHK(launch_outer_f16(out_dim, in_dim, rows, out_diff, od_stride, in, in_stride, momentum, W_corr, in_dim, W, lr, momentum,
-                              bias_corr, nullptr, 0.f, st));
-      HIPCHK(launch_axpy(bias, bias_corr, -lr_bias, out_dim, st));
-    } else {
-      HIPCHK(launch_outer_f16(out_dim, in_dim, rows, out_diff, od_stride, in, in_stride, momentum, W_corr, in_dim, W, lr, momentum,
-                              bias_corr, bias, lr_bias, st));
-    }
-    return KLSTM_OK;
-  }
-  if (in_dim % 4 == 0 && ((reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(W_corr)) & 15) == 0) {
-    // gradient product, momentum and Update of the weight matrix in one pass (no second trip over the 3 x 34 MB)
-    HIPCHK(launch_gemm_tn_update(out_dim, in_dim, rows, out_diff, od_stride, in, in_stride, momentum, W_corr, W, in_dim, lr, st));
-  } else {
-    HIPCHK(launch_gemm(true, false, out_dim, in_dim, rows, out_diff, od_stride, in, in_stride, momentum, W_corr, in_dim, nullptr, st));
-    HIPCHK(launch_axpy(W, W_corr, -lr, (long)out_dim * in_dim, st));
-  }
-  HIPCHK(launch_col_sum(out_diff, rows, out_dim, od_stride, momentum, bias_corr, st));
-  HIPCHK(launch_axpy(bias, bias_corr, -lr_bias, out_dim, st));
-  return KLSTM_OK;
-}
-klstm_status klstm_affine_gradient(const float *in, int in_stride, const float *out_diff, int od_stride, int rows, int in_dim,
-                                   int out_dim, float *W_grad, float *bias_grad, void *hip_stream) {
-  if (!in || !out_diff || !W_grad || !bias_grad) return fail(KLSTM_ERR_ARG, "klstm_affine_gradient: null argument");
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (outer_f16_supported(out_dim, in_dim, rows, out_diff, od_stride, in, in_stride, W_grad, in_dim, nullptr, bias_grad)) {
-    HIPCHK(launch_outer_f16(out_dim, in_dim, rows, out_diff, od_stride, in, in_stride, 0.f, W_grad, in_dim, nullptr, 0.f, 0.f,
-                            bias_grad, nullptr, 0.f, st));
-    return KLSTM_OK;
-  }
-  if (in_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(W_grad) & 15) == 0)
-    HIPCHK(launch_gemm_tn_coal(out_dim, in_dim, rows, out_diff, od_stride, in, in_stride, 0.f, W_grad, in_dim, st));
-  else
-    HIPCHK(launch_gemm(true, false, out_dim, in_dim, rows, out_diff, od_stride, in, in_stride, 0.f, W_grad, in_dim, nullptr, st));
-  HIPCHK(launch_col_sum(out_diff, rows, out_dim, od_stride, 0.f, bias_grad, st));
-  return KLSTM_OK;
-}
-klstm_status klstm_pack_streams(const float *feats, int dim, int feat_stride, const int *stream_desc_dev, int num_stream, int T,
-                                int shift, float *out, int out_stride, int *reset_dev, void *hip_stream) {
-  if ((!feats || !stream_desc_dev || !out) && T > 0) return fail(KLSTM_ERR_ARG, "klstm_pack_streams: null argument");
-  if (dim < 0 || num_stream <= 0 || T < 0 || feat_stride < dim || out_stride < dim)
-    return fail(KLSTM_ERR_ARG, "klstm_pack_streams: bad size (dim %d, streams %d, T %d, strides %d / %d)", dim, num_stream, T, feat_stride, out_stride);
-  if ((long)T * num_stream > 65535) return fail(KLSTM_ERR_SHAPE, "klstm_pack_streams: T * num_stream > 65535");
-  if (T == 0 || dim == 0) return KLSTM_OK;
-  HIPCHK(launch_pack_streams(feats, dim, feat_stride, stream_desc_dev, num_stream, T, shift, out, out_stride, reset_dev, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-klstm_status klstm_reverse_streams(const float *in, int in_stride, int S, int T, int cols, const int *lens_dev, float *out, int out_stride,
-                                   int mode, void *hip_stream) {
-  if (mode < KLSTM_REVERSE_SET || mode > KLSTM_REVERSE_MASK_COPY) return fail(KLSTM_ERR_ARG, "klstm_reverse_streams: unknown mode %d", mode);
-  const bool reads = mode != KLSTM_REVERSE_ZERO_PAD;
-  if (S <= 0 || T < 0 || cols < 0) return fail(KLSTM_ERR_ARG, "klstm_reverse_streams: bad size (streams %d, T %d, cols %d)", S, T, cols);
-  if ((long)T * S > INT_MAX) return fail(KLSTM_ERR_SHAPE, "klstm_reverse_streams: T * num_stream > INT_MAX");
-  if (T == 0 || cols == 0) return KLSTM_OK;
-  if (out_stride < cols || (reads && in_stride < cols))
-    return fail(KLSTM_ERR_ARG, "klstm_reverse_streams: row stride below the column count (%d / %d < %d)", in_stride, out_stride, cols);
-  if (!out || !lens_dev || (reads && !in)) return fail(KLSTM_ERR_ARG, "klstm_reverse_streams: null argument");
-  if ((mode == KLSTM_REVERSE_SET || mode == KLSTM_REVERSE_ADD) && in == out)
-    return fail(KLSTM_ERR_ARG, "klstm_reverse_streams: in == out (the reversal cannot run in place)");
-  HIPCHK(launch_reverse_streams(in, in_stride, S, T, cols, lens_dev, out, out_stride, mode, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-// ---- the checks of the CTC entry points, spelled once; fn is the entry's name, which every message begins with ----
-// the shape rule of the three workspace queries that take a label length (what: the entry's word for that length)
-static bool ctc_query_ok(const char *fn, const char *what, int T, int S, int L) {
-  if (T > 0 && S > 0 && S <= 32 && (long)T * S <= 65535 && L >= 0 && L <= 1023) return true;
-  fail(KLSTM_ERR_SHAPE, "%s: T %d, streams %d, %s length %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, L <= 1023", fn, T, S, what, L);
-  return false;
-}
-// What the calls share, in the order it has always fired: sizes, limits (min_k: the fewest classes the call takes), the call's own
-// finding about its pointers (null: none; where a call has several, the first to apply), blank, row stride (the smallest of the
-// call's), its finding about aliasing, workspace alignment.
-static klstm_status ctc_call_check(const char *fn, int T, int S, int K, int min_k, const char *pointers, int blank, int stride,
-                                   const char *aliasing, const void *workspace) {
-  if (T <= 0 || S <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "%s: bad size (T %d, streams %d, K %d)", fn, T, S, K);
-  if (S > 32 || (long)T * S > 65535 || K < min_k || K > 32768)
-    return fail(KLSTM_ERR_SHAPE, "%s: T %d, streams %d, K %d outside S <= 32, T * S <= 65535, %d <= K <= 32768", fn, T, S, K, min_k);
-  if (pointers) return fail(KLSTM_ERR_ARG, "%s: %s", fn, pointers);
-  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "%s: blank %d outside [0, %d)", fn, blank, K);
-  if (stride < K) return fail(KLSTM_ERR_ARG, "%s: row stride below K (%d < %d)", fn, stride, K);
-  if (aliasing) return fail(KLSTM_ERR_ARG, "%s: %s", fn, aliasing);
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
-  return KLSTM_OK;
-}
-// the decoders' finding about their references: a pair, and what is counted against them needs them
-static const char *ctc_refs_finding(const int *ref_labels_dev, const int *ref_offsets_dev, const int *errors_dev, const double *totals_dev) {
-  if ((ref_labels_dev == nullptr) != (ref_offsets_dev == nullptr)) return "reference labels and offsets come together or not at all";
-  if (!ref_labels_dev && (errors_dev || totals_dev)) return "errors / totals need reference labels";
-  return nullptr;
-}
-size_t klstm_ctc_workspace_bytes(int T, int S, int max_label_len) {
-  return ctc_query_ok("klstm_ctc_workspace_bytes", "label", T, S, max_label_len) ? ctc_workspace_bytes(T, S, max_label_len) : 0;
-}
-klstm_status klstm_ctc_eval(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *labels_dev,
-                            const int *label_offsets_dev, int blank, float *diff, int diff_stride, float *utt_loss_dev,
-                            double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  const char *fn = "klstm_ctc_eval";
-  const bool null = !net_out || !lens_dev || !labels_dev || !label_offsets_dev || !diff || !utt_loss_dev || !workspace;
-  const klstm_status st = ctc_call_check(fn, T, S, K, 1, null ? "null argument" : nullptr, blank, stride < diff_stride ? stride : diff_stride,
-                                         net_out == diff ? "diff == net_out (the posteriors are read while diff is written)" : nullptr, workspace);
-  if (st != KLSTM_OK) return st;
-  const int lcap = ctc_label_capacity(T, S, workspace_bytes);
-  if (lcap < 0) return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_workspace_bytes(%d, %d, 0)", fn, workspace_bytes, T, S);
-  HIPCHK(launch_ctc(net_out, T, S, K, stride, lens_dev, labels_dev, label_offsets_dev, blank, diff, diff_stride, utt_loss_dev, totals_dev,
-                    workspace, lcap, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-size_t klstm_ctc_decode_workspace_bytes(int T, int S, int max_ref_len) {
-  return ctc_query_ok("klstm_ctc_decode_workspace_bytes", "reference", T, S, max_ref_len) ? ctc_decode_workspace_bytes(T, S) : 0;
-}
-klstm_status klstm_ctc_decode(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
-                              const float *class_weight_dev, int *hyp_dev, int *hyp_len_dev, float *score_dev, int *frame_class_dev,
-                              const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev, double *totals_dev,
-                              void *workspace, size_t workspace_bytes, void *hip_stream) {
-  const char *fn = "klstm_ctc_decode";
-  const char *pointers = ctc_refs_finding(ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev);
-  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !workspace) pointers = "null argument";
-  const klstm_status st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride, nullptr, workspace);
-  if (st != KLSTM_OK) return st;
-  if (workspace_bytes < ctc_decode_workspace_bytes(T, S))
-    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_decode_workspace_bytes(%d, %d, .) = %zu", fn, workspace_bytes,
-                T, S, ctc_decode_workspace_bytes(T, S));
-  HIPCHK(launch_ctc_decode(net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, hyp_dev, hyp_len_dev, score_dev, frame_class_dev,
-                           ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-static bool ctc_beam_shape_ok(int T, int S, int beam, int cands) {
-  return T > 0 && S > 0 && S <= 32 && (long)T * S <= 65535 && beam >= 1 && beam <= 64 && cands >= 1 && cands <= 32;
-}
-size_t klstm_ctc_beam_workspace_bytes(int T, int S, int beam, int cands) {
-  if (!ctc_beam_shape_ok(T, S, beam, cands)) {
-    fail(KLSTM_ERR_SHAPE, "klstm_ctc_beam_workspace_bytes: T %d, streams %d, beam %d, candidates %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, 1 <= beam <= 64, 1 <= candidates <= 32", T, S, beam, cands);
-    return 0;
-  }
-  return ctc_beam_workspace_bytes(T, S, beam, cands);
-}
-// ---- sparse back-off models.  What a blob was built for is remembered per address, as for the MMI graphs below: the header lives
-// on the device and the calls do not wait for it ----
-struct SlmNote { int Q, A, K; size_t bytes; };
-static std::mutex slm_mu;
-static std::map<const void *, SlmNote> slm_blobs;
-static bool ctc_slm_shape_ok(int states, int arcs, int K) {
-  return states >= 1 && states <= (1 << 24) && arcs >= 1 && arcs <= (1 << 26) && K >= 2 && K <= 32768;
-}
-size_t klstm_ctc_slm_bytes(int states, int arcs, int K) {
-  if (!ctc_slm_shape_ok(states, arcs, K)) {
-    fail(KLSTM_ERR_SHAPE, "klstm_ctc_slm_bytes: %d states, %d arcs, %d classes outside 1 <= states <= 2^24, 1 <= arcs <= 2^26, 2 <= K <= 32768", states, arcs, K);
-    return 0;
-  }
-  return ctc_slm_bytes(states, arcs);
-}
-klstm_status klstm_ctc_slm_build(int states, int arcs, int K, int blank, const int *arc_offsets_dev, const int *arc_labels_dev,
-                                 const int *arc_next_dev, const float *arc_weight_dev, const int *backoff_dev, const float *backoff_weight_dev,
-                                 void *slm, size_t slm_bytes, int *status_dev, void *hip_stream) {
-  const char *fn = "klstm_ctc_slm_build";
-  if (states <= 0 || arcs <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "%s: bad size (%d states, %d arcs, K %d)", fn, states, arcs, K);
-  if (!ctc_slm_shape_ok(states, arcs, K))
-    return fail(KLSTM_ERR_SHAPE, "%s: %d states, %d arcs, %d classes outside states <= 2^24, arcs <= 2^26, 2 <= K <= 32768", fn, states, arcs, K);
-  if (!arc_offsets_dev || !arc_labels_dev || !arc_next_dev || !arc_weight_dev || !backoff_dev || !backoff_weight_dev || !slm)
-    return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
-  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "%s: blank %d outside [0, %d)", fn, blank, K);
-  if ((reinterpret_cast<uintptr_t>(slm) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: the model's buffer must be 16-byte aligned", fn);
-  if (slm_bytes < ctc_slm_bytes(states, arcs))
-    return fail(KLSTM_ERR_ARG, "%s: buffer of %zu bytes is below klstm_ctc_slm_bytes(%d, %d, %d) = %zu", fn, slm_bytes, states, arcs, K,
-                ctc_slm_bytes(states, arcs));
-  {
-    std::lock_guard<std::mutex> lk(slm_mu);
-    slm_blobs.erase(slm);
-  }
-  HIPCHK(launch_ctc_slm_build(states, arcs, K, blank, arc_offsets_dev, arc_labels_dev, arc_next_dev, arc_weight_dev, backoff_dev,
-                              backoff_weight_dev, slm, status_dev, (hipStream_t)hip_stream));
-  std::lock_guard<std::mutex> lk(slm_mu);
-  slm_blobs[slm] = SlmNote{states, arcs, K, ctc_slm_bytes(states, arcs)};
-  return KLSTM_OK;
-}
-// null: the blob serves a call with these sizes; else what is wrong with it
-static const char *ctc_slm_finding(const void *slm, size_t slm_bytes, int lm_states, int K) {
-  if (!slm) return "null sparse language model";
-  std::lock_guard<std::mutex> lk(slm_mu);
-  const auto it = slm_blobs.find(slm);
-  if (it == slm_blobs.end()) return "no sparse language model was built at this address (klstm_ctc_slm_build)";
-  if (it->second.Q != lm_states || it->second.K != K) return "the sparse language model was built for other states or classes";
-  if (slm_bytes < it->second.bytes) return "the sparse language model's bytes are below klstm_ctc_slm_bytes";
-  return nullptr;
-}
-// the checks and the launch behind klstm_ctc_beam_decode (Q = 0, no tables), klstm_ctc_beam_decode_lm (with_lm: 1 <= Q) and
-// klstm_ctc_beam_decode_slm (slm_call: lm_next_dev is the blob, slm_bytes its size, 1 <= Q)
-static klstm_status ctc_beam_decode_checked(const char *fn, bool with_lm, bool slm_call, size_t slm_bytes, const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
-                                            const float *class_weight_dev, int beam, int cands, int nbest, int Q, const int *lm_next_dev,
-                                            const float *lm_weight_dev, const float *lm_final_dev, int *hyp_dev, int *hyp_len_dev,
-                                            int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
-                                            int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  if (T <= 0 || S <= 0 || K <= 0 || beam <= 0 || cands <= 0 || nbest <= 0)
-    return fail(KLSTM_ERR_ARG, "%s: bad size (T %d, streams %d, K %d, beam %d, candidates %d, n-best %d)", fn, T, S, K, beam, cands, nbest);
-  if (!ctc_beam_shape_ok(T, S, beam, cands) || K < 2 || K > 32768 || cands > K - 1 || nbest > beam)
-    return fail(KLSTM_ERR_SHAPE, "%s: T %d, streams %d, K %d, beam %d, candidates %d, n-best %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768, beam <= 64, candidates <= min(K - 1, 32), n-best <= beam",
-                fn, T, S, K, beam, cands, nbest);
-  if (slm_call && (Q < 1 || Q > (1 << 24)))
-    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states outside 1 <= states <= 2^24", fn, Q);
-  if (!slm_call && (Q < (with_lm ? 1 : 0) || (long)Q * K > (1L << 24)))
-    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 1 <= states, states * K <= 2^24", fn, Q, K);
-  const char *pointers = ctc_refs_finding(ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev);      // (the later one here fires first)
-  if (slm_call) {
-    const char *f = ctc_slm_finding(lm_next_dev, slm_bytes, Q, K);
-    if (f) pointers = f;
-  } else if (Q > 0 && (!lm_next_dev || !lm_weight_dev)) pointers = "the language model's next and weight tables come together";
-  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !nbest_count_dev || !workspace) pointers = "null argument";
-  const klstm_status st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride, nullptr, workspace);
-  if (st != KLSTM_OK) return st;
-  if (workspace_bytes < ctc_beam_workspace_bytes(T, S, beam, cands))
-    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_beam_workspace_bytes(%d, %d, %d, %d) = %zu", fn, workspace_bytes,
-                T, S, beam, cands, ctc_beam_workspace_bytes(T, S, beam, cands));
-  if (slm_call) {
-    HIPCHK(launch_ctc_beam_slm(net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest, Q, lm_next_dev, lm_final_dev,
-                               hyp_dev, hyp_len_dev, nbest_count_dev, score_dev, ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev,
-                               workspace, (hipStream_t)hip_stream));
-    return KLSTM_OK;
-  }
-  HIPCHK(launch_ctc_beam_lm(net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest, Q, lm_next_dev, lm_weight_dev,
-                            lm_final_dev, hyp_dev, hyp_len_dev, nbest_count_dev, score_dev, ref_labels_dev, ref_offsets_dev, errors_dev,
-                            totals_dev, workspace, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-klstm_status klstm_ctc_beam_decode(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
-                                   const float *class_weight_dev, int beam, int cands, int nbest, int *hyp_dev, int *hyp_len_dev,
-                                   int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
-                                   int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  return ctc_beam_decode_checked("klstm_ctc_beam_decode", false, false, 0, net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest, 0,
-                                 nullptr, nullptr, nullptr, hyp_dev, hyp_len_dev, nbest_count_dev, score_dev, ref_labels_dev, ref_offsets_dev,
-                                 errors_dev, totals_dev, workspace, workspace_bytes, hip_stream);
-}
-klstm_status klstm_ctc_beam_decode_lm(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
-                                      const float *class_weight_dev, int beam, int cands, int nbest, int lm_states, const int *lm_next_dev,
-                                      const float *lm_weight_dev, const float *lm_final_dev, int *hyp_dev, int *hyp_len_dev,
-                                      int *nbest_count_dev, float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev,
-                                      int *errors_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  return ctc_beam_decode_checked("klstm_ctc_beam_decode_lm", true, false, 0, net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam, cands, nbest,
-                                 lm_states, lm_next_dev, lm_weight_dev, lm_final_dev, hyp_dev, hyp_len_dev, nbest_count_dev, score_dev,
-                                 ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, workspace_bytes, hip_stream);
-}
-klstm_status klstm_ctc_beam_decode_slm(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank,
-                                       const float *class_weight_dev, int beam, int cands, int nbest, const void *slm, size_t slm_bytes,
-                                       int lm_states, const float *lm_final_dev, int *hyp_dev, int *hyp_len_dev, int *nbest_count_dev,
-                                       float *score_dev, const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev,
-                                       double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  return ctc_beam_decode_checked("klstm_ctc_beam_decode_slm", true, true, slm_bytes, net_out, T, S, K, stride, lens_dev, blank, class_weight_dev, beam,
-                                 cands, nbest, lm_states, reinterpret_cast<const int *>(slm), nullptr, lm_final_dev, hyp_dev, hyp_len_dev,
-                                 nbest_count_dev, score_dev, ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev, workspace, workspace_bytes,
-                                 hip_stream);
-}
-int klstm_ctc_beam_lm_resident(int lm_states, int K, int beam, int cands) {
-  if (lm_states < 1 || K < 2 || (long)lm_states * K > (1L << 24)) return 0;
-  return ctc_beam_lm_resident(lm_states, K, beam, cands) ? 1 : 0;
-}
-static bool ctc_beam_stream_state_ok(int max_frames, int S, int beam) {
-  return max_frames >= 1 && S >= 1 && S <= 32 && beam >= 1 && beam <= 64 && (long)max_frames * beam + 1 < (1L << 31);
-}
-size_t klstm_ctc_beam_stream_state_bytes(int max_frames, int S, int beam) {
-  if (!ctc_beam_stream_state_ok(max_frames, S, beam)) {
-    fail(KLSTM_ERR_SHAPE, "klstm_ctc_beam_stream_state_bytes: %d frames, streams %d, beam %d outside 1 <= frames, 1 <= S <= 32, 1 <= beam <= 64, frames * beam + 1 < 2^31", max_frames, S, beam);
-    return 0;
-  }
-  return ctc_beam_stream_state_bytes(max_frames, S, beam);
-}
-size_t klstm_ctc_beam_stream_workspace_bytes(int T, int S, int cands, int nbest) {
-  if (!ctc_beam_shape_ok(T, S, 1, cands) || nbest < 1 || nbest > 64) {
-    fail(KLSTM_ERR_SHAPE, "klstm_ctc_beam_stream_workspace_bytes: T %d, streams %d, candidates %d, n-best %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, 1 <= candidates <= 32, 1 <= n-best <= 64", T, S, cands, nbest);
-    return 0;
-  }
-  return ctc_beam_stream_workspace_bytes(T, S, cands, nbest);
-}
-// what step and emit check alike about the state
-static klstm_status ctc_beam_stream_state_check(const char *fn, int S, int beam, const void *state, size_t state_bytes, int max_frames) {
-  if (!ctc_beam_stream_state_ok(max_frames, S, beam))
-    return fail(KLSTM_ERR_SHAPE, "%s: %d frames, streams %d, beam %d outside 1 <= frames, S <= 32, beam <= 64, frames * beam + 1 < 2^31", fn, max_frames, S, beam);
-  if (!state) return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
-  if ((reinterpret_cast<uintptr_t>(state) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: state must be 16-byte aligned", fn);
-  if (state_bytes < ctc_beam_stream_state_bytes(max_frames, S, beam))
-    return fail(KLSTM_ERR_ARG, "%s: state of %zu bytes is below klstm_ctc_beam_stream_state_bytes(%d, %d, %d) = %zu", fn, state_bytes, max_frames, S,
-                beam, ctc_beam_stream_state_bytes(max_frames, S, beam));
-  return KLSTM_OK;
-}
-// the checks and the launch behind klstm_ctc_beam_stream_step and klstm_ctc_beam_stream_step_slm (slm_call: lm_next_dev is the blob,
-// slm_bytes its size, 1 <= lm_states)
-static klstm_status ctc_beam_stream_step_checked(const char *fn, bool slm_call, size_t slm_bytes, const float *net_out, int T, int S, int K, int stride,
-                                                 const int *lens_dev, const int *start_dev, int blank, const float *class_weight_dev, int beam,
-                                                 int cands, int lm_states, const int *lm_next_dev, const float *lm_weight_dev, void *state,
-                                                 size_t state_bytes, int max_frames, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  if (T <= 0 || S <= 0 || K <= 0 || beam <= 0 || cands <= 0)
-    return fail(KLSTM_ERR_ARG, "%s: bad size (T %d, streams %d, K %d, beam %d, candidates %d)", fn, T, S, K, beam, cands);
-  if (!ctc_beam_shape_ok(T, S, beam, cands) || K < 2 || K > 32768 || cands > K - 1)
-    return fail(KLSTM_ERR_SHAPE, "%s: T %d, streams %d, K %d, beam %d, candidates %d outside S <= 32, T * S <= 65535, 2 <= K <= 32768, beam <= 64, candidates <= min(K - 1, 32)",
-                fn, T, S, K, beam, cands);
-  if (slm_call ? (lm_states < 1 || lm_states > (1 << 24)) : (lm_states < 0 || (long)lm_states * K > (1L << 24)))
-    return fail(KLSTM_ERR_SHAPE, slm_call ? "%s: %d language-model states (%d classes) outside 1 <= states <= 2^24"
-                                          : "%s: %d language-model states of %d classes outside 0 <= states, states * K <= 2^24", fn, lm_states, K);
-  klstm_status st = ctc_beam_stream_state_check(fn, S, beam, state, state_bytes, max_frames);
-  if (st != KLSTM_OK) return st;
-  const char *pointers = nullptr;
-  if (slm_call) pointers = ctc_slm_finding(lm_next_dev, slm_bytes, lm_states, K);
-  else if (lm_states > 0 && (!lm_next_dev || !lm_weight_dev)) pointers = "the language model's next and weight tables come together";
-  if (!net_out || !lens_dev || !workspace) pointers = "null argument";
-  st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride, nullptr, workspace);
-  if (st != KLSTM_OK) return st;
-  if (workspace_bytes < ctc_beam_stream_workspace_bytes(T, S, cands, 1))
-    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_beam_stream_workspace_bytes(%d, %d, %d, .) = %zu", fn, workspace_bytes,
-                T, S, cands, ctc_beam_stream_workspace_bytes(T, S, cands, 1));
-  HIPCHK(launch_ctc_beam_stream_step(net_out, T, S, K, stride, lens_dev, start_dev, blank, class_weight_dev, beam, cands, lm_states, lm_next_dev,
-                                     lm_weight_dev, slm_call, state, max_frames, workspace, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-klstm_status klstm_ctc_beam_stream_step(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *start_dev,
-                                        int blank, const float *class_weight_dev, int beam, int cands, int lm_states,
-                                        const int *lm_next_dev, const float *lm_weight_dev, void *state, size_t state_bytes, int max_frames,
-                                        void *workspace, size_t workspace_bytes, void *hip_stream) {
-  return ctc_beam_stream_step_checked("klstm_ctc_beam_stream_step", false, 0, net_out, T, S, K, stride, lens_dev, start_dev, blank, class_weight_dev,
-                                      beam, cands, lm_states, lm_next_dev, lm_weight_dev, state, state_bytes, max_frames, workspace,
-                                      workspace_bytes, hip_stream);
-}
-klstm_status klstm_ctc_beam_stream_step_slm(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *start_dev,
-                                            int blank, const float *class_weight_dev, int beam, int cands, const void *slm, size_t slm_bytes,
-                                            int lm_states, void *state, size_t state_bytes, int max_frames, void *workspace,
-                                            size_t workspace_bytes, void *hip_stream) {
-  return ctc_beam_stream_step_checked("klstm_ctc_beam_stream_step_slm", true, slm_bytes, net_out, T, S, K, stride, lens_dev, start_dev, blank,
-                                      class_weight_dev, beam, cands, lm_states, reinterpret_cast<const int *>(slm), nullptr, state, state_bytes,
-                                      max_frames, workspace, workspace_bytes, hip_stream);
-}
-klstm_status klstm_ctc_beam_stream_emit(int S, int K, int blank, int beam, int nbest, const int *mode_dev, int lm_states,
-                                        const float *lm_final_dev, const void *state, size_t state_bytes, int max_frames, int *hyp_dev,
-                                        int hyp_stride, int *hyp_len_dev, int *nbest_count_dev, float *score_dev, int *frames_dev,
-                                        int *stable_len_dev, const int *ref_labels_dev, const int *ref_offsets_dev, int *errors_dev,
-                                        double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  const char *fn = "klstm_ctc_beam_stream_emit";
-  if (S <= 0 || K <= 0 || beam <= 0 || nbest <= 0)
-    return fail(KLSTM_ERR_ARG, "%s: bad size (streams %d, K %d, beam %d, n-best %d)", fn, S, K, beam, nbest);
-  if (S > 32 || K < 2 || K > 32768 || beam > 64 || nbest > beam)
-    return fail(KLSTM_ERR_SHAPE, "%s: streams %d, K %d, beam %d, n-best %d outside S <= 32, 2 <= K <= 32768, beam <= 64, n-best <= beam", fn, S, K, beam, nbest);
-  if (lm_states < 0 || (long)lm_states * K > (1L << 24))
-    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 0 <= states, states * K <= 2^24", fn, lm_states, K);
-  if (ctc_beam_stream_state_ok(max_frames, S, beam) && hyp_stride < max_frames)      // (every limit before any pointer)
-    return fail(KLSTM_ERR_SHAPE, "%s: hypothesis stride %d below the %d frames of the state", fn, hyp_stride, max_frames);
-  klstm_status st = ctc_beam_stream_state_check(fn, S, beam, state, state_bytes, max_frames);
-  if (st != KLSTM_OK) return st;
-  const char *pointers = ctc_refs_finding(ref_labels_dev, ref_offsets_dev, errors_dev, totals_dev);
-  if (!mode_dev || !hyp_dev || !hyp_len_dev || !nbest_count_dev || !workspace) pointers = "null argument";
-  if (pointers) return fail(KLSTM_ERR_ARG, "%s: %s", fn, pointers);
-  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "%s: blank %d outside [0, %d)", fn, blank, K);
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
-  if (workspace_bytes < ctc_beam_stream_emit_workspace_bytes())
-    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_beam_stream_workspace_bytes(1, %d, 1, .) = %zu", fn, workspace_bytes, S,
-                ctc_beam_stream_workspace_bytes(1, S, 1, 1));
-  HIPCHK(launch_ctc_beam_stream_emit(S, K, blank, beam, nbest, mode_dev, lm_states, lm_final_dev, state, max_frames, hyp_dev, hyp_stride,
-                                     hyp_len_dev, nbest_count_dev, score_dev, frames_dev, stable_len_dev, ref_labels_dev, ref_offsets_dev,
-                                     errors_dev, totals_dev, workspace, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-static bool ctc_mbr_shape_ok(int T, int S, int list_n, int max_len) {
-  return T > 0 && S > 0 && S <= 32 && (long)T * S <= 65535 && list_n >= 1 && list_n <= 16 && max_len >= 0 && max_len <= 1023;
-}
-size_t klstm_ctc_mbr_workspace_bytes(int T, int S, int list_n, int max_len, int with_ref) {
-  if (!ctc_mbr_shape_ok(T, S, list_n, max_len)) {
-    fail(KLSTM_ERR_SHAPE, "klstm_ctc_mbr_workspace_bytes: T %d, streams %d, list of %d, labelling length %d outside T >= 1, 1 <= S <= 32, T * S <= 65535, 1 <= list <= 16, L <= 1023", T, S, list_n, max_len);
-    return 0;
-  }
-  return ctc_mbr_workspace_bytes(T, S, list_n, max_len, with_ref != 0);
-}
-klstm_status klstm_ctc_mbr_eval(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, int blank, const int *hyp_dev,
-                                int hyp_stride, const int *hyp_len_dev, const int *nbest_count_dev, const int *errors_dev, int list_n,
-                                const int *ref_labels_dev, const int *ref_offsets_dev, float risk_scale, float ctc_weight, float *diff,
-                                int diff_stride, float *risk_dev, float *hyp_logp_dev, float *hyp_post_dev, float *ref_loss_dev,
-                                double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  const char *fn = "klstm_ctc_mbr_eval";
-  if (T <= 0 || S <= 0 || K <= 0 || list_n <= 0 || hyp_stride <= 0)
-    return fail(KLSTM_ERR_ARG, "%s: bad size (T %d, streams %d, K %d, list of %d, hypothesis stride %d)", fn, T, S, K, list_n, hyp_stride);
-  if (list_n > 16) return fail(KLSTM_ERR_SHAPE, "%s: list of %d outside 1 <= list <= 16", fn, list_n);
-  if (!(risk_scale > 0.f) || !std::isfinite(risk_scale)) return fail(KLSTM_ERR_ARG, "%s: risk scale %g is not a finite number above 0", fn, (double)risk_scale);
-  if (!(ctc_weight >= 0.f) || !std::isfinite(ctc_weight)) return fail(KLSTM_ERR_ARG, "%s: CTC weight %g is not a finite number >= 0", fn, (double)ctc_weight);
-  const bool with_ref = ctc_weight > 0.f;
-  const char *pointers = nullptr;
-  if ((ref_labels_dev == nullptr) != (ref_offsets_dev == nullptr)) pointers = "reference labels and offsets come together or not at all";
-  else if ((ref_labels_dev != nullptr) != with_ref) pointers = "the reference is given exactly when the CTC weight is above 0";
-  if (!net_out || !lens_dev || !hyp_dev || !hyp_len_dev || !nbest_count_dev || !errors_dev || !diff || !risk_dev || !workspace) pointers = "null argument";
-  const klstm_status st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride < diff_stride ? stride : diff_stride,
-                                         net_out == diff ? "diff == net_out (the posteriors are read while diff is written)" : nullptr, workspace);
-  if (st != KLSTM_OK) return st;
-  const int lcap = ctc_mbr_label_capacity(T, S, list_n, with_ref, workspace_bytes);
-  if (lcap < 0)
-    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_mbr_workspace_bytes(%d, %d, %d, 0, %d) = %zu", fn, workspace_bytes, T, S,
-                list_n, (int)with_ref, ctc_mbr_workspace_bytes(T, S, list_n, 0, with_ref));
-  HIPCHK(launch_ctc_mbr(net_out, T, S, K, stride, lens_dev, blank, hyp_dev, hyp_stride, hyp_len_dev, nbest_count_dev, errors_dev, list_n,
-                        ref_labels_dev, ref_offsets_dev, risk_scale, ctc_weight, diff, diff_stride, risk_dev, hyp_logp_dev, hyp_post_dev,
-                        ref_loss_dev, totals_dev, workspace, lcap, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-// ---- calls over n-best lists (the consensus, the rescoring): the checks they share, each fired from the place it always had ----
-static bool ctc_nbest_shape_ok(int S, int list_n, int max_len) {
-  return S >= 1 && S <= 32 && list_n >= 1 && list_n <= 64 && max_len >= 0 && max_len <= 1023;
-}
-struct CtcNbestCall {
-  const char *fn; int S, list_n, max_len, hyp_stride;
-  klstm_status shape() const {                                     // every limit before any pointer
-    if (ctc_nbest_shape_ok(S, list_n, max_len)) return KLSTM_OK;
-    return fail(KLSTM_ERR_SHAPE, "%s: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", fn, S, list_n, max_len);
-  }
-  klstm_status strides(const char *what, int out_stride, bool written = true) const {      // of hyp, and of the output of whole entries
-    if (hyp_stride > 0 && !(written && out_stride < (hyp_stride < max_len ? hyp_stride : max_len))) return KLSTM_OK;
-    return fail(KLSTM_ERR_ARG, "%s: hypothesis stride %d, %s stride %d (at least min(hypothesis stride, length %d))", fn, hyp_stride, what, out_stride, max_len);
-  }
-  klstm_status workspace(const void *ws, size_t bytes, const char *size_fn, int word_mode, size_t need) const {      // alignment, then size
-    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
-    if (bytes >= need) return KLSTM_OK;
-    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below %s(%d, %d, %d, %d) = %zu", fn, bytes, size_fn, S, list_n, max_len, word_mode, need);
-  }
-};
-size_t klstm_ctc_consensus_workspace_bytes(int S, int list_n, int max_len, int word_mode) {
-  if (!ctc_nbest_shape_ok(S, list_n, max_len)) {
-    fail(KLSTM_ERR_SHAPE, "klstm_ctc_consensus_workspace_bytes: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", S, list_n, max_len);
-    return 0;
-  }
-  return ctc_consensus_workspace_bytes(S, list_n, max_len, word_mode != 0);
-}
-klstm_status klstm_ctc_consensus(const int *hyp_dev, int hyp_stride, const int *hyp_len_dev, const int *nbest_count_dev, const float *logp_dev,
-                                 const int *errors_dev, int S, int list_n, int max_len, float scale, int separator, int pivot_mode,
-                                 int *pick_dev, int *map_dev, int *mbr_dev, float *post_dev, float *risk_dev, int *unit_len_dev,
-                                 float *conf_dev, int conf_stride, int *dist_dev, double *totals_dev, void *workspace, size_t workspace_bytes,
-                                 void *hip_stream) {
-  const char *fn = "klstm_ctc_consensus";
-  const CtcNbestCall call{fn, S, list_n, max_len, hyp_stride};
-  if (klstm_status st = call.shape(); st != KLSTM_OK) return st;
-  if (klstm_status st = call.strides("confidence", conf_stride); st != KLSTM_OK) return st;
-  if (!(scale > 0.f) || !std::isfinite(scale)) return fail(KLSTM_ERR_ARG, "%s: scale %g is not a finite number above 0", fn, (double)scale);
-  if (pivot_mode != 0 && pivot_mode != 1) return fail(KLSTM_ERR_ARG, "%s: pivot mode %d is neither 0 (MAP) nor 1 (MBR)", fn, pivot_mode);
-  if (!hyp_dev || !hyp_len_dev || !nbest_count_dev || !logp_dev || !pick_dev || !map_dev || !mbr_dev || !post_dev || !risk_dev || !unit_len_dev ||
-      !conf_dev || !workspace)
-    return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
-  if (klstm_status st = call.workspace(workspace, workspace_bytes, "klstm_ctc_consensus_workspace_bytes", separator >= 0,
-                                       ctc_consensus_workspace_bytes(S, list_n, max_len, separator >= 0)); st != KLSTM_OK) return st;
-  HIPCHK(launch_ctc_consensus(hyp_dev, hyp_stride, hyp_len_dev, nbest_count_dev, logp_dev, errors_dev, S, list_n, max_len, scale, separator,
-                              pivot_mode, pick_dev, map_dev, mbr_dev, post_dev, risk_dev, unit_len_dev, conf_dev, conf_stride, dist_dev,
-                              totals_dev, workspace, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-// ---- second-pass rescoring of n-best lists.  The models are blobs of klstm_ctc_slm_build, known by their addresses ----
-size_t klstm_ctc_rescore_workspace_bytes(int S, int list_n, int max_len, int word_mode) {
-  if (!ctc_nbest_shape_ok(S, list_n, max_len)) {
-    fail(KLSTM_ERR_SHAPE, "klstm_ctc_rescore_workspace_bytes: streams %d, list of %d, length %d outside 1 <= S <= 32, 1 <= list <= 64, 0 <= L <= 1023", S, list_n, max_len);
-    return 0;
-  }
-  return ctc_rescore_workspace_bytes(S, list_n, max_len, word_mode != 0);
-}
-klstm_status klstm_ctc_nbest_rescore(const int *hyp_dev, int hyp_stride, const int *hyp_len_dev, const int *nbest_count_dev, const float *logp_dev,
-                                     const int *errors_dev, int S, int list_n, int max_len, int K, const void *sub_slm, size_t sub_bytes,
-                                     int sub_states, const float *sub_final_dev, const void *add_slm, size_t add_bytes, int add_states,
-                                     int add_classes, const float *add_final_dev, const unsigned long long *word_keys_dev,
-                                     const int *word_ids_dev, int num_words, int unk_id, int separator, int add_reserved, float am_scale,
-                                     float add_scale, float unit_bonus, int *order_dev, int *live_count_dev, float *score_dev,
-                                     float *add_logp_dev, float *sub_logp_dev, int *units_dev, int *oov_dev, int out_n, int *out_hyp_dev,
-                                     int out_stride, int *out_len_dev, int *out_count_dev, float *out_score_dev, int *out_errors_dev,
-                                     double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  const char *fn = "klstm_ctc_nbest_rescore";
-  const CtcNbestCall call{fn, S, list_n, max_len, hyp_stride};
-  if (klstm_status st = call.shape(); st != KLSTM_OK) return st;
-  if (K < 2 || K > 32768) return fail(KLSTM_ERR_SHAPE, "%s: %d classes outside 2 <= K <= 32768", fn, K);
-  if (num_words < 0 || num_words > (1 << 24)) return fail(KLSTM_ERR_SHAPE, "%s: %d words outside 0 <= words <= 2^24", fn, num_words);
-  if (out_n < 0 || out_n > list_n) return fail(KLSTM_ERR_SHAPE, "%s: a list of %d out of a list of %d", fn, out_n, list_n);
-  if (!hyp_dev || !hyp_len_dev || !nbest_count_dev || !logp_dev || !order_dev || !live_count_dev || !score_dev || !workspace)
-    return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
-  if (out_n >= 1 && (!out_hyp_dev || !out_len_dev || !out_count_dev || !out_score_dev))
-    return fail(KLSTM_ERR_ARG, "%s: null list output with out_n %d", fn, out_n);
-  if (klstm_status st = call.strides("output", out_stride, out_n >= 1); st != KLSTM_OK) return st;
-  if (!std::isfinite(am_scale) || !std::isfinite(add_scale) || !std::isfinite(unit_bonus))
-    return fail(KLSTM_ERR_ARG, "%s: scales %g, %g and bonus %g must be finite", fn, (double)am_scale, (double)add_scale, (double)unit_bonus);
-  if (!sub_slm && !add_slm) return fail(KLSTM_ERR_ARG, "%s: neither a model to subtract nor one to add", fn);
-  if (num_words > 0 && !add_slm) return fail(KLSTM_ERR_ARG, "%s: a word table without a model to add", fn);
-  if (num_words > 0) {
-    if (!word_keys_dev || !word_ids_dev) return fail(KLSTM_ERR_ARG, "%s: null word table", fn);
-    if (separator < 0 || separator >= K) return fail(KLSTM_ERR_ARG, "%s: separator %d outside [0, %d)", fn, separator, K);
-    if (add_reserved < 0 || add_reserved >= add_classes || unk_id >= add_classes || unk_id == add_reserved)
-      return fail(KLSTM_ERR_ARG, "%s: reserved class %d, unknown-word class %d with %d word classes", fn, add_reserved, unk_id, add_classes);
-  } else if (add_slm && add_classes != K) {
-    return fail(KLSTM_ERR_ARG, "%s: a token-level model of %d classes over %d classes", fn, add_classes, K);
-  }
-  if (sub_slm) {
-    const char *f = ctc_slm_finding(sub_slm, sub_bytes, sub_states, K);
-    if (f) return fail(KLSTM_ERR_ARG, "%s: sub: %s", fn, f);
-  }
-  if (add_slm) {
-    const char *f = ctc_slm_finding(add_slm, add_bytes, add_states, add_classes);
-    if (f) return fail(KLSTM_ERR_ARG, "%s: add: %s", fn, f);
-  }
-  if (klstm_status st = call.workspace(workspace, workspace_bytes, "klstm_ctc_rescore_workspace_bytes", num_words > 0,
-                                       ctc_rescore_workspace_bytes(S, list_n, max_len, num_words > 0)); st != KLSTM_OK) return st;
-  HIPCHK(launch_ctc_rescore(hyp_dev, hyp_stride, hyp_len_dev, nbest_count_dev, logp_dev, errors_dev, S, list_n, max_len, K, sub_slm, sub_states,
-                            sub_final_dev, add_slm, add_states, add_classes, add_final_dev, word_keys_dev, word_ids_dev, num_words, unk_id,
-                            separator, add_reserved, am_scale, add_scale, unit_bonus, order_dev, live_count_dev, score_dev, add_logp_dev,
-                            sub_logp_dev, units_dev, oov_dev, out_n, out_hyp_dev, out_stride, out_len_dev, out_count_dev, out_score_dev,
-                            out_errors_dev, totals_dev, workspace, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-// ---- MMI against a label-LM denominator.  What a graph was built for is remembered per address: the header lives on the device and
-// the calls do not wait for it, so klstm_ctc_mmi_eval knows a graph by where klstm_ctc_mmi_graph_build put it ----
-struct MmiGraphNote { int Q, K, blank; };
-static std::mutex mmi_graph_mu;
-static std::map<const void *, MmiGraphNote> mmi_graphs;
-static bool ctc_mmi_lm_ok(int lm_states, int K) { return lm_states >= 1 && K >= 2 && (long)lm_states * K <= 16384; }
-size_t klstm_ctc_mmi_graph_bytes(int lm_states, int K) {
-  if (!ctc_mmi_lm_ok(lm_states, K)) {
-    fail(KLSTM_ERR_SHAPE, "klstm_ctc_mmi_graph_bytes: %d language-model states of %d classes outside 1 <= states, 2 <= K, states * K <= 16384", lm_states, K);
-    return 0;
-  }
-  return ctc_mmi_graph_bytes(lm_states, K);
-}
-klstm_status klstm_ctc_mmi_graph_build(int lm_states, int K, int blank, const int *lm_next_dev, const float *lm_weight_dev,
-                                       const float *lm_final_dev, void *graph, size_t graph_bytes, void *hip_stream) {
-  const char *fn = "klstm_ctc_mmi_graph_build";
-  if (lm_states <= 0 || K <= 0) return fail(KLSTM_ERR_ARG, "%s: bad size (%d language-model states, K %d)", fn, lm_states, K);
-  if (!ctc_mmi_lm_ok(lm_states, K))
-    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 2 <= K, states * K <= 16384", fn, lm_states, K);
-  if (!lm_next_dev || !lm_weight_dev || !graph) return fail(KLSTM_ERR_ARG, "%s: null argument", fn);
-  if (blank < 0 || blank >= K) return fail(KLSTM_ERR_ARG, "%s: blank %d outside [0, %d)", fn, blank, K);
-  if ((reinterpret_cast<uintptr_t>(graph) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: graph must be 16-byte aligned", fn);
-  if (graph_bytes < ctc_mmi_graph_bytes(lm_states, K))
-    return fail(KLSTM_ERR_ARG, "%s: graph of %zu bytes is below klstm_ctc_mmi_graph_bytes(%d, %d) = %zu", fn, graph_bytes, lm_states, K,
-                ctc_mmi_graph_bytes(lm_states, K));
-  {
-    std::lock_guard<std::mutex> lk(mmi_graph_mu);
-    mmi_graphs.erase(graph);
-  }
-  HIPCHK(launch_ctc_mmi_graph(lm_states, K, blank, lm_next_dev, lm_weight_dev, lm_final_dev, graph, (hipStream_t)hip_stream));
-  std::lock_guard<std::mutex> lk(mmi_graph_mu);
-  mmi_graphs[graph] = MmiGraphNote{lm_states, K, blank};
-  return KLSTM_OK;
-}
-size_t klstm_ctc_mmi_workspace_bytes(int T, int S, int K, int lm_states, int max_label_len) {
-  const char *fn = "klstm_ctc_mmi_workspace_bytes";
-  if (!ctc_query_ok(fn, "label", T, S, max_label_len)) return 0;
-  if (!ctc_mmi_lm_ok(lm_states, K)) {
-    fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 1 <= states, 2 <= K, states * K <= 16384", fn, lm_states, K);
-    return 0;
-  }
-  return ctc_mmi_workspace_bytes(T, S, K, lm_states, max_label_len);
-}
-klstm_status klstm_ctc_mmi_eval(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *labels_dev,
-                                const int *label_offsets_dev, int blank, const void *graph, size_t graph_bytes, int lm_states,
-                                float ctc_weight, float *diff, int diff_stride, float *loss_dev, float *num_logp_dev, float *den_logz_dev,
-                                float *lm_logw_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  const char *fn = "klstm_ctc_mmi_eval";
-  if (T <= 0 || S <= 0 || K <= 0 || lm_states <= 0) return fail(KLSTM_ERR_ARG, "%s: bad size (T %d, streams %d, K %d, %d language-model states)", fn, T, S, K, lm_states);
-  if (!ctc_mmi_lm_ok(lm_states, K))
-    return fail(KLSTM_ERR_SHAPE, "%s: %d language-model states of %d classes outside 2 <= K, states * K <= 16384", fn, lm_states, K);
-  if (!(ctc_weight >= 0.f) || !std::isfinite(ctc_weight)) return fail(KLSTM_ERR_ARG, "%s: CTC weight %g is not a finite number >= 0", fn, (double)ctc_weight);
-  const bool null = !net_out || !lens_dev || !labels_dev || !label_offsets_dev || !graph || !diff || !loss_dev || !workspace;
-  const klstm_status st = ctc_call_check(fn, T, S, K, 2, null ? "null argument" : nullptr, blank, stride < diff_stride ? stride : diff_stride,
-                                         net_out == diff ? "diff == net_out (the posteriors are read while diff is written)" : nullptr, workspace);
-  if (st != KLSTM_OK) return st;
-  if ((reinterpret_cast<uintptr_t>(graph) & 15) != 0) return fail(KLSTM_ERR_ARG, "%s: graph must be 16-byte aligned", fn);
-  if (graph_bytes < ctc_mmi_graph_bytes(lm_states, K))
-    return fail(KLSTM_ERR_ARG, "%s: graph of %zu bytes is below klstm_ctc_mmi_graph_bytes(%d, %d) = %zu", fn, graph_bytes, lm_states, K,
-                ctc_mmi_graph_bytes(lm_states, K));
-  {
-    std::lock_guard<std::mutex> lk(mmi_graph_mu);
-    const auto it = mmi_graphs.find(graph);
-    if (it == mmi_graphs.end()) return fail(KLSTM_ERR_ARG, "%s: no graph was built at this address (klstm_ctc_mmi_graph_build)", fn);
-    if (it->second.Q != lm_states || it->second.K != K || it->second.blank != blank)
-      return fail(KLSTM_ERR_ARG, "%s: the graph was built for %d states, K %d, blank %d, not for %d states, K %d, blank %d", fn, it->second.Q,
-                  it->second.K, it->second.blank, lm_states, K, blank);
-  }
-  const int lcap = ctc_mmi_label_capacity(T, S, K, lm_states, workspace_bytes);
-  if (lcap < 0)
-    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_mmi_workspace_bytes(%d, %d, %d, %d, 0) = %zu", fn, workspace_bytes, T, S,
-                K, lm_states, ctc_mmi_workspace_bytes(T, S, K, lm_states, 0));
-  HIPCHK(launch_ctc_mmi(net_out, T, S, K, stride, lens_dev, labels_dev, label_offsets_dev, blank, graph, lm_states, ctc_weight, diff,
-                        diff_stride, loss_dev, num_logp_dev, den_logz_dev, lm_logw_dev, totals_dev, workspace, lcap, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-size_t klstm_ctc_align_workspace_bytes(int T, int S, int max_label_len) {
-  return ctc_query_ok("klstm_ctc_align_workspace_bytes", "label", T, S, max_label_len) ? ctc_align_workspace_bytes(T, S, max_label_len) : 0;
-}
-klstm_status klstm_ctc_align(const float *net_out, int T, int S, int K, int stride, const int *lens_dev, const int *labels_dev,
-                             const int *label_offsets_dev, int blank, const float *class_weight_dev, int *frame_class_dev,
-                             int *frame_pos_dev, int *token_begin_dev, int *token_end_dev, float *score_dev, double *totals_dev,
-                             void *workspace, size_t workspace_bytes, void *hip_stream) {
-  const char *fn = "klstm_ctc_align";
-  const char *pointers = (token_begin_dev == nullptr) != (token_end_dev == nullptr) ? "token begins and ends come together or not at all" : nullptr;
-  if (!net_out || !lens_dev || !labels_dev || !label_offsets_dev || !frame_class_dev || !workspace) pointers = "null argument";
-  const klstm_status st = ctc_call_check(fn, T, S, K, 2, pointers, blank, stride, nullptr, workspace);
-  if (st != KLSTM_OK) return st;
-  const int lcap = ctc_align_label_capacity(T, S, workspace_bytes);
-  if (lcap < 0)
-    return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes is below klstm_ctc_align_workspace_bytes(%d, %d, 0) = %zu", fn, workspace_bytes, T, S,
-                ctc_align_workspace_bytes(T, S, 0));
-  HIPCHK(launch_ctc_align(net_out, T, S, K, stride, lens_dev, labels_dev, label_offsets_dev, blank, class_weight_dev, frame_class_dev,
-                          frame_pos_dev, token_begin_dev, token_end_dev, score_dev, totals_dev, workspace, lcap, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-klstm_status klstm_log_softmax_scatter(const float *in, int rows, int cols, int in_stride, const int *dst_row_dev, float *out,
-                                       int out_stride, int mode, const float *log_prior_dev, float prior_scale, void *hip_stream) {
-  if ((!in || !dst_row_dev || !out) && rows > 0) return fail(KLSTM_ERR_ARG, "klstm_log_softmax_scatter: null argument");
-  if (rows < 0 || cols <= 0 || in_stride < cols || out_stride < cols) return fail(KLSTM_ERR_ARG, "klstm_log_softmax_scatter: bad size");
-  if (mode != KLSTM_SCORE_POSTERIOR && mode != KLSTM_SCORE_LOGPOST && mode != KLSTM_SCORE_LOGLIKE)
-    return fail(KLSTM_ERR_ARG, "klstm_log_softmax_scatter: unknown mode %d", mode);
-  if (mode == KLSTM_SCORE_LOGLIKE && !log_prior_dev) return fail(KLSTM_ERR_ARG, "klstm_log_softmax_scatter: log-likelihoods need log_prior");
-  if (rows == 0) return KLSTM_OK;
-  HIPCHK(launch_log_softmax_scatter(in, rows, cols, in_stride, dst_row_dev, out, out_stride, mode, log_prior_dev, prior_scale,
-                                    (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-klstm_status klstm_sgd_momentum_update(float *param, float *corr, const float *grad, long n, float momentum, float lr,
-                                       void *hip_stream) {
-  if (!param || !corr || !grad || n < 0) return fail(KLSTM_ERR_ARG, "klstm_sgd_momentum_update: bad argument");
-  if (n == 0) return KLSTM_OK;
-  hipStream_t st = (hipStream_t)hip_stream;
-  HIPCHK(launch_sgd_momentum(param, corr, grad, momentum, lr, n, st));
-  return KLSTM_OK;
-}
-klstm_status klstm_softmax(const float *in, int rows, int cols, int in_stride, float *out, int out_stride, void *hip_stream) {
-  if (!in || !out) return fail(KLSTM_ERR_ARG, "klstm_softmax: null argument");
-  if (rows > 0) HIPCHK(launch_softmax(in, rows, cols, in_stride, out, out_stride, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-klstm_status klstm_xent_eval_masked(const float *net_out, int rows, int cols, int stride, const int *targets_dev,
-                                    const float *mask_dev, float *diff, int diff_stride, float *row_xent_dev,
-                                    float *row_correct_dev, void *hip_stream) {
-  if (!net_out || !targets_dev || !mask_dev || !diff || !row_xent_dev || !row_correct_dev)
-    return fail(KLSTM_ERR_ARG, "klstm_xent_eval_masked: null argument");
-  if (rows > 0) HIPCHK(launch_xent(net_out, rows, cols, stride, targets_dev, mask_dev, diff, diff_stride, row_xent_dev,
-                                   row_correct_dev, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-
-// ticket word of the one-pass loss kernel (which workgroup is the last of a launch): one per (device, stream), zero between launches
-static klstm_status loss_ticket(hipStream_t st, unsigned **ticket) {
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, unsigned *> pool;
-  int devid = 0;
-  HIPCHK(hipGetDevice(&devid));
-  std::lock_guard<std::mutex> lk(mu);
-  unsigned *&slot = pool[std::make_pair(devid, st)];
-  if (!slot) {
-    HIPCHK(hipMalloc(&slot, sizeof(unsigned)));
-    HIPCHK(hipMemset(slot, 0, sizeof(unsigned)));       // (synchronous with respect to the host: done before any launch uses it)
-  }
-  *ticket = slot;
-  return KLSTM_OK;
-}
-klstm_status klstm_softmax_xent_masked(const float *net_in, int rows, int cols, int in_stride, float *post, int post_stride,
-                                       const int *targets_dev, const float *mask_dev, float *diff, int diff_stride, float *row_xent_dev,
-                                       float *row_correct_dev, double *totals_dev, void *hip_stream) {
-  if (!net_in || !targets_dev || !mask_dev || !diff || !row_xent_dev || !row_correct_dev)
-    return fail(KLSTM_ERR_ARG, "klstm_softmax_xent_masked: null argument");
-  if (rows <= 0) return KLSTM_OK;
-  hipStream_t st = (hipStream_t)hip_stream;
-  unsigned *ticket = nullptr;
-  if (totals_dev) {
-    const klstm_status s = loss_ticket(st, &ticket);
-    if (s != KLSTM_OK) return s;
-  }
-  const hipError_t e = launch_softmax_xent(net_in, rows, cols, in_stride, post, post_stride, targets_dev, mask_dev, diff, diff_stride,
-                                           row_xent_dev, row_correct_dev, totals_dev, ticket, st);
-  if (e == hipSuccess) return KLSTM_OK;
-  if (e != hipErrorNotSupported) HIPCHK(e);
-  // rows the one-pass kernel does not serve: the two kernels, through the caller's posterior matrix
-  if (!post) return fail(KLSTM_ERR_ARG, "klstm_softmax_xent_masked: this shape needs the posterior matrix (post) as the buffer between its two kernels");
-  HIPCHK(launch_softmax(net_in, rows, cols, in_stride, post, post_stride, st));
-  HIPCHK(launch_xent(post, rows, cols, post_stride, targets_dev, mask_dev, diff, diff_stride, row_xent_dev, row_correct_dev, st));
-  if (totals_dev) HIPCHK(launch_xent_accumulate(row_xent_dev, row_correct_dev, mask_dev, rows, totals_dev, st));
-  return KLSTM_OK;
-}
-
-klstm_status klstm_xent_accumulate(const float *row_xent_dev, const float *row_correct_dev, const float *mask_dev, int rows,
-                                   double *totals_dev, void *hip_stream) {
-  if (!row_xent_dev || !row_correct_dev || !mask_dev || !totals_dev || rows < 0) return fail(KLSTM_ERR_ARG, "klstm_xent_accumulate: bad argument");
-  if (rows > 0) HIPCHK(launch_xent_accumulate(row_xent_dev, row_correct_dev, mask_dev, rows, totals_dev, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-
-klstm_status klstm_xent_eval_masked_post(const float *net_out, int rows, int cols, int stride, const int *post_offsets_dev,
-                                         const int *post_pdf_dev, const float *post_weight_dev, const float *mask_dev, float *diff,
-                                         int diff_stride, float *row_xent_dev, float *row_entropy_dev, float *row_correct_dev,
-                                         void *hip_stream) {
-  if (!net_out || !post_offsets_dev || !mask_dev || !diff || !row_xent_dev || !row_entropy_dev || !row_correct_dev)
-    return fail(KLSTM_ERR_ARG, "klstm_xent_eval_masked_post: null argument");
-  if (rows > 0) HIPCHK(launch_xent_post(net_out, rows, cols, stride, post_offsets_dev, post_pdf_dev, post_weight_dev, mask_dev, diff,
-                                        diff_stride, row_xent_dev, row_entropy_dev, row_correct_dev, (hipStream_t)hip_stream));
-  return KLSTM_OK;
-}
-
-// ---- RCCL (data-parallel training over utterance streams: ONE sum-all-reduce of the gradient blob per minibatch) ----
-// libklstm.so has no link-time dependency on RCCL: the entry points are looked up in the process when the first DP call
-// arrives -- first among the symbols already loaded (a host framework may have brought its own librccl, e.g. PyTorch's
-// bundled one; two copies of RCCL in one process must not be mixed), then by dlopen("librccl.so.1").
-}  // extern "C"
-namespace {
-struct RcclApi {
-  ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*CommCount)(const ncclComm_t, int *) = nullptr;
-  ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  const char *(*GetErrorString)(ncclResult_t) = nullptr;
-  bool ok = false;
-  std::string why;
-};
-RcclApi &rccl() {
-  static RcclApi api;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    void *h = nullptr;
-    auto sym = [&](const char *name) -> void * {
-      void *p = dlsym(RTLD_DEFAULT, name);
-      if (!p) {
-        if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-        if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-        if (h) p = dlsym(h, name);
-      }
-      return p;
-    };
-    api.GetUniqueId = reinterpret_cast<decltype(api.GetUniqueId)>(sym("ncclGetUniqueId"));
-    api.CommInitRank = reinterpret_cast<decltype(api.CommInitRank)>(sym("ncclCommInitRank"));
-    api.CommDestroy = reinterpret_cast<decltype(api.CommDestroy)>(sym("ncclCommDestroy"));
-    api.CommCount = reinterpret_cast<decltype(api.CommCount)>(sym("ncclCommCount"));
-    api.AllReduce = reinterpret_cast<decltype(api.AllReduce)>(sym("ncclAllReduce"));
-    api.GetErrorString = reinterpret_cast<decltype(api.GetErrorString)>(sym("ncclGetErrorString"));
-    api.ok = api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.AllReduce;
-    if (!api.ok) api.why = std::string("RCCL entry points not found (") + (dlerror() ? dlerror() : "librccl.so.1 not loadable") + ")";
-  });
-  return api;
-}
-klstm_status rccl_fail(const char *what, ncclResult_t r) {
-  RcclApi &a = rccl();
-  return fail(KLSTM_ERR_HIP, "%s failed: %s", what, a.GetErrorString ? a.GetErrorString(r) : "RCCL error");
-}
-}  // namespace
-extern "C" {
-
-klstm_status klstm_comm_get_unique_id(void *id128) {
-  if (!id128) return fail(KLSTM_ERR_ARG, "klstm_comm_get_unique_id: null argument");
-  RcclApi &a = rccl();
-  if (!a.ok) return fail(KLSTM_ERR_HIP, "%s", a.why.c_str());
-  ncclUniqueId id;
-  const ncclResult_t r = a.GetUniqueId(&id);
-  if (r != ncclSuccess) return rccl_fail("ncclGetUniqueId", r);
-  static_assert(sizeof(id) == KLSTM_COMM_ID_BYTES, "ncclUniqueId size");
-  memcpy(id128, &id, sizeof(id));
-  return KLSTM_OK;
-}
-klstm_status klstm_comm_init_rank(int device, int nranks, int rank, const void *id128, void **comm) {
-  if (!id128 || !comm || nranks <= 0 || rank < 0 || rank >= nranks) return fail(KLSTM_ERR_ARG, "klstm_comm_init_rank: bad argument");
-  RcclApi &a = rccl();
-  if (!a.ok) return fail(KLSTM_ERR_HIP, "%s", a.why.c_str());
-  HIPCHK(hipSetDevice(device));
-  ncclUniqueId id;
-  memcpy(&id, id128, sizeof(id));
-  ncclComm_t c = nullptr;
-  const ncclResult_t r = a.CommInitRank(&c, nranks, id, rank);
-  if (r != ncclSuccess) return rccl_fail("ncclCommInitRank", r);
-  *comm = c;
-  return KLSTM_OK;
-}
-klstm_status klstm_comm_destroy(void *comm) {
-  if (!comm) return KLSTM_OK;
-  RcclApi &a = rccl();
-  if (!a.ok) return fail(KLSTM_ERR_HIP, "%s", a.why.c_str());
-  const ncclResult_t r = a.CommDestroy(static_cast<ncclComm_t>(comm));
-  return r == ncclSuccess ? KLSTM_OK : rccl_fail("ncclCommDestroy", r);
-}
-klstm_status klstm_comm_count(void *comm, int *nranks) {
-  if (!comm || !nranks) return fail(KLSTM_ERR_ARG, "klstm_comm_count: null argument");
-  RcclApi &a = rccl();
-  if (!a.ok || !a.CommCount) return fail(KLSTM_ERR_HIP, "%s", a.ok ? "ncclCommCount not found" : a.why.c_str());
-  const ncclResult_t r = a.CommCount(static_cast<ncclComm_t>(comm), nranks);
-  return r == ncclSuccess ? KLSTM_OK : rccl_fail("ncclCommCount", r);
-}
-klstm_status klstm_allreduce_buffer(float *buf_dev, size_t n, void *rccl_comm, void *hip_stream) {
-  if (!buf_dev || !rccl_comm) return fail(KLSTM_ERR_ARG, "klstm_allreduce_buffer: null argument");
-  if (n == 0) return KLSTM_OK;
-  RcclApi &a = rccl();
-  if (!a.ok) return fail(KLSTM_ERR_HIP, "%s", a.why.c_str());
-  const ncclResult_t r = a.AllReduce(buf_dev, buf_dev, n, ncclFloat32, ncclSum, static_cast<ncclComm_t>(rccl_comm),
-                                     static_cast<hipStream_t>(hip_stream));
-  return r == ncclSuccess ? KLSTM_OK : rccl_fail("ncclAllReduce", r);
-}
 klstm_status klstm_allreduce_grads(klstm_engine *e, void *rccl_comm) {
   if (!e) return fail(KLSTM_ERR_ARG, "null engine");
   HIPCHK(hipSetDevice(e->device));
@@ -2904,81 +1867,3 @@ klstm_status klstm_allreduce_grads_oneshot(klstm_engine *e, klstm_oneshot *group
 }
 
 }  // extern "C"
-
-// ---- test support: hold compute units busy (uneven-load tests of the persistent chain) ----
-namespace {
-__global__ __launch_bounds__(1024) void k_occupy(long long ticks, unsigned *where) {
-  extern __shared__ float hog[];                   // 96 KB: nothing else fits next to this workgroup
-  hog[threadIdx.x] = (float)threadIdx.x;
-  if (where && threadIdx.x == 0) {                   // which XCD / SE / CU this workgroup landed on (HW_REG_XCC_ID = 20, HW_REG_HW_ID = 4)
-    unsigned xcc, hwid;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    where[2 * blockIdx.x] = xcc; where[2 * blockIdx.x + 1] = hwid;
-  }
-  const long long t0 = wall_clock64();
-  while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
-  if (hog[threadIdx.x] < 0.f && where) where[0] = 1u;
-}
-}  // namespace
-
-extern "C" klstm_status klstm_debug_occupy(int device, int workgroups, int microseconds, void *hip_stream, unsigned *where_dev) {
-  if (workgroups <= 0 || microseconds <= 0) return fail(KLSTM_ERR_ARG, "klstm_debug_occupy: bad arguments");
-  HIPCHK(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (!st) {                                         // a stream of its own per device (streams belong to the device they were made on)
-    static std::mutex mu;
-    static std::map<int, hipStream_t> own;
-    std::lock_guard<std::mutex> lk(mu);
-    hipStream_t &o = own[device];
-    if (!o) HIPCHK(hipStreamCreateWithFlags(&o, hipStreamNonBlocking));
-    st = o;
-  }
-  HIPCHK(launch(k_occupy, dim3(workgroups), dim3(1024), 96 * 1024, st, LaunchProbe{}, (long long)microseconds * 100, where_dev));
-  return KLSTM_OK;
-}
-
-// Test / probe support for klstm_gemm16.hip (tools/gemm16_probe.py, tests/test_gemm16_gpu.py): C = A B^T (+ bias) (+ add) for one or
-// two products that share their K, bf16-rounded operands, fp32 accumulate, on hip_stream (NULL: the default stream).
-//   mnk: 3 ints per job; ptrs: A, B, C, bias, add per job (device pointers, bias / add may be null); lds: lda, ldb, ldc, add_ld per job
-//   force_nj / force_ks: 0 = the launcher's plan; plan_out (or null): nj, ks, output tiles of the plan that ran
-extern "C" klstm_status klstm_debug_gemm_bf16_nt2(int njobs, const int *mnk, const float *const *ptrs, const int *lds, int force_nj, int force_ks,
-                                                  void *hip_stream, int *plan_out) {
-  return klstm_debug_gemm_bf16_nt2h(njobs, mnk, ptrs, lds, nullptr, force_nj, force_ks, hip_stream, plan_out);
-}
-extern "C" klstm_status klstm_debug_gemm_bf16_nt2h(int njobs, const int *mnk, const float *const *ptrs, const int *lds,
-                                                   const unsigned short *const *copies, int force_nj, int force_ks, void *hip_stream, int *plan_out) {
-  if (njobs == 0) { gemm_bf16_nt2_debug_buffer(reinterpret_cast<long long *>(const_cast<int *>(mnk))); return KLSTM_OK; }   // (probe: timing buffer on / off)
-  if (njobs < 1 || njobs > 2 || !mnk || !ptrs || !lds) return fail(KLSTM_ERR_ARG, "klstm_debug_gemm_bf16_nt2: bad arguments");
-  Nt2Job jobs[2];
-  for (int q = 0; q < njobs; q++) {
-    jobs[q] = Nt2Job{mnk[3 * q], mnk[3 * q + 1], mnk[3 * q + 2], ptrs[5 * q], lds[4 * q], ptrs[5 * q + 1], lds[4 * q + 1],
-                     const_cast<float *>(ptrs[5 * q + 2]), lds[4 * q + 2], ptrs[5 * q + 3], ptrs[5 * q + 4], lds[4 * q + 3]};
-    if (!gemm_bf16_nt2_supported(jobs[q])) return fail(KLSTM_ERR_SHAPE, "klstm_debug_gemm_bf16_nt2: job %d not supported by the kernel", q);
-    if (copies) {
-      jobs[q].Ah = copies[2 * q]; jobs[q].Bh = copies[2 * q + 1];
-      if ((jobs[q].Ah || jobs[q].Bh) && !gemm_bf16_nt2_copies_usable(jobs[q]))
-        return fail(KLSTM_ERR_SHAPE, "klstm_debug_gemm_bf16_nt2h: job %d: both bf16 copies, 16-byte aligned, leading dimensions %% 8 == 0", q);
-    }
-  }
-  const Nt2Plan pl = gemm_bf16_nt2_plan(jobs, njobs, force_nj, force_ks);
-  static std::mutex mu;
-  static float *ws = nullptr; static size_t ws_floats = 0; static unsigned *tickets = nullptr;
-  std::lock_guard<std::mutex> lk(mu);
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (pl.ws_floats > ws_floats) {
-    HIPCHK(hipDeviceSynchronize());
-    if (ws) (void)hipFree(ws);
-    ws = nullptr; ws_floats = 0;
-    HIPCHK(hipMalloc(&ws, pl.ws_floats * sizeof(float)));
-    ws_floats = pl.ws_floats;
-  }
-  if (!tickets) {
-    HIPCHK(hipMalloc(&tickets, NT2_TICKETS * sizeof(unsigned)));
-    HIPCHK(hipMemset(tickets, 0, NT2_TICKETS * sizeof(unsigned)));
-  }
-  if (pl.nt > NT2_TICKETS) return fail(KLSTM_ERR_SHAPE, "klstm_debug_gemm_bf16_nt2: %d output tiles", pl.nt);
-  HIPCHK(launch_gemm_bf16_nt2(jobs, njobs, pl, ws, ws_floats, tickets, NT2_TICKETS, st));
-  if (plan_out) { plan_out[0] = pl.nj; plan_out[1] = pl.ks; plan_out[2] = pl.nt; }
-  return KLSTM_OK;
-}

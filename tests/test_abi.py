@@ -2,9 +2,12 @@
 include/klstm.h declares, and refuses (loudly) to create an engine when no device exists."""
 import os
 import re
+import subprocess
 
 import pytest
 import torch
+
+from tests import cpp_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,6 +26,24 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), f"libklstm.so does not export {n}"
     assert b"gfx950" in lib.klstm_version()
+
+
+def test_exported_names_are_the_recorded_list():
+    """the klstm_* names the library defines are those of tests/golden/klstm_abi_names.txt: whichever translation unit an entry lives in"""
+    import kaldi_lstm_amd as k
+    out = subprocess.run(["nm", "-D", "--defined-only", k.lib_path()], capture_output=True, text=True, check=True).stdout
+    have = sorted({ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("klstm_")})
+    want = open(os.path.join(ROOT, "tests", "golden", "klstm_abi_names.txt")).read().split()
+    assert len(want) == 100 and want == sorted(want)
+    assert have == want, f"lost {sorted(set(want) - set(have))}, added {sorted(set(have) - set(want))}"
+
+
+def test_one_error_string_behind_the_entries_of_three_translation_units():
+    """tests/cpp/error_channel_test.cpp: an entry of klstm_engine.hip, one of klstm_api_ctc.hip and one of klstm_api_ops.hip fail their
+    argument checks (before any HIP call: no GPU needed) and klstm_last_error() reads each message; a second thread reads an empty string
+    meanwhile: the string is one thread_local of the library, not one per translation unit"""
+    cpp_driver.build("error_channel_test", headers=("klstm.h",), flags=("-O1", "-pthread"))
+    cpp_driver.run("error_channel_test", headers=("klstm.h",))
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
