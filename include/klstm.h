@@ -717,7 +717,8 @@ klstm_status klstm_ctc_consensus(const int *hyp_dev, int hyp_stride, const int *
  * them KLSTM_ERR_SHAPE and nothing is launched (klstm_ctc_rescore_workspace_bytes answers 0 and leaves the message in
  * klstm_last_error(); neither touches a device then).  A null required pointer, a small or misaligned workspace, a non-finite scale,
  * neither model given, word arguments without `add`, a separator outside [0, K), an unk_id or add_reserved that is no class of the word
- * model, a model that was not built at its address or for other sizes: KLSTM_ERR_ARG with the outputs untouched. */
+ * model, a model that was not built at its address or for other sizes: KLSTM_ERR_ARG with the outputs untouched.
+ * The same lists rescored with an LSTM language model: the entries of klstm_nlm.h, a family of their own in this library. */
 size_t klstm_ctc_rescore_workspace_bytes(int S, int list_n, int max_len, int word_mode);
 klstm_status klstm_ctc_nbest_rescore(const int *hyp_dev, int hyp_stride, const int *hyp_len_dev, const int *nbest_count_dev, const float *logp_dev,
                                      const int *errors_dev, int S, int list_n, int max_len, int K, const void *sub_slm, size_t sub_bytes,

@@ -18,6 +18,7 @@
 #include <string>
 
 #include "klstm_component.hpp"
+#include "klstm_nlm.h"
 #include "klstm_trainer.hpp"
 
 namespace klstm_kaldi {
@@ -1474,6 +1475,210 @@ class CtcRescorer : private CtcCallBase {
   DeviceTotals<8> tot_;
 };
 
+// Rescoring of the same lists with an LSTM language model (the knlm_* entries, klstm_nlm.h, which defines every quantity; INTEGRATION.md
+// 3o).  The LM is an Nnet over V >= K classes, of which 0 .. num_classes - 1 are the CTC model's tokens:
+//   [<AffineTransform> D x V]  <LstmProjectedStreams | LstmProjected>...  <AffineTransform> V x R  [<Softmax>]
+// the leading Affine an embedding (gathered, never multiplied), a Softmax folded into the scoring.  The model is only read: the rescorer
+// builds engines of its own with NumStream = num_stream from the model's current parameters, as BatchScorer does.
+struct CtcNeuralRescorerOptions {
+  int32 num_stream = 16, chunk = 20;     // E entries are scored at a time, in chunks of T positions
+  int32 num_classes = 0;                 // the token classes K; 0: all V classes of the LM
+  int32 bos = 0, eos = 0;                // classes of the LM; eos < 0: no end term.  bos = eos = blank with V = K is the economical choice
+  BaseFloat am_scale = 1.f, nlm_scale = 1.f, unit_bonus = 0.f;
+  int32 out_n = 0;                       // entries the re-ranked list keeps; 0: all
+  int32 max_len = 0;                     // the token capacity the plan is laid out for; 0: min(1023, the lists' stride)
+  int device = 0;
+};
+class CtcNeuralRescorer {
+ public:
+  CtcNeuralRescorer(const Nnet &lm, const CtcNeuralRescorerOptions &o) : o_(o) {
+    int32 i0 = 0, i1 = 0;
+    CheckTopology(lm, o, &i0, &i1);                   // (before anything touches a device: a refused model needs no GPU)
+    const AffineLayer &aff = static_cast<const AffineLayer &>(lm.GetComponent(i1));
+    V_ = aff.OutputDim(); aff_in_ = aff.InputDim();
+    K_ = o.num_classes > 0 ? o.num_classes : V_;
+    cols_ = lm.GetComponent(i0).InputDim();
+    for (int32 i = i0; i < i1; i++) {
+      const LstmProjectedStreams *c = static_cast<const LstmLayer &>(lm.GetComponent(i)).Impl();
+      std::vector<BaseFloat> p;
+      c->GetParams(&p);
+      klstm_engine *e = nullptr;
+      KCheck(klstm_create(c->InputDim(), c->CellDim(), c->OutputDim(), o.num_stream, o.device, nullptr, &e));
+      engines_.emplace_back(e);
+      KCheck(klstm_set_params_host(e, p.data()));
+      KCheck(klstm_set_option(e, "persist_verify", 1));   // a persistent launch that gives up is run again inside its call: the buffers are reused
+      dims_.push_back(c->OutputDim());
+    }
+    std::vector<BaseFloat> w, b;
+    aff.HostParams(&w, &b);
+    W_.Upload(w); b_.Upload(b);
+    if (i0 == 1) {
+      static_cast<const AffineLayer &>(lm.GetComponent(0)).HostParams(&w, &b);
+      We_.Upload(w); be_.Upload(b);
+    }
+    embed_ = i0 == 1;
+    const size_t rows = (size_t)o.num_stream * o.chunk;       // tight rows, as kaldi_lstm_amd.nlm lays them out: the same kernels, the same bits
+    x_.Grow(rows * cols_ * sizeof(BaseFloat));
+    for (int32 d : dims_) { h_.emplace_back(); h_.back().Grow(rows * d * sizeof(BaseFloat)); }
+    a_.Grow(rows * V_ * sizeof(BaseFloat));
+    ws_bytes_ = knlm_workspace_bytes(o.num_stream, o.chunk);
+    if (!ws_bytes_) KLSTM_ERR("klstm: " << klstm_last_error());
+    ws_.Grow(ws_bytes_);
+  }
+  // The checks of the constructor, host only; [*lstm_begin, *lstm_end) are the LSTM components, *lstm_end the last <AffineTransform>,
+  // *lstm_begin == 1 with an embedding.  Raises (KLSTM_ERR) on a topology or an option the rescorer does not take.
+  static void CheckTopology(const Nnet &lm, const CtcNeuralRescorerOptions &o, int32 *lstm_begin = nullptr, int32 *lstm_end = nullptr) {
+    if (o.num_stream < 1 || o.num_stream > 32 || o.chunk < 1) KLSTM_ERR("CtcNeuralRescorer: num_stream must be 1..32 and chunk >= 1");
+    const int32 n = lm.NumComponents();
+    auto marker = [&](int32 i) { return i < n ? std::string(lm.GetComponent(i).Marker()) : std::string("(end of the model)"); };
+    int32 i = marker(0) == "<AffineTransform>" ? 1 : 0;
+    const int32 b = i;
+    while (marker(i) == "<LstmProjectedStreams>" || marker(i) == "<LstmProjected>") i++;
+    if (i == b) KLSTM_ERR("CtcNeuralRescorer: " << marker(i) << " at component " << i << " where an <LstmProjectedStreams> / <LstmProjected> belongs");
+    if (marker(i) != "<AffineTransform>") KLSTM_ERR("CtcNeuralRescorer: " << marker(i) << " at component " << i << " where the <AffineTransform> belongs");
+    const int32 e = i++;
+    if (marker(i) == "<Softmax>") i++;
+    if (i != n) KLSTM_ERR("CtcNeuralRescorer: " << marker(i) << " at component " << i << " is not supported (accepted: "
+                          "[<AffineTransform>] <LstmProjected[Streams]>... <AffineTransform> [<Softmax>])");
+    const int32 V = lm.GetComponent(e).OutputDim(), K = o.num_classes > 0 ? o.num_classes : V;
+    if (lm.GetComponent(0).InputDim() != V) KLSTM_ERR("CtcNeuralRescorer: the model reads " << lm.GetComponent(0).InputDim() << " classes and writes " << V);
+    if (K < 2 || K > V || V > 32768 || o.bos < 0 || o.bos >= V || o.eos >= V)
+      KLSTM_ERR("CtcNeuralRescorer: " << K << " token classes, bos " << o.bos << ", eos " << o.eos << " with " << V << " classes");
+    if (!std::isfinite(o.am_scale) || !std::isfinite(o.nlm_scale) || !std::isfinite(o.unit_bonus)) KLSTM_ERR("CtcNeuralRescorer: the scales must be finite");
+    if (lstm_begin) *lstm_begin = b;
+    if (lstm_end) *lstm_end = e;
+  }
+  CtcNeuralRescorer(const CtcNeuralRescorer &) = delete;
+  CtcNeuralRescorer &operator=(const CtcNeuralRescorer &) = delete;
+
+  // over the lists of the last lists.Decode, or any lists in that layout (CtcRescorer::DeviceLists()).  Nothing synchronises.
+  void Rescore(const CtcBeamDecoder &lists) { Rescore(lists.DeviceLists()); }
+  void Rescore(const CtcNbestDevice &nb) {
+    const int32 S = nb.num_stream, N = nb.nbest, E = o_.num_stream, T = o_.chunk, rows = E * T;
+    KLSTM_ASSERT(S > 0 && N > 0 && nb.stride > 0 && nb.score);
+    const int32 max_len = CtcNbestMaxLen(o_.max_len, nb.stride), out_n = o_.out_n > 0 ? std::min(o_.out_n, N) : N;
+    const size_t SN = (size_t)S * N;
+    acc_.Grow(SN * sizeof(double)); pos_.Grow(SN * sizeof(int32));       // (set by every group's first chunk: max_len >= 1, so there is one)
+    order_.Grow(SN * sizeof(int32)); live_.Grow((size_t)S * sizeof(int32)); score_.Grow(SN * sizeof(BaseFloat));
+    nlmlp_.Grow(SN * sizeof(BaseFloat)); units_.Grow(SN * sizeof(int32));
+    ohyp_.Grow(SN * nb.stride * sizeof(int32)); olen_.Grow(SN * sizeof(int32)); ocnt_.Grow((size_t)S * sizeof(int32));
+    oscore_.Grow(SN * sizeof(BaseFloat)); oerr_.Grow(SN * sizeof(int32));
+    const int32 chunks = (max_len + (o_.eos >= 0 ? 1 : 0) + T - 1) / T;
+    std::vector<int> flags(E, 1);
+    for (int32 first = 0; first < S * N; first += E) {
+      for (auto &eng : engines_) KCheck(klstm_reset(eng.get(), flags.data(), E));       // every group starts from zero state
+      for (int32 c = 0; c < chunks; c++) {
+        KCheck(knlm_pack(nb.hyp, nb.stride, nb.hyp_len, nb.count, nb.score, S, N, max_len, K_, V_, o_.bos, o_.eos, first, E, T, c * T,
+                         embed_ ? We_.As<BaseFloat>() : nullptr, embed_ ? be_.As<BaseFloat>() : nullptr, embed_ ? cols_ : 0, x_.As<BaseFloat>(), cols_,
+                         nullptr));
+        const BaseFloat *in = x_.As<BaseFloat>();
+        int32 in_stride = cols_;
+        for (size_t l = 0; l < engines_.size(); l++) {
+          KCheck(klstm_propagate_inference(engines_[l].get(), in, rows, in_stride, h_[l].As<BaseFloat>(), dims_[l]));
+          in = h_[l].As<BaseFloat>();
+          in_stride = dims_[l];
+        }
+        KCheck(klstm_affine_propagate(in, rows, aff_in_, in_stride, W_.As<BaseFloat>(), b_.As<BaseFloat>(), a_.As<BaseFloat>(), V_, V_, nullptr));
+        KCheck(knlm_score_rows(a_.As<BaseFloat>(), V_, nb.hyp, nb.stride, nb.hyp_len, nb.count, nb.score, S, N, max_len, K_, V_, o_.eos, first, E, T,
+                               c * T, acc_.As<double>(), pos_.As<int32>(), ws_.As<void>(), ws_bytes_, nullptr));
+      }
+    }
+    KCheck(knlm_rank(nb.hyp, nb.stride, nb.hyp_len, nb.count, nb.score, nb.errors, S, N, max_len, K_, acc_.As<double>(), o_.am_scale, o_.nlm_scale,
+                     o_.unit_bonus, o_.eos >= 0 ? 1 : 0, order_.As<int32>(), live_.As<int32>(), score_.As<BaseFloat>(), nlmlp_.As<BaseFloat>(),
+                     units_.As<int32>(), out_n, ohyp_.As<int32>(), nb.stride, olen_.As<int32>(), ocnt_.As<int32>(), oscore_.As<BaseFloat>(),
+                     nb.errors ? oerr_.As<int32>() : nullptr, tot_.Dev(), nullptr));
+    num_stream_ = S; nbest_ = N; out_nbest_ = out_n; stride_ = nb.stride; scored_ = nb.errors != nullptr;
+  }
+  // the re-ranked lists of the last Rescore on the device, in the layout of CtcBeamDecoder::DeviceLists() (CtcConsensus::Eval and CtcMbr
+  // take them); slots beyond a stream's count hold nothing
+  CtcNbestDevice DeviceLists() const {
+    return CtcNbestDevice{ohyp_.As<int32>(), olen_.As<int32>(), ocnt_.As<int32>(), scored_ ? oerr_.As<int32>() : nullptr, num_stream_, out_nbest_, stride_,
+                          oscore_.As<BaseFloat>()};
+  }
+  // of the last Rescore (each synchronises): the re-ranked list of every stream, best first, with the new scores
+  void Lists(std::vector<CtcNbestList> *lists) const {
+    const size_t SN = (size_t)num_stream_ * out_nbest_;
+    std::vector<int32> c(num_stream_), n(SN), h(SN * stride_), e(SN, -1);
+    std::vector<BaseFloat> sc(SN);
+    ocnt_.Download(c.data(), c.size()); olen_.Download(n.data(), n.size()); ohyp_.Download(h.data(), h.size());
+    oscore_.Download(sc.data(), sc.size());
+    if (scored_) oerr_.Download(e.data(), e.size());
+    lists->assign(num_stream_, CtcNbestList());
+    for (int32 s = 0; s < num_stream_; s++)
+      for (int32 q = 0; q < c[s]; q++) {
+        const size_t o = (size_t)s * out_nbest_ + q;
+        CtcHypothesis hy;
+        hy.tokens.assign(h.begin() + o * stride_, h.begin() + o * stride_ + n[o]);
+        hy.score = sc[o];
+        hy.errors = e[o];
+        (*lists)[s].push_back(hy);
+      }
+  }
+  // ... the entry of the given list at every rank [num_stream][nbest] (-1 beyond the entries ranked) and how many were ranked
+  void Order(std::vector<int32> *order, std::vector<int32> *live = nullptr) const {
+    order->assign((size_t)num_stream_ * nbest_, -1);
+    order_.Download(order->data(), order->size());
+    if (live) { live->assign(num_stream_, 0); live_.Download(live->data(), live->size()); }
+  }
+  // ... per entry of the given list [num_stream][nbest]: the new score and the LM's log probability (-inf: dropped, forbidden or
+  // unlisted), the units (any may be null)
+  void Entries(std::vector<BaseFloat> *score, std::vector<BaseFloat> *nlm_logp = nullptr, std::vector<int32> *units = nullptr) const {
+    const size_t SN = (size_t)num_stream_ * nbest_;
+    if (score) { score->assign(SN, 0.f); score_.Download(score->data(), SN); }
+    if (nlm_logp) { nlm_logp->assign(SN, 0.f); nlmlp_.Download(nlm_logp->data(), SN); }
+    if (units) { units->assign(SN, 0); units_.Download(units->data(), SN); }
+  }
+  // over the streams rescored so far
+  double NumUtterances() const { return tot_.Read()[0]; }
+  double NumChanged() const { return tot_.Read()[4]; }                 // streams whose 1-best is no longer the given list's
+  double NumFirstPassErrors() const { return tot_.Read()[5]; }         // edit errors of the given list's 1-best (lists decoded with references)
+  double NumRescoredErrors() const { return tot_.Read()[6]; }          // ... of the new 1-best
+  double NumDropped() const { return tot_.Read()[2]; }
+  double NumForbidden() const { return tot_.Read()[3]; }
+  double NumPositions() const { return tot_.Read()[7]; }
+  std::string Report() const {
+    const double *h = tot_.Read();
+    std::ostringstream oss;
+    oss << "NEURAL RESCORED: " << h[4] << " of " << h[0] << " 1-bests changed, errors " << h[5] << " -> " << h[6] << " [" << h[1]
+        << " idle or rejected, " << h[2] << " entries dropped, " << h[3] << " forbidden, " << h[7] << " positions scored]" << std::endl;
+    return oss.str();
+  }
+ private:
+  struct EngineDel { void operator()(klstm_engine *e) const { klstm_destroy(e); } };
+  CtcNeuralRescorerOptions o_;
+  std::vector<std::unique_ptr<klstm_engine, EngineDel> > engines_;
+  std::vector<int32> dims_;
+  int32 V_ = 0, K_ = 0, cols_ = 0, aff_in_ = 0, num_stream_ = 0, nbest_ = 0, out_nbest_ = 0, stride_ = 0;
+  bool embed_ = false, scored_ = false;
+  size_t ws_bytes_ = 0;
+  DeviceBuffer W_, b_, We_, be_, x_, a_, ws_, acc_, pos_;
+  std::vector<DeviceBuffer> h_;
+  DeviceBuffer order_, live_, score_, nlmlp_, units_, ohyp_, olen_, ocnt_, oscore_, oerr_;
+  DeviceTotals<8> tot_;
+};
+
+// The training data of such an LM: per token sequence one Utterance of one-hot feature rows [bos, y_0, ...] over V classes with the
+// next-token targets [y_0, ..., eos], which TrainLstmStreams trains on.  eos < 0: no end term (one row fewer; a sequence that leaves no
+// row is skipped).
+inline std::vector<Utterance> LmTrainingUtterances(const std::vector<std::vector<int32> > &sequences, int32 V, int32 bos, int32 eos) {
+  KLSTM_ASSERT(V >= 2 && bos >= 0 && bos < V && eos < V);
+  std::vector<Utterance> out;
+  for (const auto &y : sequences) {
+    for (int32 t : y) KLSTM_ASSERT(t >= 0 && t < V);
+    std::vector<int32> x(1, bos), tgt(y);
+    x.insert(x.end(), y.begin(), y.end());
+    if (eos >= 0) tgt.push_back(eos); else x.pop_back();
+    if (x.empty()) continue;
+    Utterance u;
+    u.num_frames = (int32)x.size(); u.dim = V;
+    u.feats.assign((size_t)u.num_frames * V, 0.f);
+    for (int32 p = 0; p < u.num_frames; p++) u.feats[(size_t)p * V + x[p]] = 1.f;
+    u.targets = tgt;
+    out.push_back(u);
+  }
+  return out;
+}
+
 struct TrainMbrOptions {
   NnetTrainOptions trn_opts;
   int32 num_stream = 4, blank = 0, max_frames = 0;       // max_frames 0: 65535 / num_stream
@@ -1642,6 +1847,8 @@ struct DecodeCtcOptions {
   int32 separator = -1;                                  // -1: errors and confidences per token; otherwise the class that separates words
   CtcRescorer *rescorer = nullptr;                       // beam > 0 only: runs on each minibatch's lists before the consensus step, which then
                                                          // sees the re-ranked lists, as do hypotheses and nbest_lists; not owned; null: none
+  CtcNeuralRescorer *neural_rescorer = nullptr;          // beam > 0 only: an LSTM language model over the lists, behind `rescorer` (whose re-ranked
+                                                         // lists it then reads) and before the consensus step; not owned; null: none
 };
 struct DecodeCtcStats {
   int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
@@ -1653,6 +1860,9 @@ struct DecodeCtcStats {
   // with o.rescorer only, over this pass: the token error rates of the search's 1-bests and of the rescored ones (scored passes) and
   // the utterances whose 1-best changed
   double first_pass_token_error_rate = 0, rescored_token_error_rate = 0, num_changed_1best = 0;
+  // with o.neural_rescorer only, over this pass: the token error rates of the 1-bests it was given and of its own (scored passes) and
+  // the utterances whose 1-best it changed
+  double neural_first_pass_token_error_rate = 0, neural_rescored_token_error_rate = 0, num_neural_changed_1best = 0;
 };
 
 // per-stream results of one minibatch -> per-utterance results in the order of the utterance list (idle streams carry nothing)
@@ -1682,7 +1892,9 @@ inline void FillDecodeCtcStats(const Decoder &dec, DecodeCtcStats *st, std::stri
 // every minibatch: (*hypotheses)[i] is then the entry it answers with (the MAP or the MBR one), (*confidences)[i] (may be null) holds
 // one confidence per token or word of it, and the statistics and the report carry the expected errors.  With o.rescorer the lists of
 // every minibatch are re-ranked first (CtcRescorer::Eval): hypotheses, nbest_lists and the consensus then see the re-ranked lists, and
-// the statistics carry the error rates before and after; null leaves the loop as it was.
+// the statistics carry the error rates before and after; null leaves the loop as it was.  With o.neural_rescorer an LSTM language
+// model re-ranks the lists next (CtcNeuralRescorer::Rescore, over the rescorer's lists where there is one): search -> rescorer ->
+// neural_rescorer -> consensus, each stage reading the previous one's lists; null leaves the loop as it was.
 template <class F>
 inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const DecodeCtcOptions &o,
                                                std::vector<std::vector<int32> > *hypotheses, std::vector<CtcNbestList> *nbest_lists,
@@ -1701,16 +1913,22 @@ inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utt
   if (confidences) confidences->assign(utts.size(), std::vector<BaseFloat>());
   const double resc0[3] = {o.rescorer ? o.rescorer->NumChanged() : 0, o.rescorer ? o.rescorer->NumFirstPassErrors() : 0,
                            o.rescorer ? o.rescorer->NumRescoredErrors() : 0};          // the rescorer may have seen other passes
+  CtcNeuralRescorer *const nr = o.neural_rescorer;
+  const double nresc0[3] = {nr ? nr->NumChanged() : 0, nr ? nr->NumFirstPassErrors() : 0, nr ? nr->NumRescoredErrors() : 0};
   DecodeCtcStats st = ForEachWholeUtteranceBatch<DecodeCtcStats>(nnet, utts, o.num_stream, o.sort_by_length, o.max_frames,
       [&](const UtteranceBatch &b, const DeviceMatrix &nnet_out) {
-        dec.Decode(nnet_out, b.num_stream, b.lens, o.score ? b.labels : none, want && !o.rescorer ? &lists : nullptr);
+        dec.Decode(nnet_out, b.num_stream, b.lens, o.score ? b.labels : none, want && !o.rescorer && !nr ? &lists : nullptr);
         if (o.rescorer) {
           o.rescorer->Eval(dec);
-          if (want) o.rescorer->Lists(&lists);
+          if (want && !nr) o.rescorer->Lists(&lists);
+        }
+        if (nr) {
+          if (o.rescorer) nr->Rescore(o.rescorer->DeviceLists()); else nr->Rescore(dec);
+          if (want) nr->Lists(&lists);
         }
         std::vector<int32> pick(b.num_stream, 0);          // without a consensus: the head of the list
         if (o.consensus) {
-          if (o.rescorer) cons.Eval(o.rescorer->DeviceLists()); else cons.Eval(dec);
+          if (nr) cons.Eval(nr->DeviceLists()); else if (o.rescorer) cons.Eval(o.rescorer->DeviceLists()); else cons.Eval(dec);
           if (hypotheses) cons.Picks(&pick);
           if (confidences) {
             std::vector<std::vector<BaseFloat> > conf;
@@ -1743,6 +1961,14 @@ inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utt
       st.rescored_token_error_rate = (o.rescorer->NumRescoredErrors() - resc0[2]) / st.num_ref_tokens;
     }
     if (report) *report += "\n" + o.rescorer->Report();
+  }
+  if (nr) {
+    st.num_neural_changed_1best = nr->NumChanged() - nresc0[0];
+    if (st.num_ref_tokens > 0) {
+      st.neural_first_pass_token_error_rate = (nr->NumFirstPassErrors() - nresc0[1]) / st.num_ref_tokens;
+      st.neural_rescored_token_error_rate = (nr->NumRescoredErrors() - nresc0[2]) / st.num_ref_tokens;
+    }
+    if (report) *report += "\n" + nr->Report();
   }
   return st;
 }

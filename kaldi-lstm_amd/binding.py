@@ -156,6 +156,12 @@ def load_library():
     lib.klstm_ctc_mmi_workspace_bytes.restype = ctypes.c_size_t
     lib.klstm_ctc_mmi_eval.argtypes = [P, I, I, I, I, P, P, P, I, P, ctypes.c_size_t, I, ctypes.c_float, P, I, P, P, P, P, P, P,
                                        ctypes.c_size_t, P]
+    # the knlm_* family of include/klstm_nlm.h (nlm.py)
+    lib.knlm_pack.argtypes = [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P, I, P, I, P]
+    lib.knlm_workspace_bytes.argtypes = [I, I]
+    lib.knlm_workspace_bytes.restype = ctypes.c_size_t
+    lib.knlm_score_rows.argtypes = [P, I, P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, P, P, P, ctypes.c_size_t, P]
+    lib.knlm_rank.argtypes = [P, I, P, P, P, P, I, I, I, I, P, F, F, F, I, P, P, P, P, P, I, P, I, P, P, P, P, P, P]
     _LIB = lib
     return lib
 

@@ -336,10 +336,13 @@ def ctc_beam_decode(net_out, lens, blank=0, beam=16, cands=8, nbest=1, class_wei
 
 
 def _as_nbest(nbest):
-    """what ctc_nbest_rescore returned stands for its re-ranked list"""
+    """what ctc_nbest_rescore (a dict) or CtcNeuralLm.rescore (nlm.CtcNeuralRescoreResult) returned stands for its re-ranked list"""
     if isinstance(nbest, dict):
         assert nbest.get("nbest") is not None, "the rescoring was asked for no list (out_n = 0)"
         return nbest["nbest"]
+    if hasattr(nbest, "nbest") and hasattr(nbest, "nlm_logp"):
+        assert nbest.nbest is not None, "the rescoring was asked for no list (out_n = 0)"
+        return nbest.nbest
     return nbest
 
 
