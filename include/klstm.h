@@ -300,8 +300,9 @@ klstm_status klstm_xent_accumulate(const float *row_xent_dev, const float *row_c
  * reference's `tgt(t, pdf) += weight`, :86-96).  diff = (net_out - target) * mask; per row: cross entropy -mask*sum t*log(y),
  * target entropy -mask*sum t*log(t + 1e-20), and 1 if mask == 1 and the arg-maxima of net_out and of the target row agree
  * (lowest index on ties, zeros of the dense target row included).  The dense rows x cols target matrix of the reference
- * (5.3 MB per minibatch at 80 x 16624, built on the host and copied) never exists.  pdf range checks are the caller's
- * (the reference raises on the host while it builds the matrix, :89-92). */
+ * (5.3 MB per minibatch at 80 x 16624, built on the host and copied) never exists.  A frame may carry any number of entries:
+ * there is no limit (up to 256 are staged on chip; a longer frame costs more time, not correctness).  pdf range checks are the
+ * caller's (the reference raises on the host while it builds the matrix, :89-92). */
 klstm_status klstm_xent_eval_masked_post(const float *net_out, int rows, int cols, int stride, const int *post_offsets_dev,
                                          const int *post_pdf_dev, const float *post_weight_dev, const float *mask_dev, float *diff,
                                          int diff_stride, float *row_xent_dev, float *row_entropy_dev, float *row_correct_dev,

@@ -2627,7 +2627,10 @@ __global__ void k_time_shift(const float *__restrict__ in, int rows, int cols, i
 // so repeated pdfs add up, :86-96) and then works on dense rows.  Here the dense target never exists: one workgroup per
 // row writes diff = y*mask, then the first occurrence of every pdf fixes its column to (y - t)*mask (:102-107) and
 // contributes -mask*t*log(y) (:122-128) and -mask*t*log(t + 1e-20) (:130-136); the target's arg-max (:113) is found among
-// the entries and the implicit zeros with FindRowMaxId's lowest-index tie break.
+// the entries and the implicit zeros with FindRowMaxId's lowest-index tie break.  A frame may have any number of entries: up to
+// 256 are staged in LDS for thread 0 (the fast path: diff and row_correct of such a frame are those it has always given); what lies
+// past them is kept per thread and combined afterwards, and the lowest zero of such a frame is searched by the whole workgroup.
+// The two entropies of every frame are the per-thread sums added in double.
 __global__ __launch_bounds__(256) void k_xent_post_rows(const float *__restrict__ y, int cols, int stride, const int *__restrict__ post_off,
                                                         const int *__restrict__ post_pdf, const float *__restrict__ post_w,
                                                         const float *__restrict__ mask, float *__restrict__ diff, int diff_stride,
@@ -2637,6 +2640,8 @@ __global__ __launch_bounds__(256) void k_xent_post_rows(const float *__restrict_
   __shared__ int smi[4];
   __shared__ float s_xe[256], s_en[256], s_acc[256];
   __shared__ int s_first[256];
+  __shared__ float s_tacc[256];                      // rows of more than 256 entries: every thread's best among its entries past the staging
+  __shared__ int s_tpdf[256], s_tcnt[256], s_need, s_z;
   const int row = blockIdx.x;
   const float *yp = y + (size_t)row * stride;
   float *dp = diff + (size_t)row * diff_stride;
@@ -2656,12 +2661,14 @@ __global__ __launch_bounds__(256) void k_xent_post_rows(const float *__restrict_
   if (lane == 0) { smv[wave] = best; smi[wave] = bi; }
   __syncthreads();                                   // also orders the dense diff pass before the per-entry fix-up
   float xe = 0.f, en = 0.f;
-  for (int e = threadIdx.x; e < n; e += 256) {       // (rows with more than 256 entries: the tail is handled by the loops below)
+  float lt = -3.4e38f; int li = 0x7fffffff, lc = 0;   // target arg-max and number of distinct pdfs among this thread's entries >= 256
+  for (int e = threadIdx.x; e < n; e += 256) {       // any number of entries: the first 256 are staged in LDS for thread 0, the rest kept per thread
     const int pdf = post_pdf[e0 + e];
     float acc = 0.f; bool first = true;
     for (int k = 0; k < n; k++)
       if (post_pdf[e0 + k] == pdf) { acc += post_w[e0 + k]; if (k < e) first = false; }   // same order of additions as the scatter
     if (e < 256) { s_acc[e] = acc; s_first[e] = first ? pdf : -1; }
+    else if (first) { lc++; if (acc > lt || (acc == lt && pdf < li)) { lt = acc; li = pdf; } }
     if (first) {
       const float v = yp[pdf];
       dp[pdf] = (v - acc) * m;                       // :102-107
@@ -2670,17 +2677,28 @@ __global__ __launch_bounds__(256) void k_xent_post_rows(const float *__restrict_
     }
   }
   s_xe[threadIdx.x] = xe; s_en[threadIdx.x] = en;
+  s_tacc[threadIdx.x] = lt; s_tpdf[threadIdx.x] = li; s_tcnt[threadIdx.x] = lc;
   __syncthreads();
+  float tb = -3.4e38f; int ti = 0x7fffffff;
   if (threadIdx.x == 0) {
     for (int w = 1; w < 4; w++) if (smv[w] > best || (smv[w] == best && smi[w] < bi)) { best = smv[w]; bi = smi[w]; }
-    float sx = 0.f, se = 0.f;
-    for (int t = 0; t < 256; t++) { sx += s_xe[t]; se += s_en[t]; }
+    // the 256 per-thread sums in double, rounded once (a float32 accumulator over 256 terms would lose ~sqrt(256) 2^-25 of the result,
+    // more than the 2^-21 that tests/test_output_tail_gpu.py allows)
+    double dx = 0.0, de = 0.0;
+    for (int t = 0; t < 256; t++) { dx += (double)s_xe[t]; de += (double)s_en[t]; }
+    const float sx = (float)dx, se = (float)de;
     // arg-max of the (virtual) dense target row
     const int ne = n < 256 ? n : 256;
-    float tb = -3.4e38f; int ti = 0x7fffffff, distinct = 0;
+    int distinct = 0;
     for (int e = 0; e < ne; e++)
       if (s_first[e] >= 0) { distinct++; if (s_acc[e] > tb || (s_acc[e] == tb && s_first[e] < ti)) { tb = s_acc[e]; ti = s_first[e]; } }
-    if (distinct < cols && tb <= 0.f) {              // an implicit zero is (one of) the maxima: lowest index whose value is 0
+    if (n > 256)
+      for (int t = 0; t < 256; t++) {
+        distinct += s_tcnt[t];
+        if (s_tcnt[t] && (s_tacc[t] > tb || (s_tacc[t] == tb && s_tpdf[t] < ti))) { tb = s_tacc[t]; ti = s_tpdf[t]; }
+      }
+    const bool zero_wins = distinct < cols && tb <= 0.f;   // an implicit zero is (one of) the maxima: lowest index whose value is 0
+    if (zero_wins && n <= 256) {
       int z = 0;
       for (bool again = true; again;) {
         again = false;
@@ -2689,8 +2707,30 @@ __global__ __launch_bounds__(256) void k_xent_post_rows(const float *__restrict_
       if (tb < 0.f || z < ti) ti = z;
     }
     row_xent[row] = sx; row_ent[row] = se;
-    row_correct[row] = (m == 1.f && bi == ti) ? 1.f : 0.f;
+    if (n <= 256) row_correct[row] = (m == 1.f && bi == ti) ? 1.f : 0.f;
+    s_need = zero_wins ? 1 : 0; s_z = 0x7fffffff;
   }
+  if (n <= 256) return;
+  // more than 256 entries: the accumulated weights past the staging live nowhere, so the lowest zero of the (virtual) dense target row is
+  // found by building its columns again, 256 candidates a round with the scatter's order of additions.  At most `distinct` <= n columns
+  // are not zero: a few rounds.
+  __syncthreads();
+  if (s_need) {
+    for (int base = 0; base < cols; base += 256) {
+      const int c = base + threadIdx.x;
+      if (c < cols) {
+        float acc = 0.f;
+        for (int k = 0; k < n; k++) if (post_pdf[e0 + k] == c) acc += post_w[e0 + k];
+        if (!(acc != 0.f)) atomicMin(&s_z, c);
+      }
+      __syncthreads();
+      const bool found = s_z != 0x7fffffff;
+      __syncthreads();                               // (nobody lowers s_z in the next round before everyone has read this one's)
+      if (found) break;
+    }
+    if (threadIdx.x == 0 && (tb < 0.f || s_z < ti)) ti = s_z;
+  }
+  if (threadIdx.x == 0) row_correct[row] = (m == 1.f && bi == ti) ? 1.f : 0.f;
 }
 
 
