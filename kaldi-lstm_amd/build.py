@@ -13,7 +13,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = ["csrc/klstm_kernels.hip", "csrc/klstm_persist.hip", "csrc/klstm_persist_bwd.hip", "csrc/klstm_persist_ms.hip", "csrc/klstm_persist_xl.hip", "csrc/klstm_fold.hip", "csrc/klstm_fold3.hip", "csrc/klstm_oneshot.hip", "csrc/klstm_outer.hip", "csrc/klstm_gemm16.hip", "csrc/klstm_score.hip", "csrc/klstm_ctc.hip", "csrc/klstm_ctc_decode.hip", "csrc/klstm_ctc_align.hip", "csrc/klstm_ctc_beam.hip", "csrc/klstm_ctc_mbr.hip", "csrc/klstm_ctc_mmi.hip", "csrc/klstm_ctc_consensus.hip", "csrc/klstm_ctc_rescore.hip", "csrc/klstm_ctc_nlm.hip",
+SRCS = ["csrc/klstm_kernels.hip", "csrc/klstm_output.hip", "csrc/klstm_persist.hip", "csrc/klstm_persist_bwd.hip", "csrc/klstm_persist_ms.hip", "csrc/klstm_persist_xl.hip", "csrc/klstm_fold.hip", "csrc/klstm_fold3.hip", "csrc/klstm_oneshot.hip", "csrc/klstm_outer.hip", "csrc/klstm_gemm16.hip", "csrc/klstm_score.hip", "csrc/klstm_ctc.hip", "csrc/klstm_ctc_decode.hip", "csrc/klstm_ctc_align.hip", "csrc/klstm_ctc_beam.hip", "csrc/klstm_ctc_mbr.hip", "csrc/klstm_ctc_mmi.hip", "csrc/klstm_ctc_consensus.hip", "csrc/klstm_ctc_rescore.hip", "csrc/klstm_ctc_nlm.hip",
         "csrc/klstm_api_ops.hip", "csrc/klstm_api_ctc.hip", "csrc/klstm_comm.hip", "csrc/klstm_engine.hip"]
 HDRS = ["csrc/klstm_kernels.h", "csrc/klstm_host.h","csrc/klstm_math.h", "csrc/klstm_persist_dev.h", "csrc/klstm_ctc_dev.h", "csrc/klstm_ctc_host.h", "csrc/klstm_ctc_nbest.h", "csrc/klstm_ctc_beam_frame.h", "csrc/klstm_ctc_slm.h", "../include/klstm.h", "../include/klstm_nlm.h"]
 LIB = os.path.join(HERE, "libklstm.so")
@@ -76,7 +76,7 @@ def build(force=False, verbose=False):
             for f in os.listdir(OBJDIR):
                 if f.endswith(".hash"):
                     os.remove(os.path.join(OBJDIR, f))
-        with concurrent.futures.ThreadPoolExecutor(max_workers=len(SRCS)) as pool:
+        with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(SRCS), int(os.environ.get("MAX_JOBS", "16")))) as pool:
             objs = list(pool.map(lambda s: _compile(hipcc, s, verbose), SRCS))
         tmp = LIB + ".tmp.%d" % os.getpid()
         subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp] + objs + ["-ldl"])

@@ -13,6 +13,7 @@
 //   k_grads      : all gradient accumulations (:468-487) in one grouped launch
 //   k_update_repack : Update (:504-512) + refresh of the transposed weight copies
 //   k_gemm       : batched x-projection (:246 + :259) when it is not fused into the step kernel
+// (The output tail -- time shift, softmax / xent rows, column sums, element-wise updates -- is klstm_output.hip.)
 //
 // The recurrence is latency-bound at small NumStream (a dependent kernel boundary costs ~1.6 us on
 // this chip, a dependent HBM/L2 round trip 0.5-1 us), so every step kernel is written to make
@@ -1494,23 +1495,24 @@ struct GemmJob {
   float *Cm; int ldc;
   const float *bias;
   int vecA, vecB;
-  // optional extra destinations of the same result (all null by default):
-  float *Ct; int ldct;    // transposed copy  Ct[n][m]  (M % 4 == 0)
-  float *C2; int ldc2;    // second copy      C2[m][n]
-  float *C3; int tail0;   // rows m >= tail0 also to C3[m - tail0][n], dense (ld = N)
+  // everything above comes from make_job; what follows is optional and off by default.
+  // extra destinations of the same result:
+  float *Ct = nullptr; int ldct = 0;    // transposed copy  Ct[n][m]  (M % 4 == 0)
+  float *C2 = nullptr; int ldc2 = 0;    // second copy      C2[m][n]
+  float *C3 = nullptr; int tail0 = 0;   // rows m >= tail0 also to C3[m - tail0][n], dense (ld = N)
   int kslice = 0;         // k_gemm_bf16_nt only: split K, slice length (0: off)
   // fold product only (launch_fold): rows of A are read in gates-packed order (gperm = C) and the result goes straight
   // into the two packed operand arrays of the folded step kernels instead of Cm
-  int gperm;
-  float4 *pk1; int nch1;  // [W_rm | W_x] gates array: [C/4 tiles][nch1 chunks of 32][2][64]
-  float4 *pk2; int nch2;  // W_rm^T 4-row array:       [C/4 tiles][nch2 chunks of 128][2][64]
+  int gperm = 0;
+  float4 *pk1 = nullptr; int nch1 = 0;  // [W_rm | W_x] gates array: [C/4 tiles][nch1 chunks of 32][2][64]
+  float4 *pk2 = nullptr; int nch2 = 0;  // W_rm^T 4-row array:       [C/4 tiles][nch2 chunks of 128][2][64]
   // gradient product with the Update folded in (launch_grads with a GradsUpdate): Cm is the momentum buffer,
   // Cm = beta*Cm + A*B (:468-487), clipped if clip > 0, then P -= lr*Cm (:504-512); Ct then receives the UPDATED P
-  float *P; float lr, clip;
-  int s3mode;                                // plane format (klstm_math.h split_store4)
-  unsigned short *s3; long s3pl; int s3t;   // the bf16 / fp16 planes of the UPDATED P (s3t = 0: P's layout, ld = ldc; 1: Ct's layout, ld = ldct)
+  float *P = nullptr; float lr = 0.f, clip = 0.f;
+  int s3mode = 1;                            // plane format (klstm_math.h split_store4)
+  unsigned short *s3 = nullptr; long s3pl = 0; int s3t = 0;   // the bf16 / fp16 planes of the UPDATED P (s3t = 0: P's layout, ld = ldc; 1: Ct's layout, ld = ldct)
   unsigned short *cth = nullptr;            // (or null) bf16 copy (RNE) of Ct, same layout: the B operand of klstm_gemm16.hip's LDS-DMA form
-  int coal;               // 1: Cm = beta*Cm + A*B through the same coalesced 16-byte epilogue without P (N, ldc % 4 == 0, aligned, no bias)
+  int coal = 0;           // 1: Cm = beta*Cm + A*B through the same coalesced 16-byte epilogue without P (N, ldc % 4 == 0, aligned, no bias)
   const unsigned *guard = nullptr;   // k_gemm only: the engine's control words; a persistent launch in front gave up ([2] | [6]) -> write nothing
 };
 
@@ -1876,11 +1878,11 @@ __global__ __launch_bounds__(256) void k_gemm_splitk(GemmJob g, int klen, float 
 struct ReduceArgs {
   const float *ws; int ks, M, N;
   float beta; float *Cm; int ldc;
-  const float *bias;
-  const float *add; int add_ld;       // C = beta*C + add + bias + sum of slices
-  float *C2; int ldc2;                // mirrors, as in GemmJob
-  float *C3; int tail0;
-  const unsigned *guard = nullptr;    // as in GemmJob
+  const float *bias = nullptr;
+  const float *add = nullptr; int add_ld = 0;   // C = beta*C + add + bias + sum of slices
+  float *C2 = nullptr; int ldc2 = 0;            // mirrors, as in GemmJob
+  float *C3 = nullptr; int tail0 = 0;
+  const unsigned *guard = nullptr;              // as in GemmJob
 };
 __global__ __launch_bounds__(256) void k_splitk_reduce(ReduceArgs a) {
   if (a.guard && (a.guard[2] | a.guard[6])) return;
@@ -2604,423 +2606,6 @@ __global__ __launch_bounds__(256) void k_update_repack_v(UpdArgs a) {
   }
 }
 
-// TimeShift::PropagateFnc (standard/nnet/nnet-time-shift.h:42-51): out[dst] = in[clamp(dst + shift, 0, rows-1)]
-// (shift == 0 is TransmitComponent's copy, nnet-transmit-component.h:26-33).  One row per blockIdx.y, lane-contiguous.
-__global__ void k_time_shift(const float *__restrict__ in, int rows, int cols, int in_stride, float *__restrict__ out,
-                             int out_stride, int shift, int vec) {
-  const int dst = blockIdx.y;
-  int src = dst + shift;
-  src = src < 0 ? 0 : src;
-  src = src > rows - 1 ? rows - 1 : src;
-  const float *ip = in + (size_t)src * in_stride;
-  float *op = out + (size_t)dst * out_stride;
-  if (vec) {
-    for (int c = (blockIdx.x * blockDim.x + threadIdx.x) * 4; c < cols; c += gridDim.x * blockDim.x * 4)
-      *reinterpret_cast<float4 *>(op + c) = *reinterpret_cast<const float4 *>(ip + c);
-  } else {
-    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < cols; c += gridDim.x * blockDim.x) op[c] = ip[c];
-  }
-}
-
-// Xent::EvalMasked for GENERAL posteriors (google/nnet/nnet-loss.cc:76-142): frame r carries the (pdf, weight) entries
-// post_pdf/post_w[post_off[r] .. post_off[r+1]); the reference scatters them into a dense zero matrix (`tgt(t, pdf) += w`,
-// so repeated pdfs add up, :86-96) and then works on dense rows.  Here the dense target never exists: one workgroup per
-// row writes diff = y*mask, then the first occurrence of every pdf fixes its column to (y - t)*mask (:102-107) and
-// contributes -mask*t*log(y) (:122-128) and -mask*t*log(t + 1e-20) (:130-136); the target's arg-max (:113) is found among
-// the entries and the implicit zeros with FindRowMaxId's lowest-index tie break.  A frame may have any number of entries: up to
-// 256 are staged in LDS for thread 0 (the fast path: diff and row_correct of such a frame are those it has always given); what lies
-// past them is kept per thread and combined afterwards, and the lowest zero of such a frame is searched by the whole workgroup.
-// The two entropies of every frame are the per-thread sums added in double.
-__global__ __launch_bounds__(256) void k_xent_post_rows(const float *__restrict__ y, int cols, int stride, const int *__restrict__ post_off,
-                                                        const int *__restrict__ post_pdf, const float *__restrict__ post_w,
-                                                        const float *__restrict__ mask, float *__restrict__ diff, int diff_stride,
-                                                        float *__restrict__ row_xent, float *__restrict__ row_ent,
-                                                        float *__restrict__ row_correct) {
-  __shared__ float smv[4];
-  __shared__ int smi[4];
-  __shared__ float s_xe[256], s_en[256], s_acc[256];
-  __shared__ int s_first[256];
-  __shared__ float s_tacc[256];                      // rows of more than 256 entries: every thread's best among its entries past the staging
-  __shared__ int s_tpdf[256], s_tcnt[256], s_need, s_z;
-  const int row = blockIdx.x;
-  const float *yp = y + (size_t)row * stride;
-  float *dp = diff + (size_t)row * diff_stride;
-  const float m = mask[row];
-  const int e0 = post_off[row], n = post_off[row + 1] - e0;
-  float best = -3.4e38f; int bi = 0x7fffffff;
-  for (int c = threadIdx.x; c < cols; c += 256) {
-    const float v = yp[c];
-    dp[c] = v * m;                                   // (y - 0) * mask; columns with a target are redone below
-    if (v > best) { best = v; bi = c; }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {                 // arg-max of the network output, lowest index on ties
-    const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if (lane == 0) { smv[wave] = best; smi[wave] = bi; }
-  __syncthreads();                                   // also orders the dense diff pass before the per-entry fix-up
-  float xe = 0.f, en = 0.f;
-  float lt = -3.4e38f; int li = 0x7fffffff, lc = 0;   // target arg-max and number of distinct pdfs among this thread's entries >= 256
-  for (int e = threadIdx.x; e < n; e += 256) {       // any number of entries: the first 256 are staged in LDS for thread 0, the rest kept per thread
-    const int pdf = post_pdf[e0 + e];
-    float acc = 0.f; bool first = true;
-    for (int k = 0; k < n; k++)
-      if (post_pdf[e0 + k] == pdf) { acc += post_w[e0 + k]; if (k < e) first = false; }   // same order of additions as the scatter
-    if (e < 256) { s_acc[e] = acc; s_first[e] = first ? pdf : -1; }
-    else if (first) { lc++; if (acc > lt || (acc == lt && pdf < li)) { lt = acc; li = pdf; } }
-    if (first) {
-      const float v = yp[pdf];
-      dp[pdf] = (v - acc) * m;                       // :102-107
-      xe -= (logf(v) * acc) * m;                     // :122-128
-      en -= (logf(acc + 1e-20f) * acc) * m;          // :130-136
-    }
-  }
-  s_xe[threadIdx.x] = xe; s_en[threadIdx.x] = en;
-  s_tacc[threadIdx.x] = lt; s_tpdf[threadIdx.x] = li; s_tcnt[threadIdx.x] = lc;
-  __syncthreads();
-  float tb = -3.4e38f; int ti = 0x7fffffff;
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; w++) if (smv[w] > best || (smv[w] == best && smi[w] < bi)) { best = smv[w]; bi = smi[w]; }
-    // the 256 per-thread sums in double, rounded once (a float32 accumulator over 256 terms would lose ~sqrt(256) 2^-25 of the result,
-    // more than the 2^-21 that tests/test_output_tail_gpu.py allows)
-    double dx = 0.0, de = 0.0;
-    for (int t = 0; t < 256; t++) { dx += (double)s_xe[t]; de += (double)s_en[t]; }
-    const float sx = (float)dx, se = (float)de;
-    // arg-max of the (virtual) dense target row
-    const int ne = n < 256 ? n : 256;
-    int distinct = 0;
-    for (int e = 0; e < ne; e++)
-      if (s_first[e] >= 0) { distinct++; if (s_acc[e] > tb || (s_acc[e] == tb && s_first[e] < ti)) { tb = s_acc[e]; ti = s_first[e]; } }
-    if (n > 256)
-      for (int t = 0; t < 256; t++) {
-        distinct += s_tcnt[t];
-        if (s_tcnt[t] && (s_tacc[t] > tb || (s_tacc[t] == tb && s_tpdf[t] < ti))) { tb = s_tacc[t]; ti = s_tpdf[t]; }
-      }
-    const bool zero_wins = distinct < cols && tb <= 0.f;   // an implicit zero is (one of) the maxima: lowest index whose value is 0
-    if (zero_wins && n <= 256) {
-      int z = 0;
-      for (bool again = true; again;) {
-        again = false;
-        for (int e = 0; e < ne; e++) if (s_first[e] == z && s_acc[e] != 0.f) { z++; again = true; break; }
-      }
-      if (tb < 0.f || z < ti) ti = z;
-    }
-    row_xent[row] = sx; row_ent[row] = se;
-    if (n <= 256) row_correct[row] = (m == 1.f && bi == ti) ? 1.f : 0.f;
-    s_need = zero_wins ? 1 : 0; s_z = 0x7fffffff;
-  }
-  if (n <= 256) return;
-  // more than 256 entries: the accumulated weights past the staging live nowhere, so the lowest zero of the (virtual) dense target row is
-  // found by building its columns again, 256 candidates a round with the scatter's order of additions.  At most `distinct` <= n columns
-  // are not zero: a few rounds.
-  __syncthreads();
-  if (s_need) {
-    for (int base = 0; base < cols; base += 256) {
-      const int c = base + threadIdx.x;
-      if (c < cols) {
-        float acc = 0.f;
-        for (int k = 0; k < n; k++) if (post_pdf[e0 + k] == c) acc += post_w[e0 + k];
-        if (!(acc != 0.f)) atomicMin(&s_z, c);
-      }
-      __syncthreads();
-      const bool found = s_z != 0x7fffffff;
-      __syncthreads();                               // (nobody lowers s_z in the next round before everyone has read this one's)
-      if (found) break;
-    }
-    if (threadIdx.x == 0 && (tb < 0.f || s_z < ti)) ti = s_z;
-  }
-  if (threadIdx.x == 0) row_correct[row] = (m == 1.f && bi == ti) ? 1.f : 0.f;
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// output tail of the nnet: Softmax rows, Xent::EvalMasked, and the small vector ops of
-// AffineTransform::Update.  One 256-thread workgroup per frame row, lane-contiguous column sweeps.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_reduce(float v, float *sm, bool is_max) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) { const float w = __shfl_xor(v, o); v = is_max ? fmaxf(v, w) : v + w; }
-  __syncthreads();
-  if (lane == 0) sm[wave] = v;
-  __syncthreads();
-  float r = sm[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); w++) r = is_max ? fmaxf(r, sm[w]) : r + sm[w];
-  return r;
-}
-// Softmax::PropagateFnc [UPSTREAM-unvendored nnet-activation.h -> CuMatrix::ApplySoftMaxPerRow]: y = exp(x - max) / sum
-__global__ __launch_bounds__(256) void k_softmax_rows(const float *__restrict__ in, int cols, int in_stride,
-                                                      float *__restrict__ out, int out_stride) {
-  __shared__ float sm[4];
-  const float *ip = in + (size_t)blockIdx.x * in_stride;
-  float *op = out + (size_t)blockIdx.x * out_stride;
-  float mx = -3.4e38f;
-  for (int c = threadIdx.x; c < cols; c += 256) mx = fmaxf(mx, ip[c]);
-  mx = block_reduce(mx, sm, true);
-  float sum = 0.f;
-  for (int c = threadIdx.x; c < cols; c += 256) { const float e = expf(ip[c] - mx); op[c] = e; sum += e; }
-  sum = block_reduce(sum, sm, false);
-  const float inv = 1.f / sum;
-  for (int c = threadIdx.x; c < cols; c += 256) op[c] *= inv;
-}
-// Wide rows (the 16624-way output layer): 1024 threads per row, the whole row in registers (8 x float4 per thread, all
-// loads issued up front), one pass over memory: 26 -> ~6 us at 80 x 16624.  Needs cols % 4 == 0, cols <= 32768 and
-// 16-byte aligned rows; other shapes use k_softmax_rows.
-__global__ __launch_bounds__(1024) void k_softmax_rows_v(const float *__restrict__ in, int cols, int in_stride,
-                                                        float *__restrict__ out, int out_stride) {
-  __shared__ float sm[16];
-  const float4 *ip = reinterpret_cast<const float4 *>(in + (size_t)blockIdx.x * in_stride);
-  float4 *op = reinterpret_cast<float4 *>(out + (size_t)blockIdx.x * out_stride);
-  const int n4 = cols >> 2;
-  float4 v[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) {
-    const int c = threadIdx.x + 1024 * u;
-    const float4 t = ip[c < n4 ? c : 0];
-    v[u] = c < n4 ? t : make_float4(-3.4e38f, -3.4e38f, -3.4e38f, -3.4e38f);
-  }
-  float mx = -3.4e38f;
-#pragma unroll
-  for (int u = 0; u < 8; u++) mx = fmaxf(mx, fmaxf(fmaxf(v[u].x, v[u].y), fmaxf(v[u].z, v[u].w)));
-  mx = block_reduce(mx, sm, true);
-  float sum = 0.f;
-#pragma unroll
-  for (int u = 0; u < 8; u++) {
-    const bool on = threadIdx.x + 1024 * u < n4;
-    v[u].x = on ? expf(v[u].x - mx) : 0.f; v[u].y = on ? expf(v[u].y - mx) : 0.f;
-    v[u].z = on ? expf(v[u].z - mx) : 0.f; v[u].w = on ? expf(v[u].w - mx) : 0.f;
-    sum += (v[u].x + v[u].y) + (v[u].z + v[u].w);
-  }
-  sum = block_reduce(sum, sm, false);
-  const float inv = 1.f / sum;
-#pragma unroll
-  for (int u = 0; u < 8; u++) {
-    const int c = threadIdx.x + 1024 * u;
-    if (c < n4) op[c] = make_float4(v[u].x * inv, v[u].y * inv, v[u].z * inv, v[u].w * inv);
-  }
-}
-// Xent::EvalMasked (google/nnet/nnet-loss.cc:76-142) for one-hot targets (alignments): per frame row
-//   diff = (y - t) * mask (:102-107), row_xent = -mask * log(y[target]) (:122-128),
-//   row_correct = mask == 1 && argmax(y) == target (:109-120; first maximum wins like FindRowMaxId).
-__global__ __launch_bounds__(256) void k_xent_rows(const float *__restrict__ y, int cols, int stride,
-                                                   const int *__restrict__ target, const float *__restrict__ mask,
-                                                   float *__restrict__ diff, int diff_stride,
-                                                   float *__restrict__ row_xent, float *__restrict__ row_correct) {
-  __shared__ float smv[4];
-  __shared__ int smi[4];
-  const int row = blockIdx.x;
-  const float *yp = y + (size_t)row * stride;
-  float *dp = diff + (size_t)row * diff_stride;
-  const int tgt = target[row];
-  const float m = mask[row];
-  float best = -3.4e38f; int bi = 0x7fffffff;
-  for (int c = threadIdx.x; c < cols; c += 256) {
-    const float v = yp[c];
-    dp[c] = (v - (c == tgt ? 1.f : 0.f)) * m;
-    if (v > best) { best = v; bi = c; }
-  }
-  // argmax with lowest-index tie break
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if (lane == 0) { smv[wave] = best; smi[wave] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; w++) if (smv[w] > best || (smv[w] == best && smi[w] < bi)) { best = smv[w]; bi = smi[w]; }
-    row_xent[row] = (tgt >= 0 && tgt < cols) ? -m * logf(yp[tgt]) : 0.f;
-    row_correct[row] = (m == 1.f && bi == tgt) ? 1.f : 0.f;
-  }
-}
-__global__ __launch_bounds__(1024) void k_xent_rows_v(const float *__restrict__ y, int cols, int stride,
-                                                     const int *__restrict__ target, const float *__restrict__ mask,
-                                                     float *__restrict__ diff, int diff_stride,
-                                                     float *__restrict__ row_xent, float *__restrict__ row_correct) {
-  __shared__ float smv[16];
-  __shared__ int smi[16];
-  const int row = blockIdx.x;
-  const float4 *yp = reinterpret_cast<const float4 *>(y + (size_t)row * stride);
-  float4 *dp = reinterpret_cast<float4 *>(diff + (size_t)row * diff_stride);
-  const int tgt = target[row];
-  const float m = mask[row];
-  const int n4 = cols >> 2;
-  float4 v[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) { const int c = threadIdx.x + 1024 * u; v[u] = yp[c < n4 ? c : 0]; }
-  float best = -3.4e38f; int bi = 0x7fffffff;
-#pragma unroll
-  for (int u = 0; u < 8; u++) {
-    const int c = threadIdx.x + 1024 * u;
-    if (c < n4) {
-      const float e[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-      float d[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int col = 4 * c + j;
-        d[j] = (e[j] - (col == tgt ? 1.f : 0.f)) * m;
-        if (e[j] > best) { best = e[j]; bi = col; }          // ascending columns per thread: first maximum wins
-      }
-      dp[c] = make_float4(d[0], d[1], d[2], d[3]);
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if (lane == 0) { smv[wave] = best; smi[wave] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 16; w++) if (smv[w] > best || (smv[w] == best && smi[w] < bi)) { best = smv[w]; bi = smi[w]; }
-    row_xent[row] = (tgt >= 0 && tgt < cols) ? -m * logf(y[(size_t)row * stride + tgt]) : 0.f;
-    row_correct[row] = (m == 1.f && bi == tgt) ? 1.f : 0.f;
-  }
-}
-// Softmax and Xent::EvalMasked of a wide row in ONE pass: k_softmax_rows_v's arithmetic, then k_xent_rows_v's on the registers
-// (same operations in the same order: the same bits as the pair), the posterior row written only if the caller wants it.
-// 80 x 16624: 9.2 + 6.3 us and 21 MB -> one launch, 10.6 MB.
-__global__ __launch_bounds__(1024) void k_softmax_xent_rows_v(const float *__restrict__ in, int cols, int in_stride, float *__restrict__ post,
-                                                             int post_stride, const int *__restrict__ target, const float *__restrict__ mask,
-                                                             float *__restrict__ diff, int diff_stride, float *row_xent,
-                                                             float *row_correct, double *totals, unsigned *ticket) {
-  __shared__ float sm[16];
-  __shared__ float smv[16];
-  __shared__ int smi[16];
-  __shared__ float s_yt;
-  __shared__ int s_last;
-  __shared__ double s_tot[3][16];
-  const int row = blockIdx.x;
-  const float4 *ip = reinterpret_cast<const float4 *>(in + (size_t)row * in_stride);
-  float4 *dp = reinterpret_cast<float4 *>(diff + (size_t)row * diff_stride);
-  const int tgt = target[row];
-  const float m = mask[row];
-  const int n4 = cols >> 2;
-  float4 v[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) {
-    const int c = threadIdx.x + 1024 * u;
-    const float4 t = ip[c < n4 ? c : 0];
-    v[u] = c < n4 ? t : make_float4(-3.4e38f, -3.4e38f, -3.4e38f, -3.4e38f);
-  }
-  float mx = -3.4e38f;
-#pragma unroll
-  for (int u = 0; u < 8; u++) mx = fmaxf(mx, fmaxf(fmaxf(v[u].x, v[u].y), fmaxf(v[u].z, v[u].w)));
-  mx = block_reduce(mx, sm, true);
-  float sum = 0.f;
-#pragma unroll
-  for (int u = 0; u < 8; u++) {
-    const bool on = threadIdx.x + 1024 * u < n4;
-    v[u].x = on ? expf(v[u].x - mx) : 0.f; v[u].y = on ? expf(v[u].y - mx) : 0.f;
-    v[u].z = on ? expf(v[u].z - mx) : 0.f; v[u].w = on ? expf(v[u].w - mx) : 0.f;
-    sum += (v[u].x + v[u].y) + (v[u].z + v[u].w);
-  }
-  sum = block_reduce(sum, sm, false);
-  const float inv = 1.f / sum;
-  float best = -3.4e38f; int bi = 0x7fffffff;
-#pragma unroll
-  for (int u = 0; u < 8; u++) {
-    const int c = threadIdx.x + 1024 * u;
-    if (c < n4) {
-      const float e[4] = {v[u].x * inv, v[u].y * inv, v[u].z * inv, v[u].w * inv};
-      if (post) reinterpret_cast<float4 *>(post + (size_t)row * post_stride)[c] = make_float4(e[0], e[1], e[2], e[3]);
-      float d[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int col = 4 * c + j;
-        d[j] = (e[j] - (col == tgt ? 1.f : 0.f)) * m;
-        if (col == tgt) s_yt = e[j];
-        if (e[j] > best) { best = e[j]; bi = col; }          // ascending columns per thread: first maximum wins
-      }
-      dp[c] = make_float4(d[0], d[1], d[2], d[3]);
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if (lane == 0) { smv[wave] = best; smi[wave] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 16; w++) if (smv[w] > best || (smv[w] == best && smi[w] < bi)) { best = smv[w]; bi = smi[w]; }
-    // (write-through, agent scope: the workgroup that takes the last ticket reads them with agent-scope loads)
-    __hip_atomic_store(row_xent + row, (tgt >= 0 && tgt < cols) ? -m * logf(s_yt) : 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(row_correct + row, (m == 1.f && bi == tgt) ? 1.f : 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (!totals) return;
-  // statistics onto the device totals without a launch of their own: the workgroup that takes the last ticket sees every row's two
-  // numbers and adds them up in a fixed order.  Round 6: the two numbers leave as write-through (sc1) stores and the ticket is taken
-  // once they are acknowledged (s_waitcnt vmcnt(0)) -- no __threadfence(): an agent-scope release writes back EVERY dirty line of the
-  // L2 (here: the 5.3 MB of derivatives the launch has just stored; ~3.5 us and more per workgroup, MI355X_MICROARCH.md) for 8 bytes
-  // that matter.  The same store-then-flag idiom as the granules of the persistent chains (klstm_persist_dev.h publish()).
-  if (threadIdx.x == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    s_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1 : 0;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  double t0 = 0.0, t1 = 0.0, t2 = 0.0;
-  for (int r = threadIdx.x; r < (int)gridDim.x; r += 1024) {
-    t0 += (double)__hip_atomic_load(row_xent + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    t1 += (double)__hip_atomic_load(row_correct + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    t2 += (double)mask[r];
-  }
-  for (int o = 32; o > 0; o >>= 1) { t0 += __shfl_xor(t0, o); t1 += __shfl_xor(t1, o); t2 += __shfl_xor(t2, o); }
-  if (lane == 0) { s_tot[0][wave] = t0; s_tot[1][wave] = t1; s_tot[2][wave] = t2; }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double t = 0.0;
-    for (int w = 0; w < 16; w++) t += s_tot[threadIdx.x][w];
-    totals[threadIdx.x] += t;
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (ready for the next launch on this stream)
-}
-// dst[j] = beta*dst[j] + sum_rows src[row][j]   (AddRowSumMat)
-// dst[j] = beta*dst[j] + sum over rows of src[r][j]: 64 columns x 4 row groups per workgroup, 8 loads in flight per thread
-// (a serial row loop costs one memory latency per row: 20 us for 80 rows), row groups combined through LDS in fixed order
-__global__ __launch_bounds__(256) void k_col_sum(const float *__restrict__ src, int rows, int cols, int stride, float beta,
-                                                 float *__restrict__ dst) {
-  __shared__ float part[4][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int j = blockIdx.x * 64 + tx;
-  const int jc = j < cols ? j : 0;
-  float s = 0.f;
-  for (int r0 = ty; r0 < rows; r0 += 32) {
-    float t[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) t[u] = src[(size_t)min(r0 + 4 * u, rows - 1) * stride + jc];
-#pragma unroll
-    for (int u = 0; u < 8; u++) s += (r0 + 4 * u < rows) ? t[u] : 0.f;
-  }
-  part[ty][tx] = s;
-  __syncthreads();
-  if (ty == 0 && j < cols) {
-    s = part[0][tx] + part[1][tx] + part[2][tx] + part[3][tx];
-    dst[j] = (beta != 0.f ? beta * dst[j] : 0.f) + s;
-  }
-}
-__global__ void k_axpy(float *__restrict__ y, const float *__restrict__ x, float a, long n) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = y[i] + a * x[i];
-}
-
-// corr = mmt*corr + grad ; param -= lr*corr  in one pass (the post-all-reduce step of a data-parallel Affine layer)
-__global__ void k_sgd_momentum(float *__restrict__ param, float *__restrict__ corr, const float *__restrict__ grad, float mmt,
-                               float lr, long n) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float c = mmt * corr[i] + grad[i];
-    corr[i] = c;
-    param[i] = param[i] + (-lr) * c;
-  }
-}
-__global__ void k_apply_momentum(float *__restrict__ corr, const float *__restrict__ grad, float mmt, long n, const unsigned *guard,
-                                 const float *mark) {
-  if (guard && (guard[2] | guard[6] | guard[9])) return;          // a persistent launch of this minibatch gave up: its gradient must not reach the momentum buffers
-  if (mark && *mark != 0.f) return;                               // (or a peer's: UpdArgs::mark)
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    corr[i] = mmt * corr[i] + grad[i];
-}
-
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
@@ -3078,6 +2663,14 @@ static inline VecCfg pick_vec(int S, int nch, bool gates = false) {
     if (cfg.nt == 2) return launch((KERN<2, 1, false __VA_ARGS__>), grid, _blk, 0, st, pr, args); \
     return launch((KERN<4, 1, false __VA_ARGS__>), grid, _blk, 0, st, pr, args);                  \
   } while (0)
+// many-stream kernels (FwdPtrs / BwdPtrs::fat, S > 16), MTW row tiles x KSW K splits per workgroup: (MF, KF) with the half-size
+// row tiles of fat_fine (`fine`), else (MC, KC); FS = chunks of the stream slab (16, or 32 for a long contraction)
+#define FAT_DISPATCH(KERN, fine, MF, KF, MC, KC, FS, grid, st, pr, args, ...)                     \
+  do {                                                                                            \
+    const dim3 _blk(NW * 64);                                                                     \
+    if (fine) return launch((KERN<MF, KF, FS __VA_ARGS__>), grid, _blk, 0, st, pr, args);         \
+    return launch((KERN<MC, KC, FS __VA_ARGS__>), grid, _blk, 0, st, pr, args);                   \
+  } while (0)
 #define COMMA ,
 static inline dim3 vec_grid(int ntiles, int S, const VecCfg &c, int z = 1) {
   return dim3(ntiles, cdiv(S, (c.small ? 4 : 16) * c.nt), z);
@@ -3107,35 +2700,23 @@ hipError_t launch_gates_step(const Dims &d0, const FwdPtrs &p, int t, bool fuse_
   if (vec) {
     GatesVArgs va; va.g = a; va.wpk = wpk;
     va.nch_total = cdiv(d.R, KCH) + cdiv(d.I, KCH);
-    if (p.fat && d.S > 16) {                                 // 4 row tiles (16 cells) x 2 K splits per workgroup
-      if (fat_fine(d.S)) {                       // few stream tiles: 8 cells x 4 K splits per workgroup -> twice the workgroups
-        va.gx = cdiv(d.C, 8);
-        const dim3 fg(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
-        const bool bigf = (fuse_x ? cdiv(d.R, KCH) + cdiv(d.I, KCH) : cdiv(d.R, KCH)) > 16;
-        if (p.bf16) {
-          if (fuse_x && bigf) return launch((k_gates_f<2, 4, 32, true, true>), fg, dim3(NW * 64), 0, st, pr, va);
-          if (fuse_x) return launch((k_gates_f<2, 4, 16, true, true>), fg, dim3(NW * 64), 0, st, pr, va);
-          if (bigf) return launch((k_gates_f<2, 4, 32, false, true>), fg, dim3(NW * 64), 0, st, pr, va);
-          return launch((k_gates_f<2, 4, 16, false, true>), fg, dim3(NW * 64), 0, st, pr, va);
-        }
-        if (fuse_x && bigf) return launch((k_gates_f<2, 4, 32, true, false>), fg, dim3(NW * 64), 0, st, pr, va);
-        if (fuse_x) return launch((k_gates_f<2, 4, 16, true, false>), fg, dim3(NW * 64), 0, st, pr, va);
-        if (bigf) return launch((k_gates_f<2, 4, 32, false, false>), fg, dim3(NW * 64), 0, st, pr, va);
-        return launch((k_gates_f<2, 4, 16, false, false>), fg, dim3(NW * 64), 0, st, pr, va);
-      }
-      va.gx = cdiv(d.C, 16);
+    if (p.fat && d.S > 16) {
+      // (MTW, KSW) = (4, 2): 4 row tiles (16 cells) x 2 K splits per workgroup; fine (few stream tiles) = (2, 4): 8 cells x 4 K
+      // splits -> twice the workgroups.  A 32-chunk slab when the contraction has more than 16 chunks.
+      const bool fine = fat_fine(d.S);
+      va.gx = cdiv(d.C, fine ? 8 : 16);
       const dim3 fgrid(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
       const bool big = (fuse_x ? cdiv(d.R, KCH) + cdiv(d.I, KCH) : cdiv(d.R, KCH)) > 16;
       if (p.bf16) {
-        if (fuse_x && big) return launch((k_gates_f<4, 2, 32, true, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
-        if (fuse_x) return launch((k_gates_f<4, 2, 16, true, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
-        if (big) return launch((k_gates_f<4, 2, 32, false, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
-        return launch((k_gates_f<4, 2, 16, false, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
+        if (fuse_x && big) FAT_DISPATCH(k_gates_f, fine, 2, 4, 4, 2, 32, fgrid, st, pr, va, COMMA true COMMA true);
+        if (fuse_x) FAT_DISPATCH(k_gates_f, fine, 2, 4, 4, 2, 16, fgrid, st, pr, va, COMMA true COMMA true);
+        if (big) FAT_DISPATCH(k_gates_f, fine, 2, 4, 4, 2, 32, fgrid, st, pr, va, COMMA false COMMA true);
+        FAT_DISPATCH(k_gates_f, fine, 2, 4, 4, 2, 16, fgrid, st, pr, va, COMMA false COMMA true);
       }
-      if (fuse_x && big) return launch((k_gates_f<4, 2, 32, true, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
-      if (fuse_x) return launch((k_gates_f<4, 2, 16, true, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
-      if (big) return launch((k_gates_f<4, 2, 32, false, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
-      return launch((k_gates_f<4, 2, 16, false, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
+      if (fuse_x && big) FAT_DISPATCH(k_gates_f, fine, 2, 4, 4, 2, 32, fgrid, st, pr, va, COMMA true COMMA false);
+      if (fuse_x) FAT_DISPATCH(k_gates_f, fine, 2, 4, 4, 2, 16, fgrid, st, pr, va, COMMA true COMMA false);
+      if (big) FAT_DISPATCH(k_gates_f, fine, 2, 4, 4, 2, 32, fgrid, st, pr, va, COMMA false COMMA false);
+      FAT_DISPATCH(k_gates_f, fine, 2, 4, 4, 2, 16, fgrid, st, pr, va, COMMA false COMMA false);
     }
     const VecCfg cfg = pick_vec(d.S, cdiv(d.R, KCH) + (fuse_x ? cdiv(d.I, KCH) : 0), true);
     const dim3 grid = vec_grid(cdiv(d.C, 4), d.S, cfg);
@@ -3163,24 +2744,15 @@ hipError_t launch_proj_step(const Dims &d, const FwdPtrs &p, int t, float *out, 
   if (vec) {
     ProjVArgs va; va.g = a; va.wpk = p.pk_proj;
     if (p.fat && d.S > 16) {
-      if (fat_fine(d.S)) {                       // one 16-row tile x 8 K splits per workgroup
-        va.gx = cdiv(d.R, 16);
-        const dim3 fg(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
-        if (p.bf16) {
-          if (cdiv(d.C, KCH) > 16) return launch((k_proj_f<1, 8, 32, true>), fg, dim3(NW * 64), 0, st, pr, va);
-          return launch((k_proj_f<1, 8, 16, true>), fg, dim3(NW * 64), 0, st, pr, va);
-        }
-        if (cdiv(d.C, KCH) > 16) return launch((k_proj_f<1, 8, 32, false>), fg, dim3(NW * 64), 0, st, pr, va);
-        return launch((k_proj_f<1, 8, 16, false>), fg, dim3(NW * 64), 0, st, pr, va);
-      }
-      va.gx = cdiv(d.R, 32);
+      // (MTW, KSW) = (2, 4): two 16-row tiles x 4 K splits per workgroup; fine = (1, 8): one 16-row tile x 8 K splits
+      const bool fine = fat_fine(d.S);
+      va.gx = cdiv(d.R, fine ? 16 : 32);
       const dim3 fgrid(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
-      if (p.bf16) {
-        if (cdiv(d.C, KCH) > 16) return launch((k_proj_f<2, 4, 32, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
-        return launch((k_proj_f<2, 4, 16, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
-      }
-      if (cdiv(d.C, KCH) > 16) return launch((k_proj_f<2, 4, 32, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
-      return launch((k_proj_f<2, 4, 16, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
+      const bool big = cdiv(d.C, KCH) > 16;
+      if (p.bf16 && big) FAT_DISPATCH(k_proj_f, fine, 1, 8, 2, 4, 32, fgrid, st, pr, va, COMMA true);
+      if (p.bf16) FAT_DISPATCH(k_proj_f, fine, 1, 8, 2, 4, 16, fgrid, st, pr, va, COMMA true);
+      if (big) FAT_DISPATCH(k_proj_f, fine, 1, 8, 2, 4, 32, fgrid, st, pr, va, COMMA false);
+      FAT_DISPATCH(k_proj_f, fine, 1, 8, 2, 4, 16, fgrid, st, pr, va, COMMA false);
     }
     const VecCfg cfg = pick_vec(d.S, cdiv(d.C, KCH));
     if (p.bf16) VEC_DISPATCH(k_proj_v, cfg, vec_grid(cdiv(d.R, 16), d.S, cfg), st, pr, va, COMMA true);
@@ -3222,20 +2794,16 @@ hipError_t launch_dr_step(const Dims &d, const BwdPtrs &p, int t, float *in_diff
   if (vec) {
     DrVArgs va; va.g = a; va.wpk = p.pk_dr; va.nch_total = cdiv(K, KCH);
     if (p.fat && d.S > 16) {
-      va.g.ntr = t == 0 ? 0 : cdiv(d.R, 32);                       // 32-row groups (2 row tiles x 4 K splits)
-      const int gx = cdiv(va.g.ntr + (in_diff ? cdiv(d.I, 32) : 0), 8) * 8;
-      va.gx = va.g.ntr + (in_diff ? cdiv(d.I, 32) : 0);
-      // (a 32-chunk slab was measured slower here: 66 KB of LDS and 16 weight registers per lane cost more in
-      //  occupancy than the second staging round trip they save)
-      if (fat_fine(d.S)) {                       // 16-row groups (one row tile x 8 K splits)
-        va.g.ntr = t == 0 ? 0 : cdiv(d.R, 16);
-        va.gx = va.g.ntr + (in_diff ? cdiv(d.I, 16) : 0);
-        const int gxf = cdiv(va.gx, 8) * 8;
-        if (p.bf16) return launch((k_dr_f<1, 8, 16, true>), dim3(gxf, cdiv(d.S, FST), ks), dim3(NW * 64), 0, st, pr, va);
-        return launch((k_dr_f<1, 8, 16, false>), dim3(gxf, cdiv(d.S, FST), ks), dim3(NW * 64), 0, st, pr, va);
-      }
-      if (p.bf16) return launch((k_dr_f<2, 4, 16, true>), dim3(gx, cdiv(d.S, FST), ks), dim3(NW * 64), 0, st, pr, va);
-      return launch((k_dr_f<2, 4, 16, false>), dim3(gx, cdiv(d.S, FST), ks), dim3(NW * 64), 0, st, pr, va);
+      // (MTW, KSW) = (2, 4): 32-row groups (2 row tiles x 4 K splits); fine = (1, 8): 16-row groups (one row tile x 8 K splits)
+      const bool fine = fat_fine(d.S);
+      const int grp = fine ? 16 : 32;
+      va.g.ntr = t == 0 ? 0 : cdiv(d.R, grp);
+      va.gx = va.g.ntr + (in_diff ? cdiv(d.I, grp) : 0);
+      const dim3 fgrid(cdiv(va.gx, 8) * 8, cdiv(d.S, FST), ks);
+      // the slab is 16 chunks whatever the length (a 32-chunk slab was measured slower here: 66 KB of LDS and 16 weight
+      // registers per lane cost more in occupancy than the second staging round trip they save)
+      if (p.bf16) FAT_DISPATCH(k_dr_f, fine, 1, 8, 2, 4, 16, fgrid, st, pr, va, COMMA true);
+      FAT_DISPATCH(k_dr_f, fine, 1, 8, 2, 4, 16, fgrid, st, pr, va, COMMA false);
     }
     const VecCfg cfg = pick_vec(d.S, cdiv(a.klen, KCH));
     if (p.bf16) VEC_DISPATCH(k_dr_v, cfg, vec_grid(a.ntr + ntx, d.S, cfg, ks), st, pr, va, COMMA true);
@@ -3265,24 +2833,15 @@ hipError_t launch_dm_step(const Dims &d, const BwdPtrs &p, int t, const float *o
   if (vec) {
     DmVArgs va; va.g = a; va.wpk = p.pk_dm;
     if (p.fat && d.S > 16) {
-      if (fat_fine(d.S)) {
-        va.gx = cdiv(d.C, 16);
-        const dim3 fg(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
-        if (p.bf16) {
-          if (cdiv(d.R, KCH) > 16) return launch((k_dm_f<1, 8, 32, true>), fg, dim3(NW * 64), 0, st, pr, va);
-          return launch((k_dm_f<1, 8, 16, true>), fg, dim3(NW * 64), 0, st, pr, va);
-        }
-        if (cdiv(d.R, KCH) > 16) return launch((k_dm_f<1, 8, 32, false>), fg, dim3(NW * 64), 0, st, pr, va);
-        return launch((k_dm_f<1, 8, 16, false>), fg, dim3(NW * 64), 0, st, pr, va);
-      }
-      va.gx = cdiv(d.C, 32);
+      // (MTW, KSW) = (2, 4): two 16-row tiles x 4 K splits per workgroup; fine = (1, 8): one 16-row tile x 8 K splits
+      const bool fine = fat_fine(d.S);
+      va.gx = cdiv(d.C, fine ? 16 : 32);
       const dim3 fgrid(cdiv(va.gx, 8) * 8, cdiv(d.S, FST));
-      if (p.bf16) {
-        if (cdiv(d.R, KCH) > 16) return launch((k_dm_f<2, 4, 32, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
-        return launch((k_dm_f<2, 4, 16, true>), fgrid, dim3(NW * 64), 0, st, pr, va);
-      }
-      if (cdiv(d.R, KCH) > 16) return launch((k_dm_f<2, 4, 32, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
-      return launch((k_dm_f<2, 4, 16, false>), fgrid, dim3(NW * 64), 0, st, pr, va);
+      const bool big = cdiv(d.R, KCH) > 16;
+      if (p.bf16 && big) FAT_DISPATCH(k_dm_f, fine, 1, 8, 2, 4, 32, fgrid, st, pr, va, COMMA true);
+      if (p.bf16) FAT_DISPATCH(k_dm_f, fine, 1, 8, 2, 4, 16, fgrid, st, pr, va, COMMA true);
+      if (big) FAT_DISPATCH(k_dm_f, fine, 1, 8, 2, 4, 32, fgrid, st, pr, va, COMMA false);
+      FAT_DISPATCH(k_dm_f, fine, 1, 8, 2, 4, 16, fgrid, st, pr, va, COMMA false);
     }
     const VecCfg cfg = pick_vec(d.S, cdiv(d.R, KCH));
     if (p.bf16) VEC_DISPATCH(k_dm_v, cfg, vec_grid(cdiv(d.C, 16), d.S, cfg), st, pr, va, COMMA true);
@@ -3292,9 +2851,6 @@ hipError_t launch_dm_step(const Dims &d, const BwdPtrs &p, int t, const float *o
   const dim3 grid(cdiv(d.C, 16), cdiv(d.S, 16 * nt));
   GEN_DISPATCH(k_dm_step, nt, grid, st, pr, a, );
 }
-
-static GemmJob make_job(bool transA, bool transB, int M, int N, int K, const float *A, int lda, const float *B,
-                        int ldb, float beta, float *Cm, int ldc, const float *bias);
 
 hipError_t launch_dmf_step(const Dims &d, const BwdPtrs &p, int t, const float *P, hipStream_t st, LaunchProbe pr) {
   DmfArgs a;
@@ -3316,6 +2872,19 @@ hipError_t launch_dmf_step(const Dims &d, const BwdPtrs &p, int t, const float *
   if (need == 2) return launch((k_dmf_v<2, 1>), grid, blk, 0, st, pr, a);
   return launch((k_dmf_v<4, 1>), grid, blk, 0, st, pr, a);
 }
+
+static GemmJob make_job(bool transA, bool transB, int M, int N, int K, const float *A, int lda, const float *B,
+                        int ldb, float beta, float *Cm, int ldc, const float *bias) {
+  GemmJob g;
+  g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.beta = beta;
+  g.Cm = Cm; g.ldc = ldc; g.bias = bias;
+  // branch-free 8-wide fetches need aligned rows and a contiguous extent that is a multiple of 8
+  g.vecA = aligned16(A) && lda % 4 == 0 && (transA ? M : K) % 8 == 0;
+  g.vecB = aligned16(B) && ldb % 4 == 0 && (transB ? K : N) % 8 == 0;
+  return g;
+}
+// k_gemm's 1-D grid: the 64 x 64 output tiles, padded to a multiple of 8 (one share per XCD)
+static inline dim3 gemm_grid(int M, int N) { return dim3(cdiv(cdiv(N, GT) * cdiv(M, GT), 8) * 8); }
 
 // x chunks of the folded gates array (the W_rm chunks are written by the fold product itself)
 __global__ __launch_bounds__(256) void k_pack_foldx(const float *__restrict__ wx, float4 *__restrict__ pk, int C, int I, int nch1) {
@@ -3343,7 +2912,7 @@ hipError_t launch_fold(const Dims &d, const float *param_blob, const float *wmT,
   g.gperm = d.C;
   g.pk1 = reinterpret_cast<float4 *>(pk_fold[0]); g.nch1 = cdiv(d.C, KCH) + cdiv(d.I, KCH);
   g.pk2 = reinterpret_cast<float4 *>(pk_fold[1]); g.nch2 = cdiv(4 * d.C, KCH4);
-  const dim3 grid(cdiv(cdiv(d.C, GT) * cdiv(4 * d.C, GT), 8) * 8), block(256);
+  const dim3 grid = gemm_grid(4 * d.C, d.C), block(256);
   auto first = [&]() -> hipError_t {
     if (scratch3 && fold_bf16x3_supported(d, mode3))
       return launch_fold_bf16x3(d, mode3, param_blob + o_wr, wmT, scratch3, pk_fold, g.nch1, g.nch2, st, pr3, pr, planes_fresh);   // klstm_fold3.hip
@@ -3370,8 +2939,7 @@ hipError_t launch_rbatch(const Dims &d, const FwdPtrs &p, float *out, int out_st
   g.C2 = out; g.ldc2 = out_stride;
   g.C3 = p.next_r; g.tail0 = M - d.S;
   g.guard = guard;
-  const dim3 grid(cdiv(cdiv(d.R, GT) * cdiv(M, GT), 8) * 8), block(256);
-  return launch((k_gemm<false, true>), grid, block, 0, st, pr, g);
+  return launch((k_gemm<false, true>), gemm_grid(M, d.R), dim3(256), 0, st, pr, g);
 }
 
 bool pack_supported(const Dims &d) { return d.R % 8 == 0 && d.I % 8 == 0 && d.C % 8 == 0; }
@@ -3406,33 +2974,17 @@ hipError_t launch_pack(const Dims &d, const float *param_blob, const float *wrT,
   return launch(k_pack, dim3((unsigned)(nb > 4096 ? 4096 : nb)), dim3(256), 0, st, pr, a);
 }
 
-static GemmJob make_job(bool transA, bool transB, int M, int N, int K, const float *A, int lda, const float *B,
-                        int ldb, float beta, float *Cm, int ldc, const float *bias) {
-  GemmJob g;
-  g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.beta = beta;
-  g.Cm = Cm; g.ldc = ldc; g.bias = bias;
-  g.Ct = nullptr; g.ldct = 0; g.C2 = nullptr; g.ldc2 = 0; g.C3 = nullptr; g.tail0 = 0;
-  g.gperm = 0; g.pk1 = nullptr; g.nch1 = 0; g.pk2 = nullptr; g.nch2 = 0;
-  g.P = nullptr; g.lr = 0.f; g.clip = 0.f; g.coal = 0; g.s3 = nullptr; g.s3pl = 0; g.s3t = 0; g.s3mode = 1;
-  // branch-free 8-wide fetches need aligned rows and a contiguous extent that is a multiple of 8
-  g.vecA = aligned16(A) && lda % 4 == 0 && (transA ? M : K) % 8 == 0;
-  g.vecB = aligned16(B) && ldb % 4 == 0 && (transB ? K : N) % 8 == 0;
-  return g;
-}
-
 hipError_t launch_gemm(bool transA, bool transB, int M, int N, int K, const float *A, int lda,
                        const float *B, int ldb, float beta, float *Cm, int ldc, const float *bias,
                        hipStream_t st, LaunchProbe pr) {
   const GemmJob g = make_job(transA, transB, M, N, K, A, lda, B, ldb, beta, Cm, ldc, bias);
-  const dim3 grid(cdiv(cdiv(N, GT) * cdiv(M, GT), 8) * 8), block(256);
+  const dim3 grid = gemm_grid(M, N), block(256);
   if (transA && transB) return launch((k_gemm<true, true>), grid, block, 0, st, pr, g);
   if (transA && !transB) return launch((k_gemm<true, false>), grid, block, 0, st, pr, g);
   if (!transA && transB) return launch((k_gemm<false, true>), grid, block, 0, st, pr, g);
   return launch((k_gemm<false, false>), grid, block, 0, st, pr, g);
 }
 
-// C = A B^T + bias with both operands rounded to bf16 (bf16 operand mode; M >= GRADS_BF16_MIN_ROWS rows, K >= 128 -- at K = 40 the
-// 64x64 fp32 tiles are faster: 9.8 vs 12.1 us at 640 x 4096 --, K % 8 == 0, 16-byte aligned rows)
 // C = beta C + add + A B^T with K split into ks slices of klen (a multiple of 64): the partial products go to ws ([ks][M x N] floats),
 // k_splitk_reduce adds them in slice order.  For few output tiles and a long K (640 x 512 over K = 4096: 40 tiles of 128 x 64 took 80 us).
 hipError_t launch_gemm_bf16_nt_splitk(int M, int N, int K, const float *A, int lda, const float *B, int ldb, float beta, float *Cm, int ldc,
@@ -3450,11 +3002,12 @@ hipError_t launch_gemm_bf16_nt_splitk(int M, int N, int K, const float *A, int l
   hipError_t err = first();
   if (err != hipSuccess) return err;
   ReduceArgs r;
-  r.ws = ws; r.ks = ks; r.M = M; r.N = N; r.beta = beta; r.Cm = Cm; r.ldc = ldc; r.bias = nullptr; r.add = add; r.add_ld = add_ld;
-  r.C2 = nullptr; r.ldc2 = 0; r.C3 = nullptr; r.tail0 = 0;
+  r.ws = ws; r.ks = ks; r.M = M; r.N = N; r.beta = beta; r.Cm = Cm; r.ldc = ldc; r.add = add; r.add_ld = add_ld;
   const long nb = ((long)M * N + 255) / 256;
   return launch(k_splitk_reduce, dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(256), 0, st, pr2, r);
 }
+// C = A B^T + bias with both operands rounded to bf16 (bf16 operand mode; M >= GRADS_BF16_MIN_ROWS rows, K >= 128 -- at K = 40 the
+// 64x64 fp32 tiles are faster: 9.8 vs 12.1 us at 640 x 4096 --, K % 8 == 0, 16-byte aligned rows)
 bool gemm_bf16_nt_supported(int M, int K, const float *A, int lda, const float *B, int ldb) {
   return M >= GRADS_BF16_MIN_ROWS && K >= 128 && K % 8 == 0 && lda % 4 == 0 && ldb % 4 == 0 && aligned16(A) && aligned16(B);
 }
@@ -3481,9 +3034,8 @@ hipError_t launch_gemm_bf16_nt(int M, int N, int K, const float *A, int lda, con
 hipError_t launch_gemm_tn_update(int M, int N, int K, const float *A, int lda, const float *B, int ldb, float beta, float *Cm,
                                  float *P, int ldc, float lr, hipStream_t st, LaunchProbe pr) {
   GemmJob g = make_job(true, false, M, N, K, A, lda, B, ldb, beta, Cm, ldc, nullptr);
-  g.P = P; g.lr = lr; g.clip = 0.f;
-  const dim3 grid(cdiv(cdiv(N, GT) * cdiv(M, GT), 8) * 8), block(256);
-  return launch((k_gemm<true, false>), grid, block, 0, st, pr, g);
+  g.P = P; g.lr = lr;
+  return launch((k_gemm<true, false>), gemm_grid(M, N), dim3(256), 0, st, pr, g);
 }
 
 // Cm = beta*Cm + A^T B through the coalesced epilogue (N, ldc % 4 == 0, 16-byte aligned Cm)
@@ -3491,8 +3043,7 @@ hipError_t launch_gemm_tn_coal(int M, int N, int K, const float *A, int lda, con
                                int ldc, hipStream_t st, LaunchProbe pr) {
   GemmJob g = make_job(true, false, M, N, K, A, lda, B, ldb, beta, Cm, ldc, nullptr);
   g.coal = 1;
-  const dim3 grid(cdiv(cdiv(N, GT) * cdiv(M, GT), 8) * 8), block(256);
-  return launch((k_gemm<true, false>), grid, block, 0, st, pr, g);
+  return launch((k_gemm<true, false>), gemm_grid(M, N), dim3(256), 0, st, pr, g);
 }
 
 // Split-K plan: worth it when the output tiles cover less than half the chip and K is long.
@@ -3556,8 +3107,8 @@ hipError_t launch_bwd_tail(const Dims &d, const float *dgifo, const float *wr, c
   hipError_t err = first();
   if (err != hipSuccess) return err;
   ReduceArgs r1, r2;
-  r1.ws = ws; r1.ks = ks; r1.M = M; r1.N = d.R; r1.beta = 0.f; r1.Cm = dr + (size_t)d.S * d.R; r1.ldc = d.R; r1.bias = nullptr;
-  r1.add = out_diff; r1.add_ld = od_stride; r1.C2 = nullptr; r1.ldc2 = 0; r1.C3 = nullptr; r1.tail0 = 0;
+  r1.ws = ws; r1.ks = ks; r1.M = M; r1.N = d.R; r1.beta = 0.f; r1.Cm = dr + (size_t)d.S * d.R; r1.ldc = d.R;
+  r1.add = out_diff; r1.add_ld = od_stride;
   r2 = r1;
   r2.ws = ws2; r2.N = d.I; r2.Cm = in_diff; r2.ldc = id_stride; r2.add = nullptr; r2.add_ld = 0;
   const int nbr1 = cdiv(M * d.R, 256), nbr2 = in_diff ? cdiv(M * d.I, 256) : 0;
@@ -3659,8 +3210,7 @@ hipError_t launch_update_repack(const Dims &d, float *param_blob, float *corr_bl
   a.off[1] = o_wr; a.rows[1] = 4 * C; a.cols[1] = R; a.dstT[1] = wrT;
   a.off[2] = o_wm; a.rows[2] = R;     a.cols[2] = C; a.dstT[2] = wmT;
   a.voff = o_b; a.vlen = 7 * C;
-  const bool vec = C % 4 == 0 && R % 4 == 0 && I % 4 == 0 && aligned16(param_blob) && aligned16(corr_blob) &&
-                   (!grad_blob || aligned16(grad_blob)) && aligned16(wrT) && aligned16(wmT) && aligned16(wxT);
+  const bool vec = update_repack_vectorised(d, param_blob, corr_blob, grad_blob, wrT, wmT, wxT);
   const int tsz = vec ? 64 : 32;
   int nb = 0;
   for (int i = 0; i < 3; i++) { a.tb[i] = nb; nb += cdiv(a.rows[i], tsz) * cdiv(a.cols[i], tsz); }
@@ -3672,87 +3222,6 @@ hipError_t launch_update_repack(const Dims &d, float *param_blob, float *corr_bl
   }
   if (vec) return launch(k_update_repack_v, dim3(nb), dim3(256), 0, st, pr, a);
   return launch(k_update_repack, dim3(nb), dim3(256), 0, st, pr, a);
-}
-
-hipError_t launch_time_shift(const float *in, int rows, int cols, int in_stride, float *out, int out_stride, int shift,
-                             hipStream_t st, LaunchProbe pr) {
-  const int vec = aligned16(in) && aligned16(out) && in_stride % 4 == 0 && out_stride % 4 == 0 && cols % 4 == 0;
-  const int per = vec ? 4 : 1;
-  return launch(k_time_shift, dim3(cdiv(cdiv(cols, per), 256), rows), dim3(256), 0, st, pr, in, rows, cols, in_stride, out, out_stride, shift, vec);
-}
-
-hipError_t launch_softmax(const float *in, int rows, int cols, int in_stride, float *out, int out_stride, hipStream_t st) {
-  LaunchProbe pr;
-  const bool wide = cols % 4 == 0 && cols <= 32768 && cols >= 2048 && in_stride % 4 == 0 && out_stride % 4 == 0 &&
-                    aligned16(in) && aligned16(out);
-  if (wide) return launch(k_softmax_rows_v, dim3(rows), dim3(1024), 0, st, pr, in, cols, in_stride, out, out_stride);
-  return launch(k_softmax_rows, dim3(rows), dim3(256), 0, st, pr, in, cols, in_stride, out, out_stride);
-}
-hipError_t launch_xent(const float *y, int rows, int cols, int stride, const int *target, const float *mask, float *diff,
-                       int diff_stride, float *row_xent, float *row_correct, hipStream_t st) {
-  LaunchProbe pr;
-  const bool wide = cols % 4 == 0 && cols <= 32768 && cols >= 2048 && stride % 4 == 0 && diff_stride % 4 == 0 &&
-                    aligned16(y) && aligned16(diff);
-  if (wide) return launch(k_xent_rows_v, dim3(rows), dim3(1024), 0, st, pr, y, cols, stride, target, mask, diff, diff_stride, row_xent, row_correct);
-  return launch(k_xent_rows, dim3(rows), dim3(256), 0, st, pr, y, cols, stride, target, mask, diff, diff_stride, row_xent, row_correct);
-}
-// one pass when the row fits the registers of 1024 threads (returns hipErrorNotSupported otherwise: the caller runs the pair)
-hipError_t launch_softmax_xent(const float *in, int rows, int cols, int in_stride, float *post, int post_stride, const int *target,
-                               const float *mask, float *diff, int diff_stride, float *row_xent, float *row_correct, double *totals,
-                               unsigned *ticket, hipStream_t st) {
-  LaunchProbe pr;
-  const bool wide = cols % 4 == 0 && cols <= 32768 && cols >= 2048 && in_stride % 4 == 0 && diff_stride % 4 == 0 && aligned16(in) &&
-                    aligned16(diff) && (!post || (post_stride % 4 == 0 && aligned16(post)));
-  if (!wide) return hipErrorNotSupported;
-  return launch(k_softmax_xent_rows_v, dim3(rows), dim3(1024), 0, st, pr, in, cols, in_stride, post, post_stride, target, mask, diff, diff_stride, row_xent, row_correct, totals, ticket);
-}
-hipError_t launch_xent_post(const float *y, int rows, int cols, int stride, const int *post_off, const int *post_pdf, const float *post_w,
-                            const float *mask, float *diff, int diff_stride, float *row_xent, float *row_ent, float *row_correct,
-                            hipStream_t st) {
-  LaunchProbe pr;
-  return launch(k_xent_post_rows, dim3(rows), dim3(256), 0, st, pr, y, cols, stride, post_off, post_pdf, post_w, mask, diff, diff_stride, row_xent, row_ent, row_correct);
-}
-// Loss statistics of a minibatch onto device totals (Xent::EvalMasked adds its three scalars to loss_, correct_, frames_ on the host,
-// nnet-loss.cc:136-141; a trainer that reports every N minibatches reads the totals once): totals[0] += sum row_xent (double),
-// totals[1] += sum row_correct, totals[2] += sum mask.  One workgroup, fixed summation order.
-__global__ __launch_bounds__(256) void k_xent_accumulate(const float *__restrict__ row_xent, const float *__restrict__ row_correct,
-                                                          const float *__restrict__ mask, int rows, double *totals) {
-  __shared__ double red[3][256];
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  for (int r = threadIdx.x; r < rows; r += 256) { s0 += (double)row_xent[r]; s1 += (double)row_correct[r]; s2 += (double)mask[r]; }
-  red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = s2;
-  __syncthreads();
-  for (int o = 128; o >= 1; o >>= 1) {
-    if ((int)threadIdx.x < o)
-#pragma unroll
-      for (int q = 0; q < 3; q++) red[q][threadIdx.x] += red[q][threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x < 3) totals[threadIdx.x] += red[threadIdx.x][0];
-}
-hipError_t launch_xent_accumulate(const float *row_xent, const float *row_correct, const float *mask, int rows, double *totals, hipStream_t st) {
-  LaunchProbe pr;
-  return launch(k_xent_accumulate, dim3(1), dim3(256), 0, st, pr, row_xent, row_correct, mask, rows, totals);
-}
-hipError_t launch_col_sum(const float *src, int rows, int cols, int stride, float beta, float *dst, hipStream_t st) {
-  LaunchProbe pr;
-  return launch(k_col_sum, dim3(cdiv(cols, 64)), dim3(256), 0, st, pr, src, rows, cols, stride, beta, dst);
-}
-static inline int ew_grid(long n);
-hipError_t launch_axpy(float *y, const float *x, float a, long n, hipStream_t st) {
-  LaunchProbe pr;
-  return launch(k_axpy, dim3(ew_grid(n)), dim3(256), 0, st, pr, y, x, a, n);
-}
-
-static inline int ew_grid(long n) { long g = (n + 255) / 256; return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g)); }
-
-hipError_t launch_sgd_momentum(float *param, float *corr, const float *grad, float mmt, float lr, long n, hipStream_t st) {
-  LaunchProbe pr;
-  return launch(k_sgd_momentum, dim3(ew_grid(n)), dim3(256), 0, st, pr, param, corr, grad, mmt, lr, n);
-}
-hipError_t launch_apply_momentum(float *corr, const float *grad, float mmt, long n, hipStream_t st, LaunchProbe pr, const unsigned *guard,
-                                 const float *mark) {
-  return launch(k_apply_momentum, dim3(ew_grid(n)), dim3(256), 0, st, pr, corr, grad, mmt, n, guard, mark);
 }
 
 }  // namespace klstm

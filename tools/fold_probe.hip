@@ -31,7 +31,7 @@ int main() {
   GemmJob g = make_job(false, true, 4 * C, C, R, wr, R, wmT, R, 0.f, nullptr, C, nullptr);
   g.gperm = C; g.pk1 = reinterpret_cast<float4 *>(pk[0]); g.nch1 = cdiv(C, KCH) + cdiv(I, KCH);
   g.pk2 = reinterpret_cast<float4 *>(pk[1]); g.nch2 = cdiv(4 * C, KCH4);
-  const dim3 grid(cdiv(cdiv(C, GT) * cdiv(4 * C, GT), 8) * 8), block(256);
+  const dim3 grid = gemm_grid(4 * C, C), block(256);
   for (int pad : {0, 14 * 1024, 24 * 1024, 42 * 1024}) {
     char nm[128]; snprintf(nm, sizeof nm, "packed epilogue, +%d KB LDS (=> %d workgroups per CU)", pad / 1024, 160 * 1024 / (40 * 1024 + pad));
     if (pad) CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, pad));
@@ -85,7 +85,7 @@ int main() {
   // fewer tiles: M = 2560 (40 x 13 = 520 tiles, ~2 per CU), M = 1216 (19 x 13 = 247 tiles, <= 1 per CU)
   for (int M : {1216, 2560, 3200}) {
     GemmJob q = make_job(false, true, M, C, R, wr, R, wmT, R, 0.f, out, C, nullptr);
-    const dim3 gq(cdiv(cdiv(C, GT) * cdiv(M, GT), 8) * 8);
+    const dim3 gq = gemm_grid(M, C);
     char nm[128]; snprintf(nm, sizeof nm, "plain epilogue, M = %d (%d tiles)", M, cdiv(C, GT) * cdiv(M, GT));
     time(nm, [&]() { hipLaunchKernelGGL((k_gemm<false, true>), gq, block, 0, st, q); });
   }
