@@ -18,6 +18,7 @@
 #include <string>
 
 #include "klstm_component.hpp"
+#include "klstm_dropout.h"
 #include "klstm_nlm.h"
 #include "klstm_trainer.hpp"
 
@@ -305,6 +306,82 @@ class SoftmaxLayer : public Layer {
   int32 in_, out_;
 };
 
+// [UPSTREAM-unvendored nnet-various.h] Dropout, the component the reference points at (nnet-nnet.h:98-99 declares
+// Nnet::SetDropoutRetention; its own "LSTM forward dropout" is commented out, bd-nnet-lstm-projected-streams.h:247-256): model line
+// "<Dropout> 512 512 <DropoutRetention> 0.8 ".  It stands BETWEEN layers -- the operator acts on what goes up, never on what goes
+// through time -- and runs kdrop_apply (klstm_dropout.h: the definition).  Only the retention is in the model file; the rest is
+// run-time state:
+//   active     OFF by default: the layer is a copy for every caller of Propagate that is not training (decoders, aligner, scorers)
+//   seed, salt the key and the layer's own word of the counter (Nnet::SetDropoutSeed gives component i salt i); SetSeed also winds
+//              the step and the sequence counter back to 0, so the same seed and the same calls replay the same masks bit for bit
+//   step       advances with every active PropagateFnc; BackpropagateFnc replays the counters of the last PropagateFnc
+//   per-sequence mode: one mask per (stream, sequence) for all its frames: a stream gets the next id of the layer's counter whenever
+//              Reset(flags) flags it; the ids go to the device only when they changed
+class DropoutLayer : public Layer {
+ public:
+  DropoutLayer(int32 i, int32 o) : dim_(i) { if (i != o) KLSTM_ERR("<Dropout>: input dim " << i << " != output dim " << o); }
+  const char *Marker() const override { return "<Dropout>"; }
+  int32 InputDim() const override { return dim_; }
+  int32 OutputDim() const override { return dim_; }
+  void ReadData(std::istream &is, bool binary) override {
+    ExpectToken(is, binary, "<DropoutRetention>");
+    BaseFloat r = 0;
+    ReadBasicType(is, binary, &r);
+    SetRetention(r);
+  }
+  void WriteData(std::ostream &os, bool binary) const override {
+    WriteToken(os, binary, "<DropoutRetention>");
+    WriteBasicType(os, binary, retention_);
+    if (!binary) os << "\n";
+  }
+  void SetRetention(BaseFloat r) {
+    unsigned thr; BaseFloat scale;
+    if (!(r > 0.f && r <= 1.f) || kdrop_threshold(r, &thr, &scale) != KLSTM_OK) KLSTM_ERR("<Dropout>: retention " << r << " outside (0, 1]");
+    retention_ = r;
+  }
+  BaseFloat Retention() const { return retention_; }
+  void SetActive(bool on) { active_ = on; }
+  bool Active() const { return active_; }
+  void SetSeed(uint64_t seed, uint32_t salt) {
+    if (salt >= 0x80000000u) KLSTM_ERR("<Dropout>: salt " << salt << " is not below 2^31");
+    seed_ = seed; salt_ = salt; step_ = last_step_ = 0; next_seq_ = 0; seq_ids_.clear(); ids_fresh_ = false;
+  }
+  void SetPerSequence(bool on) { per_sequence_ = on; }
+  bool PerSequence() const { return per_sequence_; }
+  uint32_t Step() const { return step_; }
+  void Reset(std::vector<int> &flags) override {
+    if (seq_ids_.size() != flags.size()) {                       // a new stream count: every stream starts a sequence
+      seq_ids_.resize(flags.size());
+      for (unsigned &id : seq_ids_) id = next_seq_++;
+      ids_fresh_ = false;
+      return;
+    }
+    for (size_t s = 0; s < flags.size(); s++) if (flags[s]) { seq_ids_[s] = next_seq_++; ids_fresh_ = false; }
+  }
+  void PropagateFnc(const MatrixView &in, MatrixView *out) override {
+    if (active_) last_step_ = step_++;
+    Apply(in, out);
+  }
+  void BackpropagateFnc(const MatrixView &, const MatrixView &, const MatrixView &od, MatrixView *id) override { if (id) Apply(od, id); }
+ private:
+  void Apply(const MatrixView &in, MatrixView *out) {
+    const bool seq = active_ && per_sequence_ && retention_ != 1.f;
+    if (seq) {
+      if (seq_ids_.empty()) KLSTM_ERR("<Dropout>: per-sequence masks need a Reset(flags) before the first Propagate");
+      if (!ids_fresh_) { ids_.Upload(seq_ids_); ids_fresh_ = true; }
+    }
+    KCheck(kdrop_apply(in.Data(), in.Stride(), in.NumRows(), dim_, out->Data(), out->Stride(), active_ ? retention_ : 1.f, seed_, last_step_,
+                       salt_, seq ? KDROP_SEQUENCE : KDROP_ELEMENT, seq ? (int)seq_ids_.size() : 1, seq ? ids_.As<unsigned>() : nullptr, nullptr));
+  }
+  int32 dim_;
+  BaseFloat retention_ = 1.f;
+  bool active_ = false, per_sequence_ = false, ids_fresh_ = false;
+  uint64_t seed_ = 0;
+  uint32_t salt_ = 0, step_ = 0, last_step_ = 0, next_seq_ = 0;
+  std::vector<unsigned> seq_ids_;
+  DeviceBuffer ids_;
+};
+
 class Nnet {                                  // google/nnet/nnet-nnet.h:36-150
  public:
   Nnet() {}
@@ -336,6 +413,7 @@ class Nnet {                                  // google/nnet/nnet-nnet.h:36-150
       else if (token == "<Transmit>") l = new TransmitLayer(dim_in, dim_out);
       else if (token == "<AffineTransform>") l = new AffineLayer(dim_in, dim_out);
       else if (token == "<Softmax>") l = new SoftmaxLayer(dim_in, dim_out);
+      else if (token == "<Dropout>") l = new DropoutLayer(dim_in, dim_out);
       else KLSTM_ERR("Unknown component marker " << token);
       std::unique_ptr<Layer> guard(l);
       l->ReadData(is, binary);
@@ -366,6 +444,24 @@ class Nnet {                                  // google/nnet/nnet-nnet.h:36-150
   }
   void SetSeqLengths(const std::vector<int32> &lens) {       // fan out to every component (a no-op for all but the bidirectional layer)
     for (auto &l : layers_) l->SetSeqLengths(lens);
+  }
+
+  // The <Dropout> components (klstm_dropout.h).  SetDropoutRetention is the reference's declared method (nnet-nnet.h:98-99): every
+  // <Dropout> takes r.  They are OFF until SetDropoutActive(true); SetDropoutSeed gives component i the salt i and winds the
+  // counters back (same seed, same calls: the same masks); SetDropoutPerSequence: one mask per (stream, sequence).
+  int32 NumDropout() const { int32 n = 0; for (const auto &l : layers_) n += Dropout(l.get()) != nullptr; return n; }
+  void SetDropoutRetention(BaseFloat r) { for (auto &l : layers_) if (DropoutLayer *d = Dropout(l.get())) d->SetRetention(r); }
+  void SetDropoutActive(bool on) { for (auto &l : layers_) if (DropoutLayer *d = Dropout(l.get())) d->SetActive(on); }
+  void SetDropoutSeed(uint64_t seed) { for (size_t i = 0; i < layers_.size(); i++) if (DropoutLayer *d = Dropout(layers_[i].get())) d->SetSeed(seed, (uint32_t)i); }
+  void SetDropoutPerSequence(bool on) { for (auto &l : layers_) if (DropoutLayer *d = Dropout(l.get())) d->SetPerSequence(on); }
+  std::vector<bool> DropoutActive() const {                 // of the <Dropout> components, in order
+    std::vector<bool> v;
+    for (const auto &l : layers_) if (const DropoutLayer *d = Dropout(l.get())) v.push_back(d->Active());
+    return v;
+  }
+  void SetDropoutActive(const std::vector<bool> &v) {
+    size_t k = 0;
+    for (auto &l : layers_) if (DropoutLayer *d = Dropout(l.get())) { if (k < v.size()) d->SetActive(v[k]); k++; }
   }
 
   // Nnet::Propagate [UPSTREAM]: each component's output buffer is (re)sized, then PropagateFnc.
@@ -405,10 +501,47 @@ class Nnet {                                  // google/nnet/nnet-nnet.h:36-150
     }
   }
  private:
+  static DropoutLayer *Dropout(Layer *l) { return std::string(l->Marker()) == "<Dropout>" ? static_cast<DropoutLayer *>(l) : nullptr; }
+  static const DropoutLayer *Dropout(const Layer *l) { return std::string(l->Marker()) == "<Dropout>" ? static_cast<const DropoutLayer *>(l) : nullptr; }
   std::vector<std::unique_ptr<Layer> > layers_;
   std::vector<std::unique_ptr<DeviceMatrix> > prop_, bprop_;
   MatrixView in0_;
   NnetTrainOptions opts_;
+};
+
+// The model as inference sees it: the <Dropout> components removed, the rest through the binary form (the result is what Nnet::Read
+// makes of that file).  A <Dropout> that is off is a copy, so both models compute the same; this one has the contiguous run of LSTM
+// layers that BatchScorer and CtcNeuralRescorer ask for.  Host only.
+inline void WithoutDropout(const Nnet &in, Nnet *out) {
+  std::stringstream ss;
+  WriteToken(ss, true, "<Nnet>");
+  for (int32 i = 0; i < in.NumComponents(); i++)
+    if (std::string(in.GetComponent(i).Marker()) != "<Dropout>") in.GetComponent(i).Write(ss, true);
+  WriteToken(ss, true, "</Nnet>");
+  out->Read(ss, true);
+}
+
+// What the four trainers do about dropout: for the scope's duration, and only when it trains (not under crossvalidate), the
+// <Dropout> components are switched on with the options' seed and mode (and retention, unless 0: the model's own); every exit path,
+// an exception included, puts the active flags back as they were.
+class DropoutTrainingScope {
+ public:
+  DropoutTrainingScope(Nnet *nnet, bool crossvalidate, BaseFloat retention, uint64_t seed, bool per_sequence)
+      : nnet_(nnet), on_(!crossvalidate && nnet->NumDropout() > 0) {
+    if (!on_) return;
+    was_ = nnet->DropoutActive();
+    if (retention != 0.f) nnet->SetDropoutRetention(retention);
+    nnet->SetDropoutSeed(seed);
+    nnet->SetDropoutPerSequence(per_sequence);
+    nnet->SetDropoutActive(true);
+  }
+  ~DropoutTrainingScope() { if (on_) nnet_->SetDropoutActive(was_); }
+  DropoutTrainingScope(const DropoutTrainingScope &) = delete;
+  DropoutTrainingScope &operator=(const DropoutTrainingScope &) = delete;
+ private:
+  Nnet *nnet_;
+  bool on_;
+  std::vector<bool> was_;
 };
 
 // Kaldi's Posterior (hmm/posterior.h [UPSTREAM-unvendored]; used as such in nnet-loss.cc:78): per frame a list of (pdf-id, weight)
@@ -491,6 +624,9 @@ struct TrainLstmStreamsOptions {              // bd-nnet-train-lstm-streams.cc:2
   NnetTrainOptions trn_opts;
   int32 targets_delay = 5, batch_size = 20, num_stream = 4;
   bool crossvalidate = false;
+  BaseFloat dropout_retention = 0.f;                     // the <Dropout> components while training (klstm_dropout.h): 0: the model's own retention
+  uint64_t dropout_seed = 0;                             // same seed, same data: the same masks, bit for bit; give every epoch its own
+  bool dropout_per_sequence = false;                     // one mask per (stream, sequence) instead of one per element and step
 };
 struct TrainLstmStreamsStats { int32 num_done = 0; double total_frames = 0, seconds = 0, avg_loss = 0, frame_accuracy = 0; int32 num_minibatches = 0; };
 
@@ -498,6 +634,7 @@ struct TrainLstmStreamsStats { int32 num_done = 0; double total_frames = 0, seco
 inline TrainLstmStreamsStats TrainLstmStreams(Nnet *nnet, const std::vector<Utterance> &utts, const TrainLstmStreamsOptions &o,
                                               std::string *report = nullptr) {
   nnet->SetTrainOptions(o.trn_opts);                                                  // :104
+  DropoutTrainingScope dropout(nnet, o.crossvalidate, o.dropout_retention, o.dropout_seed, o.dropout_per_sequence);
   MultiStreamBatcher batcher(&utts, o.num_stream, o.batch_size, o.targets_delay);
   Xent xent;
   StreamBatch b;
@@ -626,6 +763,9 @@ struct TrainCtcOptions {
   NnetTrainOptions trn_opts;
   int32 num_stream = 4, blank = 0, max_frames = 0;       // max_frames 0: 65535 / num_stream
   bool sort_by_length = true, crossvalidate = false;
+  BaseFloat dropout_retention = 0.f;                     // the <Dropout> components while training (klstm_dropout.h): 0: the model's own retention
+  uint64_t dropout_seed = 0;                             // same seed, same data: the same masks, bit for bit; give every epoch its own
+  bool dropout_per_sequence = false;                     // one mask per (stream, sequence) instead of one per element and step
 };
 struct TrainCtcStats {
   int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
@@ -667,6 +807,7 @@ template <class F>
 inline TrainCtcStats TrainCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const TrainCtcOptions &o, std::string *report,
                                              F every_batch) {
   nnet->SetTrainOptions(o.trn_opts);
+  DropoutTrainingScope dropout(nnet, o.crossvalidate, o.dropout_retention, o.dropout_seed, o.dropout_per_sequence);
   Ctc ctc(o.blank);
   DeviceMatrix obj_diff;
   TrainCtcStats st = ForEachWholeUtteranceBatch<TrainCtcStats>(nnet, utts, o.num_stream, o.sort_by_length, o.max_frames,
@@ -1531,15 +1672,16 @@ class CtcNeuralRescorer {
     if (o.num_stream < 1 || o.num_stream > 32 || o.chunk < 1) KLSTM_ERR("CtcNeuralRescorer: num_stream must be 1..32 and chunk >= 1");
     const int32 n = lm.NumComponents();
     auto marker = [&](int32 i) { return i < n ? std::string(lm.GetComponent(i).Marker()) : std::string("(end of the model)"); };
+    auto hint = [&](int32 i) { return marker(i) == "<Dropout>" ? " (pass the model through WithoutDropout first)" : ""; };
     int32 i = marker(0) == "<AffineTransform>" ? 1 : 0;
     const int32 b = i;
     while (marker(i) == "<LstmProjectedStreams>" || marker(i) == "<LstmProjected>") i++;
-    if (i == b) KLSTM_ERR("CtcNeuralRescorer: " << marker(i) << " at component " << i << " where an <LstmProjectedStreams> / <LstmProjected> belongs");
-    if (marker(i) != "<AffineTransform>") KLSTM_ERR("CtcNeuralRescorer: " << marker(i) << " at component " << i << " where the <AffineTransform> belongs");
+    if (i == b) KLSTM_ERR("CtcNeuralRescorer: " << marker(i) << " at component " << i << " where an <LstmProjectedStreams> / <LstmProjected> belongs" << hint(i));
+    if (marker(i) != "<AffineTransform>") KLSTM_ERR("CtcNeuralRescorer: " << marker(i) << " at component " << i << " where the <AffineTransform> belongs" << hint(i));
     const int32 e = i++;
     if (marker(i) == "<Softmax>") i++;
     if (i != n) KLSTM_ERR("CtcNeuralRescorer: " << marker(i) << " at component " << i << " is not supported (accepted: "
-                          "[<AffineTransform>] <LstmProjected[Streams]>... <AffineTransform> [<Softmax>])");
+                          "[<AffineTransform>] <LstmProjected[Streams]>... <AffineTransform> [<Softmax>])" << hint(i));
     const int32 V = lm.GetComponent(e).OutputDim(), K = o.num_classes > 0 ? o.num_classes : V;
     if (lm.GetComponent(0).InputDim() != V) KLSTM_ERR("CtcNeuralRescorer: the model reads " << lm.GetComponent(0).InputDim() << " classes and writes " << V);
     if (K < 2 || K > V || V > 32768 || o.bos < 0 || o.bos >= V || o.eos >= V)
@@ -1688,6 +1830,9 @@ struct TrainMbrOptions {
   const CtcLabelLm *lm = nullptr;                        // fused into the search; not owned
   std::vector<BaseFloat> class_weights;                  // empty: none
   int32 max_hyp_len = 0;                                 // 0: min(1023, 2 * longest reference + 8)
+  BaseFloat dropout_retention = 0.f;                     // the <Dropout> components while training (klstm_dropout.h): 0: the model's own retention
+  uint64_t dropout_seed = 0;                             // same seed, same data: the same masks, bit for bit; give every epoch its own
+  bool dropout_per_sequence = false;                     // one mask per (stream, sequence) instead of one per element and step
 };
 struct TrainMbrStats {
   int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
@@ -1702,6 +1847,7 @@ template <class F>
 inline TrainMbrStats TrainMbrWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const TrainMbrOptions &o, std::string *report,
                                              F every_batch) {
   nnet->SetTrainOptions(o.trn_opts);
+  DropoutTrainingScope dropout(nnet, o.crossvalidate, o.dropout_retention, o.dropout_seed, o.dropout_per_sequence);
   CtcBeamDecoder dec(o.blank, o.beam, o.cands, o.nbest);
   if (!o.class_weights.empty()) dec.SetClassWeights(o.class_weights);
   dec.SetLanguageModel(o.lm);
@@ -1798,6 +1944,9 @@ struct TrainMmiOptions {
   bool sort_by_length = true, crossvalidate = false;
   BaseFloat ctc_weight = 0.f;
   const CtcLabelLm *lm = nullptr;                        // the denominator's model (required); not owned
+  BaseFloat dropout_retention = 0.f;                     // the <Dropout> components while training (klstm_dropout.h): 0: the model's own retention
+  uint64_t dropout_seed = 0;                             // same seed, same data: the same masks, bit for bit; give every epoch its own
+  bool dropout_per_sequence = false;                     // one mask per (stream, sequence) instead of one per element and step
 };
 struct TrainMmiStats {
   int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
@@ -1812,6 +1961,7 @@ inline TrainMmiStats TrainMmiWholeUtterances(Nnet *nnet, const std::vector<Utter
                                              F every_batch) {
   KLSTM_ASSERT(o.lm);
   nnet->SetTrainOptions(o.trn_opts);
+  DropoutTrainingScope dropout(nnet, o.crossvalidate, o.dropout_retention, o.dropout_seed, o.dropout_per_sequence);
   CtcMmi mmi(o.blank, o.ctc_weight);
   mmi.SetLanguageModel(o.lm);
   DeviceMatrix obj_diff;

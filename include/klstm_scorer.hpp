@@ -21,7 +21,7 @@ namespace klstm_kaldi {
 
 // ---- FAQ Q1 as code: <Transmit> -> <TimeShift> <Shift> shift, <LstmProjectedStreams> -> <LstmProjected> (no <NumStream>),
 // parameters unchanged.  A model that does not begin with the <Transmit> (the shift would have nowhere to go), a <TimeShift> already in
-// the model, or a component other than these and <AffineTransform> / <Softmax>, is refused.  (The model is read through its binary form: the result is what Nnet::Read makes of the converted file.)
+// the model, or a component other than these and <AffineTransform> / <Softmax>, is refused; a <Dropout> is left out (WithoutDropout).  (The model is read through its binary form: the result is what Nnet::Read makes of the converted file.)
 inline void ConvertToStandard(const Nnet &in, int32 shift, Nnet *out) {
   if (in.NumComponents() == 0 || std::string(in.GetComponent(0).Marker()) != "<Transmit>")
     KLSTM_ERR("ConvertToStandard: the first component is " << (in.NumComponents() ? in.GetComponent(0).Marker() : "missing")
@@ -50,6 +50,7 @@ inline void ConvertToStandard(const Nnet &in, int32 shift, Nnet *out) {
       WriteMatrix(ss, true, q, R, C, C);
     } else if (m == "<AffineTransform>" || m == "<Softmax>") {
       l.Write(ss, true);
+    } else if (m == "<Dropout>") {                          // a copy at inference: dropped, as WithoutDropout drops it
     } else {
       KLSTM_ERR("ConvertToStandard: " << m << " at position " << i << " has no standard form here (the google model is "
                 "<Transmit> <LstmProjectedStreams>... <AffineTransform> <Softmax>)");
@@ -164,6 +165,7 @@ class BatchScorer {
     if (o.mode != KLSTM_SCORE_POSTERIOR && o.mode != KLSTM_SCORE_LOGPOST && o.mode != KLSTM_SCORE_LOGLIKE) KLSTM_ERR("BatchScorer: unknown mode");
     const int32 n = nnet.NumComponents();
     auto marker = [&](int32 i) { return i < n ? std::string(nnet.GetComponent(i).Marker()) : std::string("(end of the model)"); };
+    auto hint = [&](int32 i) { return marker(i) == "<Dropout>" ? " (pass the model through WithoutDropout first)" : ""; };
     int32 i = 0, shift = 0;
     if (marker(0) == "<TimeShift>") {
       shift = static_cast<const TimeShiftLayer &>(nnet.GetComponent(0)).Shift();
@@ -176,12 +178,12 @@ class BatchScorer {
     }
     const int32 b = i;
     while (marker(i) == "<LstmProjectedStreams>" || marker(i) == "<LstmProjected>") i++;
-    if (i == b) KLSTM_ERR("BatchScorer: " << marker(i) << " at component " << i << " where an <LstmProjectedStreams> / <LstmProjected> belongs");
-    if (marker(i) != "<AffineTransform>") KLSTM_ERR("BatchScorer: " << marker(i) << " at component " << i << " where the <AffineTransform> belongs");
+    if (i == b) KLSTM_ERR("BatchScorer: " << marker(i) << " at component " << i << " where an <LstmProjectedStreams> / <LstmProjected> belongs" << hint(i));
+    if (marker(i) != "<AffineTransform>") KLSTM_ERR("BatchScorer: " << marker(i) << " at component " << i << " where the <AffineTransform> belongs" << hint(i));
     const int32 e = i++;
     if (marker(i) == "<Softmax>") i++;
     if (i != n) KLSTM_ERR("BatchScorer: " << marker(i) << " at component " << i << " is not supported (accepted: "
-                          "[<Transmit>|<TimeShift>] <LstmProjected[Streams]>... <AffineTransform> [<Softmax>])");
+                          "[<Transmit>|<TimeShift>] <LstmProjected[Streams]>... <AffineTransform> [<Softmax>])" << hint(i));
     if (o.mode == KLSTM_SCORE_LOGLIKE && (int32)o.log_prior.size() != nnet.GetComponent(e).OutputDim())
       KLSTM_ERR("BatchScorer: log_prior needs " << nnet.GetComponent(e).OutputDim() << " values");
     if (lstm_begin) *lstm_begin = b;

@@ -162,6 +162,9 @@ def load_library():
     lib.knlm_workspace_bytes.restype = ctypes.c_size_t
     lib.knlm_score_rows.argtypes = [P, I, P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, P, P, P, ctypes.c_size_t, P]
     lib.knlm_rank.argtypes = [P, I, P, P, P, P, I, I, I, I, P, F, F, F, I, P, P, P, P, P, I, P, I, P, P, P, P, P, P]
+    # the kdrop_* family of include/klstm_dropout.h (dropout.py)
+    lib.kdrop_threshold.argtypes = [F, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_float)]
+    lib.kdrop_apply.argtypes = [P, I, I, I, P, I, F, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, I, I, P, P]
     _LIB = lib
     return lib
 
