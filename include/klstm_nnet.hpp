@@ -17,6 +17,7 @@
 #include <sstream>
 #include <string>
 
+#include "klstm_cnn.h"
 #include "klstm_component.hpp"
 #include "klstm_dropout.h"
 #include "klstm_nlm.h"
@@ -382,6 +383,193 @@ class DropoutLayer : public Layer {
   DeviceBuffer ids_;
 };
 
+// [UPSTREAM-unvendored nnet-convolutional-component.h] ConvolutionalComponent: the filters slide along the frequency axis of n spliced
+// blocks of st values (klstm_cnn.h: THE DEFINITION and the kcnn_conv_* entries; no im2col matrix exists at any point).  Model line
+// "<ConvolutionalComponent> 4224 440 <PatchDim> 8 <PatchStep> 1 <PatchStride> 40 <LearnRateCoef> 1 <BiasLearnRateCoef> 1 <MaxNorm> 0
+// <Filters>  [ F x K ] <Bias>  [ F ]": the tokens before <Filters> are read in any order and written in this one; <MaxNorm> is read,
+// kept and written as AffineLayer does.  Parameters keep a host shadow (files are read, written and converted without a GPU); the device
+// copy is created at the first PropagateFnc.  The update is the affine rule (klstm_affine_update): at momentum 0 what upstream does.
+class ConvolutionalLayer : public Layer {
+ public:
+  ConvolutionalLayer(int32 in, int32 out) : in_(in), out_(out) {}
+  ConvolutionalLayer(int32 in, int32 out, int32 patch_dim, int32 patch_step, int32 patch_stride) : in_(in), out_(out) { SetGeometry(patch_dim, patch_step, patch_stride); }
+  const char *Marker() const override { return "<ConvolutionalComponent>"; }
+  int32 InputDim() const override { return in_; }
+  int32 OutputDim() const override { return out_; }
+  bool IsUpdatable() const override { return true; }
+  int32 PatchDim() const { return pd_; }
+  int32 PatchStep() const { return ps_; }
+  int32 PatchStride() const { return st_; }
+  int32 NumPatches() const { return P_; }
+  int32 NumFilters() const { return F_; }
+  int32 FilterDim() const { return K_; }
+  void ReadData(std::istream &is, bool binary) override {
+    int32 pd = 0, ps = 0, st = 0;
+    while (true) {
+      std::string tok;
+      ReadToken(is, binary, &tok);
+      if (tok == "<Filters>") break;
+      if (tok == "<PatchDim>") ReadBasicType(is, binary, &pd);
+      else if (tok == "<PatchStep>") ReadBasicType(is, binary, &ps);
+      else if (tok == "<PatchStride>") ReadBasicType(is, binary, &st);
+      else if (tok == "<LearnRateCoef>") ReadBasicType(is, binary, &lr_coef_);
+      else if (tok == "<BiasLearnRateCoef>") ReadBasicType(is, binary, &bias_lr_coef_);
+      else if (tok == "<MaxNorm>") ReadBasicType(is, binary, &max_norm_);
+      else KLSTM_ERR("ConvolutionalComponent: unknown token " << tok);
+    }
+    SetGeometry(pd, ps, st);
+    std::vector<BaseFloat> w, b;
+    int32 r, c;
+    ReadMatrix(is, binary, &w, &r, &c);
+    ExpectToken(is, binary, "<Bias>");
+    ReadVector(is, binary, &b);
+    if (r != F_ || c != K_ || (int32)b.size() != F_)
+      KLSTM_ERR("ConvolutionalComponent: <Filters> " << r << " x " << c << ", <Bias> " << b.size() << " where " << F_ << " x " << K_ << " and " << F_ << " belong");
+    SetParams(w, b);
+  }
+  void WriteData(std::ostream &os, bool binary) const override {
+    std::vector<BaseFloat> w, b;
+    HostParams(&w, &b);
+    WriteToken(os, binary, "<PatchDim>"); WriteBasicType(os, binary, pd_);
+    WriteToken(os, binary, "<PatchStep>"); WriteBasicType(os, binary, ps_);
+    WriteToken(os, binary, "<PatchStride>"); WriteBasicType(os, binary, st_);
+    WriteToken(os, binary, "<LearnRateCoef>"); WriteBasicType(os, binary, lr_coef_);
+    WriteToken(os, binary, "<BiasLearnRateCoef>"); WriteBasicType(os, binary, bias_lr_coef_);
+    WriteToken(os, binary, "<MaxNorm>"); WriteBasicType(os, binary, max_norm_);
+    WriteToken(os, binary, "<Filters>");
+    WriteMatrix(os, binary, w.data(), F_, K_, K_);
+    WriteToken(os, binary, "<Bias>");
+    WriteVector(os, binary, b.data(), F_);
+  }
+  void SetParams(const std::vector<BaseFloat> &w, const std::vector<BaseFloat> &b) {       // filters F x K row-major, bias F
+    KLSTM_ASSERT(K_ > 0 && (int32)w.size() == F_ * K_ && (int32)b.size() == F_);
+    hw_ = w; hb_ = b; host_fresh_ = true;
+    if (on_device_) Upload();
+  }
+  void HostParams(std::vector<BaseFloat> *w, std::vector<BaseFloat> *b) const {
+    if (on_device_ && !host_fresh_) {
+      hw_.resize((size_t)F_ * K_); hb_.resize(F_);
+      W_.Download(hw_.data(), hw_.size());
+      b_.Download(hb_.data(), hb_.size());
+      host_fresh_ = true;
+    }
+    *w = hw_; *b = hb_;
+  }
+  int32 NumParams() const override { return F_ * K_ + F_; }
+  void GetParams(std::vector<BaseFloat> *p) const override {                                // filters, then bias
+    std::vector<BaseFloat> w, b; HostParams(&w, &b); *p = w; p->insert(p->end(), b.begin(), b.end());
+  }
+  void PropagateFnc(const MatrixView &in, MatrixView *out) override {
+    Alloc();
+    KCheck(kcnn_conv_propagate(in.Data(), in.Stride(), in.NumRows(), in_, out_, pd_, ps_, st_, W(), b(), out->Data(), out->Stride(), nullptr));
+  }
+  void BackpropagateFnc(const MatrixView &, const MatrixView &, const MatrixView &od, MatrixView *id) override {
+    if (id) KCheck(kcnn_conv_backpropagate(od.Data(), od.Stride(), od.NumRows(), in_, out_, pd_, ps_, st_, W(), id->Data(), id->Stride(), nullptr));
+  }
+  void Update(const MatrixView &input, const MatrixView &diff) override {
+    if (opts_.l2_penalty != 0.f || opts_.l1_penalty != 0.f) KLSTM_ERR("ConvolutionalComponent: l1/l2 penalties are not implemented");
+    const size_t need = kcnn_conv_workspace_floats(input.NumRows(), in_, out_, pd_, ps_, st_);
+    ws_.Grow(need * sizeof(BaseFloat));
+    KCheck(kcnn_conv_update(input.Data(), input.Stride(), diff.Data(), diff.Stride(), input.NumRows(), in_, out_, pd_, ps_, st_, W(), b(),
+                            Wc_.As<BaseFloat>(), bc_.As<BaseFloat>(), opts_.learn_rate * lr_coef_, opts_.learn_rate * bias_lr_coef_,
+                            opts_.momentum, ws_.As<BaseFloat>(), ws_.Capacity() / sizeof(BaseFloat), nullptr));
+    host_fresh_ = false;
+  }
+  void SetTrainOptions(const NnetTrainOptions &o) override { opts_ = o; }
+ private:
+  void SetGeometry(int32 pd, int32 ps, int32 st) {
+    int n, P, K, F;
+    if (kcnn_conv_plan(in_, out_, pd, ps, st, &n, &P, &K, &F) != KLSTM_OK) KLSTM_ERR("ConvolutionalComponent: " << klstm_last_error());
+    pd_ = pd; ps_ = ps; st_ = st; P_ = P; K_ = K; F_ = F;
+  }
+  void Alloc() {                          // on_device_ only once everything is there: a failure half way is tried again in full
+    if (on_device_) return;
+    Wc_.Grow((size_t)F_ * K_ * 4);
+    bc_.Grow((size_t)F_ * 4);
+    KCheck(klstm_memset_zero(Wc_.As<BaseFloat>(), (size_t)F_ * K_ * 4, nullptr));
+    KCheck(klstm_memset_zero(bc_.As<BaseFloat>(), (size_t)F_ * 4, nullptr));
+    Upload();
+    on_device_ = true;
+  }
+  void Upload() {
+    KLSTM_ASSERT((int32)hw_.size() == F_ * K_ && (int32)hb_.size() == F_);
+    W_.Upload(hw_);
+    b_.Upload(hb_);
+  }
+  BaseFloat *W() const { return W_.As<BaseFloat>(); }
+  BaseFloat *b() const { return b_.As<BaseFloat>(); }
+  int32 in_, out_, pd_ = 0, ps_ = 0, st_ = 0, P_ = 0, K_ = 0, F_ = 0;
+  BaseFloat lr_coef_ = 1.f, bias_lr_coef_ = 1.f, max_norm_ = 0.f;
+  NnetTrainOptions opts_;
+  DeviceBuffer W_, b_, Wc_, bc_, ws_;
+  bool on_device_ = false;
+  mutable std::vector<BaseFloat> hw_, hb_;
+  mutable bool host_fresh_ = true;
+};
+
+// [UPSTREAM-unvendored nnet-max-pooling-component.h] MaxPoolingComponent: the maximum over z neighbouring patches of w values (w = the
+// number of filters below), every g patches; model line "<MaxPoolingComponent> 1408 4224 <PoolSize> 3 <PoolStep> 3 <PoolStride> 128 ".
+// The backward pass is nnet1's rule (klstm_cnn.h): with overlapping pools it is not the true gradient of the maximum.
+class MaxPoolingLayer : public Layer {
+ public:
+  MaxPoolingLayer(int32 in, int32 out) : in_(in), out_(out) {}
+  MaxPoolingLayer(int32 in, int32 out, int32 size, int32 step, int32 stride) : in_(in), out_(out) { SetGeometry(size, step, stride); }
+  const char *Marker() const override { return "<MaxPoolingComponent>"; }
+  int32 InputDim() const override { return in_; }
+  int32 OutputDim() const override { return out_; }
+  int32 PoolSize() const { return z_; }
+  int32 PoolStep() const { return g_; }
+  int32 PoolStride() const { return w_; }
+  void ReadData(std::istream &is, bool binary) override {
+    int32 z = 0, g = 0, w = 0;
+    ExpectToken(is, binary, "<PoolSize>"); ReadBasicType(is, binary, &z);
+    ExpectToken(is, binary, "<PoolStep>"); ReadBasicType(is, binary, &g);
+    ExpectToken(is, binary, "<PoolStride>"); ReadBasicType(is, binary, &w);
+    SetGeometry(z, g, w);
+  }
+  void WriteData(std::ostream &os, bool binary) const override {
+    WriteToken(os, binary, "<PoolSize>"); WriteBasicType(os, binary, z_);
+    WriteToken(os, binary, "<PoolStep>"); WriteBasicType(os, binary, g_);
+    WriteToken(os, binary, "<PoolStride>"); WriteBasicType(os, binary, w_);
+    if (!binary) os << "\n";
+  }
+  void PropagateFnc(const MatrixView &in, MatrixView *out) override {
+    KCheck(kcnn_pool_propagate(in.Data(), in.Stride(), in.NumRows(), in_, out_, z_, g_, w_, out->Data(), out->Stride(), nullptr));
+  }
+  void BackpropagateFnc(const MatrixView &in, const MatrixView &out, const MatrixView &od, MatrixView *id) override {
+    if (id) KCheck(kcnn_pool_backpropagate(in.Data(), in.Stride(), out.Data(), out.Stride(), od.Data(), od.Stride(), in.NumRows(), in_, out_, z_, g_, w_,
+                                           id->Data(), id->Stride(), nullptr));
+  }
+ private:
+  void SetGeometry(int32 z, int32 g, int32 w) {
+    const bool ok = z >= 1 && g >= 1 && w >= 1 && in_ % w == 0 && z <= in_ / w && (int64_t)(1 + (in_ / w - z) / g) * w == out_;
+    if (!ok) KLSTM_ERR("MaxPoolingComponent: inconsistent numbers (in " << in_ << ", out " << out_ << ", pool size " << z << ", step " << g << ", stride " << w << ")");
+    z_ = z; g_ = g; w_ = w;
+  }
+  int32 in_, out_, z_ = 0, g_ = 0, w_ = 0;
+};
+
+// [UPSTREAM-unvendored nnet-activation.h] Sigmoid / Tanh between the layers: no data; the backward pass works from the OUTPUT
+// (in_diff = out_diff y (1 - y) or out_diff (1 - y y)); the forms of the LSTM cell (klstm_cnn.h).
+template <int KIND>
+class ActivationLayer : public Layer {
+ public:
+  ActivationLayer(int32 i, int32 o) : dim_(i) { if (i != o) KLSTM_ERR(Marker() << ": input dim " << i << " != output dim " << o); }
+  const char *Marker() const override { return KIND == KCNN_SIGMOID ? "<Sigmoid>" : "<Tanh>"; }
+  int32 InputDim() const override { return dim_; }
+  int32 OutputDim() const override { return dim_; }
+  void PropagateFnc(const MatrixView &in, MatrixView *out) override {
+    KCheck(kcnn_activation(KIND, in.Data(), in.Stride(), in.NumRows(), dim_, out->Data(), out->Stride(), nullptr));
+  }
+  void BackpropagateFnc(const MatrixView &, const MatrixView &out, const MatrixView &od, MatrixView *id) override {
+    if (id) KCheck(kcnn_activation_diff(KIND, out.Data(), out.Stride(), od.Data(), od.Stride(), out.NumRows(), dim_, id->Data(), id->Stride(), nullptr));
+  }
+ private:
+  int32 dim_;
+};
+typedef ActivationLayer<KCNN_SIGMOID> SigmoidLayer;
+typedef ActivationLayer<KCNN_TANH> TanhLayer;
+
 class Nnet {                                  // google/nnet/nnet-nnet.h:36-150
  public:
   Nnet() {}
@@ -414,6 +602,10 @@ class Nnet {                                  // google/nnet/nnet-nnet.h:36-150
       else if (token == "<AffineTransform>") l = new AffineLayer(dim_in, dim_out);
       else if (token == "<Softmax>") l = new SoftmaxLayer(dim_in, dim_out);
       else if (token == "<Dropout>") l = new DropoutLayer(dim_in, dim_out);
+      else if (token == "<ConvolutionalComponent>") l = new ConvolutionalLayer(dim_in, dim_out);
+      else if (token == "<MaxPoolingComponent>") l = new MaxPoolingLayer(dim_in, dim_out);
+      else if (token == "<Sigmoid>") l = new SigmoidLayer(dim_in, dim_out);
+      else if (token == "<Tanh>") l = new TanhLayer(dim_in, dim_out);
       else KLSTM_ERR("Unknown component marker " << token);
       std::unique_ptr<Layer> guard(l);
       l->ReadData(is, binary);

@@ -25,6 +25,8 @@ from .ctc import CtcWordTable, ctc_nbest_rescore, ctc_rescore_workspace_bytes  #
 from .ctc import CtcMmiDenominator, CtcMmiResult, ctc_mmi_eval, ctc_mmi_workspace_bytes  # noqa: F401,E402
 from .nlm import CtcNeuralLm, CtcNeuralRescoreResult, knlm_pack, knlm_rank, knlm_score_rows, knlm_workspace_bytes, lm_training_utterances  # noqa: F401,E402
 from .dropout import DROPOUT_ELEMENT, DROPOUT_SEQUENCE, Dropout, dropout_apply, dropout_threshold  # noqa: F401,E402
+from .cnn import (Convolutional, MaxPooling, Sigmoid, Tanh, activation, activation_diff, conv_backpropagate, conv_gradient,  # noqa: F401,E402
+                  conv_plan, conv_propagate, conv_update, conv_workspace_floats, pool_backpropagate, pool_propagate)
 from .lm import lexicon_label_lm, ngram_label_lm  # noqa: F401,E402
 from .lm import dense_lm_to_sparse, word_key, word_sequences, word_table  # noqa: F401,E402
 from .lm import SparseLm, arpa_label_lm, backoff_ngram_label_lm, sparse_lm_lookup, sparse_lm_to_dense, sparse_lm_validate  # noqa: F401,E402

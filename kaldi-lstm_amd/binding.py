@@ -165,6 +165,19 @@ def load_library():
     # the kdrop_* family of include/klstm_dropout.h (dropout.py)
     lib.kdrop_threshold.argtypes = [F, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_float)]
     lib.kdrop_apply.argtypes = [P, I, I, I, P, I, F, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, I, I, P, P]
+    # the kcnn_* family of include/klstm_cnn.h (cnn.py)
+    IP, Z = ctypes.POINTER(ctypes.c_int), ctypes.c_size_t
+    lib.kcnn_conv_plan.argtypes = [I, I, I, I, I, IP, IP, IP, IP]
+    lib.kcnn_conv_workspace_floats.argtypes = [I, I, I, I, I, I]
+    lib.kcnn_conv_workspace_floats.restype = Z
+    lib.kcnn_conv_propagate.argtypes = [P, I, I, I, I, I, I, I, P, P, P, I, P]
+    lib.kcnn_conv_backpropagate.argtypes = [P, I, I, I, I, I, I, I, P, P, I, P]
+    lib.kcnn_conv_gradient.argtypes = [P, I, P, I, I, I, I, I, I, I, P, P, P, Z, P]
+    lib.kcnn_conv_update.argtypes = [P, I, P, I, I, I, I, I, I, I, P, P, P, P, F, F, F, P, Z, P]
+    lib.kcnn_pool_propagate.argtypes = [P, I, I, I, I, I, I, I, P, I, P]
+    lib.kcnn_pool_backpropagate.argtypes = [P, I, P, I, P, I, I, I, I, I, I, I, P, I, P]
+    lib.kcnn_activation.argtypes = [I, P, I, I, I, P, I, P]
+    lib.kcnn_activation_diff.argtypes = [I, P, I, P, I, I, I, P, I, P]
     _LIB = lib
     return lib
 

@@ -13,9 +13,9 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = ["csrc/klstm_kernels.hip", "csrc/klstm_output.hip", "csrc/klstm_persist.hip", "csrc/klstm_persist_bwd.hip", "csrc/klstm_persist_ms.hip", "csrc/klstm_persist_xl.hip", "csrc/klstm_fold.hip", "csrc/klstm_fold3.hip", "csrc/klstm_oneshot.hip", "csrc/klstm_outer.hip", "csrc/klstm_gemm16.hip", "csrc/klstm_score.hip", "csrc/klstm_ctc.hip", "csrc/klstm_ctc_decode.hip", "csrc/klstm_ctc_align.hip", "csrc/klstm_ctc_beam.hip", "csrc/klstm_ctc_mbr.hip", "csrc/klstm_ctc_mmi.hip", "csrc/klstm_ctc_consensus.hip", "csrc/klstm_ctc_rescore.hip", "csrc/klstm_ctc_nlm.hip", "csrc/klstm_dropout.hip",
+SRCS = ["csrc/klstm_kernels.hip", "csrc/klstm_output.hip", "csrc/klstm_persist.hip", "csrc/klstm_persist_bwd.hip", "csrc/klstm_persist_ms.hip", "csrc/klstm_persist_xl.hip", "csrc/klstm_fold.hip", "csrc/klstm_fold3.hip", "csrc/klstm_oneshot.hip", "csrc/klstm_outer.hip", "csrc/klstm_gemm16.hip", "csrc/klstm_score.hip", "csrc/klstm_ctc.hip", "csrc/klstm_ctc_decode.hip", "csrc/klstm_ctc_align.hip", "csrc/klstm_ctc_beam.hip", "csrc/klstm_ctc_mbr.hip", "csrc/klstm_ctc_mmi.hip", "csrc/klstm_ctc_consensus.hip", "csrc/klstm_ctc_rescore.hip", "csrc/klstm_ctc_nlm.hip", "csrc/klstm_dropout.hip", "csrc/klstm_cnn.hip",
         "csrc/klstm_api_ops.hip", "csrc/klstm_api_ctc.hip", "csrc/klstm_comm.hip", "csrc/klstm_engine.hip"]
-HDRS = ["csrc/klstm_kernels.h", "csrc/klstm_host.h","csrc/klstm_math.h", "csrc/klstm_persist_dev.h", "csrc/klstm_ctc_dev.h", "csrc/klstm_ctc_host.h", "csrc/klstm_ctc_nbest.h", "csrc/klstm_ctc_beam_frame.h", "csrc/klstm_ctc_slm.h", "../include/klstm.h", "../include/klstm_nlm.h", "../include/klstm_dropout.h"]
+HDRS = ["csrc/klstm_kernels.h", "csrc/klstm_host.h","csrc/klstm_math.h", "csrc/klstm_persist_dev.h", "csrc/klstm_ctc_dev.h", "csrc/klstm_ctc_host.h", "csrc/klstm_ctc_nbest.h", "csrc/klstm_ctc_beam_frame.h", "csrc/klstm_ctc_slm.h", "../include/klstm.h", "../include/klstm_nlm.h", "../include/klstm_dropout.h", "../include/klstm_cnn.h"]
 LIB = os.path.join(HERE, "libklstm.so")
 OBJDIR = os.path.join(HERE, "build")
 STAMP = LIB + ".srchash"
