@@ -2,7 +2,7 @@
 //
 // The recurrence of ...streams.h substitutes r(t-1) = W_r_m m(t-1) (:312) into the gates pre-activation (:275):
 // W_gifo_r r(t-1) = (W_gifo_r W_r_m) m(t-1).  This product is the largest single piece of work outside the chain
-// (2.6 GFLOP at 800/512: 16.7 us at the fp32 MFMA peak), and the generic 64x64-tile kernel (klstm_kernels.hip k_gemm)
+// (2.6 GFLOP at 800/512: 16.7 us at the fp32 MFMA peak), and the generic 64x64-tile kernel (klstm_gemm.hip k_gemm)
 // loses a third of it to tile quantisation alone: 650 tiles over 256 CUs = 3 tiles on the slowest CU against 2.54 on
 // average, on top of a single-buffered LDS pipeline (tools/fold_probe.hip: 4.0 us per 64-wide K tile against 3.1 us for
 // three tiles' MFMAs).

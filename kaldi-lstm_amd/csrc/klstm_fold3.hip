@@ -22,7 +22,7 @@
 //
 //   k_split3        both operands -> three bf16 planes each (reads 8 MB, writes 12 MB, 4.5 us) -- only when the parameters changed
 //                   outside an Update (set_params ...): both Update kernels write the planes from the tile they have just updated
-//                   (klstm_kernels.hip: GradsUpdate::a3 / b3, bf16_split3_store4)
+//                   (klstm_grads.hip: GradsUpdate::a3 / b3, bf16_split3_store4)
 //   k_fold_bf16x3   128 x 96 tiles (2 x 2 MFMA waves of 64 x 48 = 4 x 3 MFMA blocks x 6 products), K in stages of 32:
 //                   one stage = 3 planes x (128 + 96) rows x 64 B = 42 KB, brought in by LDS-DMA
 //                   (global_load_lds_dwordx4: 16 rows x 64 B per wave instruction, no registers) issued by FOUR LOADER WAVES,

@@ -8,7 +8,7 @@
 //       d_r           out_diff + dgifo(2..T+1) W_gifo_r  :391                        640 x  512 over K = 4C
 //       in_diff       dgifo(1..T) W_gifo_x               :457                        640 x    I over K = 4C
 //
-// Round 4's kernel (k_gemm_bf16_nt, klstm_kernels.hip) ran these at 5 % of the bf16 matrix peak and 0.9 TB/s.  What was measured on the
+// Round 4's kernel (k_gemm_bf16_nt, klstm_grads.hip) ran these at 5 % of the bf16 matrix peak and 0.9 TB/s.  What was measured on the
 // way here (tools/gemm16_probe.py, tools/gemm16_anatomy.py = per-workgroup shader clocks of a TIMING instantiation; profiles/r05_gemm16_*.txt),
 // in the order it was tried, x-projection 640 x 4096 x 512 as the yardstick (round 4: 16.2 us):
 //   1. two register prefetch stages per workgroup instead of one: 19 us -- the compiler folds the stages' registers onto each other and

@@ -3,7 +3,7 @@
 // output layer 512 -> 16624 ([UPSTREAM] nnet-affine-transform.h, not vendored in the reference -- include/klstm.h, output tail:
 // linearity_corr = mmt * linearity_corr + out_diff^T in, bias_corr = mmt * bias_corr + column sums of out_diff).
 //
-// The product is 1.36 GFLOP writing 34 MB; the 64 x 64-tile fp32 kernel (klstm_kernels.hip k_gemm<true, false>) took 27 us for it
+// The product is 1.36 GFLOP writing 34 MB; the 64 x 64-tile fp32 kernel (klstm_gemm.hip k_gemm<true, false>) took 27 us for it
 // (+ 3 us for the column sums in a launch of their own): 2080 tiles whose 80-deep contraction is over before the loads of the tile
 // are amortised, and 10 us of fp32 MFMA issue on top.
 //

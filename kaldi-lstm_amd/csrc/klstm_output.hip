@@ -1,6 +1,6 @@
 // kaldi-lstm_amd/csrc/klstm_output.hip -- the output tail of the gfx950 kernels: time shift, softmax / cross-entropy
 // rows, column sums and the element-wise updates, then their launchers.  fp32 throughout (Kaldi BaseFloat).
-// (The per-step recurrence kernels, the tile GEMMs, gradients and Update: klstm_kernels.hip.)
+// (The per-step recurrence kernels: klstm_kernels.hip; the tile GEMMs: klstm_gemm.hip; gradients and Update: klstm_grads.hip.)
 #include "klstm_kernels.h"
 #include "klstm_math.h"
 

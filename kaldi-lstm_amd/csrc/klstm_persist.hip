@@ -318,7 +318,7 @@ __global__ __launch_bounds__(PNW * 64) void k_fwd_persist(PersistFwdArgs a) {
       float4 a0[MAXC], a1[MAXC];
       auto load_folded = [&]() {
         // ---- steps 2..T: resident folded rows [W_rm | W_x], k = 128*chunk + 64*h + 4*kg + e.  W_rm from the packed operand the
-        // fold product writes (klstm_kernels.hip: pk[tile][chunk32][h32][lane32][4], row = lane32 & 15,
+        // fold product writes (klstm_gemm_dev.h: pk[tile][chunk32][h32][lane32][4], row = lane32 & 15,
         // k = 32*chunk32 + 8*(lane32 >> 4) + 4*h32 + e), W_x from the natural W_gifo_x.
 #pragma unroll
         for (int i = 0; i < MAXC; i++) {

@@ -21,7 +21,7 @@ def sigmoid(x):
     return 1.0 / (1.0 + np.exp(-x))
 
 
-GRADS_BF16_MIN_ROWS = 256      # klstm_kernels.hip: the gradient products run on the bf16 pipe from this many frames on
+GRADS_BF16_MIN_ROWS = 256      # klstm_grads.hip: the gradient products run on the bf16 pipe from this many frames on
 
 
 def minibatch(parts, x, od, c0, r0, S, fuse_x, want_in_diff=True, fold=False, fold_bwd=False):

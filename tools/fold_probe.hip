@@ -1,9 +1,9 @@
 // tools/fold_probe.hip -- where do the 36 us of the fold product (W_rm = W_gifo_r W_r_m, 3200 x 800 x 512, fp32 MFMA) go?
-// Times the product kernel of klstm_kernels.hip under different residency limits (dynamic LDS padding) and epilogues.
-#include "../kaldi-lstm_amd/csrc/klstm_kernels.hip"
+// Times the product kernel of klstm_gemm.hip under different residency limits (dynamic LDS padding) and epilogues.
+#include "../kaldi-lstm_amd/csrc/klstm_gemm.hip"
 #define KLSTM_FOLD_TIMING
 #include "../kaldi-lstm_amd/csrc/klstm_fold.hip"
-#include "../kaldi-lstm_amd/csrc/klstm_fold3.hip"      // (launch_fold of klstm_kernels.hip dispatches to it)
+#include "../kaldi-lstm_amd/csrc/klstm_fold3.hip"      // (launch_fold of klstm_gemm.hip dispatches to it)
 #include <cstdio>
 #include <vector>
 #include <cmath>

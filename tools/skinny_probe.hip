@@ -1,6 +1,6 @@
 // tools/skinny_probe.hip -- where does k_skinny_nn (klstm_fold.hip: in_diff of the output layer, 80 x 512 x 16624) spend its time?
 // Per wave: shader clocks entry -> all loads issued -> MFMAs done -> exit.
-#include "../kaldi-lstm_amd/csrc/klstm_kernels.hip"
+#include "../kaldi-lstm_amd/csrc/klstm_gemm.hip"
 #include "../kaldi-lstm_amd/csrc/klstm_fold3.hip"
 #define KLSTM_SKINNY_TIMING
 #include "../kaldi-lstm_amd/csrc/klstm_fold.hip"
