@@ -21,6 +21,7 @@
 #include "klstm_component.hpp"
 #include "klstm_dropout.h"
 #include "klstm_nlm.h"
+#include "klstm_rnnt.h"
 #include "klstm_trainer.hpp"
 
 namespace klstm_kaldi {
@@ -1018,6 +1019,191 @@ inline TrainCtcStats TrainCtcWholeUtterances(Nnet *nnet, const std::vector<Utter
 inline TrainCtcStats TrainCtcWholeUtterances(Nnet *nnet, const std::vector<Utterance> &utts, const TrainCtcOptions &o,
                                              std::string *report = nullptr) {
   return TrainCtcWholeUtterances(nnet, utts, o, report, [](const UtteranceBatch &, const DeviceMatrix &, const DeviceMatrix &, const Ctc &) {});
+}
+
+// ---- RNN-transducer training (the krnnt_* entries of klstm_rnnt.h, which states the arithmetic) ----
+// The joint's output layer: W [V x J] and b [V] on the device with their momentum buffers and the gradient of the last Eval.  In a
+// model file it is an <AffineTransform> V J, so the file stays an nnet1 file; the host shadow makes I/O work without a GPU.
+class TransducerJoint {
+ public:
+  TransducerJoint(int32 joint_dim, int32 num_classes) : J_(joint_dim), V_(num_classes) {}
+  int32 JointDim() const { return J_; }
+  int32 NumClasses() const { return V_; }
+  void SetParams(const std::vector<BaseFloat> &w, const std::vector<BaseFloat> &b) {
+    KLSTM_ASSERT((int32)w.size() == V_ * J_ && (int32)b.size() == V_);
+    hw_ = w; hb_ = b;
+    if (on_device_) { W_.Upload(hw_); b_.Upload(hb_); }
+  }
+  void HostParams(std::vector<BaseFloat> *w, std::vector<BaseFloat> *b) const {
+    if (on_device_) { W_.Download(hw_.data(), hw_.size()); b_.Download(hb_.data(), hb_.size()); }
+    *w = hw_; *b = hb_;
+  }
+  void Read(std::istream &is, bool binary) {
+    std::string token;
+    ReadToken(is, binary, &token);
+    if (token != "<AffineTransform>") KLSTM_ERR("TransducerJoint: expected <AffineTransform>, got " << token);
+    int32 dim_out, dim_in;
+    ReadBasicType(is, binary, &dim_out);
+    ReadBasicType(is, binary, &dim_in);
+    AffineLayer aff(dim_in, dim_out);
+    aff.ReadData(is, binary);
+    std::vector<BaseFloat> w, b;
+    aff.HostParams(&w, &b);
+    J_ = dim_in; V_ = dim_out;
+    SetParams(w, b);
+  }
+  void Write(std::ostream &os, bool binary) const {
+    AffineLayer aff(J_, V_);
+    std::vector<BaseFloat> w, b;
+    HostParams(&w, &b);
+    aff.SetParams(w, b);
+    const std::streamsize was = os.precision(9);       // text: nine digits bring every float back bit for bit
+    aff.Write(os, binary);
+    os.precision(was);
+  }
+  void SetTrainOptions(const NnetTrainOptions &o) { opts_ = o; }
+  const BaseFloat *W() { Alloc(); return W_.As<BaseFloat>(); }
+  const BaseFloat *b() { Alloc(); return b_.As<BaseFloat>(); }
+  BaseFloat *WGrad() { Alloc(); return Wg_.As<BaseFloat>(); }       // written by Transducer::Eval
+  BaseFloat *bGrad() { Alloc(); return bg_.As<BaseFloat>(); }
+  void Update() {                                                     // corr = momentum corr + grad; param -= lr corr
+    Alloc();
+    KCheck(klstm_sgd_momentum_update(W_.As<BaseFloat>(), Wc_.As<BaseFloat>(), Wg_.As<BaseFloat>(), (long)V_ * J_, opts_.momentum, opts_.learn_rate, nullptr));
+    KCheck(klstm_sgd_momentum_update(b_.As<BaseFloat>(), bc_.As<BaseFloat>(), bg_.As<BaseFloat>(), (long)V_, opts_.momentum, opts_.learn_rate, nullptr));
+  }
+ private:
+  void Alloc() {
+    if (on_device_) return;
+    KLSTM_ASSERT((int32)hw_.size() == V_ * J_ && (int32)hb_.size() == V_);
+    const size_t nw = (size_t)V_ * J_ * sizeof(BaseFloat), nb = (size_t)V_ * sizeof(BaseFloat);
+    Wc_.Grow(nw); bc_.Grow(nb); Wg_.Grow(nw); bg_.Grow(nb);
+    KCheck(klstm_memset_zero(Wc_.As<BaseFloat>(), nw, nullptr));
+    KCheck(klstm_memset_zero(bc_.As<BaseFloat>(), nb, nullptr));
+    W_.Upload(hw_); b_.Upload(hb_);
+    on_device_ = true;
+  }
+  int32 J_, V_;
+  NnetTrainOptions opts_;
+  DeviceBuffer W_, b_, Wc_, bc_, Wg_, bg_;
+  bool on_device_ = false;
+  mutable std::vector<BaseFloat> hw_, hb_;
+};
+
+// The call holder of krnnt_pack / krnnt_eval: workspace, packed labels and the five totals on the device, like class Ctc.
+class Transducer : private CtcCallBase {
+ public:
+  explicit Transducer(int32 blank = 0) : CtcCallBase(blank) {}
+  // the prediction network's input: row u*S + s = the one-hot of x_u over V columns (x_0 = bos, x_u = y_u), zeros behind the labels
+  void Pack(int32 num_stream, const std::vector<std::vector<int32> > &labels, int32 V, int32 bos, DeviceMatrix *out) {
+    KLSTM_ASSERT((int32)labels.size() == num_stream);
+    lab_.Upload(labels);
+    out->Resize(((int32)lab_.longest + 1) * num_stream, V, false);
+    MatrixView ov = out->View();
+    KCheck(krnnt_pack(lab_.Labels(), lab_.Offsets(), num_stream, (int)lab_.longest, V, bos, nullptr, nullptr, 0, ov.Data(), ov.Stride(), nullptr));
+  }
+  // enc [T*S x J], pred [(Umax+1)*S x J] with Umax = the longest label list.  d_enc, d_pred (both or neither): the gradients, zero on
+  // the rows of idle and rejected streams; with them the joint's WGrad / bGrad are written.  Only the shape is checked here.
+  void Eval(const DeviceMatrix &enc, const DeviceMatrix &pred, int32 num_stream, const std::vector<int32> &lens,
+            const std::vector<std::vector<int32> > &labels, TransducerJoint *joint, DeviceMatrix *d_enc, DeviceMatrix *d_pred) {
+    const int32 *lens_dev = UploadLens(num_stream, lens);
+    const int32 T = NumFrames(enc, num_stream, lens_dev, labels.size(), false), J = joint->JointDim(), V = joint->NumClasses();
+    lab_.Upload(labels);
+    const int32 Umax = (int32)lab_.longest;
+    KLSTM_ASSERT(enc.NumCols() == J && pred.NumCols() == J && pred.NumRows() == (Umax + 1) * num_stream && (d_enc != nullptr) == (d_pred != nullptr));
+    const size_t need = krnnt_workspace_bytes(T, num_stream, Umax, J, V);
+    void *ws = Workspace(need);
+    loss_.Grow((size_t)num_stream * sizeof(BaseFloat));
+    MatrixView e = enc.View(), p = pred.View(), de, dp;
+    if (d_enc) {                                    // zeroed: the rows of a rejected stream are left alone by the call
+      d_enc->Resize(enc.NumRows(), J, true); d_pred->Resize(pred.NumRows(), J, true);
+      de = d_enc->View(); dp = d_pred->View();
+    }
+    KCheck(krnnt_eval(e.Data(), e.Stride(), p.Data(), p.Stride(), joint->W(), joint->b(), T, num_stream, Umax, J, V, lens_dev, lab_.Labels(),
+                      lab_.Offsets(), blank_, d_enc ? de.Data() : nullptr, d_enc ? de.Stride() : 0, d_enc ? dp.Data() : nullptr,
+                      d_enc ? dp.Stride() : 0, d_enc ? joint->WGrad() : nullptr, d_enc ? joint->bGrad() : nullptr, loss_.As<BaseFloat>(),
+                      tot_.Dev(), ws, need, nullptr));
+    num_stream_ = num_stream;
+  }
+  // -log p(labels | x) of the streams of the last Eval (0: idle or rejected).  Synchronises.
+  void UttLoss(std::vector<BaseFloat> *loss) const { loss->assign(num_stream_, 0.f); loss_.Download(loss->data(), loss->size()); }
+  double NumUtterances() const { const double *h = tot_.Read(); return h[3] - h[4]; }          // evaluated
+  double NumRejected() const { return tot_.Read()[4]; }
+  double Frames() const { return tot_.Read()[1]; }
+  double Labels() const { return tot_.Read()[2]; }
+  double AvgLoss() const { const double *h = tot_.Read(); return h[0] / (h[3] - h[4]); }
+  double AvgLossPerFrame() const { const double *h = tot_.Read(); return h[0] / h[1]; }
+  std::string Report() const {
+    const double *h = tot_.Read();
+    std::ostringstream oss;
+    oss << "AvgLoss: " << h[0] / (h[3] - h[4]) << " (Transducer) per utterance, " << h[0] / h[1] << " per frame, [" << h[3] - h[4]
+        << " utterances, " << h[1] << " frames, " << h[2] << " labels, " << h[4] << " rejected]" << std::endl;
+    return oss.str();
+  }
+ private:
+  PackedLabels lab_;
+  DeviceBuffer loss_;
+  DeviceTotals<5> tot_;
+};
+
+struct TrainTransducerOptions {
+  NnetTrainOptions trn_opts;
+  int32 num_stream = 4, blank = 0, bos = -1, max_frames = 0;   // bos -1: the blank's column starts the label history
+  bool sort_by_length = true, crossvalidate = false;
+  BaseFloat dropout_retention = 0.f;                     // as in TrainCtcOptions, for both networks
+  uint64_t dropout_seed = 0;
+  bool dropout_per_sequence = false;
+};
+struct TrainTransducerStats {
+  int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
+  double num_rejected = 0, total_frames = 0, total_labels = 0, seconds = 0, avg_loss = 0, avg_loss_per_frame = 0;
+};
+
+// One pass over the utterances.  Per minibatch of the whole-utterance batch loop: the encoder's Propagate (uni- or bidirectional, the
+// lengths set as the CTC trainer sets them), krnnt_pack, the predictor's Propagate (Umax + 1 steps from reset state over one-hot rows
+// of V columns: unidirectional layers only), krnnt_eval, both Backpropagates and the three Updates.  Both networks end at the joint's
+// width.  every_batch (optional) sees each minibatch after Transducer::Eval: (batch, enc_out, pred_out, transducer).
+template <class F>
+inline TrainTransducerStats TrainTransducerWholeUtterances(Nnet *encoder, Nnet *predictor, TransducerJoint *joint, const std::vector<Utterance> &utts,
+                                                           const TrainTransducerOptions &o, std::string *report, F every_batch) {
+  const int32 J = joint->JointDim(), V = joint->NumClasses();
+  if (encoder->OutputDim() != J || predictor->OutputDim() != J)
+    KLSTM_ERR("TrainTransducerWholeUtterances: encoder (" << encoder->OutputDim() << ") and predictor (" << predictor->OutputDim() << ") must end at the joint's width " << J);
+  if (predictor->InputDim() != V) KLSTM_ERR("TrainTransducerWholeUtterances: the predictor reads one-hot rows of " << V << " columns, its input dim is " << predictor->InputDim());
+  for (int32 i = 0; i < predictor->NumComponents(); i++)
+    if (std::string(predictor->GetComponent(i).Marker()) == "<BLstmProjectedStreams>")
+      KLSTM_ERR("TrainTransducerWholeUtterances: the predictor conditions on the label history: component " << i << " is bidirectional");
+  encoder->SetTrainOptions(o.trn_opts);
+  predictor->SetTrainOptions(o.trn_opts);
+  joint->SetTrainOptions(o.trn_opts);
+  DropoutTrainingScope drop_enc(encoder, o.crossvalidate, o.dropout_retention, o.dropout_seed, o.dropout_per_sequence);
+  DropoutTrainingScope drop_pred(predictor, o.crossvalidate, o.dropout_retention, o.dropout_seed + 1, o.dropout_per_sequence);
+  Transducer tr(o.blank);
+  DeviceMatrix pred_in, pred_out, d_enc, d_pred;
+  std::vector<int> all(o.num_stream, 1);
+  TrainTransducerStats st = ForEachWholeUtteranceBatch<TrainTransducerStats>(encoder, utts, o.num_stream, o.sort_by_length, o.max_frames,
+      [&](const UtteranceBatch &b, const DeviceMatrix &enc_out) {
+        tr.Pack(b.num_stream, b.labels, V, o.bos < 0 ? o.blank : o.bos, &pred_in);
+        predictor->Reset(all);
+        predictor->Propagate(pred_in.View(), &pred_out);
+        tr.Eval(enc_out, pred_out, b.num_stream, b.lens, b.labels, joint, o.crossvalidate ? nullptr : &d_enc, o.crossvalidate ? nullptr : &d_pred);
+        every_batch(b, enc_out, pred_out, tr);
+        if (o.crossvalidate) return;
+        encoder->Backpropagate(d_enc.View(), nullptr);
+        predictor->Backpropagate(d_pred.View(), nullptr);
+        joint->Update();
+      });
+  st.num_rejected = tr.NumRejected();
+  st.total_frames = tr.Frames();
+  st.total_labels = tr.Labels();
+  st.avg_loss = tr.AvgLoss();
+  st.avg_loss_per_frame = tr.AvgLossPerFrame();
+  if (report) *report = tr.Report();
+  return st;
+}
+inline TrainTransducerStats TrainTransducerWholeUtterances(Nnet *encoder, Nnet *predictor, TransducerJoint *joint, const std::vector<Utterance> &utts,
+                                                           const TrainTransducerOptions &o, std::string *report = nullptr) {
+  return TrainTransducerWholeUtterances(encoder, predictor, joint, utts, o, report,
+                                        [](const UtteranceBatch &, const DeviceMatrix &, const DeviceMatrix &, const Transducer &) {});
 }
 
 // CTC best-path decoding of whole utterances and the token error rate against reference label sequences (klstm_ctc_decode, klstm.h;

@@ -178,6 +178,14 @@ def load_library():
     lib.kcnn_pool_backpropagate.argtypes = [P, I, P, I, P, I, I, I, I, I, I, I, P, I, P]
     lib.kcnn_activation.argtypes = [I, P, I, I, I, P, I, P]
     lib.kcnn_activation_diff.argtypes = [I, P, I, P, I, I, I, P, I, P]
+    # the krnnt_* family of include/klstm_rnnt.h (rnnt.py)
+    lib.krnnt_grad_splits.argtypes = [I, I]
+    lib.krnnt_workspace_bytes.argtypes = [I, I, I, I, I]
+    lib.krnnt_workspace_bytes.restype = Z
+    lib.krnnt_forward_workspace_bytes.argtypes = [I, I, I]
+    lib.krnnt_forward_workspace_bytes.restype = Z
+    lib.krnnt_eval.argtypes = [P, I, P, I, P, P, I, I, I, I, I, P, P, P, I, P, I, P, I, P, P, P, P, P, Z, P]
+    lib.krnnt_pack.argtypes = [P, P, I, I, I, I, P, P, I, P, I, P]
     _LIB = lib
     return lib
 
