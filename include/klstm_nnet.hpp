@@ -2547,6 +2547,140 @@ inline DecodeCtcStats DecodeCtcWholeUtterances(Nnet *nnet, const std::vector<Utt
   return DecodeCtcWholeUtterances(nnet, utts, o, hypotheses, report, [](const UtteranceBatch &, const DeviceMatrix &, const CtcGreedyDecoder &) {});
 }
 
+// ---- Greedy RNN-transducer decoding (krnnt_greedy_begin / krnnt_greedy_step, klstm_rnnt.h, which states the search) ----
+struct TransducerHypothesis {
+  std::vector<int32> tokens, frames;               // the labels and the frame each was emitted at
+  BaseFloat score = 0.f;                           // log-probability of the greedy path
+  int32 flags = 0;                                 // klstm_rnnt.h: 1 finished, 2 truncated (max_len labels), 4 rejected, 8 idle
+};
+
+// The call holder of the two entries: it owns the state, the hypotheses and the predictor's next-input matrix.  Begin, then per step
+// the predictor's Propagate over NextInput() (S rows, its state carried from call to call) and Step; Results after at least one Step.
+class TransducerGreedy : private CtcCallBase {
+ public:
+  explicit TransducerGreedy(int32 blank = 0, int32 max_symbols = 10, int32 max_len = 255)
+      : CtcCallBase(blank), max_symbols_(max_symbols), max_len_(max_len) {}
+  void Begin(const DeviceMatrix &enc, int32 num_stream, const std::vector<int32> &lens, int32 V, int32 bos) {
+    const int32 *lens_dev = UploadLens(num_stream, lens);
+    T_ = NumFrames(enc, num_stream, lens_dev, 0, true); J_ = enc.NumCols(); V_ = V;
+    need_ = krnnt_greedy_state_bytes(T_, num_stream, J_);
+    state_ = Workspace(need_);
+    next_in_.Resize(num_stream, V, false);
+    const size_t n = (size_t)num_stream * sizeof(int32);
+    hyp_.Grow(n * max_len_); frames_.Grow(n * max_len_); len_.Grow(n); flags_.Grow(n); score_.Grow(n); live_.Grow(sizeof(int32));
+    MatrixView nv = next_in_.View();
+    KCheck(krnnt_greedy_begin(T_, num_stream, J_, V, bos, lens_dev, nullptr, nullptr, 0, nv.Data(), nv.Stride(), state_, need_, nullptr));
+    num_stream_ = num_stream;
+  }
+  const DeviceMatrix &NextInput() const { return next_in_; }
+  // pred_rows [S x J]: the predictor's output for NextInput(); one more label per live stream, NextInput() rewritten
+  void Step(const DeviceMatrix &enc, const DeviceMatrix &pred_rows, TransducerJoint *joint) {
+    KLSTM_ASSERT(enc.NumRows() == T_ * num_stream_ && enc.NumCols() == J_ && pred_rows.NumRows() == num_stream_ && pred_rows.NumCols() == J_ &&
+                 joint->JointDim() == J_ && joint->NumClasses() == V_);
+    MatrixView e = enc.View(), p = pred_rows.View(), nv = next_in_.View();
+    KCheck(krnnt_greedy_step(e.Data(), e.Stride(), p.Data(), p.Stride(), joint->W(), joint->b(), T_, num_stream_, J_, V_, blank_, max_symbols_,
+                             max_len_, nullptr, nullptr, 0, nv.Data(), nv.Stride(), hyp_.As<int32>(), len_.As<int32>(), frames_.As<int32>(),
+                             score_.As<BaseFloat>(), flags_.As<int32>(), live_.As<int32>(), state_, need_, nullptr));
+  }
+  int32 Live() const { int32 n = 0; live_.Download(&n, 1); return n; }        // the streams still decoding.  Synchronises.
+  void Results(std::vector<TransducerHypothesis> *out) const {                // per stream.  Synchronises.
+    const size_t S = num_stream_;
+    std::vector<int32> hyp(S * max_len_), frames(S * max_len_), len(S), flags(S);
+    std::vector<BaseFloat> score(S);
+    hyp_.Download(hyp.data(), hyp.size()); frames_.Download(frames.data(), frames.size()); len_.Download(len.data(), S);
+    flags_.Download(flags.data(), S); score_.Download(score.data(), S);
+    out->assign(S, TransducerHypothesis());
+    for (size_t s = 0; s < S; s++) {
+      TransducerHypothesis &h = (*out)[s];
+      h.tokens.assign(hyp.begin() + s * max_len_, hyp.begin() + s * max_len_ + len[s]);
+      h.frames.assign(frames.begin() + s * max_len_, frames.begin() + s * max_len_ + len[s]);
+      h.score = score[s]; h.flags = flags[s];
+    }
+  }
+  int32 MaxLen() const { return max_len_; }
+ private:
+  int32 max_symbols_, max_len_, T_ = 0, J_ = 0, V_ = 0;
+  size_t need_ = 0;
+  void *state_ = nullptr;
+  DeviceMatrix next_in_;
+  DeviceBuffer hyp_, frames_, len_, flags_, score_, live_;
+};
+
+struct DecodeTransducerOptions {
+  int32 num_stream = 4, blank = 0, bos = -1, max_frames = 0;   // bos -1: the blank's column starts the label history (as the trainer)
+  int32 max_symbols = 10, max_len = 255;                       // labels per frame, labels per utterance (then: truncated)
+  int32 poll_every = 8;                                        // the live count is read back every so many steps; 0: never (max_len + 1 steps)
+  bool sort_by_length = true;
+};
+struct DecodeTransducerStats {
+  int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
+  double seconds = 0;
+  int64_t num_utterances = 0, total_labels = 0, num_truncated = 0, num_rejected = 0, num_steps = 0;
+};
+
+// One pass over the utterances on the whole-utterance batch loop of the trainer.  Per minibatch: the encoder's Propagate, the
+// predictor reset, krnnt_greedy_begin, then per step the predictor's Propagate of S one-hot rows (its state carried by the engine
+// between the calls; every live stream emits exactly one label per step, so no stream ever holds its state) and krnnt_greedy_step.
+// (*hypotheses)[i] belongs to utts[i]; an utterance the batcher skipped keeps an empty one.  The networks are used as they are: a
+// <Dropout> that is switched on is refused.  every_batch (optional) sees each minibatch after its last step: (batch, enc_out, greedy).
+template <class F>
+inline DecodeTransducerStats DecodeTransducerWholeUtterances(Nnet *encoder, Nnet *predictor, TransducerJoint *joint, const std::vector<Utterance> &utts,
+                                                             const DecodeTransducerOptions &o, std::vector<TransducerHypothesis> *hypotheses,
+                                                             std::string *report, F every_batch) {
+  const int32 J = joint->JointDim(), V = joint->NumClasses();
+  if (encoder->OutputDim() != J || predictor->OutputDim() != J)
+    KLSTM_ERR("DecodeTransducerWholeUtterances: encoder (" << encoder->OutputDim() << ") and predictor (" << predictor->OutputDim() << ") must end at the joint's width " << J);
+  if (predictor->InputDim() != V) KLSTM_ERR("DecodeTransducerWholeUtterances: the predictor reads one-hot rows of " << V << " columns, its input dim is " << predictor->InputDim());
+  for (int32 i = 0; i < predictor->NumComponents(); i++)
+    if (std::string(predictor->GetComponent(i).Marker()) == "<BLstmProjectedStreams>")
+      KLSTM_ERR("DecodeTransducerWholeUtterances: the predictor conditions on the label history: component " << i << " is bidirectional");
+  for (Nnet *n : {encoder, predictor})
+    for (bool on : n->DropoutActive())
+      if (on) KLSTM_ERR("DecodeTransducerWholeUtterances: a <Dropout> component is switched on");
+  TransducerGreedy greedy(o.blank, o.max_symbols, o.max_len);
+  DeviceMatrix pred_out;
+  std::vector<int> all(o.num_stream, 1);
+  std::vector<TransducerHypothesis> hyps;
+  if (hypotheses) hypotheses->assign(utts.size(), TransducerHypothesis());
+  DecodeTransducerStats totals;
+  DecodeTransducerStats st = ForEachWholeUtteranceBatch<DecodeTransducerStats>(encoder, utts, o.num_stream, o.sort_by_length, o.max_frames,
+      [&](const UtteranceBatch &b, const DeviceMatrix &enc_out) {
+        greedy.Begin(enc_out, b.num_stream, b.lens, V, o.bos < 0 ? o.blank : o.bos);
+        predictor->Reset(all);
+        for (int32 step = 1; step <= o.max_len + 1; step++) {
+          predictor->Propagate(greedy.NextInput().View(), &pred_out);
+          greedy.Step(enc_out, pred_out, joint);
+          totals.num_steps++;
+          if (o.poll_every > 0 && step % o.poll_every == 0 && greedy.Live() == 0) break;
+        }
+        greedy.Results(&hyps);
+        for (int32 s = 0; s < b.num_stream; s++) {
+          if (b.utt_index[s] < 0) continue;
+          totals.num_utterances++;
+          totals.total_labels += (int64_t)hyps[s].tokens.size();
+          totals.num_truncated += (hyps[s].flags & 2) != 0;
+          totals.num_rejected += (hyps[s].flags & 4) != 0;
+        }
+        if (hypotheses) ScatterByUtterance(b, hyps, hypotheses);
+        every_batch(b, enc_out, greedy);
+      });
+  st.num_utterances = totals.num_utterances; st.total_labels = totals.total_labels; st.num_truncated = totals.num_truncated;
+  st.num_rejected = totals.num_rejected; st.num_steps = totals.num_steps;
+  if (report) {
+    std::ostringstream oss;
+    oss << "Greedy transducer decoding: [" << st.num_utterances << " utterances, " << st.total_labels << " labels, " << st.num_truncated
+        << " truncated, " << st.num_rejected << " rejected, " << st.num_steps << " steps]" << std::endl;
+    *report = oss.str();
+  }
+  return st;
+}
+inline DecodeTransducerStats DecodeTransducerWholeUtterances(Nnet *encoder, Nnet *predictor, TransducerJoint *joint, const std::vector<Utterance> &utts,
+                                                             const DecodeTransducerOptions &o, std::vector<TransducerHypothesis> *hypotheses,
+                                                             std::string *report = nullptr) {
+  return DecodeTransducerWholeUtterances(encoder, predictor, joint, utts, o, hypotheses, report,
+                                         [](const UtteranceBatch &, const DeviceMatrix &, const TransducerGreedy &) {});
+}
+
 // CTC forced alignment of whole utterances: the most probable alignment of each stream's labels to its frames (klstm_ctc_align,
 // klstm.h).  The five totals stay on the device and are read when somebody asks, like Ctc's.
 class CtcAligner : private CtcCallBase {

@@ -82,6 +82,54 @@ klstm_status krnnt_eval(const float *enc, int enc_stride, const float *pred, int
 klstm_status krnnt_pack(const int *labels_dev, const int *label_offsets_dev, int S, int Umax, int V, int bos, const float *embed,
                         const float *embed_bias, int D, float *out, int out_stride, void *hip_stream);
 
+/* GREEDY (BEST-PATH) DECODING, label-synchronous (the torch yardstick: tests/rnnt_greedy_ref.py).
+ * Plain greedy search per stream, with h, a, lse as in THE DEFINITION above:
+ *     t = 0, u = 0, n = 0, score = 0
+ *     while t < T_s:   k = argmax_v a_v(t, u)                              (`>` decides: a tie goes to the lower class)
+ *         k == blank:  score += a_blank - lse ; t += 1 ; n = 0
+ *         otherwise:   score += a_k - lse ; append (k, t) ; u += 1 ; n += 1 ; stop (truncated) when u == max_len ;
+ *                      n == max_symbols: t += 1 ; n = 0                    (at most max_symbols labels per frame, no blank is scored)
+ * The node (t, u) depends on enc[t] and on the predictor after bos, y_1 .. y_u only, so the walk along t at a fixed u needs one
+ * predictor row: krnnt_greedy_step is step u of ALL streams together.  Every live stream has emitted u labels; pred_rows row s is its
+ * predictor output; all its frames from t_s on are scanned against that row in parallel (16 frames per matrix tile); the first frame
+ * whose argmax is not blank gives label u + 1 and its time, the frames before it are the blank steps of the path and the frames behind
+ * it are discarded.  A stream without a hit up to T_s is finished.  So the loop is
+ *     krnnt_greedy_begin(...)                          next_in = the rows of bos
+ *     repeat up to max_len + 1 times:  pred_rows = predictor(next_in), one row per stream, its state carried from call to call
+ *                                      krnnt_greedy_step(...)             next_in = the rows of the labels just emitted
+ * and the predictor advances for all live streams at once: no stream ever has to hold its state.  U + 1 dependent steps instead of
+ * T + U.  Tokens, frames and score are those of the plain loop: only nodes on the greedy path reach them.
+ *
+ * next_in [S x width]: row s is the predictor's next input, written as krnnt_pack writes a row (one-hot over V columns, or with embed
+ * [D x V] the gathered column plus bias over D); zeros for a stream that is not live.  hyp_dev / frame_dev [S][max_len]: labels and
+ * their frames (frame_dev may be NULL); hyp_len_dev [S]; score_dev [S]: the path's log-probability so far, summed in double (blank
+ * terms in frame order, each label's term behind the blanks before it) and given as a float; a finished stream's score includes the
+ * blanks up to T_s, a truncated stream's ends with its last label.  flags_dev [S]: bit 0 finished, bit 1 truncated (max_len labels),
+ * bit 2 rejected (T_s < 0 or T_s > T: no labels, score 0), bit 3 idle (T_s = 0); 0: live.  live_dev: one int, the streams still live.
+ * A step after every stream has stopped launches workgroups that leave at once and rewrites the same outputs.
+ *
+ * state: krnnt_greedy_state_bytes(T, S, J) bytes (0 and a message beyond the limits), 256-byte aligned, private to the decode between
+ * begin and the last step, which must give the same T, S, J: per stream the flags, T_s, t_s, the symbols at the current frame, the
+ * length, the score in double and hit_chunk; per (stream, chunk of 64 frames, 32 for J > 512) one record: hit frame or -1, label, the
+ * label's log-probability, and the sum of log p(blank) over the chunk's frames before the hit.  hit_chunk is lowered with an integer
+ * atomicMin by a chunk that has a hit, and a workgroup that starts later and sees a lower chunk there leaves without work: its record
+ * would never be read, so the result does not depend on that race.  No floating-point atomics; runs are bit-identical and a stream's
+ * tokens, frames and score do not depend on its company.
+ *
+ * LIMITS: those of krnnt_eval on S, T (T S <= 2^24), J, V and blank; bos in [0, V); 1 <= max_len <= 1023; 1 <= max_symbols; D >= 1 with
+ * embed: KLSTM_ERR_SHAPE.  A null required pointer, a row stride below the row, a pointer that is not 4-byte aligned, a state that is
+ * too small or not 256-byte aligned: KLSTM_ERR_ARG with the outputs untouched.  Every check runs before the first HIP call; everything
+ * is asynchronous on hip_stream; nothing is read back. */
+size_t krnnt_greedy_state_bytes(int T, int S, int J);
+
+klstm_status krnnt_greedy_begin(int T, int S, int J, int V, int bos, const int *lens_dev, const float *embed, const float *embed_bias, int D,
+                                float *next_in, int next_in_stride, void *state, size_t state_bytes, void *hip_stream);
+
+klstm_status krnnt_greedy_step(const float *enc, int enc_stride, const float *pred_rows, int pred_stride, const float *W, const float *b, int T,
+                               int S, int J, int V, int blank, int max_symbols, int max_len, const float *embed, const float *embed_bias, int D,
+                               float *next_in, int next_in_stride, int *hyp_dev, int *hyp_len_dev, int *frame_dev, float *score_dev,
+                               int *flags_dev, int *live_dev, void *state, size_t state_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@
 // logits W h + b of a lattice node ever go to memory: both exist only in registers, in the forward pass and again in the backward pass.
 //   k_rnnt_prep       one thread per stream: status (1 runs, 0 idle, -1 rejected), T_s, U_s and the label offset, for every kernel behind it.
 //   k_rnnt_joint_fwd  a workgroup (4 waves) owns KRNNT_TILE_T x KRNNT_TILE_U = 16 x 8 nodes of one stream: the 16 enc rows and the 8 pred
-//                     rows go to LDS once; a wave owns two M-tiles (16 t at one u each).  joint_logits(): h is formed in registers as the A
+//                     rows go to LDS once; a wave owns two M-tiles (16 t at one u each).  joint_logits() (klstm_rnnt_dev.h, shared
+//                     with the decoder, klstm_rnnt_decode.hip): h is formed in registers as the A
 //                     operand of MFMA16 (lane (i, kg) computes tanh for row i, column k0 + kg: exactly the element it feeds), taken once
 //                     per k-step and used against all of the pass's class tiles (up to KRNNT_PASS_V = 128 classes, 8 accumulator tiles per
 //                     M-tile); W streams through LDS in panels of 32 k shared by the four waves, stored [class][k] with a row stride of 34
@@ -42,14 +43,13 @@
 #include "klstm_host.h"
 #include "klstm_kernels.h"
 #include "klstm_math.h"
+#include "klstm_rnnt_dev.h"
 
 namespace klstm {
 
-constexpr int RT = KRNNT_TILE_T, RU = KRNNT_TILE_U, VP = KRNNT_PASS_V, NVT = VP / 16;
-constexpr int KP = 32, WPS = KP + 2;        // k per W panel, floats per panel row
+constexpr int RU = KRNNT_TILE_U;            // (RT, VP, NVT, KP, WPS and RLOG0: klstm_rnnt_dev.h)
 constexpr int BU = 4, GS = VP + 2;          // u per backward step (one per wave), floats per row of the g tile
 constexpr int ESLOTS = 4;                   // d_enc partial slots = waves of the backward workgroup
-constexpr float RLOG0 = -1e30f;
 
 struct RnntWs {
   int4 *meta; double *loss, *offs;
@@ -107,69 +107,6 @@ __global__ __launch_bounds__(64) void k_rnnt_prep(RnntArgs a) {
       if (y < 0 || y >= a.V || y == a.blank) { st = -1; break; }
     }
   a.ws.meta[s] = make_int4(st, st == 1 ? Ts : 0, st == 1 ? U : 0, o0);
-}
-
-// rows row0 .. row0 + nrows - 1 of stream s (row r of the matrix: (row0 + r) S + s) into dst [nrows][Jp]; rows from nvalid on: zeros
-__device__ __forceinline__ void rnnt_stage(float *dst, int Jp, const float *src, int stride, int row0, int nrows, int nvalid, int S, int s, int J) {
-  for (int e = threadIdx.x; e < nrows * J; e += blockDim.x) {
-    const int r = e / J, c = e - r * J;
-    dst[r * Jp + c] = r < nvalid ? src[((size_t)(row0 + r) * S + s) * stride + c] : 0.f;
-  }
-}
-
-__device__ __forceinline__ float red16_max(float x) {
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) x = fmaxf(x, __shfl_xor(x, o));
-  return x;
-}
-__device__ __forceinline__ float red16_sum(float x) {
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
-// The logits (without bias) of MT M-tiles of 16 nodes against the classes v0 .. v0 + 16 nvt - 1: acc[m][vt] in the C layout (row 4 kg + j,
-// class 16 vt + i16).  encL [16][Jp]: the M-tiles' enc rows; pl[m]: the pred row of M-tile m.  Called by all 256 threads together.
-template <int MT>
-__device__ __forceinline__ void joint_logits(const float *encL, int Jp, const float *const (&pl)[MT], const float *__restrict__ W, int J, int V,
-                                             int v0, int nvt, float *Wp, f32x4 (&acc)[MT][NVT]) {
-  const int tid = threadIdx.x, lane = tid & 63, i16 = lane & 15, kg = lane >> 4;
-#pragma unroll
-  for (int m = 0; m < MT; m++)
-#pragma unroll
-    for (int vt = 0; vt < NVT; vt++) acc[m][vt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kp = 0; kp < J; kp += KP) {
-    const int kw = min(KP, J - kp);
-    __syncthreads();                                   // the panel before is done with (and the caller's LDS stores are visible)
-    for (int e = tid; e < nvt * 16 * KP; e += 256) {
-      const int v = e / KP, k = e - v * KP;
-      Wp[v * WPS + k] = (v0 + v < V && k < kw) ? W[(size_t)(v0 + v) * J + kp + k] : 0.f;
-    }
-    __syncthreads();
-    f32x4 part[MT][NVT];
-#pragma unroll
-    for (int m = 0; m < MT; m++)
-#pragma unroll
-      for (int vt = 0; vt < NVT; vt++) part[m][vt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int ks = 0; ks < kw; ks += 4) {
-      const int k = kp + ks + kg;
-      float h[MT];
-#pragma unroll
-      for (int m = 0; m < MT; m++) h[m] = k_tanh(encL[i16 * Jp + k] + pl[m][k]);
-#pragma unroll
-      for (int vt = 0; vt < NVT; vt++)
-        if (vt < nvt) {
-          const float bv = Wp[(vt * 16 + i16) * WPS + ks + kg];
-#pragma unroll
-          for (int m = 0; m < MT; m++) part[m][vt] = MFMA16(h[m], bv, part[m][vt]);
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < MT; m++)
-#pragma unroll
-      for (int vt = 0; vt < NVT; vt++)
-        if (vt < nvt) acc[m][vt] += part[m][vt];
-  }
 }
 
 __global__ __launch_bounds__(256) void k_rnnt_joint_fwd(RnntArgs a) {

@@ -1,0 +1,79 @@
+// kaldi-lstm_amd/csrc/klstm_rnnt_dev.h -- device code shared by the transducer sources (klstm_rnnt.hip: training; klstm_rnnt_decode.hip:
+// greedy decoding): the tile constants, the staging of rows into LDS, the 16-lane reductions of a node's row and joint_logits(), the
+// product W tanh(enc[t] + pred[u]) of M-tiles of 16 nodes in MFMA registers (klstm_rnnt.hip's head describes its layout).  Both sources
+// are compiled with the same flags (build.py EXTRA_FLAGS), so the logits of a node are the same bits in training and in decoding.
+#pragma once
+#include "../../include/klstm_rnnt.h"
+#include "klstm_kernels.h"
+#include "klstm_math.h"
+
+namespace klstm {
+
+constexpr int RT = KRNNT_TILE_T, VP = KRNNT_PASS_V, NVT = VP / 16;
+constexpr int KP = 32, WPS = KP + 2;        // k per W panel, floats per panel row
+constexpr float RLOG0 = -1e30f;
+
+// rows row0 .. row0 + nrows - 1 of stream s (row r of the matrix: (row0 + r) S + s) into dst [nrows][Jp]; rows from nvalid on: zeros
+__device__ __forceinline__ void rnnt_stage(float *dst, int Jp, const float *src, int stride, int row0, int nrows, int nvalid, int S, int s, int J) {
+  for (int e = threadIdx.x; e < nrows * J; e += blockDim.x) {
+    const int r = e / J, c = e - r * J;
+    dst[r * Jp + c] = r < nvalid ? src[((size_t)(row0 + r) * S + s) * stride + c] : 0.f;
+  }
+}
+
+__device__ __forceinline__ float red16_max(float x) {
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) x = fmaxf(x, __shfl_xor(x, o));
+  return x;
+}
+__device__ __forceinline__ float red16_sum(float x) {
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) x += __shfl_xor(x, o);
+  return x;
+}
+
+// The logits (without bias) of MT M-tiles of 16 nodes against the classes v0 .. v0 + 16 nvt - 1: acc[m][vt] in the C layout (row 4 kg + j,
+// class 16 vt + i16).  encL [16][Jp]: the M-tiles' enc rows; pl[m]: the pred row of M-tile m.  Called by all 256 threads together.
+template <int MT>
+__device__ __forceinline__ void joint_logits(const float *encL, int Jp, const float *const (&pl)[MT], const float *__restrict__ W, int J, int V,
+                                             int v0, int nvt, float *Wp, f32x4 (&acc)[MT][NVT]) {
+  const int tid = threadIdx.x, lane = tid & 63, i16 = lane & 15, kg = lane >> 4;
+#pragma unroll
+  for (int m = 0; m < MT; m++)
+#pragma unroll
+    for (int vt = 0; vt < NVT; vt++) acc[m][vt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kp = 0; kp < J; kp += KP) {
+    const int kw = min(KP, J - kp);
+    __syncthreads();                                   // the panel before is done with (and the caller's LDS stores are visible)
+    for (int e = tid; e < nvt * 16 * KP; e += 256) {
+      const int v = e / KP, k = e - v * KP;
+      Wp[v * WPS + k] = (v0 + v < V && k < kw) ? W[(size_t)(v0 + v) * J + kp + k] : 0.f;
+    }
+    __syncthreads();
+    f32x4 part[MT][NVT];
+#pragma unroll
+    for (int m = 0; m < MT; m++)
+#pragma unroll
+      for (int vt = 0; vt < NVT; vt++) part[m][vt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ks = 0; ks < kw; ks += 4) {
+      const int k = kp + ks + kg;
+      float h[MT];
+#pragma unroll
+      for (int m = 0; m < MT; m++) h[m] = k_tanh(encL[i16 * Jp + k] + pl[m][k]);
+#pragma unroll
+      for (int vt = 0; vt < NVT; vt++)
+        if (vt < nvt) {
+          const float bv = Wp[(vt * 16 + i16) * WPS + ks + kg];
+#pragma unroll
+          for (int m = 0; m < MT; m++) part[m][vt] = MFMA16(h[m], bv, part[m][vt]);
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MT; m++)
+#pragma unroll
+      for (int vt = 0; vt < NVT; vt++)
+        if (vt < nvt) acc[m][vt] += part[m][vt];
+  }
+}
+
+}  // namespace klstm

@@ -1,5 +1,5 @@
-"""RNN-transducer training on torch CUDA tensors: the krnnt_* entries of include/klstm_rnnt.h (which defines every quantity;
-INTEGRATION.md 3r; the torch yardstick: tests/rnnt_ref.py).  Plumbing only, no arithmetic: the label lists become the CSR arrays of the
+"""RNN-transducer training and greedy decoding on torch CUDA tensors: the krnnt_* entries of include/klstm_rnnt.h (which defines every
+quantity; the torch yardsticks: tests/rnnt_ref.py, tests/rnnt_greedy_ref.py).  Plumbing only, no arithmetic: the label lists become the CSR arrays of the
 C-ABI through ctc.py's helpers, the workspace is cached per shape; without the library or a GPU the calls raise."""
 import ctypes
 
@@ -85,3 +85,69 @@ def rnnt_pack(labels, S, V, bos, embed=None, bias=None, Umax=None, device="cuda"
     _chk(load_library().krnnt_pack(lab_dev.data_ptr(), off_dev.data_ptr(), int(S), Umax, int(V), int(bos), _ptr(embed), _ptr(bias), D,
                                    out.data_ptr(), out.stride(0), _sp(stream)))
     return out
+
+
+def rnnt_greedy_state_bytes(T, S, J):
+    """bytes of state krnnt_greedy_begin / krnnt_greedy_step need (include/klstm_rnnt.h: per stream and per chunk of frames)"""
+    return _workspace_bytes("krnnt_greedy_state_bytes", T, S, J)
+
+
+def _embedding(embed, bias, V):
+    import torch
+    if embed is None:
+        return 0
+    assert embed.is_cuda and embed.dtype == torch.float32 and embed.is_contiguous() and embed.dim() == 2 and embed.shape[1] == V
+    assert bias is None or (bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == embed.shape[0])
+    return embed.shape[0]
+
+
+def rnnt_greedy_begin(T, S, J, V, bos, lens_dev, next_in, state, embed=None, bias=None, stream=None):
+    """Start a greedy decode of S streams (lens_dev: int32 CUDA lengths): the state is reset and next_in [S, V or D] gets the rows of bos."""
+    D = _embedding(embed, bias, V)
+    _chk(load_library().krnnt_greedy_begin(int(T), int(S), int(J), int(V), int(bos), lens_dev.data_ptr(), _ptr(embed), _ptr(bias), D,
+                                           _rows(next_in).data_ptr(), next_in.stride(0), state.data_ptr(), ctypes.c_size_t(state.numel()), _sp(stream)))
+
+
+def rnnt_greedy_step(enc, pred_rows, W, b, T, S, blank, max_symbols, next_in, hyp, hyp_len, frames, score, flags, live, state,
+                     embed=None, bias=None, stream=None):
+    """Step u of all streams: pred_rows [S, J] are the predictor's outputs for next_in; one more label (hyp / frames [S, max_len] int32,
+    hyp_len [S]) per live stream, score [S] float32, flags [S] and live [1] int32 updated, next_in rewritten.  Nothing synchronises."""
+    J, V = _rows(enc).shape[1], W.shape[0]
+    _rows(pred_rows, J)
+    D = _embedding(embed, bias, V)
+    _chk(load_library().krnnt_greedy_step(enc.data_ptr(), enc.stride(0), pred_rows.data_ptr(), pred_rows.stride(0), W.data_ptr(), b.data_ptr(),
+                                          int(T), int(S), J, V, int(blank), int(max_symbols), hyp.shape[1], _ptr(embed), _ptr(bias), D,
+                                          _rows(next_in).data_ptr(), next_in.stride(0), hyp.data_ptr(), hyp_len.data_ptr(), _ptr(frames),
+                                          score.data_ptr(), flags.data_ptr(), live.data_ptr(), state.data_ptr(), ctypes.c_size_t(state.numel()),
+                                          _sp(stream)))
+
+
+def rnnt_greedy_decode(enc, lens, W, b, predictor, bos, blank=0, max_symbols=10, max_len=255, embed=None, bias=None, poll_every=8,
+                       stream=None):
+    """Greedy transducer decoding of enc [T*S, J] (row t*S + s; lens: S lengths).  predictor: a callable from the next-input rows
+    [S, V] (one-hot; [S, D] with embed [D, V]) to [S, J] float32 CUDA rows that carries its own state from call to call and starts
+    from reset state.  At most max_len + 1 steps; the number of live streams is read back every poll_every steps (0: never).
+    Returns a dict: tokens, frames (S lists), score [S] float32, flags [S] int32 (klstm_rnnt.h), steps."""
+    import torch
+    dev = enc.device
+    assert W.is_cuda and W.dtype == torch.float32 and W.is_contiguous() and b.is_cuda and b.dtype == torch.float32 and b.is_contiguous()
+    lens_dev = lens if isinstance(lens, torch.Tensor) and lens.is_cuda else torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
+    assert lens_dev.dtype == torch.int32 and lens_dev.is_contiguous()
+    S, (V, J) = lens_dev.numel(), W.shape
+    assert S > 0 and enc.shape[0] % S == 0 and enc.shape[1] == J and b.numel() == V
+    T = enc.shape[0] // S
+    nbytes = rnnt_greedy_state_bytes(T, S, J)
+    state = _workspace("rnnt_greedy", (T, S, J), nbytes, dev)[:nbytes]
+    ints = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+    next_in = torch.empty(S, embed.shape[0] if embed is not None else V, device=dev)
+    hyp, frames, hyp_len, flags, live, score = ints(S, max_len), ints(S, max_len), ints(S), ints(S), ints(1), torch.zeros(S, device=dev)
+    rnnt_greedy_begin(T, S, J, V, bos, lens_dev, next_in, state, embed, bias, stream)
+    steps = 0
+    while steps < max_len + 1:
+        rnnt_greedy_step(enc, predictor(next_in), W, b, T, S, blank, max_symbols, next_in, hyp, hyp_len, frames, score, flags, live, state,
+                         embed, bias, stream)
+        steps += 1
+        if poll_every and steps % poll_every == 0 and int(live) == 0:
+            break
+    n, h, f = hyp_len.tolist(), hyp.tolist(), frames.tolist()
+    return dict(tokens=[h[s][:n[s]] for s in range(S)], frames=[f[s][:n[s]] for s in range(S)], score=score, flags=flags, steps=steps)
