@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "klstm.h"
+#include "klstm_rnnt.h"
 #include "klstm_kaldi_io.hpp"
 
 namespace klstm_kaldi {
@@ -192,6 +193,12 @@ class LstmProjectedStreams {
     KLSTM_ASSERT(nstream_ == (int32)stream_reset_flag.size());   // :214
     EnsureEngine();
     Check(klstm_reset(eng_, stream_reset_flag.data(), (int)stream_reset_flag.size()));
+  }
+  // stream i takes the carried state of stream src_dev[i] (nstream_ ints on the device; -1: zero state), without a host round trip
+  // (krnnt_gather_state of klstm_rnnt.h: a transducer beam search reorders its predictor this way between two label steps)
+  void GatherStreams(const int32 *src_dev) {
+    EnsureEngine();
+    Check(krnnt_gather_state(eng_, src_dev));
   }
 
   // PropagateFnc, ...streams.h:222-332.  in/out hold device pointers (a CuMatrix with the GPU enabled) or host pointers.

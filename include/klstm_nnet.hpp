@@ -132,6 +132,7 @@ class Layer {
   virtual void SetUpdateFollows(bool) {}                     // Nnet::Backpropagate: Update comes right behind BackpropagateFnc
   virtual void SetTrainOptions(const NnetTrainOptions &) {}
   virtual void Reset(std::vector<int> &) {}                  // the overlay adds Reset to every Component (nnet-nnet.h:133-137)
+  virtual void GatherStreams(const int32 *) {}               // carried state of stream i <- stream src_dev[i] (krnnt_gather_state); stateless: nothing
   virtual void SetSeqLengths(const std::vector<int32> &) {}   // per-utterance lengths (nnet1's name; the bidirectional layer, klstm_blstm.hpp)
   virtual int32 NumParams() const { return 0; }
   virtual void GetParams(std::vector<BaseFloat> *p) const { p->clear(); }
@@ -160,6 +161,7 @@ class LstmLayer : public Layer {            // LstmProjectedStreams / LstmProjec
   void SetUpdateFollows(bool v) override { c_->SetUpdateFollows(v); }
   void SetTrainOptions(const NnetTrainOptions &o) override { c_->SetTrainOptions(o); }
   void Reset(std::vector<int> &f) override { if (std::string(c_->Marker()) == "<LstmProjectedStreams>") c_->Reset(f); }
+  void GatherStreams(const int32 *src_dev) override { if (std::string(c_->Marker()) == "<LstmProjectedStreams>") c_->GatherStreams(src_dev); }
   int32 NumParams() const override { return c_->NumParams(); }
   void GetParams(std::vector<BaseFloat> *p) const override { c_->GetParams(p); }
   LstmProjectedStreams *Impl() { return c_.get(); }
@@ -634,6 +636,9 @@ class Nnet {                                  // google/nnet/nnet-nnet.h:36-150
   void SetTrainOptions(const NnetTrainOptions &o) { opts_ = o; for (auto &l : layers_) l->SetTrainOptions(o); }
   void Reset(std::vector<int> &stream_reset_flag) {          // nnet-nnet.h:132-138: fan out to EVERY component
     for (auto &l : layers_) l->Reset(stream_reset_flag);
+  }
+  void GatherStreams(const int32 *src_dev) {                 // every recurrent layer reorders its streams on the device
+    for (auto &l : layers_) l->GatherStreams(src_dev);
   }
   void SetSeqLengths(const std::vector<int32> &lens) {       // fan out to every component (a no-op for all but the bidirectional layer)
     for (auto &l : layers_) l->SetSeqLengths(lens);
@@ -2618,6 +2623,20 @@ struct DecodeTransducerStats {
   int64_t num_utterances = 0, total_labels = 0, num_truncated = 0, num_rejected = 0, num_steps = 0;
 };
 
+// what both transducer decoders refuse before the first minibatch
+inline void RefuseTransducerDecode(const char *who, Nnet *encoder, Nnet *predictor, TransducerJoint *joint) {
+  const int32 J = joint->JointDim(), V = joint->NumClasses();
+  if (encoder->OutputDim() != J || predictor->OutputDim() != J)
+    KLSTM_ERR(who << ": encoder (" << encoder->OutputDim() << ") and predictor (" << predictor->OutputDim() << ") must end at the joint's width " << J);
+  if (predictor->InputDim() != V) KLSTM_ERR(who << ": the predictor reads one-hot rows of " << V << " columns, its input dim is " << predictor->InputDim());
+  for (int32 i = 0; i < predictor->NumComponents(); i++)
+    if (std::string(predictor->GetComponent(i).Marker()) == "<BLstmProjectedStreams>")
+      KLSTM_ERR(who << ": the predictor conditions on the label history: component " << i << " is bidirectional");
+  for (Nnet *n : {encoder, predictor})
+    for (bool on : n->DropoutActive())
+      if (on) KLSTM_ERR(who << ": a <Dropout> component is switched on");
+}
+
 // One pass over the utterances on the whole-utterance batch loop of the trainer.  Per minibatch: the encoder's Propagate, the
 // predictor reset, krnnt_greedy_begin, then per step the predictor's Propagate of S one-hot rows (its state carried by the engine
 // between the calls; every live stream emits exactly one label per step, so no stream ever holds its state) and krnnt_greedy_step.
@@ -2627,16 +2646,8 @@ template <class F>
 inline DecodeTransducerStats DecodeTransducerWholeUtterances(Nnet *encoder, Nnet *predictor, TransducerJoint *joint, const std::vector<Utterance> &utts,
                                                              const DecodeTransducerOptions &o, std::vector<TransducerHypothesis> *hypotheses,
                                                              std::string *report, F every_batch) {
-  const int32 J = joint->JointDim(), V = joint->NumClasses();
-  if (encoder->OutputDim() != J || predictor->OutputDim() != J)
-    KLSTM_ERR("DecodeTransducerWholeUtterances: encoder (" << encoder->OutputDim() << ") and predictor (" << predictor->OutputDim() << ") must end at the joint's width " << J);
-  if (predictor->InputDim() != V) KLSTM_ERR("DecodeTransducerWholeUtterances: the predictor reads one-hot rows of " << V << " columns, its input dim is " << predictor->InputDim());
-  for (int32 i = 0; i < predictor->NumComponents(); i++)
-    if (std::string(predictor->GetComponent(i).Marker()) == "<BLstmProjectedStreams>")
-      KLSTM_ERR("DecodeTransducerWholeUtterances: the predictor conditions on the label history: component " << i << " is bidirectional");
-  for (Nnet *n : {encoder, predictor})
-    for (bool on : n->DropoutActive())
-      if (on) KLSTM_ERR("DecodeTransducerWholeUtterances: a <Dropout> component is switched on");
+  const int32 V = joint->NumClasses();
+  RefuseTransducerDecode("DecodeTransducerWholeUtterances", encoder, predictor, joint);
   TransducerGreedy greedy(o.blank, o.max_symbols, o.max_len);
   DeviceMatrix pred_out;
   std::vector<int> all(o.num_stream, 1);
@@ -2679,6 +2690,151 @@ inline DecodeTransducerStats DecodeTransducerWholeUtterances(Nnet *encoder, Nnet
                                                              std::string *report = nullptr) {
   return DecodeTransducerWholeUtterances(encoder, predictor, joint, utts, o, hypotheses, report,
                                          [](const UtteranceBatch &, const DeviceMatrix &, const TransducerGreedy &) {});
+}
+
+// ---- Transducer beam search with n-best lists (krnnt_beam_begin / krnnt_beam_step, klstm_rnnt.h, which states the search) ----
+// The call holder: it owns the state, the lists, the parents and the predictor's next-input matrix of S * beam rows (row s * beam + b:
+// slot b of stream s).  Begin, then per step the predictor's GatherStreams(Parents()), its Propagate over NextInput() and Step;
+// Results after at least one Step.
+class TransducerBeam : private CtcCallBase {
+ public:
+  explicit TransducerBeam(int32 blank = 0, int32 beam = 4, int32 nbest = 4, int32 max_len = 255)
+      : CtcCallBase(blank), beam_(beam), nbest_(nbest), max_len_(max_len) {}
+  void Begin(const DeviceMatrix &enc, int32 num_stream, const std::vector<int32> &lens, int32 V, int32 bos) {
+    const int32 *lens_dev = UploadLens(num_stream, lens);
+    T_ = NumFrames(enc, num_stream, lens_dev, 0, true); J_ = enc.NumCols(); V_ = V;
+    need_ = krnnt_beam_state_bytes(T_, num_stream, beam_, J_, V);
+    state_ = Workspace(need_);
+    KLSTM_ASSERT(nbest_ >= 1 && max_len_ >= 1);
+    next_in_.Resize(num_stream * beam_, V, false);
+    const size_t n = (size_t)num_stream * sizeof(int32);
+    parents_.Grow(n * beam_); hyp_.Grow(n * nbest_ * max_len_); len_.Grow(n * nbest_); score_.Grow(n * nbest_); count_.Grow(n); flags_.Grow(n);
+    live_.Grow(sizeof(int32));
+    MatrixView nv = next_in_.View();
+    KCheck(krnnt_beam_begin(T_, num_stream, beam_, J_, V, bos, lens_dev, nullptr, nullptr, 0, nv.Data(), nv.Stride(), parents_.As<int32>(), state_,
+                            need_, nullptr));
+    num_stream_ = num_stream;
+  }
+  const DeviceMatrix &NextInput() const { return next_in_; }
+  // [S * beam] on the device: the row of the previous step's pred_rows that each row of NextInput() continues, -1: from zero state
+  const int32 *Parents() const { return parents_.As<int32>(); }
+  // pred_rows [S * beam x J]: the predictor's output for NextInput(); the lists take this step's complete hypotheses, NextInput() and
+  // Parents() become those of the next live set
+  void Step(const DeviceMatrix &enc, const DeviceMatrix &pred_rows, TransducerJoint *joint) {
+    KLSTM_ASSERT(enc.NumRows() == T_ * num_stream_ && enc.NumCols() == J_ && pred_rows.NumRows() == num_stream_ * beam_ && pred_rows.NumCols() == J_ &&
+                 joint->JointDim() == J_ && joint->NumClasses() == V_);
+    MatrixView e = enc.View(), p = pred_rows.View(), nv = next_in_.View();
+    KCheck(krnnt_beam_step(e.Data(), e.Stride(), p.Data(), p.Stride(), joint->W(), joint->b(), T_, num_stream_, beam_, nbest_, J_, V_, blank_,
+                           max_len_, nullptr, nullptr, 0, nv.Data(), nv.Stride(), parents_.As<int32>(), hyp_.As<int32>(), len_.As<int32>(),
+                           score_.As<BaseFloat>(), count_.As<int32>(), flags_.As<int32>(), live_.As<int32>(), state_, need_, nullptr));
+  }
+  int32 Live() const { int32 n = 0; live_.Download(&n, 1); return n; }        // the live slots of all streams.  Synchronises.
+  // per stream the list, best first, and the flags (klstm_rnnt.h: the greedy bits plus 16, pruned).  Synchronises.
+  void Results(std::vector<CtcNbestList> *lists, std::vector<int32> *flags) const {
+    const size_t S = num_stream_, N = nbest_, L = max_len_;
+    std::vector<int32> hyp(S * N * L), len(S * N), count(S);
+    std::vector<BaseFloat> score(S * N);
+    hyp_.Download(hyp.data(), hyp.size()); len_.Download(len.data(), len.size()); score_.Download(score.data(), score.size());
+    count_.Download(count.data(), S);
+    flags->resize(S);
+    flags_.Download(flags->data(), S);
+    lists->assign(S, CtcNbestList());
+    for (size_t s = 0; s < S; s++)
+      for (size_t q = 0; q < (size_t)count[s]; q++) {
+        CtcHypothesis h;
+        h.tokens.assign(hyp.begin() + (s * N + q) * L, hyp.begin() + (s * N + q) * L + len[s * N + q]);
+        h.score = score[s * N + q];
+        (*lists)[s].push_back(h);
+      }
+  }
+  int32 Beam() const { return beam_; }
+  int32 MaxLen() const { return max_len_; }
+ private:
+  int32 beam_, nbest_, max_len_, T_ = 0, J_ = 0, V_ = 0;
+  size_t need_ = 0;
+  void *state_ = nullptr;
+  DeviceMatrix next_in_;
+  DeviceBuffer parents_, hyp_, len_, score_, count_, flags_, live_;
+};
+
+struct DecodeTransducerBeamOptions {
+  int32 num_stream = 4, blank = 0, bos = -1, max_frames = 0;   // as DecodeTransducerOptions
+  int32 beam = 4, nbest = 4, max_len = 255;                    // slots per stream, list size (<= beam), labels per hypothesis
+  int32 poll_every = 8;                                        // the live count is read back every so many steps; 0: never (max_len + 1 steps)
+  bool sort_by_length = true;
+};
+struct DecodeTransducerBeamStats {
+  int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
+  double seconds = 0;
+  int64_t num_utterances = 0, total_hypotheses = 0, num_truncated = 0, num_pruned = 0, num_steps = 0;
+};
+
+// The greedy pass above with the beam search in its place: the same batch loop and the same refusals.  The predictor runs
+// num_stream * beam streams, one per slot, so every <LstmProjectedStreams> of it must have been built with that <NumStream>, which
+// must fit the 256 streams an engine is run with elsewhere (BatchScorer).  Per step: predictor->GatherStreams(Parents()) (after Begin
+// every parent is -1: zero state, which is the reset), the Propagate of num_stream * beam rows, Step.  (*nbest)[i] belongs to utts[i];
+// flags, if given, likewise.  every_batch (optional) sees each minibatch after its last step: (batch, enc_out, beam).
+template <class F>
+inline DecodeTransducerBeamStats DecodeTransducerBeamWholeUtterances(Nnet *encoder, Nnet *predictor, TransducerJoint *joint,
+                                                                     const std::vector<Utterance> &utts, const DecodeTransducerBeamOptions &o,
+                                                                     std::vector<CtcNbestList> *nbest, std::vector<int32> *flags,
+                                                                     std::string *report, F every_batch) {
+  const char *who = "DecodeTransducerBeamWholeUtterances";
+  const int32 V = joint->NumClasses();
+  RefuseTransducerDecode(who, encoder, predictor, joint);
+  if (o.beam < 1 || o.beam > 32 || o.nbest < 1 || o.nbest > o.beam) KLSTM_ERR(who << ": 1 <= nbest (" << o.nbest << ") <= beam (" << o.beam << ") <= 32");
+  const int32 rows = o.num_stream * o.beam;
+  if (o.num_stream < 1 || rows > 256)
+    KLSTM_ERR(who << ": the predictor runs num_stream x beam = " << o.num_stream << " x " << o.beam << " streams, an engine at most 256");
+  for (int32 i = 0; i < predictor->NumComponents(); i++)
+    if (const LstmLayer *l = dynamic_cast<const LstmLayer *>(&predictor->GetComponent(i)))
+      if (std::string(l->Marker()) != "<LstmProjectedStreams>" || l->Impl()->NumStream() != rows)
+        KLSTM_ERR(who << ": component " << i << " of the predictor (" << l->Marker() << ", " << l->Impl()->NumStream()
+                      << " streams) must be an <LstmProjectedStreams> of num_stream x beam = " << rows << " streams");
+  TransducerBeam beam(o.blank, o.beam, o.nbest, o.max_len);
+  DeviceMatrix pred_out;
+  std::vector<CtcNbestList> lists;
+  std::vector<int32> fl;
+  if (nbest) nbest->assign(utts.size(), CtcNbestList());
+  if (flags) flags->assign(utts.size(), 0);
+  DecodeTransducerBeamStats totals;
+  DecodeTransducerBeamStats st = ForEachWholeUtteranceBatch<DecodeTransducerBeamStats>(encoder, utts, o.num_stream, o.sort_by_length, o.max_frames,
+      [&](const UtteranceBatch &b, const DeviceMatrix &enc_out) {
+        beam.Begin(enc_out, b.num_stream, b.lens, V, o.bos < 0 ? o.blank : o.bos);
+        for (int32 step = 1; step <= o.max_len + 1; step++) {
+          predictor->GatherStreams(beam.Parents());
+          predictor->Propagate(beam.NextInput().View(), &pred_out);
+          beam.Step(enc_out, pred_out, joint);
+          totals.num_steps++;
+          if (o.poll_every > 0 && step % o.poll_every == 0 && beam.Live() == 0) break;
+        }
+        beam.Results(&lists, &fl);
+        for (int32 s = 0; s < b.num_stream; s++) {
+          if (b.utt_index[s] < 0) continue;
+          totals.num_utterances++;
+          totals.total_hypotheses += (int64_t)lists[s].size();
+          totals.num_truncated += (fl[s] & 2) != 0;
+          totals.num_pruned += (fl[s] & 16) != 0;
+        }
+        if (nbest) ScatterByUtterance(b, lists, nbest);
+        if (flags) ScatterByUtterance(b, fl, flags);
+        every_batch(b, enc_out, beam);
+      });
+  st.num_utterances = totals.num_utterances; st.total_hypotheses = totals.total_hypotheses; st.num_truncated = totals.num_truncated;
+  st.num_pruned = totals.num_pruned; st.num_steps = totals.num_steps;
+  if (report) {
+    std::ostringstream oss;
+    oss << "Transducer beam search: [" << st.num_utterances << " utterances, " << st.total_hypotheses << " hypotheses, " << st.num_truncated
+        << " truncated, " << st.num_pruned << " pruned, " << st.num_steps << " steps]" << std::endl;
+    *report = oss.str();
+  }
+  return st;
+}
+inline DecodeTransducerBeamStats DecodeTransducerBeamWholeUtterances(Nnet *encoder, Nnet *predictor, TransducerJoint *joint,
+                                                                     const std::vector<Utterance> &utts, const DecodeTransducerBeamOptions &o,
+                                                                     std::vector<CtcNbestList> *nbest, std::string *report = nullptr) {
+  return DecodeTransducerBeamWholeUtterances(encoder, predictor, joint, utts, o, nbest, (std::vector<int32> *)nullptr, report,
+                                             [](const UtteranceBatch &, const DeviceMatrix &, const TransducerBeam &) {});
 }
 
 // CTC forced alignment of whole utterances: the most probable alignment of each stream's labels to its frames (klstm_ctc_align,

@@ -130,6 +130,69 @@ klstm_status krnnt_greedy_step(const float *enc, int enc_stride, const float *pr
                                float *next_in, int next_in_stride, int *hyp_dev, int *hyp_len_dev, int *frame_dev, float *score_dev,
                                int *flags_dev, int *live_dev, void *state, size_t state_bytes, void *hip_stream);
 
+/* BEAM SEARCH WITH N-BEST LISTS, label-synchronous (the torch yardstick: tests/rnnt_beam_ref.py).
+ * A hypothesis is a label prefix y = y_1 .. y_u; its predictor row is p(y), the predictor after bos, y_1 .. y_u; h, a, lse, lpb are those
+ * of THE DEFINITION at node (t, u) with that row, and lpy_y(t, k) = a_k - lse for every class k != blank.
+ *     alpha_()(t)  = sum_{t' < t} lpb_()(t')                                  (the empty prefix; alpha(0) = 0)
+ *     e_{y+k}(t)   = alpha_y(t) + lpy_y(t, k)                                 the entry column of the child y+k
+ *     alpha_{y}(t) = logadd(alpha_y(t-1) + lpb_y(t-1), e_y(t)),  alpha_y(-1) = log 0
+ *     complete(y)  = alpha_y(T_s-1) + lpb_y(T_s-1)                            = log Pr(y | x) = -loss_s of krnnt_eval on labels y
+ *     prefix(y+k)  = logsumexp_t e_{y+k}(t)                                   = log Pr(the labels start with y+k | x);  prefix(()) = 0
+ * In probabilities prefix(y) = complete(y) + sum_k prefix(y+k): prefix(y) bounds complete(z) of every z that extends y.  The search per
+ * stream, with beam B, list size N <= B and label cap max_len:
+ *     L_0 = { () };  list = empty
+ *     step u = 0, 1, ...:
+ *         for every y in L_u (slot order): offer (y, complete(y)) to the list   (the N best by score; a tie keeps the earlier entry)
+ *         thr = the N-th best score in the list, -inf while it holds fewer than N
+ *         candidates (y, k), y in L_u, k != blank, scored prefix(y+k); keep those with score > thr
+ *         L_{u+1} = the B best candidates, score descending, ties to the lower (parent slot, class)
+ *         L_{u+1} empty: finished.   u + 1 > max_len with L_{u+1} not empty: truncated (the list stands as it is)
+ * If no candidate above thr was ever cut by B, the list is the exact N-best over all label sequences of length <= max_len; otherwise bit
+ * 4 of the stream's flags (pruned) is set.  alpha, the chunk sums and every listed score are summed in double; scores are given as floats.
+ * The loop is that of the greedy search over S B rows, row s B + b: slot b of stream s:
+ *     krnnt_beam_begin(...)                          next_in = the bos row in slot 0 of every live stream, parent_dev = -1 everywhere
+ *     repeat up to max_len + 1 times:  the predictor's state of row i becomes that of row parent_dev[i] (zero state at -1:
+ *                                      krnnt_gather_state), pred_rows = predictor(next_in)
+ *                                      krnnt_beam_step(...)               next_in, parent_dev = those of L_{u+1}
+ * next_in [S B x width]: rows as krnnt_pack writes them, zeros for an empty slot.  parent_dev [S B]: the ROW (s B + b') of the previous
+ * step's pred_rows that the new slot continues, -1 for an empty slot.  The list follows the contract of csrc/klstm_ctc_nbest.h:
+ * nbest_hyp [S][N][max_len], nbest_len [S][N], nbest_score [S][N] (complete(y), descending), nbest_count [S]; entries beyond the count:
+ * length 0, score 0, tokens untouched.  flags_dev [S]: the bits of the greedy search (a rejected or idle stream: count 0) plus bit 4.
+ * live_dev: one int, the live slots of all streams.  A step after every stream has stopped rewrites the same outputs.
+ *
+ * state: krnnt_beam_state_bytes(T, S, B, J, V) bytes (0 and a message beyond the limits), 256-byte aligned, private to the decode between
+ * begin and the last step, which give the same T, S, B, J, V (and every step the same N and max_len).  With SB = S B, FB = 64 (32 for
+ * J > 512), nc = ceil(T / FB) and every term rounded up to 256:
+ *     bytes = 5 x 4 S                       flags, T_s, step, live slots, list count per stream
+ *           + 8 x 32 S + 4 x 32 S           the list's scores in double and its lengths
+ *           + 3 x 4 SB                      live, parent row, label per slot
+ *           + 4 x 2 x 1024 SB               the token rows of two generations
+ *           + 3 x 8 SB T + 2 x 4 SB T       per frame in double: the entry column e, Bl, Cl; lse as two floats (maximum, log of the sum)
+ *           + 4 x 8 SB nc                   per chunk in double: A_in, Bl(f1), Cl(f1-1), the offset of Y
+ *           + 4 x 2 V SB nc                 X_k and Y_k of every chunk: 2 V floats per (slot, chunk), never T x V
+ *           + 8 SB V                        the candidates' prefix scores
+ * No atomics; runs are bit-identical, and a stream's list does not depend on its company.
+ *
+ * LIMITS: those of krnnt_greedy_* on S, T, J, V, blank, bos, max_len and D, and 1 <= N <= B <= 32: KLSTM_ERR_SHAPE.  A null required
+ * pointer, a row stride below the row, a pointer that is not 4-byte aligned, a state that is too small or not 256-byte aligned:
+ * KLSTM_ERR_ARG with the outputs untouched.  Every check runs before the first HIP call; everything is asynchronous on hip_stream;
+ * nothing is read back. */
+size_t krnnt_beam_state_bytes(int T, int S, int B, int J, int V);
+
+/* The predictor's side of a step: klstm_set_state_host on the device, without a host round trip.  Stream i of the engine takes the
+ * carried (c, r) of stream src_dev[i] (num_stream ints on the device; -1, or anything outside [0, num_stream): zero state).
+ * Asynchronous on the engine's stream; afterwards the engine is as if klstm_set_state_host had been given the gathered arrays (resets
+ * issued before are forgotten).  An entry of this family, defined with the engine: the list of klstm_* names stays as it is. */
+klstm_status krnnt_gather_state(klstm_engine *e, const int *src_dev);
+
+klstm_status krnnt_beam_begin(int T, int S, int B, int J, int V, int bos, const int *lens_dev, const float *embed, const float *embed_bias, int D,
+                              float *next_in, int next_in_stride, int *parent_dev, void *state, size_t state_bytes, void *hip_stream);
+
+klstm_status krnnt_beam_step(const float *enc, int enc_stride, const float *pred_rows, int pred_stride, const float *W, const float *b, int T,
+                             int S, int B, int N, int J, int V, int blank, int max_len, const float *embed, const float *embed_bias, int D,
+                             float *next_in, int next_in_stride, int *parent_dev, int *nbest_hyp, int *nbest_len, float *nbest_score,
+                             int *nbest_count, int *flags_dev, int *live_dev, void *state, size_t state_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -190,6 +190,11 @@ def load_library():
     lib.krnnt_greedy_state_bytes.restype = Z
     lib.krnnt_greedy_begin.argtypes = [I, I, I, I, I, P, P, P, I, P, I, P, Z, P]
     lib.krnnt_greedy_step.argtypes = [P, I, P, I, P, P, I, I, I, I, I, I, I, P, P, I, P, I, P, P, P, P, P, P, P, Z, P]
+    lib.krnnt_gather_state.argtypes = [P, P]
+    lib.krnnt_beam_state_bytes.argtypes = [I, I, I, I, I]
+    lib.krnnt_beam_state_bytes.restype = Z
+    lib.krnnt_beam_begin.argtypes = [I, I, I, I, I, I, P, P, P, I, P, I, P, P, Z, P]
+    lib.krnnt_beam_step.argtypes = [P, I, P, I, P, P, I, I, I, I, I, I, I, I, P, P, I, P, I, P, P, P, P, P, P, P, P, Z, P]
     _LIB = lib
     return lib
 
@@ -311,6 +316,12 @@ class Engine:
         c, r = _f32(c), _f32(r)
         assert c.shape == (self.S, self.C) and r.shape == (self.S, self.R)
         self._chk(self.lib.klstm_set_state_host(self.h, c.ctypes.data, r.ctypes.data))
+
+    def gather_state(self, src):
+        """stream i takes the carried state of stream src[i] (an int32 CUDA tensor of S entries; -1: zero state), on the device"""
+        import torch
+        assert src.is_cuda and src.dtype == torch.int32 and src.is_contiguous() and src.numel() == self.S
+        self._chk(self.lib.krnnt_gather_state(self.h, src.data_ptr()))
 
     # ---- PropagateFnc / BackpropagateFnc / Update (reference :222, :334, :501) ----
     def propagate(self, x, out):

@@ -25,6 +25,7 @@
 #include <tuple>
 #include <vector>
 
+#include "../../include/klstm_rnnt.h"
 #include "klstm_host.h"
 #include "klstm_kernels.h"
 
@@ -930,6 +931,20 @@ klstm_status klstm_set_state_host(klstm_engine *e, const float *c, const float *
   HIPCHK(hipMemcpyAsync(e->prev_r[e->sp], r, (size_t)e->S * e->R * sizeof(float), hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   e->resets.clear();                                  // (the state is what the caller says, whatever was reset before)
+  return KLSTM_OK;
+}
+klstm_status krnnt_gather_state(klstm_engine *e, const int *src_dev) {      // include/klstm_rnnt.h
+  if (!e || !src_dev) return fail(KLSTM_ERR_ARG, "krnnt_gather_state: null argument");
+  HIPCHK(hipSetDevice(e->device));
+  { klstm_status ss = settle(e); if (ss != KLSTM_OK) return ss; }       // (which buffer is current depends on it)
+  // through the other buffer, which nothing reads before the next forward pass overwrites it, and back: the current one stays current
+  float *cur[2] = {e->prev_c[e->sp], e->prev_r[e->sp]}, *other[2] = {e->prev_c[e->sp ^ 1], e->prev_r[e->sp ^ 1]};
+  const int cols[2] = {e->C, e->R};
+  for (int i = 0; i < 2; i++) {
+    HIPCHK(launch_gather_rows(cur[i], src_dev, e->S, cols[i], other[i], e->stream));
+    HIPCHK(hipMemcpyAsync(cur[i], other[i], (size_t)e->S * cols[i] * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  }
+  e->resets.clear();                                  // (as klstm_set_state_host: the state is what the caller says)
   return KLSTM_OK;
 }
 

@@ -305,6 +305,8 @@ hipError_t launch_pack(const Dims &d, const float *param_blob, const float *wrT,
 // out[dst] = in[clamp(dst + shift)] row gather (TimeShift; shift 0 = Transmit copy)
 hipError_t launch_time_shift(const float *in, int rows, int cols, int in_stride, float *out, int out_stride, int shift,
                              hipStream_t st, LaunchProbe pr = {});
+// out [rows x cols] row i = in row src[i] (src on the device; outside [0, rows): zeros); in and out dense and distinct (krnnt_gather_state)
+hipError_t launch_gather_rows(const float *in, const int *src, int rows, int cols, float *out, hipStream_t st, LaunchProbe pr = {});
 
 // output tail (Softmax, Xent::EvalMasked) and AffineTransform::Update helpers
 hipError_t launch_softmax(const float *in, int rows, int cols, int in_stride, float *out, int out_stride, hipStream_t st);

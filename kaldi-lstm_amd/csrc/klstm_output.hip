@@ -460,6 +460,16 @@ hipError_t launch_time_shift(const float *in, int rows, int cols, int in_stride,
   return launch(k_time_shift, dim3(cdiv(cdiv(cols, per), 256), rows), dim3(256), 0, st, pr, in, rows, cols, in_stride, out, out_stride, shift, vec);
 }
 
+// out row i = in row src[i]; zeros where src[i] lies outside [0, rows) (-1: no source).  blockIdx.y = i, columns over the threads.
+__global__ void k_gather_rows(const float *__restrict__ in, const int *__restrict__ src, int rows, int cols, float *__restrict__ out) {
+  const int i = blockIdx.y, from = src[i];
+  const bool has = from >= 0 && from < rows;
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < cols; c += gridDim.x * 256) out[(size_t)i * cols + c] = has ? in[(size_t)from * cols + c] : 0.f;
+}
+hipError_t launch_gather_rows(const float *in, const int *src, int rows, int cols, float *out, hipStream_t st, LaunchProbe pr) {
+  return launch(k_gather_rows, dim3(cols > 2048 ? 8 : cdiv(cols, 256), rows), dim3(256), 0, st, pr, in, src, rows, cols, out);
+}
+
 hipError_t launch_softmax(const float *in, int rows, int cols, int in_stride, float *out, int out_stride, hipStream_t st) {
   LaunchProbe pr;
   const bool wide = row_in_registers(cols, in, in_stride, out, out_stride);

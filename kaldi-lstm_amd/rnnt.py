@@ -1,5 +1,5 @@
-"""RNN-transducer training and greedy decoding on torch CUDA tensors: the krnnt_* entries of include/klstm_rnnt.h (which defines every
-quantity; the torch yardsticks: tests/rnnt_ref.py, tests/rnnt_greedy_ref.py).  Plumbing only, no arithmetic: the label lists become the CSR arrays of the
+"""RNN-transducer training, greedy decoding and beam search on torch CUDA tensors: the krnnt_* entries of include/klstm_rnnt.h (which defines every
+quantity; the torch yardsticks: tests/rnnt_ref.py, tests/rnnt_greedy_ref.py, tests/rnnt_beam_ref.py).  Plumbing only, no arithmetic: the label lists become the CSR arrays of the
 C-ABI through ctc.py's helpers, the workspace is cached per shape; without the library or a GPU the calls raise."""
 import ctypes
 
@@ -151,3 +151,70 @@ def rnnt_greedy_decode(enc, lens, W, b, predictor, bos, blank=0, max_symbols=10,
             break
     n, h, f = hyp_len.tolist(), hyp.tolist(), frames.tolist()
     return dict(tokens=[h[s][:n[s]] for s in range(S)], frames=[f[s][:n[s]] for s in range(S)], score=score, flags=flags, steps=steps)
+
+
+def rnnt_beam_state_bytes(T, S, B, J, V):
+    """bytes of state krnnt_beam_begin / krnnt_beam_step need (include/klstm_rnnt.h gives the formula)"""
+    return _workspace_bytes("krnnt_beam_state_bytes", T, S, B, J, V)
+
+
+def rnnt_beam_begin(T, S, B, J, V, bos, lens_dev, next_in, parents, state, embed=None, bias=None, stream=None):
+    """Start a beam search of S streams with B slots each: the state is reset, next_in [S*B, V or D] gets the bos row in slot 0 of every
+    live stream and parents [S*B] int32 gets -1."""
+    D = _embedding(embed, bias, V)
+    _chk(load_library().krnnt_beam_begin(int(T), int(S), int(B), int(J), int(V), int(bos), lens_dev.data_ptr(), _ptr(embed), _ptr(bias), D,
+                                         _rows(next_in).data_ptr(), next_in.stride(0), parents.data_ptr(), state.data_ptr(),
+                                         ctypes.c_size_t(state.numel()), _sp(stream)))
+
+
+def rnnt_beam_step(enc, pred_rows, W, b, T, S, B, blank, next_in, parents, hyp, hyp_len, score, count, flags, live, state, embed=None,
+                   bias=None, stream=None):
+    """Step u of all streams: pred_rows [S*B, J] are the predictor's outputs for next_in (row s*B + b: slot b of stream s).  The lists
+    (hyp [S, N, max_len], hyp_len / score [S, N], count [S]), flags [S] and live [1] are updated; next_in and parents (the row of
+    pred_rows each new slot continues, -1: empty) are rewritten.  Nothing synchronises."""
+    J, V = _rows(enc).shape[1], W.shape[0]
+    _rows(pred_rows, J)
+    D = _embedding(embed, bias, V)
+    _chk(load_library().krnnt_beam_step(enc.data_ptr(), enc.stride(0), pred_rows.data_ptr(), pred_rows.stride(0), W.data_ptr(), b.data_ptr(),
+                                        int(T), int(S), int(B), hyp.shape[1], J, V, int(blank), hyp.shape[2], _ptr(embed), _ptr(bias), D,
+                                        _rows(next_in).data_ptr(), next_in.stride(0), parents.data_ptr(), hyp.data_ptr(), hyp_len.data_ptr(),
+                                        score.data_ptr(), count.data_ptr(), flags.data_ptr(), live.data_ptr(), state.data_ptr(),
+                                        ctypes.c_size_t(state.numel()), _sp(stream)))
+
+
+def rnnt_beam_decode(enc, lens, pred_fn, W, b, bos, blank=0, beam=4, nbest=None, max_len=255, embed=None, bias=None, poll_every=8,
+                     stream=None, on_step=None):
+    """Transducer beam search of enc [T*S, J] (row t*S + s; lens: S lengths) with n-best lists scored by the full-sum probability.
+    pred_fn(next_in, parents): from the next-input rows [S*beam, V] (one-hot; [S*beam, D] with embed [D, V]) and the int32 rows
+    [S*beam] each one continues (-1: from reset state) to [S*beam, J] float32 CUDA rows; an LSTM predictor calls
+    Engine.gather_state(parents) and propagates.  At most max_len + 1 steps; the number of live slots is read back every poll_every
+    steps (0: never).  on_step(parents, flags, count), if given, sees the device arrays after every step.
+    Returns a dict: nbest (per stream a list of (tokens, score)), score [S, N] float32, count [S], flags [S] int32, steps."""
+    import torch
+    dev = enc.device
+    assert W.is_cuda and W.dtype == torch.float32 and W.is_contiguous() and b.is_cuda and b.dtype == torch.float32 and b.is_contiguous()
+    lens_dev = lens if isinstance(lens, torch.Tensor) and lens.is_cuda else torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
+    assert lens_dev.dtype == torch.int32 and lens_dev.is_contiguous()
+    S, (V, J), B = lens_dev.numel(), W.shape, int(beam)
+    N = B if nbest is None else int(nbest)
+    assert S > 0 and enc.shape[0] % S == 0 and enc.shape[1] == J and b.numel() == V
+    T = enc.shape[0] // S
+    nbytes = rnnt_beam_state_bytes(T, S, B, J, V)
+    state = _workspace("rnnt_beam", (T, S, B, J, V), nbytes, dev)[:nbytes]
+    ints = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+    next_in = torch.empty(S * B, embed.shape[0] if embed is not None else V, device=dev)
+    parents, hyp, hyp_len, count, flags, live = ints(S * B), ints(S, N, max_len), ints(S, N), ints(S), ints(S), ints(1)
+    score = torch.zeros(S, N, device=dev)
+    rnnt_beam_begin(T, S, B, J, V, bos, lens_dev, next_in, parents, state, embed, bias, stream)
+    steps = 0
+    while steps < max_len + 1:
+        rnnt_beam_step(enc, pred_fn(next_in, parents), W, b, T, S, B, blank, next_in, parents, hyp, hyp_len, score, count, flags, live, state,
+                       embed, bias, stream)
+        steps += 1
+        if on_step is not None:
+            on_step(parents, flags, count)
+        if poll_every and steps % poll_every == 0 and int(live) == 0:
+            break
+    n, ln, h, sc = count.tolist(), hyp_len.tolist(), hyp.tolist(), score.tolist()
+    lists = [[(h[s][q][:ln[s][q]], sc[s][q]) for q in range(n[s])] for s in range(S)]
+    return dict(nbest=lists, score=score, count=count, flags=flags, steps=steps)
