@@ -1129,6 +1129,56 @@ class Transducer : private CtcCallBase {
                       tot_.Dev(), ws, need, nullptr));
     num_stream_ = num_stream;
   }
+  // A valid band of width R around an alignment for EvalBanded (krnnt_band_from_frames states the rule): label_frames[s][i] = the frame
+  // of label i of stream s (from klstm_ctc_align of an auxiliary CTC head, or a greedy hypothesis); label_frames null, or no frame at
+  // all: the straight line.  left < 0: (R - 1) / 2.  A stream that no band of width R serves gets a row of -1 and EvalBanded rejects it.
+  const int32 *BandFromFrames(int32 T, int32 num_stream, const std::vector<int32> &lens, const std::vector<std::vector<int32> > &labels,
+                              const std::vector<std::vector<int32> > *label_frames, int32 R, int32 left = -1) {
+    const int32 *lens_dev = UploadLens(num_stream, lens);
+    KLSTM_ASSERT((int32)labels.size() == num_stream && (!label_frames || (int32)label_frames->size() == num_stream));
+    lab_.Upload(labels);
+    std::vector<int32> flat;
+    for (int32 s = 0; label_frames && s < num_stream; s++) {
+      const std::vector<int32> &f = (*label_frames)[s];
+      if (f.empty()) { flat.insert(flat.end(), labels[s].size(), 0); continue; }     // this stream: the straight line's frames
+      KLSTM_ASSERT(f.size() == labels[s].size());
+      flat.insert(flat.end(), f.begin(), f.end());
+    }
+    for (int32 s = 0; label_frames && s < num_stream; s++)
+      if ((*label_frames)[s].empty())                // label i of the straight line c(t) = t U / T_s sits at the first t with c(t) > i
+        for (size_t i = 0, o = FlatOffset(labels, s), U = labels[s].size(); i < U; i++)
+          flat[o + i] = (int32)std::min<long long>(((long long)(i + 1) * lens[s] + (long long)U - 1) / (long long)U - 1, std::max(lens[s] - 1, 0));
+    const bool any = !flat.empty();
+    if (any) frames_.Upload(flat);
+    band_.Grow((size_t)num_stream * T * sizeof(int32));
+    KCheck(krnnt_band_from_frames(any ? frames_.As<int32>() : nullptr, lens_dev, lab_.Offsets(), T, num_stream, R, left < 0 ? (R - 1) / 2 : left,
+                                  band_.As<int32>(), nullptr));
+    return band_.As<int32>();
+  }
+  // Eval inside a band: band_lo_dev [num_stream][T] on the device (BandFromFrames, or any valid band) and its width R.
+  void EvalBanded(const DeviceMatrix &enc, const DeviceMatrix &pred, int32 num_stream, const std::vector<int32> &lens,
+                  const std::vector<std::vector<int32> > &labels, const int32 *band_lo_dev, int32 R, TransducerJoint *joint, DeviceMatrix *d_enc,
+                  DeviceMatrix *d_pred) {
+    const int32 *lens_dev = UploadLens(num_stream, lens);
+    const int32 T = NumFrames(enc, num_stream, lens_dev, labels.size(), false), J = joint->JointDim(), V = joint->NumClasses();
+    lab_.Upload(labels);
+    const int32 Umax = (int32)lab_.longest;
+    KLSTM_ASSERT(band_lo_dev && enc.NumCols() == J && pred.NumCols() == J && pred.NumRows() == (Umax + 1) * num_stream &&
+                 (d_enc != nullptr) == (d_pred != nullptr));
+    const size_t need = d_enc ? krnnt_band_workspace_bytes(T, num_stream, Umax, R, J, V) : krnnt_band_forward_workspace_bytes(T, num_stream, R);
+    void *ws = Workspace(need);
+    loss_.Grow((size_t)num_stream * sizeof(BaseFloat));
+    MatrixView e = enc.View(), p = pred.View(), de, dp;
+    if (d_enc) {                                    // zeroed: the rows of a rejected stream are left alone by the call
+      d_enc->Resize(enc.NumRows(), J, true); d_pred->Resize(pred.NumRows(), J, true);
+      de = d_enc->View(); dp = d_pred->View();
+    }
+    KCheck(krnnt_band_eval(e.Data(), e.Stride(), p.Data(), p.Stride(), joint->W(), joint->b(), T, num_stream, Umax, J, V, lens_dev, lab_.Labels(),
+                           lab_.Offsets(), blank_, R, band_lo_dev, d_enc ? de.Data() : nullptr, d_enc ? de.Stride() : 0,
+                           d_enc ? dp.Data() : nullptr, d_enc ? dp.Stride() : 0, d_enc ? joint->WGrad() : nullptr,
+                           d_enc ? joint->bGrad() : nullptr, loss_.As<BaseFloat>(), tot_.Dev(), ws, need, nullptr));
+    num_stream_ = num_stream;
+  }
   // -log p(labels | x) of the streams of the last Eval (0: idle or rejected).  Synchronises.
   void UttLoss(std::vector<BaseFloat> *loss) const { loss->assign(num_stream_, 0.f); loss_.Download(loss->data(), loss->size()); }
   double NumUtterances() const { const double *h = tot_.Read(); return h[3] - h[4]; }          // evaluated
@@ -1145,8 +1195,13 @@ class Transducer : private CtcCallBase {
     return oss.str();
   }
  private:
+  static size_t FlatOffset(const std::vector<std::vector<int32> > &labels, int32 s) {
+    size_t o = 0;
+    for (int32 i = 0; i < s; i++) o += labels[i].size();
+    return o;
+  }
   PackedLabels lab_;
-  DeviceBuffer loss_;
+  DeviceBuffer loss_, frames_, band_;
   DeviceTotals<5> tot_;
 };
 
@@ -1157,6 +1212,9 @@ struct TrainTransducerOptions {
   BaseFloat dropout_retention = 0.f;                     // as in TrainCtcOptions, for both networks
   uint64_t dropout_seed = 0;
   bool dropout_per_sequence = false;
+  int32 band = 0;                                        // 0: the full lattice (krnnt_eval); R > 0: krnnt_band_eval in a band of R label positions
+  const std::vector<std::vector<int32> > *label_frames = nullptr;   // with band: per utterance (indexed like utts) the frame of every label;
+                                                         // null, or an absent or empty entry: the band follows the straight line
 };
 struct TrainTransducerStats {
   int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
@@ -1165,7 +1223,8 @@ struct TrainTransducerStats {
 
 // One pass over the utterances.  Per minibatch of the whole-utterance batch loop: the encoder's Propagate (uni- or bidirectional, the
 // lengths set as the CTC trainer sets them), krnnt_pack, the predictor's Propagate (Umax + 1 steps from reset state over one-hot rows
-// of V columns: unidirectional layers only), krnnt_eval, both Backpropagates and the three Updates.  Both networks end at the joint's
+// of V columns: unidirectional layers only), krnnt_eval (with o.band > 0: krnnt_band_from_frames and krnnt_band_eval), both
+// Backpropagates and the three Updates.  Both networks end at the joint's
 // width.  every_batch (optional) sees each minibatch after Transducer::Eval: (batch, enc_out, pred_out, transducer).
 template <class F>
 inline TrainTransducerStats TrainTransducerWholeUtterances(Nnet *encoder, Nnet *predictor, TransducerJoint *joint, const std::vector<Utterance> &utts,
@@ -1190,7 +1249,15 @@ inline TrainTransducerStats TrainTransducerWholeUtterances(Nnet *encoder, Nnet *
         tr.Pack(b.num_stream, b.labels, V, o.bos < 0 ? o.blank : o.bos, &pred_in);
         predictor->Reset(all);
         predictor->Propagate(pred_in.View(), &pred_out);
-        tr.Eval(enc_out, pred_out, b.num_stream, b.lens, b.labels, joint, o.crossvalidate ? nullptr : &d_enc, o.crossvalidate ? nullptr : &d_pred);
+        if (o.band > 0) {
+          std::vector<std::vector<int32> > fr(b.num_stream);
+          for (int32 s = 0; o.label_frames && s < b.num_stream; s++)
+            if (b.utt_index[s] >= 0 && (size_t)b.utt_index[s] < o.label_frames->size()) fr[s] = (*o.label_frames)[b.utt_index[s]];
+          const int32 *band = tr.BandFromFrames(b.num_frames, b.num_stream, b.lens, b.labels, o.label_frames ? &fr : nullptr, o.band);
+          tr.EvalBanded(enc_out, pred_out, b.num_stream, b.lens, b.labels, band, o.band, joint, o.crossvalidate ? nullptr : &d_enc,
+                        o.crossvalidate ? nullptr : &d_pred);
+        } else
+          tr.Eval(enc_out, pred_out, b.num_stream, b.lens, b.labels, joint, o.crossvalidate ? nullptr : &d_enc, o.crossvalidate ? nullptr : &d_pred);
         every_batch(b, enc_out, pred_out, tr);
         if (o.crossvalidate) return;
         encoder->Backpropagate(d_enc.View(), nullptr);

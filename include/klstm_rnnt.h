@@ -60,6 +60,7 @@ extern "C" {
 #endif
 
 enum { KRNNT_TILE_T = 16, KRNNT_TILE_U = 8, KRNNT_PASS_V = 128 };   /* lattice nodes of a forward tile (t x u), classes of a register pass */
+enum { KRNNT_BAND_TILE_R = 8 };                                     /* band offsets of a banded forward tile (16 t x 8 r) */
 
 int krnnt_grad_splits(int J, int V);
 
@@ -75,6 +76,59 @@ klstm_status krnnt_eval(const float *enc, int enc_stride, const float *pred, int
                         int Umax, int J, int V, const int *lens_dev, const int *labels_dev, const int *label_offsets_dev, int blank,
                         float *d_enc, int d_enc_stride, float *d_pred, int d_pred_stride, float *W_grad, float *b_grad,
                         float *utt_loss_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* BAND-PRUNED TRAINING (the torch yardstick: tests/rnnt_band_ref.py).  The lattice is evaluated only
+ * inside a band of R label positions per frame.  Per stream, with h, a, lse, lpb, lpy as in THE DEFINITION:
+ *     band_lo[s][t] = u0(t), 0 <= t < T_s ;  node (t, u) is IN BAND iff u0(t) <= u <= min(U, u0(t) + R - 1)
+ *     alpha, beta, w_b, w_y: those of THE DEFINITION with every node outside the band taken as log 0: a blank step from (t, u) counts
+ *              only if (t+1, u) is in band (or t = T_s - 1, u = U), a label step only if (t, u+1) is in band
+ *     loss_s   = -log of the probability of all alignments that stay in the band  (= the full loss when R >= U + 1 and u0 = 0)
+ *     d_enc[t], d_pred[u], W_grad, b_grad: the gradients of that loss, the sums over the nodes in band only; a d_pred row whose u is in
+ *              no band is zero; rows t >= T_s and u > U_s are zero as in krnnt_eval
+ * A band is VALID iff u0(0) = 0, 0 <= u0(t+1) - u0(t) <= R - 1 and u0(T_s - 1) <= U <= u0(T_s - 1) + R - 1: then it is connected and
+ * the loss is finite.  A stream with an invalid band is REJECTED on the device like a stream with a bad label: loss 0, counted in
+ * totals[3] and totals[4], its rows of d_enc and d_pred untouched.  Entries t >= T_s of a row of band_lo are not read.
+ * alpha and beta are kept per anti-diagonal d = t + u relative to the maximum of the diagonal before, in double while they are carried,
+ * the offsets summed in double, the loss taken in double; no floating-point atomics, fixed summation orders: runs are bit-identical,
+ * loss, d_enc and d_pred of a stream do not depend on its company, and the logits of a node are the same bits in the forward and in
+ * the backward kernel.
+ *
+ * LIMITS: those of krnnt_eval on S, J, V, blank and Umax <= 1023; 1 <= R <= 64; S T R <= 2^24 (in place of T (Umax+1) S <= 2^24):
+ * KLSTM_ERR_SHAPE; the argument checks of krnnt_eval (band_lo_dev is required): KLSTM_ERR_ARG.  Every check runs before the first
+ * HIP call; everything is asynchronous on hip_stream; nothing is read back.
+ *
+ * THE WORKSPACE has no term in T (Umax+1): the node planes are band-relative [S][T][R], d_enc needs no partials (a block of 16 frames
+ * owns its rows and adds to d_enc itself), and the d_pred partials of a block of frames cover only the label rows its band touches:
+ * block k's rows u0(16 k) .. u0(its last frame) + R - 1 live at rows u + k R of a per-stream array of (Umax+1) + tb R rows.  With
+ * N = S T R, tb = ceil(T / KRNNT_TILE_T), splits = krnnt_grad_splits(J, V):
+ *     bytes = up256(16 S)                                  status, T_s, U_s, label offset per stream
+ *           + up256(8 S)                                   the losses in double
+ *           + up256(16 S (T + 1024))                       the offsets of the alpha and the beta diagonals in double, sized for Umax = 1023
+ *           + 7 up256(4 N)                                 lpb, lpy, lse, alpha, beta, w_b, w_y: one float per band node each
+ *           + up256(4 S ((Umax+1) + tb R) J)               the d_pred windows of the frame blocks                     } the partials' term:
+ *           + up256(4 splits V J) + up256(8 splits V)      the partial W_grad (float) and b_grad (double)             } gradients only
+ * At S = 8, T = 500, U = 50, R = 8, J = 512, V = 64: 39.8 MB against the 99 MB of krnnt_workspace_bytes, 33.6 MB of it the W_grad
+ * partials that both share; forward only 1.1 MB against 5.8 MB. */
+size_t krnnt_band_workspace_bytes(int T, int S, int Umax, int R, int J, int V);
+size_t krnnt_band_forward_workspace_bytes(int T, int S, int R);
+
+/* The arguments of krnnt_eval plus R and band_lo_dev [S][T] (int); the four gradient outputs are given together or all NULL. */
+klstm_status krnnt_band_eval(const float *enc, int enc_stride, const float *pred, int pred_stride, const float *W, const float *b, int T, int S,
+                             int Umax, int J, int V, const int *lens_dev, const int *labels_dev, const int *label_offsets_dev, int blank, int R,
+                             const int *band_lo_dev, float *d_enc, int d_enc_stride, float *d_pred, int d_pred_stride, float *W_grad,
+                             float *b_grad, float *utt_loss_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* A valid band around an alignment.  label_frames_dev: the frame f_i of every label, CSR by label_offsets_dev (what klstm_ctc_align of
+ * an auxiliary CTC head or the greedy decoder's frame_dev give), or NULL.  Per stream, with U = its label count:
+ *     c(t)  = #{i : f_i < t}                    NULL frames: the linear c(t) = t U / T_s (integer division)
+ *     hi    = max(0, U + 1 - R)
+ *     u0(t) = min(max(c(t) - left, 0), hi) ;  u0(T_s - 1) = hi
+ *     from the end: u0(t) = max(u0(t), u0(t+1) - (R - 1))            (a suffix maximum of u0(t) - t (R - 1))
+ * If the last step lifts u0(0) above 0 (hi > (T_s - 1)(R - 1)), or the frames are not nondecreasing within [0, T_s), the whole row is
+ * written as -1 and krnnt_band_eval rejects the stream; so is the row of a stream with T_s < 0 or T_s > T; an idle stream's row is 0.
+ * Entries t >= T_s repeat the last value.  LIMITS: 1 <= S <= 32, 1 <= T, 1 <= R <= 64, S T R <= 2^24, 0 <= left < R: KLSTM_ERR_SHAPE. */
+klstm_status krnnt_band_from_frames(const int *label_frames_dev, const int *lens_dev, const int *label_offsets_dev, int T, int S, int R, int left,
+                                    int *band_lo_dev, void *hip_stream);
 
 /* The prediction network's input: row u*S + s of out [(Umax+1)*S x width] from x_u (x_0 = bos, x_u = y_u).  embed NULL: width = V and
  * the row is the one-hot of x_u.  embed [D x V] row-major (bias [D] or NULL): width = D and out[r, d] = embed[d, x_u] + bias[d].  Rows

@@ -1,5 +1,5 @@
-"""RNN-transducer training, greedy decoding and beam search on torch CUDA tensors: the krnnt_* entries of include/klstm_rnnt.h (which defines every
-quantity; the torch yardsticks: tests/rnnt_ref.py, tests/rnnt_greedy_ref.py, tests/rnnt_beam_ref.py).  Plumbing only, no arithmetic: the label lists become the CSR arrays of the
+"""RNN-transducer training (full lattice and band-pruned), greedy decoding and beam search on torch CUDA tensors: the krnnt_* entries of include/klstm_rnnt.h (which defines every
+quantity; the torch yardsticks: tests/rnnt_ref.py, tests/rnnt_band_ref.py, tests/rnnt_greedy_ref.py, tests/rnnt_beam_ref.py).  Plumbing only, no arithmetic: the label lists become the CSR arrays of the
 C-ABI through ctc.py's helpers, the workspace is cached per shape; without the library or a GPU the calls raise."""
 import ctypes
 
@@ -66,6 +66,82 @@ def rnnt_eval(enc, pred, W, b, lens, labels, blank=0, want_grads=True, totals=No
                         lens_dev.data_ptr(), lab_dev.data_ptr(), off_dev.data_ptr(), int(blank), _ptr(g[0]), g[0].stride(0) if want_grads else 0,
                         _ptr(g[1]), g[1].stride(0) if want_grads else 0, _ptr(g[2]), _ptr(g[3]), res["loss"].data_ptr(), _ptr(totals),
                         ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    return res
+
+
+def rnnt_band_workspace_bytes(T, S, Umax, R, J, V, want_grads=True):
+    """bytes of workspace krnnt_band_eval needs (include/klstm_rnnt.h gives the formula: no term in T (Umax+1)); without gradients
+    Umax, J and V do not enter it"""
+    full = _workspace_bytes("krnnt_band_workspace_bytes", T, S, Umax, R, J, V)      # the limits on Umax, J and V hold either way
+    return full if want_grads else _workspace_bytes("krnnt_band_forward_workspace_bytes", T, S, R)
+
+
+def _lens_dev(lens, dev):
+    import torch
+    if isinstance(lens, torch.Tensor) and lens.is_cuda:
+        assert lens.dtype == torch.int32 and lens.is_contiguous()
+        return lens
+    return torch.tensor([int(v) for v in lens], dtype=torch.int32, device=dev)
+
+
+def rnnt_band_from_frames(lens, labels, R, frames=None, left=None, T=None, device="cuda", stream=None):
+    """band_lo [S, T] int32 for rnnt_band_eval (krnnt_band_from_frames states the rule): a valid band of width R around the alignment
+    that puts label i of stream s at frame frames[s][i] (S lists like labels, or an int32 CUDA tensor packed like the labels: what
+    ctc_align or the greedy decoder give), around the straight line without frames.  left: label positions kept below the
+    alignment, (R-1)//2 by default.  A stream no band of width R can serve gets a row of -1 (rnnt_band_eval rejects it).
+    T: the longest length by default (lens on the host)."""
+    import torch
+    lens_dev = _lens_dev(lens, device)
+    S, dev = lens_dev.numel(), lens_dev.device
+    T = max(int(v) for v in lens) if T is None else int(T)
+    lab_dev, off_dev, _ = _packed(labels, S, dev)
+    fr = frames
+    if fr is not None and not isinstance(fr, torch.Tensor):
+        assert len(fr) == S
+        flat = [int(f) for row in fr for f in row]      # no label at all: nothing to pack, and the straight line is the same band
+        fr = torch.tensor(flat, dtype=torch.int32, device=dev) if flat else None
+    if fr is not None:
+        assert fr.is_cuda and fr.dtype == torch.int32 and fr.is_contiguous() and fr.numel() == lab_dev.numel(), "one frame per label"
+    band = torch.empty(S, max(T, 1), dtype=torch.int32, device=dev)
+    _chk(load_library().krnnt_band_from_frames(_ptr(fr), lens_dev.data_ptr(), off_dev.data_ptr(), T, S, int(R),
+                                               (int(R) - 1) // 2 if left is None else int(left), band.data_ptr(), _sp(stream)))
+    return band
+
+
+def rnnt_band_eval(enc, pred, W, b, lens, labels, band_lo, R, blank=0, want_grads=True, totals=None, stream=None, out=None):
+    """rnnt_eval inside a band: band_lo [S, T] int32 CUDA (rnnt_band_from_frames, or any valid band: klstm_rnnt.h) and its width R.
+    Arguments and the returned dict are those of rnnt_eval; a stream whose band is not valid is rejected like one with a bad label."""
+    import torch
+    lib, dev = load_library(), enc.device
+    _rows(enc)
+    J = enc.shape[1]
+    _rows(pred, J)
+    assert W.is_cuda and W.dtype == torch.float32 and W.dim() == 2 and W.is_contiguous() and W.shape[1] == J
+    V = W.shape[0]
+    assert b.is_cuda and b.dtype == torch.float32 and b.is_contiguous() and b.numel() == V
+    lens_dev = _lens_dev(lens, dev)
+    S = lens_dev.numel()
+    assert S > 0 and enc.shape[0] % S == 0 and pred.shape[0] % S == 0, "rows must be T * len(lens) and (Umax + 1) * len(lens)"
+    T, Umax, R = enc.shape[0] // S, pred.shape[0] // S - 1, int(R)
+    assert band_lo.is_cuda and band_lo.dtype == torch.int32 and band_lo.is_contiguous() and tuple(band_lo.shape) == (S, T)
+    lab_dev, off_dev, _ = _packed(labels, S, dev)
+    _check_totals(totals, 5)
+    nbytes = rnnt_band_workspace_bytes(T, S, Umax, R, J, V, want_grads)
+    ws = _workspace("rnnt_band", (T, S, Umax, R, J, V, bool(want_grads)), nbytes, dev)
+    res = {"loss": torch.empty(S, device=dev)}
+    g = [None] * 4
+    if want_grads:
+        out = out or {}
+        g = [out.get("d_enc"), out.get("d_pred"), out.get("W_grad"), out.get("b_grad")]
+        g = [t if t is not None else torch.empty(shape, device=dev)
+             for t, shape in zip(g, [(T * S, J), ((Umax + 1) * S, J), (V, J), (V,)])]
+        _rows(g[0], J), _rows(g[1], J)
+        assert g[0].shape[0] == T * S and g[1].shape[0] == (Umax + 1) * S and g[2].is_contiguous() and g[2].shape == (V, J) and g[3].numel() == V
+        res.update(d_enc=g[0], d_pred=g[1], W_grad=g[2], b_grad=g[3])
+    _chk(lib.krnnt_band_eval(enc.data_ptr(), enc.stride(0), pred.data_ptr(), pred.stride(0), W.data_ptr(), b.data_ptr(), T, S, Umax, J, V,
+                             lens_dev.data_ptr(), lab_dev.data_ptr(), off_dev.data_ptr(), int(blank), R, band_lo.data_ptr(), _ptr(g[0]),
+                             g[0].stride(0) if want_grads else 0, _ptr(g[1]), g[1].stride(0) if want_grads else 0, _ptr(g[2]), _ptr(g[3]),
+                             res["loss"].data_ptr(), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
     return res
 
 
