@@ -1179,6 +1179,46 @@ class Transducer : private CtcCallBase {
                            d_enc ? joint->bGrad() : nullptr, loss_.As<BaseFloat>(), tot_.Dev(), ws, need, nullptr));
     num_stream_ = num_stream;
   }
+  // The simple-joiner loss (krnnt_simple_eval states it): am [T*S x V], lm [(Umax+1)*S x V].  d_am, d_lm (both or neither): the gradients,
+  // zero on the rows of idle and rejected streams.  want_occ: the node occupations [num_stream][T][Umax+1] stay on the device for
+  // BandFromOccupation (the pointer is returned; null without).
+  const BaseFloat *EvalSimple(const DeviceMatrix &am, const DeviceMatrix &lm, int32 num_stream, const std::vector<int32> &lens,
+                              const std::vector<std::vector<int32> > &labels, DeviceMatrix *d_am, DeviceMatrix *d_lm, bool want_occ = true) {
+    const int32 *lens_dev = UploadLens(num_stream, lens);
+    const int32 T = NumFrames(am, num_stream, lens_dev, labels.size(), false), V = am.NumCols();
+    lab_.Upload(labels);
+    const int32 Umax = (int32)lab_.longest;
+    KLSTM_ASSERT(lm.NumCols() == V && lm.NumRows() == (Umax + 1) * num_stream && (d_am != nullptr) == (d_lm != nullptr));
+    const size_t need = krnnt_simple_workspace_bytes(T, num_stream, Umax, V);
+    void *ws = Workspace(need);
+    loss_.Grow((size_t)num_stream * sizeof(BaseFloat));
+    MatrixView a = am.View(), l = lm.View(), da, dl;
+    if (d_am) {                                     // zeroed: the rows of a rejected stream are left alone by the call
+      d_am->Resize(am.NumRows(), V, true); d_lm->Resize(lm.NumRows(), V, true);
+      da = d_am->View(); dl = d_lm->View();
+    }
+    const size_t nocc = (size_t)num_stream * T * (Umax + 1) * sizeof(BaseFloat);
+    if (want_occ) {
+      occ_.Grow(nocc);
+      KCheck(klstm_memset_zero(occ_.As<BaseFloat>(), nocc, nullptr));
+    }
+    KCheck(krnnt_simple_eval(a.Data(), a.Stride(), l.Data(), l.Stride(), T, num_stream, Umax, V, lens_dev, lab_.Labels(), lab_.Offsets(), blank_,
+                             d_am ? da.Data() : nullptr, d_am ? da.Stride() : 0, d_am ? dl.Data() : nullptr, d_am ? dl.Stride() : 0,
+                             want_occ ? occ_.As<BaseFloat>() : nullptr, loss_.As<BaseFloat>(), tot_.Dev(), ws, need, nullptr));
+    num_stream_ = num_stream;
+    return want_occ ? occ_.As<BaseFloat>() : nullptr;
+  }
+  // A valid band of width R for EvalBanded from node occupations occ_dev [num_stream][T][Umax+1] (EvalSimple's, with Umax the longest
+  // label list): krnnt_band_from_occupation states the rule.  A stream that no band of width R serves gets a row of -1.
+  const int32 *BandFromOccupation(const BaseFloat *occ_dev, int32 T, int32 num_stream, const std::vector<int32> &lens,
+                                  const std::vector<std::vector<int32> > &labels, int32 R) {
+    const int32 *lens_dev = UploadLens(num_stream, lens);
+    KLSTM_ASSERT(occ_dev && (int32)labels.size() == num_stream);
+    lab_.Upload(labels);
+    band_.Grow((size_t)num_stream * T * sizeof(int32));
+    KCheck(krnnt_band_from_occupation(occ_dev, lens_dev, lab_.Offsets(), T, num_stream, (int)lab_.longest, R, band_.As<int32>(), nullptr));
+    return band_.As<int32>();
+  }
   // -log p(labels | x) of the streams of the last Eval (0: idle or rejected).  Synchronises.
   void UttLoss(std::vector<BaseFloat> *loss) const { loss->assign(num_stream_, 0.f); loss_.Download(loss->data(), loss->size()); }
   double NumUtterances() const { const double *h = tot_.Read(); return h[3] - h[4]; }          // evaluated
@@ -1201,7 +1241,7 @@ class Transducer : private CtcCallBase {
     return o;
   }
   PackedLabels lab_;
-  DeviceBuffer loss_, frames_, band_;
+  DeviceBuffer loss_, frames_, band_, occ_;
   DeviceTotals<5> tot_;
 };
 

@@ -130,6 +130,68 @@ klstm_status krnnt_band_eval(const float *enc, int enc_stride, const float *pred
 klstm_status krnnt_band_from_frames(const int *label_frames_dev, const int *lens_dev, const int *label_offsets_dev, int T, int S, int R, int left,
                                     int *band_lo_dev, void *hip_stream);
 
+/* THE SIMPLE JOINER (the torch yardstick: tests/rnnt_simple_ref.py).  The first pass of pruned
+ * transducer training: a joiner without tanh and without W, whose logits are the sum of an encoder-side and a predictor-side row, is
+ * evaluated over the whole lattice; its node occupations select the band that krnnt_band_eval then runs the real joint in.  Per stream s:
+ * T_s frames and labels y_1 .. y_U through the CSR arrays of krnnt_eval.
+ *     am [T*S x V]          row t*S + s : encoder-side logits      (row stride am_stride)
+ *     lm [(Umax+1)*S x V]   row u*S + s : predictor-side logits    (row stride lm_stride)
+ *     node (t, u):  a_v      = am[t][v] + lm[u][v]
+ *                   ma(t)    = max_v am[t][v]        ml(u) = max_v lm[u][v]
+ *                   P(t,u)   = sum_v exp(am[t][v] - ma(t)) * exp(lm[u][v] - ml(u))       clamped below at FLT_MIN
+ *                   lse(t,u) = ma(t) + ml(u) + log P(t,u)
+ *                   lpb      = a_blank - lse ;  lpy = a_{y_{u+1}} - lse  (u < U)
+ *     alpha, beta, loss_s, w_b, w_y : exactly those of THE DEFINITION of krnnt_eval on these lpb, lpy
+ *     occ(t,u)   = w_b(t,u) + w_y(t,u)                 the node's posterior; 0 outside t < T_s, u <= U_s
+ *     g_v(t,u)   = occ * exp(a_v - lse) - [v = blank] w_b - [v = y_{u+1}] w_y
+ *     d_am[t][v] = sum_u g_v(t,u)       d_lm[u][v] = sum_t g_v(t,u)
+ * P is the product of two matrices, [T x V] . [V x (Umax+1)]: no array of nodes x classes is ever formed.  exp(a_v - lse) is taken as
+ * exp(am[t][v] - ma(t)) exp(lm[u][v] - ml(u)) / P, and the indicator terms are summed in double.
+ * DOMAIN.  With the spread max - min of every row of am and of lm at most 40, every factor is at least e^-40 and every term of P at
+ * least e^-80 > FLT_MIN: no term leaves the normal float range and the formula is the log-softmax of a.  Beyond that spread terms
+ * flush to zero, the clamp keeps log P finite, and the result is approximate (a class both of whose factors vanished counts as
+ * impossible).
+ * What carries over from krnnt_eval unchanged: the rejection rules (T_s < 0, T_s > T, U_s > Umax, a label outside [0, V) or equal to
+ * blank: loss 0, counted in the totals, the stream's rows of d_am and d_lm and its part of occ untouched); the five totals; zero rows
+ * t >= T_s of d_am and u > U_s of d_lm, and of idle streams; every check before the first HIP call; everything asynchronous on
+ * hip_stream; no floating-point atomics, every sum in a fixed order: runs are bit-identical and a stream's loss, rows and occ do not
+ * depend on its company.
+ *
+ * LIMITS: 1 <= S <= 32, 1 <= T, 0 <= Umax <= 1023, T (Umax+1) S <= 2^24, 2 <= V <= 4096, blank in [0, V): KLSTM_ERR_SHAPE.  The pointer,
+ * stride (>= V), alignment and workspace checks of krnnt_eval: KLSTM_ERR_ARG.  d_am [T*S x V] and d_lm [(Umax+1)*S x V] are given
+ * together or both NULL; occ_dev [S][T][Umax+1] floats or NULL.
+ *
+ * THE WORKSPACE holds no array of S T (Umax+1) V elements.  With N = S T (Umax+1) and Vp = V rounded up to 32 (the K panel):
+ *     bytes = up256(16 S)                                  status, T_s, U_s, label offset per stream
+ *           + up256(8 S)                                   the losses in double
+ *           + up256(16 S (T + Umax + 1))                   the offsets of the alpha and the beta diagonals in double
+ *           + 7 up256(4 N)                                 lpb, lpy, P (then q = occ / P), alpha, beta, w_b, w_y: one float per node each
+ *           + up256(4 S T Vp) + up256(4 S (Umax+1) Vp)     exp(am - ma) and exp(lm - ml), the rows zero-padded to Vp
+ *           + up256(4 S T) + up256(4 S (Umax+1))           the row maxima ma and ml
+ * At S = 8, T = 500, U = 50, V = 1024: 23.9 MB, 18.1 MB of it the two operands. */
+size_t krnnt_simple_workspace_bytes(int T, int S, int Umax, int V);
+
+klstm_status krnnt_simple_eval(const float *am, int am_stride, const float *lm, int lm_stride, int T, int S, int Umax, int V,
+                               const int *lens_dev, const int *labels_dev, const int *label_offsets_dev, int blank, float *d_am,
+                               int d_am_stride, float *d_lm, int d_lm_stride, float *occ_dev, float *utt_loss_dev, double *totals_dev,
+                               void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* THE BAND RULE: a valid band of width R from node occupations (any non-negative plane [S][T][Umax+1]; krnnt_simple_eval's occ is the
+ * intended one).  Per stream, with U its label count and hi = max(0, U + 1 - R):
+ *     w(t, k)  = sum_{r = 0}^{R-1} (double) occ(t, k + r)      added in the order of r; terms with k + r > U are 0
+ *     c(t)     = the k in [0, hi] with the largest w(t, k); `>` decides, from -infinity at k = 0 on: a tie goes to the lower k, and a
+ *                NaN never wins
+ *     c(0) = 0, then c(T_s - 1) = hi
+ *     m(t)     = max_{t' <= t} c(t')                                   (prefix maximum: nondecreasing)
+ *     u0(T_s - 1) = hi ;  from the end: u0(t) = max(m(t), u0(t+1) - (R - 1))
+ * If this leaves u0(0) > 0 the row is all -1, as krnnt_band_from_frames writes for a stream that no band of width R can serve; so is
+ * the row of a stream with T_s < 0, T_s > T or more labels than Umax.  An idle stream's row is 0; entries t >= T_s repeat the last
+ * value.  By construction the result is a VALID band in the sense of krnnt_band_eval.  Sums in double in a fixed order and integer
+ * scans: the result is exact.  LIMITS: 1 <= S <= 32, 1 <= T, 0 <= Umax <= 1023, T (Umax+1) S <= 2^24, 1 <= R <= 64: KLSTM_ERR_SHAPE;
+ * a null or misaligned pointer: KLSTM_ERR_ARG.  band_lo_dev: [S][T] int, as krnnt_band_eval reads it. */
+klstm_status krnnt_band_from_occupation(const float *occ_dev, const int *lens_dev, const int *label_offsets_dev, int T, int S, int Umax,
+                                        int R, int *band_lo_dev, void *hip_stream);
+
 /* The prediction network's input: row u*S + s of out [(Umax+1)*S x width] from x_u (x_0 = bos, x_u = y_u).  embed NULL: width = V and
  * the row is the one-hot of x_u.  embed [D x V] row-major (bias [D] or NULL): width = D and out[r, d] = embed[d, x_u] + bias[d].  Rows
  * without an input (u > U_s, or x_u outside [0, V)) are zeros.  1 <= S <= 32, 0 <= Umax <= 1023, 1 <= V, D; bos in [0, V). */

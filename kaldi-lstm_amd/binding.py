@@ -191,6 +191,10 @@ def load_library():
     lib.krnnt_band_forward_workspace_bytes.restype = Z
     lib.krnnt_band_eval.argtypes = [P, I, P, I, P, P, I, I, I, I, I, P, P, P, I, I, P, P, I, P, I, P, P, P, P, P, Z, P]
     lib.krnnt_band_from_frames.argtypes = [P, P, P, I, I, I, I, P, P]
+    lib.krnnt_simple_workspace_bytes.argtypes = [I, I, I, I]
+    lib.krnnt_simple_workspace_bytes.restype = Z
+    lib.krnnt_simple_eval.argtypes = [P, I, P, I, I, I, I, I, P, P, P, I, P, I, P, I, P, P, P, P, Z, P]
+    lib.krnnt_band_from_occupation.argtypes = [P, P, P, I, I, I, I, P, P]
     lib.krnnt_pack.argtypes = [P, P, I, I, I, I, P, P, I, P, I, P]
     lib.krnnt_greedy_state_bytes.argtypes = [I, I, I]
     lib.krnnt_greedy_state_bytes.restype = Z

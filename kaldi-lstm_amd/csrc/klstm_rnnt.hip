@@ -51,22 +51,7 @@ constexpr int RU = KRNNT_TILE_U;            // (RT, VP, NVT, KP, WPS and RLOG0: 
 constexpr int BU = 4, GS = VP + 2;          // u per backward step (one per wave), floats per row of the g tile
 constexpr int ESLOTS = 4;                   // d_enc partial slots = waves of the backward workgroup
 
-struct RnntWs {
-  int4 *meta; double *loss, *offs;
-  float *lpb, *lpy, *lse, *A, *B, *wb, *wy, *dep, *dpp, *wpart;
-  double *bpart;
-};
-
-struct RnntArgs {
-  const float *enc, *pred, *W, *b;
-  int enc_stride, pred_stride, T, S, U1, J, V, blank;
-  const int *lens, *labels, *loff;
-  float *d_enc, *d_pred, *Wg, *bg;
-  int de_stride, dp_stride;
-  float *utt_loss; double *totals;
-  RnntWs ws;
-  int splits, ntb;
-};
+// (RnntWs and RnntArgs: klstm_rnnt_dev.h, shared with klstm_rnnt_simple.hip)
 
 static int rnnt_splits(int J, int V) {
   const long long s = (1ll << 24) / ((long long)V * J);
@@ -74,7 +59,7 @@ static int rnnt_splits(int J, int V) {
 }
 
 // the layout of the workspace (include/klstm_rnnt.h states the formula); base null: only bytes() counts
-static RnntWs rnnt_carve(void *base, int T, int S, int U1, int J, int V, bool grads, size_t *bytes) {
+RnntWs rnnt_carve(void *base, int T, int S, int U1, int J, int V, bool grads, size_t *bytes) {
   CtcCarver c(base);
   RnntWs w;
   const size_t N = (size_t)S * T * U1, ntb = (size_t)(T + RT - 1) / RT;
@@ -488,6 +473,15 @@ __global__ __launch_bounds__(256) void k_rnnt_pack(const int *labels, const int 
   }
 }
 
+hipError_t rnnt_launch_prep(const RnntArgs &a, hipStream_t st) { return launch(k_rnnt_prep, dim3(1), dim3(64), 0, st, LaunchProbe(), a); }
+
+hipError_t rnnt_launch_lattice(const RnntArgs &a, hipStream_t st) {
+  const size_t N = (size_t)a.S * a.T * a.U1;
+  const hipError_t e = launch(k_rnnt_lattice, dim3(a.S, 2), dim3((a.U1 + 63) / 64 * 64), 0, st, LaunchProbe(), a);
+  if (e != hipSuccess) return e;
+  return launch(k_rnnt_weights, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, LaunchProbe(), a);
+}
+
 static bool al4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 static const char *rnnt_limits(int T, int S, int Umax, int J, int V) {
@@ -557,11 +551,9 @@ klstm_status krnnt_eval(const float *enc, int enc_stride, const float *pred, int
   a.splits = rnnt_splits(J, V); a.ntb = (T + RT - 1) / RT;
   hipStream_t st = (hipStream_t)hip_stream;
   const int Jp = J + 2, U1 = a.U1;
-  const size_t N = (size_t)S * T * U1;
-  HIPCHK(launch(k_rnnt_prep, dim3(1), dim3(64), 0, st, LaunchProbe(), a));
+  HIPCHK(rnnt_launch_prep(a, st));
   HIPCHK(launch(k_rnnt_joint_fwd, dim3(a.ntb, (U1 + RU - 1) / RU, S), dim3(256), ((size_t)(RT + RU) * Jp + VP * WPS) * sizeof(float), st, LaunchProbe(), a));
-  HIPCHK(launch(k_rnnt_lattice, dim3(S, 2), dim3((U1 + 63) / 64 * 64), 0, st, LaunchProbe(), a));
-  HIPCHK(launch(k_rnnt_weights, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, LaunchProbe(), a));
+  HIPCHK(rnnt_launch_lattice(a, st));
   if (!ngrad) return KLSTM_OK;
   const size_t shm = ((size_t)(RT + BU) * Jp + VP * WPS + 64 * GS) * sizeof(float);
   if (J <= 128) HIPCHK(launch(k_rnnt_joint_bwd<8>, dim3(a.splits), dim3(256), shm, st, LaunchProbe(), a));

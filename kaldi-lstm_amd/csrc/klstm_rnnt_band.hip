@@ -35,7 +35,8 @@
 //   k_rband_finish    d_pred[u] = the windows that hold u, in block order (they are consecutive: a binary search finds the first);
 //                     zero rows of d_enc and d_pred where the definition says so; W_grad / b_grad = the splits in order, in double.
 //   k_rband_from_frames  one workgroup per stream: c(t) by binary search in the label frames, the clamp, then the suffix maximum of
-//                     u0(t) - t (R-1) in chunks of 256 frames from the end (an LDS scan per chunk and a carry).
+//                     u0(t) - t (R-1) in chunks of 256 frames from the end (band_close() of klstm_rnnt_dev.h, which
+//                     krnnt_band_from_occupation ends with as well).
 // BOUNDS.  A node is touched only with t < T_s, r < R and u0(t) + r <= U_s (nodeU[] in LDS holds u or -1 per node of the tile and every
 // access goes through it); band entries are read only for t < T_s of a stream whose band the prep kernel accepted; classes >= V are
 // masked at the panel load and in the epilogues; offsets are size_t products.
@@ -627,39 +628,18 @@ __global__ __launch_bounds__(256) void k_rband_from_frames(const int *frames, co
     }
     if (b) atomicOr(&bad, 1);
   }
-  for (int c0 = (Ts - 1) / 256 * 256; c0 >= 0; c0 -= 256) {
-    const int t = c0 + tid;
-    int g = INT_MIN;
-    if (t < Ts) {
-      int c;
-      if (frames) {                                    // c(t) = #{i : f_i < t}
-        int i0 = 0, i1 = U;
-        while (i0 < i1) {
-          const int m = (i0 + i1) >> 1;
-          if (frames[o0 + m] < t) i0 = m + 1; else i1 = m;
-        }
-        c = i0;
-      } else c = (int)((long long)t * U / Ts);
-      const int u = t == Ts - 1 ? hi : min(max(c - left, 0), hi);
-      g = u - t * R1;
-    }
-    __syncthreads();                                   // the chunk before is done with sc and carry
-    sc[tid] = g;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {                // suffix maximum of the chunk
-      const int v = tid + o < 256 ? sc[tid + o] : INT_MIN;
-      __syncthreads();
-      sc[tid] = max(sc[tid], v);
-      __syncthreads();
-    }
-    g = max(sc[tid], carry);
-    __syncthreads();
-    if (tid == 0) carry = g;
-    if (t < Ts) row[t] = g + t * R1;
-  }
-  __syncthreads();
-  const bool infeasible = bad || carry != 0;           // carry = u0(0) after the last step
-  for (int t = infeasible ? tid : Ts + tid; t < T; t += 256) row[t] = infeasible ? -1 : hi;
+  band_close(row, Ts, T, R1, hi, [&](int t) {          // the suffix scan and the row: klstm_rnnt_dev.h
+    int c;
+    if (frames) {                                      // c(t) = #{i : f_i < t}
+      int i0 = 0, i1 = U;
+      while (i0 < i1) {
+        const int m = (i0 + i1) >> 1;
+        if (frames[o0 + m] < t) i0 = m + 1; else i1 = m;
+      }
+      c = i0;
+    } else c = (int)((long long)t * U / Ts);
+    return t == Ts - 1 ? hi : min(max(c - left, 0), hi);
+  }, sc, &carry, &bad);
 }
 
 static bool band_al4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }

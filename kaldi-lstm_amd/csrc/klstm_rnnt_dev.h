@@ -2,7 +2,11 @@
 // greedy decoding): the tile constants, the staging of rows into LDS, the 16-lane reductions of a node's row and joint_logits(), the
 // product W tanh(enc[t] + pred[u]) of M-tiles of 16 nodes in MFMA registers (klstm_rnnt.hip's head describes its layout).  Both sources
 // are compiled with the same flags (build.py EXTRA_FLAGS), so the logits of a node are the same bits in training and in decoding.
+// Also here: the argument and workspace types of klstm_rnnt.hip's kernels with the host helpers that launch its prep, lattice and
+// weights kernels (klstm_rnnt_simple.hip runs them on its own lpb / lpy), and band_close(), the scan both band builders end with.
 #pragma once
+#include <climits>
+
 #include "../../include/klstm_rnnt.h"
 #include "klstm_kernels.h"
 #include "klstm_math.h"
@@ -12,6 +16,63 @@ namespace klstm {
 constexpr int RT = KRNNT_TILE_T, VP = KRNNT_PASS_V, NVT = VP / 16;
 constexpr int KP = 32, WPS = KP + 2;        // k per W panel, floats per panel row
 constexpr float RLOG0 = -1e30f;
+
+// The workspace and the arguments of klstm_rnnt.hip's kernels.  klstm_rnnt_simple.hip fills lpb / lpy itself and runs the same prep,
+// lattice and weights kernels on these planes through the two host helpers below (defined in klstm_rnnt.hip).
+struct RnntWs {
+  int4 *meta; double *loss, *offs;
+  float *lpb, *lpy, *lse, *A, *B, *wb, *wy, *dep, *dpp, *wpart;
+  double *bpart;
+};
+
+struct RnntArgs {
+  const float *enc, *pred, *W, *b;
+  int enc_stride, pred_stride, T, S, U1, J, V, blank;
+  const int *lens, *labels, *loff;
+  float *d_enc, *d_pred, *Wg, *bg;
+  int de_stride, dp_stride;
+  float *utt_loss; double *totals;
+  RnntWs ws;
+  int splits, ntb;
+};
+
+// the layout of krnnt_eval's workspace; base null: only *bytes counts
+RnntWs rnnt_carve(void *base, int T, int S, int U1, int J, int V, bool grads, size_t *bytes);
+// k_rnnt_prep (status, T_s, U_s, label offset of every stream into ws.meta), and, once lpb / lpy of every node under t < T_s, u <= U_s
+// are written, k_rnnt_lattice + k_rnnt_weights (alpha, beta, the loss, w_b, w_y, the totals).  They read T, S, U1, V, blank, lens,
+// labels, loff, utt_loss, totals and ws of a.
+hipError_t rnnt_launch_prep(const RnntArgs &a, hipStream_t st);
+hipError_t rnnt_launch_lattice(const RnntArgs &a, hipStream_t st);
+
+// The end of a band builder (krnnt_band_from_frames, krnnt_band_from_occupation; 256 threads, one workgroup per stream).  cand(t) is
+// u0(t) before the closure, with cand(T_s - 1) = hi.  From the end u0(t) = max(cand(t), u0(t+1) - R1): the suffix maximum of
+// cand(t) - t R1 in chunks of 256 frames (an LDS scan per chunk and a carry).  Then the row: u0 for t < T_s and hi behind it, or -1
+// everywhere if *bad is set or u0(0) > 0.  sc [256], carry: LDS; *carry = INT_MIN and *bad are set and fenced by the caller.
+template <class F>
+__device__ __forceinline__ void band_close(int *row, int Ts, int T, int R1, int hi, F cand, int *sc, int *carry, const int *bad) {
+  const int tid = threadIdx.x;
+  for (int c0 = (Ts - 1) / 256 * 256; c0 >= 0; c0 -= 256) {
+    const int t = c0 + tid;
+    int g = INT_MIN;
+    if (t < Ts) g = cand(t) - t * R1;
+    __syncthreads();                                   // the chunk before is done with sc and carry
+    sc[tid] = g;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {                // suffix maximum of the chunk
+      const int v = tid + o < 256 ? sc[tid + o] : INT_MIN;
+      __syncthreads();
+      sc[tid] = max(sc[tid], v);
+      __syncthreads();
+    }
+    g = max(sc[tid], *carry);
+    __syncthreads();
+    if (tid == 0) *carry = g;
+    if (t < Ts) row[t] = g + t * R1;
+  }
+  __syncthreads();
+  const bool infeasible = *bad || *carry != 0;         // carry = u0(0) after the last step
+  for (int t = infeasible ? tid : Ts + tid; t < T; t += 256) row[t] = infeasible ? -1 : hi;
+}
 
 // rows row0 .. row0 + nrows - 1 of stream s (row r of the matrix: (row0 + r) S + s) into dst [nrows][Jp]; rows from nvalid on: zeros
 __device__ __forceinline__ void rnnt_stage(float *dst, int Jp, const float *src, int stride, int row0, int nrows, int nvalid, int S, int s, int J) {

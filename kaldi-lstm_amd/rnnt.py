@@ -145,6 +145,65 @@ def rnnt_band_eval(enc, pred, W, b, lens, labels, band_lo, R, blank=0, want_grad
     return res
 
 
+def rnnt_simple_workspace_bytes(T, S, Umax, V):
+    """bytes of workspace krnnt_simple_eval needs (include/klstm_rnnt.h gives the formula: no term in T (Umax+1) V)"""
+    return _workspace_bytes("krnnt_simple_workspace_bytes", T, S, Umax, V)
+
+
+def rnnt_simple_eval(am, lm, lens, labels, blank=0, want_grads=True, want_occ=False, totals=None, stream=None, out=None):
+    """The additive simple-joiner loss (klstm_rnnt.h, THE SIMPLE JOINER): am [T*S, V] (row t*S + s), lm [(Umax+1)*S, V] (row u*S + s),
+    float32 CUDA, any row stride; lens, labels, totals as in rnnt_eval.  Returns a dict: loss [S] and, with want_grads, d_am, d_lm
+    (like am, lm); with want_occ, occ [S, T, Umax+1], the node posteriors that rnnt_band_from_occupation turns into a band.
+    out: a dict of preallocated d_am / d_lm / occ (the parts of rejected streams are left as they are).  Nothing synchronises."""
+    import torch
+    lib, dev = load_library(), am.device
+    _rows(am)
+    V = am.shape[1]
+    _rows(lm, V)
+    lens_dev = _lens_dev(lens, dev)
+    S = lens_dev.numel()
+    assert S > 0 and am.shape[0] % S == 0 and lm.shape[0] % S == 0, "rows must be T * len(lens) and (Umax + 1) * len(lens)"
+    T, Umax = am.shape[0] // S, lm.shape[0] // S - 1
+    lab_dev, off_dev, _ = _packed(labels, S, dev)
+    _check_totals(totals, 5)
+    nbytes = rnnt_simple_workspace_bytes(T, S, Umax, V)
+    ws = _workspace("rnnt_simple", (T, S, Umax, V), nbytes, dev)
+    res, out = {"loss": torch.empty(S, device=dev)}, out or {}
+    g, occ = [None, None], None
+    if want_grads:
+        g = [out.get("d_am"), out.get("d_lm")]
+        g = [t if t is not None else torch.empty(shape, device=dev) for t, shape in zip(g, [(T * S, V), ((Umax + 1) * S, V)])]
+        _rows(g[0], V), _rows(g[1], V)
+        assert g[0].shape[0] == T * S and g[1].shape[0] == (Umax + 1) * S
+        res.update(d_am=g[0], d_lm=g[1])
+    if want_occ:
+        occ = out.get("occ")
+        occ = occ if occ is not None else torch.empty(S, T, Umax + 1, device=dev)
+        assert occ.is_cuda and occ.dtype == torch.float32 and occ.is_contiguous() and tuple(occ.shape) == (S, T, Umax + 1)
+        res["occ"] = occ
+    _chk(lib.krnnt_simple_eval(am.data_ptr(), am.stride(0), lm.data_ptr(), lm.stride(0), T, S, Umax, V, lens_dev.data_ptr(), lab_dev.data_ptr(),
+                               off_dev.data_ptr(), int(blank), _ptr(g[0]), g[0].stride(0) if want_grads else 0, _ptr(g[1]),
+                               g[1].stride(0) if want_grads else 0, _ptr(occ), res["loss"].data_ptr(), _ptr(totals), ws.data_ptr(),
+                               ctypes.c_size_t(nbytes), _sp(stream)))
+    return res
+
+
+def rnnt_band_from_occupation(occ, lens, labels, R, stream=None):
+    """band_lo [S, T] int32 for rnnt_band_eval from node occupations occ [S, T, Umax+1] float32 CUDA (rnnt_simple_eval's): per frame the
+    R label positions that hold the most mass, made monotone and connected (krnnt_band_from_occupation states the rule).  A stream no
+    band of width R can serve gets a row of -1."""
+    import torch
+    assert occ.is_cuda and occ.dtype == torch.float32 and occ.dim() == 3 and occ.is_contiguous()
+    S, T, U1 = occ.shape
+    lens_dev = _lens_dev(lens, occ.device)
+    assert lens_dev.numel() == S
+    _, off_dev, _ = _packed(labels, S, occ.device)
+    band = torch.empty(S, T, dtype=torch.int32, device=occ.device)
+    _chk(load_library().krnnt_band_from_occupation(occ.data_ptr(), lens_dev.data_ptr(), off_dev.data_ptr(), T, S, U1 - 1, int(R),
+                                                   band.data_ptr(), _sp(stream)))
+    return band
+
+
 def rnnt_pack(labels, S, V, bos, embed=None, bias=None, Umax=None, device="cuda", stream=None):
     """The prediction network's input [(Umax+1)*S, width], row u*S + s from x_u (x_0 = bos, x_u = y_u): the one-hot over V columns, or
     with embed [D, V] (and bias [D]) the gathered column plus bias; rows without an input are zeros.  labels: S label sequences or
