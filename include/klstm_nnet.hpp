@@ -1158,14 +1158,16 @@ class Transducer : private CtcCallBase {
   // Eval inside a band: band_lo_dev [num_stream][T] on the device (BandFromFrames, or any valid band) and its width R.
   void EvalBanded(const DeviceMatrix &enc, const DeviceMatrix &pred, int32 num_stream, const std::vector<int32> &lens,
                   const std::vector<std::vector<int32> > &labels, const int32 *band_lo_dev, int32 R, TransducerJoint *joint, DeviceMatrix *d_enc,
-                  DeviceMatrix *d_pred) {
+                  DeviceMatrix *d_pred, bool bf16_joint = false) {   // bf16_joint: krnnt_band_eval_bf16 (klstm_rnnt.h, THE BF16 JOINT)
     const int32 *lens_dev = UploadLens(num_stream, lens);
     const int32 T = NumFrames(enc, num_stream, lens_dev, labels.size(), false), J = joint->JointDim(), V = joint->NumClasses();
     lab_.Upload(labels);
     const int32 Umax = (int32)lab_.longest;
     KLSTM_ASSERT(band_lo_dev && enc.NumCols() == J && pred.NumCols() == J && pred.NumRows() == (Umax + 1) * num_stream &&
                  (d_enc != nullptr) == (d_pred != nullptr));
-    const size_t need = d_enc ? krnnt_band_workspace_bytes(T, num_stream, Umax, R, J, V) : krnnt_band_forward_workspace_bytes(T, num_stream, R);
+    const size_t need = bf16_joint ? krnnt_band_bf16_workspace_bytes(T, num_stream, Umax, R, J, V, d_enc != nullptr)
+                        : d_enc    ? krnnt_band_workspace_bytes(T, num_stream, Umax, R, J, V)
+                                   : krnnt_band_forward_workspace_bytes(T, num_stream, R);
     void *ws = Workspace(need);
     loss_.Grow((size_t)num_stream * sizeof(BaseFloat));
     MatrixView e = enc.View(), p = pred.View(), de, dp;
@@ -1173,10 +1175,10 @@ class Transducer : private CtcCallBase {
       d_enc->Resize(enc.NumRows(), J, true); d_pred->Resize(pred.NumRows(), J, true);
       de = d_enc->View(); dp = d_pred->View();
     }
-    KCheck(krnnt_band_eval(e.Data(), e.Stride(), p.Data(), p.Stride(), joint->W(), joint->b(), T, num_stream, Umax, J, V, lens_dev, lab_.Labels(),
-                           lab_.Offsets(), blank_, R, band_lo_dev, d_enc ? de.Data() : nullptr, d_enc ? de.Stride() : 0,
-                           d_enc ? dp.Data() : nullptr, d_enc ? dp.Stride() : 0, d_enc ? joint->WGrad() : nullptr,
-                           d_enc ? joint->bGrad() : nullptr, loss_.As<BaseFloat>(), tot_.Dev(), ws, need, nullptr));
+    KCheck((bf16_joint ? krnnt_band_eval_bf16 : krnnt_band_eval)(
+        e.Data(), e.Stride(), p.Data(), p.Stride(), joint->W(), joint->b(), T, num_stream, Umax, J, V, lens_dev, lab_.Labels(), lab_.Offsets(),
+        blank_, R, band_lo_dev, d_enc ? de.Data() : nullptr, d_enc ? de.Stride() : 0, d_enc ? dp.Data() : nullptr, d_enc ? dp.Stride() : 0,
+        d_enc ? joint->WGrad() : nullptr, d_enc ? joint->bGrad() : nullptr, loss_.As<BaseFloat>(), tot_.Dev(), ws, need, nullptr));
     num_stream_ = num_stream;
   }
   // The simple-joiner loss (krnnt_simple_eval states it): am [T*S x V], lm [(Umax+1)*S x V].  d_am, d_lm (both or neither): the gradients,
@@ -1255,6 +1257,7 @@ struct TrainTransducerOptions {
   int32 band = 0;                                        // 0: the full lattice (krnnt_eval); R > 0: krnnt_band_eval in a band of R label positions
   const std::vector<std::vector<int32> > *label_frames = nullptr;   // with band: per utterance (indexed like utts) the frame of every label;
                                                          // null, or an absent or empty entry: the band follows the straight line
+  bool bf16_joint = false;                               // with band: krnnt_band_eval_bf16, the joint products in bf16; without band: an error
 };
 struct TrainTransducerStats {
   int32 num_done = 0, num_skipped = 0, num_minibatches = 0;
@@ -1279,6 +1282,7 @@ inline TrainTransducerStats TrainTransducerWholeUtterances(Nnet *encoder, Nnet *
   encoder->SetTrainOptions(o.trn_opts);
   predictor->SetTrainOptions(o.trn_opts);
   joint->SetTrainOptions(o.trn_opts);
+  if (o.bf16_joint && o.band <= 0) KLSTM_ERR("TrainTransducerWholeUtterances: bf16_joint needs band > 0: the full-lattice joint (krnnt_eval) has no bf16 variant");
   DropoutTrainingScope drop_enc(encoder, o.crossvalidate, o.dropout_retention, o.dropout_seed, o.dropout_per_sequence);
   DropoutTrainingScope drop_pred(predictor, o.crossvalidate, o.dropout_retention, o.dropout_seed + 1, o.dropout_per_sequence);
   Transducer tr(o.blank);
@@ -1295,7 +1299,7 @@ inline TrainTransducerStats TrainTransducerWholeUtterances(Nnet *encoder, Nnet *
             if (b.utt_index[s] >= 0 && (size_t)b.utt_index[s] < o.label_frames->size()) fr[s] = (*o.label_frames)[b.utt_index[s]];
           const int32 *band = tr.BandFromFrames(b.num_frames, b.num_stream, b.lens, b.labels, o.label_frames ? &fr : nullptr, o.band);
           tr.EvalBanded(enc_out, pred_out, b.num_stream, b.lens, b.labels, band, o.band, joint, o.crossvalidate ? nullptr : &d_enc,
-                        o.crossvalidate ? nullptr : &d_pred);
+                        o.crossvalidate ? nullptr : &d_pred, o.bf16_joint);
         } else
           tr.Eval(enc_out, pred_out, b.num_stream, b.lens, b.labels, joint, o.crossvalidate ? nullptr : &d_enc, o.crossvalidate ? nullptr : &d_pred);
         every_batch(b, enc_out, pred_out, tr);

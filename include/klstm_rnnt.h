@@ -130,6 +130,33 @@ klstm_status krnnt_band_eval(const float *enc, int enc_stride, const float *pred
 klstm_status krnnt_band_from_frames(const int *label_frames_dev, const int *lens_dev, const int *label_offsets_dev, int T, int S, int R, int left,
                                     int *band_lo_dev, void *hip_stream);
 
+/* THE BF16 JOINT (the torch yardstick: tests/rnnt_band_bf16_ref.py).  BAND-PRUNED TRAINING with the
+ * three joint products on the bf16 matrix instruction, f32 accumulation; inputs and outputs stay f32.  It is THE DEFINITION inside the
+ * band with three roundings, bf(x) = round to nearest even to bfloat16:
+ *     h  = tanh(enc[t] + pred[u]) in f32 ;  hb = bf(h) ;  Wb = bf(W), converted once per call
+ *     a  = Wb hb + b        products of bf16 values are exact, accumulated in f32 in a fixed order; b is f32
+ *     lse, lpb, lpy, alpha, beta, w_b, w_y, the loss: unchanged, from these a (the same lattice and weights kernels run on the planes)
+ *     g_v(t, u) in f32 as in THE DEFINITION ;  gb = bf(g)
+ *     dz     = (gb^T Wb) o (1 - h^2)   with the unrounded h: the rounding of h counts as the identity (straight-through)
+ *     W_grad = sum gb hb^T             f32 accumulation, the partials in a fixed order
+ *     b_grad = sum g                   unrounded, in double
+ *     d_enc, d_pred: the sums of dz as in BAND-PRUNED TRAINING
+ * Everything else is krnnt_band_eval's, word for word: the limits, the argument checks (all before the first HIP call), rejected and
+ * idle streams, the five totals, no floating-point atomics, bit-identical runs, a stream's loss and rows independent of its company,
+ * a node's logits the same bits in the forward and the backward kernel, everything asynchronous on hip_stream, nothing read back.
+ * J is a multiple of 16: the last k-panel of 32 may be half full and is zero-filled.
+ * THE WORKSPACE is krnnt_band_workspace_bytes (want_grads) or krnnt_band_forward_workspace_bytes (without) plus the bf16 copies of W,
+ * with Jp = J and Vp = V rounded up to a multiple of 32:
+ *           + up256(2 V Jp)                                Wb [V][Jp], zeros behind J                     (with and without gradients)
+ *           + up256(2 J Vp)                                its transpose [J][Vp], zeros behind V: the B operand of gb Wb   (gradients only)
+ * At J = 512, V = 1024: 2 MiB on top of the banded workspace.  0 (and the message) beyond the limits. */
+size_t krnnt_band_bf16_workspace_bytes(int T, int S, int Umax, int R, int J, int V, int want_grads);
+klstm_status krnnt_band_eval_bf16(const float *enc, int enc_stride, const float *pred, int pred_stride, const float *W, const float *b, int T, int S,
+                                  int Umax, int J, int V, const int *lens_dev, const int *labels_dev, const int *label_offsets_dev, int blank,
+                                  int R, const int *band_lo_dev, float *d_enc, int d_enc_stride, float *d_pred, int d_pred_stride, float *W_grad,
+                                  float *b_grad, float *utt_loss_dev, double *totals_dev, void *workspace, size_t workspace_bytes,
+                                  void *hip_stream);
+
 /* THE SIMPLE JOINER (the torch yardstick: tests/rnnt_simple_ref.py).  The first pass of pruned
  * transducer training: a joiner without tanh and without W, whose logits are the sum of an encoder-side and a predictor-side row, is
  * evaluated over the whole lattice; its node occupations select the band that krnnt_band_eval then runs the real joint in.  Per stream s:

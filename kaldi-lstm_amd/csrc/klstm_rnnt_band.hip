@@ -44,34 +44,11 @@
 #include <cstdint>
 
 #include "../../include/klstm_rnnt.h"
-#include "klstm_ctc_host.h"
-#include "klstm_host.h"
 #include "klstm_kernels.h"
 #include "klstm_math.h"
-#include "klstm_rnnt_dev.h"
+#include "klstm_rnnt_band_dev.h"            // the tile constants, BandWs, BandArgs and the device code shared with klstm_rnnt_band16.hip
 
 namespace klstm {
-
-constexpr int BR = KRNNT_BAND_TILE_R;       // band offsets of a forward tile (RT, VP, NVT, KP, WPS and RLOG0: klstm_rnnt_dev.h)
-constexpr int BBU = 4, BGS = VP + 2;        // offsets per backward step (one per wave), floats per row of the g tile
-constexpr int OFFS_U = 1024;                // the offsets are sized for Umax = 1023: the forward workspace does not depend on Umax
-
-struct BandWs {
-  int4 *meta; double *loss, *offs;
-  float *lpb, *lpy, *lse, *A, *B, *wb, *wy, *dpp, *wpart;
-  double *bpart;
-};
-
-struct BandArgs {
-  const float *enc, *pred, *W, *b;
-  int enc_stride, pred_stride, T, S, U1, J, V, blank, R;
-  const int *lens, *labels, *loff, *band;
-  float *d_enc, *d_pred, *Wg, *bg;
-  int de_stride, dp_stride;
-  float *utt_loss; double *totals;
-  BandWs ws;
-  int splits, ntb, prow, L;                 // prow: window rows per stream, L: offsets per (stream, direction)
-};
 
 static int band_splits(int J, int V) {
   const long long s = (1ll << 24) / ((long long)V * J);
@@ -79,7 +56,7 @@ static int band_splits(int J, int V) {
 }
 
 // the layout of the workspace (include/klstm_rnnt.h states the formula); base null: only bytes() counts
-static BandWs band_carve(void *base, int T, int S, int U1, int R, int J, int V, bool grads, size_t *bytes) {
+BandWs band_carve(void *base, int T, int S, int U1, int R, int J, int V, bool grads, size_t *bytes) {
   CtcCarver c(base);
   BandWs w;
   const size_t N = (size_t)S * T * R, ntb = (size_t)(T + RT - 1) / RT;
@@ -128,19 +105,6 @@ __global__ __launch_bounds__(256) void k_rband_prep(BandArgs a) {
   if (tid == 0) {
     if (st == 1 && bad) st = -1;
     a.ws.meta[s] = make_int4(st, st == 1 ? Ts : 0, st == 1 ? U : 0, o0);
-  }
-}
-
-// u of the tile's nodes into LDS: node = 16 (r - r0) + frame; -1: no such node
-__device__ __forceinline__ void band_nodes(int *nodeU, int nnode, const int *u0, int t0, int r0, int Ts, int U, int R) {
-  if ((int)threadIdx.x < nnode) {
-    const int t = t0 + (threadIdx.x & 15), r = r0 + (threadIdx.x >> 4);
-    int u = -1;
-    if (t < Ts && r < R) {
-      const int c = u0[t] + r;
-      if (c <= U) u = c;
-    }
-    nodeU[threadIdx.x] = u;
   }
 }
 
@@ -644,7 +608,7 @@ __global__ __launch_bounds__(256) void k_rband_from_frames(const int *frames, co
 
 static bool band_al4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
-static const char *band_limits(int T, int S, int Umax, int R, int J, int V) {
+const char *band_limits(int T, int S, int Umax, int R, int J, int V) {
   if (S < 1 || S > 32) return "1 <= S <= 32";
   if (T < 1) return "1 <= T";
   if (Umax < 0 || Umax > 1023) return "0 <= Umax <= 1023";
@@ -653,6 +617,55 @@ static const char *band_limits(int T, int S, int Umax, int R, int J, int V) {
   if (J < 16 || J > 1024 || J % 16 != 0) return "16 <= J <= 1024, J % 16 == 0";
   if (V < 2 || V > 4096) return "2 <= V <= 4096";
   return nullptr;
+}
+
+klstm_status band_eval_args(const char *name, const float *enc, int enc_stride, const float *pred, int pred_stride, const float *W, const float *b,
+                            int T, int S, int Umax, int J, int V, const int *lens_dev, const int *labels_dev, const int *label_offsets_dev, int blank,
+                            int R, const int *band_lo_dev, float *d_enc, int d_enc_stride, float *d_pred, int d_pred_stride, float *W_grad,
+                            float *b_grad, float *utt_loss_dev, double *totals_dev, void *workspace, size_t workspace_bytes, size_t extra, BandArgs *out,
+                            int *ngrad_out, size_t *band_bytes) {
+  if (const char *why = band_limits(T, S, Umax, R, J, V))
+    return fail(KLSTM_ERR_SHAPE, "%s: T %d, S %d, Umax %d, R %d, J %d, V %d: the limit is %s", name, T, S, Umax, R, J, V, why);
+  if (blank < 0 || blank >= V) return fail(KLSTM_ERR_SHAPE, "%s: blank %d outside [0, %d)", name, blank, V);
+  if (!enc || !pred || !W || !b || !lens_dev || !labels_dev || !label_offsets_dev || !band_lo_dev || !utt_loss_dev || !workspace)
+    return fail(KLSTM_ERR_ARG, "%s: null argument", name);
+  const int ngrad = (d_enc != nullptr) + (d_pred != nullptr) + (W_grad != nullptr) + (b_grad != nullptr);
+  if (ngrad != 0 && ngrad != 4) return fail(KLSTM_ERR_ARG, "%s: the four gradient outputs are given together or not at all", name);
+  if (enc_stride < J || pred_stride < J || (ngrad && (d_enc_stride < J || d_pred_stride < J)))
+    return fail(KLSTM_ERR_ARG, "%s: row stride below the width %d (%d, %d, %d, %d)", name, J, enc_stride, pred_stride, d_enc_stride, d_pred_stride);
+  if (!band_al4(enc) || !band_al4(pred) || !band_al4(W) || !band_al4(b) || !band_al4(d_enc) || !band_al4(d_pred) || !band_al4(W_grad) ||
+      !band_al4(b_grad) || !band_al4(utt_loss_dev) || !band_al4(band_lo_dev) || (reinterpret_cast<uintptr_t>(totals_dev) & 7))
+    return fail(KLSTM_ERR_ARG, "%s: misaligned pointer", name);
+  BandArgs a;
+  size_t need = 0;
+  a.ws = band_carve(workspace, T, S, Umax + 1, R, J, V, ngrad != 0, &need);
+  *band_bytes = need;
+  need += extra;
+  if (workspace_bytes < need) return fail(KLSTM_ERR_ARG, "%s: workspace of %zu bytes, %zu needed", name, workspace_bytes, need);
+  if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(KLSTM_ERR_ARG, "%s: the workspace is not 256-byte aligned", name);
+  a.enc = enc; a.pred = pred; a.W = W; a.b = b; a.enc_stride = enc_stride; a.pred_stride = pred_stride;
+  a.T = T; a.S = S; a.U1 = Umax + 1; a.J = J; a.V = V; a.blank = blank; a.R = R;
+  a.lens = lens_dev; a.labels = labels_dev; a.loff = label_offsets_dev; a.band = band_lo_dev;
+  a.d_enc = d_enc; a.d_pred = d_pred; a.Wg = W_grad; a.bg = b_grad; a.de_stride = d_enc_stride; a.dp_stride = d_pred_stride;
+  a.utt_loss = utt_loss_dev; a.totals = totals_dev;
+  a.splits = band_splits(J, V); a.ntb = (T + RT - 1) / RT; a.prow = a.U1 + a.ntb * R; a.L = T + OFFS_U;
+  *out = a;
+  *ngrad_out = ngrad;
+  return KLSTM_OK;
+}
+
+hipError_t band_launch_prep(const BandArgs &a, hipStream_t st) { return launch(k_rband_prep, dim3(a.S), dim3(256), 0, st, LaunchProbe(), a); }
+
+hipError_t band_launch_lattice(const BandArgs &a, hipStream_t st) {
+  const size_t N = (size_t)a.S * a.T * a.R;
+  const hipError_t e = launch(k_rband_lattice, dim3(a.S, 2), dim3(64), 0, st, LaunchProbe(), a);
+  return e != hipSuccess ? e : launch(k_rband_weights, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, LaunchProbe(), a);
+}
+
+hipError_t band_launch_finish(const BandArgs &a, hipStream_t st) {
+  const size_t nfin = (size_t)a.S * a.T * a.J + (size_t)a.S * a.U1 * a.J + (size_t)a.V * a.J + a.V;
+  const size_t gfin = (nfin + 255) / 256;
+  return launch(k_rband_finish, dim3((unsigned)(gfin < 4096 ? gfin : 4096)), dim3(256), 0, st, LaunchProbe(), a);
 }
 
 }  // namespace klstm
@@ -685,44 +698,23 @@ klstm_status krnnt_band_eval(const float *enc, int enc_stride, const float *pred
                              int Umax, int J, int V, const int *lens_dev, const int *labels_dev, const int *label_offsets_dev, int blank, int R,
                              const int *band_lo_dev, float *d_enc, int d_enc_stride, float *d_pred, int d_pred_stride, float *W_grad,
                              float *b_grad, float *utt_loss_dev, double *totals_dev, void *workspace, size_t workspace_bytes, void *hip_stream) {
-  if (const char *why = band_limits(T, S, Umax, R, J, V))
-    return fail(KLSTM_ERR_SHAPE, "krnnt_band_eval: T %d, S %d, Umax %d, R %d, J %d, V %d: the limit is %s", T, S, Umax, R, J, V, why);
-  if (blank < 0 || blank >= V) return fail(KLSTM_ERR_SHAPE, "krnnt_band_eval: blank %d outside [0, %d)", blank, V);
-  if (!enc || !pred || !W || !b || !lens_dev || !labels_dev || !label_offsets_dev || !band_lo_dev || !utt_loss_dev || !workspace)
-    return fail(KLSTM_ERR_ARG, "krnnt_band_eval: null argument");
-  const int ngrad = (d_enc != nullptr) + (d_pred != nullptr) + (W_grad != nullptr) + (b_grad != nullptr);
-  if (ngrad != 0 && ngrad != 4) return fail(KLSTM_ERR_ARG, "krnnt_band_eval: the four gradient outputs are given together or not at all");
-  if (enc_stride < J || pred_stride < J || (ngrad && (d_enc_stride < J || d_pred_stride < J)))
-    return fail(KLSTM_ERR_ARG, "krnnt_band_eval: row stride below the width %d (%d, %d, %d, %d)", J, enc_stride, pred_stride, d_enc_stride,
-                d_pred_stride);
-  if (!band_al4(enc) || !band_al4(pred) || !band_al4(W) || !band_al4(b) || !band_al4(d_enc) || !band_al4(d_pred) || !band_al4(W_grad) ||
-      !band_al4(b_grad) || !band_al4(utt_loss_dev) || !band_al4(band_lo_dev) || (reinterpret_cast<uintptr_t>(totals_dev) & 7))
-    return fail(KLSTM_ERR_ARG, "krnnt_band_eval: misaligned pointer");
   BandArgs a;
-  size_t need = 0;
-  a.ws = band_carve(workspace, T, S, Umax + 1, R, J, V, ngrad != 0, &need);
-  if (workspace_bytes < need) return fail(KLSTM_ERR_ARG, "krnnt_band_eval: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-  if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(KLSTM_ERR_ARG, "krnnt_band_eval: the workspace is not 256-byte aligned");
-  a.enc = enc; a.pred = pred; a.W = W; a.b = b; a.enc_stride = enc_stride; a.pred_stride = pred_stride;
-  a.T = T; a.S = S; a.U1 = Umax + 1; a.J = J; a.V = V; a.blank = blank; a.R = R;
-  a.lens = lens_dev; a.labels = labels_dev; a.loff = label_offsets_dev; a.band = band_lo_dev;
-  a.d_enc = d_enc; a.d_pred = d_pred; a.Wg = W_grad; a.bg = b_grad; a.de_stride = d_enc_stride; a.dp_stride = d_pred_stride;
-  a.utt_loss = utt_loss_dev; a.totals = totals_dev;
-  a.splits = band_splits(J, V); a.ntb = (T + RT - 1) / RT; a.prow = a.U1 + a.ntb * R; a.L = T + OFFS_U;
+  int ngrad = 0;
+  size_t band_bytes = 0;
+  const klstm_status bad = band_eval_args("krnnt_band_eval", enc, enc_stride, pred, pred_stride, W, b, T, S, Umax, J, V, lens_dev, labels_dev,
+                                          label_offsets_dev, blank, R, band_lo_dev, d_enc, d_enc_stride, d_pred, d_pred_stride, W_grad, b_grad,
+                                          utt_loss_dev, totals_dev, workspace, workspace_bytes, 0, &a, &ngrad, &band_bytes);
+  if (bad != KLSTM_OK) return bad;
   hipStream_t st = (hipStream_t)hip_stream;
-  const size_t N = (size_t)S * T * R;
-  HIPCHK(launch(k_rband_prep, dim3(S), dim3(256), 0, st, LaunchProbe(), a));
+  HIPCHK(band_launch_prep(a, st));
   HIPCHK(launch(k_rband_joint_fwd, dim3(a.ntb, (R + BR - 1) / BR, S), dim3(256), 0, st, LaunchProbe(), a));
-  HIPCHK(launch(k_rband_lattice, dim3(S, 2), dim3(64), 0, st, LaunchProbe(), a));
-  HIPCHK(launch(k_rband_weights, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, LaunchProbe(), a));
+  HIPCHK(band_launch_lattice(a, st));
   if (!ngrad) return KLSTM_OK;
   const size_t shm = ((size_t)RT * (J + 2) + VP * WPS + 64 * WPS + 64 * BGS + 64) * sizeof(float);
   if (J <= 128) HIPCHK(launch(k_rband_joint_bwd<8>, dim3(a.splits), dim3(256), shm, st, LaunchProbe(), a));
   else if (J <= 512) HIPCHK(launch(k_rband_joint_bwd<32>, dim3(a.splits), dim3(256), shm, st, LaunchProbe(), a));
   else HIPCHK(launch(k_rband_joint_bwd<64>, dim3(a.splits), dim3(256), shm, st, LaunchProbe(), a));
-  const size_t nfin = (size_t)S * T * J + (size_t)S * a.U1 * J + (size_t)V * J + V;
-  const size_t gfin = (nfin + 255) / 256;
-  HIPCHK(launch(k_rband_finish, dim3((unsigned)(gfin < 4096 ? gfin : 4096)), dim3(256), 0, st, LaunchProbe(), a));
+  HIPCHK(band_launch_finish(a, st));
   return KLSTM_OK;
 }
 

@@ -69,9 +69,17 @@ def rnnt_eval(enc, pred, W, b, lens, labels, blank=0, want_grads=True, totals=No
     return res
 
 
-def rnnt_band_workspace_bytes(T, S, Umax, R, J, V, want_grads=True):
+def _band_precision(precision):
+    if precision not in ("f32", "bf16"):
+        raise ValueError("precision %r: the band-pruned joint runs in 'f32' or 'bf16'" % (precision,))
+    return precision == "bf16"
+
+
+def rnnt_band_workspace_bytes(T, S, Umax, R, J, V, want_grads=True, precision="f32"):
     """bytes of workspace krnnt_band_eval needs (include/klstm_rnnt.h gives the formula: no term in T (Umax+1)); without gradients
-    Umax, J and V do not enter it"""
+    Umax, J and V do not enter it.  precision "bf16": what krnnt_band_eval_bf16 needs (the bf16 copies of W on top)"""
+    if _band_precision(precision):
+        return _workspace_bytes("krnnt_band_bf16_workspace_bytes", T, S, Umax, R, J, V, bool(want_grads))
     full = _workspace_bytes("krnnt_band_workspace_bytes", T, S, Umax, R, J, V)      # the limits on Umax, J and V hold either way
     return full if want_grads else _workspace_bytes("krnnt_band_forward_workspace_bytes", T, S, R)
 
@@ -108,10 +116,12 @@ def rnnt_band_from_frames(lens, labels, R, frames=None, left=None, T=None, devic
     return band
 
 
-def rnnt_band_eval(enc, pred, W, b, lens, labels, band_lo, R, blank=0, want_grads=True, totals=None, stream=None, out=None):
+def rnnt_band_eval(enc, pred, W, b, lens, labels, band_lo, R, blank=0, want_grads=True, totals=None, stream=None, out=None, precision="f32"):
     """rnnt_eval inside a band: band_lo [S, T] int32 CUDA (rnnt_band_from_frames, or any valid band: klstm_rnnt.h) and its width R.
-    Arguments and the returned dict are those of rnnt_eval; a stream whose band is not valid is rejected like one with a bad label."""
+    Arguments and the returned dict are those of rnnt_eval; a stream whose band is not valid is rejected like one with a bad label.
+    precision "bf16": the three joint products on the bf16 matrix instruction (krnnt_band_eval_bf16; klstm_rnnt.h, THE BF16 JOINT)."""
     import torch
+    bf16 = _band_precision(precision)
     lib, dev = load_library(), enc.device
     _rows(enc)
     J = enc.shape[1]
@@ -126,8 +136,8 @@ def rnnt_band_eval(enc, pred, W, b, lens, labels, band_lo, R, blank=0, want_grad
     assert band_lo.is_cuda and band_lo.dtype == torch.int32 and band_lo.is_contiguous() and tuple(band_lo.shape) == (S, T)
     lab_dev, off_dev, _ = _packed(labels, S, dev)
     _check_totals(totals, 5)
-    nbytes = rnnt_band_workspace_bytes(T, S, Umax, R, J, V, want_grads)
-    ws = _workspace("rnnt_band", (T, S, Umax, R, J, V, bool(want_grads)), nbytes, dev)
+    nbytes = rnnt_band_workspace_bytes(T, S, Umax, R, J, V, want_grads, precision)
+    ws = _workspace("rnnt_band", (T, S, Umax, R, J, V, bool(want_grads), precision), nbytes, dev)
     res = {"loss": torch.empty(S, device=dev)}
     g = [None] * 4
     if want_grads:
@@ -138,10 +148,11 @@ def rnnt_band_eval(enc, pred, W, b, lens, labels, band_lo, R, blank=0, want_grad
         _rows(g[0], J), _rows(g[1], J)
         assert g[0].shape[0] == T * S and g[1].shape[0] == (Umax + 1) * S and g[2].is_contiguous() and g[2].shape == (V, J) and g[3].numel() == V
         res.update(d_enc=g[0], d_pred=g[1], W_grad=g[2], b_grad=g[3])
-    _chk(lib.krnnt_band_eval(enc.data_ptr(), enc.stride(0), pred.data_ptr(), pred.stride(0), W.data_ptr(), b.data_ptr(), T, S, Umax, J, V,
-                             lens_dev.data_ptr(), lab_dev.data_ptr(), off_dev.data_ptr(), int(blank), R, band_lo.data_ptr(), _ptr(g[0]),
-                             g[0].stride(0) if want_grads else 0, _ptr(g[1]), g[1].stride(0) if want_grads else 0, _ptr(g[2]), _ptr(g[3]),
-                             res["loss"].data_ptr(), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    entry = lib.krnnt_band_eval_bf16 if bf16 else lib.krnnt_band_eval
+    _chk(entry(enc.data_ptr(), enc.stride(0), pred.data_ptr(), pred.stride(0), W.data_ptr(), b.data_ptr(), T, S, Umax, J, V,
+               lens_dev.data_ptr(), lab_dev.data_ptr(), off_dev.data_ptr(), int(blank), R, band_lo.data_ptr(), _ptr(g[0]),
+               g[0].stride(0) if want_grads else 0, _ptr(g[1]), g[1].stride(0) if want_grads else 0, _ptr(g[2]), _ptr(g[3]),
+               res["loss"].data_ptr(), _ptr(totals), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
     return res
 
 
