@@ -1181,6 +1181,33 @@ class Transducer : private CtcCallBase {
         d_enc ? joint->WGrad() : nullptr, d_enc ? joint->bGrad() : nullptr, loss_.As<BaseFloat>(), tot_.Dev(), ws, need, nullptr));
     num_stream_ = num_stream;
   }
+  // The best alignment of the labels (klstm_rnnt.h, FORCED ALIGNMENT): enc, pred, lens, labels as in Eval.  Align: the full lattice
+  // (krnnt_align); AlignBanded: inside band_lo_dev of width R (krnnt_band_align), bf16_joint: on the bf16 joint's log-probabilities.
+  // The frames stay on the device, packed like the labels: AlignFrames() is what krnnt_band_from_frames takes as label_frames_dev.
+  void Align(const DeviceMatrix &enc, const DeviceMatrix &pred, int32 num_stream, const std::vector<int32> &lens,
+             const std::vector<std::vector<int32> > &labels, TransducerJoint *joint) {
+    AlignCall(enc, pred, num_stream, lens, labels, nullptr, 0, joint, false);
+  }
+  void AlignBanded(const DeviceMatrix &enc, const DeviceMatrix &pred, int32 num_stream, const std::vector<int32> &lens,
+                   const std::vector<std::vector<int32> > &labels, const int32 *band_lo_dev, int32 R, TransducerJoint *joint,
+                   bool bf16_joint = false) {
+    KLSTM_ASSERT(band_lo_dev);
+    AlignCall(enc, pred, num_stream, lens, labels, band_lo_dev, R, joint, bf16_joint);
+  }
+  const int32 *AlignFrames() const { return align_frames_.As<int32>(); }
+  // per stream of the last Align / AlignBanded: the frame and the log-probability of every label step (either may be null) and the
+  // best path's log-probability (0, and zeros for its labels: an idle or rejected stream).  Synchronises.
+  void Alignment(std::vector<std::vector<int32> > *frames, std::vector<std::vector<BaseFloat> > *logp, std::vector<BaseFloat> *score) const {
+    std::vector<int32> f(lab_.num_labels);
+    std::vector<BaseFloat> l(lab_.num_labels);
+    align_frames_.Download(f.data(), f.size());
+    align_logp_.Download(l.data(), l.size());
+    if (score) { score->assign(num_stream_, 0.f); align_score_.Download(score->data(), score->size()); }
+    for (int32 s = 0; s < num_stream_; s++) {
+      if (frames) { if (s == 0) frames->clear(); frames->emplace_back(f.begin() + lab_.offsets[s], f.begin() + lab_.offsets[s + 1]); }
+      if (logp) { if (s == 0) logp->clear(); logp->emplace_back(l.begin() + lab_.offsets[s], l.begin() + lab_.offsets[s + 1]); }
+    }
+  }
   // The simple-joiner loss (krnnt_simple_eval states it): am [T*S x V], lm [(Umax+1)*S x V].  d_am, d_lm (both or neither): the gradients,
   // zero on the rows of idle and rejected streams.  want_occ: the node occupations [num_stream][T][Umax+1] stay on the device for
   // BandFromOccupation (the pointer is returned; null without).
@@ -1242,8 +1269,31 @@ class Transducer : private CtcCallBase {
     for (int32 i = 0; i < s; i++) o += labels[i].size();
     return o;
   }
+  void AlignCall(const DeviceMatrix &enc, const DeviceMatrix &pred, int32 num_stream, const std::vector<int32> &lens,
+                 const std::vector<std::vector<int32> > &labels, const int32 *band_lo_dev, int32 R, TransducerJoint *joint, bool bf16_joint) {
+    const int32 *lens_dev = UploadLens(num_stream, lens);
+    const int32 T = NumFrames(enc, num_stream, lens_dev, labels.size(), false), J = joint->JointDim(), V = joint->NumClasses();
+    lab_.Upload(labels);
+    const int32 Umax = (int32)lab_.longest;
+    KLSTM_ASSERT(enc.NumCols() == J && pred.NumCols() == J && pred.NumRows() == (Umax + 1) * num_stream);
+    const size_t need = band_lo_dev ? krnnt_band_align_workspace_bytes(T, num_stream, R, J, V, bf16_joint) : krnnt_align_workspace_bytes(T, num_stream, Umax);
+    void *ws = Workspace(need);
+    const size_t n = std::max<size_t>(lab_.num_labels, 1);
+    align_frames_.Grow(n * sizeof(int32)); align_logp_.Grow(n * sizeof(BaseFloat)); align_score_.Grow((size_t)num_stream * sizeof(BaseFloat));
+    KCheck(klstm_memset_zero(align_frames_.As<int32>(), n * sizeof(int32), nullptr));       // a rejected stream's entries are left alone by the call
+    KCheck(klstm_memset_zero(align_logp_.As<BaseFloat>(), n * sizeof(BaseFloat), nullptr));
+    MatrixView e = enc.View(), p = pred.View();
+    if (band_lo_dev)
+      KCheck(krnnt_band_align(e.Data(), e.Stride(), p.Data(), p.Stride(), joint->W(), joint->b(), T, num_stream, Umax, J, V, lens_dev, lab_.Labels(),
+                              lab_.Offsets(), blank_, R, band_lo_dev, bf16_joint, align_frames_.As<int32>(), align_logp_.As<BaseFloat>(),
+                              align_score_.As<BaseFloat>(), ws, need, nullptr));
+    else
+      KCheck(krnnt_align(e.Data(), e.Stride(), p.Data(), p.Stride(), joint->W(), joint->b(), T, num_stream, Umax, J, V, lens_dev, lab_.Labels(),
+                         lab_.Offsets(), blank_, align_frames_.As<int32>(), align_logp_.As<BaseFloat>(), align_score_.As<BaseFloat>(), ws, need, nullptr));
+    num_stream_ = num_stream;
+  }
   PackedLabels lab_;
-  DeviceBuffer loss_, frames_, band_, occ_;
+  DeviceBuffer loss_, frames_, band_, occ_, align_frames_, align_logp_, align_score_;
   DeviceTotals<5> tot_;
 };
 

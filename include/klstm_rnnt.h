@@ -157,6 +157,38 @@ klstm_status krnnt_band_eval_bf16(const float *enc, int enc_stride, const float 
                                   float *b_grad, float *utt_loss_dev, double *totals_dev, void *workspace, size_t workspace_bytes,
                                   void *hip_stream);
 
+/* FORCED ALIGNMENT (the torch yardstick: tests/rnnt_align_ref.py).  The best single alignment of the
+ * given labels: where the model puts its transcript.  Per stream, with lpb, lpy as in THE DEFINITION (krnnt_band_align: as in BAND-PRUNED
+ * TRAINING, every node outside the band is log 0; with bf16 != 0 lpb, lpy are those of THE BF16 JOINT, Wb converted once per call):
+ *     v(0,0)  = 0
+ *     v(t,u)  = max( v(t-1,u) + lpb(t-1,u) ,  v(t,u-1) + lpy(t,u-1) )
+ * carried in double.  The label step is taken iff its candidate is strictly greater (`>`): a tie takes the blank step, and a candidate
+ * that is log 0 never wins.
+ *     score_s = v(T_s-1, U) + lpb(T_s-1, U)         the log-probability of the best alignment, given as a float
+ *     path    : the backtrace from (T_s-1, U) to (0,0)
+ *     f_i     = the frame t of the label step into node (t, i), i = 1 .. U
+ *     logp_i  = lpy(f_i, i-1)
+ * f is nondecreasing within [0, T_s): what krnnt_band_from_frames accepts as label_frames_dev.  label_frames_dev and label_logp_dev (may
+ * be NULL) are CSR by label_offsets_dev, indexed like labels_dev; score_dev [S].  No diagonal is normalised: a max-plus value is a sum of
+ * at most T + U floats.  A REJECTED stream (the rules of krnnt_eval; krnnt_band_align: and an invalid band) and an idle stream get score
+ * 0 and their entries of label_frames_dev and label_logp_dev stay untouched.  No atomics: runs are bit-identical and a stream's result
+ * does not depend on its company.  Every check runs before the first HIP call; everything is asynchronous on hip_stream; nothing is read
+ * back.  LIMITS and argument checks: krnnt_align those of krnnt_eval, krnnt_band_align those of krnnt_band_eval.
+ * The decisions are kept as bits, one 64-bit word per (diagonal, wave of 64 label positions), not as a plane of nodes, and neither
+ * workspace has a term in N V or N J; the banded one has none in T (Umax+1):
+ *     krnnt_align:       up256(16 S) + 3 up256(4 S T (Umax+1)) + up256(8 S (T+Umax+1) ceil((Umax+1)/64))      meta; lpb, lpy, lse; the words
+ *     krnnt_band_align:  up256(16 S) + 3 up256(4 S T R) + up256(8 S (T+1024))  [+ up256(2 V Jp) with bf16, Jp = J rounded up to 32] */
+size_t krnnt_align_workspace_bytes(int T, int S, int Umax);
+klstm_status krnnt_align(const float *enc, int enc_stride, const float *pred, int pred_stride, const float *W, const float *b, int T, int S,
+                         int Umax, int J, int V, const int *lens_dev, const int *labels_dev, const int *label_offsets_dev, int blank,
+                         int *label_frames_dev, float *label_logp_dev, float *score_dev, void *workspace, size_t workspace_bytes,
+                         void *hip_stream);
+size_t krnnt_band_align_workspace_bytes(int T, int S, int R, int J, int V, int bf16);
+klstm_status krnnt_band_align(const float *enc, int enc_stride, const float *pred, int pred_stride, const float *W, const float *b, int T, int S,
+                              int Umax, int J, int V, const int *lens_dev, const int *labels_dev, const int *label_offsets_dev, int blank, int R,
+                              const int *band_lo_dev, int bf16, int *label_frames_dev, float *label_logp_dev, float *score_dev, void *workspace,
+                              size_t workspace_bytes, void *hip_stream);
+
 /* THE SIMPLE JOINER (the torch yardstick: tests/rnnt_simple_ref.py).  The first pass of pruned
  * transducer training: a joiner without tanh and without W, whose logits are the sum of an encoder-side and a predictor-side row, is
  * evaluated over the whole lattice; its node occupations select the band that krnnt_band_eval then runs the real joint in.  Per stream s:

@@ -29,6 +29,7 @@ from .cnn import (Convolutional, MaxPooling, Sigmoid, Tanh, activation, activati
                   conv_plan, conv_propagate, conv_update, conv_workspace_floats, pool_backpropagate, pool_propagate)
 from .rnnt import rnnt_eval, rnnt_grad_splits, rnnt_pack, rnnt_workspace_bytes  # noqa: F401,E402
 from .rnnt import rnnt_band_eval, rnnt_band_from_frames, rnnt_band_workspace_bytes  # noqa: F401,E402
+from .rnnt import rnnt_align, rnnt_align_workspace_bytes  # noqa: F401,E402
 from .rnnt import rnnt_band_from_occupation, rnnt_simple_eval, rnnt_simple_workspace_bytes  # noqa: F401,E402
 from .rnnt import rnnt_greedy_begin, rnnt_greedy_decode, rnnt_greedy_state_bytes, rnnt_greedy_step  # noqa: F401,E402
 from .rnnt import rnnt_beam_begin, rnnt_beam_decode, rnnt_beam_state_bytes, rnnt_beam_step  # noqa: F401,E402

@@ -193,6 +193,12 @@ def load_library():
     lib.krnnt_band_bf16_workspace_bytes.argtypes = [I, I, I, I, I, I, I]
     lib.krnnt_band_bf16_workspace_bytes.restype = Z
     lib.krnnt_band_eval_bf16.argtypes = lib.krnnt_band_eval.argtypes
+    lib.krnnt_align_workspace_bytes.argtypes = [I, I, I]
+    lib.krnnt_align_workspace_bytes.restype = Z
+    lib.krnnt_align.argtypes = [P, I, P, I, P, P, I, I, I, I, I, P, P, P, I, P, P, P, P, Z, P]
+    lib.krnnt_band_align_workspace_bytes.argtypes = [I, I, I, I, I, I]
+    lib.krnnt_band_align_workspace_bytes.restype = Z
+    lib.krnnt_band_align.argtypes = [P, I, P, I, P, P, I, I, I, I, I, P, P, P, I, I, P, I, P, P, P, P, Z, P]
     lib.krnnt_band_from_frames.argtypes = [P, P, P, I, I, I, I, P, P]
     lib.krnnt_simple_workspace_bytes.argtypes = [I, I, I, I]
     lib.krnnt_simple_workspace_bytes.restype = Z

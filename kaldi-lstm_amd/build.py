@@ -13,7 +13,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = ["csrc/klstm_kernels.hip", "csrc/klstm_gemm.hip", "csrc/klstm_grads.hip", "csrc/klstm_output.hip", "csrc/klstm_persist.hip", "csrc/klstm_persist_bwd.hip", "csrc/klstm_persist_ms.hip", "csrc/klstm_persist_xl.hip", "csrc/klstm_fold.hip", "csrc/klstm_fold3.hip", "csrc/klstm_oneshot.hip", "csrc/klstm_outer.hip", "csrc/klstm_gemm16.hip", "csrc/klstm_score.hip", "csrc/klstm_ctc.hip", "csrc/klstm_ctc_decode.hip", "csrc/klstm_ctc_align.hip", "csrc/klstm_ctc_beam.hip", "csrc/klstm_ctc_mbr.hip", "csrc/klstm_ctc_mmi.hip", "csrc/klstm_ctc_consensus.hip", "csrc/klstm_ctc_rescore.hip", "csrc/klstm_ctc_nlm.hip", "csrc/klstm_dropout.hip", "csrc/klstm_cnn.hip", "csrc/klstm_rnnt.hip", "csrc/klstm_rnnt_decode.hip", "csrc/klstm_rnnt_beam.hip", "csrc/klstm_rnnt_band.hip", "csrc/klstm_rnnt_band16.hip", "csrc/klstm_rnnt_simple.hip",
+SRCS = ["csrc/klstm_kernels.hip", "csrc/klstm_gemm.hip", "csrc/klstm_grads.hip", "csrc/klstm_output.hip", "csrc/klstm_persist.hip", "csrc/klstm_persist_bwd.hip", "csrc/klstm_persist_ms.hip", "csrc/klstm_persist_xl.hip", "csrc/klstm_fold.hip", "csrc/klstm_fold3.hip", "csrc/klstm_oneshot.hip", "csrc/klstm_outer.hip", "csrc/klstm_gemm16.hip", "csrc/klstm_score.hip", "csrc/klstm_ctc.hip", "csrc/klstm_ctc_decode.hip", "csrc/klstm_ctc_align.hip", "csrc/klstm_ctc_beam.hip", "csrc/klstm_ctc_mbr.hip", "csrc/klstm_ctc_mmi.hip", "csrc/klstm_ctc_consensus.hip", "csrc/klstm_ctc_rescore.hip", "csrc/klstm_ctc_nlm.hip", "csrc/klstm_dropout.hip", "csrc/klstm_cnn.hip", "csrc/klstm_rnnt.hip", "csrc/klstm_rnnt_decode.hip", "csrc/klstm_rnnt_beam.hip", "csrc/klstm_rnnt_band.hip", "csrc/klstm_rnnt_band16.hip", "csrc/klstm_rnnt_simple.hip", "csrc/klstm_rnnt_align.hip",
         "csrc/klstm_api_ops.hip", "csrc/klstm_api_ctc.hip", "csrc/klstm_comm.hip", "csrc/klstm_engine.hip"]
 HDRS = ["csrc/klstm_kernels.h", "csrc/klstm_step_dev.h", "csrc/klstm_gemm_dev.h", "csrc/klstm_host.h","csrc/klstm_math.h", "csrc/klstm_persist_dev.h", "csrc/klstm_ctc_dev.h", "csrc/klstm_ctc_host.h", "csrc/klstm_ctc_nbest.h", "csrc/klstm_ctc_beam_frame.h", "csrc/klstm_ctc_slm.h", "csrc/klstm_rnnt_dev.h", "csrc/klstm_rnnt_band_dev.h", "../include/klstm.h", "../include/klstm_nlm.h", "../include/klstm_dropout.h", "../include/klstm_cnn.h", "../include/klstm_rnnt.h"]
 LIB = os.path.join(HERE, "libklstm.so")
@@ -24,7 +24,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # joint and from run to run, and which neighbouring f32 operations the compiler pairs into v_pk_* forms changes with the code around
 # them.  The other sources keep their flags and their code objects.
 _NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"csrc/klstm_rnnt.hip": _NO_PK, "csrc/klstm_rnnt_decode.hip": _NO_PK, "csrc/klstm_rnnt_beam.hip": _NO_PK, "csrc/klstm_rnnt_band.hip": _NO_PK, "csrc/klstm_rnnt_band16.hip": _NO_PK, "csrc/klstm_rnnt_simple.hip": _NO_PK}
+EXTRA_FLAGS = {"csrc/klstm_rnnt.hip": _NO_PK, "csrc/klstm_rnnt_decode.hip": _NO_PK, "csrc/klstm_rnnt_beam.hip": _NO_PK, "csrc/klstm_rnnt_band.hip": _NO_PK, "csrc/klstm_rnnt_band16.hip": _NO_PK, "csrc/klstm_rnnt_simple.hip": _NO_PK, "csrc/klstm_rnnt_align.hip": _NO_PK}
 
 
 def _hash(files):

@@ -475,6 +475,11 @@ __global__ __launch_bounds__(256) void k_rnnt_pack(const int *labels, const int 
 
 hipError_t rnnt_launch_prep(const RnntArgs &a, hipStream_t st) { return launch(k_rnnt_prep, dim3(1), dim3(64), 0, st, LaunchProbe(), a); }
 
+hipError_t rnnt_launch_joint_fwd(const RnntArgs &a, hipStream_t st) {
+  return launch(k_rnnt_joint_fwd, dim3((a.T + RT - 1) / RT, (a.U1 + RU - 1) / RU, a.S), dim3(256),
+                ((size_t)(RT + RU) * (a.J + 2) + VP * WPS) * sizeof(float), st, LaunchProbe(), a);
+}
+
 hipError_t rnnt_launch_lattice(const RnntArgs &a, hipStream_t st) {
   const size_t N = (size_t)a.S * a.T * a.U1;
   const hipError_t e = launch(k_rnnt_lattice, dim3(a.S, 2), dim3((a.U1 + 63) / 64 * 64), 0, st, LaunchProbe(), a);
@@ -484,7 +489,7 @@ hipError_t rnnt_launch_lattice(const RnntArgs &a, hipStream_t st) {
 
 static bool al4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
-static const char *rnnt_limits(int T, int S, int Umax, int J, int V) {
+const char *rnnt_limits(int T, int S, int Umax, int J, int V) {
   if (S < 1 || S > 32) return "1 <= S <= 32";
   if (T < 1) return "1 <= T";
   if (Umax < 0 || Umax > 1023) return "0 <= Umax <= 1023";
@@ -552,7 +557,7 @@ klstm_status krnnt_eval(const float *enc, int enc_stride, const float *pred, int
   hipStream_t st = (hipStream_t)hip_stream;
   const int Jp = J + 2, U1 = a.U1;
   HIPCHK(rnnt_launch_prep(a, st));
-  HIPCHK(launch(k_rnnt_joint_fwd, dim3(a.ntb, (U1 + RU - 1) / RU, S), dim3(256), ((size_t)(RT + RU) * Jp + VP * WPS) * sizeof(float), st, LaunchProbe(), a));
+  HIPCHK(rnnt_launch_joint_fwd(a, st));
   HIPCHK(rnnt_launch_lattice(a, st));
   if (!ngrad) return KLSTM_OK;
   const size_t shm = ((size_t)(RT + BU) * Jp + VP * WPS + 64 * GS) * sizeof(float);

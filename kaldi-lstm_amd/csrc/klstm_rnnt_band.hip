@@ -656,6 +656,10 @@ klstm_status band_eval_args(const char *name, const float *enc, int enc_stride, 
 
 hipError_t band_launch_prep(const BandArgs &a, hipStream_t st) { return launch(k_rband_prep, dim3(a.S), dim3(256), 0, st, LaunchProbe(), a); }
 
+hipError_t band_launch_joint_fwd(const BandArgs &a, hipStream_t st) {
+  return launch(k_rband_joint_fwd, dim3(a.ntb, (a.R + BR - 1) / BR, a.S), dim3(256), 0, st, LaunchProbe(), a);
+}
+
 hipError_t band_launch_lattice(const BandArgs &a, hipStream_t st) {
   const size_t N = (size_t)a.S * a.T * a.R;
   const hipError_t e = launch(k_rband_lattice, dim3(a.S, 2), dim3(64), 0, st, LaunchProbe(), a);
@@ -707,7 +711,7 @@ klstm_status krnnt_band_eval(const float *enc, int enc_stride, const float *pred
   if (bad != KLSTM_OK) return bad;
   hipStream_t st = (hipStream_t)hip_stream;
   HIPCHK(band_launch_prep(a, st));
-  HIPCHK(launch(k_rband_joint_fwd, dim3(a.ntb, (R + BR - 1) / BR, S), dim3(256), 0, st, LaunchProbe(), a));
+  HIPCHK(band_launch_joint_fwd(a, st));
   HIPCHK(band_launch_lattice(a, st));
   if (!ngrad) return KLSTM_OK;
   const size_t shm = ((size_t)RT * (J + 2) + VP * WPS + 64 * WPS + 64 * BGS + 64) * sizeof(float);

@@ -368,6 +368,21 @@ static size_t band16_extra(int J, int V, bool grads, size_t *wbt_off) {
   return c.bytes();
 }
 
+size_t band16_wb_bytes(int J, int V) {
+  size_t off = 0;
+  band16_extra(J, V, false, &off);
+  return off;
+}
+
+hipError_t band16_launch_joint_fwd(const BandArgs &a, void *wb, hipStream_t st) {
+  Band16Args p;
+  p.a = a; p.Wb = static_cast<const bf16_t *>(wb); p.WbT = nullptr; p.Jp = (int)up32(a.J); p.Vp = (int)up32(a.V);
+  const size_t ncv = (size_t)a.V * p.Jp, gcv = (ncv + 255) / 256;
+  const hipError_t e = launch(k_rband16_convert, dim3((unsigned)(gcv < 4096 ? gcv : 4096)), dim3(256), 0, st, LaunchProbe(), a.W, a.V, a.J, p.Jp, p.Vp,
+                              static_cast<bf16_t *>(wb), (bf16_t *)nullptr);
+  return e != hipSuccess ? e : launch(k_rband16_joint_fwd, dim3(a.ntb, (a.R + BR - 1) / BR, a.S), dim3(256), 0, st, LaunchProbe(), p);
+}
+
 }  // namespace klstm
 
 using namespace klstm;

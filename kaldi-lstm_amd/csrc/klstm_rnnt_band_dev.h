@@ -41,6 +41,11 @@ klstm_status band_eval_args(const char *name, const float *enc, int enc_stride, 
                             float *b_grad, float *utt_loss_dev, double *totals_dev, void *workspace, size_t workspace_bytes, size_t extra, BandArgs *a,
                             int *ngrad, size_t *band_bytes);
 hipError_t band_launch_prep(const BandArgs &a, hipStream_t st);                // k_rband_prep: ws.meta
+hipError_t band_launch_joint_fwd(const BandArgs &a, hipStream_t st);           // k_rband_joint_fwd: lpb / lpy / lse of the band's nodes
+// The bf16 joint's forward (klstm_rnnt_band16.hip): Wb [V][Jp] = bf(W) into wb (band16_wb_bytes(J, V) bytes, 256-byte aligned), then
+// k_rband16_joint_fwd on it: the same three planes.
+size_t band16_wb_bytes(int J, int V);
+hipError_t band16_launch_joint_fwd(const BandArgs &a, void *wb, hipStream_t st);
 hipError_t band_launch_lattice(const BandArgs &a, hipStream_t st);             // k_rband_lattice + k_rband_weights, once lpb / lpy / lse are written
 hipError_t band_launch_finish(const BandArgs &a, hipStream_t st);              // k_rband_finish, behind the backward joint
 

@@ -42,7 +42,12 @@ RnntWs rnnt_carve(void *base, int T, int S, int U1, int J, int V, bool grads, si
 // are written, k_rnnt_lattice + k_rnnt_weights (alpha, beta, the loss, w_b, w_y, the totals).  They read T, S, U1, V, blank, lens,
 // labels, loff, utt_loss, totals and ws of a.
 hipError_t rnnt_launch_prep(const RnntArgs &a, hipStream_t st);
+// k_rnnt_joint_fwd: lpb, lpy, lse of every node under t < T_s, u <= U_s from enc, pred, W, b (krnnt_align runs it on a workspace that
+// holds nothing but meta and these three planes)
+hipError_t rnnt_launch_joint_fwd(const RnntArgs &a, hipStream_t st);
 hipError_t rnnt_launch_lattice(const RnntArgs &a, hipStream_t st);
+
+const char *rnnt_limits(int T, int S, int Umax, int J, int V);                  // the limit of krnnt_eval that is broken, or null
 
 // The end of a band builder (krnnt_band_from_frames, krnnt_band_from_occupation; 256 threads, one workgroup per stream).  cand(t) is
 // u0(t) before the closure, with cand(T_s - 1) = hi.  From the end u0(t) = max(cand(t), u0(t+1) - R1): the suffix maximum of

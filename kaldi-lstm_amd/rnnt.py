@@ -156,6 +156,56 @@ def rnnt_band_eval(enc, pred, W, b, lens, labels, band_lo, R, blank=0, want_grad
     return res
 
 
+def rnnt_align_workspace_bytes(T, S, Umax, J=16, V=2, R=None, precision="f32"):
+    """bytes of workspace krnnt_align needs (R None: the full lattice; J and V do not enter it) or krnnt_band_align (width R; J and V
+    enter with precision "bf16" only); include/klstm_rnnt.h, FORCED ALIGNMENT, gives both formulas"""
+    if R is None:
+        return _workspace_bytes("krnnt_align_workspace_bytes", T, S, Umax)
+    return _workspace_bytes("krnnt_band_align_workspace_bytes", T, S, R, J, V, _band_precision(precision))
+
+
+def rnnt_align(enc, pred, W, b, lens, labels, blank=0, band_lo=None, R=None, precision="f32", want_logp=False, stream=None):
+    """The best alignment of the labels (klstm_rnnt.h, FORCED ALIGNMENT): enc, pred, W, b, lens, labels as in rnnt_eval.  band_lo None:
+    the full lattice (krnnt_align); band_lo [S, T] int32 CUDA with its width R: inside that band (krnnt_band_align), precision "bf16":
+    with the bf16 joint's log-probabilities.  Returns a dict: frames, int32 CUDA, one frame per label packed like the labels (what
+    rnnt_band_from_frames takes as frames=); score [S] float32, the log-probability of the best path (0: idle or rejected); logp,
+    the label steps' log-probabilities packed like frames (None without want_logp).  The entries of a rejected stream stay as
+    allocated (zeros).  Nothing synchronises."""
+    import torch
+    bf16 = _band_precision(precision)
+    if band_lo is None and bf16:
+        raise ValueError("precision 'bf16': only the band-pruned joint has a bf16 variant; give band_lo and R")
+    lib, dev = load_library(), enc.device
+    _rows(enc)
+    J = enc.shape[1]
+    _rows(pred, J)
+    assert W.is_cuda and W.dtype == torch.float32 and W.dim() == 2 and W.is_contiguous() and W.shape[1] == J
+    V = W.shape[0]
+    assert b.is_cuda and b.dtype == torch.float32 and b.is_contiguous() and b.numel() == V
+    lens_dev = _lens_dev(lens, dev)
+    S = lens_dev.numel()
+    assert S > 0 and enc.shape[0] % S == 0 and pred.shape[0] % S == 0, "rows must be T * len(lens) and (Umax + 1) * len(lens)"
+    T, Umax = enc.shape[0] // S, pred.shape[0] // S - 1
+    lab_dev, off_dev, _ = _packed(labels, S, dev)
+    frames = torch.zeros(lab_dev.numel(), dtype=torch.int32, device=dev)
+    logp = torch.zeros(lab_dev.numel(), device=dev) if want_logp else None
+    score = torch.empty(S, device=dev)
+    head = (enc.data_ptr(), enc.stride(0), pred.data_ptr(), pred.stride(0), W.data_ptr(), b.data_ptr(), T, S, Umax, J, V, lens_dev.data_ptr(),
+            lab_dev.data_ptr(), off_dev.data_ptr(), int(blank))
+    if band_lo is None:
+        nbytes = rnnt_align_workspace_bytes(T, S, Umax)
+        ws = _workspace("rnnt_align", (T, S, Umax), nbytes, dev)
+        _chk(lib.krnnt_align(*head, frames.data_ptr(), _ptr(logp), score.data_ptr(), ws.data_ptr(), ctypes.c_size_t(nbytes), _sp(stream)))
+    else:
+        R = int(R)
+        assert band_lo.is_cuda and band_lo.dtype == torch.int32 and band_lo.is_contiguous() and tuple(band_lo.shape) == (S, T)
+        nbytes = rnnt_align_workspace_bytes(T, S, Umax, J, V, R, precision)
+        ws = _workspace("rnnt_band_align", (T, S, R, J, V, precision), nbytes, dev)
+        _chk(lib.krnnt_band_align(*head, R, band_lo.data_ptr(), int(bf16), frames.data_ptr(), _ptr(logp), score.data_ptr(), ws.data_ptr(),
+                                  ctypes.c_size_t(nbytes), _sp(stream)))
+    return dict(frames=frames, score=score, logp=logp)
+
+
 def rnnt_simple_workspace_bytes(T, S, Umax, V):
     """bytes of workspace krnnt_simple_eval needs (include/klstm_rnnt.h gives the formula: no term in T (Umax+1) V)"""
     return _workspace_bytes("krnnt_simple_workspace_bytes", T, S, Umax, V)
